@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py - images/sec of the Yolo-FastestV2 hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: one rank per GPU over RCCL.  Under torch.distributed.run the ranks read RANK / LOCAL_RANK / WORLD_SIZE / MASTER_*;
      called PLAIN with --gpus N > 1, bench.py launches itself: it re-executes under `python -m torch.distributed.run --nnodes=1
      --nproc-per-node N --master-addr 127.0.0.1 --master-port <free port>` and rank 0 prints the one JSON line.)
@@ -17,12 +17,17 @@ maximum of 300 detections, i.e. NMS runs its WORST case inside `value`.
 Consecutive steps are independent batches: they rotate over three handles
 (own workspaces) on three HIP streams, so that one step's launches fill the
 under-filled tails of its neighbours' (all K steps complete inside the timed
-region); `single_stream_img_s` is the same K steps on one handle and one stream.
+region); `single_stream_img_s` (--full) is the same K steps on one handle and one stream.
 Order of a run: set-up (handles, one call per handle) -> SPIN-UP: the device is held under load for --spinup-seconds (2 s)
 of the same steps, because a fresh process runs its first steps 8-10 % slower until the device has left its idle power state
-(reported as `spinup`, not as warm-up) -> exactly W warm-up steps -> --blocks (5) back-to-back timed blocks of EXACTLY K steps,
-each bracketed by barrier + device synchronize.  `value` / `ms_per_step` are the MEDIAN block; every block's rate and the
-min / max ride along (`blocks`), so that a clock ramp or a noisy box is visible instead of guessed.  `box` records what the
+(reported as `spinup` by --full, not as warm-up) -> exactly W warm-up steps -> ONE timed block of EXACTLY K steps, bracketed by
+barrier + device synchronize: `value` / `ms_per_step` -> with --dump-outputs DIR, the last timed step's detections (what a
+caller of Engine.detect receives) as DIR/*.npy -> the JSON line.  The inputs are seeded, so the same arguments give the same
+outputs from run to run.  A plain run stops there and prints only the headline fields.
+
+--full measures everything else, after the same headline: --blocks (15) back-to-back timed blocks of EXACTLY K steps in all,
+the headline's first; every block's rate, the min / max / median ride along (`blocks`), so that a clock ramp or a noisy box
+is visible instead of guessed.  `box` records what the
 run ran at: the effective shader clock measured by the shader itself (s_memtime against the constant reference clock) under
 an all-CU vector load before and after the timed blocks and - by sleeping probe waves on a side stream - WHILE the timed kind
 of step loop and the per-kernel profile run, plus whatever rocm-smi / sysfs give on the box (performance level, power cap,
@@ -32,8 +37,10 @@ the shipped JPEGs, thresholds 0.3/0.4 and 0.01/0.4) is timed as well and reporte
 in `coco_e2e` (extra fields, never `value`).
 
 Prints ONE JSON line on rank 0 (see README / DESIGN.md for the field meanings):
-  value      whole-job images/s (all ranks' images / max-over-ranks time of the median block), consecutive steps (= batches
+  value      whole-job images/s (all ranks' images / max-over-ranks time of the K timed steps), consecutive steps (= batches
              of 256) pipelined over three handles / HIP streams: up to three batches are in flight at any time
+  ms_per_step  milliseconds per timed step (the same block)
+--full adds:
   single_stream_img_s   the same steps strictly one batch at a time on one handle and one stream
   fp32_mfma_plan   the same two figures with every contraction on the fp32 matrix instructions (YFV2_BF6=0) instead of fp16x3
   roofline   the kernel that owns the most forward time (sum over its launches, the
@@ -128,8 +135,11 @@ def parse():
     ap.add_argument("--batch", type=int, default=256, help="images per GPU (BASELINE.json: 256)")
     ap.add_argument("--conf", type=float, default=0.3)
     ap.add_argument("--iou", type=float, default=0.4)
+    ap.add_argument("--full", action="store_true", help="after the headline, measure everything else: timed blocks, clocks, one stream, forward only, "
+                                                        "roofline, fp32 plan, COCO, CPU baseline, training (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's detections, counts and survivor indices as DIR/<name>.npy")
     ap.add_argument("--profile-iters", type=int, default=5)
-    ap.add_argument("--blocks", type=int, default=15, help="back-to-back timed blocks of --steps steps each; value = the median block")
+    ap.add_argument("--blocks", type=int, default=15, help="--full: back-to-back timed blocks of --steps steps each, the headline's first (`blocks`)")
     ap.add_argument("--inputs", type=int, default=3, help="distinct resident input batches the steps rotate over (3 x 381 MB exceeds the 256 MB Infinity Cache: "
                                                           "the streaming front end provably reads HBM)")
     ap.add_argument("--spinup-seconds", type=float, default=2.0, help="set-up: hold the device under load this long before the warm-up (a fresh process runs its first steps 8-10 %% slower until the device has left its idle power state)")
@@ -181,6 +191,30 @@ def _cpu_instance(args):
         el = time.perf_counter() - t0
         if el >= seconds:
             return n, el
+
+
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, dets, idx, cnt):
+    """--dump-outputs: what Engine.detect hands its caller, as .npy files - detections (B,300,6) float32, survivor_indices (B,300)
+    and counts (B,) float64.  Only the first counts[b] rows of an image are results: the padding is written as 0 (indices -1), so
+    that two builds compare file for file.  A batch too large for DUMP_MAX_BYTES keeps a fixed, seeded sample of its images
+    (image_index.npy says which)."""
+    import numpy as np
+    n = cnt.cpu().numpy().astype(np.int64)
+    d, i = dets.cpu().numpy(), idx.cpu().numpy()
+    valid = np.arange(d.shape[1])[None, :] < n[:, None]
+    out = {"detections": np.where(valid[..., None], d, 0.0).astype(np.float32), "survivor_indices": np.where(valid, i, -1).astype(np.float64),
+           "counts": n.astype(np.float64)}
+    per_image = sum(v[0].nbytes for v in out.values())
+    if per_image * len(n) > DUMP_MAX_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(len(n), DUMP_MAX_BYTES // per_image - 1, replace=False))
+        out = {k: v[keep] for k, v in out.items()}
+        out["image_index"] = keep.astype(np.float64)
+    os.makedirs(path, exist_ok=True)
+    for k, v in out.items():
+        np.save(os.path.join(path, k + ".npy"), v)
 
 
 def timed(fn, steps, sync, barrier, finish=None):
@@ -431,6 +465,7 @@ def main():
     sets = pipe.buffers
     recv = [torch.empty(world * a.batch * (300 * 7 + 1), dtype=torch.float32, device=dev) for _ in sets] if use_dist else []
     works = [None] * len(sets)
+    last = [None]        # (dets, idx, cnt) of the latest step: --dump-outputs
 
     def step():
         with pipe.slot() as (j, e, bufs):      # next handle in rotation, its stream current
@@ -438,6 +473,7 @@ def main():
                 works[j].wait_host()      # issued len(sets) steps ago; the gathered result stays packed in recv[j] (sharded.rank_views)
                 works[j] = None
             d, i, c = e.detect(next_x(), a.conf, a.iou, out=bufs)     # (looks at the range guard first: Engine.detect check=True, a host memory read)
+            last[0] = (d, i, c)
             if use_dist:
                 works[j] = yfv2.gather_detections(d, i, c, force=True, async_op=True, out=recv[j])
 
@@ -477,7 +513,8 @@ def main():
     if getattr(props, "pci_bus_id", None) is not None:
         pci = "%04x:%02x:%02x" % (int(getattr(props, "pci_domain_id", 0)), int(props.pci_bus_id), int(getattr(props, "pci_device_id", 0)))
         box["pci"] = pci
-    if rank == 0:
+    telemetry = a.full and rank == 0
+    if telemetry:
         box.update(smi_snapshot(local, pci))
         box["sclk_cold"] = clock_busy()          # first look, before the device was held under load
     # SPIN-UP (set-up, not a step, not the warm-up): hold the device under load for --spinup-seconds of the same steps on one
@@ -490,28 +527,54 @@ def main():
             with pipe.slot() as (j, e, bufs):
                 e.detect(next_x(), a.conf, a.iou, out=bufs)
         n_spin += 20
-        if rank == 0 and "sysfs_under_pipelined_load" not in box and time.perf_counter() - t_spin > 0.6 * a.spinup_seconds:
+        if telemetry and "sysfs_under_pipelined_load" not in box and time.perf_counter() - t_spin > 0.6 * a.spinup_seconds:
             box["sysfs_under_pipelined_load"] = sysfs_power_clock(pci)     # the 20 steps just queued are still running
         sync()
     spin_s = time.perf_counter() - t_spin
+    nx[0] = 0      # the warm-up and timed steps see the same inputs in every run, however many spin-up steps there were
     # (no probe between the spin-up and the timed blocks: the all-CU FMA kernel drains the pipeline, and the first timed block then
     # pays for refilling it - round 5's first form measured 368 k for block 1 against 385-392 k for blocks 2-5)
-    # exactly W warm-up steps (with the collective), then --blocks timed blocks of exactly K steps
+    # exactly W warm-up steps (with the collective), then the headline: ONE timed block of exactly K steps
     for _ in range(a.warmup):
         step()
     finish()
     sync()
-    dts = [timed(step, a.steps, sync, barrier, finish) for _ in range(max(1, a.blocks))]
-    t = torch.tensor(dts, device=dev, dtype=torch.float64)
-    if use_dist:
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)       # per block: the slowest rank
-    chrono = [float(v) for v in t.cpu()]
-    dts = sorted(chrono)
-    dt = dts[len(dts) // 2] if len(dts) % 2 else 0.5 * (dts[len(dts) // 2 - 1] + dts[len(dts) // 2])
+
+    def slowest_rank(dts):
+        if not dts:
+            return []
+        t = torch.tensor(dts, device=dev, dtype=torch.float64)
+        if use_dist:
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)       # per block: the slowest rank
+        return [float(v) for v in t.cpu()]
+    dt = slowest_rank([timed(step, a.steps, sync, barrier, finish)])[0]
     value = world * a.batch * a.steps / dt
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, *last[0])
+    out = {"metric": "images/sec at 352x352 bs=256 per GPU (forward+decode+NMS)", "value": round(value, 1), "unit": "images/s",
+           "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(1e3 * dt / a.steps, 4),
+           "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+           "dtype": "f32 tensors; contractions fp16x3 (two-term fp16 split operands on v_mfma_f32_16x16x32_f16, fp32 accumulate); depthwise/BN/ReLU/decode/NMS fp32 VALU"
+                    if FP16X3 else "f32 (fp32 MFMA contractions: YFV2_BF6=0 plan)",
+           "data": "synthetic"}
+
+    def close():
+        barrier()
+        if use_dist:
+            dist.destroy_process_group()
+    if not a.full:
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        return close()
+
+    # ---- --full: everything beyond the headline -------------------------------------------
+    # --blocks back-to-back blocks of exactly K steps in all, the headline's first
+    chrono = [dt] + slowest_rank([timed(step, a.steps, sync, barrier, finish) for _ in range(max(1, a.blocks) - 1)])
+    dts = sorted(chrono)
     blocks = {"n": len(dts), "steps_each": a.steps, "img_s": [round(world * a.batch * a.steps / v, 1) for v in chrono],
               "img_s_min": round(world * a.batch * a.steps / dts[-1], 1), "img_s_max": round(world * a.batch * a.steps / dts[0], 1),
-              "value_is": "median block", "img_s_order": "chronological"}
+              "img_s_median": round(world * a.batch * a.steps / (dts[len(dts) // 2] if len(dts) % 2 else 0.5 * (dts[len(dts) // 2 - 1] + dts[len(dts) // 2])), 1),
+              "value_is": "first block", "img_s_order": "chronological"}
     if rank == 0:
         box["sclk_after_timed"] = clock_busy()
         # the same kind of loop once more with the sleeping probe beside it: the clock the timed steps ran at
@@ -577,7 +640,6 @@ def main():
     del xu
 
     cnt_h = det_bufs[2].float().cpu()
-    out = None
     if rank == 0:
         # ---- roofline: per-launch hipEvent times grouped by kernel, the way a rocprofv3 --stats table groups them ----
         # Bytes are SURVEY.md 8(d)'s: a fused launch is charged its EXTERNAL reads + writes only (`yfv2_stage_info`'s third
@@ -795,14 +857,8 @@ def main():
                              "launch- and pass-count bound (about 900 kernels per iteration: DESIGN.md 4.3), not a throughput path"}
             del model, opt, xt
 
-        out = {
-            "metric": "images/sec at 352x352 bs=256 per GPU (forward+decode+NMS)", "value": round(value, 1), "unit": "images/s",
+        out.update({
             "single_stream_img_s": round(a.batch * a.steps / dt_s, 1),
-            "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(1e3 * dt / a.steps, 4),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32 tensors; contractions fp16x3 (two-term fp16 split operands on v_mfma_f32_16x16x32_f16, fp32 accumulate); depthwise/BN/ReLU/decode/NMS fp32 VALU"
-                     if FP16X3 else "f32 (fp32 MFMA contractions: YFV2_BF6=0 plan)",
-            "data": "synthetic",
             "arithmetic": "fp32 tensors, fp32 accumulation everywhere.  Depthwise convs, BatchNorm, ReLU, max-pool, decode: fp32 VALU.  Every "
                           "convolution with a channel contraction - stem (fp32 input), stage 2, stage3.0, the stage-3 chain, stage4.0, the stage-4 chain, "
                           "the FPN reduces, the towers and the output convs - is fp16x3: both operands split into two fp16 terms whose sum "
@@ -839,11 +895,9 @@ def main():
             "detections_per_image": {"mean": round(float(cnt_h.mean()), 1), "max": int(cnt_h.max())},
             "forward_launches": len(stages), "forward_sum_of_launch_ms": round(tot_ms, 4), "kernel_table": kernel_table,
             "coco_e2e": coco, "train_iteration": train,
-        }
+        })
         print(json.dumps(out), flush=True)
-    barrier()
-    if use_dist:
-        dist.destroy_process_group()
+    close()
 
 
 if __name__ == "__main__":

@@ -725,6 +725,39 @@ def test_bench_without_a_gpu_fails_loudly(tmp_path):
     assert r.returncode != 0 and "needs an MI355X" in r.stderr
 
 
+def test_bench_dump_outputs_writes_results_only_and_bounds_its_size(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the valid rows of the padded detect buffers as float32 / float64 .npy files, the padding as 0 / -1 whatever
+    the buffers held; a batch beyond the size bound keeps a fixed, seeded sample of its images and says which."""
+    sys.path.insert(0, REPO)
+    import bench
+    B = 8
+    dets = torch.full((B, 300, 6), float("nan"))
+    idx = torch.full((B, 300), 12345, dtype=torch.int32)
+    cnt = torch.tensor([0, 3, 300, 1, 2, 0, 5, 7], dtype=torch.int32)
+    for b in range(B):
+        dets[b, :int(cnt[b])] = torch.arange(int(cnt[b]) * 6, dtype=torch.float32).reshape(-1, 6) + b
+        idx[b, :int(cnt[b])] = torch.arange(int(cnt[b]), dtype=torch.int32) * 3
+    bench.dump_outputs(str(tmp_path / "all"), dets, idx, cnt)
+    got = {k: np.load(str(tmp_path / "all" / (k + ".npy"))) for k in ("detections", "survivor_indices", "counts")}
+    assert sorted(os.listdir(str(tmp_path / "all"))) == ["counts.npy", "detections.npy", "survivor_indices.npy"]
+    assert got["detections"].dtype == np.float32 and got["survivor_indices"].dtype == np.float64 and got["counts"].dtype == np.float64
+    assert got["counts"].tolist() == cnt.tolist()
+    for b in range(B):
+        n = int(cnt[b])
+        assert np.array_equal(got["detections"][b, :n], dets[b, :n].numpy()) and (got["detections"][b, n:] == 0).all()
+        assert np.array_equal(got["survivor_indices"][b, :n], 3.0 * np.arange(n)) and (got["survivor_indices"][b, n:] == -1).all()
+    per_image = 300 * 6 * 4 + 300 * 8 + 8
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4 * per_image)
+    for run in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / run), dets, idx, cnt)
+    s1 = {f: np.load(str(tmp_path / "s1" / f)) for f in os.listdir(str(tmp_path / "s1"))}
+    assert sum(v.nbytes for v in s1.values()) <= 4 * per_image
+    keep = s1["image_index.npy"].astype(np.int64)
+    assert len(keep) == 3 and (np.diff(keep) > 0).all() and np.array_equal(s1["counts.npy"], cnt.numpy()[keep].astype(np.float64))
+    assert np.array_equal(s1["detections.npy"], got["detections"][keep])
+    assert all(np.array_equal(v, np.load(str(tmp_path / "s2" / f))) for f, v in s1.items())       # the same sample every run
+
+
 def test_bench_reads_power_and_clock_of_its_own_device_from_sysfs(tmp_path):
     """bench.py's `box.sysfs_under_*_load`: the GPU boxes expose every GPU of their node (and render nodes without sensors);
     the reading must be the one of the device the run uses (matched by PCI bus id through the card's resolved path), in watts and

@@ -427,7 +427,7 @@ def test_bench_under_torchrun_single_rank_uses_rccl(dev):
     import sys
     from conftest import REPO
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
-           "--master-port", "29617", os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+           "--master-port", "29617", os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--full",
            "--batch", "32", "--no-cpu-baseline", "--profile-iters", "1", "--no-extras", "--spinup-seconds", "0.3", "--blocks", "3"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -445,6 +445,37 @@ def test_bench_under_torchrun_single_rank_uses_rccl(dev):
         assert 90.0 < c["ref_clock_mhz"] < 110.0
     assert j["box"]["sclk_after_timed"]["xcds_seen"] == 8
     assert all(r["kcycles"] > 0 for r in j["kernel_table"])
+
+
+def test_bench_plain_run_times_the_headline_and_dumps_its_last_step(yfv2, dev, tmp_path):
+    """A plain bench run prints the headline only, timed over exactly --steps steps, and --dump-outputs writes what the last timed
+    step's Engine.detect returned: here recomputed in this process from the same seeded inputs, bit for bit."""
+    import json
+    import subprocess
+    import sys
+    import bench
+    from conftest import REPO
+    B, steps, warmup = 32, 4, 1
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", str(steps), "--warmup", str(warmup), "--batch", str(B),
+                          "--spinup-seconds", "0.3", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    j = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
+    assert j["steps"] == steps and j["warmup"] == warmup and j["unit"] == "images/s" and j["higher_is_better"] is True and "fp16x3" in j["dtype"]
+    assert abs(j["value"] - B * 1e3 / j["ms_per_step"]) <= 1e-3 * j["value"]
+    assert "blocks" not in j and "kernel_table" not in j and "cpu_baseline" not in j      # --full only
+    got = {k: np.load(str(tmp_path / (k + ".npy"))) for k in ("detections", "survivor_indices", "counts")}
+    assert got["detections"].dtype == np.float32 and got["survivor_indices"].dtype == np.float64 and got["counts"].dtype == np.float64
+    eng = yfv2.Engine(dev, 352, 352, 80, 3, anchors=bench.ANCHORS, max_batch=B)
+    eng.load_state_dict(yfv2.random_state_dict(0))
+    g = torch.Generator(device=dev).manual_seed(1000)
+    xs = [torch.rand(B, 3, 352, 352, device=dev, generator=g) for _ in range(3)]
+    d, i, c = eng.detect(xs[(warmup + steps) % 3], 0.3, 0.4)       # step k of the warm-up + timed steps reads xs[k % 3]
+    assert np.array_equal(got["counts"], c.cpu().numpy().astype(np.float64)) and int(c.min()) > 0
+    rows, ids = yfv2.unpack_detections(d, i, c)
+    for b in range(B):
+        n = int(c[b])
+        assert np.array_equal(got["detections"][b, :n].view(np.uint32), rows[b].numpy().view(np.uint32)), b
+        assert np.array_equal(got["survivor_indices"][b, :n], ids[b].numpy()) and (got["survivor_indices"][b, n:] == -1).all(), b
 
 
 def _batch_from_reference_images(images_u8, n, seed):

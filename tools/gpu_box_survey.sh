@@ -2,7 +2,7 @@
 # What kind of box is this one?  One short bench run (no extras), its headline and its `box` telemetry in one line - called a few
 # times over a round, the lines show how much of the run-to-run spread is the machine (clock, power, cap) and how much is not.
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}; cd $ROOT; mkdir -p gpurun_out
-timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras 2>/dev/null | tail -1 | python -c "
+timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-extras 2>/dev/null | tail -1 | python -c "
 import json,sys,time; j=json.loads(sys.stdin.readline()); b=j['box']
 pl=list(b.get('sysfs_under_pipelined_load',{}).values()); sl=list(b.get('sysfs_under_single_stream_load',{}).values())
 cap=[v.get('power1_cap') for v in b.get('sysfs',{}).values()]

@@ -15,7 +15,7 @@ tail -25 $OUT/pytest_gpu.log
 cp gpurun_out/parity_counts.json $OUT/parity_counts.json 2>/dev/null
 if [ "$MODE" = "quick" ]; then
   echo "== bench (quick)"
-  timeout 600 python bench.py --steps 20 --warmup 5 > $OUT/bench.log 2>&1; echo "bench rc=$?"; tail -1 $OUT/bench.log | cut -c1-3000
+  timeout 600 python bench.py --full --steps 20 --warmup 5 > $OUT/bench.log 2>&1; echo "bench rc=$?"; tail -1 $OUT/bench.log | cut -c1-3000
   timeout 300 python tools/scale_probe.py 1 256 > $OUT/scale_probe.txt 2>&1; tail -22 $OUT/scale_probe.txt | cut -c1-150
   echo "== post: fused / two launches"
   timeout 120 python tools/nms_probe.py 2>&1 | grep -v amdgpu.ids; YFV2_POSTFUSE=0 timeout 120 python tools/nms_probe.py 2>&1 | grep -v amdgpu.ids
@@ -25,10 +25,10 @@ echo "== smoke"
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; echo "smoke rc=$?"; tail -2 $OUT/smoke.log
 cd /tmp && export TMPDIR=/tmp
 echo "== rocprofv3 kernel stats"   # --pipeline 1: one stream, so that a launch's duration is its own (overlapped launches share the machine)
-timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o $TAG -- python $ROOT/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-extras --pipeline 1 --blocks 2 > $OUT/rocprof.log 2>&1; echo "rocprof rc=$?"
+timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o $TAG -- python $ROOT/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-extras --pipeline 1 --blocks 2 > $OUT/rocprof.log 2>&1; echo "rocprof rc=$?"
 find $OUT/prof -name "*kernel_stats*" | head -1 | while read f; do cp "$f" $OUT/kernel_stats.csv; head -30 "$f" | cut -c1-150; done
 echo "== pmc SQ pass"
-timeout 600 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $OUT/pmc1 -o $TAG -- python $ROOT/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras --profile-iters 1 --pipeline 1 --blocks 1 --spinup-seconds 0.3 > $OUT/pmc1.log 2>&1; echo "pmc1 rc=$?"
+timeout 600 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_VALU_MFMA_BUSY_CYCLES SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE GRBM_GUI_ACTIVE --kernel-trace --output-format csv -d $OUT/pmc1 -o $TAG -- python $ROOT/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extras --profile-iters 1 --pipeline 1 --blocks 1 --spinup-seconds 0.3 > $OUT/pmc1.log 2>&1; echo "pmc1 rc=$?"
 python $ROOT/tools/pmc_table.py $OUT/pmc1 $OUT/pmc.json > $OUT/pmc_sq_summary.txt; head -40 $OUT/pmc_sq_summary.txt | cut -c1-140
 echo "== traffic passes"
 timeout 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/fetch -o $TAG -- python $ROOT/tools/traffic_probe.py > $OUT/fetch.log 2>&1; echo "fetch rc=$?"
@@ -41,7 +41,7 @@ for k,v in j['kernels'].items():
 cd $ROOT
 cp $OUT/traffic.json profiles/${TAG}_traffic.json; cp $OUT/pmc.json profiles/${TAG}_pmc.json
 echo "== bench"
-timeout 900 python bench.py --steps 20 --warmup 5 > $OUT/bench.log 2>&1; echo "bench rc=$?"; tail -1 $OUT/bench.log | cut -c1-1500
+timeout 900 python bench.py --full --steps 20 --warmup 5 > $OUT/bench.log 2>&1; echo "bench rc=$?"; tail -1 $OUT/bench.log | cut -c1-1500
 echo "== scale probe"
 timeout 300 python tools/scale_probe.py 1 32 256 > $OUT/scale_probe.txt 2>&1; echo "probe rc=$?"; tail -30 $OUT/scale_probe.txt | cut -c1-150
 rm -rf $OUT/prof/*/*.db $OUT/fetch $OUT/write 2>/dev/null; du -sh $OUT

@@ -3,7 +3,7 @@
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}; cd $ROOT; OUT=$ROOT/gpurun_out/x1; mkdir -p $OUT
 for rep in 1 2; do
 for cfg in "" "YFV2_POSTFUSE=0"; do
-  env $cfg timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras > $OUT/bench_${rep}_${cfg:-default}.log 2>&1
+  env $cfg timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-extras > $OUT/bench_${rep}_${cfg:-default}.log 2>&1
   tail -1 $OUT/bench_${rep}_${cfg:-default}.log | python -c "
 import json,sys; j=json.loads(sys.stdin.readline()); b=j['box']
 print('[%s] value %.0f (blocks %s) single %.0f fwd_ms %.4f two_lanes %.0f | sclk busy %.0f pipelined %.0f single %.0f' % ('$cfg', j['value'], j['blocks']['img_s'], j['single_stream_img_s'], j['forward_only_ms'], j['single_call_two_lanes_img_s'], b['sclk_after_timed']['sclk_mhz_mean'], b['sclk_during_pipelined_steps']['sclk_mhz_mean'], b['sclk_during_single_stream_steps']['sclk_mhz_mean']))
