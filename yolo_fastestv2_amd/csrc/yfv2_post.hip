@@ -9,35 +9,52 @@
 // fp32 sigmoid as ATen's CPU kernel evaluates it: 1 / (1 + exp(-x)), true division
 __device__ __forceinline__ float sigmoid_f32(float x) { return __fdiv_rn(1.0f, __fadd_rn(1.0f, expf(-x))); }
 
+// Lane exchanges that move bits only (no arithmetic), for a wave whose lanes are all active.  Within a group of four
+// lanes: DPP quad_perm.  Across a wave: xor_lane64 below.
+template <int J>
+__device__ __forceinline__ int quad_xor(int v) {
+  static_assert(J == 1 || J == 2, "quad_perm exchange inside four lanes");
+  return __builtin_amdgcn_update_dpp(0, v, J == 1 ? 0xB1 : 0x4E, 0xF, 0xF, false);   // quad_perm [1,0,3,2] / [2,3,0,1]
+}
+template <int J> __device__ __forceinline__ float quad_xor(float v) { return __int_as_float(quad_xor<J>(__float_as_int(v))); }
+
 // One compact candidate row (cx, cy, w, h | obj, conf, class, 0) of image b, scale sc, grid cell `cell`, anchor `part`
 // (part 3 of a cell's 4-lane group only helps with the softmax).  Called by 4 consecutive lanes per cell with `cc` = the
-// cell clamped into the map, so that the group's shuffles stay convergent; the result is meaningful for ok && part < 3.
+// cell clamped into the map, so that the group's exchanges stay convergent; the result is meaningful for ok && part < 3.
 // Arithmetic = handel_preds (utils/utils.py:303-358) followed by the first two steps of non_max_suppression
 // (conf = max_j fl32(cls_j * obj) with the FIRST maximal j, :261,267), SURVEY.md App. B.
-// `skip_ct` (the fused NMS launch): when none of the cell's three anchors has obj > skip_ct - their logits arrive in objl,
-// fetched one pass ahead - the class slice is not read at all: non_max_suppression drops rows with obj <= conf_thres before it
-// looks at a class (utils.py:254), so conf / class of such rows are never used (they are written as 0).  With trained weights
-// that is nearly every cell: the launch's decode phase stops being a 164 MB read.
+// `skip_ct` (the fused NMS launch): when none of the cell's three anchors has obj > skip_ct - the lane's own anchor's logit
+// arrives in objl, fetched one pass ahead - the class slice is not read at all: non_max_suppression drops rows with
+// obj <= conf_thres before it looks at a class (utils.py:254), so conf / class of such rows are never used (they are written
+// as 0).  With trained weights that is nearly every cell: the launch's decode phase stops being a 164 MB read.
+// Each objectness sigmoid is evaluated once, by the lane of its anchor (lane 3 repeats anchor 0), and reaches the other
+// lanes of the cell by quad exchanges; only lanes 0-2 decode a box.
 // MAXPER >= ceil(classes / 4): 24 for up to 96 classes (every register count and schedule note below refers to that form), 64
 // for up to 255 (the general form: only reached through decode_kernel, 256 threads per workgroup).
 template <bool SKIP = false, int MAXPER = 24>
 __device__ __forceinline__ void yfv2_compact_row(const DecodeArgs& a, int b, int sc, int cc, int part, f32x4& r0, f32x4& r1,
-                                                 const float (&objl)[3] = {0.f, 0.f, 0.f}, float skip_ct = 0.f) {
+                                                 float objl = 0.f, float skip_ct = 0.f) {
   const int fh = a.fh[sc], fw = a.fw[sc], hw = fh * fw;
   const int nc = a.classes;
   const int per = (nc + 3) >> 2;
   const int c_lo = part * per, c_hi = min(nc, c_lo + per);
+  const int an = part < 3 ? part : 0;
   const float* cls = a.cls[sc] + (size_t)b * nc * hw;   // wave-uniform base: the per-lane part stays a 32-bit offset (24 addresses live)
+  const float so = sigmoid_f32(SKIP ? objl : a.obj[sc][((size_t)b * 3 + an) * hw + cc]);   // obj of this lane's anchor
   // The lane's class slice is loaded ONCE, all 24 loads in flight together (masked slots re-read a valid class), and the
   // three sweeps (max, sum, best product) run on registers; the second sweep leaves exp(v - max) in the logit's register,
   // the third divides it (this runs inside the 1024-thread NMS workgroup: 128 registers, and it is VALU-bound there -
   // four waves per SIMD - not bandwidth-bound: 24 fewer expf per lane and pass).  The first fused version re-read the
   // logits in every sweep in batches of four: 18 dependent round trips per pass instead of one.
   // Every value is computed by the same expression as in decode_kernel<false>, so the results are identical.
-  float best[3] = {0.f, 0.f, 0.f};
-  int bj[3] = {0, 0, 0};
-  bool need = true;   // (the four lanes of a cell agree: the shuffles below stay inside a converged group of four)
-  if constexpr (SKIP) need = sigmoid_f32(objl[0]) > skip_ct || sigmoid_f32(objl[1]) > skip_ct || sigmoid_f32(objl[2]) > skip_ct;
+  float conf = 0.f;
+  int cj = 0;
+  int need = 1;   // (the four lanes of a cell agree: the exchanges below stay inside a converged group of four)
+  if constexpr (SKIP) {
+    need = so > skip_ct ? 1 : 0;
+    need |= quad_xor<1>(need);
+    need |= quad_xor<2>(need);
+  }
   if (need) {
     float lv[MAXPER];
 #pragma unroll
@@ -49,8 +66,8 @@ __device__ __forceinline__ void yfv2_compact_row(const DecodeArgs& a, int b, int
 #pragma unroll
     for (int i = 0; i < MAXPER; ++i)
       if (c_lo + i < c_hi) m = fmaxf(m, lv[i]);
-    m = fmaxf(m, __shfl_xor(m, 1));
-    m = fmaxf(m, __shfl_xor(m, 2));
+    m = fmaxf(m, quad_xor<1>(m));
+    m = fmaxf(m, quad_xor<2>(m));
     float sum = 0.f;
 #pragma unroll
     for (int i = 0; i < MAXPER; ++i) {
@@ -59,15 +76,8 @@ __device__ __forceinline__ void yfv2_compact_row(const DecodeArgs& a, int b, int
       if (c_lo + i < c_hi) sum = __fadd_rn(sum, e);
       if ((i & 3) == 3) __builtin_amdgcn_sched_barrier(0); // four exps at a time (a free schedule interleaves all 24: spills)
     }
-    sum = __fadd_rn(sum, __shfl_xor(sum, 1));
-    sum = __fadd_rn(sum, __shfl_xor(sum, 2));
-    float obj3[3];
-#pragma unroll
-    for (int an = 0; an < 3; ++an) {
-      obj3[an] = sigmoid_f32(a.obj[sc][((size_t)b * 3 + an) * hw + cc]);
-      best[an] = -INFINITY;
-      bj[an] = 0x7fffffff;
-    }
+    sum = __fadd_rn(sum, quad_xor<1>(sum));
+    sum = __fadd_rn(sum, quad_xor<2>(sum));
     // conf = max_j fl32(fl32(e_j / sum) * obj) and its FIRST maximal j (utils.py:261,267).  The map e -> fl32(fl32(e / sum) * obj)
     // is non-decreasing (division by and multiplication with a non-negative constant, round to nearest), and the largest
     // exponential is exactly 1 (its logit IS the maximum), so conf = fl32(fl32(1 / sum) * obj) - one division per cell instead
@@ -85,54 +95,65 @@ __device__ __forceinline__ void yfv2_compact_row(const DecodeArgs& a, int b, int
       first = near_max ? min(first, c_lo + i) : first;
       cnt += near_max ? 1 : 0;
     }
-    cnt += __shfl_xor(cnt, 1);
-    cnt += __shfl_xor(cnt, 2);
-    first = min(first, __shfl_xor(first, 1));
-    first = min(first, __shfl_xor(first, 2));
-    bool exact = cnt != 1;
+    cnt += quad_xor<1>(cnt);
+    cnt += quad_xor<2>(cnt);
+    first = min(first, quad_xor<1>(first));
+    first = min(first, quad_xor<2>(first));
+    conf = __fmul_rn(ev1, so);
+    cj = first;
+    int exact = cnt != 1 || !(conf > 7.888609052210118e-31f) ? 1 : 0;   // 2^-100 (also catches a NaN logit: every comparison false, as in the exact sweep)
+    exact |= quad_xor<1>(exact);
+    exact |= quad_xor<2>(exact);
+    if (exact) {   // the four lanes of a cell agree on this (cnt and the three objectness values are cell-wide)
+      // obj of anchor `an` sits in lane part ^ (part ^ an) of the group: own value, or one / two quad exchanges away
+      const float o1 = quad_xor<1>(so), o2 = quad_xor<2>(so), o3 = quad_xor<1>(o2);
+      float obj3[3], best[3];
+      int bj[3];
 #pragma unroll
-    for (int an = 0; an < 3; ++an) {
-      best[an] = __fmul_rn(ev1, obj3[an]);
-      bj[an] = first;
-      exact |= !(best[an] > 7.888609052210118e-31f);   // 2^-100 (also catches a NaN logit: every comparison false, as in the exact sweep)
-    }
-    if (exact) {   // the four lanes of a cell agree on this (cnt and obj3 are cell-wide)
-#pragma unroll
-      for (int an = 0; an < 3; ++an) { best[an] = -INFINITY; bj[an] = 0x7fffffff; }
+      for (int k = 0; k < 3; ++k) {
+        const int d = k ^ part;
+        obj3[k] = d == 0 ? so : (d == 1 ? o1 : (d == 2 ? o2 : o3));
+        best[k] = -INFINITY;
+        bj[k] = 0x7fffffff;
+      }
 #pragma unroll
       for (int i = 0; i < MAXPER; ++i) {
         if (c_lo + i < c_hi) {
           const float ev = __fdiv_rn(lv[i], sum);   // the class probability, as decode_kernel<false> stores it
 #pragma unroll
-          for (int an = 0; an < 3; ++an) {
-            const float pj = __fmul_rn(ev, obj3[an]);
-            if (pj > best[an]) { best[an] = pj; bj[an] = c_lo + i; }  // strict: first maximal index of this slice
+          for (int k = 0; k < 3; ++k) {
+            const float pj = __fmul_rn(ev, obj3[k]);
+            if (pj > best[k]) { best[k] = pj; bj[k] = c_lo + i; }  // strict: first maximal index of this slice
           }
         }
         if ((i & 3) == 3) __builtin_amdgcn_sched_barrier(0);
       }
 #pragma unroll
-      for (int an = 0; an < 3; ++an)
-#pragma unroll
-        for (int msk = 1; msk < 4; msk <<= 1) {
-          const float ob_ = __shfl_xor(best[an], msk);
-          const int oi = __shfl_xor(bj[an], msk);
-          if (ob_ > best[an] || (ob_ == best[an] && oi < bj[an])) { best[an] = ob_; bj[an] = oi; }
-        }
+      for (int k = 0; k < 3; ++k) {
+        float ob_ = quad_xor<1>(best[k]);
+        int oi = quad_xor<1>(bj[k]);
+        if (ob_ > best[k] || (ob_ == best[k] && oi < bj[k])) { best[k] = ob_; bj[k] = oi; }
+        ob_ = quad_xor<2>(best[k]);
+        oi = quad_xor<2>(bj[k]);
+        if (ob_ > best[k] || (ob_ == best[k] && oi < bj[k])) { best[k] = ob_; bj[k] = oi; }
+      }
+      conf = part == 0 ? best[0] : (part == 1 ? best[1] : best[2]);
+      cj = part == 0 ? bj[0] : (part == 1 ? bj[1] : bj[2]);
     }
   }
-  const int an = part < 3 ? part : 0;
-  const int y = cc / fw, x = cc - y * fw;
-  const float* reg = a.reg[sc] + ((size_t)b * 12 + an * 4) * hw + cc;
-  const float t0 = reg[0], t1 = reg[(size_t)hw], t2 = reg[(size_t)2 * hw], t3 = reg[(size_t)3 * hw];
-  const float ob = a.obj[sc][((size_t)b * 3 + an) * hw + cc];
-  const float st = a.stride[sc];
-  const float qw = __fmul_rn(sigmoid_f32(t2), 2.0f), qh = __fmul_rn(sigmoid_f32(t3), 2.0f);
-  r0 = (f32x4){__fmul_rn(__fadd_rn(__fsub_rn(__fmul_rn(sigmoid_f32(t0), 2.0f), 0.5f), (float)x), st),
-               __fmul_rn(__fadd_rn(__fsub_rn(__fmul_rn(sigmoid_f32(t1), 2.0f), 0.5f), (float)y), st),
-               (float)((double)__fmul_rn(qw, qw) * a.anchors[(sc * 3 + an) * 2 + 0]),
-               (float)((double)__fmul_rn(qh, qh) * a.anchors[(sc * 3 + an) * 2 + 1])};
-  r1 = (f32x4){sigmoid_f32(ob), part == 0 ? best[0] : (part == 1 ? best[1] : best[2]), (float)(part == 0 ? bj[0] : (part == 1 ? bj[1] : bj[2])), 0.f};
+  r0 = (f32x4){0.f, 0.f, 0.f, 0.f};
+  if (part < 3) {
+    const int y = cc / fw, x = cc - y * fw;
+    const float* reg = a.reg[sc] + ((size_t)b * 12 + an * 4) * hw + cc;
+    const float t0 = reg[0], t1 = reg[(size_t)hw], t2 = reg[(size_t)2 * hw], t3 = reg[(size_t)3 * hw];
+    const float st = a.stride[sc];
+    const float qw = __fmul_rn(sigmoid_f32(t2), 2.0f), qh = __fmul_rn(sigmoid_f32(t3), 2.0f);
+    r0 = (f32x4){__fmul_rn(__fadd_rn(__fsub_rn(__fmul_rn(sigmoid_f32(t0), 2.0f), 0.5f), (float)x), st),
+                 __fmul_rn(__fadd_rn(__fsub_rn(__fmul_rn(sigmoid_f32(t1), 2.0f), 0.5f), (float)y), st),
+                 (float)((double)__fmul_rn(qw, qw) * a.anchors[(sc * 3 + an) * 2 + 0]),
+                 (float)((double)__fmul_rn(qh, qh) * a.anchors[(sc * 3 + an) * 2 + 1])};
+  }
+  r1 = (f32x4){so, conf, (float)cj, 0.f};
 }
 
 // ============================================================================
@@ -295,6 +316,98 @@ constexpr int NMS_NQ = NMS_THREADS / 64;  // thread groups per 64-candidate chun
 constexpr int NMS_CAP = 2048;      // >= rows (1815); power of two for the bitonic network (KPT = 2 keys per thread; KPT = 4: 4096 rows)
 constexpr int NMS_MAX_DET = 300;   // utils/utils.py:243 (== YFV2_MAX_DET)
 
+// Key of lane (lane ^ J), J < 64, for a wave whose lanes are all active: DPP inside a row of 16 lanes, v_permlane16_swap /
+// v_permlane32_swap across rows - VALU moves instead of two ds_bpermute round trips per 64-bit key.  Which of the two
+// candidate sources a lane takes (row_ror by 4 or 12; the first or second result of a swap) is decided by applying the
+// same move to the lane ids once: `sel` bit J says "the first one".
+__device__ __forceinline__ unsigned xor_sel_mask() {
+  const int l = (int)(threadIdx.x & 63);
+  const bool s4 = __builtin_amdgcn_update_dpp(0, l, 0x124, 0xF, 0xF, false) == (l ^ 4);   // row_ror:4
+  const auto p16 = __builtin_amdgcn_permlane16_swap(l, l, false, false);
+  const auto p32 = __builtin_amdgcn_permlane32_swap(l, l, false, false);
+  return (s4 ? 4u : 0u) | ((int)p16[0] == (l ^ 16) ? 16u : 0u) | ((int)p32[0] == (l ^ 32) ? 32u : 0u);
+}
+template <int J>
+__device__ __forceinline__ unsigned xor_lane32(unsigned v, unsigned sel) {
+  const int x = (int)v;
+  if constexpr (J == 1 || J == 2) return (unsigned)quad_xor<J>(x);
+  else if constexpr (J == 8) return (unsigned)__builtin_amdgcn_update_dpp(0, x, 0x128, 0xF, 0xF, false);   // row_ror:8 = xor 8
+  else if constexpr (J == 4) {
+    const int r4 = __builtin_amdgcn_update_dpp(0, x, 0x124, 0xF, 0xF, false), r12 = __builtin_amdgcn_update_dpp(0, x, 0x12C, 0xF, 0xF, false);
+    return (unsigned)((sel & 4u) ? r4 : r12);
+  } else if constexpr (J == 16) {
+    const auto p = __builtin_amdgcn_permlane16_swap(x, x, false, false);
+    return (unsigned)((sel & 16u) ? (int)p[0] : (int)p[1]);
+  } else {
+    static_assert(J == 32, "lane distance");
+    const auto p = __builtin_amdgcn_permlane32_swap(x, x, false, false);
+    return (unsigned)((sel & 32u) ? (int)p[0] : (int)p[1]);
+  }
+}
+template <int J>
+__device__ __forceinline__ unsigned long long xor_lane64(unsigned long long v, unsigned sel) {
+  return ((unsigned long long)xor_lane32<J>((unsigned)(v >> 32), sel) << 32) | xor_lane32<J>((unsigned)v, sel);
+}
+
+// Bitonic sort, descending, of key[0 .. np2) (np2 a power of two <= KPT * NMS_THREADS) with the keys in REGISTERS: thread t
+// owns indices t + 1024 r.  A compare-exchange distance below 64 is a lane exchange inside the wave (xor_lane64), a
+// distance >= 1024 pairs two keys of the same thread, and only distances 64..512 go through LDS, alternating the two
+// buffers so that one barrier per LDS step is enough (10 barriers for 1024 keys).  Keys are distinct except zero padding.
+// key2 must hold KPT * NMS_THREADS keys.  The result is back in key[0 .. np2), followed by a barrier.
+template <int KPT>
+__device__ __forceinline__ void bitonic_sort(unsigned long long* key, unsigned long long* key2, int np2, int tid) {
+  const unsigned sel = xor_sel_mask();
+  unsigned long long k[KPT];
+#pragma unroll
+  for (int r = 0; r < KPT; ++r) { const int i = tid + r * NMS_THREADS; k[r] = i < np2 ? key[i] : 0ull; }
+  auto cx = [](unsigned long long x, unsigned long long y, bool take_max) { return take_max == (x > y) ? x : y; };
+  int pb = 0;
+  for (int kk = 2; kk <= np2; kk <<= 1) {
+    int j = kk >> 1;
+    for (; j >= 64; j >>= 1) {
+      if (j >= NMS_THREADS) {
+        const int jr = j / NMS_THREADS;                           // partner key r ^ jr of the same thread
+#pragma unroll
+        for (int r = 0; r < KPT; ++r) {
+          if ((r & jr) == 0 && (r | jr) < KPT) {
+            const int r2 = r | jr;
+            const bool desc = ((tid + r * NMS_THREADS) & kk) == 0;  // (the same for both keys: jr * 1024 < kk)
+            const unsigned long long hi = k[r] > k[r2] ? k[r] : k[r2], lo = k[r] > k[r2] ? k[r2] : k[r];
+            k[r] = desc ? hi : lo; k[r2] = desc ? lo : hi;
+          }
+        }
+      } else {                                                    // partner in another wave: through LDS
+        unsigned long long* buf = pb ? key2 : key;
+#pragma unroll
+        for (int r = 0; r < KPT; ++r) buf[tid + r * NMS_THREADS] = k[r];
+        __syncthreads();
+        const bool low = (tid & j) == 0;
+#pragma unroll
+        for (int r = 0; r < KPT; ++r) {
+          const int i = tid + r * NMS_THREADS;
+          k[r] = cx(k[r], buf[i ^ j], low == ((i & kk) == 0));
+        }
+        pb ^= 1;
+      }
+    }
+    // distances 32 .. 1 (those below kk): partner = lane ^ j of the same wave
+#define YFV2_SORT_STEP(J)                                                                   \
+    if (J < kk) {                                                                           \
+      const bool low = (tid & J) == 0;                                                      \
+      _Pragma("unroll") for (int r = 0; r < KPT; ++r) {                                     \
+        const int i = tid + r * NMS_THREADS;                                                \
+        k[r] = cx(k[r], xor_lane64<J>(k[r], sel), low == ((i & kk) == 0));                 \
+      }                                                                                     \
+    }
+    YFV2_SORT_STEP(32) YFV2_SORT_STEP(16) YFV2_SORT_STEP(8) YFV2_SORT_STEP(4) YFV2_SORT_STEP(2) YFV2_SORT_STEP(1)
+#undef YFV2_SORT_STEP
+  }
+  __syncthreads();                                                // readers of either buffer are done
+#pragma unroll
+  for (int r = 0; r < KPT; ++r) { const int i = tid + r * NMS_THREADS; if (i < np2) key[i] = k[r]; }
+  __syncthreads();
+}
+
 // SRC 0: the (B, rows, 5 + classes) decoded tensor (yfv2_nms); 1: compact candidate rows in global memory (decode_kernel<true>);
 // 2: the logits themselves - the workgroup decodes its image into compact rows in LDS first (yfv2_detect: one launch for
 // handel_preds + non_max_suppression, the candidate rows never exist in HBM)
@@ -326,27 +439,28 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(NmsArgs a, DecodeArgs 
   const float ct = a.conf_thres;
   NMS_STAMP(0);
   if constexpr (SRC == 2) {
-    // decode this image: 4 lanes per grid cell (yfv2_compact_row), 256 cells per pass over the workgroup
-    constexpr int CPP = NMS_THREADS / 4;                 // cells per pass
+    // decode this image: 4 lanes per grid cell (yfv2_compact_row), 16 cells per wave.  The waves are numbered across both
+    // scales (scale 0's last wave is padded, so that a wave's scale and base pointers stay uniform): at 352 x 352, 31 + 8
+    // waves of work in three passes of 16, and the 9 waves past the end of the third pass skip it.
+    constexpr int WC = 16;                                // cells per wave
     const int hw0 = dec.fh[0] * dec.fw[0], hw1 = dec.fh[1] * dec.fw[1];
-    const int np0 = (hw0 + CPP - 1) / CPP, np = np0 + (hw1 + CPP - 1) / CPP;
-    const int part = tid & 3;
-    // the three objectness logits of this lane's cell, one pass ahead of their use (they decide whether the pass reads
-    // its class logits at all)
-    auto obj_of = [&](int ps, float (&o)[3]) {
-      const int sc = ps < np0 ? 0 : 1, hw = sc ? hw1 : hw0;
-      const int cell = (ps - (sc ? np0 : 0)) * CPP + (tid >> 2);
-      const int cc = cell < hw ? cell : hw - 1;
-#pragma unroll
-      for (int an = 0; an < 3; ++an) o[an] = ps < np ? dec.obj[sc][((size_t)b * 3 + an) * hw + cc] : 0.f;
+    const int nw0 = (hw0 + WC - 1) / WC, nw = nw0 + (hw1 + WC - 1) / WC;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int part = tid & 3, an = part < 3 ? part : 0;
+    // the objectness logit of this lane's anchor, one pass ahead of its use (it decides whether the pass reads its class
+    // logits at all)
+    auto obj_of = [&](int w) -> float {
+      if (w >= nw) return 0.f;
+      const int sc = w >= nw0 ? 1 : 0, hw = sc ? hw1 : hw0;
+      const int cell = (w - (sc ? nw0 : 0)) * WC + ((tid & 63) >> 2);
+      return dec.obj[sc][((size_t)b * 3 + an) * hw + (cell < hw ? cell : hw - 1)];
     };
-    float ocur[3], onxt[3];
-    obj_of(0, ocur);
-    for (int ps = 0; ps < np; ++ps) {
-      obj_of(ps + 1, onxt);
-      const int sc = ps < np0 ? 0 : 1, hw = sc ? hw1 : hw0;
+    float ocur = obj_of(wv);
+    for (int w = wv; w < nw; w += NMS_NQ) {               // (wave-uniform trip count)
+      const float onxt = obj_of(w + NMS_NQ);
+      const int sc = w >= nw0 ? 1 : 0, hw = sc ? hw1 : hw0;
       const int row_base = sc ? 3 * hw0 : 0;
-      const int cell = (ps - (sc ? np0 : 0)) * CPP + (tid >> 2);
+      const int cell = (w - (sc ? nw0 : 0)) * WC + ((tid & 63) >> 2);
       const bool ok = cell < hw;
       f32x4 r0, r1;
       yfv2_compact_row<true>(dec, b, sc, ok ? cell : hw - 1, part, r0, r1, ocur, ct);
@@ -355,8 +469,7 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(NmsArgs a, DecodeArgs 
         *reinterpret_cast<f32x4*>(d) = r0;
         *reinterpret_cast<f32x4*>(d + 4) = r1;
       }
-#pragma unroll
-      for (int an = 0; an < 3; ++an) ocur[an] = onxt[an];
+      ocur = onxt;
     }
     __syncthreads();
   }
@@ -441,92 +554,14 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(NmsArgs a, DecodeArgs 
     return;
   }
 
-  // ---- 2. sort (descending) on the next power of two >= n, zero keys pad the end.  Bitonic network with the keys in
-  // REGISTERS (thread t owns indices t and t + 1024): a compare-exchange distance below 64 is a lane shuffle inside the
-  // wave, distance 1024 is the thread's own second key, and only distances 64..512 go through LDS - 14 barriers for
-  // 2048 keys instead of 66, alternating two key buffers so that one barrier per LDS step is enough.
+  // ---- 2. sort (descending) on the next power of two >= n, zero keys pad the end (bitonic_sort below).  Up to 1024
+  // candidates - the bench's random weights give 850-960 - one key per thread.
   int np2 = 1;
   while (np2 < n) np2 <<= 1;
   for (int i = n + tid; i < np2; i += NMS_THREADS) key[i] = 0ull;
   __syncthreads();
-  if constexpr (KPT == 2) {
-    static_assert(NMS_CAP == 2 * NMS_THREADS, "two keys per thread");
-    const int i0 = tid, i1 = tid + NMS_THREADS;
-    unsigned long long k0 = i0 < np2 ? key[i0] : 0ull, k1 = i1 < np2 ? key[i1] : 0ull;
-    auto cx = [](unsigned long long x, unsigned long long y, bool take_max) { return take_max == (x > y) ? x : y; };   // x != y or both zero
-    int pb = 0;
-    for (int k = 2; k <= np2; k <<= 1) {
-      for (int j = k >> 1; j > 0; j >>= 1) {
-        const bool d0 = (i0 & k) == 0, d1 = (i1 & k) == 0;          // descending run?
-        if (j >= NMS_THREADS) {                                     // partner = this thread's other key (i0 < i1)
-          const unsigned long long hi = k0 > k1 ? k0 : k1, lo = k0 > k1 ? k1 : k0;
-          k0 = d0 ? hi : lo; k1 = d0 ? lo : hi;
-        } else if (j >= 64) {                                       // partner in another wave: through LDS
-          unsigned long long* buf = pb ? key2 : key;
-          buf[i0] = k0; buf[i1] = k1;
-          __syncthreads();
-          const unsigned long long y0 = buf[i0 ^ j], y1 = buf[i1 ^ j];
-          const bool low = (i0 & j) == 0;                           // same bit for i0 and i1 (j < 1024)
-          k0 = cx(k0, y0, low == d0); k1 = cx(k1, y1, low == d1);
-          pb ^= 1;
-        } else {                                                    // partner = lane ^ j of the same wave
-          const unsigned long long y0 = __shfl_xor(k0, j), y1 = __shfl_xor(k1, j);
-          const bool low = (i0 & j) == 0;
-          k0 = cx(k0, y0, low == d0); k1 = cx(k1, y1, low == d1);
-        }
-      }
-    }
-    __syncthreads();                                                // readers of either buffer are done
-    if (i0 < np2) key[i0] = k0;
-    if (i1 < np2) key[i1] = k1;
-    __syncthreads();
-  } else {
-    // the same network with KPT keys per thread: thread t owns indices t + 1024 r; a distance >= 1024 pairs two of its own keys
-    unsigned long long k[KPT];
-#pragma unroll
-    for (int r = 0; r < KPT; ++r) { const int i = tid + r * NMS_THREADS; k[r] = i < np2 ? key[i] : 0ull; }
-    auto cx = [](unsigned long long x, unsigned long long y, bool take_max) { return take_max == (x > y) ? x : y; };
-    int pb = 0;
-    for (int kk = 2; kk <= np2; kk <<= 1) {
-      for (int j = kk >> 1; j > 0; j >>= 1) {
-        if (j >= NMS_THREADS) {
-          const int jr = j / NMS_THREADS;                           // 1 or 2: partner key r ^ jr of the same thread
-#pragma unroll
-          for (int r = 0; r < KPT; ++r) {
-            if ((r & jr) == 0) {
-              const int r2 = r | jr;
-              const bool desc = ((tid + r * NMS_THREADS) & kk) == 0;  // (the same for both keys: jr * 1024 < kk)
-              const unsigned long long hi = k[r] > k[r2] ? k[r] : k[r2], lo = k[r] > k[r2] ? k[r2] : k[r];
-              k[r] = desc ? hi : lo; k[r2] = desc ? lo : hi;
-            }
-          }
-        } else if (j >= 64) {
-          unsigned long long* buf = pb ? key2 : key;
-#pragma unroll
-          for (int r = 0; r < KPT; ++r) buf[tid + r * NMS_THREADS] = k[r];
-          __syncthreads();
-          const bool low = (tid & j) == 0;
-#pragma unroll
-          for (int r = 0; r < KPT; ++r) {
-            const int i = tid + r * NMS_THREADS;
-            k[r] = cx(k[r], buf[i ^ j], low == ((i & kk) == 0));
-          }
-          pb ^= 1;
-        } else {
-          const bool low = (tid & j) == 0;
-#pragma unroll
-          for (int r = 0; r < KPT; ++r) {
-            const int i = tid + r * NMS_THREADS;
-            k[r] = cx(k[r], __shfl_xor(k[r], j), low == ((i & kk) == 0));
-          }
-        }
-      }
-    }
-    __syncthreads();
-#pragma unroll
-    for (int r = 0; r < KPT; ++r) { const int i = tid + r * NMS_THREADS; if (i < np2) key[i] = k[r]; }
-    __syncthreads();
-  }
+  if (np2 <= NMS_THREADS) bitonic_sort<1>(key, key2, np2, tid);
+  else bitonic_sort<KPT>(key, key2, np2, tid);
 
   NMS_STAMP(3);   // sorted
   // ---- 3. per-candidate geometry in sorted order
