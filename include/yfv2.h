@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define YFV2_ABI_VERSION 6 /* 2: yfv2_stage_info reports external bytes as well; 3: yfv2_train_*, yfv2_sgd_step; 4: yfv2_nonfinite, lanes; 5: yfv2_nonfinite_peek, yfv2_clock_probe_*; 6: yfv2_plan / yfv2_create_ex (the library reads no environment variable) */
+#define YFV2_ABI_VERSION 7 /* 2: yfv2_stage_info reports external bytes as well; 3: yfv2_train_*, yfv2_sgd_step; 4: yfv2_nonfinite, lanes; 5: yfv2_nonfinite_peek, yfv2_clock_probe_*; 6: yfv2_plan / yfv2_create_ex (the library reads no environment variable); 7: yfv2_debug_post */
 #define YFV2_API __attribute__((visibility("default")))
 #define YFV2_MAX_DET 300 /* utils/utils.py:243 max_det */
 
@@ -302,6 +302,13 @@ YFV2_API int yfv2_clock_probe_end(yfv2_handle h, double out[6], void* stream);
  * `stream`; enqueue only.  A launch repeated for a few hundred milliseconds is long enough for the device's power sensor:
  * tools/power_probe.py reads it meanwhile and prices every launch in joules (the pipelined headline is power-limited). */
 YFV2_API int yfv2_debug_repeat_step(yfv2_handle h, const float* x, int32_t B, float* const out6[6], int32_t step, int32_t iters, void* stream);
+
+/* Test hook: what yfv2_detect runs after its forward, on the caller's logits out6 (the six maps of yfv2_forward, device pointers):
+ * the fused decode + NMS launch where the plan and the shape allow it, otherwise decode into compact candidate rows + NMS over
+ * them.  Output as yfv2_detect; enqueue only.  Lets a test feed chosen logits (ties, saturated or non-finite values) to the
+ * launches yfv2_detect uses, which yfv2_decode + yfv2_nms do not reach. */
+YFV2_API int yfv2_debug_post(yfv2_handle h, const float* const out6[6], int32_t B, float conf_thres, double iou_thres,
+                             float* dets, int32_t* idx, int32_t* count, void* stream);
 
 /* Debug/parity helper: copy one internal NHWC activation of the LAST forward
  * to host as (B,H,W,C).  which: 0 stem+pool, 1 stage2, 2 stage3 (C2), 3 stage4

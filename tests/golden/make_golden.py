@@ -24,6 +24,8 @@ Outputs (all small, committed):
                        its own float64 evaluation - the noise floor a device path is held to (python make_golden.py floor)
   golden_loss.npz      seeded logits + targets -> reference utils/loss.py compute_loss values and its autograd
                        gradients w.r.t. the six logit maps (python make_golden.py loss)
+  golden_post_adversarial.npz  crafted decoded tensors (tests/adversarial_post.py, rebuilt from seeds) -> reference
+                       non_max_suppression rows + survivor indices over a grid of thresholds (python make_golden.py adversarial)
 
 usage: PYTHONDONTWRITEBYTECODE=1 python tests/golden/make_golden.py
 """
@@ -615,6 +617,60 @@ def make_floor_golden():
     print("golden_floor.npz", os.path.getsize(os.path.join(HERE, "golden_floor.npz")), "bytes; detections per image", out["n_det"])
 
 
+def adversarial_nms_grid(dec, nms):
+    """nms(dec, conf, iou, classes) -> (rows, idx) over the grid of tests/adversarial_post.py; yields (key, b, rows_b, idx_b)"""
+    import adversarial_post as A
+    for a, ct in enumerate(A.CONF_THRES):
+        for i, it in enumerate(A.IOU_THRES):
+            for f, cl in enumerate(A.CLASS_FILTER):
+                rows, idx = nms(dec, ct, it, None if cl is None else list(cl))
+                for b in range(dec.shape[0]):
+                    yield (a, i, f, b), rows[b], idx[b]
+
+
+def make_adversarial_golden():
+    """golden_post_adversarial.npz: the reference's own non_max_suppression (torchvision.ops.nms = oracle.nms_greedy, as for every
+    NMS fixture) on the crafted decoded tensors of tests/adversarial_post.py - NaN class scores, negative and signed-zero conf,
+    thresholds met exactly, IoU exactly at the threshold, zero-area boxes, suppression chains, ties across the 300 cut, boxes wider
+    than the class offset - at every (conf, iou, class filter) of its grid, for 352 x 352 / 512 x 512 row counts and 80 / 255
+    classes.  Inputs are rebuilt from seeds (a probe of their bits is stored); results are stored once per distinct outcome."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import adversarial_post as A
+    torch.set_num_threads(1)
+    _, uu = import_reference()
+
+    def ref_nms(dec, ct, it, cl):
+        rows = []
+        for b in range(dec.shape[0]):
+            x = torch.from_numpy(dec[b:b + 1].copy())
+            rows.append(uu.non_max_suppression(x, conf_thres=ct, iou_thres=it, classes=cl)[0].numpy().astype(np.float32))
+        o_rows, o_idx = oracle.non_max_suppression(dec, ct, it, classes=cl)
+        for b in range(dec.shape[0]):   # survivor indices from the oracle's restatement: its rows must be the reference's
+            assert A.same_bits(rows[b], o_rows[b]), ("oracle NMS != reference NMS", ct, it, cl, b, rows[b], o_rows[b])
+        return rows, o_idx
+
+    shape = (len(A.DECODED_CONFIGS), len(A.CONF_THRES), len(A.IOU_THRES), len(A.CLASS_FILTER), len(A.DECODED_CASES))
+    result = np.full(shape, -1, np.int32)
+    uniq, u_rows, u_idx = {}, [], []
+    out = {"configs": np.asarray(A.DECODED_CONFIGS, np.int32), "conf_thres": np.asarray(A.CONF_THRES, np.float64),
+           "iou_thres": np.asarray(A.IOU_THRES, np.float64), "cases": np.asarray([n for n, _ in A.DECODED_CASES])}
+    for c, (rows, nc) in enumerate(A.DECODED_CONFIGS):
+        dec = A.decoded_batch(rows, nc)
+        out["probe%d" % c] = A.probe(dec)
+        for key, r, i in adversarial_nms_grid(dec, ref_nms):
+            k = (r.tobytes(), np.asarray(i, np.int32).tobytes())
+            if k not in uniq:
+                uniq[k] = len(u_rows)
+                u_rows.append(r.astype(np.float32)); u_idx.append(np.asarray(i, np.int64))
+            result[(c,) + key] = uniq[k]
+        print("config", rows, nc, "survivors per case at 0.3 / 0.4:", [int((result[c, 0, 0, 0, b] >= 0) and len(u_idx[result[c, 0, 0, 0, b]])) for b in range(shape[-1])])
+    out["result"] = result
+    pack_ragged("nms", u_rows, u_idx, out)
+    path = os.path.join(HERE, "golden_post_adversarial.npz")
+    np.savez_compressed(path, **out)
+    print("golden_post_adversarial.npz", os.path.getsize(path), "bytes;", len(u_rows), "distinct results of", result.size)
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "train":
         make_train_golden()   # only golden_train.npz
@@ -624,6 +680,8 @@ if __name__ == "__main__":
         make_loss_golden()    # only golden_loss.npz
     elif len(sys.argv) > 1 and sys.argv[1] == "floor":
         make_floor_golden()   # only golden_floor.npz
+    elif len(sys.argv) > 1 and sys.argv[1] == "adversarial":
+        make_adversarial_golden()   # only golden_post_adversarial.npz
     elif len(sys.argv) > 1 and sys.argv[1] == "ap":
         make_ap_golden()      # only golden_ap.npz (the other files are left as committed)
     else:

@@ -27,7 +27,9 @@ def _lib():
     return _lib
 
 
-def test_library_exports_every_declared_symbol():
+def test_library_exports_every_declared_symbol_and_its_abi_version():
+    """every YFV2_API symbol of include/yfv2.h is bound and exported, nothing else leaks, and the library, the binding and this
+    pin agree on the ABI number (7: yfv2_debug_post) - a new entry point must bump all three"""
     _lib_mod = _lib()
     hdr = open(os.path.join(REPO, "include", "yfv2.h")).read()
     declared = set(re.findall(r"YFV2_API\s+[\w\s\*]+?\b(yfv2_\w+)\s*\(", hdr))
@@ -36,7 +38,7 @@ def test_library_exports_every_declared_symbol():
     raw = C.CDLL(_lib_mod.LIB_PATH)
     for name in declared:
         assert hasattr(raw, name), "libyfv2.so does not export %s" % name
-    assert _lib_mod.lib().yfv2_abi_version() == _lib_mod.ABI_VERSION == 6
+    assert _lib_mod.lib().yfv2_abi_version() == _lib_mod.ABI_VERSION == 7
     # nothing else leaks out of the library's namespace
     syms = subprocess.run(["nm", "-D", "--defined-only", _lib_mod.LIB_PATH], capture_output=True, text=True).stdout
     exported = {l.split()[-1] for l in syms.splitlines() if " T " in l}

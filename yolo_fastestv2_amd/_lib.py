@@ -11,7 +11,7 @@ import os
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # YFV2_LIB: opt-in override used only for same-box A/B of two builds (tools/gpu_quick.sh)
 LIB_PATH = os.environ.get("YFV2_LIB") or os.path.join(_HERE, "libyfv2.so")
-ABI_VERSION = 6
+ABI_VERSION = 7
 MAX_DET = 300
 
 OK, ERR_ARG, ERR_CONFIG, ERR_DEVICE, ERR_WEIGHTS, ERR_STATE, ERR_BATCH, ERR_RANGE = 0, -1, -2, -3, -4, -5, -6, -7
@@ -121,6 +121,8 @@ _PROTOTYPES = {
     "yfv2_profile_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.c_int32,
                                        C.POINTER(C.c_float), C.c_void_p]),
     "yfv2_debug_repeat_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p), C.c_int32, C.c_int32, C.c_void_p]),
+    "yfv2_debug_post": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_float, C.c_double, C.c_void_p, C.c_void_p,
+                                  C.c_void_p, C.c_void_p]),
     "yfv2_debug_activation": (C.c_int64, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64]),
     "yfv2_debug_train_relu_output": (C.c_int64, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]),
 }

@@ -2395,9 +2395,10 @@ static DecodeArgs decode_args(yfv2_handle h, const float* const out6[6], int32_t
   a.rows = h->rows;
   return a;
 }
-// handel_preds + non_max_suppression behind a forward whose logits sit in h->logits: one launch that decodes each image into
+// handel_preds + non_max_suppression of the logits out6 (h->logits behind a forward): one launch that decodes each image into
 // LDS (default), or decode_kernel<compact> + nms_kernel over candidate rows in HBM (YFV2_POSTFUSE=0, the A/B reference)
-static int post_impl(yfv2_handle h, int32_t B, float conf_thres, double iou_thres, float* dets, int32_t* idx, int32_t* count, void* stream);
+static int post_impl(yfv2_handle h, const float* const out6[6], int32_t B, float conf_thres, double iou_thres, float* dets, int32_t* idx,
+                     int32_t* count, void* stream);
 static int decode_impl(yfv2_handle h, const float* const out6[6], int32_t B, float* boxes, float* cand, void* stream);
 static int nms_impl(yfv2_handle h, const float* boxes, int compact, int32_t B, float conf_thres, double iou_thres,
                     const int32_t* classes, int32_t n_classes, float* dets, int32_t* idx, int32_t* count, void* stream);
@@ -2465,13 +2466,22 @@ int yfv2_detect(yfv2_handle h, const float* x, int32_t B, float conf_thres, doub
   for (int i = 0; i < 6; ++i) out6[i] = h->logits[i].p;
   rc = yfv2_forward(h, x, B, out6, stream);
   if (rc) return rc;
-  return post_impl(h, B, conf_thres, iou_thres, dets, idx, count, stream);
+  return post_impl(h, out6, B, conf_thres, iou_thres, dets, idx, count, stream);
 }
 
-static int post_impl(yfv2_handle h, int32_t B, float conf_thres, double iou_thres, float* dets, int32_t* idx, int32_t* count, void* stream) {
+int yfv2_debug_post(yfv2_handle h, const float* const out6[6], int32_t B, float conf_thres, double iou_thres, float* dets, int32_t* idx,
+                    int32_t* count, void* stream) {
+  int rc = check_call(h, B, false);
+  if (rc) return rc;
+  if (!out6) return fail(h, YFV2_ERR_ARG, "yfv2_debug_post: null pointer");
+  for (int i = 0; i < 6; ++i)
+    if (!out6[i]) return fail(h, YFV2_ERR_ARG, "yfv2_debug_post: null logit tensor");
+  return post_impl(h, out6, B, conf_thres, iou_thres, dets, idx, count, stream);
+}
+
+static int post_impl(yfv2_handle h, const float* const out6[6], int32_t B, float conf_thres, double iou_thres, float* dets, int32_t* idx,
+                     int32_t* count, void* stream) {
   if (!dets || !idx || !count) return fail(h, YFV2_ERR_ARG, "yfv2_detect: null pointer");
-  float* out6[6];
-  for (int i = 0; i < 6; ++i) out6[i] = h->logits[i].p;
   if (!h->postfuse || !yfv2_post_fusable(h->cfg.classes, h->rows)) {
     // compact candidate rows instead of the (B,1815,85) tensor: same arithmetic, 10x less traffic
     const int rc = decode_impl(h, out6, B, nullptr, h->cand.p, stream);
@@ -2507,7 +2517,7 @@ int yfv2_detect_u8(yfv2_handle h, const uint8_t* x, int32_t B, float conf_thres,
   for (int i = 0; i < 6; ++i) out6[i] = h->logits[i].p;
   rc = yfv2_forward_u8(h, x, B, out6, stream);
   if (rc) return rc;
-  return post_impl(h, B, conf_thres, iou_thres, dets, idx, count, stream);
+  return post_impl(h, out6, B, conf_thres, iou_thres, dets, idx, count, stream);
 }
 
 // enqueue only: the overflow flag is sticky in the handle until yfv2_batch_statistics_overflow reads it

@@ -303,9 +303,9 @@ int yfv2_nms_max_rows() { return 4096; }
 // ============================================================================
 // One workgroup per image, everything in LDS:
 //   1. filter   obj > ct ; conf = max_j fl32(cls_j*obj) (first max) ; conf > ct ; class filter
-//   2. sort     bitonic sort of 64-bit keys (conf bits << 32 | ~row): descending
+//   2. sort     bitonic sort of 64-bit keys (conf_key << 32 | ~row): descending
 //               conf, ties -> lower row first (stable order of the reference's
-//               filtered list); conf > ct >= 0 so the fp32 bit pattern is monotone
+//               filtered list); conf_key is monotone in conf for any sign
 //   3. prepare  xywh -> xyxy, + cls*4096 offset, area - all in fp32 exactly as
 //               utils.py:67-74,283-285 and torchvision compute them
 //   4. greedy   walk the sorted list; a kept box suppresses later boxes whose
@@ -408,6 +408,14 @@ __device__ __forceinline__ void bitonic_sort(unsigned long long* key, unsigned l
   __syncthreads();
 }
 
+// High word of a candidate's sort key: unsigned order of the key = numeric order of conf, negative values included, and -0.0
+// keys like +0.0 (the reference sorts by value, stably: equal confs keep row order).  The output row reads conf from the
+// candidate's row, not from the key.
+__device__ __forceinline__ unsigned conf_key(float c) {
+  const unsigned u = __float_as_uint(c == 0.f ? 0.f : c);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
 // SRC 0: the (B, rows, 5 + classes) decoded tensor (yfv2_nms); 1: compact candidate rows in global memory (decode_kernel<true>);
 // 2: the logits themselves - the workgroup decodes its image into compact rows in LDS first (yfv2_detect: one launch for
 // handel_preds + non_max_suppression, the candidate rows never exist in HBM)
@@ -497,7 +505,7 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(NmsArgs a, DecodeArgs 
       base = __shfl(base, 0);
       if (pass) {
         const int slot = base + (int)__popcll(m & ((1ull << (tid & 63)) - 1ull));
-        key[slot] = ((unsigned long long)__float_as_uint(t[1]) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)n);
+        key[slot] = ((unsigned long long)conf_key(t[1]) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)n);
         cls_of_row[n] = (unsigned char)(int)t[2];
       }
     }
@@ -521,15 +529,17 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(NmsArgs a, DecodeArgs 
         const float obj = r[4];
         float best = -INFINITY;
         int bj = 0x7fffffff;
+        // torch.max: a NaN wins over every number (the first NaN among NaNs), and then conf > ct drops the row
         for (int j = l16; j < a.nc; j += 16) {
           const float pj = __fmul_rn(r[5 + j], obj);
-          if (pj > best) { best = pj; bj = j; }  // strict: first maximal index of this lane
+          if (pj > best || (pj != pj && best == best)) { best = pj; bj = j; }  // the lane's first NaN, else its first maximal index
         }
 #pragma unroll
         for (int m = 1; m < 16; m <<= 1) {
           const float ob = __shfl_xor(best, m, 16);
           const int oj = __shfl_xor(bj, m, 16);
-          if (ob > best || (ob == best && oj < bj)) { best = ob; bj = oj; }
+          const bool take = ob != ob ? (best == best || oj < bj) : (best == best && (ob > best || (ob == best && oj < bj)));
+          if (take) { best = ob; bj = oj; }
         }
         if (l16 == 0 && best > ct) {
           bool hit = true;
@@ -539,7 +549,7 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(NmsArgs a, DecodeArgs 
           }
           if (hit) {
             const int slot = atomicAdd(&n_cand, 1);
-            key[slot] = ((unsigned long long)__float_as_uint(best) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)n);
+            key[slot] = ((unsigned long long)conf_key(best) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)n);
             cls_of_row[n] = (unsigned char)bj;
           }
         }
@@ -696,7 +706,7 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(NmsArgs a, DecodeArgs 
     float* d = a.dets + ((size_t)b * NMS_MAX_DET + k) * 6;
     d[0] = __fsub_rn(cx, hw_); d[1] = __fsub_rn(cy, hh);
     d[2] = __fadd_rn(cx, hw_); d[3] = __fadd_rn(cy, hh);
-    d[4] = __uint_as_float((unsigned)(kk >> 32));
+    d[4] = COMPACT ? r[5] : __fmul_rn(r[5 + cls_of_row[row]], r[4]);   // the filter's own product: its bits, -0.0 included
     d[5] = (float)cls_of_row[row];
     a.idx[(size_t)b * NMS_MAX_DET + k] = (int)row;
   }

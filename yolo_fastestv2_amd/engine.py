@@ -186,6 +186,22 @@ class Engine:
                                   _ptr(idx), _ptr(cnt), _stream(self.device)), self._h)
         return dets, idx, cnt
 
+    def post(self, preds, conf_thres, iou_thres, out=None):
+        """What detect() runs after its forward, on the caller's six logit maps (include/yfv2.h yfv2_debug_post): the fused
+        decode + NMS launch where the plan and the shape allow it, else decode into compact rows + NMS.  Enqueue only."""
+        self._need_anchors("post")
+        preds = [p.contiguous() for p in preds]
+        B = preds[0].shape[0]
+        for p, s in zip(preds, self.logit_shapes(B)):
+            if tuple(p.shape) != s or p.dtype != torch.float32 or p.device != self.device:
+                raise ValueError("logit tensor %s %s on %s, expected fp32 %s on %s" % (p.dtype, tuple(p.shape), p.device, s, self.device))
+        self.ensure_batch(B)
+        dets, idx, cnt = out if out is not None else self.new_det_buffers(B)
+        ptrs = (C.c_void_p * 6)(*[t.data_ptr() for t in preds])
+        check(_lib.lib().yfv2_debug_post(self._h, ptrs, B, float(conf_thres), float(iou_thres), _ptr(dets), _ptr(idx), _ptr(cnt),
+                                         _stream(self.device)), self._h)
+        return dets, idx, cnt
+
     def detect(self, x, conf_thres, iou_thres, out=None, check=True):
         """forward + decode + NMS, enqueue only: the results are device tensors and nothing waits for the device.  check=True
         (default) LOOKS at the range-guard word first (yfv2_nonfinite_peek: a host memory read, no synchronisation) and raises if a
