@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define YFV2_ABI_VERSION 7 /* 2: yfv2_stage_info reports external bytes as well; 3: yfv2_train_*, yfv2_sgd_step; 4: yfv2_nonfinite, lanes; 5: yfv2_nonfinite_peek, yfv2_clock_probe_*; 6: yfv2_plan / yfv2_create_ex (the library reads no environment variable); 7: yfv2_debug_post */
+#define YFV2_ABI_VERSION 7 /* 2: yfv2_stage_info reports external bytes as well; 3: yfv2_train_*, yfv2_sgd_step; 4: yfv2_nonfinite, lanes; 5: yfv2_nonfinite_peek, yfv2_clock_probe_*; 6: yfv2_plan / yfv2_create_ex (the library reads no environment variable); 7: yfv2_debug_post; still 7 with the additive yfv2_frame, yfv2_resize_frames_u8, yfv2_detect_frames_u8 (old callers are unaffected) */
 #define YFV2_API __attribute__((visibility("default")))
 #define YFV2_MAX_DET 300 /* utils/utils.py:243 max_det */
 
@@ -184,6 +184,31 @@ YFV2_API int yfv2_detect_u8(yfv2_handle h, const uint8_t* x, int32_t B, float co
  * arithmetic is OpenCV's 8-bit fixed-point bilinear path (11-bit coefficients, see yfv2_pre.hip); src size == dst
  * size is an exact copy.  Source rows up to ~27 000 pixels wide.  SURVEY.md section 8(f) row 1. */
 YFV2_API int yfv2_resize_u8(yfv2_handle h, const uint8_t* src, int32_t B, int32_t src_h, int32_t src_w, uint8_t* dst, void* stream);
+
+/* One uint8 HWC frame of a batch of frames of DIFFERENT sizes.  data: DEVICE pointer to its first byte (any alignment);
+ * row r starts at data + r * row_pitch (row_pitch >= 3 * width: a crop of a larger frame needs no copy). */
+typedef struct yfv2_frame {
+  const uint8_t* data;
+  int32_t height, width;
+  int64_t row_pitch;
+} yfv2_frame;
+
+/* yfv2_resize_u8 for B frames of any sizes at once: frames is a HOST array of B descriptors; dst (B, cfg.height, cfg.width, 3)
+ * on the device, 4-byte aligned.  Frame b's output is bit-identical to yfv2_resize_u8 of that frame alone.  Checked before
+ * anything is enqueued (YFV2_ERR_ARG with a message): NULL pointers, B < 1, height or width < 1, row_pitch < 3 * width, a
+ * frame wider than (160 KiB - 3 cfg.width) / 6 - 2 pixels (27 128 at width 352), dst not 4-byte aligned.  B > max_batch is
+ * YFV2_ERR_BATCH: the descriptors go to a table of max_batch entries the handle owns, in one copy on `stream`.
+ * Replaces test.py:35 over a list of decoded frames. */
+YFV2_API int yfv2_resize_frames_u8(yfv2_handle h, const yfv2_frame* frames, int32_t B, uint8_t* dst, void* stream);
+
+/* test.py:34-68 for a batch of frames of any sizes: yfv2_resize_frames_u8 into a (max_batch, height, width, 3) buffer the
+ * handle owns (allocated by the first call, which waits for the device once, like yfv2_loss's workspace), yfv2_detect_u8 on it
+ * (on the handle's lanes where the plan has them), then columns 0-3 of the first count[b] rows of frame b are multiplied by
+ * width_b / cfg.width (x) and height_b / cfg.height (y): fp32(double(x) * (double(w) / double(W))), test.py:58,65-66, no
+ * clipping.  conf, class, idx, count and the rows beyond count[b] are exactly what yfv2_detect_u8 writes.  Same checks as
+ * yfv2_resize_frames_u8 plus those of yfv2_detect_u8 (B <= max_batch, weights loaded). */
+YFV2_API int yfv2_detect_frames_u8(yfv2_handle h, const yfv2_frame* frames, int32_t B, float conf_thres, double iou_thres,
+                                   float* dets, int32_t* idx, int32_t* count, void* stream);
 
 /* replaces: utils/utils.py:194-230 get_batch_statistics (with bbox_iou :76-108), the per-detection loop of
  * evaluation() (:361-395).  dets/count: the padded output of yfv2_nms / yfv2_detect; targets: (T,6) fp32 device rows

@@ -68,6 +68,11 @@ class SgdItem(C.Structure):
     _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("momentum_buf", C.c_void_p), ("n", C.c_int64), ("first_step", C.c_int32), ("reserved", C.c_int32)]
 
 
+class Frame(C.Structure):
+    """yfv2_frame (include/yfv2.h): one uint8 HWC frame of a ragged batch; data is a DEVICE pointer."""
+    _fields_ = [("data", C.c_void_p), ("height", C.c_int32), ("width", C.c_int32), ("row_pitch", C.c_int64)]
+
+
 class Yfv2Error(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("libyfv2 error %d: %s" % (code, msg))
@@ -108,6 +113,9 @@ _PROTOTYPES = {
     "yfv2_sgd_step": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_int32, C.c_void_p]),
     "yfv2_sgd_step_multi": (C.c_int, [C.c_void_p, C.POINTER(SgdItem), C.c_int32, C.c_float, C.c_float, C.c_float, C.c_void_p]),
     "yfv2_resize_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]),
+    "yfv2_resize_frames_u8": (C.c_int, [C.c_void_p, C.POINTER(Frame), C.c_int32, C.c_void_p, C.c_void_p]),
+    "yfv2_detect_frames_u8": (C.c_int, [C.c_void_p, C.POINTER(Frame), C.c_int32, C.c_float, C.c_double, C.c_void_p, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
     "yfv2_debug_plan_dryrun": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "yfv2_debug_plan_dryrun_ex": (C.c_int, [C.c_void_p, C.POINTER(Plan), C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "yfv2_debug_plan_image": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_char_p, C.c_int32, C.c_void_p, C.c_int64]),

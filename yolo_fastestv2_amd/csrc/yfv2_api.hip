@@ -102,6 +102,8 @@ struct yfv2_ctx {
   Buf cand;  // (rows, 8) compact candidate rows of yfv2_detect
   int32_t* d_classes = nullptr;  // class filter scratch (<= 256 entries), then one int32 of its own for the statistics overflow flag
   int32_t* d_stats_flag = nullptr;  // = d_classes + 256
+  ResizeFrame* d_frames = nullptr;   // frame descriptors of yfv2_resize_frames_u8 / yfv2_detect_frames_u8 (max_batch entries)
+  uint8_t* d_frames_u8 = nullptr;    // yfv2_detect_frames_u8's resized batch (max_batch, H, W, 3): allocated by its first call
   // the sticky range-guard word of the fp16x3 plan (yfv2_nonfinite): ONE int32 in host-mapped, coherent memory.  The kernels
   // store 1 into it through d_nonfinite (the rare path, a plain store); the host reads h_nonfinite - after waiting for a stream
   // (yfv2_nonfinite: exact) or without waiting (yfv2_nonfinite_peek: what has landed so far).  A lane uses its parent's word.
@@ -2146,6 +2148,8 @@ int yfv2_create_ex(yfv2_handle* out, const yfv2_config* cfg, const yfv2_plan* pl
   int rc = setup_ctx(h, cfg, rows, alloc_buf);
   if (rc == YFV2_OK && hipMalloc(reinterpret_cast<void**>(&h->d_classes), 258 * sizeof(int32_t)) != hipSuccess)
     rc = fail(h, YFV2_ERR_DEVICE, "hipMalloc(class filter) failed");
+  if (rc == YFV2_OK && hipMalloc(reinterpret_cast<void**>(&h->d_frames), sizeof(ResizeFrame) * (size_t)cfg->max_batch) != hipSuccess)
+    rc = fail(h, YFV2_ERR_DEVICE, "hipMalloc(frame table) failed");
   if (rc == YFV2_OK) {
     h->d_stats_flag = h->d_classes + 256;
     if (hipMemset(h->d_stats_flag, 0, 2 * sizeof(int32_t)) != hipSuccess) rc = fail(h, YFV2_ERR_DEVICE, "hipMemset(flags) failed");
@@ -2295,6 +2299,8 @@ void yfv2_destroy(yfv2_handle h) {
   for (int i = 0; i < 6; ++i) free_buf(&h->logits[i]);
   free_buf(&h->cand);
   if (h->d_classes) (void)hipFree(h->d_classes);
+  if (h->d_frames) (void)hipFree(h->d_frames);
+  if (h->d_frames_u8) (void)hipFree(h->d_frames_u8);
   if (h->h_nonfinite) (void)hipHostFree(h->h_nonfinite);
   if (h->d_probe) (void)hipFree(h->d_probe);
   if (h->d_loss_ws) (void)hipFree(h->d_loss_ws);
@@ -2690,6 +2696,83 @@ int yfv2_resize_u8(yfv2_handle h, const uint8_t* src, int32_t B, int32_t src_h, 
   a.scale_x = 1.0 / ((double)a.W / (double)src_w);      // cv::resize: inv_scale = dsize / ssize, scale = 1 / inv_scale
   a.scale_y = 1.0 / ((double)a.H / (double)src_h);
   yfv2_launch_resize(a, s);
+  HIP_TRY(h, hipGetLastError());
+  return YFV2_OK;
+}
+
+// Ragged batches (yfv2_resize_frames_u8 / yfv2_detect_frames_u8): every frame is checked here, before anything is enqueued,
+// and expanded by its scales into t; *max_w = the widest frame (it sizes the resize launch's LDS).  The table is B entries of
+// the handle's max_batch, so B is bound by max_batch on both entry points.
+static int check_frames(yfv2_handle h, const char* what, const yfv2_frame* frames, int32_t B, std::vector<ResizeFrame>& t, int* max_w) {
+  const std::string w_ = what;
+  if (!frames) return fail(h, YFV2_ERR_ARG, w_ + ": null pointer");
+  if (B < 1) return fail(h, YFV2_ERR_ARG, w_ + ": B < 1");
+  if (B > h->cfg.max_batch)
+    return fail(h, YFV2_ERR_BATCH, w_ + ": batch " + std::to_string(B) + " above max_batch=" + std::to_string(h->cfg.max_batch));
+  const int H = h->cfg.height, W = h->cfg.width;
+  const int limit = (160 * 1024 - 3 * W) / 6 - 2;
+  t.assign((size_t)B, ResizeFrame{});
+  int mw = 1;
+  for (int32_t b = 0; b < B; ++b) {
+    const yfv2_frame& f = frames[b];
+    const std::string at = w_ + ": frame " + std::to_string(b) + ": ";
+    if (f.height < 1 || f.width < 1) return fail(h, YFV2_ERR_ARG, at + "height and width must be >= 1");
+    if (!f.data) return fail(h, YFV2_ERR_ARG, at + "null data");
+    if (f.row_pitch < 3ll * f.width) return fail(h, YFV2_ERR_ARG, at + "row_pitch " + std::to_string(f.row_pitch) + " < 3 * width");
+    if (f.width > limit || yfv2_resize_lds_bytes(f.width, W) > 160 * 1024)
+      return fail(h, YFV2_ERR_ARG, at + "frames wider than " + std::to_string(limit) + " pixels are not supported");
+    if (f.row_pitch > (1ll << 40) || (long long)(f.height - 1) * f.row_pitch > (1ll << 52))
+      return fail(h, YFV2_ERR_ARG, at + "row_pitch out of range");
+    ResizeFrame& r = t[(size_t)b];
+    r.data = f.data; r.pitch = f.row_pitch; r.h = f.height; r.w = f.width;
+    r.scale_x = 1.0 / ((double)W / (double)f.width);      // exactly yfv2_resize_u8's scales
+    r.scale_y = 1.0 / ((double)H / (double)f.height);
+    r.box_x = (double)f.width / (double)W;                // test.py:58  scale_w = w / cfg["width"]
+    r.box_y = (double)f.height / (double)H;
+    mw = std::max(mw, (int)f.width);
+  }
+  if ((long long)B * H > 0x7fffffffll) return fail(h, YFV2_ERR_ARG, w_ + ": batch too large");
+  *max_w = mw;
+  return YFV2_OK;
+}
+
+int yfv2_resize_frames_u8(yfv2_handle h, const yfv2_frame* frames, int32_t B, uint8_t* dst, void* stream) {
+  if (!h) return fail(nullptr, YFV2_ERR_ARG, "null handle");
+  if (!dst) return fail(h, YFV2_ERR_ARG, "yfv2_resize_frames_u8: null pointer");
+  if ((reinterpret_cast<uintptr_t>(dst) & 3) != 0) return fail(h, YFV2_ERR_ARG, "yfv2_resize_frames_u8: dst must be 4-byte aligned");
+  std::vector<ResizeFrame> t;
+  int max_w = 0;
+  int rc = check_frames(h, "yfv2_resize_frames_u8", frames, B, t, &max_w);
+  if (rc) return rc;
+  DeviceGuard guard(h->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  HIP_TRY(h, hipMemcpyAsync(h->d_frames, t.data(), sizeof(ResizeFrame) * (size_t)B, hipMemcpyHostToDevice, s));
+  yfv2_launch_resize_frames(h->d_frames, B, max_w, dst, h->cfg.height, h->cfg.width, s);
+  HIP_TRY(h, hipGetLastError());
+  return YFV2_OK;
+}
+
+int yfv2_detect_frames_u8(yfv2_handle h, const yfv2_frame* frames, int32_t B, float conf_thres, double iou_thres, float* dets,
+                          int32_t* idx, int32_t* count, void* stream) {
+  int rc = check_call(h, B, true);
+  if (rc) return rc;
+  if (!dets || !idx || !count) return fail(h, YFV2_ERR_ARG, "yfv2_detect_frames_u8: null pointer");
+  std::vector<ResizeFrame> t;
+  int max_w = 0;
+  rc = check_frames(h, "yfv2_detect_frames_u8", frames, B, t, &max_w);
+  if (rc) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DeviceGuard guard(h->device);
+  if (!h->d_frames_u8) {   // the resized batch, allocated on first use: handles that never see frames keep their footprint
+    HIP_TRY(h, hipDeviceSynchronize());   // like the loss workspace: the allocation waits for the device once
+    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&h->d_frames_u8), (size_t)h->cfg.height * h->cfg.width * 3 * (size_t)h->cfg.max_batch));
+  }
+  HIP_TRY(h, hipMemcpyAsync(h->d_frames, t.data(), sizeof(ResizeFrame) * (size_t)B, hipMemcpyHostToDevice, s));
+  yfv2_launch_resize_frames(h->d_frames, B, max_w, h->d_frames_u8, h->cfg.height, h->cfg.width, s);
+  HIP_TRY(h, hipGetLastError());
+  rc = yfv2_detect_u8(h, h->d_frames_u8, B, conf_thres, iou_thres, dets, idx, count, stream);
+  if (rc) return rc;
+  yfv2_launch_frame_boxes(dets, count, h->d_frames, B, s);
   HIP_TRY(h, hipGetLastError());
   return YFV2_OK;
 }

@@ -407,6 +407,17 @@ struct ResizeArgs {
 };
 size_t yfv2_resize_lds_bytes(int SW, int W);
 void yfv2_launch_resize(const ResizeArgs& a, hipStream_t s);
+// one frame of a ragged batch (yfv2_resize_frames_u8 / yfv2_detect_frames_u8), expanded on the host and uploaded as a table
+struct ResizeFrame {
+  const unsigned char* data;  // first byte of the frame (any alignment), device
+  long long pitch;            // bytes from one row to the next, >= 3 w
+  int h, w;
+  double scale_x, scale_y;    // resize: 1 / (W / w), 1 / (H / h), as ResizeArgs
+  double box_x, box_y;        // frame-coordinate epilogue: w / W, h / H (test.py:58)
+};
+void yfv2_launch_resize_frames(const ResizeFrame* frames, int B, int max_w, unsigned char* dst, int H, int W, hipStream_t s);
+// dets columns 0-3 of the first count[b] rows of frame b times frames[b].box_x / box_y (yfv2_post.hip)
+void yfv2_launch_frame_boxes(float* dets, const int32_t* count, const ResizeFrame* frames, int B, hipStream_t s);
 void yfv2_launch_decode(const DecodeArgs& a, hipStream_t s);
 void yfv2_launch_nms(const NmsArgs& a, hipStream_t s);
 void yfv2_launch_decode_nms(const DecodeArgs& d, const NmsArgs& a, hipStream_t s);   // yfv2_detect: decode + NMS in one launch

@@ -815,3 +815,26 @@ __global__ __launch_bounds__(64) void stats_kernel(StatsArgs a) {
 }
 
 void yfv2_launch_stats(const StatsArgs& a, hipStream_t s) { YFV2_LAUNCH(stats_kernel, dim3(a.B), dim3(64), 0, s, a); }
+
+// yfv2_detect_frames_u8's epilogue: network coordinates -> frame coordinates.  test.py:58-68 scales each box by
+// scale_w = w / cfg["width"], scale_h = h / cfg["height"] (Python floats) and multiplies box[k] (a Python float, i.e. the fp32
+// value exactly) by it: double(x) * double(w / W), rounded here once more to fp32 (the ratio itself is formed on the host in
+// double).  No clipping (the reference clips nothing).  One thread per (frame, detection row); rows at or beyond count[b], and
+// columns 4-5 of every row, are not touched.
+__global__ __launch_bounds__(256) void frame_boxes_kernel(float* __restrict__ dets, const int32_t* __restrict__ count,
+                                                          const ResizeFrame* __restrict__ frames, int B) {
+  const int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= B * NMS_MAX_DET) return;
+  const int b = t / NMS_MAX_DET, i = t - b * NMS_MAX_DET;
+  if (i >= count[b]) return;
+  const double sx = frames[b].box_x, sy = frames[b].box_y;
+  float* d = dets + (size_t)t * 6;
+  d[0] = __double2float_rn(__dmul_rn((double)d[0], sx));
+  d[1] = __double2float_rn(__dmul_rn((double)d[1], sy));
+  d[2] = __double2float_rn(__dmul_rn((double)d[2], sx));
+  d[3] = __double2float_rn(__dmul_rn((double)d[3], sy));
+}
+
+void yfv2_launch_frame_boxes(float* dets, const int32_t* count, const ResizeFrame* frames, int B, hipStream_t s) {
+  YFV2_LAUNCH(frame_boxes_kernel, dim3((unsigned)((B * NMS_MAX_DET + 255) / 256)), dim3(256), 0, s, dets, count, frames, B);
+}

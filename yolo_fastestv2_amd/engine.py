@@ -230,6 +230,58 @@ class Engine:
         check(_lib.lib().yfv2_resize_u8(self._h, _ptr(frames), B, sh, sw, _ptr(out), _stream(self.device)), self._h)
         return out
 
+    def _frame_table(self, frames):
+        """list / tuple of uint8 (h_i, w_i, 3) device tensors -> (yfv2_frame array, the tensors it points into).  A tensor whose rows are
+        packed pixels (stride(2) == 1, stride(1) == 3) with a row pitch stride(0) >= 3 w - a crop of a larger frame, any base
+        address - is passed as it is; anything else is made contiguous first."""
+        if not isinstance(frames, (list, tuple)) or not frames:
+            raise ValueError("frames must be a non-empty list or tuple of uint8 (h,w,3) tensors")
+        keep = []
+        arr = (_lib.Frame * len(frames))()
+        for i, f in enumerate(frames):
+            if not isinstance(f, torch.Tensor) or f.dtype != torch.uint8 or f.device != self.device or f.dim() != 3 or f.shape[2] != 3:
+                raise ValueError("frame %d: expected a uint8 (h,w,3) tensor on %s, got %s" % (
+                    i, self.device, "%s %s on %s" % (f.dtype, tuple(f.shape), f.device) if isinstance(f, torch.Tensor) else type(f).__name__))
+            h, w = int(f.shape[0]), int(f.shape[1])
+            packed = lambda t: t.stride(2) == 1 and (w <= 1 or t.stride(1) == 3) and (h <= 1 or t.stride(0) >= 3 * w)
+            if not packed(f):
+                f = f.contiguous()
+            keep.append(f)
+            arr[i].data, arr[i].height, arr[i].width = f.data_ptr(), h, w
+            arr[i].row_pitch = f.stride(0) if h > 1 else 3 * w
+        return arr, keep
+
+    def resize_frames(self, frames, out=None):
+        """A list of uint8 (h_i, w_i, 3) frames of any sizes on the GPU -> uint8 (B, height, width, 3): `resize` for a batch whose frames
+        differ in size (test.py:34-35 per frame, include/yfv2.h yfv2_resize_frames_u8).  Frame b's output is bit-identical to
+        resize() of that frame alone.  Grows max_batch like every batched call (the descriptor table has max_batch entries)."""
+        arr, keep = self._frame_table(frames)
+        B = len(keep)
+        self.ensure_batch(B)
+        if out is None:
+            out = torch.empty((B, self.height, self.width, 3), device=self.device, dtype=torch.uint8)
+        elif out.dtype != torch.uint8 or tuple(out.shape) != (B, self.height, self.width, 3) or out.device != self.device or not out.is_contiguous():
+            raise ValueError("out must be a contiguous uint8 (%d,%d,%d,3) tensor on %s" % (B, self.height, self.width, self.device))
+        check(_lib.lib().yfv2_resize_frames_u8(self._h, arr, B, _ptr(out), _stream(self.device)), self._h)
+        return out
+
+    def detect_frames(self, frames, conf_thres, iou_thres, out=None, check=True):
+        """test.py:34-35,58-68 for a batch of frames of any sizes: resize each uint8 (h_i, w_i, 3) device frame to (height, width)
+        (cv2.resize INTER_LINEAR, test.py:34-35), detect, then scale each box back to its frame - x by w_i / width, y by h_i / height,
+        in double and rounded to fp32, as test.py:58-68 does with its Python floats (no clipping).  Returns (dets, idx, cnt) like
+        detect(), dets in frame coordinates; conf, class, idx, cnt are what detect() returns for the resized batch.  Enqueue only:
+        nothing waits for the device (the first call on a handle allocates its resize buffer and waits once); check= as in detect()."""
+        self._need_anchors("detect_frames")
+        if check and self.peek_nonfinite():
+            self.check_finite("detect_frames (an earlier call on this handle)")
+        arr, keep = self._frame_table(frames)
+        B = len(keep)
+        self.ensure_batch(B)
+        dets, idx, cnt = out if out is not None else self.new_det_buffers(B)
+        _lib.check(_lib.lib().yfv2_detect_frames_u8(self._h, arr, B, float(conf_thres), float(iou_thres), _ptr(dets), _ptr(idx), _ptr(cnt),
+                                                    _stream(self.device)), self._h)
+        return dets, idx, cnt
+
     def batch_statistics(self, dets, cnt, targets, iou_threshold, sync=True):
         """True-positive flags (B, 300) int32 for the padded detections of nms()/detect() against targets (T,6)
         [image index, label, x1, y1, x2, y2] - utils/utils.py:194-230 get_batch_statistics on the device.
