@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define YFV2_ABI_VERSION 7 /* 2: yfv2_stage_info reports external bytes as well; 3: yfv2_train_*, yfv2_sgd_step; 4: yfv2_nonfinite, lanes; 5: yfv2_nonfinite_peek, yfv2_clock_probe_*; 6: yfv2_plan / yfv2_create_ex (the library reads no environment variable); 7: yfv2_debug_post; still 7 with the additive yfv2_frame, yfv2_resize_frames_u8, yfv2_detect_frames_u8 (old callers are unaffected) */
+#define YFV2_ABI_VERSION 7 /* 2: yfv2_stage_info reports external bytes as well; 3: yfv2_train_*, yfv2_sgd_step; 4: yfv2_nonfinite, lanes; 5: yfv2_nonfinite_peek, yfv2_clock_probe_*; 6: yfv2_plan / yfv2_create_ex (the library reads no environment variable); 7: yfv2_debug_post; still 7 with the additive yfv2_frame, yfv2_resize_frames_u8, yfv2_detect_frames_u8 and the additive yfv2_anchor_kmeans, yfv2_kmeans_info, yfv2_debug_kmeans_group (old callers are unaffected) */
 #define YFV2_API __attribute__((visibility("default")))
 #define YFV2_MAX_DET 300 /* utils/utils.py:243 max_det */
 
@@ -243,6 +243,47 @@ YFV2_API int yfv2_batch_statistics_overflow(yfv2_handle h, int32_t* overflowed, 
  * handle's loss workspace grows (one device synchronisation) when T exceeds what earlier calls needed. */
 YFV2_API int yfv2_loss(yfv2_handle h, const float* const out6[6], int32_t B, const float* targets, int32_t T, float* losses,
                        float* const grad6[6], void* stream);
+
+/* ---- anchors from a label set: the first step a user of the reference takes on their own data (genanchors.py) ---- */
+
+typedef struct yfv2_kmeans_info {
+  int32_t struct_size;    /* in: sizeof(yfv2_kmeans_info) of the caller's header (the struct may grow at its end; 0 = this header's) */
+  int32_t iterations;     /* passes run, the terminating one included (the reference's `iter`) */
+  int32_t converged;      /* 1: assignments repeated; 0: stopped at max_iter, on an empty cluster or on bad input */
+  int32_t empty_cluster;  /* -1, or the first cluster index that received no point (the reference divides 0/0 there) */
+  int32_t bad_input;      /* 1: some w or h is not a finite number > 0 */
+} yfv2_kmeans_info;
+
+/* replaces: genanchors.py:67-102 kmeans (+ IOU :17-32, avg_IOU :34-40).  IoU k-means over N label sizes, float64 throughout:
+ * every pass assigns each point to the centroid of smallest 1 - IoU (the reference's four cases, each with its own formula;
+ * first minimum on ties) and, unless the pass ends the loop, replaces every centroid by the mean of its points.
+ *   wh         device (N, 2) float64: w, h of every label (the reference's annotation_dims), 8-byte aligned
+ *   centroids  device (k, 2) float64, 8-byte aligned: in = the initial centroids, out = the final ones in the reference's
+ *              order (unsorted); 1 <= k <= 32
+ *   assign     device (N) int32 or NULL: the cluster of every point under the RETURNED centroids
+ *   avg_iou    device, 1 double: sum over the points of their largest IoU with a returned centroid / N (avg_IOU)
+ *   info       HOST; set info->struct_size before the call
+ * Termination is the reference's (:87-92): the loop ends in the first pass whose assignments equal the previous pass's; that
+ * pass does not move the centroids, and `iterations` counts it.  The loop also ends - still YFV2_OK, info says why - after
+ * pass number max_iter (>= 1), on a cluster that received no point and, in the first pass, on a w or h that is not a finite
+ * number > 0.  DELIBERATE DIFFERENCE: the reference divides 0 / 0 on an empty cluster and carries NaN centroids on; here the
+ * pass that ends the loop, for whatever reason, never moves the centroids: they hold the last completed update, and assign
+ * and avg_iou are those of exactly these centroids (on bad input avg_iou may itself be not a number).
+ * Every output bit is a function of (wh, initial centroids, k) alone - not of the device, the launch geometry or the run:
+ * sums are taken over fixed chunks of 1024 points in a fixed tree, no floating-point atomics.
+ * Work is enqueued on `stream` in groups of passes; like yfv2_batch_statistics, and unlike the hot path, this call WAITS for
+ * the stream after every group and before it returns (it reads the verdict of the passes back).  Argument errors (a NULL
+ * wh / centroids / avg_iou / info, N < 1, k outside 1..32, max_iter < 1, wh or centroids not 8-byte aligned) are
+ * YFV2_ERR_ARG with a message, before anything is enqueued.  Works on any handle, whatever its configuration; needs no
+ * weights; touches nothing of the forward / detect workspace (its own buffer grows - one device synchronisation - when
+ * ceil(N / 1024) * k, or N where assign is NULL, exceeds what earlier calls needed). */
+YFV2_API int yfv2_anchor_kmeans(yfv2_handle h, const double* wh /* device (N,2) */, int64_t N,
+                                double* centroids /* device (k,2): in = initial, out = final, reference order (unsorted) */,
+                                int32_t k, int32_t max_iter, int32_t* assign /* device (N) or NULL */,
+                                double* avg_iou /* device, 1 double */, yfv2_kmeans_info* info /* host */, void* stream);
+/* Test hook: how many passes yfv2_anchor_kmeans enqueues between two looks at the verdict (1..64, default 8).  No output bit
+ * depends on it (tests/test_gpu_anchors.py shows that); it only trades host waits against launches that return at once. */
+YFV2_API int yfv2_debug_kmeans_group(yfv2_handle h, int32_t group);
 
 /* ---- the rest of the training path: one iteration of train.py:96-123 on the device.
  * Parameters, their gradients and the BatchNorm buffers are the CALLER's device tensors in the reference's own layouts and

@@ -8,6 +8,8 @@ anchor decode and class-aware NMS as hand-written HIP kernels behind a C ABI
     non_max_suppression(prediction, conf_thres, iou_thres, classes) utils/utils.py:232
     get_batch_statistics(outputs, targets, iou_threshold, device)   utils/utils.py:194  (evaluation's matching loop)
     compute_loss(preds, targets, cfg, device)                       utils/loss.py:130   (training loss + its gradient w.r.t. the logits)
+    genanchors.kmeans(X, centroids, eps, anchor_file, width, height) genanchors.py:67    (anchor k-means over a label set, + write_anchors_to_file,
+                                                                                         read_label_dims, anchors_for_cfg, main)
 
 There is no CPU / PyTorch fallback: importing works anywhere, running needs the
 built libyfv2.so and an MI355X.
@@ -21,6 +23,7 @@ from .utils.loss import compute_loss  # noqa: F401
 from .utils.optim import SGD  # noqa: F401
 from .weights import export_weights, random_state_dict  # noqa: F401
 from .pipeline import DetectPipeline  # noqa: F401
+from . import genanchors  # noqa: F401
 from .sharded import average_gradients_, detect_sharded, gather_decoded, gather_detections, shard_range  # noqa: F401
 
 

@@ -73,6 +73,12 @@ class Frame(C.Structure):
     _fields_ = [("data", C.c_void_p), ("height", C.c_int32), ("width", C.c_int32), ("row_pitch", C.c_int64)]
 
 
+class KmeansInfo(C.Structure):
+    """yfv2_kmeans_info (include/yfv2.h): what ended yfv2_anchor_kmeans' loop."""
+    _fields_ = [("struct_size", C.c_int32), ("iterations", C.c_int32), ("converged", C.c_int32), ("empty_cluster", C.c_int32),
+                ("bad_input", C.c_int32)]
+
+
 class Yfv2Error(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("libyfv2 error %d: %s" % (code, msg))
@@ -116,6 +122,9 @@ _PROTOTYPES = {
     "yfv2_resize_frames_u8": (C.c_int, [C.c_void_p, C.POINTER(Frame), C.c_int32, C.c_void_p, C.c_void_p]),
     "yfv2_detect_frames_u8": (C.c_int, [C.c_void_p, C.POINTER(Frame), C.c_int32, C.c_float, C.c_double, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p]),
+    "yfv2_anchor_kmeans": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                     C.POINTER(KmeansInfo), C.c_void_p]),
+    "yfv2_debug_kmeans_group": (C.c_int, [C.c_void_p, C.c_int32]),
     "yfv2_debug_plan_dryrun": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "yfv2_debug_plan_dryrun_ex": (C.c_int, [C.c_void_p, C.POINTER(Plan), C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "yfv2_debug_plan_image": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_char_p, C.c_int32, C.c_void_p, C.c_int64]),

@@ -115,6 +115,14 @@ struct yfv2_ctx {
   // counters and float64 sums; grown on demand (a growth waits for the device)
   void* d_loss_ws = nullptr;
   size_t loss_ws_bytes = 0;
+  // anchor k-means (yfv2_anchor_kmeans): chunk partials, the device `done` word and, when the caller wants no assignments, N
+  // int32 of them; grown on demand (a growth waits for the device).  km_word: int32[5] in host-mapped, coherent memory that the
+  // finalise launch publishes its verdict to (allocated by the first call)
+  void* d_km_ws = nullptr;
+  size_t km_ws_bytes = 0;
+  int32_t* h_km_word = nullptr;
+  int32_t* d_km_word = nullptr;
+  int km_group = 8;              // passes enqueued between two looks at km_word (yfv2_debug_kmeans_group); changes no output bit
   void* train = nullptr;         // training state (yfv2_train.hip), created by yfv2_train_bind
   long long* d_trace = nullptr;  // YFV2_TRACE=1: cycle stamps of the last fused s1 launch (debug)
   int trace_step = -1;           // YFV2_TRACE_STEP=i: only launch i of the plan writes stamps (towers: only then)
@@ -2304,6 +2312,8 @@ void yfv2_destroy(yfv2_handle h) {
   if (h->h_nonfinite) (void)hipHostFree(h->h_nonfinite);
   if (h->d_probe) (void)hipFree(h->d_probe);
   if (h->d_loss_ws) (void)hipFree(h->d_loss_ws);
+  if (h->d_km_ws) (void)hipFree(h->d_km_ws);
+  if (h->h_km_word) (void)hipHostFree(h->h_km_word);
   if (h->train) { yfv2_train_release(h->train); h->train = nullptr; }
   if (h->d_params) (void)hipFree(h->d_params);
   for (yfv2_ctx* lane : h->lanes) yfv2_destroy(lane);
@@ -2680,6 +2690,83 @@ int yfv2_loss(yfv2_handle h, const float* const out6[6], int32_t B, const float*
   a.B = B; a.T = T; a.classes = h->cfg.classes;
   yfv2_launch_loss(a, s);
   HIP_TRY(h, hipGetLastError());
+  return YFV2_OK;
+}
+
+// genanchors.py:67-102 on the device (yfv2_anchors.hip).  Passes are enqueued in groups of km_group; a launch that finds the
+// device `done` word set returns at once, so the passes of a group that follow the terminating one change nothing and the
+// group size is invisible in the results.
+int yfv2_anchor_kmeans(yfv2_handle h, const double* wh, int64_t N, double* centroids, int32_t k, int32_t max_iter, int32_t* assign,
+                       double* avg_iou, yfv2_kmeans_info* info, void* stream) {
+  if (!h) return fail(nullptr, YFV2_ERR_ARG, "null handle");
+  if (!wh || !centroids || !avg_iou || !info) return fail(h, YFV2_ERR_ARG, "yfv2_anchor_kmeans: null pointer (wh, centroids, avg_iou and info are required)");
+  if (N < 1) return fail(h, YFV2_ERR_ARG, "yfv2_anchor_kmeans: N must be at least 1");
+  if (N > (int64_t)0x7fffffff * YFV2_KM_CH) return fail(h, YFV2_ERR_ARG, "yfv2_anchor_kmeans: N beyond 2^31 chunks of 1024 points");
+  if (k < 1 || k > YFV2_KM_MAXK) return fail(h, YFV2_ERR_ARG, "yfv2_anchor_kmeans: k must be in 1..32");
+  if (max_iter < 1) return fail(h, YFV2_ERR_ARG, "yfv2_anchor_kmeans: max_iter must be at least 1");
+  if ((reinterpret_cast<uintptr_t>(wh) & 7) != 0 || (reinterpret_cast<uintptr_t>(centroids) & 7) != 0)
+    return fail(h, YFV2_ERR_ARG, "yfv2_anchor_kmeans: wh and centroids must be 8-byte aligned");
+  if ((reinterpret_cast<uintptr_t>(avg_iou) & 7) != 0 || (reinterpret_cast<uintptr_t>(assign) & 3) != 0)
+    return fail(h, YFV2_ERR_ARG, "yfv2_anchor_kmeans: avg_iou must be 8-byte and assign 4-byte aligned");
+  DeviceGuard guard(h->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (!h->h_km_word) {
+    void* hp = nullptr; void* dp = nullptr;
+    if (hipHostMalloc(&hp, 64, hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess || hipHostGetDevicePointer(&dp, hp, 0) != hipSuccess) {
+      if (hp) (void)hipHostFree(hp);
+      return fail(h, YFV2_ERR_DEVICE, "hipHostMalloc(k-means word) failed");
+    }
+    h->h_km_word = static_cast<int32_t*>(hp);
+    h->d_km_word = static_cast<int32_t*>(dp);
+  }
+  const int64_t nch = (N + YFV2_KM_CH - 1) / YFV2_KM_CH;
+  // layout: [done word, 64 bytes][sums (2k + 1) nch doubles][counts k nch ints][flags nch ints][assignments N ints, if the caller has none]
+  const size_t off_sum = 64, off_cnt = off_sum + sizeof(double) * (size_t)(2 * k + 1) * (size_t)nch;
+  const size_t off_flag = off_cnt + sizeof(int) * (size_t)k * (size_t)nch, off_asg = off_flag + sizeof(int) * (size_t)nch;
+  const size_t need = off_asg + (assign ? 0 : sizeof(int32_t) * (size_t)N);
+  if (need > h->km_ws_bytes) {
+    HIP_TRY(h, hipDeviceSynchronize());               // an earlier call's launches may still be using the old block
+    if (h->d_km_ws) { (void)hipFree(h->d_km_ws); h->d_km_ws = nullptr; h->km_ws_bytes = 0; }
+    const size_t cap = need + need / 2;
+    HIP_TRY(h, hipMalloc(&h->d_km_ws, cap));
+    h->km_ws_bytes = cap;
+  }
+  char* ws = static_cast<char*>(h->d_km_ws);
+  KmArgs a{};
+  a.wh = wh; a.N = N; a.centroids = centroids; a.k = k; a.nchunks = nch;
+  a.assign = assign ? assign : reinterpret_cast<int32_t*>(ws + off_asg);
+  a.avg_iou = avg_iou;
+  a.done = reinterpret_cast<int*>(ws);
+  a.part_sum = reinterpret_cast<double*>(ws + off_sum);
+  a.part_cnt = reinterpret_cast<int*>(ws + off_cnt);
+  a.part_flag = reinterpret_cast<int*>(ws + off_flag);
+  a.host_word = h->d_km_word;
+  volatile int32_t* hw = h->h_km_word;   // every earlier call waited for its stream before it returned: nothing is writing the word now
+  for (int i = 0; i < 5; ++i) hw[i] = 0;
+  HIP_TRY(h, hipMemsetAsync(a.done, 0, 64, s));
+  const int group = h->km_group < 1 ? 1 : h->km_group;
+  int pass = 0;
+  while (pass < max_iter) {
+    for (int g = 0; g < group && pass < max_iter; ++g, ++pass) yfv2_launch_km_pass(a, pass, pass == max_iter - 1 ? 1 : 0, s);
+    HIP_TRY(h, hipGetLastError());
+    HIP_TRY(h, hipStreamSynchronize(s));              // a kernel's stores to coherent host memory are visible once it has completed
+    if (hw[0]) break;
+  }
+  if (!hw[0]) return fail(h, YFV2_ERR_DEVICE, "yfv2_anchor_kmeans: the last pass did not publish its verdict");
+  yfv2_kmeans_info out{};
+  out.iterations = hw[1]; out.converged = hw[2]; out.empty_cluster = hw[3]; out.bad_input = hw[4];
+  // (a caller built against a shorter struct gets the fields it has)
+  const size_t n = info->struct_size > 0 && (size_t)info->struct_size < sizeof(yfv2_kmeans_info) ? (size_t)info->struct_size : sizeof(yfv2_kmeans_info);
+  out.struct_size = (int32_t)n;
+  std::memcpy(info, &out, n);
+  return YFV2_OK;
+}
+
+// Test hook: passes enqueued between two host looks (1..64; the default is 8).  Exists so that a test can show that the group
+// size changes no output bit.
+int yfv2_debug_kmeans_group(yfv2_handle h, int32_t group) {
+  if (!h || group < 1 || group > 64) return fail(h, YFV2_ERR_ARG, "yfv2_debug_kmeans_group: group must be in 1..64");
+  h->km_group = group;
   return YFV2_OK;
 }
 

@@ -423,6 +423,24 @@ void yfv2_launch_nms(const NmsArgs& a, hipStream_t s);
 void yfv2_launch_decode_nms(const DecodeArgs& d, const NmsArgs& a, hipStream_t s);   // yfv2_detect: decode + NMS in one launch
 bool yfv2_post_fusable(int classes, int rows);   // ... which exists for up to 96 classes and 2048 decode rows; beyond: two launches
 int yfv2_nms_max_rows();                         // decode rows per image nms_kernel handles (4096)
+// ---- anchor k-means (yfv2_anchors.hip; genanchors.py:67-102): one pass = assign + partial sums, then finalise
+constexpr int YFV2_KM_CH = 1024;    // points per chunk: part of the RESULT's definition (the summation tree), never tuned per device
+constexpr int YFV2_KM_MAXK = 32;
+struct KmArgs {
+  const double* wh;      // (N, 2) label sizes
+  int64_t N;
+  double* centroids;     // (k, 2): read by the assign launch, rewritten by the finalise launch
+  int k;
+  int64_t nchunks;       // ceil(N / YFV2_KM_CH)
+  int32_t* assign;       // (N): the previous pass's assignment in, this pass's out
+  double* avg_iou;       // 1 double
+  double* part_sum;      // [2k + 1][nchunks]: sum of w per cluster, sum of h per cluster, sum of max IoU
+  int* part_cnt;         // [k][nchunks]
+  int* part_flag;        // [nchunks]: bit 0 an assignment changed, bit 1 a w or h is not a finite number > 0
+  int* done;             // device word: set by the finalise launch that ends the loop; every later launch returns at once
+  int32_t* host_word;    // host-mapped int32[5]: done, iterations, converged, empty_cluster, bad_input
+};
+void yfv2_launch_km_pass(const KmArgs& a, int pass, int last, hipStream_t s);
 // ---- measurement: effective shader clock (yfv2_probe.hip)
 struct ClockProbeArgs {
   unsigned long long* out;       // [workgroups][4]: shader cycles, reference ticks, XCC id, (unused)

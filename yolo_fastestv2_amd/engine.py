@@ -315,6 +315,32 @@ class Engine:
                                    gptrs, _stream(self.device)), self._h)
         return losses, grads
 
+    # ---- anchors from a label set: genanchors.py:67-102 on the device -------------------------------------------------
+    def anchor_kmeans(self, wh, centroids, max_iter=1000, want_assign=True):
+        """IoU k-means over label sizes (include/yfv2.h yfv2_anchor_kmeans): ``wh`` (N, 2) and ``centroids`` (k, 2) float64 tensors
+        on this engine's device, ``centroids`` = the initial ones (not modified).  Returns ``(centroids, assign, avg_iou, info)``:
+        the final (k, 2) centroids in the reference's order (unsorted), the (N,) int32 assignments (None unless ``want_assign``),
+        the average IoU as a 0-d float64 device tensor and ``info`` = dict(iterations, converged, empty_cluster, bad_input).
+        Waits for the stream.  Needs no weights and no anchors."""
+        for name, t in (("wh", wh), ("centroids", centroids)):
+            if not torch.is_tensor(t) or t.dtype != torch.float64 or t.device != self.device or t.dim() != 2 or t.shape[1] != 2:
+                raise ValueError("%s must be a float64 (n, 2) tensor on %s" % (name, self.device))
+        wh = wh.contiguous()
+        cent = centroids.contiguous().clone()
+        N, k = int(wh.shape[0]), int(cent.shape[0])
+        assign = torch.empty(max(N, 1), device=self.device, dtype=torch.int32)[:N] if want_assign else None
+        avg = torch.zeros((), device=self.device, dtype=torch.float64)
+        info = _lib.KmeansInfo()
+        info.struct_size = C.sizeof(_lib.KmeansInfo)
+        check(_lib.lib().yfv2_anchor_kmeans(self._h, _ptr(wh) if N else None, N, _ptr(cent) if k else None, k, int(max_iter),
+                                            _ptr(assign) if want_assign else None, _ptr(avg), C.byref(info), _stream(self.device)), self._h)
+        return cent, assign, avg, {"iterations": int(info.iterations), "converged": int(info.converged),
+                                   "empty_cluster": int(info.empty_cluster), "bad_input": int(info.bad_input)}
+
+    def debug_kmeans_group(self, group):
+        """Test hook: passes anchor_kmeans enqueues between two looks at the verdict (1..64, default 8); changes no output bit."""
+        check(_lib.lib().yfv2_debug_kmeans_group(self._h, int(group)), self._h)
+
     # ---- training path (SURVEY.md 8(f) row 3): train.py:96-123 on the device -----------------------------------------
     def train_bind(self, tensors, grads):
         """tensors: name -> fp32 device tensor for every floating-point state_dict entry (weights, biases, BatchNorm running
