@@ -1,5 +1,5 @@
-// yfv2_api.hip - host side of libyfv2.so: handle, weight folding/re-layout, the
-// forward launch plan and the extern "C" entry points declared in include/yfv2.h.
+// yfv2_api.hip - host side of libyfv2.so: handle, the forward launch plan and the
+// extern "C" entry points declared in include/yfv2.h (weight folding / re-layout: yfv2_pack.hip).
 //
 // The forward is a static list of launches ("plan") built once per handle from
 // the model configuration; executing it enqueues the launches on the caller's
@@ -19,6 +19,7 @@
 
 #include "../../include/yfv2.h"
 #include "yfv2_internal.h"
+#include "yfv2_pack.h"
 
 thread_local Yfv2LaunchProbe yfv2_launch_probe;   // (yfv2_internal.h: YFV2_LAUNCH)
 
@@ -26,8 +27,6 @@ namespace {
 
 thread_local std::string g_tls_error;
 thread_local bool g_creating_lane = false;   // yfv2_create called for a child handle of a laned handle (create_lanes)
-
-struct Folded { size_t w = 0, scale = 0, shift = 0; };  // offsets (floats) into the param blob
 
 enum StepKind { STEP_STEM = 0, STEP_PW = 1, STEP_DW = 2, STEP_TOWER = 4, STEP_S2 = 5, STEP_S1PX = 7, STEP_S2PX = 8, STEP_S1CHAIN = 11, STEP_S1POOL = 12 };
 
@@ -170,797 +169,6 @@ struct DeviceGuard {
   ~DeviceGuard() {
     int cur = -1;
     if (prev >= 0 && hipGetDevice(&cur) == hipSuccess && cur != prev) (void)hipSetDevice(prev);
-  }
-};
-
-// ---------------------------------------------------------------------------
-// weights: reference state_dict -> one device blob of kernel-ready parameters
-// ---------------------------------------------------------------------------
-struct WeightPacker {
-  std::map<std::string, const yfv2_tensor_desc*> byname;
-  std::vector<float> blob;
-  std::string missing;
-
-  const float* get(const std::string& name, int64_t numel) {
-    auto it = byname.find(name);
-    if (it == byname.end() || it->second->data == nullptr) {
-      if (missing.empty()) missing = "missing tensor '" + name + "'";
-      return nullptr;
-    }
-    if (it->second->numel != numel) {
-      if (missing.empty())
-        missing = "tensor '" + name + "' has " + std::to_string(it->second->numel) + " elements, expected " +
-                  std::to_string(numel);
-      return nullptr;
-    }
-    return it->second->data;
-  }
-  size_t reserve(size_t n) {  // 16-byte aligned slots
-    size_t off = (blob.size() + 3) & ~size_t(3);
-    blob.resize(off + n, 0.f);
-    return off;
-  }
-  // eval-mode BatchNorm2d -> y = x*scale + shift  (ATen: alpha = gamma*invstd, beta = bias - mean*alpha)
-  bool bn(const std::string& name, int c, Folded* f) {
-    const float* g = get(name + ".weight", c);
-    const float* b = get(name + ".bias", c);
-    const float* m = get(name + ".running_mean", c);
-    const float* v = get(name + ".running_var", c);
-    if (!g || !b || !m || !v) return false;
-    f->scale = reserve(c);
-    f->shift = reserve(c);
-    for (int i = 0; i < c; ++i) {
-      const float invstd = 1.0f / std::sqrt(v[i] + 1e-5f);
-      const float alpha = g[i] * invstd;
-      blob[f->scale + i] = alpha;
-      blob[f->shift + i] = b[i] - m[i] * alpha;
-    }
-    return true;
-  }
-  // pointwise conv weight (co, ci, 1, 1) is already the [M][K] row-major A operand
-  bool pw(const std::string& conv, const std::string& bnname, int co, int ci, Folded* f) {
-    const float* w = get(conv + ".weight", (int64_t)co * ci);
-    if (!w) return false;
-    f->w = reserve((size_t)co * ci);
-    std::memcpy(&blob[f->w], w, sizeof(float) * co * ci);
-    return bn(bnname, co, f);
-  }
-  // depthwise weight (C,1,k,k) -> [k*k][C] so that a channel quad is one 16-byte load
-  bool dw(const std::string& conv, const std::string& bnname, int c, int k, Folded* f) {
-    const float* w = get(conv + ".weight", (int64_t)c * k * k);
-    if (!w) return false;
-    f->w = reserve((size_t)c * k * k);
-    for (int ch = 0; ch < c; ++ch)
-      for (int t = 0; t < k * k; ++t) blob[f->w + (size_t)t * c + ch] = w[(size_t)ch * k * k + t];
-    return bn(bnname, c, f);
-  }
-  // stem weight (24,3,3,3) -> [27 taps][24 co]
-  bool stem(const std::string& conv, const std::string& bnname, Folded* f) {
-    const float* w = get(conv + ".weight", 24 * 27);
-    if (!w) return false;
-    f->w = reserve(24 * 27);
-    for (int co = 0; co < 24; ++co)
-      for (int t = 0; t < 27; ++t) blob[f->w + (size_t)t * 24 + co] = w[co * 27 + t];
-    return bn(bnname, 24, f);
-  }
-  // biased output convs: rows of several (co_i, 72) matrices stacked; scale = 1, shift = bias
-  bool heads(const std::vector<std::pair<std::string, int>>& parts, int ci, Folded* f) {
-    int total = 0;
-    for (auto& p : parts) total += p.second;
-    f->w = reserve((size_t)total * ci);
-    f->scale = reserve(total);
-    f->shift = reserve(total);
-    int row = 0;
-    for (auto& p : parts) {
-      const float* w = get(p.first + ".weight", (int64_t)p.second * ci);
-      const float* b = get(p.first + ".bias", p.second);
-      if (!w || !b) return false;
-      std::memcpy(&blob[f->w + (size_t)row * ci], w, sizeof(float) * p.second * ci);
-      for (int i = 0; i < p.second; ++i) {
-        blob[f->scale + row + i] = 1.0f;
-        blob[f->shift + row + i] = b[i];
-      }
-      row += p.second;
-    }
-    return true;
-  }
-
-  // rows [r0, r0 + n) of one biased output conv (the class head of a model with more classes than one launch's 96 rows)
-  bool heads_range(const std::string& name, int rows_total, int r0, int n, int ci, Folded* f) {
-    const float* w = get(name + ".weight", (int64_t)rows_total * ci);
-    const float* b = get(name + ".bias", rows_total);
-    if (!w || !b || r0 < 0 || r0 + n > rows_total) return false;
-    f->w = reserve((size_t)n * ci); f->scale = reserve(n); f->shift = reserve(n);
-    std::memcpy(&blob[f->w], w + (size_t)r0 * ci, sizeof(float) * n * ci);
-    for (int i = 0; i < n; ++i) { blob[f->scale + i] = 1.0f; blob[f->shift + i] = b[r0 + i]; }
-    return true;
-  }
-
-  // ---- LDS images: the exact, zero-padded block of floats a kernel copies into LDS (or its
-  // registers) in its prologue.  Built from the arrays packed above.
-  // fragment-major filter: frag (mt, s), lane l -> W[16mt + (l&15)][16s + 4(l>>4) .. +3]  (zero outside M x K)
-  static void push_frag(std::vector<float>& im, const float* w, int M, int K, int MT, int KC) {
-    for (int mt = 0; mt < MT; ++mt)
-      for (int s = 0; s < KC; ++s)
-        for (int l = 0; l < 64; ++l)
-          for (int j = 0; j < 4; ++j) {
-            const int r = 16 * mt + (l & 15), c = 16 * s + 4 * (l >> 4) + j;
-            im.push_back((r < M && c < K) ? w[(size_t)r * K + c] : 0.f);
-          }
-  }
-  static void push_rows(std::vector<float>& im, const float* w, int nrows, int C, int KS) {  // [nrows][C] -> [nrows][KS]
-    for (int r = 0; r < nrows; ++r)
-      for (int c = 0; c < KS; ++c) im.push_back(c < C ? w[(size_t)r * C + c] : 0.f);
-  }
-  static void push_vec(std::vector<float>& im, const float* v, int n, int padded) {
-    for (int i = 0; i < padded; ++i) im.push_back((v && i < n) ? v[i] : 0.f);
-  }
-  size_t put(const std::vector<float>& im) {
-    const size_t off = reserve(im.size());
-    std::memcpy(&blob[off], im.data(), sizeof(float) * im.size());
-    return off;
-  }
-  // pw_kernel: filter fragments [MT][K/16][64 lanes][4] (+ an 8-channel tail [MT][64 lanes][2]), scale[MT*16], shift[MT*16]
-  size_t image_pw(const Folded& f, int M, int K, int MT /* the M tiles of the kernel instantiation, yfv2_pw_tiles */, bool presplit = false) {
-    std::vector<float> im;
-    build_pw(im, f, M, K, MT, presplit);
-    return put(im);
-  }
-  // PW_DUAL: two convs on the same input as ONE image of 2 MT output tiles - fragments of the first, fragments of the second (each filter
-  // with its own power-of-two scale), then scale[2 MT 16], shift[2 MT 16]
-  size_t image_pw_dual(const Folded& f0, const Folded& f1, int M, int K, int MT) {
-    std::vector<float> i0, i1, im;
-    build_pw(i0, f0, M, K, MT, true);
-    build_pw(i1, f1, M, K, MT, true);
-    const size_t fr = i0.size() - 2 * (size_t)MT * 16, r = (size_t)MT * 16;
-    im.insert(im.end(), i0.begin(), i0.begin() + fr);
-    im.insert(im.end(), i1.begin(), i1.begin() + fr);
-    im.insert(im.end(), i0.begin() + fr, i0.begin() + fr + r);
-    im.insert(im.end(), i1.begin() + fr, i1.begin() + fr + r);
-    im.insert(im.end(), i0.begin() + fr + r, i0.end());
-    im.insert(im.end(), i1.begin() + fr + r, i1.end());
-    return put(im);
-  }
-  void build_pw(std::vector<float>& im, const Folded& f, int M, int K, int MT, bool presplit) {
-    const int rows = MT * 16, K16 = K / 16;
-    int sw = 0;
-    if (presplit) {
-      // pw_kernel<.., PRE>: the filter x 2^sw as two fp16 terms, [mt][chunk pair][term][64 lanes][4 dwords]: dwords 0,1 = K
-      // positions 4g..4g+3 of the pair's first chunk, 2,3 = of its second (one A operand of v_mfma_f32_16x16x32_f16)
-      float mx = 0.f;
-      for (int i = 0; i < M * K; ++i) mx = std::fmax(mx, std::fabs(blob[f.w + i]));
-      sw = pow2_for(mx);
-      for (int mt = 0; mt < MT; ++mt)
-        for (int sp = 0; sp < K16 / 2; ++sp)
-          for (int term = 0; term < 2; ++term)
-            for (int l = 0; l < 64; ++l)
-              for (int d = 0; d < 4; ++d) {
-                unsigned packed = 0;
-                for (int e = 0; e < 2; ++e) {
-                  const int r = 16 * mt + (l & 15), c = 16 * (2 * sp + (d >> 1)) + 4 * (l >> 4) + 2 * (d & 1) + e;
-                  const float v = (r < M && c < K) ? std::ldexp(blob[f.w + (size_t)r * K + c], sw) : 0.f;
-                  const float h1 = rn_f16(v);
-                  packed |= f16_bits(term == 0 ? h1 : v - h1) << (16 * e);
-                }
-                float fb; std::memcpy(&fb, &packed, 4);
-                im.push_back(fb);
-              }
-    } else {
-      push_frag(im, &blob[f.w], M, K, MT, K16);
-    }
-    if (K % 16)
-      for (int mt = 0; mt < MT; ++mt)
-        for (int l = 0; l < 64; ++l)
-          for (int j = 0; j < 2; ++j) {
-            const int r = 16 * mt + (l & 15), c = 16 * K16 + 2 * (l >> 4) + j;
-            im.push_back((r < M && c < K) ? blob[f.w + (size_t)r * K + c] : 0.f);
-          }
-    if (presplit) for (int i = 0; i < rows; ++i) im.push_back(i < M ? std::ldexp(blob[f.scale + i], -(sw + 4)) : 0.f);   // the accumulators carry 2^(sw+4): undone exactly inside the BN scale
-    else push_vec(im, &blob[f.scale], M, rows);
-    push_vec(im, &blob[f.shift], M, rows);
-  }
-  // columns [c0, c0 + n) of a folded conv's filter as a conv of its own (same BN scale / shift)
-  Folded pw_columns(const Folded& f, int co, int ci, int c0, int n) {
-    Folded g = f;
-    g.w = reserve((size_t)co * n);
-    for (int r = 0; r < co; ++r)
-      for (int k = 0; k < n; ++k) blob[g.w + (size_t)r * n + k] = blob[f.w + (size_t)r * ci + c0 + k];
-    return g;
-  }
-  // block_s1chain6_kernel: a 48x48 filter as [mt (3)][six 16-byte operands][64 lanes][4 dwords]: hi / mid / lo quads of the
-  // chunk PAIR (chunks 0, 1: the 32 k-slots of one bf16 MFMA), then {hi,hi} {mid,mid} {hi,lo} of the single chunk 2 (the
-  // register form of yfv2_split_a); every dword = two truncated bf16, low half first
-  // block_s1chain6_kernel: a 48x48 filter x 2^sw as two fp16 terms (w1 = RN16, w2 = RN16 of the rest), [mt (3)][three 16-byte
-  // operands][64 lanes][4 dwords]: {w1 chunk 0, w1 chunk 1}, {w2 chunk 0, w2 chunk 1}, {w1 chunk 2, w2 chunk 2}; a lane's two
-  // dwords of a chunk = K positions 4g..4g+3.  Returns sw.
-  static int push_chain6_filter(std::vector<float>& im, const float* w /* [48][48] */) {
-    float mx = 0.f;
-    for (int i = 0; i < 48 * 48; ++i) mx = std::fmax(mx, std::fabs(w[i]));
-    const int sw = pow2_for(mx);
-    auto term = [&](int r, int c, int t) {               // packed (value c, value c + 1) of row r, fp16 term t
-      unsigned u = 0;
-      for (int e = 0; e < 2; ++e) {
-        const float v = std::ldexp(w[(size_t)r * 48 + c + e], sw), h1 = rn_f16(v);
-        u |= f16_bits(t == 0 ? h1 : v - h1) << (16 * e);
-      }
-      return u;
-    };
-    auto put_u = [&](unsigned u) { float f; std::memcpy(&f, &u, 4); im.push_back(f); };
-    for (int mt = 0; mt < 3; ++mt)
-      for (int op = 0; op < 3; ++op)
-        for (int l = 0; l < 64; ++l)
-          for (int d = 0; d < 4; ++d) {
-            const int r = 16 * mt + (l & 15), kq = 4 * (l >> 4) + 2 * (d & 1);
-            if (op < 2) put_u(term(r, 16 * (d >> 1) + kq, op));   // the pair: dwords 0, 1 = chunk 0, dwords 2, 3 = chunk 1
-            else put_u(term(r, 32 + kq, d >> 1));                 // chunk 2: dwords 0, 1 = first term, 2, 3 = second
-          }
-    return sw;
-  }
-  void append_s1_bf6(std::vector<float>& im, const Folded& f1, const Folded& fd, const Folded& f2) {
-    const int sw1 = push_chain6_filter(im, &blob[f1.w]);
-    const int sw2 = push_chain6_filter(im, &blob[f2.w]);
-    push_rows(im, &blob[fd.w], 9, 48, 48);
-    for (const Folded* f : {&f1, &fd, &f2}) {
-      const int un = f == &f1 ? sw1 + 4 : (f == &f2 ? sw2 + 4 : 0);   // the pointwise accumulators carry 2^(sw+4): undone exactly inside the BN scale
-      for (int i = 0; i < 48; ++i) im.push_back(std::ldexp(blob[f->scale + i], -un));
-      push_vec(im, &blob[f->shift], 48, 48);
-    }
-  }
-  // block_s2_kernel<CIN>: W1 | W2 | Wproj | main dw taps | proj dw taps | sc1 sh1 scd shd sc2 sh2 scpd shpd scpp shpp
-  size_t image_s2(const Folded& f1, const Folded& fd, const Folded& f2, const Folded& fpd, const Folded& fpp, int cin) {
-    const int KC = (cin + 15) / 16, KS = 16 * KC;
-    std::vector<float> im;
-    push_frag(im, &blob[f1.w], cin, cin, KC, KC);
-    push_frag(im, &blob[f2.w], cin, cin, KC, KC);
-    push_frag(im, &blob[fpp.w], cin, cin, KC, KC);
-    push_rows(im, &blob[fd.w], 9, cin, KS);
-    push_rows(im, &blob[fpd.w], 9, cin, KS);
-    for (const Folded* f : {&f1, &fd, &f2, &fpd, &fpp}) { push_vec(im, &blob[f->scale], cin, KS); push_vec(im, &blob[f->shift], cin, KS); }
-    return put(im);
-  }
-  // block_s2w_kernel (96 channels): W1 pre-split for bf16x6 | W2 | Wproj | taps | taps | BN vectors as image_s2.
-  // W1 pre-split: an fp32 weight is the exact sum of three truncated bf16 terms (hi, mid, lo).  Per (tile of 16 output
-  // channels mt, PAIR of 16-channel chunks sp, term) one 16-byte lane quad: {term(w0),term(w1)} {term(w2),term(w3)} of chunk
-  // 2sp, then the same of chunk 2sp+1 - the A operand of one v_mfma_f32_16x16x32_bf16 whose 32 k-slots are the two chunks.
-  static unsigned bf16_trunc_bits(float v) { unsigned u; std::memcpy(&u, &v, 4); return u >> 16; }
-  static float bf16_trunc(float v) { unsigned u; std::memcpy(&u, &v, 4); u &= 0xffff0000u; float r; std::memcpy(&r, &u, 4); return r; }
-  // the same layout from an element accessor (sub-matrices): MT output tiles x KP chunk pairs, el(row, column)
-  template <class Fn>
-  static void push_split3_fn(std::vector<float>& im, int MT, int KP, Fn el) {
-    for (int mt = 0; mt < MT; ++mt)
-      for (int sp = 0; sp < KP; ++sp)
-        for (int term = 0; term < 3; ++term)
-          for (int l = 0; l < 64; ++l)
-            for (int d = 0; d < 4; ++d) {
-              const int r = 16 * mt + (l & 15), c = 16 * (2 * sp + (d >> 1)) + 4 * (l >> 4) + 2 * (d & 1);
-              unsigned packed = 0;
-              for (int e = 0; e < 2; ++e) {
-                float v = el(r, c + e);
-                for (int t = 0; t < term; ++t) v = v - bf16_trunc(v);   // exact in fp32
-                packed |= bf16_trunc_bits(v) << (16 * e);
-              }
-              float f; std::memcpy(&f, &packed, 4);
-              im.push_back(f);
-            }
-  }
-  // fp16x3 form of the same layout: [mt][chunk pair][term 2][64 lanes][4 dwords of fp16 pairs], el(row, column) already
-  // carrying its power of two
-  template <class Fn>
-  static void push_h2_fn(std::vector<float>& im, int MT, int KP, Fn el) {
-    for (int mt = 0; mt < MT; ++mt)
-      for (int sp = 0; sp < KP; ++sp)
-        for (int term = 0; term < 2; ++term)
-          for (int l = 0; l < 64; ++l)
-            for (int d = 0; d < 4; ++d) {
-              const int r = 16 * mt + (l & 15), c = 16 * (2 * sp + (d >> 1)) + 4 * (l >> 4) + 2 * (d & 1);
-              unsigned packed = 0;
-              for (int e = 0; e < 2; ++e) {
-                const float v = el(r, c + e), h1 = rn_f16(v);
-                packed |= f16_bits(term == 0 ? h1 : v - h1) << (16 * e);
-              }
-              float f; std::memcpy(&f, &packed, 4);
-              im.push_back(f);
-            }
-  }
-  static void push_frag_split3(std::vector<float>& im, const float* w, int M, int K, int MT, int KC) {
-    for (int mt = 0; mt < MT; ++mt)
-      for (int sp = 0; sp < KC / 2; ++sp)
-        for (int term = 0; term < 3; ++term)
-          for (int l = 0; l < 64; ++l)
-            for (int d = 0; d < 4; ++d) {
-              const int s = 2 * sp + (d >> 1);
-              const int r = 16 * mt + (l & 15), c = 16 * s + 4 * (l >> 4) + 2 * (d & 1);
-              unsigned packed = 0;
-              for (int e = 0; e < 2; ++e) {
-                float v = (r < M && c + e < K) ? w[(size_t)r * K + c + e] : 0.f;
-                for (int t = 0; t < term; ++t) v = v - bf16_trunc(v);   // exact in fp32
-                packed |= bf16_trunc_bits(v) << (16 * e);
-              }
-              float f; std::memcpy(&f, &packed, 4);
-              im.push_back(f);
-            }
-  }
-  size_t image_s2w(const Folded& f1, const Folded& fd, const Folded& f2, const Folded& fpd, const Folded& fpp) {
-    const int cin = 96, KC = 6, KS = 96;
-    std::vector<float> im;
-    push_frag_split3(im, &blob[f1.w], cin, cin, KC, KC);
-    push_frag(im, &blob[f2.w], cin, cin, KC, KC);
-    push_frag(im, &blob[fpp.w], cin, cin, KC, KC);
-    push_rows(im, &blob[fd.w], 9, cin, KS);
-    push_rows(im, &blob[fpd.w], 9, cin, KS);
-    for (const Folded* f : {&f1, &fd, &f2, &fpd, &fpp}) { push_vec(im, &blob[f->scale], cin, KS); push_vec(im, &blob[f->shift], cin, KS); }
-    return put(im);
-  }
-  // tower kernels: pw [80][84] | output conv [mh16][84] | dw taps [25][80] | scd shd scp shp bias [5][96]
-  size_t image_tower(const Folded& fd, const Folded& fp, const Folded* fh, int mh) {
-    std::vector<float> im;
-    push_frag(im, &blob[fp.w], 72, 72, 5, 5);
-    const int mh_tiles = fh ? ((mh + 15) / 16 <= 1 ? 1 : 6) : 0;  // kernels are instantiated for 1 or 6 output tiles
-    if (fh) push_frag(im, &blob[fh->w], mh, 72, mh_tiles, 5);
-    push_rows(im, &blob[fd.w], 25, 72, 80);
-    push_vec(im, &blob[fd.scale], 72, 96); push_vec(im, &blob[fd.shift], 72, 96);
-    push_vec(im, &blob[fp.scale], 72, 96); push_vec(im, &blob[fp.shift], 72, 96);
-    push_vec(im, fh ? &blob[fh->shift] : nullptr, mh, 96);
-    return put(im);
-  }
-  // towerh_kernel (yfv2_towerh.hip): WP [5][5][64][4 dwords of fp16 pairs: term 1, term 1, term 2, term 2] | CS [4][96] |
-  // WH [mh tiles][5][64][4] | TAPS [5][4][27][4] + 16
-  template <class Fn>
-  static void push_a16(std::vector<float>& im, Fn el, int MT) {   // el(row, col) already scaled
-    for (int mt = 0; mt < MT; ++mt)
-      for (int s = 0; s < 5; ++s)
-        for (int l = 0; l < 64; ++l) {
-          unsigned dw[4] = {0, 0, 0, 0};
-          for (int e = 0; e < 4; ++e) {
-            const float v = el(16 * mt + (l & 15), 16 * s + 4 * (l >> 4) + e);
-            const float h1 = rn_f16(v);
-            dw[e >> 1] |= f16_bits(h1) << (16 * (e & 1));
-            dw[2 + (e >> 1)] |= f16_bits(v - h1) << (16 * (e & 1));
-          }
-          for (int d = 0; d < 4; ++d) { float fb; std::memcpy(&fb, &dw[d], 4); im.push_back(fb); }
-        }
-  }
-  size_t image_towerh(const Folded& fd, const Folded& fp, const Folded* fh, int mh, int mh_tiles) {
-    std::vector<float> im;
-    const float* wpw = &blob[fp.w];
-    float mp = 0.f, mhd = 0.f;
-    for (int i = 0; i < 72 * 72; ++i) mp = std::fmax(mp, std::fabs(wpw[i]));
-    const int sw = pow2_for(mp);
-    push_a16(im, [&](int r, int c) { return (r < 72 && c < 72) ? std::ldexp(wpw[(size_t)r * 72 + c], sw) : 0.f; }, 5);
-    // A half that ends in an output conv: pointwise conv, its BatchNorm and the biased output conv are three linear maps in a row
-    // (fpn.py:16-17,23-24 - no activation behind the block's last BN; detector.py:25-31), so the kernels apply their PRODUCT to the
-    // depthwise result: M = Wh diag(scale) Wp (mh x 72), bias = Wh shift + b, both formed here in double and rounded once - closer
-    // to the exact value than the reference's own two fp32 steps.  (The 72 x 72 filter above stays in the image: a launch has one
-    // LDS layout for all its jobs, and the halves WITHOUT an output conv use it.)
-    std::vector<float> mw, mb;
-    int swh = 0;
-    if (fh) {
-      mw.assign((size_t)mh * 72, 0.f); mb.assign((size_t)mh, 0.f);
-      for (int o = 0; o < mh; ++o) {
-        double bacc = blob[fh->shift + o];
-        for (int k = 0; k < 72; ++k) bacc += (double)blob[fh->w + (size_t)o * 72 + k] * (double)blob[fp.shift + k];
-        mb[o] = (float)bacc;
-        for (int c = 0; c < 72; ++c) {
-          double acc = 0.0;
-          for (int k = 0; k < 72; ++k) acc += (double)blob[fh->w + (size_t)o * 72 + k] * (double)blob[fp.scale + k] * (double)wpw[(size_t)k * 72 + c];
-          mw[(size_t)o * 72 + c] = (float)acc;
-          mhd = std::fmax(mhd, std::fabs((float)acc));
-        }
-      }
-      swh = pow2_for(mhd);
-    }
-    for (int c = 0; c < 96; ++c) im.push_back(c < 72 ? std::ldexp(blob[fp.scale + c], -(sw + 4)) : 0.f);
-    push_vec(im, &blob[fp.shift], 72, 96);
-    push_vec(im, fh ? mb.data() : nullptr, mh, 96);
-    for (int c = 0; c < 96; ++c) im.push_back(c == 0 ? std::ldexp(1.0f, -(swh + 4)) : 0.f);
-    push_a16(im, [&](int r, int c) { return (fh && r < mh && c < 72) ? std::ldexp(mw[(size_t)r * 72 + c], swh) : 0.f; }, mh_tiles);   // zero tiles where a job has no (or a narrower) output conv: one LDS layout per launch
-    for (int s = 0; s < 5; ++s)
-      for (int q = 0; q < 4; ++q)
-        for (int t = 0; t < 27; ++t)
-          for (int e = 0; e < 4; ++e) {
-            const int ch = 16 * s + 4 * q + e;
-            im.push_back(ch >= 72 ? 0.f : t < 25 ? blob[fd.w + (size_t)t * 72 + ch] : 16.0f * (t == 25 ? blob[fd.scale + ch] : blob[fd.shift + ch]));   // x 2^4: exact
-          }
-    for (int i = 0; i < 16; ++i) im.push_back(0.f);   // the scalar-cache warm-up reads whole 64-byte lines
-    // towerp_kernel's table (round 6): the same numbers per channel PAIR, one 256-byte record per (chunk, pair) = what a wave's
-    // depthwise unit pulls into 54 SGPRs: floats 2 t + e = tap t of channel 16 s + 2 pair + e, 50 + e = BN scale x 16, 52 + e = BN shift x 16
-    for (int s = 0; s < 5; ++s)
-      for (int pr = 0; pr < 8; ++pr)
-        for (int i = 0; i < 64; ++i) {
-          const int t = i >> 1, ch = 16 * s + 2 * pr + (i & 1);
-          im.push_back((ch >= 72 || t > 26) ? 0.f : t < 25 ? blob[fd.w + (size_t)t * 72 + ch] : 16.0f * (t == 25 ? blob[fd.scale + ch] : blob[fd.shift + ch]));
-        }
-    return put(im);
-  }
-  // ---- stage 2 in lane-per-pixel form (yfv2_stage2.hip)
-  // pointwise 24->24 in the 4x4x1 broadcast form [10][64]: register q, lane 4j+i holds entry (m, k) of
-  // output position 4m+i, (m*25 + k) = 16q + j; k = 24 is the bias column.  row(n) / col(k) give the
-  // filter row / column of output position n / input position k.
-  template <class RowFn, class ColFn, class BiasFn>
-  static void push_pw24_bcast(std::vector<float>& im, RowFn row, ColFn col, BiasFn bias, const float* w, const float* scale) {
-    const size_t base = im.size();
-    im.resize(base + 640, 0.f);
-    for (int m = 0; m < 6; ++m)
-      for (int i = 0; i < 4; ++i) {
-        const int r = row(4 * m + i);
-        for (int k = 0; k < 25; ++k) {
-          const int idx = m * 25 + k;
-          im[base + (idx >> 4) * 64 + 4 * (idx & 15) + i] = k < 24 ? w[(size_t)r * 24 + col(k)] * scale[r] : bias(r);
-        }
-      }
-  }
-  // s1px_kernel image: w1q | w2q | depthwise taps [54][64] (lane&3 = k holds scaled tap 4q+k, flat index c*9 + dy*3 + dx).
-  // order[n] = which branch-input channel sits at input position n = which branch-output channel goes to output position n
-  size_t image_s1px(const Folded& f1, const Folded& fd, const Folded& f2, const int (&order)[24]) {
-    std::vector<float> im;
-    const float* w1 = &blob[f1.w]; const float* w2 = &blob[f2.w]; const float* wd = &blob[fd.w];
-    const float* sc1 = &blob[f1.scale]; const float* sh1 = &blob[f1.shift];
-    const float* scd = &blob[fd.scale]; const float* shd = &blob[fd.shift];
-    const float* sc2 = &blob[f2.scale]; const float* sh2 = &blob[f2.shift];
-    push_pw24_bcast(im, [](int n) { return n; }, [&](int k) { return order[k]; }, [&](int r) { return sh1[r]; }, w1, sc1);
-    // the depthwise BN shift goes through pw2 (linear): bias2 = shift2 + scale2 * (W2 . shiftd)
-    push_pw24_bcast(im, [&](int n) { return order[n]; }, [](int k) { return k; },
-                    [&](int r) { double acc = 0; for (int k = 0; k < 24; ++k) acc += (double)w2[(size_t)r * 24 + k] * shd[k]; return sh2[r] + sc2[r] * (float)acc; },
-                    w2, sc2);
-    push_taps_quad(im, wd, scd);
-    return put(im);
-  }
-  // ---- s1h_kernel (yfv2_stage2h.hip): the same block with both pointwise convs as two-term fp16 operands in the A-operand
-  // order of v_mfma_f32_16x16x32_f16.  Lane (l, g = lane >> 4) owns channel POSITIONS npos(g, j), j = 0..7: 4g + j for j < 4
-  // (channel tile 0), 16 + 4g + (j - 4) for j >= 4 and g < 2 (tile 1), none otherwise - as K slots of the B operand and as
-  // rows 4g..4g+3 of the D tiles alike.  Position n = pair n / 2, element n & 1 of the 12 branch pairs; order[] as image_s1px.
-  static int s1h_npos(int g, int j) { return j < 4 ? 4 * g + j : (g < 2 ? 16 + 4 * g + (j - 4) : -1); }
-  static int pow2_for(float mx) {   // sw with mx * 2^sw in (2^13, 2^14]
-    if (!(mx > 0.f) || !std::isfinite(mx)) return 0;
-    int sw = 14 - (int)std::ceil(std::log2(mx));
-    return sw > 24 ? 24 : (sw < -14 ? -14 : sw);
-  }
-  // el(row position, K position) -> [tile 2][term 2][64][4 dwords] of fp16 pairs
-  template <class Fn>
-  static void push_h3_filter(std::vector<float>& im, Fn el) {
-    for (int t = 0; t < 2; ++t)
-      for (int term = 0; term < 2; ++term)
-        for (int l = 0; l < 64; ++l)
-          for (int d = 0; d < 4; ++d) {
-            unsigned packed = 0;
-            for (int e = 0; e < 2; ++e) {
-              const int n = s1h_npos(l >> 4, 2 * d + e), r = 16 * t + (l & 15);
-              const float v = (n >= 0 && r < 24) ? el(r, n) : 0.f;
-              const float h1 = rn_f16(v);
-              packed |= f16_bits(term == 0 ? h1 : v - h1) << (16 * e);
-            }
-            float fb; std::memcpy(&fb, &packed, 4);
-            im.push_back(fb);
-          }
-  }
-  size_t image_s1h(const Folded& f1, const Folded& fd, const Folded& f2, const int (&order)[24], const int (&src_off)[12], const int (&dst_off)[12]) {
-    const float* w1 = &blob[f1.w]; const float* w2 = &blob[f2.w]; const float* wd = &blob[fd.w];
-    const float* sc1 = &blob[f1.scale]; const float* sh1 = &blob[f1.shift];
-    const float* scd = &blob[fd.scale]; const float* shd = &blob[fd.shift];
-    const float* sc2 = &blob[f2.scale]; const float* sh2 = &blob[f2.shift];
-    auto e1 = [&](int r, int n) { return w1[(size_t)r * 24 + order[n]] * sc1[r]; };                 // pw1: natural output channel r, input position n
-    auto e2 = [&](int r, int n) { return w2[(size_t)order[r] * 24 + n] * sc2[order[r]]; };          // pw2: output position r, natural input channel n
-    float m1 = 0.f, m2 = 0.f;
-    for (int r = 0; r < 24; ++r)
-      for (int n = 0; n < 24; ++n) { m1 = std::fmax(m1, std::fabs(e1(r, n))); m2 = std::fmax(m2, std::fabs(e2(r, n))); }
-    const int sw1 = pow2_for(m1), sw2 = pow2_for(m2);
-    std::vector<float> im;
-    push_h3_filter(im, [&](int r, int n) { return std::ldexp(e1(r, n), sw1); });
-    push_h3_filter(im, [&](int r, int n) { return std::ldexp(e2(r, n), sw2); });
-    // taps [18][64]: lane (l, g), register q holds tap f = 4q + (l & 3) = cs * 9 + dy * 3 + dx of the lane's channel slot cs;
-    // they see relu(pw1) * 2^(sw1+4) and must hand pw2 its input times 2^4: BN scale * 2^-sw1
-    for (int q = 0; q < 18; ++q)
-      for (int l = 0; l < 64; ++l) {
-        const int f = 4 * q + (l & 3), cs = f / 9, tt = f % 9, n = s1h_npos(l >> 4, cs);
-        im.push_back(n >= 0 ? std::ldexp(wd[(size_t)tt * 24 + n] * scd[n], -sw1) : 0.f);
-      }
-    for (int n = 0; n < 32; ++n) im.push_back(n < 24 ? std::ldexp(sh1[n], sw1 + 4) : 0.f);
-    for (int n = 0; n < 32; ++n) {   // the depthwise BN shift goes through pw2 (linear): bias2 = shift2 + scale2 * (W2 . shiftd)
-      float v = 0.f;
-      if (n < 24) {
-        const int r = order[n];
-        double acc = 0; for (int k = 0; k < 24; ++k) acc += (double)w2[(size_t)r * 24 + k] * shd[k];
-        v = std::ldexp(sh2[r] + sc2[r] * (float)acc, sw2 + 4);
-      }
-      im.push_back(v);
-    }
-    im.push_back(std::ldexp(1.0f, -(sw2 + 4)));
-    while (im.size() < 3272) im.push_back(0.f);
-    for (int which = 0; which < 2; ++which)           // per-lane byte offsets of the lane's four pairs: read from / written to
-      for (int k = 0; k < 4; ++k)
-        for (int l = 0; l < 64; ++l) {
-          const int g = l >> 4, kk = k < 2 ? 2 * g + k : (g < 2 ? 8 + 2 * g + (k - 2) : -1);
-          const int v = kk < 0 ? (int)0x80000000 : (which ? dst_off[kk] : src_off[kk]);
-          float fb; std::memcpy(&fb, &v, 4);
-          im.push_back(fb);
-        }
-    return put(im);
-  }
-  // s2h_kernel (yfv2_stage2h.hip): stage2.0 with both branches in one wave.  Input positions = natural channels (the stem's
-  // pair planes); output position r of a branch = its channel pos[r] (pos[][] of PlanBuilder::s2px_block: 0..15 = the branch's
-  // eight whole pairs, 16..23 = its halves of the eight pairs that mix a proj and a main channel).
-  static void push_quad_taps(std::vector<float>& im, const float* wd, const float* scd, int shift_pow2) {
-    for (int q = 0; q < 18; ++q)
-      for (int l = 0; l < 64; ++l) {
-        const int f = 4 * q + (l & 3), cs = f / 9, tt = f % 9, n = s1h_npos(l >> 4, cs);
-        im.push_back(n >= 0 ? std::ldexp(wd[(size_t)tt * 24 + n] * scd[n], shift_pow2) : 0.f);
-      }
-  }
-  size_t image_s2h(const Folded& f1, const Folded& fd, const Folded& f2, const Folded& fpd, const Folded& fpp, const int (&pos)[2][24],
-                   const int (&st2_off)[2][8], const int (&st1_off)[2][8], int IH, int IW) {
-    const float* w1 = &blob[f1.w]; const float* w2 = &blob[f2.w]; const float* wq = &blob[fpp.w];
-    const float* sc1 = &blob[f1.scale]; const float* sc2 = &blob[f2.scale]; const float* scq = &blob[fpp.scale];
-    auto e1 = [&](int r, int n) { return w1[(size_t)r * 24 + n] * sc1[r]; };
-    auto ep = [&](int r, int n) { return wq[(size_t)pos[0][r] * 24 + n] * scq[pos[0][r]]; };
-    auto e2 = [&](int r, int n) { return w2[(size_t)pos[1][r] * 24 + n] * sc2[pos[1][r]]; };
-    float m1 = 0.f, mp = 0.f, m2 = 0.f;
-    for (int r = 0; r < 24; ++r)
-      for (int n = 0; n < 24; ++n) { m1 = std::fmax(m1, std::fabs(e1(r, n))); mp = std::fmax(mp, std::fabs(ep(r, n))); m2 = std::fmax(m2, std::fabs(e2(r, n))); }
-    const int sw1 = pow2_for(m1), swp = pow2_for(mp), sw2 = pow2_for(m2);
-    std::vector<float> im;
-    push_h3_filter(im, [&](int r, int n) { return std::ldexp(e1(r, n), sw1); });
-    push_h3_filter(im, [&](int r, int n) { return std::ldexp(ep(r, n), swp); });
-    push_h3_filter(im, [&](int r, int n) { return std::ldexp(e2(r, n), sw2); });
-    push_quad_taps(im, &blob[fd.w], &blob[fd.scale], -sw1);     // main: sees relu(pw1) * 2^(sw1+4), hands pw2 its input * 2^4
-    push_quad_taps(im, &blob[fpd.w], &blob[fpd.scale], 0);      // proj: sees the raw input * 2^4
-    for (int n = 0; n < 32; ++n) im.push_back(n < 24 ? std::ldexp(blob[f1.shift + n], sw1 + 4) : 0.f);
-    auto bias = [&](const float* w, const Folded& fp_, const Folded& fdw, int c) {   // shift + scale * (W . depthwise shift)
-      double acc = 0; for (int k = 0; k < 24; ++k) acc += (double)w[(size_t)c * 24 + k] * blob[fdw.shift + k];
-      return blob[fp_.shift + c] + blob[fp_.scale + c] * (float)acc;
-    };
-    for (int n = 0; n < 32; ++n) im.push_back(n < 24 ? std::ldexp(bias(wq, fpp, fpd, pos[0][n]), swp + 4) : 0.f);
-    for (int n = 0; n < 32; ++n) im.push_back(n < 24 ? std::ldexp(bias(w2, f2, fd, pos[1][n]), sw2 + 4) : 0.f);
-    im.push_back(std::ldexp(1.0f, -(swp + 4)));
-    im.push_back(std::ldexp(1.0f, -(sw2 + 4)));
-    while (im.size() < 5480) im.push_back(0.f);
-    auto put_i = [&](int v) { float fb; std::memcpy(&fb, &v, 4); im.push_back(fb); };
-    const int NONE = (int)0x80000000;
-    for (int k = 0; k < 4; ++k)                      // loads: the lane's four input pair planes
-      for (int l = 0; l < 64; ++l) {
-        const int g = l >> 4, kk = k < 2 ? 2 * g + k : (g < 2 ? 8 + 2 * g + (k - 2) : -1);
-        put_i(kk < 0 ? NONE : kk * IH * IW * 8);
-      }
-    for (int k = 0; k < 8; ++k)                      // stores: proj whole pairs (2), main whole pairs (2), mixed pairs (4)
-      for (int l = 0; l < 64; ++l) {
-        const int g = l >> 4;
-        int v = NONE;
-        if (k < 2) v = st2_off[0][2 * g + k];
-        else if (k < 4) v = st2_off[1][2 * g + (k - 2)];
-        else if (g < 2) v = st1_off[0][4 * g + (k - 4)];   // the pair's base: proj sits in element 0, main in element 1
-        put_i(v);
-      }
-    return put(im);
-  }
-  // s3h_kernel (yfv2_stage2h.hip): stage3.0 (48 -> 96) in the same form.  Lane (l, g) owns positions n48(g, q) = 16 (q / 4) +
-  // 4g + q % 4, q = 0..11; as K slots: chunk q / 8, slot q % 8.  Input positions = stage 2's pair-plane slots (the Folded
-  // objects passed in already have their input columns / depthwise channels in slot order), outputs natural.
-  static int n48(int g, int q) { return 16 * (q >> 2) + 4 * g + (q & 3); }
-  size_t image_s3h(const Folded& f1, const Folded& fd, const Folded& f2, const Folded& fpd, const Folded& fpp, unsigned pp_mask,
-                   long long pp_bufstride, int IH, int IW) {
-    const Folded* fs[3] = {&f1, &fpp, &f2};
-    int sw[3];
-    std::vector<float> im;
-    for (int f = 0; f < 3; ++f) {
-      const float* w = &blob[fs[f]->w]; const float* sc = &blob[fs[f]->scale];
-      float mx = 0.f;
-      for (int r = 0; r < 48; ++r)
-        for (int n = 0; n < 48; ++n) mx = std::fmax(mx, std::fabs(w[(size_t)r * 48 + n] * sc[r]));
-      sw[f] = pow2_for(mx);
-      for (int t = 0; t < 3; ++t)
-        for (int c = 0; c < 2; ++c)
-          for (int term = 0; term < 2; ++term)
-            for (int l = 0; l < 64; ++l)
-              for (int d = 0; d < 4; ++d) {
-                unsigned packed = 0;
-                for (int e = 0; e < 2; ++e) {
-                  const int q = 8 * c + 2 * d + e, r = 16 * t + (l & 15);
-                  const float v = q < 12 ? std::ldexp(w[(size_t)r * 48 + n48(l >> 4, q)] * sc[r], sw[f]) : 0.f;
-                  const float h1 = rn_f16(v);
-                  packed |= f16_bits(term == 0 ? h1 : v - h1) << (16 * e);
-                }
-                float fb; std::memcpy(&fb, &packed, 4);
-                im.push_back(fb);
-              }
-    }
-    auto taps = [&](const Folded& fdw, int shift_pow2) {     // [27][64]: lane (l, g), register q' holds tap f = 4q' + (l & 3) = q * 9 + dy * 3 + dx
-      for (int qq = 0; qq < 27; ++qq)
-        for (int l = 0; l < 64; ++l) {
-          const int f = 4 * qq + (l & 3), q = f / 9, tt = f % 9, n = n48(l >> 4, q);
-          im.push_back(std::ldexp(blob[fdw.w + (size_t)tt * 48 + n] * blob[fdw.scale + n], shift_pow2));
-        }
-    };
-    taps(fd, -sw[0]);      // main: sees relu(pw1) * 2^(sw1+4), hands pw2 its input * 2^4
-    taps(fpd, 0);          // proj: sees the raw input * 2^4
-    for (int n = 0; n < 48; ++n) im.push_back(std::ldexp(blob[f1.shift + n], sw[0] + 4));
-    auto bias = [&](const Folded& fp_, const Folded& fdw, int c) {
-      double acc = 0; for (int k = 0; k < 48; ++k) acc += (double)blob[fp_.w + (size_t)c * 48 + k] * blob[fdw.shift + k];
-      return blob[fp_.shift + c] + blob[fp_.scale + c] * (float)acc;
-    };
-    for (int n = 0; n < 48; ++n) im.push_back(std::ldexp(bias(fpp, fpd, n), sw[1] + 4));
-    for (int n = 0; n < 48; ++n) im.push_back(std::ldexp(bias(f2, fd, n), sw[2] + 4));
-    im.push_back(std::ldexp(1.0f, -(sw[1] + 4)));
-    im.push_back(std::ldexp(1.0f, -(sw[2] + 4)));
-    im.push_back(0.f); im.push_back(0.f);
-    for (int k = 0; k < 6; ++k)                      // per-lane byte offset of input pair 8t + 2g + h, k = 2t + h
-      for (int l = 0; l < 64; ++l) {
-        const int pair = 8 * (k >> 1) + 2 * (l >> 4) + (k & 1);
-        const long long off = (((pp_mask >> pair) & 1u) ? pp_bufstride * 4 : 0) + (long long)pair * IH * IW * 8;
-        const int v = (int)off;
-        float fb; std::memcpy(&fb, &v, 4);
-        im.push_back(fb);
-      }
-    return put(im);
-  }
-  // s4h_kernel (yfv2_stage2h.hip): stage4.0 (96 -> 192).  Lane (l, g) owns positions n96(g, q) = 16 (q / 4) + 4g + q % 4,
-  // q = 0..23; K chunk q / 8, slot q % 8.  Input positions = physical NHWC channel positions of stage 3's output (the Folded
-  // objects passed in already have their input columns / depthwise channels in that order), outputs natural.
-  size_t image_s4h(const Folded& f1, const Folded& fd, const Folded& f2, const Folded& fpd, const Folded& fpp) {
-    const Folded* fs[3] = {&f1, &fpp, &f2};
-    int sw[3];
-    std::vector<float> im;
-    for (int f = 0; f < 3; ++f) {
-      const float* w = &blob[fs[f]->w]; const float* sc = &blob[fs[f]->scale];
-      float mx = 0.f;
-      for (int r = 0; r < 96; ++r)
-        for (int n = 0; n < 96; ++n) mx = std::fmax(mx, std::fabs(w[(size_t)r * 96 + n] * sc[r]));
-      sw[f] = pow2_for(mx);
-      for (int t = 0; t < 6; ++t)
-        for (int c = 0; c < 3; ++c)
-          for (int term = 0; term < 2; ++term)
-            for (int l = 0; l < 64; ++l)
-              for (int d = 0; d < 4; ++d) {
-                unsigned packed = 0;
-                for (int e = 0; e < 2; ++e) {
-                  const int q = 8 * c + 2 * d + e, r = 16 * t + (l & 15);
-                  const float v = std::ldexp(w[(size_t)r * 96 + n48(l >> 4, q)] * sc[r], sw[f]);   // n48's formula is n96's
-                  const float h1 = rn_f16(v);
-                  packed |= f16_bits(term == 0 ? h1 : v - h1) << (16 * e);
-                }
-                float fb; std::memcpy(&fb, &packed, 4);
-                im.push_back(fb);
-              }
-    }
-    auto taps = [&](const Folded& fdw, int shift_pow2) {     // [54][64]: lane (l, g), register q' holds tap f = 4q' + (l & 3) = q * 9 + dy * 3 + dx
-      for (int qq = 0; qq < 54; ++qq)
-        for (int l = 0; l < 64; ++l) {
-          const int f = 4 * qq + (l & 3), q = f / 9, tt = f % 9, n = n48(l >> 4, q);
-          im.push_back(std::ldexp(blob[fdw.w + (size_t)tt * 96 + n] * blob[fdw.scale + n], shift_pow2));
-        }
-    };
-    taps(fd, -sw[0]);
-    taps(fpd, 0);
-    for (int n = 0; n < 96; ++n) im.push_back(std::ldexp(blob[f1.shift + n], sw[0] + 4));
-    auto bias = [&](const Folded& fp_, const Folded& fdw, int c) {
-      double acc = 0; for (int k = 0; k < 96; ++k) acc += (double)blob[fp_.w + (size_t)c * 96 + k] * blob[fdw.shift + k];
-      return blob[fp_.shift + c] + blob[fp_.scale + c] * (float)acc;
-    };
-    for (int n = 0; n < 96; ++n) im.push_back(std::ldexp(bias(fpp, fpd, n), sw[1] + 4));
-    for (int n = 0; n < 96; ++n) im.push_back(std::ldexp(bias(f2, fd, n), sw[2] + 4));
-    im.push_back(std::ldexp(1.0f, -(sw[1] + 4)));
-    im.push_back(std::ldexp(1.0f, -(sw[2] + 4)));
-    im.push_back(0.f); im.push_back(0.f);
-    return put(im);
-  }
-  // depthwise 3x3 taps of 24 channels, BN scale folded: [54][64], lane&3 = k of register q holds tap 4q+k, flat index c*9 + dy*3 + dx
-  static void push_taps_quad(std::vector<float>& im, const float* wd, const float* scd) {
-    const size_t base = im.size();
-    im.resize(base + 54 * 64, 0.f);
-    for (int c = 0; c < 24; ++c)
-      for (int t = 0; t < 9; ++t) {
-        const int f = c * 9 + t;
-        for (int quad = 0; quad < 16; ++quad) im[base + (f >> 2) * 64 + 4 * quad + (f & 3)] = wd[(size_t)t * 24 + c] * scd[c];
-      }
-  }
-  // s2px_kernel role images.  pos[n] = branch-local output channel at output position n of the role's last pointwise conv
-  size_t image_s2px_proj(const Folded& fpd, const Folded& fpp, const int (&pos)[24]) {
-    std::vector<float> im;
-    const float* w = &blob[fpp.w]; const float* sc = &blob[fpp.scale]; const float* sh = &blob[fpp.shift]; const float* shd = &blob[fpd.shift];
-    push_pw24_bcast(im, [&](int n) { return pos[n]; }, [](int k) { return k; },
-                    [&](int r) { double acc = 0; for (int k = 0; k < 24; ++k) acc += (double)w[(size_t)r * 24 + k] * shd[k]; return sh[r] + sc[r] * (float)acc; }, w, sc);
-    push_taps_quad(im, &blob[fpd.w], &blob[fpd.scale]);
-    return put(im);
-  }
-  size_t image_s2px_main(const Folded& f1, const Folded& fd, const Folded& f2, const int (&pos)[24]) {
-    std::vector<float> im;
-    const float* w2 = &blob[f2.w]; const float* sc2 = &blob[f2.scale]; const float* sh2 = &blob[f2.shift]; const float* shd = &blob[fd.shift];
-    const float* sh1 = &blob[f1.shift];
-    push_pw24_bcast(im, [](int n) { return n; }, [](int k) { return k; }, [&](int r) { return sh1[r]; }, &blob[f1.w], &blob[f1.scale]);
-    push_pw24_bcast(im, [&](int n) { return pos[n]; }, [](int k) { return k; },
-                    [&](int r) { double acc = 0; for (int k = 0; k < 24; ++k) acc += (double)w2[(size_t)r * 24 + k] * shd[k]; return sh2[r] + sc2[r] * (float)acc; }, w2, sc2);
-    push_taps_quad(im, &blob[fd.w], &blob[fd.scale]);
-    return put(im);
-  }
-  // copies with the INPUT channels re-ordered: position k takes logical channel label[k]
-  Folded permuted_pw_inputs(const Folded& f, int co, int ci, const int* label) {
-    Folded g = f;
-    g.w = reserve((size_t)co * ci);
-    for (int r = 0; r < co; ++r)
-      for (int k = 0; k < ci; ++k) blob[g.w + (size_t)r * ci + k] = blob[f.w + (size_t)r * ci + label[k]];
-    return g;
-  }
-  // copy with the OUTPUT channels re-ordered: row r (and its BN scale / shift) takes logical output channel label[r]
-  Folded permuted_pw_outputs(const Folded& f, int co, int ci, const int* label) {
-    Folded g;
-    g.w = reserve((size_t)co * ci); g.scale = reserve(co); g.shift = reserve(co);
-    for (int r = 0; r < co; ++r) {
-      for (int k = 0; k < ci; ++k) blob[g.w + (size_t)r * ci + k] = blob[f.w + (size_t)label[r] * ci + k];
-      blob[g.scale + r] = blob[f.scale + label[r]];
-      blob[g.shift + r] = blob[f.shift + label[r]];
-    }
-    return g;
-  }
-  Folded permuted_dw_channels(const Folded& f, int c, int kk, const int* label) {
-    Folded g;
-    g.w = reserve((size_t)c * kk); g.scale = reserve(c); g.shift = reserve(c);
-    for (int k = 0; k < c; ++k) {
-      for (int t = 0; t < kk; ++t) blob[g.w + (size_t)t * c + k] = blob[f.w + (size_t)t * c + label[k]];
-      blob[g.scale + k] = blob[f.scale + label[k]];
-      blob[g.shift + k] = blob[f.shift + label[k]];
-    }
-    return g;
-  }
-  // stem_px_kernel: filter registers in the 4x4x1 broadcast form [11][64]: register q, lane 4j+i holds
-  // scale[co] * W[co = 4m+i][k] for (m*27 + k) = 16q + j, k = ky*9 + ci*3 + kx; then shift[24]
-  // in_scale: 1 for fp32 input in [0,1]; 1/255 for the uint8 entry points (test.py:38's float()/255 folded into the filter)
-  size_t image_stem(const Folded& f, float in_scale = 1.0f) {
-    std::vector<float> im(11 * 64 + 24, 0.f);
-    const float* w = &blob[f.w];  // [27 taps t = ci*9 + ky*3 + kx][24 co]
-    for (int idx = 0; idx < 162; ++idx)
-      for (int i = 0; i < 4; ++i) {
-        const int co = 4 * (idx / 27) + i, k = idx % 27, ky = k / 9, ci = (k % 9) / 3, kx = k % 3;
-        im[(idx >> 4) * 64 + 4 * (idx & 15) + i] = w[(ci * 9 + ky * 3 + kx) * 24 + co] * blob[f.scale + co] * in_scale;
-      }
-    for (int co = 0; co < 24; ++co) im[11 * 64 + co] = blob[f.shift + co];
-    return put(im);
-  }
-  // stem_h3_kernel (yfv2_stem16.hip): the BN-folded filter times 2^sw as TWO fp16 terms (w = h1 + h2 to 2^-24, round to
-  // nearest) in the A-operand order of v_mfma_f32_16x16x32_f16: [channel tile 2][term 2][lane 64][dword 4], lane = 16 g + r
-  // holds output channel 16 t + r, K slots 8 g .. 8 g + 7, two halves per dword (low half = even slot).  Slot -> tap:
-  //   g < 3 (input channel g): (ky,kx) = (0,1) (0,2) (1,1) (1,2) (0,0) (1,0) (2,0) (2,1);   g = 3: slots 2, 3, 7 = tap (2,2)
-  //   of input channels 0, 1, 2, the rest zero.       Then shift * 2^(sw+8) [32 channels, zero beyond 24] and 2^-(sw+8).
-  static float rn_f16(float v) { return (float)(_Float16)v; }
-  static unsigned f16_bits(float v) { const _Float16 h = (_Float16)v; unsigned short u; std::memcpy(&u, &h, 2); return u; }
-  size_t image_stem16(const Folded& f) {
-    const float* w = &blob[f.w];   // [27 taps t = ci*9 + ky*3 + kx][24 co]
-    auto folded = [&](int co, int ci, int ky, int kx) { return w[(ci * 9 + ky * 3 + kx) * 24 + co] * blob[f.scale + co]; };
-    float mx = 0.f;
-    for (int co = 0; co < 24; ++co)
-      for (int t = 0; t < 27; ++t) mx = std::fmax(mx, std::fabs(w[t * 24 + co] * blob[f.scale + co]));
-    int sw = 0;
-    if (mx > 0.f && std::isfinite(mx)) { sw = 14 - (int)std::ceil(std::log2(mx)); if (sw > 24) sw = 24; if (sw < -14) sw = -14; }
-    const float up = std::ldexp(1.0f, sw);
-    static const int TAP[8][2] = {{0, 1}, {0, 2}, {1, 1}, {1, 2}, {0, 0}, {1, 0}, {2, 0}, {2, 1}};
-    auto slot_value = [&](int co, int g, int j) -> float {
-      if (co >= 24) return 0.f;
-      if (g < 3) return folded(co, g, TAP[j][0], TAP[j][1]) * up;
-      if (j == 2) return folded(co, 0, 2, 2) * up;
-      if (j == 3) return folded(co, 1, 2, 2) * up;
-      if (j == 7) return folded(co, 2, 2, 2) * up;
-      return 0.f;
-    };
-    std::vector<float> im;
-    for (int t = 0; t < 2; ++t)
-      for (int term = 0; term < 2; ++term)
-        for (int l = 0; l < 64; ++l)
-          for (int d = 0; d < 4; ++d) {
-            unsigned packed = 0;
-            for (int e = 0; e < 2; ++e) {
-              const float v = slot_value(16 * t + (l & 15), l >> 4, 2 * d + e);
-              const float h1 = rn_f16(v);
-              packed |= f16_bits(term == 0 ? h1 : v - h1) << (16 * e);   // v - h1 is exact in fp32
-            }
-            float fb; std::memcpy(&fb, &packed, 4);
-            im.push_back(fb);
-          }
-    // the kernel scales the image by 2^8 before splitting it (yfv2_stem16.hip): accumulators carry 2^(sw+8)
-    for (int co = 0; co < 32; ++co) im.push_back(co < 24 ? std::ldexp(blob[f.shift + co], sw + 8) : 0.f);
-    im.push_back(std::ldexp(1.0f, -(sw + 8)));
-    while (im.size() % 4) im.push_back(0.f);
-    // stem_h3u_kernel (uint8 pixels 0..255 as they are, one exact fp16 term): accumulators carry 2^sw 255
-    for (int co = 0; co < 32; ++co) im.push_back(co < 24 ? (float)(std::ldexp((double)blob[f.shift + co], sw) * 255.0) : 0.f);
-    im.push_back((float)(std::ldexp(1.0, -sw) / 255.0));
-    while (im.size() % 4) im.push_back(0.f);
-    return put(im);
   }
 };
 
@@ -1347,11 +555,7 @@ struct PlanBuilder {
         }
         act.swap(nxt);
         wp.append_s1_bf6(im, f1k, fd[k], f2k);
-        for (int t = 0; t < 64; ++t) {                  // int tables as raw bits behind the BN vectors
-          float fbits; const int v = t < 36 ? tables[k][t] : 0;
-          std::memcpy(&fbits, &v, sizeof(float));
-          im.push_back(fbits);
-        }
+        for (int t = 0; t < 64; ++t) WeightPacker::push_bits(im, t < 36 ? tables[k][t] : 0);   // int tables as raw bits behind the BN vectors
       }
       if (ok) {
         for (int k = 2; k < NB; ++k) if (group_n[k] != 12) ok = false;
@@ -1389,50 +593,17 @@ struct PlanBuilder {
   }
 
   // ---- a chain of stride-1 blocks with the whole activation resident in LDS (block_s1pool_kernel, yfv2_block.hip): natural
-  // channel order, so the only host work is cutting every block's filters into the three 32-channel passes the kernel runs:
-  // per pass W1 rows 32 t .. +31 (fragment-major [2][6][64][4]) | W2 columns 32 t .. +31 ([6][2][64][4]) | depthwise taps
-  // [9][32] | sc1 sh1 scd shd [32] | sc2 sh2 [96]
+  // channel order, no bookkeeping - the image is WeightPacker::image_s1pool's
   void s1pool_block(const std::vector<std::string>& names, int c, int H, int W, const Buf& x, const Buf& y) {
     const int c2 = c / 2, NB = (int)names.size();
     const bool pre = h->bf6;   // bf16x6 on pre-split filters; YFV2_BF6=0: the fp32-MFMA form of the same kernel
-    std::vector<float> im;
+    std::vector<Folded> f1, fd, f2;
     for (int k = 0; k < NB && ok; ++k) {
-      Folded f1, fd, f2;
-      ok &= wp.pw(names[k] + ".branch_main.0", names[k] + ".branch_main.1", c2, c2, &f1);
-      ok &= wp.dw(names[k] + ".branch_main.3", names[k] + ".branch_main.4", c2, 3, &fd);
-      ok &= wp.pw(names[k] + ".branch_main.5", names[k] + ".branch_main.6", c2, c2, &f2);
-      if (!ok) break;
-      const float* w1 = &wp.blob[f1.w]; const float* w2 = &wp.blob[f2.w]; const float* wd = &wp.blob[fd.w];
-      int sw1 = 0, sw2 = 0;   // fp16x3: one power of two per filter; the BN scales below carry the exact 2^-(sw+4)
-      if (pre) {
-        float m1 = 0.f, m2 = 0.f;
-        for (int i = 0; i < c2 * c2; ++i) { m1 = std::fmax(m1, std::fabs(w1[i])); m2 = std::fmax(m2, std::fabs(w2[i])); }
-        sw1 = WeightPacker::pow2_for(m1); sw2 = WeightPacker::pow2_for(m2);
-      }
-      const int un1 = pre ? sw1 + 4 : 0, un2 = pre ? sw2 + 4 : 0;
-      for (int t = 0; t < 3; ++t) {
-        const size_t start = im.size();
-        if (pre) {   // two fp16 terms x 2^sw per chunk pair (block_s1pool_kernel<.., PRE>: fp16x3)
-          WeightPacker::push_h2_fn(im, 2, 3, [&](int r, int cc) { return std::ldexp(w1[(size_t)(32 * t + r) * c2 + cc], sw1); });    // W1 rows 32 t .. +31, K = 96
-          WeightPacker::push_h2_fn(im, 6, 1, [&](int r, int cc) { return std::ldexp(w2[(size_t)r * c2 + 32 * t + cc], sw2); });      // W2 columns 32 t .. +31
-        } else {
-        for (int mt = 0; mt < 2; ++mt)
-          for (int s = 0; s < 6; ++s)
-            for (int l = 0; l < 64; ++l)
-              for (int j = 0; j < 4; ++j) im.push_back(w1[(size_t)(32 * t + 16 * mt + (l & 15)) * c2 + 16 * s + 4 * (l >> 4) + j]);
-        for (int mt = 0; mt < 6; ++mt)
-          for (int s = 0; s < 2; ++s)
-            for (int l = 0; l < 64; ++l)
-              for (int j = 0; j < 4; ++j) im.push_back(w2[(size_t)(16 * mt + (l & 15)) * c2 + 32 * t + 16 * s + 4 * (l >> 4) + j]);
-        }
-        for (int tap = 0; tap < 9; ++tap)
-          for (int ch = 0; ch < 32; ++ch) im.push_back(wd[(size_t)tap * c2 + 32 * t + ch]);
-        for (const size_t* v : {&f1.scale, &f1.shift, &fd.scale, &fd.shift})
-          for (int ch = 0; ch < 32; ++ch) im.push_back(v == &f1.scale ? std::ldexp(wp.blob[*v + 32 * t + ch], -un1) : wp.blob[*v + 32 * t + ch]);
-        for (int ch = 0; ch < c2; ++ch) im.push_back(std::ldexp(wp.blob[f2.scale + ch], -un2));
-        for (int ch = 0; ch < c2; ++ch) im.push_back(wp.blob[f2.shift + ch]);
-        if ((int)(im.size() - start) != yfv2_s1pool_image_floats(pre)) ok = false;
-      }
+      Folded a, d, b;
+      ok &= wp.pw(names[k] + ".branch_main.0", names[k] + ".branch_main.1", c2, c2, &a);
+      ok &= wp.dw(names[k] + ".branch_main.3", names[k] + ".branch_main.4", c2, 3, &d);
+      ok &= wp.pw(names[k] + ".branch_main.5", names[k] + ".branch_main.6", c2, c2, &b);
+      if (ok) { f1.push_back(a); fd.push_back(d); f2.push_back(b); }
     }
     Step s;
     s.kind = STEP_S1POOL;
@@ -1440,7 +611,7 @@ struct PlanBuilder {
     s.s1.in = x.p; s.s1.out = y.p;
     s.s1.H = H; s.s1.W = W; s.s1.R = H; s.s1.nblk = NB;
     s.s1.presplit = pre ? 1 : 0;
-    s.img_off = wp.put(im);
+    s.img_off = wp.image_s1pool(f1, fd, f2, c2, pre, &ok);
     s.name = names.front() + " .. " + names.back().substr(names.back().rfind('.') + 1) + " chain of " + std::to_string(NB) +
              " fused s1 blocks in one launch (whole activation resident in LDS)";
     s.flops = NB * 2.0 * H * W * (2.0 * c2 * c2 + 9.0 * c2);
@@ -2118,6 +1289,39 @@ int run_lanes(yfv2_ctx* h, int B, hipStream_t s, F f) {
 
 bool use_lanes(const yfv2_ctx* h, int B) { return !h->lanes.empty() && B >= h->lane_min; }
 
+// The host half of yfv2_load_weights: index the tensors, build the plan of `h` and pack its blob into wp.  A failure is the
+// WEIGHTS code with the packer's message, reported on `report` (the handle of a real load; nullptr in a dry run)
+int build_plan(yfv2_ctx* h, WeightPacker& wp, const yfv2_tensor_desc* tensors, int32_t n, yfv2_ctx* report) {
+  wp.index(tensors, n);
+  h->plan.clear();
+  h->c2_permuted = false;
+  PlanBuilder pb{h, wp};
+  pb.build();
+  if (!pb.ok || !wp.missing.empty()) return fail(report, YFV2_ERR_WEIGHTS, wp.missing.empty() ? "weight packing failed" : wp.missing);
+  return YFV2_OK;
+}
+
+// What yfv2_create + yfv2_load_weights do on the host, without a device: the configuration check, a handle whose workspace
+// gets made-up addresses that are only ever used for pointer arithmetic, the plan and the packed blob.
+struct DryRun {
+  yfv2_ctx ctx;
+  WeightPacker wp;
+  int build(const yfv2_config* cfg, const yfv2_plan* plan, const yfv2_tensor_desc* tensors, int32_t n) {
+    int rows = 0;
+    if (int rc = check_config(cfg, &rows)) return rc;
+    uintptr_t next = 0x100000000ull;
+    auto fake = [&](yfv2_ctx* hh, Buf* b, size_t per_img) {
+      b->per_img = per_img;
+      b->p = reinterpret_cast<float*>(next);
+      next += (per_img * sizeof(float) * (size_t)hh->cfg.max_batch + 4095) & ~(uintptr_t)4095;
+      return (int)YFV2_OK;
+    };
+    setup_ctx(&ctx, cfg, rows, fake);
+    read_plan_switches(&ctx, plan);
+    return build_plan(&ctx, wp, tensors, n, nullptr);
+  }
+};
+
 }  // namespace
 
 void** yfv2_ctx_train_slot(yfv2_ctx* h) { return h ? &h->train : nullptr; }
@@ -2198,28 +1402,12 @@ int yfv2_debug_plan_dryrun(const yfv2_config* cfg, const yfv2_tensor_desc* tenso
 
 int yfv2_debug_plan_dryrun_ex(const yfv2_config* cfg, const yfv2_plan* plan, const yfv2_tensor_desc* tensors, int32_t n, int32_t* n_steps, int64_t* blob_floats) {
   if (!cfg || !tensors || n <= 0) return fail(nullptr, YFV2_ERR_ARG, "yfv2_debug_plan_dryrun: bad argument");
-  int rows = 0;
-  if (int rc = check_config(cfg, &rows)) return rc;
-  yfv2_ctx ctx;
-  uintptr_t next = 0x100000000ull;
-  auto fake = [&](yfv2_ctx* hh, Buf* b, size_t per_img) {
-    b->per_img = per_img;
-    b->p = reinterpret_cast<float*>(next);
-    next += (per_img * sizeof(float) * (size_t)hh->cfg.max_batch + 4095) & ~(uintptr_t)4095;
-    return (int)YFV2_OK;
-  };
-  setup_ctx(&ctx, cfg, rows, fake);
-  read_plan_switches(&ctx, plan);
-  WeightPacker wp;
-  for (int i = 0; i < n; ++i)
-    if (tensors[i].name) wp.byname[tensors[i].name] = &tensors[i];
-  PlanBuilder pb{&ctx, wp};
-  pb.build();
-  if (!pb.ok || !wp.missing.empty()) return fail(nullptr, YFV2_ERR_WEIGHTS, wp.missing.empty() ? "weight packing failed" : wp.missing);
-  for (const Step& st : ctx.plan)
-    if (st.img_off > wp.blob.size()) return fail(nullptr, YFV2_ERR_WEIGHTS, "step '" + st.name + "': image offset outside the blob");
-  if (n_steps) *n_steps = (int32_t)ctx.plan.size();
-  if (blob_floats) *blob_floats = (int64_t)wp.blob.size();
+  DryRun d;
+  if (int rc = d.build(cfg, plan, tensors, n)) return rc;
+  for (const Step& st : d.ctx.plan)
+    if (st.img_off > d.wp.blob.size()) return fail(nullptr, YFV2_ERR_WEIGHTS, "step '" + st.name + "': image offset outside the blob");
+  if (n_steps) *n_steps = (int32_t)d.ctx.plan.size();
+  if (blob_floats) *blob_floats = (int64_t)d.wp.blob.size();
   return YFV2_OK;
 }
 
@@ -2234,39 +1422,23 @@ int64_t yfv2_debug_plan_image(const yfv2_config* cfg, const yfv2_tensor_desc* te
 int64_t yfv2_debug_plan_image_ex(const yfv2_config* cfg, const yfv2_plan* plan, const yfv2_tensor_desc* tensors, int32_t n, int32_t step, char* name,
                                  int32_t name_cap, float* dst, int64_t cap) {
   if (!cfg || !tensors || n <= 0 || (step != -1 && (!dst || cap <= 0))) return fail(nullptr, YFV2_ERR_ARG, "yfv2_debug_plan_image: bad argument");
-  int rows = 0;
-  if (int rc = check_config(cfg, &rows)) return rc;
-  yfv2_ctx ctx;
-  uintptr_t next = 0x100000000ull;
-  auto fake = [&](yfv2_ctx* hh, Buf* b, size_t per_img) {
-    b->per_img = per_img;
-    b->p = reinterpret_cast<float*>(next);
-    next += (per_img * sizeof(float) * (size_t)hh->cfg.max_batch + 4095) & ~(uintptr_t)4095;
-    return (int)YFV2_OK;
-  };
-  setup_ctx(&ctx, cfg, rows, fake);
-  read_plan_switches(&ctx, plan);
-  WeightPacker wp;
-  for (int i = 0; i < n; ++i)
-    if (tensors[i].name) wp.byname[tensors[i].name] = &tensors[i];
-  PlanBuilder pb{&ctx, wp};
-  pb.build();
-  if (!pb.ok || !wp.missing.empty()) return fail(nullptr, YFV2_ERR_WEIGHTS, wp.missing.empty() ? "weight packing failed" : wp.missing);
+  DryRun d;
+  if (int rc = d.build(cfg, plan, tensors, n)) return rc;
   // step + 1000 (k + 1): job k of a launch that runs several tower halves (towers_kernel's list, towerh_kernel's side-by-side pair)
   const int job = step >= 1000 ? step / 1000 - 1 : -1;
   if (step >= 1000) step %= 1000;
   // the images are those of the launches as packed: under front_kernel (one launch for the stem and stage2.0) the stem's step is
   // put back in front and stage2.0 answers to its own name - step indices are those of the two-launch plan
-  std::vector<Step> view = ctx.plan;
-  if (ctx.front_fused) { view.insert(view.begin(), ctx.stem_aside); view[1].name = view[1].name_plain; }
+  std::vector<Step> view = d.ctx.plan;
+  if (d.ctx.front_fused) { view.insert(view.begin(), d.ctx.stem_aside); view[1].name = view[1].name_plain; }
   if (step == -1) return (int64_t)view.size();   // the number of steps of THIS index space (launch plan + 1 where the front is one launch)
   if (step < 0 || step >= (int32_t)view.size()) return fail(nullptr, YFV2_ERR_ARG, "yfv2_debug_plan_image: step out of range");
   if (job >= (int)view[step].jobs.size()) return fail(nullptr, YFV2_ERR_ARG, "yfv2_debug_plan_image: job out of range");
   const Step& st = job >= 0 ? view[step].jobs[job] : view[step];
   if (name && name_cap > 0) std::snprintf(name, (size_t)name_cap, "%s", st.name.c_str());
-  const int64_t avail = (int64_t)wp.blob.size() - (int64_t)st.img_off;
+  const int64_t avail = (int64_t)d.wp.blob.size() - (int64_t)st.img_off;
   const int64_t cnt = avail < cap ? avail : cap;
-  if (cnt > 0) std::memcpy(dst, &wp.blob[st.img_off], sizeof(float) * (size_t)cnt);
+  if (cnt > 0) std::memcpy(dst, &d.wp.blob[st.img_off], sizeof(float) * (size_t)cnt);
   return cnt;
 }
 
@@ -2274,26 +1446,10 @@ int64_t yfv2_debug_plan_image_ex(const yfv2_config* cfg, const yfv2_plan* plan, 
 // physical position k; returns 1 if the plan permutes (chain kernel), 0 if C2 is plain NHWC, or a negative error code.
 int yfv2_debug_plan_c2_label(const yfv2_config* cfg, const yfv2_tensor_desc* tensors, int32_t n, int32_t* label) {
   if (!cfg || !tensors || n <= 0 || !label) return fail(nullptr, YFV2_ERR_ARG, "yfv2_debug_plan_c2_label: bad argument");
-  int rows = 0;
-  if (int rc = check_config(cfg, &rows)) return rc;
-  yfv2_ctx ctx;
-  uintptr_t next = 0x100000000ull;
-  auto fake = [&](yfv2_ctx* hh, Buf* b, size_t per_img) {
-    b->per_img = per_img;
-    b->p = reinterpret_cast<float*>(next);
-    next += (per_img * sizeof(float) * (size_t)hh->cfg.max_batch + 4095) & ~(uintptr_t)4095;
-    return (int)YFV2_OK;
-  };
-  setup_ctx(&ctx, cfg, rows, fake);
-  read_plan_switches(&ctx, nullptr);
-  WeightPacker wp;
-  for (int i = 0; i < n; ++i)
-    if (tensors[i].name) wp.byname[tensors[i].name] = &tensors[i];
-  PlanBuilder pb{&ctx, wp};
-  pb.build();
-  if (!pb.ok || !wp.missing.empty()) return fail(nullptr, YFV2_ERR_WEIGHTS, wp.missing.empty() ? "weight packing failed" : wp.missing);
-  for (int k = 0; k < 96; ++k) label[k] = ctx.c2_permuted ? ctx.c2_label[k] : k;
-  return ctx.c2_permuted ? 1 : 0;
+  DryRun d;
+  if (int rc = d.build(cfg, nullptr, tensors, n)) return rc;
+  for (int k = 0; k < 96; ++k) label[k] = d.ctx.c2_permuted ? d.ctx.c2_label[k] : k;
+  return d.ctx.c2_permuted ? 1 : 0;
 }
 
 void yfv2_destroy(yfv2_handle h) {
@@ -2328,16 +1484,10 @@ int yfv2_load_weights(yfv2_handle h, const yfv2_tensor_desc* tensors, int32_t n)
   if (!tensors || n <= 0) return fail(h, YFV2_ERR_ARG, "yfv2_load_weights: no tensors");
   DeviceGuard guard(h->device);
   WeightPacker wp;
-  for (int i = 0; i < n; ++i)
-    if (tensors[i].name) wp.byname[tensors[i].name] = &tensors[i];
-  h->plan.clear();
-  h->c2_permuted = false;
-  PlanBuilder pb{h, wp};
-  pb.build();
-  if (!pb.ok || !wp.missing.empty()) {
+  if (int rc = build_plan(h, wp, tensors, n, h)) {
     h->plan.clear();
     h->weights_loaded = false;
-    return fail(h, YFV2_ERR_WEIGHTS, wp.missing.empty() ? "weight packing failed" : wp.missing);
+    return rc;
   }
   HIP_TRY(h, hipDeviceSynchronize());  // nothing of ours may still read the old blob
   if (h->d_params && h->n_params < wp.blob.size()) { (void)hipFree(h->d_params); h->d_params = nullptr; }

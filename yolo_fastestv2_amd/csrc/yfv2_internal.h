@@ -1,5 +1,5 @@
 // yfv2_internal.h - launch-argument structs shared by the kernel translation
-// units and the host-side plan (yfv2_api.hip).  Not part of the public ABI.
+// units, the host-side weight packer (yfv2_pack.hip) and the host-side plan (yfv2_api.hip).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
@@ -200,7 +200,7 @@ struct DwArgs {
 struct BlockS1Args {
   const float* in;   // (B,H,W,2*C2) NHWC
   float* out;        // (B,H,W,2*C2) NHWC, distinct from in
-  const float* img;  // the blocks' LDS images back to back (host-packed, WeightPacker::append_s1_bf6 / PlanBuilder::s1pool_block)
+  const float* img;  // the blocks' LDS images back to back (host-packed, WeightPacker::append_s1_bf6 / image_s1pool)
   long long* trace;  // debug: workgroup 0 / thread 0 writes s_memtime stamps at phase boundaries (or null)
   int B, H, W;
   int R;             // rows per work item (H % R == 0)
@@ -259,7 +259,7 @@ __host__ __device__ inline int yfv2_stage2_channel(int slot) {
 }
 struct S1PxArgs {
   float* act;          // the stage: [max_batch][2 buffers][24 pairs][H][W][2] (src_off / dst_off carry the buffer: + 48*H*W floats for buffer 1)
-  const float* img;    // w1q[10][64] | w2q[10][64] | (unused 24) | dw taps [9][24]  (yfv2_api.hip image_s1px)
+  const float* img;    // w1q[10][64] | w2q[10][64] | (unused 24) | dw taps [9][24]  (WeightPacker::image_s1px)
   int B, H, W;
   int nstrips, nb, R;  // set by the launcher
   int img_stride;      // floats per image (2*48*H*W: both buffers)

@@ -73,7 +73,7 @@ __device__ __forceinline__ f32x4 mfma_main1(u32x4 w, u32x4 x, f32x4 acc) {    //
 
 }  // namespace
 
-// image (floats), packed by WeightPacker::image_towerh (yfv2_api.hip):
+// image (floats), packed by WeightPacker::image_towerh (yfv2_pack.hip):
 //   WP   [mt 5][s 5][64 lanes][4 dwords]   pointwise filter x 2^sw: dwords 0,1 = first fp16 term of W[16mt + l%16][16s + 4(l/16) .. +3], 2,3 = second
 //   CS   [4][96]                           pw BN scale x 2^-(sw+4) | pw BN shift | output-conv bias | [0] = 2^-(swh+4)
 //   WH   [m MH][s 5][64][4]                output conv x 2^swh, as WP
