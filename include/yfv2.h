@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define YFV2_ABI_VERSION 7 /* 2: yfv2_stage_info reports external bytes as well; 3: yfv2_train_*, yfv2_sgd_step; 4: yfv2_nonfinite, lanes; 5: yfv2_nonfinite_peek, yfv2_clock_probe_*; 6: yfv2_plan / yfv2_create_ex (the library reads no environment variable); 7: yfv2_debug_post; still 7 with the additive yfv2_frame, yfv2_resize_frames_u8, yfv2_detect_frames_u8 and the additive yfv2_anchor_kmeans, yfv2_kmeans_info, yfv2_debug_kmeans_group (old callers are unaffected) */
+#define YFV2_ABI_VERSION 7 /* 2: yfv2_stage_info reports external bytes as well; 3: yfv2_train_*, yfv2_sgd_step; 4: yfv2_nonfinite, lanes; 5: yfv2_nonfinite_peek, yfv2_clock_probe_*; 6: yfv2_plan / yfv2_create_ex (the library reads no environment variable); 7: yfv2_debug_post; still 7 with the additive yfv2_frame, yfv2_resize_frames_u8, yfv2_detect_frames_u8 and the additive yfv2_anchor_kmeans, yfv2_kmeans_info, yfv2_debug_kmeans_group; still 7 with the additive yfv2_tile, yfv2_tile_plan, yfv2_merge_tiles, yfv2_detect_tiled_u8 (old callers are unaffected) */
 #define YFV2_API __attribute__((visibility("default")))
 #define YFV2_MAX_DET 300 /* utils/utils.py:243 max_det */
 
@@ -209,6 +209,57 @@ YFV2_API int yfv2_resize_frames_u8(yfv2_handle h, const yfv2_frame* frames, int3
  * yfv2_resize_frames_u8 plus those of yfv2_detect_u8 (B <= max_batch, weights loaded). */
 YFV2_API int yfv2_detect_frames_u8(yfv2_handle h, const yfv2_frame* frames, int32_t B, float conf_thres, double iou_thres,
                                    float* dets, int32_t* idx, int32_t* count, void* stream);
+
+/* ---- tiled detection of large frames: plan tiles, detect on every tile, merge on the device ----
+ * The network sees cfg.width x cfg.height pixels; a 1920x1080 frame resized to that loses its small objects.  The usual remedy is
+ * to cut the frame into overlapping tiles, detect on each, move the boxes back into the frame and suppress the duplicates the
+ * overlaps produce.  A tile is a crop, which yfv2_frame reads in place; what these entry points add is the plan and the last step. */
+typedef struct yfv2_tile { int32_t frame; int32_t x0, y0, width, height; } yfv2_tile; /* a rectangle inside frames[frame] */
+
+/* Host only, no handle, no device.  Per axis of length L, tile t and overlap o (0 <= o < t): L <= t is the one interval [0, L);
+ * otherwise s = t - o, n = ceil((L - t) / s) + 1 tiles of length t starting at min(i * s, L - t) - the last one ends on the edge.
+ * Tiles are written row-major, y outer, .frame = 0; with include_full != 0 and more than one grid tile, one more tile covering
+ * the whole frame comes last.  Returns the tile count (>= 1); tiles may be NULL to ask for it.  YFV2_ERR_ARG (negative): a size
+ * < 1, an overlap outside [0, tile), cap smaller than the count. */
+YFV2_API int yfv2_tile_plan(int32_t frame_h, int32_t frame_w, int32_t tile_h, int32_t tile_w, int32_t overlap_h, int32_t overlap_w,
+                            int32_t include_full, yfv2_tile* tiles, int32_t cap);
+
+/* The merge alone, on tile detections the caller already has: tile_dets (T, 300, 6) / tile_count (T) on the device in the layout
+ * of yfv2_detect_frames_u8's output (every tile's rows conf-descending, finite coordinates, in TILE coordinates); tiles: HOST, T
+ * entries, of which .frame, .x0 and .y0 are read here.  THE RULE, bit for bit (tests/tiles_ref.py merge_model restates it):
+ *   candidates of frame f   its tiles in ascending k, rows r = 0 .. tile_count[k] - 1 of each; x1, x2 become fp32(x + fp32(x0)),
+ *                           y1, y2 become fp32(y + fp32(y0)); conf and class are untouched
+ *   order                   conf descending, stable over (k, r)
+ *   greedy walk             a candidate is dropped if an already KEPT candidate has the same class (the floats compare equal) and a
+ *                           match with it for which double(match) > merge_thres.  match, in fp32 as torchvision's kernel computes
+ *                           IoU: w = max(0, min(x2) - max(x1)), h likewise, inter = w * h, areas (x2 - x1) * (y2 - y1);
+ *                           merge_metric 0: inter / (a_i + a_j - inter); 1: inter / min(a_i, a_j) - intersection over the smaller
+ *                           box, which merges an object cut by a tile edge with its whole view next door.  A NaN match (0 / 0)
+ *                           suppresses nothing.  Classes are compared, not offset by cls * 4096 as non_max_suppression does: that
+ *                           trick rounds away box bits at frame scale and breaks beyond 4096 pixels.
+ *   stop                    after max_out kept rows
+ * dets (F, max_out, 6): the kept rows of frame f in walk order, frame coordinates; src (F, max_out) or NULL: k * 300 + r, the
+ * origin of each; count (F).  Rows beyond count[f] are not written; a frame without tiles has count 0.  Checked before anything
+ * is enqueued (YFV2_ERR_ARG with a message): NULL pointers, T or F outside 1..65536, tiles[k].frame outside [0, F) or decreasing
+ * in k (a frame's tiles are one contiguous range), merge_metric not 0 or 1, max_out outside 1..4096, merge_thres not finite.
+ * Enqueue only.  The ordered candidate lists (32 bytes per tile row) live in a workspace of the handle, allocated by the first call
+ * (one device wait) and grown - another wait - only by a call with more tiles or frames than any before.  No output bit
+ * depends on the launch geometry or the run: positions come from binary searches, nothing is accumulated in floating point. */
+YFV2_API int yfv2_merge_tiles(yfv2_handle h, const float* tile_dets /* (T,300,6) */, const int32_t* tile_count /* (T) */,
+                              const yfv2_tile* tiles /* HOST, T entries */, int32_t T, int32_t F,
+                              double merge_thres, int32_t merge_metric, int32_t max_out,
+                              float* dets /* (F,max_out,6) */, int32_t* src /* (F,max_out) or NULL */, int32_t* count /* (F) */,
+                              void* stream);
+
+/* crop -> resize -> detect -> tile-to-frame -> merge, enqueue only.  frames: HOST array of F descriptors; tile k is the crop
+ * {frames[f].data + y0 * row_pitch + 3 * x0, height, width, row_pitch}; the T crops go through yfv2_detect_frames_u8 unchanged
+ * (same kernels, resize buffer and lanes), their results into a (max_batch, 300, 6) / idx / count workspace of the handle
+ * (allocated by the first call, one device wait), then the merge above runs on them.  Checked before anything is enqueued:
+ * everything yfv2_detect_frames_u8 checks, per crop; everything yfv2_merge_tiles checks; each frame's height, width >= 1, data,
+ * row_pitch >= 3 * width; each rectangle inside its frame with width and height >= 1; T > max_batch is YFV2_ERR_BATCH. */
+YFV2_API int yfv2_detect_tiled_u8(yfv2_handle h, const yfv2_frame* frames, int32_t F, const yfv2_tile* tiles, int32_t T,
+                                  float conf_thres, double iou_thres, double merge_thres, int32_t merge_metric, int32_t max_out,
+                                  float* dets, int32_t* src, int32_t* count, void* stream);
 
 /* replaces: utils/utils.py:194-230 get_batch_statistics (with bbox_iou :76-108), the per-detection loop of
  * evaluation() (:361-395).  dets/count: the padded output of yfv2_nms / yfv2_detect; targets: (T,6) fp32 device rows

@@ -73,6 +73,11 @@ class Frame(C.Structure):
     _fields_ = [("data", C.c_void_p), ("height", C.c_int32), ("width", C.c_int32), ("row_pitch", C.c_int64)]
 
 
+class Tile(C.Structure):
+    """yfv2_tile (include/yfv2.h): a rectangle inside frames[frame]."""
+    _fields_ = [("frame", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("width", C.c_int32), ("height", C.c_int32)]
+
+
 class KmeansInfo(C.Structure):
     """yfv2_kmeans_info (include/yfv2.h): what ended yfv2_anchor_kmeans' loop."""
     _fields_ = [("struct_size", C.c_int32), ("iterations", C.c_int32), ("converged", C.c_int32), ("empty_cluster", C.c_int32),
@@ -122,6 +127,11 @@ _PROTOTYPES = {
     "yfv2_resize_frames_u8": (C.c_int, [C.c_void_p, C.POINTER(Frame), C.c_int32, C.c_void_p, C.c_void_p]),
     "yfv2_detect_frames_u8": (C.c_int, [C.c_void_p, C.POINTER(Frame), C.c_int32, C.c_float, C.c_double, C.c_void_p, C.c_void_p,
                                         C.c_void_p, C.c_void_p]),
+    "yfv2_tile_plan": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(Tile), C.c_int32]),
+    "yfv2_merge_tiles": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(Tile), C.c_int32, C.c_int32, C.c_double, C.c_int32, C.c_int32,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "yfv2_detect_tiled_u8": (C.c_int, [C.c_void_p, C.POINTER(Frame), C.c_int32, C.POINTER(Tile), C.c_int32, C.c_float, C.c_double, C.c_double,
+                                       C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "yfv2_anchor_kmeans": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                      C.POINTER(KmeansInfo), C.c_void_p]),
     "yfv2_debug_kmeans_group": (C.c_int, [C.c_void_p, C.c_int32]),

@@ -103,6 +103,13 @@ struct yfv2_ctx {
   int32_t* d_stats_flag = nullptr;  // = d_classes + 256
   ResizeFrame* d_frames = nullptr;   // frame descriptors of yfv2_resize_frames_u8 / yfv2_detect_frames_u8 (max_batch entries)
   uint8_t* d_frames_u8 = nullptr;    // yfv2_detect_frames_u8's resized batch (max_batch, H, W, 3): allocated by its first call
+  // tiled detection (yfv2_merge_tiles / yfv2_detect_tiled_u8).  d_tile_ws: the ordered candidate lists of tile_cap_t tiles (two float4
+  // per row) and the tile / frame table of tile_cap_t + tile_cap_f entries; allocated by the first call, grown (one device wait) only by
+  // a call with more tiles or frames than any before.  d_tile_out: yfv2_detect_tiled_u8's per-tile results (max_batch, 300, 6) +
+  // idx (max_batch, 300) + count (max_batch), allocated by its first call.
+  void* d_tile_ws = nullptr;
+  int tile_cap_t = 0, tile_cap_f = 0;
+  float* d_tile_out = nullptr;
   // the sticky range-guard word of the fp16x3 plan (yfv2_nonfinite): ONE int32 in host-mapped, coherent memory.  The kernels
   // store 1 into it through d_nonfinite (the rare path, a plain store); the host reads h_nonfinite - after waiting for a stream
   // (yfv2_nonfinite: exact) or without waiting (yfv2_nonfinite_peek: what has landed so far).  A lane uses its parent's word.
@@ -1465,6 +1472,8 @@ void yfv2_destroy(yfv2_handle h) {
   if (h->d_classes) (void)hipFree(h->d_classes);
   if (h->d_frames) (void)hipFree(h->d_frames);
   if (h->d_frames_u8) (void)hipFree(h->d_frames_u8);
+  if (h->d_tile_ws) (void)hipFree(h->d_tile_ws);
+  if (h->d_tile_out) (void)hipFree(h->d_tile_out);
   if (h->h_nonfinite) (void)hipHostFree(h->h_nonfinite);
   if (h->d_probe) (void)hipFree(h->d_probe);
   if (h->d_loss_ws) (void)hipFree(h->d_loss_ws);
@@ -2012,6 +2021,152 @@ int yfv2_detect_frames_u8(yfv2_handle h, const yfv2_frame* frames, int32_t B, fl
   yfv2_launch_frame_boxes(dets, count, h->d_frames, B, s);
   HIP_TRY(h, hipGetLastError());
   return YFV2_OK;
+}
+
+// ---- tiled detection ----------------------------------------------------------------------------------
+
+// One axis of the tile plan: L <= t is the single interval [0, L); otherwise tiles of length t at min(i * (t - o), L - t).
+static int64_t tile_axis_count(int32_t L, int32_t t, int32_t o) {
+  if (L <= t) return 1;
+  const int64_t s = (int64_t)t - o;
+  return ((int64_t)L - t + s - 1) / s + 1;
+}
+
+int yfv2_tile_plan(int32_t frame_h, int32_t frame_w, int32_t tile_h, int32_t tile_w, int32_t overlap_h, int32_t overlap_w,
+                   int32_t include_full, yfv2_tile* tiles, int32_t cap) {
+  if (frame_h < 1 || frame_w < 1 || tile_h < 1 || tile_w < 1) return fail(nullptr, YFV2_ERR_ARG, "yfv2_tile_plan: frame and tile sizes must be >= 1");
+  if (overlap_h < 0 || overlap_h >= tile_h || overlap_w < 0 || overlap_w >= tile_w)
+    return fail(nullptr, YFV2_ERR_ARG, "yfv2_tile_plan: overlap must be in [0, tile)");
+  const int64_t ny = tile_axis_count(frame_h, tile_h, overlap_h), nx = tile_axis_count(frame_w, tile_w, overlap_w);
+  const int64_t total = ny * nx + (include_full && ny * nx > 1 ? 1 : 0);
+  if (total > 0x7fffffffll) return fail(nullptr, YFV2_ERR_ARG, "yfv2_tile_plan: more than 2^31 - 1 tiles");
+  if (!tiles) return (int)total;
+  if (cap < total) return fail(nullptr, YFV2_ERR_ARG, "yfv2_tile_plan: cap " + std::to_string(cap) + " < " + std::to_string(total) + " tiles");
+  const int32_t th = std::min(tile_h, frame_h), tw = std::min(tile_w, frame_w);     // L <= t: the one interval is [0, L)
+  const int64_t sy = (int64_t)tile_h - overlap_h, sx = (int64_t)tile_w - overlap_w;
+  yfv2_tile* o = tiles;
+  for (int64_t iy = 0; iy < ny; ++iy)
+    for (int64_t ix = 0; ix < nx; ++ix, ++o) {
+      o->frame = 0;
+      o->y0 = (int32_t)std::min<int64_t>(iy * sy, frame_h - th);
+      o->x0 = (int32_t)std::min<int64_t>(ix * sx, frame_w - tw);
+      o->height = th; o->width = tw;
+    }
+  if (total > ny * nx) { o->frame = 0; o->x0 = 0; o->y0 = 0; o->width = frame_w; o->height = frame_h; }
+  return (int)total;
+}
+
+constexpr int TILE_MAX_T = 65536, TILE_MAX_F = 65536, TILE_MAX_OUT = 4096;
+
+// What both entry points check of the merge itself; fills the device table's host image: [T][4] x0, y0, k0, k1, then [F][2] k0, k1.
+static int check_merge(yfv2_handle h, const char* what, const yfv2_tile* tiles, int32_t T, int32_t F, double merge_thres, int32_t merge_metric,
+                       int32_t max_out, std::vector<int32_t>& table) {
+  const std::string w_ = what;
+  if (!tiles) return fail(h, YFV2_ERR_ARG, w_ + ": null pointer");
+  if (T < 1 || T > TILE_MAX_T) return fail(h, YFV2_ERR_ARG, w_ + ": T must be in 1.." + std::to_string(TILE_MAX_T));
+  if (F < 1 || F > TILE_MAX_F) return fail(h, YFV2_ERR_ARG, w_ + ": F must be in 1.." + std::to_string(TILE_MAX_F));
+  if (merge_metric != 0 && merge_metric != 1) return fail(h, YFV2_ERR_ARG, w_ + ": merge_metric must be 0 (IoU) or 1 (intersection over the smaller box)");
+  if (max_out < 1 || max_out > TILE_MAX_OUT) return fail(h, YFV2_ERR_ARG, w_ + ": max_out must be in 1.." + std::to_string(TILE_MAX_OUT));
+  if (!std::isfinite(merge_thres)) return fail(h, YFV2_ERR_ARG, w_ + ": merge_thres must be a finite number");
+  table.assign((size_t)4 * T + (size_t)2 * F, 0);
+  int32_t* fr = table.data() + (size_t)4 * T;
+  for (int32_t k = 0; k < T; ++k) {
+    const int32_t f = tiles[k].frame;
+    if (f < 0 || f >= F) return fail(h, YFV2_ERR_ARG, w_ + ": tile " + std::to_string(k) + ": frame " + std::to_string(f) + " outside [0, F)");
+    if (k > 0 && f < tiles[k - 1].frame)
+      return fail(h, YFV2_ERR_ARG, w_ + ": tile " + std::to_string(k) + ": frame index decreases (a frame's tiles must be one contiguous range)");
+    if (fr[2 * f + 1] == 0) fr[2 * f] = k;      // first tile of frame f
+    fr[2 * f + 1] = k + 1;
+  }
+  for (int32_t k = 0; k < T; ++k) {
+    int32_t* e = table.data() + (size_t)4 * k;
+    e[0] = tiles[k].x0; e[1] = tiles[k].y0; e[2] = fr[2 * tiles[k].frame]; e[3] = fr[2 * tiles[k].frame + 1];
+  }
+  return YFV2_OK;
+}
+
+static int ensure_tile_ws(yfv2_handle h, int T, int F) {
+  if (h->d_tile_ws && T <= h->tile_cap_t && F <= h->tile_cap_f) return YFV2_OK;
+  const int ct = std::max(T, h->tile_cap_t), cf = std::max(F, h->tile_cap_f);
+  HIP_TRY(h, hipDeviceSynchronize());            // like the resize buffer: an allocation waits for the device once
+  if (h->d_tile_ws) { (void)hipFree(h->d_tile_ws); h->d_tile_ws = nullptr; h->tile_cap_t = h->tile_cap_f = 0; }
+  const size_t bytes = (size_t)ct * YFV2_MAX_DET * 32 + sizeof(int32_t) * ((size_t)4 * ct + (size_t)2 * cf);
+  HIP_TRY(h, hipMalloc(&h->d_tile_ws, bytes));
+  h->tile_cap_t = ct; h->tile_cap_f = cf;
+  return YFV2_OK;
+}
+
+// uploads the table and enqueues the two launches; everything was checked
+static int enqueue_merge(yfv2_handle h, const float* tile_dets, const int32_t* tile_count, const std::vector<int32_t>& table, int32_t T, int32_t F,
+                         double merge_thres, int32_t merge_metric, int32_t max_out, float* dets, int32_t* src, int32_t* count, hipStream_t s) {
+  char* base = static_cast<char*>(h->d_tile_ws);
+  const size_t list = (size_t)h->tile_cap_t * YFV2_MAX_DET * 16;
+  int32_t* d_table = reinterpret_cast<int32_t*>(base + 2 * list);
+  HIP_TRY(h, hipMemcpyAsync(d_table, table.data(), sizeof(int32_t) * table.size(), hipMemcpyHostToDevice, s));
+  TileMergeArgs a{};
+  a.tile_dets = tile_dets; a.tile_count = tile_count; a.table = d_table; a.T = T; a.F = F;
+  a.geo = reinterpret_cast<float*>(base); a.meta = reinterpret_cast<float*>(base + list);
+  a.thres = merge_thres; a.metric = merge_metric; a.max_out = max_out; a.dets = dets; a.src = src; a.count = count;
+  yfv2_launch_tile_merge(a, s);
+  HIP_TRY(h, hipGetLastError());
+  return YFV2_OK;
+}
+
+int yfv2_merge_tiles(yfv2_handle h, const float* tile_dets, const int32_t* tile_count, const yfv2_tile* tiles, int32_t T, int32_t F,
+                     double merge_thres, int32_t merge_metric, int32_t max_out, float* dets, int32_t* src, int32_t* count, void* stream) {
+  if (!h) return fail(nullptr, YFV2_ERR_ARG, "null handle");
+  if (!tile_dets || !tile_count || !dets || !count) return fail(h, YFV2_ERR_ARG, "yfv2_merge_tiles: null pointer");
+  std::vector<int32_t> table;
+  if (int rc = check_merge(h, "yfv2_merge_tiles", tiles, T, F, merge_thres, merge_metric, max_out, table)) return rc;
+  DeviceGuard guard(h->device);
+  if (int rc = ensure_tile_ws(h, T, F)) return rc;
+  return enqueue_merge(h, tile_dets, tile_count, table, T, F, merge_thres, merge_metric, max_out, dets, src, count, static_cast<hipStream_t>(stream));
+}
+
+int yfv2_detect_tiled_u8(yfv2_handle h, const yfv2_frame* frames, int32_t F, const yfv2_tile* tiles, int32_t T, float conf_thres, double iou_thres,
+                         double merge_thres, int32_t merge_metric, int32_t max_out, float* dets, int32_t* src, int32_t* count, void* stream) {
+  if (!h) return fail(nullptr, YFV2_ERR_ARG, "null handle");
+  if (!frames || !tiles || !dets || !count) return fail(h, YFV2_ERR_ARG, "yfv2_detect_tiled_u8: null pointer");
+  if (T > h->cfg.max_batch)
+    return fail(h, YFV2_ERR_BATCH, "yfv2_detect_tiled_u8: " + std::to_string(T) + " tiles above max_batch=" + std::to_string(h->cfg.max_batch));
+  std::vector<int32_t> table;
+  if (int rc = check_merge(h, "yfv2_detect_tiled_u8", tiles, T, F, merge_thres, merge_metric, max_out, table)) return rc;
+  for (int32_t f = 0; f < F; ++f) {
+    const yfv2_frame& fr = frames[f];
+    const std::string at = "yfv2_detect_tiled_u8: frame " + std::to_string(f) + ": ";
+    if (fr.height < 1 || fr.width < 1) return fail(h, YFV2_ERR_ARG, at + "height and width must be >= 1");
+    if (!fr.data) return fail(h, YFV2_ERR_ARG, at + "null data");
+    if (fr.row_pitch < 3ll * fr.width) return fail(h, YFV2_ERR_ARG, at + "row_pitch " + std::to_string(fr.row_pitch) + " < 3 * width");
+  }
+  std::vector<yfv2_frame> crops((size_t)T);
+  for (int32_t k = 0; k < T; ++k) {
+    const yfv2_tile& t = tiles[k];
+    const yfv2_frame& fr = frames[t.frame];
+    if (t.width < 1 || t.height < 1 || t.x0 < 0 || t.y0 < 0 || (int64_t)t.x0 + t.width > fr.width || (int64_t)t.y0 + t.height > fr.height)
+      return fail(h, YFV2_ERR_ARG, "yfv2_detect_tiled_u8: tile " + std::to_string(k) + ": [" + std::to_string(t.x0) + ", " + std::to_string((int64_t)t.x0 + t.width) +
+                                       ") x [" + std::to_string(t.y0) + ", " + std::to_string((int64_t)t.y0 + t.height) + ") is not a rectangle of at least one pixel inside its " +
+                                       std::to_string(fr.width) + " x " + std::to_string(fr.height) + " frame");
+    crops[(size_t)k] = yfv2_frame{fr.data + (int64_t)t.y0 * fr.row_pitch + 3ll * t.x0, t.height, t.width, fr.row_pitch};
+  }
+  // everything yfv2_detect_frames_u8 checks, per crop, before the workspaces are touched (it checks again: host work only)
+  if (int rc = check_call(h, T, true)) return rc;
+  {
+    std::vector<ResizeFrame> t;
+    int max_w = 0;
+    if (int rc = check_frames(h, "yfv2_detect_tiled_u8", crops.data(), T, t, &max_w)) return rc;
+  }
+  DeviceGuard guard(h->device);
+  const size_t mb = (size_t)h->cfg.max_batch;
+  if (!h->d_tile_out) {
+    HIP_TRY(h, hipDeviceSynchronize());
+    HIP_TRY(h, hipMalloc(reinterpret_cast<void**>(&h->d_tile_out), sizeof(float) * mb * YFV2_MAX_DET * 6 + sizeof(int32_t) * (mb * YFV2_MAX_DET + mb)));
+  }
+  if (int rc = ensure_tile_ws(h, h->cfg.max_batch, F)) return rc;    // for max_batch tiles: no later call on this handle grows it for its tiles
+  float* t_dets = h->d_tile_out;
+  int32_t* t_idx = reinterpret_cast<int32_t*>(t_dets + mb * YFV2_MAX_DET * 6);
+  int32_t* t_count = t_idx + mb * YFV2_MAX_DET;
+  if (int rc = yfv2_detect_frames_u8(h, crops.data(), T, conf_thres, iou_thres, t_dets, t_idx, t_count, stream)) return rc;
+  return enqueue_merge(h, t_dets, t_count, table, T, F, merge_thres, merge_metric, max_out, dets, src, count, static_cast<hipStream_t>(stream));
 }
 
 int32_t yfv2_num_rows(yfv2_handle h) { return h ? h->rows : 0; }

@@ -423,6 +423,22 @@ void yfv2_launch_nms(const NmsArgs& a, hipStream_t s);
 void yfv2_launch_decode_nms(const DecodeArgs& d, const NmsArgs& a, hipStream_t s);   // yfv2_detect: decode + NMS in one launch
 bool yfv2_post_fusable(int classes, int rows);   // ... which exists for up to 96 classes and 2048 decode rows; beyond: two launches
 int yfv2_nms_max_rows();                         // decode rows per image nms_kernel handles (4096)
+// ---- tiled detection (yfv2_tiles.hip): a frame's tile detections -> one conf-descending list -> greedy walk
+struct TileMergeArgs {
+  const float* tile_dets;      // (T, 300, 6): rows of yfv2_detect_frames_u8, conf-descending per tile, tile coordinates
+  const int32_t* tile_count;   // (T)
+  const int32_t* table;        // device int32: [T][4] = x0, y0, k0, k1 (k0 <= k < k1: the tiles of tile k's frame), then [F][2] = k0, k1
+  int T, F;
+  float* geo;                  // workspace [T * 300] float4: x1, y1, x2, y2 in frame coordinates; frame f's ordered list starts at k0 * 300
+  float* meta;                 // workspace [T * 300] float4: conf, class, origin k * 300 + r (int bits), area
+  double thres;
+  int metric;                  // 0: IoU, 1: intersection over the smaller box
+  int max_out;                 // 1 .. 4096 (the kept set lives in LDS: 24 bytes per row)
+  float* dets;                 // (F, max_out, 6)
+  int32_t* src;                // (F, max_out) or null
+  int32_t* count;              // (F)
+};
+void yfv2_launch_tile_merge(const TileMergeArgs& a, hipStream_t s);   // two launches: rank + scatter, then one workgroup per frame
 // ---- anchor k-means (yfv2_anchors.hip; genanchors.py:67-102): one pass = assign + partial sums, then finalise
 constexpr int YFV2_KM_CH = 1024;    // points per chunk: part of the RESULT's definition (the summation tree), never tuned per device
 constexpr int YFV2_KM_MAXK = 32;

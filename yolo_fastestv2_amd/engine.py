@@ -5,7 +5,7 @@ import ctypes as C
 
 import torch
 
-from . import _lib
+from . import _lib, tiling
 from ._lib import MAX_DET, Config, TensorDesc, check
 
 LOGIT_ORDER = ("reg_2", "obj_2", "cls_2", "reg_3", "obj_3", "cls_3")  # detector.py:47
@@ -281,6 +281,76 @@ class Engine:
         _lib.check(_lib.lib().yfv2_detect_frames_u8(self._h, arr, B, float(conf_thres), float(iou_thres), _ptr(dets), _ptr(idx), _ptr(cnt),
                                                     _stream(self.device)), self._h)
         return dets, idx, cnt
+
+    # ---- tiled detection of large frames (include/yfv2.h yfv2_merge_tiles / yfv2_detect_tiled_u8) ----------------
+    def new_tiled_buffers(self, F, max_out=MAX_DET):
+        """(dets (F, max_out, 6) fp32, src (F, max_out) int32, count (F) int32) for detect_tiled / merge_tiles"""
+        return (torch.empty((F, max_out, 6), device=self.device, dtype=torch.float32),
+                torch.empty((F, max_out), device=self.device, dtype=torch.int32), torch.empty((F,), device=self.device, dtype=torch.int32))
+
+    def _tiled_out(self, out, F, max_out):
+        if out is None:
+            return self.new_tiled_buffers(F, max_out)
+        dets, src, cnt = out
+        for t, shape, dt in ((dets, (F, max_out, 6), torch.float32), (src, (F, max_out), torch.int32), (cnt, (F,), torch.int32)):
+            if t is None and shape == (F, max_out):
+                continue            # src is optional
+            if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != dt or t.device != self.device or not t.is_contiguous():
+                raise ValueError("out must be contiguous (dets %s fp32, src %s int32 or None, count %s int32) on %s" % (
+                    (F, max_out, 6), (F, max_out), (F,), self.device))
+        return dets, src, cnt
+
+    def merge_tiles(self, tile_dets, tile_count, tiles, F, merge_thres, metric="iou", max_out=MAX_DET, out=None):
+        """The merge alone: tile_dets (T, 300, 6) fp32 / tile_count (T) int32 on the device in detect_frames' layout (tile
+        coordinates), tiles = T tuples (frame, x0, y0, width, height) with non-decreasing frame in [0, F).  Every frame's rows are
+        moved into the frame, ordered by conf (stable over tile, row) and walked greedily: a row is dropped if a kept row of the
+        same class matches it by more than merge_thres (metric "iou", or "ios" = intersection over the smaller box).  Returns
+        (dets (F, max_out, 6), src (F, max_out) = tile * 300 + row of each kept row, count (F)); rows beyond count are not
+        written.  Enqueue only."""
+        code = tiling.metric_code(metric)
+        arr = tiling.tile_table(tiles)
+        T, F, max_out = len(arr), int(F), int(max_out)
+        if (not torch.is_tensor(tile_dets) or tuple(tile_dets.shape) != (T, MAX_DET, 6) or tile_dets.dtype != torch.float32 or tile_dets.device != self.device
+                or not torch.is_tensor(tile_count) or tuple(tile_count.shape) != (T,) or tile_count.dtype != torch.int32 or tile_count.device != self.device):
+            raise ValueError("tile_dets must be fp32 (%d,%d,6) and tile_count int32 (%d,) on %s" % (T, MAX_DET, T, self.device))
+        if F < 1 or not 1 <= max_out <= 4096:
+            raise ValueError("F must be >= 1 and max_out in 1..4096")
+        tile_dets, tile_count = tile_dets.contiguous(), tile_count.contiguous()
+        dets, src, cnt = self._tiled_out(out, F, max_out)
+        check(_lib.lib().yfv2_merge_tiles(self._h, _ptr(tile_dets), _ptr(tile_count), arr, T, F, float(merge_thres), code, max_out, _ptr(dets),
+                                          _ptr(src) if src is not None else None, _ptr(cnt), _stream(self.device)), self._h)
+        return dets, src, cnt
+
+    def detect_tiled(self, frames, tiles=None, conf_thres=0.3, iou_thres=0.4, merge_thres=None, metric="iou", max_out=MAX_DET,
+                     tile=(352, 352), overlap=(64, 64), include_full=False, out=None, check=True):
+        """Detection on frames larger than the network's input: every tile (a crop of its frame, read in place) goes through
+        detect_frames' path, the boxes move into frame coordinates and one greedy pass per frame removes the duplicates the
+        overlaps produce - on the device, in one call.  frames: list of uint8 (h_i, w_i, 3) device tensors; tiles: list of
+        (frame, x0, y0, width, height), frame non-decreasing - None plans every frame with `tile`, `overlap`, `include_full`
+        (tiling.plan_tiles).  merge_thres None = iou_thres; metric "iou" or "ios" (intersection over the smaller box: merges an
+        object cut by a tile edge with its whole view next door).  Returns (dets (F, max_out, 6), src (F, max_out), count (F));
+        src = tile * 300 + row in that tile's detections.  The number of tiles is this call's batch: max_batch grows to it.
+        Enqueue only (the first call on a handle allocates its tile workspaces and waits once); check= as in detect()."""
+        self._need_anchors("detect_tiled")
+        code = tiling.metric_code(metric)
+        max_out = int(max_out)
+        if not 1 <= max_out <= 4096:
+            raise ValueError("max_out must be in 1..4096, got %d" % max_out)
+        if merge_thres is None:
+            merge_thres = iou_thres
+        if check and self.peek_nonfinite():
+            self.check_finite("detect_tiled (an earlier call on this handle)")
+        farr, keep = self._frame_table(frames)
+        F = len(keep)
+        if tiles is None:
+            tiles = [t for f, fr in enumerate(keep) for t in tiling.plan_tiles(int(fr.shape[0]), int(fr.shape[1]), tile, overlap, include_full, frame=f)]
+        tarr = tiling.tile_table(tiles)
+        T = len(tarr)
+        self.ensure_batch(T)
+        dets, src, cnt = self._tiled_out(out, F, max_out)
+        _lib.check(_lib.lib().yfv2_detect_tiled_u8(self._h, farr, F, tarr, T, float(conf_thres), float(iou_thres), float(merge_thres), code, max_out,
+                                                   _ptr(dets), _ptr(src) if src is not None else None, _ptr(cnt), _stream(self.device)), self._h)
+        return dets, src, cnt
 
     def batch_statistics(self, dets, cnt, targets, iou_threshold, sync=True):
         """True-positive flags (B, 300) int32 for the padded detections of nms()/detect() against targets (T,6)

@@ -21,6 +21,7 @@ import contextlib
 
 import torch
 
+from . import tiling
 from .engine import Engine
 
 
@@ -44,6 +45,7 @@ class DetectPipeline:
         self._serial = 0
         self._last = [None] * self.depth          # serial of the ticket that owns each slot's buffers
         self._readers = [[] for _ in range(self.depth)]   # events recorded on the consumer streams result() ordered behind a slot
+        self._tiled_buffers = [None] * self.depth         # (dets, src, count) of submit_tiled, per slot
 
     def load_state_dict(self, state_dict):
         for e in self.engines:
@@ -121,6 +123,43 @@ class DetectPipeline:
                 for f in frames:
                     f.record_stream(self.streams[j])
             out = eng.detect_frames(frames, conf_thres, iou_thres, out=(dets[:B], idx[:B], cnt[:B]), check=False)
+            ev = torch.cuda.Event()
+            ev.record(self.streams[j])
+        return Ticket(j, ev, out, self._serial)
+
+    def submit_tiled(self, frames, conf_thres, iou_thres, wait_for_input=True, **tiled):
+        """`submit` for large frames cut into tiles (Engine.detect_tiled; `tiled`: its keyword arguments tiles, merge_thres, metric, max_out,
+        tile, overlap, include_full) on the next slot.  The tiles are the batch: their number must not exceed max_batch.  The ticket's
+        tensors are (dets (F, max_out, 6), src, count), owned by the slot like every ticket's."""
+        if "out" in tiled or "check" in tiled:
+            raise ValueError("submit_tiled owns `out` and `check`")
+        if tiled.get("tiles") is None:      # planned here: the number of tiles is the batch, and a slot's handle does not grow
+            plan = {k: tiled.pop(k) for k in ("tile", "overlap", "include_full") if k in tiled}
+            tiled["tiles"] = [t for f, fr in enumerate(frames) for t in tiling.plan_tiles(int(fr.shape[0]), int(fr.shape[1]), frame=f, **plan)]
+        T = len(tiled["tiles"])
+        if T > self.max_batch:
+            raise ValueError("%d tiles exceed max_batch %d" % (T, self.max_batch))
+        cur = torch.cuda.current_stream(self.device)
+        jn = self._serial % self.depth
+        if self.engines[jn].peek_nonfinite():     # as in submit(): the slot's previous batch, before the rotation advances
+            try:
+                with torch.cuda.stream(self.streams[jn]):
+                    self.engines[jn].check_finite("DetectPipeline.submit_tiled: the batch of ticket #%s (slot %d), the last one run on this slot" % (self._last[jn], jn))
+            except Exception as e:
+                e.slot, e.serial = jn, self._last[jn]
+                raise
+        with self.slot() as (j, eng, _):
+            for ev in self._readers[j]:
+                self.streams[j].wait_event(ev)
+            self._readers[j] = []
+            if wait_for_input:
+                self.streams[j].wait_stream(cur)
+                for f in frames:
+                    f.record_stream(self.streams[j])
+            F, max_out = len(frames), int(tiled.pop("max_out", 300))
+            if self._tiled_buffers[j] is None or tuple(self._tiled_buffers[j][0].shape[:2]) != (F, max_out):
+                self._tiled_buffers[j] = eng.new_tiled_buffers(F, max_out)      # (allocated on the slot's stream, reused while the shape repeats)
+            out = eng.detect_tiled(frames, conf_thres=conf_thres, iou_thres=iou_thres, max_out=max_out, out=self._tiled_buffers[j], check=False, **tiled)
             ev = torch.cuda.Event()
             ev.record(self.streams[j])
         return Ticket(j, ev, out, self._serial)
