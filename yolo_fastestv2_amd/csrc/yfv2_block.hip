@@ -488,7 +488,7 @@ int yfv2_s1chain_image_floats() { return CH6_IMG_FL; }
 bool yfv2_s1chain_supported(int c2, int H, int W) {
   if (c2 != 48 || H < 2 || (H & 1) || (W & 1)) return false;
   if ((H / 2) * (W / 2) > 16 * 8) return false;            // one 2x2 patch per (wave, lane & 15): 8 waves
-  if (yfv2_s1chain_park_floats(H, W, 7) > 24L * (4 * H) * (4 * W)) return false;   // the park scratch is a stem-sized temporary (yfv2_api.hip: t1)
+  if (yfv2_s1chain_park_floats(H, W, 7) > 24L * (4 * H) * (4 * W)) return false;   // the park scratch is a stem-sized temporary (yfv2_plan.h: Workspace::t1)
   return s1chain_lds_floats(H, W) * 4 <= 160 * 1024;
 }
 

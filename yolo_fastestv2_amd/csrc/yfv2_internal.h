@@ -1,5 +1,5 @@
 // yfv2_internal.h - launch-argument structs shared by the kernel translation
-// units, the host-side weight packer (yfv2_pack.hip) and the host-side plan (yfv2_api.hip).  Not part of the public ABI.
+// units, the host-side weight packer (yfv2_pack.hip) and the host-side plan (yfv2_plan.hip).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>

@@ -1,6 +1,6 @@
 // yfv2_pack.h - the host-side weight packer of libyfv2.so: reference state_dict -> one blob of kernel-ready parameters
 // (BatchNorm folded, every filter laid out in the register / LDS order its kernel reads).  Host only: no kernel, no HIP
-// runtime call.  The layouts are specified above the definitions in yfv2_pack.hip; the plan (yfv2_api.hip: PlanBuilder)
+// runtime call.  The layouts are specified above the definitions in yfv2_pack.hip; the plan (yfv2_plan.hip: PlanBuilder)
 // decides which images a configuration needs and in which order they enter the blob.  Not part of the public ABI.
 #pragma once
 #include <cstddef>

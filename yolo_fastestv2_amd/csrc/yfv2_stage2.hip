@@ -17,7 +17,7 @@
 // Activation layout of stage 2 ("pair planes"): [image][24 pairs][H][W][2] fp32.  A lane = a pixel reads /
 // writes one 8-byte pair per instruction, 16 lanes = 128 contiguous bytes.  Which logical channel sits in
 // which (pair, element) slot, and in which of the two stage buffers a pair currently lives, is tracked on
-// the host (yfv2_api.hip, Stage2Layout): a stride-1 block only ever reads the 12 pairs that hold its odd
+// the host (yfv2_plan.hip, Stage2Layout): a stride-1 block only ever reads the 12 pairs that hold its odd
 // (branch) channels and writes the branch result into the other buffer's copy of the same 12 pairs; the
 // even (pass-through) channels are never touched, channel_shuffle / concat are pure bookkeeping that is
 // folded into the order of the filter columns / rows when the weights are packed.
