@@ -336,6 +336,41 @@ YFV2_API int yfv2_anchor_kmeans(yfv2_handle h, const double* wh /* device (N,2) 
  * depends on it (tests/test_gpu_anchors.py shows that); it only trades host waits against launches that return at once. */
 YFV2_API int yfv2_debug_kmeans_group(yfv2_handle h, int32_t group);
 
+/* ---- average precision over a whole validation set: the last line of evaluation() (utils/utils.py:397) ---- */
+
+typedef struct yfv2_ap_result {
+  int32_t struct_size;          /* in: sizeof(yfv2_ap_result) of the caller's header (the struct may grow at its end; 0 = this header's) */
+  int32_t classes_present;      /* distinct target classes */
+  int32_t bad_input;            /* 1: a target class that is not an integer in 0..254, or a conf that is not finite; the rest is then undefined */
+  int64_t n_gt[256], n_pred[256];    /* per class: targets, predictions (0 where the class has no target) */
+  double p[256], r[256], ap[256];    /* per class: final precision, final recall, average precision; 0 where the class is absent */
+  double mean_p, mean_r, mean_ap, mean_f1;   /* over the present classes in ascending order, added one after the other on the host; NaN if there is none */
+} yfv2_ap_result;
+
+/* replaces: utils/utils.py:136-192 ap_per_class with :110-134 compute_ap, the host tail of evaluation() (:397).
+ *   tp          device (N) int32: 1 = true positive, what yfv2_batch_statistics writes (any non-zero value counts as 1)
+ *   conf        device (N) fp32 confidences, pred_cls device (N) fp32 class labels of the same detections
+ *   target_cls  device (T) fp32: the class of every ground-truth object; each must be an integer in 0..254
+ *   out         HOST; set out->struct_size before the call
+ * TIE RULE.  Detections are ranked by conf descending and, where conf is equal (+0 and -0 are equal), by ascending input index:
+ * np.argsort(-conf, kind="stable").  The reference calls np.argsort(-conf), an unstable sort whose order among equal confidences
+ * is an accident of numpy's implementation; this is the ONLY place where the result may differ from the reference's by more
+ * than the order of a summation.  Per class c of target_cls: n_gt / n_pred = its count in target_cls / pred_cls; over its
+ * detections in rank order prec_i = tpc_i / (i + 1), rec_i = tpc_i / (n_gt + 1e-16) with tpc the running count of tp; p and r
+ * are the last prec and rec; ap = sum over the true positives of (rec_i - rec_{i-1}) * max(prec_j, j >= i) - compute_ap's
+ * envelope sum (its closing term to recall 1 is +-0).  A pred_cls that equals no target class is ignored, as the reference's
+ * `pred_cls == c` ignores it; a class without predictions scores 0 on all three.
+ * Every output bit is a function of the four arrays alone: the ap sum is one fixed tree over chunks of 1024 ranked positions
+ * (DESIGN.md 4.12), no floating-point atomics.  A target class outside 0..254 or not an integer, or a NaN / infinite conf,
+ * sets bad_input (still YFV2_OK; such a value is never used as an index).  N = 0 gives all zeros; T = 0 gives
+ * classes_present = 0 and NaN means (np.mean of an empty list).  N and T are limited to 2^31 - 1 (YFV2_ERR_ARG beyond, as for
+ * NULL arrays, negative sizes or arrays that are not 4-byte aligned - before anything is enqueued).
+ * Work is enqueued on `stream`; like yfv2_anchor_kmeans this call WAITS for the stream before it returns.  Works on any handle;
+ * touches nothing of the forward / detect workspace (its own buffer: a call needs about 17 bytes per detection; when N exceeds
+ * what earlier calls needed it is re-allocated - one device synchronisation - at 1.5 times the need, about 25 bytes per detection). */
+YFV2_API int yfv2_ap_per_class(yfv2_handle h, const int32_t* tp, const float* conf, const float* pred_cls, int64_t N,
+                               const float* target_cls, int64_t T, yfv2_ap_result* out, void* stream);
+
 /* ---- the rest of the training path: one iteration of train.py:96-123 on the device.
  * Parameters, their gradients and the BatchNorm buffers are the CALLER's device tensors in the reference's own layouts and
  * under the reference's state_dict names; nothing is copied.  Correctness-first kernels (plain NCHW fp32, float64

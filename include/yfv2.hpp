@@ -145,6 +145,31 @@ class Detector {
     return YFV2_OK;
   }
 
+  /* utils.py:136-192 ap_per_class over HOST arrays (yfv2.h yfv2_ap_per_class: equal confidences rank by input index): one upload,
+     the device call, `out` filled on return.  Needs no weights.  out.bad_input = 1: a target class outside 0..254 or a conf that is not finite. */
+  int apPerClass(const int32_t* tp, const float* conf, const float* pred_cls, int64_t n, const float* target_cls, int64_t t, yfv2_ap_result& out) {
+    if (!ok()) return rc_;
+    if (n < 0 || t < 0 || (n > 0 && (!tp || !conf || !pred_cls)) || (t > 0 && !target_cls)) return fail(YFV2_ERR_ARG, "apPerClass: bad argument");
+    const size_t bytes = 4 * (3 * (size_t)n + (size_t)t);
+    char* d = nullptr;
+    if (bytes && hipMalloc(reinterpret_cast<void**>(&d), bytes) != hipSuccess) return fail(YFV2_ERR_DEVICE, "hipMalloc for the statistics failed");
+    const void* src[4] = {tp, conf, pred_cls, target_cls};
+    const size_t len[4] = {4 * (size_t)n, 4 * (size_t)n, 4 * (size_t)n, 4 * (size_t)t};
+    char* at[4];
+    size_t off = 0;
+    for (int i = 0; i < 4; ++i) {
+      at[i] = len[i] ? d + off : nullptr;
+      if (len[i] && hipMemcpyAsync(at[i], src[i], len[i], hipMemcpyHostToDevice, stream_) != hipSuccess) { (void)hipFree(d); return fail(YFV2_ERR_DEVICE, "upload failed"); }
+      off += len[i];
+    }
+    out.struct_size = (int32_t)sizeof(yfv2_ap_result);
+    const int rc = yfv2_ap_per_class(h_, reinterpret_cast<const int32_t*>(at[0]), reinterpret_cast<const float*>(at[1]), reinterpret_cast<const float*>(at[2]), n,
+                                     reinterpret_cast<const float*>(at[3]), t, &out, stream_);   // waits for the stream
+    if (d) (void)hipFree(d);
+    if (rc != YFV2_OK) return fail(rc, yfv2_last_error(h_));
+    return YFV2_OK;
+  }
+
  private:
   int fail(int rc, const std::string& msg) { err_ = msg; return rc; }
   yfv2_handle h_ = nullptr;

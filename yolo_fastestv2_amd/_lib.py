@@ -84,6 +84,13 @@ class KmeansInfo(C.Structure):
                 ("bad_input", C.c_int32)]
 
 
+class ApResult(C.Structure):
+    """yfv2_ap_result (include/yfv2.h): per-class precision, recall and average precision of a whole validation set."""
+    _fields_ = [("struct_size", C.c_int32), ("classes_present", C.c_int32), ("bad_input", C.c_int32),
+                ("n_gt", C.c_int64 * 256), ("n_pred", C.c_int64 * 256), ("p", C.c_double * 256), ("r", C.c_double * 256), ("ap", C.c_double * 256),
+                ("mean_p", C.c_double), ("mean_r", C.c_double), ("mean_ap", C.c_double), ("mean_f1", C.c_double)]
+
+
 class Yfv2Error(RuntimeError):
     def __init__(self, code, msg):
         super().__init__("libyfv2 error %d: %s" % (code, msg))
@@ -135,6 +142,7 @@ _PROTOTYPES = {
     "yfv2_anchor_kmeans": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                      C.POINTER(KmeansInfo), C.c_void_p]),
     "yfv2_debug_kmeans_group": (C.c_int, [C.c_void_p, C.c_int32]),
+    "yfv2_ap_per_class": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(ApResult), C.c_void_p]),
     "yfv2_debug_plan_dryrun": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "yfv2_debug_plan_dryrun_ex": (C.c_int, [C.c_void_p, C.POINTER(Plan), C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "yfv2_debug_plan_image": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_char_p, C.c_int32, C.c_void_p, C.c_int64]),

@@ -69,6 +69,10 @@ struct yfv2_ctx {
   int32_t* h_km_word = nullptr;
   int32_t* d_km_word = nullptr;
   int km_group = 8;              // passes enqueued between two looks at km_word (yfv2_debug_kmeans_group); changes no output bit
+  // average precision (yfv2_ap_per_class): the result head, the sort's table and ping-pong buffers, the chunk sums (yfv2_ap.hip);
+  // grown on demand (a growth waits for the device)
+  void* d_ap_ws = nullptr;
+  size_t ap_ws_bytes = 0;
   void* train = nullptr;         // training state (yfv2_train.hip), created by yfv2_train_bind
   long long* d_trace = nullptr;  // YFV2_TRACE=1: cycle stamps of the last fused s1 launch (debug)
   int trace_step = -1;           // YFV2_TRACE_STEP=i: only launch i of the plan writes stamps (towers: only then)
@@ -455,6 +459,7 @@ void yfv2_destroy(yfv2_handle h) {
   if (h->d_probe) (void)hipFree(h->d_probe);
   if (h->d_loss_ws) (void)hipFree(h->d_loss_ws);
   if (h->d_km_ws) (void)hipFree(h->d_km_ws);
+  if (h->d_ap_ws) (void)hipFree(h->d_ap_ws);
   if (h->h_km_word) (void)hipHostFree(h->h_km_word);
   if (h->train) { yfv2_train_release(h->train); h->train = nullptr; }
   if (h->d_params) (void)hipFree(h->d_params);
@@ -902,6 +907,44 @@ int yfv2_anchor_kmeans(yfv2_handle h, const double* wh, int64_t N, double* centr
 int yfv2_debug_kmeans_group(yfv2_handle h, int32_t group) {
   if (!h || group < 1 || group > 64) return fail(h, YFV2_ERR_ARG, "yfv2_debug_kmeans_group: group must be in 1..64");
   h->km_group = group;
+  return YFV2_OK;
+}
+
+// utils/utils.py:110-192 on the device (yfv2_ap.hip): rank, per-class curve, one fixed summation tree; the means on the host.
+int yfv2_ap_per_class(yfv2_handle h, const int32_t* tp, const float* conf, const float* pred_cls, int64_t N, const float* target_cls,
+                      int64_t T, yfv2_ap_result* out, void* stream) {
+  if (!h) return fail(nullptr, YFV2_ERR_ARG, "null handle");
+  if (!out) return fail(h, YFV2_ERR_ARG, "yfv2_ap_per_class: out is required");
+  if (N < 0 || T < 0) return fail(h, YFV2_ERR_ARG, "yfv2_ap_per_class: N and T must not be negative");
+  if (N > 0x7fffffffLL || T > 0x7fffffffLL) return fail(h, YFV2_ERR_ARG, "yfv2_ap_per_class: N and T are limited to 2^31 - 1 (the payload holds tp in bit 31)");
+  if (N > 0 && (!tp || !conf || !pred_cls)) return fail(h, YFV2_ERR_ARG, "yfv2_ap_per_class: null pointer (tp, conf and pred_cls are required when N > 0)");
+  if (T > 0 && !target_cls) return fail(h, YFV2_ERR_ARG, "yfv2_ap_per_class: null pointer (target_cls is required when T > 0)");
+  if (((reinterpret_cast<uintptr_t>(tp) | reinterpret_cast<uintptr_t>(conf) | reinterpret_cast<uintptr_t>(pred_cls) | reinterpret_cast<uintptr_t>(target_cls)) & 3) != 0)
+    return fail(h, YFV2_ERR_ARG, "yfv2_ap_per_class: the arrays must be 4-byte aligned");
+  DeviceGuard guard(h->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const size_t need = yfv2_ap_ws_bytes(N);
+  if (need > h->ap_ws_bytes) {
+    HIP_TRY(h, hipDeviceSynchronize());               // (every earlier call waited for its stream; another stream's work may not have)
+    if (h->d_ap_ws) { (void)hipFree(h->d_ap_ws); h->d_ap_ws = nullptr; h->ap_ws_bytes = 0; }
+    const size_t cap = need + need / 2;
+    HIP_TRY(h, hipMalloc(&h->d_ap_ws, cap));
+    h->ap_ws_bytes = cap;
+  }
+  ApArgs a{};
+  a.tp = tp; a.conf = conf; a.pred_cls = pred_cls; a.N = N; a.target_cls = target_cls; a.T = T;
+  yfv2_ap_carve(a, static_cast<char*>(h->d_ap_ws));
+  yfv2_launch_ap(a, s);
+  HIP_TRY(h, hipGetLastError());
+  ApHead head;
+  HIP_TRY(h, hipMemcpyAsync(&head, a.head, sizeof(ApHead), hipMemcpyDeviceToHost, s));
+  HIP_TRY(h, hipStreamSynchronize(s));
+  yfv2_ap_result res{};
+  yfv2_ap_finish(head, &res);
+  // (a caller built against a shorter struct gets the fields it has)
+  const size_t n = out->struct_size > 0 && (size_t)out->struct_size < sizeof(yfv2_ap_result) ? (size_t)out->struct_size : sizeof(yfv2_ap_result);
+  res.struct_size = (int32_t)n;
+  std::memcpy(out, &res, n);
   return YFV2_OK;
 }
 

@@ -457,6 +457,32 @@ struct KmArgs {
   int32_t* host_word;    // host-mapped int32[5]: done, iterations, converged, empty_cluster, bad_input
 };
 void yfv2_launch_km_pass(const KmArgs& a, int pass, int last, hipStream_t s);
+// ---- average precision per class (yfv2_ap.hip; utils/utils.py:110-192 compute_ap + ap_per_class)
+constexpr int YFV2_AP_CH = 1024;     // terms per chunk of the AP sum: part of the RESULT's definition (the summation tree), never tuned
+constexpr int YFV2_AP_TILE = 2048;   // detections per workgroup of a radix-sort pass (changes no output bit: the sort is stable)
+struct ApHead {                      // zeroed before every call, copied to the host in one piece after it
+  long long n_gt[256], n_pred[256];
+  double p[256], r[256], ap[256];
+  int32_t bad, pad;
+};
+struct ApArgs {
+  const int32_t* tp; const float* conf; const float* pred_cls;   // (N)
+  int64_t N;
+  const float* target_cls;                                        // (T)
+  int64_t T;
+  uint32_t* key[2];    // (N) each: the order-preserving image of -conf, ping-pong
+  uint32_t* val[2];    // (N) each: input index | tp << 31, ping-pong; the ranked list ends in val[1]
+  uint32_t* hist;      // [256 digits][nblk]: per-workgroup digit counts, scanned in place along each row
+  uint32_t* tot;       // [256]: row totals of the current pass
+  double* part;        // chunk sums of the AP terms: class c's start at floor(segment start / YFV2_AP_CH) + c
+  ApHead* head;
+  int nblk;            // ceil(N / YFV2_AP_TILE)
+};
+size_t yfv2_ap_ws_bytes(int64_t N);                                   // the whole workspace, ApHead first
+void yfv2_ap_carve(ApArgs& a, char* ws);                              // sets the workspace pointers of a (N already set)
+void yfv2_launch_ap(const ApArgs& a, hipStream_t s);                  // memset of the head + every launch
+struct yfv2_ap_result;
+void yfv2_ap_finish(const ApHead& head, yfv2_ap_result* out);         // host: head -> result, means sequential over the present classes
 // ---- measurement: effective shader clock (yfv2_probe.hip)
 struct ClockProbeArgs {
   unsigned long long* out;       // [workgroups][4]: shader cycles, reference ticks, XCC id, (unused)

@@ -411,6 +411,34 @@ class Engine:
         """Test hook: passes anchor_kmeans enqueues between two looks at the verdict (1..64, default 8); changes no output bit."""
         check(_lib.lib().yfv2_debug_kmeans_group(self._h, int(group)), self._h)
 
+    # ---- average precision over a validation set: utils/utils.py:110-192 on the device ----------------------------------
+    def ap_per_class(self, tp, conf, pred_cls, target_cls):
+        """Per-class precision, recall and average precision (include/yfv2.h yfv2_ap_per_class): ``tp`` (N) int32, ``conf`` and
+        ``pred_cls`` (N) float32, ``target_cls`` (T) float32, all tensors on this engine's device.  Returns a dict of numpy arrays
+        indexed by class 0..255 - ``p``, ``r``, ``ap`` (float64), ``n_gt``, ``n_pred`` (int64) - with ``present`` (the ascending
+        classes of target_cls), ``bad_input`` and ``means`` = (mean_p, mean_r, mean_ap, mean_f1) added class after class by the
+        library.  Equal confidences rank by input index (np.argsort(-conf, kind="stable")).  Waits for the stream."""
+        import numpy as np
+        want = (("tp", tp, torch.int32), ("conf", conf, torch.float32), ("pred_cls", pred_cls, torch.float32), ("target_cls", target_cls, torch.float32))
+        for name, t, dt in want:
+            if not torch.is_tensor(t) or t.dtype != dt or t.device != self.device or t.dim() != 1:
+                raise ValueError("%s must be a 1-d %s tensor on %s" % (name, dt, self.device))
+        tp, conf, pred_cls, target_cls = tp.contiguous(), conf.contiguous(), pred_cls.contiguous(), target_cls.contiguous()
+        N, T = int(tp.shape[0]), int(target_cls.shape[0])
+        if int(conf.shape[0]) != N or int(pred_cls.shape[0]) != N:
+            raise ValueError("tp, conf and pred_cls must have one length (got %d, %d, %d)" % (N, conf.shape[0], pred_cls.shape[0]))
+        res = _lib.ApResult()
+        res.struct_size = C.sizeof(_lib.ApResult)
+        check(_lib.lib().yfv2_ap_per_class(self._h, _ptr(tp) if N else None, _ptr(conf) if N else None, _ptr(pred_cls) if N else None, N,
+                                           _ptr(target_cls) if T else None, T, C.byref(res), _stream(self.device)), self._h)
+        out = {"n_gt": np.array(res.n_gt, np.int64), "n_pred": np.array(res.n_pred, np.int64),
+               "p": np.array(res.p, np.float64), "r": np.array(res.r, np.float64), "ap": np.array(res.ap, np.float64)}
+        out["present"] = np.flatnonzero(out["n_gt"] > 0)
+        out["bad_input"] = int(res.bad_input)
+        out["classes_present"] = int(res.classes_present)
+        out["means"] = (float(res.mean_p), float(res.mean_r), float(res.mean_ap), float(res.mean_f1))
+        return out
+
     # ---- training path (SURVEY.md 8(f) row 3): train.py:96-123 on the device -----------------------------------------
     def train_bind(self, tensors, grads):
         """tensors: name -> fp32 device tensor for every floating-point state_dict entry (weights, biases, BatchNorm running

@@ -5,7 +5,7 @@ signatures and return types, executed by libyfv2's HIP kernels.  Also
 evaluation loop around the path: ``get_batch_statistics`` (:194-230,
 one kernel launch per batch), ``evaluation`` (:360-397, device-resident until the last line)
 and the dataset-level host arithmetic ``ap_per_class`` / ``compute_ap`` (:110-192, numpy like
-the reference: a few thousand float64 operations once per evaluation).
+the reference) with its device form ``ap_per_class_device`` (a radix sort and one walk per class, yfv2_ap.hip).
 """
 import os
 
@@ -173,11 +173,54 @@ def ap_per_class(tp, conf, pred_cls, target_cls):
     return np.mean(p), np.mean(r), np.mean(ap), np.mean(f1)
 
 
-def evaluation(val_dataloader, cfg, model, device, conf_thres=0.01, nms_thresh=0.4, iou_thres=0.5):
+def _ap_means(out):
+    """the reference's last two lines (utils.py:190-192) over the present classes of an Engine.ap_per_class result"""
+    import numpy as np
+    p, r, ap = out["p"][out["present"]], out["r"][out["present"]], out["ap"][out["present"]]
+    f1 = 2 * p * r / (p + r + 1e-16)
+    return np.mean(p), np.mean(r), np.mean(ap), np.mean(f1)
+
+
+def ap_per_class_device(tp, conf, pred_cls, target_cls, device=None):
+    """``ap_per_class`` on the MI355X (include/yfv2.h yfv2_ap_per_class): the reference's argument order and the same 4-tuple.
+    Arrays, lists or tensors; whatever is not on the device yet is moved there.  Equal confidences rank by input index
+    (``np.argsort(-conf, kind="stable")``; the reference's unstable sort leaves that order to numpy), so mean AP can differ from
+    ``ap_per_class`` where confidences tie; P, R and F1 cannot.  Raises ValueError on a target class that is not an integer in
+    0..254 or a confidence that is not finite."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("ap_per_class_device: no MI355X visible (there is no CPU path)")
+    tensors = [t for t in (tp, conf, pred_cls, target_cls) if torch.is_tensor(t) and t.device.type == "cuda"]
+    if device is not None:
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError("ap_per_class_device: no CPU path, pass the MI355X device (got %s)" % device)
+    else:
+        dev = tensors[0].device if tensors else torch.device("cuda", torch.cuda.current_device())
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+
+    def move(x, dtype):
+        import numpy as np
+        t = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(np.asarray(x, np.float64 if dtype != torch.int32 else None)))
+        if dtype == torch.int32 and t.dtype != torch.int32:
+            t = t != 0
+        return t.to(dev).to(dtype).reshape(-1)
+
+    eng = get_engine(dev, 32, 32, 1, 3)      # no forward workspace is involved: the smallest handle there is
+    out = eng.ap_per_class(move(tp, torch.int32), move(conf, torch.float32), move(pred_cls, torch.float32), move(target_cls, torch.float32))
+    if out["bad_input"]:
+        raise ValueError("ap_per_class_device: a target class is not an integer in 0..254, or a confidence is not a finite number")
+    return _ap_means(out)
+
+
+def evaluation(val_dataloader, cfg, model, device, conf_thres=0.01, nms_thresh=0.4, iou_thres=0.5, *, ap_on_device=False):
     """utils/utils.py:360-397 with the same signature and return value (``ap_per_class``'s 4-tuple, or None when the
     loader is empty).  Per batch: the pre-process (`float()/255`, or none for a uint8 (B,H,W,3) batch), ONE fused
     forward+decode+NMS call and ONE matching launch; detections, true-positive flags and counts stay on the GPU and
-    come back in a single copy after the last batch.  ``model`` is a yolo_fastestv2_amd.Detector."""
+    come back in a single copy after the last batch.  ``model`` is a yolo_fastestv2_amd.Detector.
+    ``ap_on_device=True`` (keyword only): the last line runs on the device too - true-positive flags, confidences, classes and
+    the labels never leave it, one ``Engine.ap_per_class`` call on the last engine used replaces the copy and the numpy
+    ``ap_per_class`` (equal confidences then rank by their order in the run, see ``ap_per_class_device``)."""
     import numpy as np
     device = torch.device(device)
     if device.type != "cuda":
@@ -185,12 +228,16 @@ def evaluation(val_dataloader, cfg, model, device, conf_thres=0.01, nms_thresh=0
     labels, kept = [], []
     engines = set()
     scale = None
+    eng = None
     for imgs, targets in val_dataloader:
         imgs = imgs.to(device)
         u8_hwc = imgs.dtype == torch.uint8 and imgs.dim() == 4 and imgs.shape[-1] == 3
         x = imgs if u8_hwc else imgs.float() / 255.0
         targets = targets.to(device).clone()
-        labels += targets[:, 1].tolist()
+        if ap_on_device:
+            labels.append(targets[:, 1].clone())
+        else:
+            labels += targets[:, 1].tolist()
         # normalised (cx, cy, w, h) -> corner pixels, in fp32 on the device like the reference (:372-376)
         c = targets[:, 2:].clone()
         targets[:, 2] = c[:, 0] - c[:, 2] / 2
@@ -219,6 +266,12 @@ def evaluation(val_dataloader, cfg, model, device, conf_thres=0.01, nms_thresh=0
     if not kept:
         print("---- No detections over whole validation set ----")
         return None
+    if ap_on_device:
+        out = eng.ap_per_class(torch.cat([k[0] for k in kept]), torch.cat([k[1] for k in kept]), torch.cat([k[2] for k in kept]),
+                               torch.cat(labels).float())
+        if out["bad_input"]:
+            raise RuntimeError("evaluation: a label is not an integer class in 0..254, or a confidence is not finite (yfv2_ap_per_class)")
+        return _ap_means(out)
     tp = torch.cat([k[0] for k in kept]).cpu().numpy().astype(np.float64)
     conf = torch.cat([k[1] for k in kept]).cpu().numpy()
     cls = torch.cat([k[2] for k in kept]).cpu().numpy()
