@@ -279,6 +279,22 @@ YFV2_API int yfv2_batch_statistics(yfv2_handle h, const float* dets, const int32
 YFV2_API int yfv2_batch_statistics_async(yfv2_handle h, const float* dets, const int32_t* count, int32_t B, const float* targets,
                                          int32_t T, float iou_threshold, int32_t* tp, void* stream);
 YFV2_API int yfv2_batch_statistics_overflow(yfv2_handle h, int32_t* overflowed, void* stream);
+/* The same matching at K IoU thresholds in ONE launch (for AP at several thresholds, e.g. 0.50:0.05:0.95; the definition stays
+ * the reference's get_batch_statistics at each of them - nothing of pycocotools is modelled).
+ *   thresholds  HOST array of K floats, copied before the call returns; any values, in any order, repeats allowed
+ *   K           1..32
+ *   tpmask      device (B, 300) uint32: bit k of tpmask[b][i] is EXACTLY what yfv2_batch_statistics_async writes to tp[b][i] at
+ *               iou_threshold = thresholds[k] (compared in fp32; a NaN threshold gives a zero bit); bits at and above K are 0
+ * The target with the largest IoU for a detection does not depend on the threshold: it is found once per detection, and only
+ * the walk "above the threshold and still free" runs per threshold (one lane each).  Note that bit k is NOT monotone in the
+ * threshold: a detection can miss at 0.5 because a higher-ranked one took its target, and hit at 0.75 where that one failed.
+ * The 1024-targets-per-image rule and its sticky flag are those of yfv2_batch_statistics_async (the same word, read by
+ * yfv2_batch_statistics_overflow); the blocking form reads it back and fails like yfv2_batch_statistics.  K outside 1..32 or a
+ * NULL thresholds / tpmask is YFV2_ERR_ARG before anything is enqueued. */
+YFV2_API int yfv2_batch_statistics_multi_async(yfv2_handle h, const float* dets, const int32_t* count, int32_t B, const float* targets,
+                                               int32_t T, const float* thresholds /* host */, int32_t K, uint32_t* tpmask, void* stream);
+YFV2_API int yfv2_batch_statistics_multi(yfv2_handle h, const float* dets, const int32_t* count, int32_t B, const float* targets,
+                                         int32_t T, const float* thresholds /* host */, int32_t K, uint32_t* tpmask, void* stream);
 
 /* replaces: utils/loss.py:130-208 compute_loss (with build_target :53-124 and bbox_iou(CIoU) :8-51) and, when grad6 is
  * not NULL, what autograd derives from it: the gradient of the TOTAL loss w.r.t. each of the six logit maps (same
@@ -370,6 +386,22 @@ typedef struct yfv2_ap_result {
  * what earlier calls needed it is re-allocated - one device synchronisation - at 1.5 times the need, about 25 bytes per detection). */
 YFV2_API int yfv2_ap_per_class(yfv2_handle h, const int32_t* tp, const float* conf, const float* pred_cls, int64_t N,
                                const float* target_cls, int64_t T, yfv2_ap_result* out, void* stream);
+/* yfv2_ap_per_class at K thresholds in one pass (mAP@[.5:.95] is the mean of out[k].mean_ap over the ten thresholds; the
+ * definition is the reference's ap_per_class + compute_ap at each threshold - no 101-point interpolation, no crowd flags, no
+ * area ranges).
+ *   tpmask  device (N) uint32: bit k = tp at threshold k, what yfv2_batch_statistics_multi writes; bits at and above K are ignored
+ *   K       1..32
+ *   out     HOST, K records one after the other; set out[k].struct_size before the call (out[0]'s is the distance between records)
+ * out[k] equals, bit for bit and in every field, what yfv2_ap_per_class returns for tp[i] = (tpmask[i] >> k) & 1: the targets'
+ * histogram, the keys and the five sort passes run once (the rank does not look at tp), one launch brings the masks into rank
+ * order, and the per-class walk - the same device code, reading bit k where the single form reads its tp bit - runs on a
+ * (class, threshold) grid.  The tie rule, bad_input (reported in every record), the limits on N and T, the alignment and NULL
+ * checks and "waits for the stream" are yfv2_ap_per_class's; K outside 1..32 is YFV2_ERR_ARG.  Workspace: about 21 bytes per
+ * detection (the single form's 17 and the 4 of the permuted mask) plus K result blocks of 10 KB and K sets of chunk sums (8 bytes
+ * per 1024 detections each); re-allocated at 1.5 times the need, about 32 bytes per detection, when N or K exceed what earlier
+ * calls needed. */
+YFV2_API int yfv2_ap_per_class_multi(yfv2_handle h, const uint32_t* tpmask, const float* conf, const float* pred_cls, int64_t N,
+                                     const float* target_cls, int64_t T, int32_t K, yfv2_ap_result* out, void* stream);
 
 /* ---- the rest of the training path: one iteration of train.py:96-123 on the device.
  * Parameters, their gradients and the BatchNorm buffers are the CALLER's device tensors in the reference's own layouts and

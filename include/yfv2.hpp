@@ -148,12 +148,26 @@ class Detector {
   /* utils.py:136-192 ap_per_class over HOST arrays (yfv2.h yfv2_ap_per_class: equal confidences rank by input index): one upload,
      the device call, `out` filled on return.  Needs no weights.  out.bad_input = 1: a target class outside 0..254 or a conf that is not finite. */
   int apPerClass(const int32_t* tp, const float* conf, const float* pred_cls, int64_t n, const float* target_cls, int64_t t, yfv2_ap_result& out) {
+    return apCall(tp, conf, pred_cls, n, target_cls, t, 0, &out);
+  }
+
+  /* apPerClass at k = 1..32 thresholds in one pass (yfv2.h yfv2_ap_per_class_multi): tpmask holds tp at threshold j in bit j, out points
+     at k records; out[j] is what apPerClass reports for tp = bit j.  The reference's ap_per_class at each threshold, nothing of pycocotools. */
+  int apPerClassMulti(const uint32_t* tpmask, const float* conf, const float* pred_cls, int64_t n, const float* target_cls, int64_t t, int k,
+                      yfv2_ap_result* out) {
+    if (ok() && (k < 1 || k > 32)) return fail(YFV2_ERR_ARG, "apPerClassMulti: k must be in 1..32");
+    return apCall(tpmask, conf, pred_cls, n, target_cls, t, k, out);
+  }
+
+ private:
+  /* both AP methods: k = 0 is the single-threshold form (first = tp), k >= 1 the multi form (first = tpmask, k records) */
+  int apCall(const void* first, const float* conf, const float* pred_cls, int64_t n, const float* target_cls, int64_t t, int k, yfv2_ap_result* out) {
     if (!ok()) return rc_;
-    if (n < 0 || t < 0 || (n > 0 && (!tp || !conf || !pred_cls)) || (t > 0 && !target_cls)) return fail(YFV2_ERR_ARG, "apPerClass: bad argument");
+    if (!out || n < 0 || t < 0 || (n > 0 && (!first || !conf || !pred_cls)) || (t > 0 && !target_cls)) return fail(YFV2_ERR_ARG, "apPerClass: bad argument");
     const size_t bytes = 4 * (3 * (size_t)n + (size_t)t);
     char* d = nullptr;
     if (bytes && hipMalloc(reinterpret_cast<void**>(&d), bytes) != hipSuccess) return fail(YFV2_ERR_DEVICE, "hipMalloc for the statistics failed");
-    const void* src[4] = {tp, conf, pred_cls, target_cls};
+    const void* src[4] = {first, conf, pred_cls, target_cls};
     const size_t len[4] = {4 * (size_t)n, 4 * (size_t)n, 4 * (size_t)n, 4 * (size_t)t};
     char* at[4];
     size_t off = 0;
@@ -162,15 +176,17 @@ class Detector {
       if (len[i] && hipMemcpyAsync(at[i], src[i], len[i], hipMemcpyHostToDevice, stream_) != hipSuccess) { (void)hipFree(d); return fail(YFV2_ERR_DEVICE, "upload failed"); }
       off += len[i];
     }
-    out.struct_size = (int32_t)sizeof(yfv2_ap_result);
-    const int rc = yfv2_ap_per_class(h_, reinterpret_cast<const int32_t*>(at[0]), reinterpret_cast<const float*>(at[1]), reinterpret_cast<const float*>(at[2]), n,
-                                     reinterpret_cast<const float*>(at[3]), t, &out, stream_);   // waits for the stream
+    for (int j = 0; j < (k > 1 ? k : 1); ++j) out[j].struct_size = (int32_t)sizeof(yfv2_ap_result);
+    const float* c = reinterpret_cast<const float*>(at[1]);
+    const float* p = reinterpret_cast<const float*>(at[2]);
+    const float* g = reinterpret_cast<const float*>(at[3]);
+    const int rc = k == 0 ? yfv2_ap_per_class(h_, reinterpret_cast<const int32_t*>(at[0]), c, p, n, g, t, out, stream_)      // both wait for the stream
+                          : yfv2_ap_per_class_multi(h_, reinterpret_cast<const uint32_t*>(at[0]), c, p, n, g, t, k, out, stream_);
     if (d) (void)hipFree(d);
     if (rc != YFV2_OK) return fail(rc, yfv2_last_error(h_));
     return YFV2_OK;
   }
 
- private:
   int fail(int rc, const std::string& msg) { err_ = msg; return rc; }
   yfv2_handle h_ = nullptr;
   int rc_ = YFV2_OK;

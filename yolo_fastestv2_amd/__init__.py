@@ -9,6 +9,7 @@ anchor decode and class-aware NMS as hand-written HIP kernels behind a C ABI
     get_batch_statistics(outputs, targets, iou_threshold, device)   utils/utils.py:194  (evaluation's matching loop)
     compute_loss(preds, targets, cfg, device)                       utils/loss.py:130   (training loss + its gradient w.r.t. the logits)
     ap_per_class_device(tp, conf, pred_cls, target_cls)              utils/utils.py:136  (the same 4-tuple, ranked and summed on the device)
+    ap_per_class_multi_device(tpmask, conf, pred_cls, target_cls, K), evaluation_multi(...)  (the same at K IoU thresholds in one device pass)
     genanchors.kmeans(X, centroids, eps, anchor_file, width, height) genanchors.py:67    (anchor k-means over a label set, + write_anchors_to_file,
                                                                                          read_label_dims, anchors_for_cfg, main)
 
@@ -18,8 +19,8 @@ built libyfv2.so and an MI355X.
 from ._lib import LIB_PATH, Yfv2Error  # noqa: F401
 from .engine import Engine, get_engine, unpack_detections  # noqa: F401
 from .model.detector import Detector  # noqa: F401
-from .utils.utils import (ap_per_class, ap_per_class_device, compute_ap, evaluation, get_batch_statistics, handel_preds, load_datafile,  # noqa: F401
-                          nms_with_indices, non_max_suppression)
+from .utils.utils import (ap_per_class, ap_per_class_device, ap_per_class_multi_device, compute_ap, evaluation, evaluation_multi,  # noqa: F401
+                          get_batch_statistics, handel_preds, load_datafile, nms_with_indices, non_max_suppression)
 from .utils.loss import compute_loss  # noqa: F401
 from .utils.optim import SGD  # noqa: F401
 from .weights import export_weights, random_state_dict  # noqa: F401

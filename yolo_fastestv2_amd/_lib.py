@@ -120,6 +120,10 @@ _PROTOTYPES = {
     "yfv2_batch_statistics_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_float,
                                               C.c_void_p, C.c_void_p]),
     "yfv2_batch_statistics_overflow": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
+    "yfv2_batch_statistics_multi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_float),
+                                              C.c_int32, C.c_void_p, C.c_void_p]),
+    "yfv2_batch_statistics_multi_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_float),
+                                                    C.c_int32, C.c_void_p, C.c_void_p]),
     "yfv2_nonfinite": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
     "yfv2_nonfinite_peek": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
     "yfv2_clock_probe_begin": (C.c_int, [C.c_void_p, C.c_int32, C.c_float, C.c_int32, C.c_void_p]),
@@ -143,6 +147,8 @@ _PROTOTYPES = {
                                      C.POINTER(KmeansInfo), C.c_void_p]),
     "yfv2_debug_kmeans_group": (C.c_int, [C.c_void_p, C.c_int32]),
     "yfv2_ap_per_class": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.POINTER(ApResult), C.c_void_p]),
+    "yfv2_ap_per_class_multi": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32,
+                                          C.POINTER(ApResult), C.c_void_p]),
     "yfv2_debug_plan_dryrun": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "yfv2_debug_plan_dryrun_ex": (C.c_int, [C.c_void_p, C.POINTER(Plan), C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]),
     "yfv2_debug_plan_image": (C.c_int64, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_char_p, C.c_int32, C.c_void_p, C.c_int64]),

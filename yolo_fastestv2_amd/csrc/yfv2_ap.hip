@@ -21,6 +21,12 @@
 // wave values are added in ascending order; the chunk sums are added in ascending chunk order.  Its shape depends only on a term's
 // position inside its class's segment - not on the grid, the device or the run.  No floating-point atomic anywhere; counts use
 // integer atomics.  tests/ap_model.py is the numpy restatement the device is compared with bit for bit.
+//
+// K THRESHOLDS (yfv2_ap_per_class_multi).  The rank does not look at tp, so targets, keys and the five passes run once; then
+// ap_permute_kernel brings the callers' masks (bit k = tp at threshold k) into rank order and ap_curve_kernel<true> runs on a
+// (class, k) grid, reading bit k of the permuted word where ap_curve_kernel<false> reads bit 31 of the payload.  It is ONE body: the
+// template parameter selects where the bit comes from and which result block and chunk-sum set are written, nothing else, so
+// slice k is what the single-threshold call computes from tp = bit k.  n_gt and the bad-input word exist once, in block 0.
 #include "../../include/yfv2.h"
 #include "yfv2_internal.h"
 
@@ -58,7 +64,7 @@ __global__ __launch_bounds__(AP_THREADS) void ap_prep_kernel(ApArgs a) {
   if ((cb << 1) >= 0xff000000u) atomicOr(&a.head->bad, 1);          // exponent all ones: NaN or infinity
   const unsigned u = (cb << 1) == 0 ? 0u : cb ^ 0x80000000u;         // the bits of -conf; +0 and -0 are one key
   a.key[0][i] = (u & 0x80000000u) ? ~u : (u | 0x80000000u);          // ascending as unsigned = ascending -conf = descending conf
-  a.val[0][i] = (unsigned)i | (a.tp[i] != 0 ? 0x80000000u : 0u);
+  a.val[0][i] = (unsigned)i | (a.tp != nullptr && a.tp[i] != 0 ? 0x80000000u : 0u);
 }
 
 // digit of a detection in pass 0..3 (a byte of the key) or 4 (its class; 255: a class no target has)
@@ -203,7 +209,16 @@ __device__ __forceinline__ T ap_wave_fold(T v) {   // yfv2_anchors.hip's fold: l
   return v;
 }
 
-// ---- one workgroup per class: its ranked segment from the back, chunk by chunk
+// ---- K thresholds: the callers' masks in rank order, bits at and above K cleared
+__global__ __launch_bounds__(AP_THREADS) void ap_permute_kernel(ApArgs a) {
+  const int64_t q = (int64_t)blockIdx.x * AP_THREADS + threadIdx.x;
+  if (q >= a.N) return;
+  const unsigned keep = a.K >= 32 ? ~0u : (1u << a.K) - 1u;
+  a.pmask[q] = a.tpmask[a.val[1][q] & 0x7fffffffu] & keep;
+}
+
+// ---- one workgroup per class (MULTI: per class and threshold blockIdx.y): its ranked segment from the back, chunk by chunk
+template <bool MULTI>
 __global__ __launch_bounds__(AP_THREADS) void ap_curve_kernel(ApArgs a) {
   __shared__ unsigned s_tot[256];
   __shared__ int s_cnt[4 * AP_ROWS];
@@ -212,6 +227,8 @@ __global__ __launch_bounds__(AP_THREADS) void ap_curve_kernel(ApArgs a) {
   __shared__ long long s_tp[4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int c = blockIdx.x;
+  const int k = MULTI ? (int)blockIdx.y : 0;
+  ApHead* head = a.head + k;
   const long long n_gt = a.head->n_gt[c];
   if (n_gt == 0) return;   // uniform: the class is absent, its outputs stay 0
   s_tot[tid] = a.N > 0 ? a.tot[tid] : 0u;
@@ -219,12 +236,13 @@ __global__ __launch_bounds__(AP_THREADS) void ap_curve_kernel(ApArgs a) {
   int64_t start = 0;
   for (int j = 0; j < c; ++j) start += s_tot[j];
   const int64_t n_p = s_tot[c];
-  if (tid == 0) a.head->n_pred[c] = n_p;
+  if (tid == 0) head->n_pred[c] = n_p;
   if (n_p == 0) return;    // uniform: p = r = ap = 0
-  const unsigned* v = a.val[1] + start;
+  const unsigned* v = (MULTI ? a.pmask : a.val[1]) + start;
+  const int sh = MULTI ? k : 31;   // where tp sits in a word of v
 
   long long total = 0;
-  for (int64_t i = tid; i < n_p; i += AP_THREADS) total += v[i] >> 31;
+  for (int64_t i = tid; i < n_p; i += AP_THREADS) total += (v[i] >> sh) & 1u;
   total = ap_wave_fold(total);
   if (lane == 0) s_tp[wave] = total;
   __syncthreads();
@@ -232,7 +250,7 @@ __global__ __launch_bounds__(AP_THREADS) void ap_curve_kernel(ApArgs a) {
 
   const double den = (double)n_gt + 1e-16;
   const int64_t nch = (n_p + YFV2_AP_CH - 1) / YFV2_AP_CH;
-  double* part = a.part + (start / YFV2_AP_CH + c);
+  double* part = a.part + (int64_t)k * a.part_stride + (start / YFV2_AP_CH + c);
   const unsigned long long le = lane == 63 ? ~0ull : ((1ull << (lane + 1)) - 1ull);
   long long after = total;    // true positives up to the end of the current chunk
   double carry_env = 0.0;     // max of prec over every later chunk (prec >= 0: 0 is neutral)
@@ -245,7 +263,7 @@ __global__ __launch_bounds__(AP_THREADS) void ap_curve_kernel(ApArgs a) {
     for (int r = 0; r < AP_ROWS; ++r) {
       const int64_t pos = base + (int64_t)r * AP_THREADS;
       valid[r] = pos < n_p;
-      bit[r] = valid[r] ? v[pos] >> 31 : 0u;
+      bit[r] = valid[r] ? (v[pos] >> sh) & 1u : 0u;
       m[r] = __ballot(bit[r] != 0);
       if (lane == 0) s_cnt[r * 4 + wave] = __popcll(m[r]);
     }
@@ -300,35 +318,39 @@ __global__ __launch_bounds__(AP_THREADS) void ap_curve_kernel(ApArgs a) {
   double ap = part[0];     // thread 0 wrote every chunk sum itself
 #pragma unroll 8
   for (int64_t ch = 1; ch < nch; ++ch) ap += part[ch];
-  a.head->ap[c] = ap;
-  a.head->p[c] = (double)total / (double)n_p;
-  a.head->r[c] = (double)total / den;
+  head->ap[c] = ap;
+  head->p[c] = (double)total / (double)n_p;
+  head->r[c] = (double)total / den;
 }
 
 constexpr size_t ap_align(size_t n) { return (n + 255) & ~(size_t)255; }
 
 }  // namespace
 
-// layout: [head][row totals 256][table 256 x nblk][chunk sums N / 1024 + 512][key 0][key 1][payload 0][payload 1]
-size_t yfv2_ap_ws_bytes(int64_t N) {
-  const size_t n = (size_t)N, nblk = (n + YFV2_AP_TILE - 1) / YFV2_AP_TILE;
-  return ap_align(sizeof(ApHead)) + ap_align(256 * sizeof(uint32_t)) + ap_align(256 * nblk * sizeof(uint32_t)) +
-         ap_align((n / YFV2_AP_CH + 512) * sizeof(double)) + 4 * ap_align(n * sizeof(uint32_t));
+constexpr size_t ap_part_doubles(size_t n) { return ap_align((n / YFV2_AP_CH + 512) * sizeof(double)) / sizeof(double); }
+
+// layout: [head x max(K, 1)][row totals 256][table 256 x nblk][chunk sums (N / 1024 + 512) x max(K, 1)][key 0][key 1][payload 0][payload 1]
+// and, for K >= 1, [permuted mask].  K = 0 is the single-threshold form and asks for what it always did; K = 1 asks for 4 N bytes more.
+size_t yfv2_ap_ws_bytes(int64_t N, int K) {
+  const size_t n = (size_t)N, nblk = (n + YFV2_AP_TILE - 1) / YFV2_AP_TILE, sets = K > 1 ? (size_t)K : 1;
+  return ap_align(sets * sizeof(ApHead)) + ap_align(256 * sizeof(uint32_t)) + ap_align(256 * nblk * sizeof(uint32_t)) +
+         sets * ap_part_doubles(n) * sizeof(double) + (K > 0 ? 5 : 4) * ap_align(n * sizeof(uint32_t));
 }
 
 void yfv2_ap_carve(ApArgs& a, char* ws) {
-  const size_t n = (size_t)a.N, nblk = (n + YFV2_AP_TILE - 1) / YFV2_AP_TILE;
+  const size_t n = (size_t)a.N, nblk = (n + YFV2_AP_TILE - 1) / YFV2_AP_TILE, sets = a.K > 1 ? (size_t)a.K : 1;
   a.nblk = (int)nblk;
-  a.head = reinterpret_cast<ApHead*>(ws); ws += ap_align(sizeof(ApHead));
+  a.head = reinterpret_cast<ApHead*>(ws); ws += ap_align(sets * sizeof(ApHead));
   a.tot = reinterpret_cast<uint32_t*>(ws); ws += ap_align(256 * sizeof(uint32_t));
   a.hist = reinterpret_cast<uint32_t*>(ws); ws += ap_align(256 * nblk * sizeof(uint32_t));
-  a.part = reinterpret_cast<double*>(ws); ws += ap_align((n / YFV2_AP_CH + 512) * sizeof(double));
+  a.part = reinterpret_cast<double*>(ws); a.part_stride = (int64_t)ap_part_doubles(n); ws += sets * ap_part_doubles(n) * sizeof(double);
   for (int i = 0; i < 2; ++i) { a.key[i] = reinterpret_cast<uint32_t*>(ws); ws += ap_align(n * sizeof(uint32_t)); }
   for (int i = 0; i < 2; ++i) { a.val[i] = reinterpret_cast<uint32_t*>(ws); ws += ap_align(n * sizeof(uint32_t)); }
+  a.pmask = a.K > 0 ? reinterpret_cast<uint32_t*>(ws) : nullptr;
 }
 
 void yfv2_launch_ap(const ApArgs& a, hipStream_t s) {
-  (void)hipMemsetAsync(a.head, 0, sizeof(ApHead), s);
+  (void)hipMemsetAsync(a.head, 0, (a.K > 1 ? (size_t)a.K : 1) * sizeof(ApHead), s);
   if (a.T > 0) {
     const int64_t blocks = (a.T + AP_THREADS * 8 - 1) / (AP_THREADS * 8);
     hipLaunchKernelGGL(ap_targets_kernel, dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(AP_THREADS), 0, s, a);
@@ -341,7 +363,12 @@ void yfv2_launch_ap(const ApArgs& a, hipStream_t s) {
       hipLaunchKernelGGL(ap_scatter_kernel, dim3((unsigned)a.nblk), dim3(AP_THREADS), 0, s, a, pass);
     }
   }
-  hipLaunchKernelGGL(ap_curve_kernel, dim3(255), dim3(AP_THREADS), 0, s, a);
+  if (a.K > 0) {
+    if (a.N > 0) hipLaunchKernelGGL(ap_permute_kernel, dim3((unsigned)((a.N + AP_THREADS - 1) / AP_THREADS)), dim3(AP_THREADS), 0, s, a);
+    hipLaunchKernelGGL(ap_curve_kernel<true>, dim3(255, (unsigned)a.K), dim3(AP_THREADS), 0, s, a);
+  } else {
+    hipLaunchKernelGGL(ap_curve_kernel<false>, dim3(255), dim3(AP_THREADS), 0, s, a);
+  }
 }
 
 void yfv2_ap_finish(const ApHead& head, yfv2_ap_result* out) {
@@ -360,4 +387,14 @@ void yfv2_ap_finish(const ApHead& head, yfv2_ap_result* out) {
   out->bad_input = head.bad ? 1 : 0;
   const double n = (double)present;              // 0 / 0 = NaN for an empty target list: np.mean([])
   out->mean_p = sp / n; out->mean_r = sr / n; out->mean_ap = sa / n; out->mean_f1 = sf / n;
+}
+
+void yfv2_ap_finish_multi(ApHead* heads, int K, yfv2_ap_result* out) {
+  for (int k = 0; k < K; ++k) {
+    if (k > 0) {
+      for (int c = 0; c < 256; ++c) heads[k].n_gt[c] = heads[0].n_gt[c];
+      heads[k].bad = heads[0].bad;
+    }
+    yfv2_ap_finish(heads[k], out + k);
+  }
 }

@@ -692,6 +692,24 @@ int yfv2_batch_statistics_async(yfv2_handle h, const float* dets, const int32_t*
   return YFV2_OK;
 }
 
+// the same matching at K thresholds in one launch: bit k of tpmask = tp at thresholds[k]; the same sticky overflow word
+int yfv2_batch_statistics_multi_async(yfv2_handle h, const float* dets, const int32_t* count, int32_t B, const float* targets, int32_t T,
+                                      const float* thresholds, int32_t K, uint32_t* tpmask, void* stream) {
+  if (!h) return fail(nullptr, YFV2_ERR_ARG, "null handle");
+  if (B < 1) return fail(h, YFV2_ERR_BATCH, "yfv2_batch_statistics_multi: B < 1");
+  if (K < 1 || K > 32) return fail(h, YFV2_ERR_ARG, "yfv2_batch_statistics_multi: K must be in 1..32");
+  if (!dets || !count || !thresholds || !tpmask || T < 0 || (T > 0 && !targets)) return fail(h, YFV2_ERR_ARG, "yfv2_batch_statistics_multi: bad argument");
+  DeviceGuard guard(h->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  StatsMultiArgs a{};
+  a.dets = dets; a.count = count; a.targets = targets; a.tpmask = tpmask; a.overflow = h->d_stats_flag;
+  a.B = B; a.T = T; a.K = K;
+  for (int k = 0; k < K; ++k) a.thr[k] = thresholds[k];      // copied here: the caller's array may go once this returns
+  yfv2_launch_stats_multi(a, s);
+  HIP_TRY(h, hipGetLastError());
+  return YFV2_OK;
+}
+
 int yfv2_batch_statistics_overflow(yfv2_handle h, int32_t* overflowed, void* stream) {
   if (!h || !overflowed) return fail(h, YFV2_ERR_ARG, "yfv2_batch_statistics_overflow: null pointer");
   DeviceGuard guard(h->device);
@@ -780,6 +798,17 @@ int yfv2_batch_statistics(yfv2_handle h, const float* dets, const int32_t* count
   rc = yfv2_batch_statistics_overflow(h, &over, stream);
   if (rc) return rc;
   if (over) return fail(h, YFV2_ERR_ARG, "yfv2_batch_statistics: an image has more than 1024 targets");
+  return YFV2_OK;
+}
+
+int yfv2_batch_statistics_multi(yfv2_handle h, const float* dets, const int32_t* count, int32_t B, const float* targets, int32_t T,
+                                const float* thresholds, int32_t K, uint32_t* tpmask, void* stream) {
+  int rc = yfv2_batch_statistics_multi_async(h, dets, count, B, targets, T, thresholds, K, tpmask, stream);
+  if (rc) return rc;
+  int32_t over = 0;
+  rc = yfv2_batch_statistics_overflow(h, &over, stream);
+  if (rc) return rc;
+  if (over) return fail(h, YFV2_ERR_ARG, "yfv2_batch_statistics_multi: an image has more than 1024 targets");
   return YFV2_OK;
 }
 
@@ -910,6 +939,24 @@ int yfv2_debug_kmeans_group(yfv2_handle h, int32_t group) {
   return YFV2_OK;
 }
 
+// both AP entry points after their argument checks: grow the workspace, enqueue everything, copy the max(K, 1) result blocks back, wait
+static int ap_run(yfv2_handle h, ApArgs& a, ApHead* heads, hipStream_t s) {
+  const size_t need = yfv2_ap_ws_bytes(a.N, a.K);
+  if (need > h->ap_ws_bytes) {
+    HIP_TRY(h, hipDeviceSynchronize());               // (every earlier call waited for its stream; another stream's work may not have)
+    if (h->d_ap_ws) { (void)hipFree(h->d_ap_ws); h->d_ap_ws = nullptr; h->ap_ws_bytes = 0; }
+    const size_t cap = need + need / 2;
+    HIP_TRY(h, hipMalloc(&h->d_ap_ws, cap));
+    h->ap_ws_bytes = cap;
+  }
+  yfv2_ap_carve(a, static_cast<char*>(h->d_ap_ws));
+  yfv2_launch_ap(a, s);
+  HIP_TRY(h, hipGetLastError());
+  HIP_TRY(h, hipMemcpyAsync(heads, a.head, (size_t)(a.K > 1 ? a.K : 1) * sizeof(ApHead), hipMemcpyDeviceToHost, s));
+  HIP_TRY(h, hipStreamSynchronize(s));
+  return YFV2_OK;
+}
+
 // utils/utils.py:110-192 on the device (yfv2_ap.hip): rank, per-class curve, one fixed summation tree; the means on the host.
 int yfv2_ap_per_class(yfv2_handle h, const int32_t* tp, const float* conf, const float* pred_cls, int64_t N, const float* target_cls,
                       int64_t T, yfv2_ap_result* out, void* stream) {
@@ -923,28 +970,47 @@ int yfv2_ap_per_class(yfv2_handle h, const int32_t* tp, const float* conf, const
     return fail(h, YFV2_ERR_ARG, "yfv2_ap_per_class: the arrays must be 4-byte aligned");
   DeviceGuard guard(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const size_t need = yfv2_ap_ws_bytes(N);
-  if (need > h->ap_ws_bytes) {
-    HIP_TRY(h, hipDeviceSynchronize());               // (every earlier call waited for its stream; another stream's work may not have)
-    if (h->d_ap_ws) { (void)hipFree(h->d_ap_ws); h->d_ap_ws = nullptr; h->ap_ws_bytes = 0; }
-    const size_t cap = need + need / 2;
-    HIP_TRY(h, hipMalloc(&h->d_ap_ws, cap));
-    h->ap_ws_bytes = cap;
-  }
   ApArgs a{};
   a.tp = tp; a.conf = conf; a.pred_cls = pred_cls; a.N = N; a.target_cls = target_cls; a.T = T;
-  yfv2_ap_carve(a, static_cast<char*>(h->d_ap_ws));
-  yfv2_launch_ap(a, s);
-  HIP_TRY(h, hipGetLastError());
   ApHead head;
-  HIP_TRY(h, hipMemcpyAsync(&head, a.head, sizeof(ApHead), hipMemcpyDeviceToHost, s));
-  HIP_TRY(h, hipStreamSynchronize(s));
+  const int rc = ap_run(h, a, &head, s);
+  if (rc) return rc;
   yfv2_ap_result res{};
   yfv2_ap_finish(head, &res);
   // (a caller built against a shorter struct gets the fields it has)
   const size_t n = out->struct_size > 0 && (size_t)out->struct_size < sizeof(yfv2_ap_result) ? (size_t)out->struct_size : sizeof(yfv2_ap_result);
   res.struct_size = (int32_t)n;
   std::memcpy(out, &res, n);
+  return YFV2_OK;
+}
+
+// ... at K thresholds: one rank, a (class, threshold) grid of walks (yfv2_ap.hip); out[k] is what yfv2_ap_per_class returns for tp = bit k
+int yfv2_ap_per_class_multi(yfv2_handle h, const uint32_t* tpmask, const float* conf, const float* pred_cls, int64_t N,
+                            const float* target_cls, int64_t T, int32_t K, yfv2_ap_result* out, void* stream) {
+  if (!h) return fail(nullptr, YFV2_ERR_ARG, "null handle");
+  if (!out) return fail(h, YFV2_ERR_ARG, "yfv2_ap_per_class_multi: out is required");
+  if (K < 1 || K > 32) return fail(h, YFV2_ERR_ARG, "yfv2_ap_per_class_multi: K must be in 1..32");
+  if (N < 0 || T < 0) return fail(h, YFV2_ERR_ARG, "yfv2_ap_per_class_multi: N and T must not be negative");
+  if (N > 0x7fffffffLL || T > 0x7fffffffLL) return fail(h, YFV2_ERR_ARG, "yfv2_ap_per_class_multi: N and T are limited to 2^31 - 1");
+  if (N > 0 && (!tpmask || !conf || !pred_cls)) return fail(h, YFV2_ERR_ARG, "yfv2_ap_per_class_multi: null pointer (tpmask, conf and pred_cls are required when N > 0)");
+  if (T > 0 && !target_cls) return fail(h, YFV2_ERR_ARG, "yfv2_ap_per_class_multi: null pointer (target_cls is required when T > 0)");
+  if (((reinterpret_cast<uintptr_t>(tpmask) | reinterpret_cast<uintptr_t>(conf) | reinterpret_cast<uintptr_t>(pred_cls) | reinterpret_cast<uintptr_t>(target_cls)) & 3) != 0)
+    return fail(h, YFV2_ERR_ARG, "yfv2_ap_per_class_multi: the arrays must be 4-byte aligned");
+  DeviceGuard guard(h->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  ApArgs a{};
+  a.tpmask = tpmask; a.K = K; a.conf = conf; a.pred_cls = pred_cls; a.N = N; a.target_cls = target_cls; a.T = T;
+  std::vector<ApHead> heads((size_t)K);
+  const int rc = ap_run(h, a, heads.data(), s);
+  if (rc) return rc;
+  std::vector<yfv2_ap_result> res((size_t)K);
+  yfv2_ap_finish_multi(heads.data(), K, res.data());
+  // the records lie one caller's struct apart (a caller built against a shorter struct gets the fields it has)
+  const size_t n = out->struct_size > 0 && (size_t)out->struct_size < sizeof(yfv2_ap_result) ? (size_t)out->struct_size : sizeof(yfv2_ap_result);
+  for (int k = 0; k < K; ++k) {
+    res[(size_t)k].struct_size = (int32_t)n;
+    std::memcpy(reinterpret_cast<char*>(out) + (size_t)k * n, &res[(size_t)k], n);
+  }
   return YFV2_OK;
 }
 

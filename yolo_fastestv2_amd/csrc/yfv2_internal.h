@@ -377,6 +377,14 @@ struct StatsArgs {
 };
 constexpr int STATS_MAX_TARGETS = 1024;
 void yfv2_launch_stats(const StatsArgs& a, hipStream_t s);
+struct StatsMultiArgs {   // the same matching at K thresholds: bit k of tpmask = StatsArgs::tp at thr[k]
+  const float* dets; const int32_t* count; const float* targets;
+  uint32_t* tpmask;      // (B, 300)
+  int32_t* overflow;
+  int B, T, K;           // 1 <= K <= 32
+  float thr[32];
+};
+void yfv2_launch_stats_multi(const StatsMultiArgs& a, hipStream_t s);
 // ---- training loss and its gradient w.r.t. the logits (yfv2_loss.hip; utils/loss.py:8-208)
 struct LossMatch {            // one (scale, offset candidate, anchor, label) slot of build_target
   int valid, b, a, gj, gi, cls;
@@ -466,7 +474,9 @@ struct ApHead {                      // zeroed before every call, copied to the 
   int32_t bad, pad;
 };
 struct ApArgs {
-  const int32_t* tp; const float* conf; const float* pred_cls;   // (N)
+  const int32_t* tp; const float* conf; const float* pred_cls;   // (N); tp is null in the multi-threshold form
+  const uint32_t* tpmask;                                         // (N), multi-threshold form: bit k = tp at threshold k
+  int K;                                                          // 0: the single-threshold form; 1..32: thresholds
   int64_t N;
   const float* target_cls;                                        // (T)
   int64_t T;
@@ -474,15 +484,18 @@ struct ApArgs {
   uint32_t* val[2];    // (N) each: input index | tp << 31, ping-pong; the ranked list ends in val[1]
   uint32_t* hist;      // [256 digits][nblk]: per-workgroup digit counts, scanned in place along each row
   uint32_t* tot;       // [256]: row totals of the current pass
-  double* part;        // chunk sums of the AP terms: class c's start at floor(segment start / YFV2_AP_CH) + c
-  ApHead* head;
+  double* part;        // chunk sums of the AP terms: class c's start at floor(segment start / YFV2_AP_CH) + c; threshold k's set at k * part_stride
+  int64_t part_stride;
+  uint32_t* pmask;     // (N), multi-threshold form: tpmask in rank order, bits at and above K cleared
+  ApHead* head;        // max(K, 1) blocks; n_gt and bad live in block 0 alone
   int nblk;            // ceil(N / YFV2_AP_TILE)
 };
-size_t yfv2_ap_ws_bytes(int64_t N);                                   // the whole workspace, ApHead first
-void yfv2_ap_carve(ApArgs& a, char* ws);                              // sets the workspace pointers of a (N already set)
+size_t yfv2_ap_ws_bytes(int64_t N, int K);                            // the whole workspace, ApHead first (K = 0: the single-threshold form)
+void yfv2_ap_carve(ApArgs& a, char* ws);                              // sets the workspace pointers of a (N and K already set)
 void yfv2_launch_ap(const ApArgs& a, hipStream_t s);                  // memset of the head + every launch
 struct yfv2_ap_result;
 void yfv2_ap_finish(const ApHead& head, yfv2_ap_result* out);         // host: head -> result, means sequential over the present classes
+void yfv2_ap_finish_multi(ApHead* heads, int K, yfv2_ap_result* out); // host: block 0's n_gt and bad into every block, then yfv2_ap_finish on each
 // ---- measurement: effective shader clock (yfv2_probe.hip)
 struct ClockProbeArgs {
   unsigned long long* out;       // [workgroups][4]: shader cycles, reference ticks, XCC id, (unused)

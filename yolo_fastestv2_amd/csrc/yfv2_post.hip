@@ -754,28 +754,64 @@ void yfv2_launch_decode_nms(const DecodeArgs& d, const NmsArgs& a, hipStream_t s
 // The walk is sequential through the matched set; lanes run over the targets (kept in LDS with their matched flag).
 // fp32 arithmetic in the reference's operation order (this file is compiled with -ffp-contract=off); the
 // threshold is compared in fp32, as torch does for a float32 tensor against a Python float.
-__global__ __launch_bounds__(64) void stats_kernel(StatsArgs a) {
-  __shared__ float tx1[STATS_MAX_TARGETS], ty1[STATS_MAX_TARGETS], tx2[STATS_MAX_TARGETS], ty2[STATS_MAX_TARGETS], tlab[STATS_MAX_TARGETS];
-  __shared__ int tdone[STATS_MAX_TARGETS];
-  const int b = blockIdx.x, lane = threadIdx.x;
-  // this image's targets, in their order of appearance (box_index of the reference = position in this list)
+// (one wave) this image's targets into LDS, in their order of appearance (box_index of the reference = position in this list);
+// returns their number, which may exceed STATS_MAX_TARGETS (only the first STATS_MAX_TARGETS are stored)
+__device__ __forceinline__ int stats_load_targets(const float* __restrict__ targets, int T, int b, int lane, float* tx1, float* ty1, float* tx2,
+                                                  float* ty2, float* tlab) {
   int nt = 0;
-  for (int t0 = 0; t0 < a.T; t0 += 64) {
+  for (int t0 = 0; t0 < T; t0 += 64) {
     const int t = t0 + lane;
-    const bool mine = t < a.T && a.targets[(size_t)t * 6] == (float)b;
+    const bool mine = t < T && targets[(size_t)t * 6] == (float)b;
     const unsigned long long m = __ballot(mine);
     if (mine) {
       const int pos = nt + __popcll(m & ((1ull << lane) - 1ull));
       if (pos < STATS_MAX_TARGETS) {
-        tlab[pos] = a.targets[(size_t)t * 6 + 1];
-        tx1[pos] = a.targets[(size_t)t * 6 + 2]; ty1[pos] = a.targets[(size_t)t * 6 + 3];
-        tx2[pos] = a.targets[(size_t)t * 6 + 4]; ty2[pos] = a.targets[(size_t)t * 6 + 5];
-        tdone[pos] = 0;
+        tlab[pos] = targets[(size_t)t * 6 + 1];
+        tx1[pos] = targets[(size_t)t * 6 + 2]; ty1[pos] = targets[(size_t)t * 6 + 3];
+        tx2[pos] = targets[(size_t)t * 6 + 4]; ty2[pos] = targets[(size_t)t * 6 + 5];
       }
     }
     nt += __popcll(m);
   }
+  return nt;
+}
+
+// (one wave) detection row d against the nt targets in LDS: this lane's share of "label occurs among the targets" and of
+// (largest IoU, its first index); stats_best_reduce folds the latter over the wave
+__device__ __forceinline__ void stats_best_scan(const float* __restrict__ d, int nt, int lane, const float* tx1, const float* ty1, const float* tx2,
+                                                const float* ty2, const float* tlab, bool& has, float& best, int& bidx) {
+  const float bx1 = d[0], by1 = d[1], bx2 = d[2], by2 = d[3], lab = d[5];
+  const float barea = __fmul_rn(__fadd_rn(__fsub_rn(bx2, bx1), 1.f), __fadd_rn(__fsub_rn(by2, by1), 1.f));
+  has = false;
+  best = -1.f;
+  bidx = 0x7fffffff;
+  for (int t = lane; t < nt; t += 64) {
+    has |= tlab[t] == lab;
+    const float ix1 = fmaxf(bx1, tx1[t]), iy1 = fmaxf(by1, ty1[t]), ix2 = fminf(bx2, tx2[t]), iy2 = fminf(by2, ty2[t]);
+    const float iw = fmaxf(__fadd_rn(__fsub_rn(ix2, ix1), 1.f), 0.f), ih = fmaxf(__fadd_rn(__fsub_rn(iy2, iy1), 1.f), 0.f);
+    const float inter = __fmul_rn(iw, ih);
+    const float tarea = __fmul_rn(__fadd_rn(__fsub_rn(tx2[t], tx1[t]), 1.f), __fadd_rn(__fsub_rn(ty2[t], ty1[t]), 1.f));
+    const float iou = __fdiv_rn(inter, __fadd_rn(__fsub_rn(__fadd_rn(barea, tarea), inter), 1e-16f));
+    if (iou > best) { best = iou; bidx = t; }   // ascending t per lane: the first maximum stays
+  }
+}
+
+__device__ __forceinline__ void stats_best_reduce(float& best, int& bidx) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {      // (max IoU, lowest index) over the wave
+    const float ob = __shfl_xor(best, off);
+    const int oi = __shfl_xor(bidx, off);
+    if (ob > best || (ob == best && oi < bidx)) { best = ob; bidx = oi; }
+  }
+}
+
+__global__ __launch_bounds__(64) void stats_kernel(StatsArgs a) {
+  __shared__ float tx1[STATS_MAX_TARGETS], ty1[STATS_MAX_TARGETS], tx2[STATS_MAX_TARGETS], ty2[STATS_MAX_TARGETS], tlab[STATS_MAX_TARGETS];
+  __shared__ int tdone[STATS_MAX_TARGETS];
+  const int b = blockIdx.x, lane = threadIdx.x;
+  int nt = stats_load_targets(a.targets, a.T, b, lane, tx1, ty1, tx2, ty2, tlab);
   if (nt > STATS_MAX_TARGETS) { if (lane == 0) *a.overflow = 1; nt = STATS_MAX_TARGETS; }
+  for (int t = lane; t < nt; t += 64) tdone[t] = 0;
   __syncthreads();
   const int n = a.count[b];
   int* tp = a.tp + (size_t)b * NMS_MAX_DET;
@@ -784,28 +820,12 @@ __global__ __launch_bounds__(64) void stats_kernel(StatsArgs a) {
   const float thr = a.iou_thres;
   int matched = 0;
   for (int i = 0; i < n && matched < nt; ++i) {
-    const float* d = a.dets + ((size_t)b * NMS_MAX_DET + i) * 6;
-    const float bx1 = d[0], by1 = d[1], bx2 = d[2], by2 = d[3], lab = d[5];
-    const float barea = __fmul_rn(__fadd_rn(__fsub_rn(bx2, bx1), 1.f), __fadd_rn(__fsub_rn(by2, by1), 1.f));
-    bool has = false;
-    float best = -1.f;
-    int bidx = 0x7fffffff;
-    for (int t = lane; t < nt; t += 64) {
-      has |= tlab[t] == lab;
-      const float ix1 = fmaxf(bx1, tx1[t]), iy1 = fmaxf(by1, ty1[t]), ix2 = fminf(bx2, tx2[t]), iy2 = fminf(by2, ty2[t]);
-      const float iw = fmaxf(__fadd_rn(__fsub_rn(ix2, ix1), 1.f), 0.f), ih = fmaxf(__fadd_rn(__fsub_rn(iy2, iy1), 1.f), 0.f);
-      const float inter = __fmul_rn(iw, ih);
-      const float tarea = __fmul_rn(__fadd_rn(__fsub_rn(tx2[t], tx1[t]), 1.f), __fadd_rn(__fsub_rn(ty2[t], ty1[t]), 1.f));
-      const float iou = __fdiv_rn(inter, __fadd_rn(__fsub_rn(__fadd_rn(barea, tarea), inter), 1e-16f));
-      if (iou > best) { best = iou; bidx = t; }   // ascending t per lane: the first maximum stays
-    }
+    bool has;
+    float best;
+    int bidx;
+    stats_best_scan(a.dets + ((size_t)b * NMS_MAX_DET + i) * 6, nt, lane, tx1, ty1, tx2, ty2, tlab, has, best, bidx);
     if (__ballot(has) == 0ull) continue;          // label not among the target labels (wave-uniform)
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {      // (max IoU, lowest index) over the wave
-      const float ob = __shfl_xor(best, off);
-      const int oi = __shfl_xor(bidx, off);
-      if (ob > best || (ob == best && oi < bidx)) { best = ob; bidx = oi; }
-    }
+    stats_best_reduce(best, bidx);
     if (best >= thr && tdone[bidx] == 0) {        // wave-uniform
       if (lane == 0) { tp[i] = 1; tdone[bidx] = 1; }
       ++matched;
@@ -814,7 +834,74 @@ __global__ __launch_bounds__(64) void stats_kernel(StatsArgs a) {
   }
 }
 
+// The same rule at K thresholds in one launch (yfv2_batch_statistics_multi): bit k of tpmask[b][i] is what stats_kernel writes to
+// tp[b][i] at thr[k].  The target with the largest IoU does not depend on the threshold, so
+//   phase 1 (every wave, one detection each, lanes over the targets: stats_kernel's own scan and fold) leaves per detection its
+//           best IoU and that target's index, or -1 where the label occurs among no target's;
+//   phase 2 (wave 0, lane k = threshold k) walks the detections in order: every lane reads the one word done[bidx] (bit k: the target
+//           is taken at threshold k), decides best >= thr_k && !bit k, and one ballot is both the detection's mask and the bits to set.
+// stats_kernel's "stop once every target is matched" needs no code: then every bit is set and nothing hits.  Lanes at and above K
+// hold a NaN threshold, which no IoU reaches.  An image whose every IoU with a detection is NaN leaves bidx out of range: such a
+// detection hits at no threshold here (stats_kernel has no defined answer there for a threshold <= -1 and the same for any other).
+constexpr int STATSM_WAVES = 8;
+__global__ __launch_bounds__(64 * STATSM_WAVES) void stats_multi_kernel(StatsMultiArgs a) {
+  __shared__ float tx1[STATS_MAX_TARGETS], ty1[STATS_MAX_TARGETS], tx2[STATS_MAX_TARGETS], ty2[STATS_MAX_TARGETS], tlab[STATS_MAX_TARGETS];
+  __shared__ unsigned tdone[STATS_MAX_TARGETS];
+  __shared__ float s_best[NMS_MAX_DET];
+  __shared__ int s_bidx[NMS_MAX_DET];
+  __shared__ float s_thr[32];
+  __shared__ int s_nt;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (wave == 0) {
+    const int all = stats_load_targets(a.targets, a.T, b, lane, tx1, ty1, tx2, ty2, tlab);
+    if (lane == 0) {
+      if (all > STATS_MAX_TARGETS) *a.overflow = 1;
+      s_nt = all > STATS_MAX_TARGETS ? STATS_MAX_TARGETS : all;
+    }
+  } else if (wave == 1) {
+    if (lane < 32) s_thr[lane] = lane < a.K ? a.thr[lane] : __builtin_nanf("");
+  }
+  for (int t = tid; t < STATS_MAX_TARGETS; t += 64 * STATSM_WAVES) tdone[t] = 0u;
+  __syncthreads();
+  const int nt = s_nt;
+  unsigned* out = a.tpmask + (size_t)b * NMS_MAX_DET;
+  int n = a.count[b];
+  n = n < 0 ? 0 : (n > NMS_MAX_DET ? NMS_MAX_DET : n);
+  if (nt == 0) n = 0;
+  for (int i = n + tid; i < NMS_MAX_DET; i += 64 * STATSM_WAVES) out[i] = 0u;
+  if (n == 0) return;                              // uniform over the workgroup
+  for (int i = wave; i < n; i += STATSM_WAVES) {
+    bool has;
+    float best;
+    int bidx;
+    stats_best_scan(a.dets + ((size_t)b * NMS_MAX_DET + i) * 6, nt, lane, tx1, ty1, tx2, ty2, tlab, has, best, bidx);
+    const bool any = __ballot(has) != 0ull;
+    stats_best_reduce(best, bidx);
+    if (lane == 0) { s_best[i] = best; s_bidx[i] = any && bidx < nt ? bidx : -1; }
+  }
+  __syncthreads();
+  if (wave != 0) return;
+  const float thr = s_thr[lane & 31];
+  unsigned mine = 0u;                              // lane l keeps the mask of detection 64 j + l until the 64 are stored together
+  for (int i = 0; i < n; ++i) {
+    const int bidx = s_bidx[i];                    // wave-uniform
+    unsigned m = 0u;
+    if (bidx >= 0) {
+      const unsigned d = tdone[bidx];              // one word, every lane: an LDS broadcast
+      const bool hit = lane < 32 && s_best[i] >= thr && ((d >> (lane & 31)) & 1u) == 0u;
+      m = (unsigned)__ballot(hit);
+      if (m != 0u) tdone[bidx] = d | m;            // every lane stores the same word; the wave's LDS accesses stay in program order
+    }
+    if (lane == (i & 63)) mine = m;
+    if ((i & 63) == 63 || i == n - 1) {
+      const int at = (i & ~63) + lane;
+      if (at <= i) out[at] = mine;
+    }
+  }
+}
+
 void yfv2_launch_stats(const StatsArgs& a, hipStream_t s) { YFV2_LAUNCH(stats_kernel, dim3(a.B), dim3(64), 0, s, a); }
+void yfv2_launch_stats_multi(const StatsMultiArgs& a, hipStream_t s) { YFV2_LAUNCH(stats_multi_kernel, dim3(a.B), dim3(64 * STATSM_WAVES), 0, s, a); }
 
 // yfv2_detect_frames_u8's epilogue: network coordinates -> frame coordinates.  test.py:58-68 scales each box by
 // scale_w = w / cfg["width"], scale_h = h / cfg["height"] (Python floats) and multiplies box[k] (a Python float, i.e. the fp32

@@ -19,6 +19,18 @@ def _stream(device):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+def _ap_dict(res):
+    """a yfv2_ap_result as Engine.ap_per_class returns it"""
+    import numpy as np
+    out = {"n_gt": np.array(res.n_gt, np.int64), "n_pred": np.array(res.n_pred, np.int64),
+           "p": np.array(res.p, np.float64), "r": np.array(res.r, np.float64), "ap": np.array(res.ap, np.float64)}
+    out["present"] = np.flatnonzero(out["n_gt"] > 0)
+    out["bad_input"] = int(res.bad_input)
+    out["classes_present"] = int(res.classes_present)
+    out["means"] = (float(res.mean_p), float(res.mean_r), float(res.mean_ap), float(res.mean_f1))
+    return out
+
+
 class Engine:
     """Owns a yfv2 handle.  ``max_batch`` grows on demand (the handle is re-created
     and the weights re-uploaded)."""
@@ -366,6 +378,23 @@ class Engine:
                  int(targets.shape[0]), float(iou_threshold), _ptr(tp), _stream(self.device)), self._h)
         return tp
 
+    def batch_statistics_multi(self, dets, cnt, targets, thresholds, sync=True):
+        """``batch_statistics`` at K = len(thresholds) IoU thresholds (1..32, any floats in any order) in one launch
+        (include/yfv2.h yfv2_batch_statistics_multi): an int32 (B, 300) tensor whose bit k is exactly the flag ``batch_statistics``
+        returns at ``thresholds[k]``; bits at and above K are 0 (so bit 31, the sign, is set only where K = 32).  ``sync`` as there."""
+        import numpy as np
+        B = dets.shape[0]
+        if tuple(dets.shape) != (B, MAX_DET, 6) or dets.dtype != torch.float32 or dets.device != self.device:
+            raise ValueError("dets must be fp32 (B,%d,6) on %s" % (MAX_DET, self.device))
+        thr = np.ascontiguousarray(np.asarray(thresholds, np.float32).reshape(-1))
+        K = int(thr.shape[0])
+        targets = targets.to(self.device, torch.float32).reshape(-1, 6).contiguous()
+        mask = torch.empty((B, MAX_DET), device=self.device, dtype=torch.int32)
+        fn = _lib.lib().yfv2_batch_statistics_multi if sync else _lib.lib().yfv2_batch_statistics_multi_async
+        check(fn(self._h, _ptr(dets.contiguous()), _ptr(cnt.contiguous()), B, _ptr(targets) if targets.numel() else None,
+                 int(targets.shape[0]), thr.ctypes.data_as(C.POINTER(C.c_float)) if K else None, K, _ptr(mask), _stream(self.device)), self._h)
+        return mask
+
     def loss(self, preds, targets, want_grad=False):
         """utils/loss.py:130-208 compute_loss on the device: (losses, grads) with losses a float32 (4,) device tensor
         [lbox, lobj, lcls, total] and grads the gradients of `total` w.r.t. the six logit maps (None unless want_grad)."""
@@ -418,7 +447,6 @@ class Engine:
         indexed by class 0..255 - ``p``, ``r``, ``ap`` (float64), ``n_gt``, ``n_pred`` (int64) - with ``present`` (the ascending
         classes of target_cls), ``bad_input`` and ``means`` = (mean_p, mean_r, mean_ap, mean_f1) added class after class by the
         library.  Equal confidences rank by input index (np.argsort(-conf, kind="stable")).  Waits for the stream."""
-        import numpy as np
         want = (("tp", tp, torch.int32), ("conf", conf, torch.float32), ("pred_cls", pred_cls, torch.float32), ("target_cls", target_cls, torch.float32))
         for name, t, dt in want:
             if not torch.is_tensor(t) or t.dtype != dt or t.device != self.device or t.dim() != 1:
@@ -431,13 +459,27 @@ class Engine:
         res.struct_size = C.sizeof(_lib.ApResult)
         check(_lib.lib().yfv2_ap_per_class(self._h, _ptr(tp) if N else None, _ptr(conf) if N else None, _ptr(pred_cls) if N else None, N,
                                            _ptr(target_cls) if T else None, T, C.byref(res), _stream(self.device)), self._h)
-        out = {"n_gt": np.array(res.n_gt, np.int64), "n_pred": np.array(res.n_pred, np.int64),
-               "p": np.array(res.p, np.float64), "r": np.array(res.r, np.float64), "ap": np.array(res.ap, np.float64)}
-        out["present"] = np.flatnonzero(out["n_gt"] > 0)
-        out["bad_input"] = int(res.bad_input)
-        out["classes_present"] = int(res.classes_present)
-        out["means"] = (float(res.mean_p), float(res.mean_r), float(res.mean_ap), float(res.mean_f1))
-        return out
+        return _ap_dict(res)
+
+    def ap_per_class_multi(self, tpmask, conf, pred_cls, target_cls, K):
+        """``ap_per_class`` at K thresholds in one pass (include/yfv2.h yfv2_ap_per_class_multi): ``tpmask`` (N) int32, bit k = tp at
+        threshold k (what ``batch_statistics_multi`` returns, flattened); bits at and above K are ignored.  Returns a list of K dicts
+        shaped like ``ap_per_class``'s; entry k equals ``ap_per_class`` on ``(tpmask >> k) & 1`` bit for bit.  The definition is the
+        reference's ap_per_class at each threshold: no 101-point interpolation, no crowd flags, no area ranges.  Waits for the stream."""
+        want = (("tpmask", tpmask, torch.int32), ("conf", conf, torch.float32), ("pred_cls", pred_cls, torch.float32), ("target_cls", target_cls, torch.float32))
+        for name, t, dt in want:
+            if not torch.is_tensor(t) or t.dtype != dt or t.device != self.device or t.dim() != 1:
+                raise ValueError("%s must be a 1-d %s tensor on %s" % (name, dt, self.device))
+        tpmask, conf, pred_cls, target_cls = tpmask.contiguous(), conf.contiguous(), pred_cls.contiguous(), target_cls.contiguous()
+        N, T, K = int(tpmask.shape[0]), int(target_cls.shape[0]), int(K)
+        if int(conf.shape[0]) != N or int(pred_cls.shape[0]) != N:
+            raise ValueError("tpmask, conf and pred_cls must have one length (got %d, %d, %d)" % (N, conf.shape[0], pred_cls.shape[0]))
+        res = (_lib.ApResult * max(K, 1))()
+        for r in res:
+            r.struct_size = C.sizeof(_lib.ApResult)
+        check(_lib.lib().yfv2_ap_per_class_multi(self._h, _ptr(tpmask) if N else None, _ptr(conf) if N else None, _ptr(pred_cls) if N else None, N,
+                                                 _ptr(target_cls) if T else None, T, K, res, _stream(self.device)), self._h)
+        return [_ap_dict(r) for r in res]
 
     # ---- training path (SURVEY.md 8(f) row 3): train.py:96-123 on the device -----------------------------------------
     def train_bind(self, tensors, grads):

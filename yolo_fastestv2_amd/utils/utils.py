@@ -181,23 +181,29 @@ def _ap_means(out):
     return np.mean(p), np.mean(r), np.mean(ap), np.mean(f1)
 
 
+def _ap_device(who, arrays, device):
+    """the device an AP call runs on: the one named, else that of the first argument already on a GPU, else the current one"""
+    if not torch.cuda.is_available():
+        raise RuntimeError("%s: no MI355X visible (there is no CPU path)" % who)
+    tensors = [t for t in arrays if torch.is_tensor(t) and t.device.type == "cuda"]
+    if device is not None:
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise RuntimeError("%s: no CPU path, pass the MI355X device (got %s)" % (who, device))
+    else:
+        dev = tensors[0].device if tensors else torch.device("cuda", torch.cuda.current_device())
+    if dev.index is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    return dev
+
+
 def ap_per_class_device(tp, conf, pred_cls, target_cls, device=None):
     """``ap_per_class`` on the MI355X (include/yfv2.h yfv2_ap_per_class): the reference's argument order and the same 4-tuple.
     Arrays, lists or tensors; whatever is not on the device yet is moved there.  Equal confidences rank by input index
     (``np.argsort(-conf, kind="stable")``; the reference's unstable sort leaves that order to numpy), so mean AP can differ from
     ``ap_per_class`` where confidences tie; P, R and F1 cannot.  Raises ValueError on a target class that is not an integer in
     0..254 or a confidence that is not finite."""
-    if not torch.cuda.is_available():
-        raise RuntimeError("ap_per_class_device: no MI355X visible (there is no CPU path)")
-    tensors = [t for t in (tp, conf, pred_cls, target_cls) if torch.is_tensor(t) and t.device.type == "cuda"]
-    if device is not None:
-        dev = torch.device(device)
-        if dev.type != "cuda":
-            raise RuntimeError("ap_per_class_device: no CPU path, pass the MI355X device (got %s)" % device)
-    else:
-        dev = tensors[0].device if tensors else torch.device("cuda", torch.cuda.current_device())
-    if dev.index is None:
-        dev = torch.device("cuda", torch.cuda.current_device())
+    dev = _ap_device("ap_per_class_device", (tp, conf, pred_cls, target_cls), device)
 
     def move(x, dtype):
         import numpy as np
@@ -211,6 +217,93 @@ def ap_per_class_device(tp, conf, pred_cls, target_cls, device=None):
     if out["bad_input"]:
         raise ValueError("ap_per_class_device: a target class is not an integer in 0..254, or a confidence is not a finite number")
     return _ap_means(out)
+
+
+def ap_per_class_multi_device(tpmask, conf, pred_cls, target_cls, K, device=None):
+    """``ap_per_class_device`` at K thresholds in one pass (include/yfv2.h yfv2_ap_per_class_multi): ``tpmask`` holds tp at threshold k
+    in bit k (integers; what ``Engine.batch_statistics_multi`` returns).  Returns K 4-tuples, entry k equal to
+    ``ap_per_class_device((tpmask >> k) & 1, ...)``.  The definition at each threshold is the reference's own ``ap_per_class`` +
+    ``compute_ap`` - nothing of pycocotools (101-point interpolation, crowd flags, area ranges) is modelled."""
+    import numpy as np
+    dev = _ap_device("ap_per_class_multi_device", (tpmask, conf, pred_cls, target_cls), device)
+
+    def move(x):
+        t = x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(np.asarray(x, np.float64)))
+        return t.to(dev).to(torch.float32).reshape(-1)
+
+    if torch.is_tensor(tpmask):
+        mask = tpmask.to(dev).to(torch.int32).reshape(-1)
+    else:   # through uint32, so that bit 31 survives the way into an int32 tensor
+        mask = torch.from_numpy(np.ascontiguousarray(np.asarray(tpmask).astype(np.int64).astype(np.uint32)).view(np.int32)).to(dev).reshape(-1)
+    eng = get_engine(dev, 32, 32, 1, 3)      # no forward workspace is involved: the smallest handle there is
+    outs = eng.ap_per_class_multi(mask, move(conf), move(pred_cls), move(target_cls), K)
+    if outs[0]["bad_input"]:
+        raise ValueError("ap_per_class_multi_device: a target class is not an integer in 0..254, or a confidence is not a finite number")
+    return [_ap_means(out) for out in outs]
+
+
+def evaluation_multi(val_dataloader, cfg, model, device, conf_thres=0.01, nms_thresh=0.4, iou_thresholds=None):
+    """``evaluation(..., ap_on_device=True)`` at K IoU thresholds in one pass over the loader: one fused detect call and ONE matching
+    launch per batch (``Engine.batch_statistics_multi``), one ``Engine.ap_per_class_multi`` call at the end.  ``iou_thresholds``
+    defaults to ``np.linspace(0.5, 0.95, 10)`` cast to fp32 (at most 32 values).  Returns None for an empty loader, else a dict:
+    ``thresholds`` (fp32 array), ``per_threshold`` (K 4-tuples, entry k what ``evaluation(..., iou_thres=thresholds[k],
+    ap_on_device=True)`` returns), ``map`` (``np.mean`` of the K mean APs) and, where a threshold equals fp32 0.5, ``map50``.
+    The definition at every threshold is the reference's ``get_batch_statistics`` + ``ap_per_class`` + ``compute_ap``; nothing of
+    pycocotools is modelled: no 101-point interpolation, no crowd flags, no area ranges."""
+    import numpy as np
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("evaluation_multi: no CPU path, pass the MI355X device")
+    thr = np.linspace(0.5, 0.95, 10) if iou_thresholds is None else np.asarray(iou_thresholds, np.float64).reshape(-1)
+    thr = thr.astype(np.float32)
+    K = int(thr.shape[0])
+    if not 1 <= K <= 32:
+        raise ValueError("evaluation_multi: 1 to 32 thresholds, got %d" % K)
+    labels, kept = [], []
+    engines = set()
+    scale = None
+    eng = None
+    for imgs, targets in val_dataloader:
+        imgs = imgs.to(device)
+        u8_hwc = imgs.dtype == torch.uint8 and imgs.dim() == 4 and imgs.shape[-1] == 3
+        x = imgs if u8_hwc else imgs.float() / 255.0
+        targets = targets.to(device).clone()
+        labels.append(targets[:, 1].clone())
+        c = targets[:, 2:].clone()
+        targets[:, 2] = c[:, 0] - c[:, 2] / 2
+        targets[:, 3] = c[:, 1] - c[:, 3] / 2
+        targets[:, 4] = c[:, 0] + c[:, 2] / 2
+        targets[:, 5] = c[:, 1] + c[:, 3] / 2
+        if scale is None:
+            scale = torch.tensor([cfg["width"], cfg["height"], cfg["width"], cfg["height"]]).to(device)
+        targets[:, 2:] *= scale
+        eng = model.engine_for(x)
+        eng.set_anchors(cfg["anchors"])
+        dets, _, cnt = eng.detect(x, conf_thres, nms_thresh)
+        mask = eng.batch_statistics_multi(dets, cnt, targets, thr, sync=False)
+        engines.add(eng)
+        live = torch.arange(dets.shape[1], device=device)[None, :] < cnt[:, None]
+        kept.append((mask[live], dets[..., 4][live], dets[..., 5][live]))
+    over = [eng.stats_overflowed() for eng in engines]      # read (and cleared) on every engine before any return path, as evaluation does
+    bad = [eng.nonfinite() for eng in engines]
+    if any(over):
+        raise RuntimeError("evaluation_multi: an image has more than 1024 targets (yfv2_batch_statistics limit)")
+    if any(bad):
+        raise RuntimeError("evaluation_multi: an activation left the range of the default (fp16x3) plan (include/yfv2.h yfv2_nonfinite); "
+                           "run on the fp32-matrix plan (YFV2_BF6=0 in the environment of the Python layer / yfv2_plan.fp32_matrix = 1)")
+    if not kept:
+        print("---- No detections over whole validation set ----")
+        return None
+    outs = eng.ap_per_class_multi(torch.cat([k[0] for k in kept]), torch.cat([k[1] for k in kept]), torch.cat([k[2] for k in kept]),
+                                  torch.cat(labels).float(), K)
+    if outs[0]["bad_input"]:
+        raise RuntimeError("evaluation_multi: a label is not an integer class in 0..254, or a confidence is not finite (yfv2_ap_per_class_multi)")
+    per = [_ap_means(out) for out in outs]
+    res = {"thresholds": thr, "per_threshold": per, "map": np.mean([m[2] for m in per])}
+    at50 = np.flatnonzero(thr == np.float32(0.5))
+    if at50.size:
+        res["map50"] = per[int(at50[0])][2]
+    return res
 
 
 def evaluation(val_dataloader, cfg, model, device, conf_thres=0.01, nms_thresh=0.4, iou_thres=0.5, *, ap_on_device=False):
