@@ -405,7 +405,7 @@ def test_ap_per_class_bit_exact_vs_reference_golden():
     assert yfv2.compute_ap(np.array([0.5, 1.0]), np.array([1.0, 0.5])) == 0.75
 
 
-def _dryrun(classes, H, W, drop=None, max_batch=4, weights_classes=None):
+def _dryrun(classes, H, W, drop=None, max_batch=4, weights_classes=None, short=None):
     import ctypes as C
 
     import yolo_fastestv2_amd as yfv2
@@ -414,6 +414,8 @@ def _dryrun(classes, H, W, drop=None, max_batch=4, weights_classes=None):
 
     w = yfv2.random_state_dict(1, classes=weights_classes or min(max(classes, 1), 255))
     host = {k: v.float().contiguous() for k, v in w.items() if v.is_floating_point() and k != drop}
+    if short:
+        host[short] = host[short].flatten()[:-1].clone()      # one element short, in a block of its own
     arr = (TensorDesc * len(host))()
     for i, (k, t) in enumerate(host.items()):
         arr[i].name, arr[i].data, arr[i].numel = k.encode(), t.data_ptr(), t.numel()
@@ -477,8 +479,30 @@ def test_plan_and_weight_packing_on_the_host_for_every_admitted_config():
     assert _dryrun(0, 352, 352)[0] == ERR_CONFIG
     assert _dryrun(80, 350, 352)[0] == ERR_CONFIG
     assert _dryrun(80, 352, 352, drop="fpn.conv1x1_2.0.weight")[0] == ERR_WEIGHTS
+    # ... whichever tensor it is: the whole table is checked before anything is packed, so the first conv (whose image was built
+    # from an empty blob), a BatchNorm leaf, a tensor of the middle of the backbone and a head's bias are all refused by name
+    for name in ("backbone.first_conv.0.weight", "backbone.first_conv.1.running_var", "backbone.stage2.0.branch_proj.0.weight", "output_reg_layers.bias"):
+        assert _dryrun(80, 352, 352, drop=name)[0] == ERR_WEIGHTS and _lib.last_error() == "missing tensor '%s'" % name, (name, _lib.last_error())
+    assert _dryrun(80, 352, 352, short="backbone.first_conv.0.weight")[0] == ERR_WEIGHTS
+    assert _lib.last_error() == "tensor 'backbone.first_conv.0.weight' has 647 elements, expected 648", _lib.last_error()
     assert _dryrun(80, 352, 352, weights_classes=20)[0] == ERR_WEIGHTS     # a 20-class checkpoint into an 80-class handle
     assert _dryrun(20, 352, 352)[2] < _dryrun(80, 352, 352)[2]
+
+
+def test_host_api_under_sanitizers_refuses_every_incomplete_state_dict():
+    """tests/cpp/yfv2_host_san.cpp: the API, plan and pack units built with AddressSanitizer and UBSan (host side only) into a program
+    of its own.  It packs a complete state dict for 80 and 100 classes, 352x352 and 64x96, default and layer-by-layer plan, then
+    drops every tensor in turn and shortens every tensor by one element - each must be the WEIGHTS code naming the tensor, with no
+    sanitizer report - and walks yfv2_tile_plan and every entry point's null-handle path.  Sanitized code belongs on CPU machines:
+    where a device is visible the test has nothing to do."""
+    if torch.cuda.is_available():
+        pytest.skip("host-only sanitizer build: not built or run where a GPU is visible")
+    _lib()      # (the kernel objects the program links come from the library's build)
+    csrc = os.path.join(REPO, "yolo_fastestv2_amd", "csrc")
+    made = subprocess.run(["make", "-C", csrc, "host_san", "-j8"], capture_output=True, text=True)
+    assert made.returncode == 0, made.stdout[-3000:] + made.stderr[-3000:]
+    run = subprocess.run([os.path.join(REPO, "tests", "cpp", "yfv2_host_san")], capture_output=True, text=True)
+    assert run.returncode == 0 and "host_san ok" in run.stdout and "ERROR" not in run.stderr and "runtime error" not in run.stderr, run.stdout[-2000:] + run.stderr[-6000:]
 
 
 def test_bench_quotes_counters_only_from_a_profile_of_the_same_tree(tmp_path, monkeypatch):

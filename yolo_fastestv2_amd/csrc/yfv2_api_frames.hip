@@ -1,0 +1,242 @@
+// yfv2_api_frames.hip - host side of libyfv2.so, the entry points that take caller frames: the resize, detection on ragged
+// batches of frames, and tiled detection (tile plan, merge, both in one call).  The handle and the shared plumbing: yfv2_ctx.h.
+#include <algorithm>
+#include <cmath>
+
+#include "yfv2_ctx.h"
+
+extern "C" {
+
+int yfv2_resize_u8(yfv2_handle h, const uint8_t* src, int32_t B, int32_t src_h, int32_t src_w, uint8_t* dst, void* stream) {
+  if (!h) return fail(nullptr, YFV2_ERR_ARG, "null handle");
+  if (!src || !dst || B < 1 || src_h < 1 || src_w < 1) return fail(h, YFV2_ERR_ARG, "yfv2_resize_u8: bad argument");
+  if ((reinterpret_cast<uintptr_t>(dst) & 3) != 0) return fail(h, YFV2_ERR_ARG, "yfv2_resize_u8: dst must be 4-byte aligned");
+  if (yfv2_resize_lds_bytes(src_w, h->cfg.width) > 160 * 1024 || (long long)B * h->cfg.height > 0x7fffffffll)
+    return fail(h, YFV2_ERR_ARG, "yfv2_resize_u8: source rows wider than " + std::to_string((160 * 1024 - 3 * h->cfg.width) / 6 - 2) + " pixels are not supported");
+  DeviceGuard guard(h->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  ResizeArgs a{};
+  a.src = src; a.dst = dst; a.B = B; a.SH = src_h; a.SW = src_w; a.H = h->cfg.height; a.W = h->cfg.width;
+  a.scale_x = 1.0 / ((double)a.W / (double)src_w);      // cv::resize: inv_scale = dsize / ssize, scale = 1 / inv_scale
+  a.scale_y = 1.0 / ((double)a.H / (double)src_h);
+  yfv2_launch_resize(a, s);
+  HIP_TRY(h, hipGetLastError());
+  return YFV2_OK;
+}
+
+// what every entry point checks of a caller's frame; `at` = "<entry point>: frame <i>: "
+static int check_frame(yfv2_handle h, const std::string& at, const yfv2_frame& f) {
+  if (f.height < 1 || f.width < 1) return fail(h, YFV2_ERR_ARG, at + "height and width must be >= 1");
+  if (!f.data) return fail(h, YFV2_ERR_ARG, at + "null data");
+  if (f.row_pitch < 3ll * f.width) return fail(h, YFV2_ERR_ARG, at + "row_pitch " + std::to_string(f.row_pitch) + " < 3 * width");
+  return YFV2_OK;
+}
+
+// Ragged batches (yfv2_resize_frames_u8 / yfv2_detect_frames_u8): every frame is checked here, before anything is enqueued,
+// and expanded by its scales into t; *max_w = the widest frame (it sizes the resize launch's LDS).  The table is B entries of
+// the handle's max_batch, so B is bound by max_batch on both entry points.
+static int check_frames(yfv2_handle h, const char* what, const yfv2_frame* frames, int32_t B, std::vector<ResizeFrame>& t, int* max_w) {
+  const std::string w_ = what;
+  if (!frames) return fail(h, YFV2_ERR_ARG, w_ + ": null pointer");
+  if (B < 1) return fail(h, YFV2_ERR_ARG, w_ + ": B < 1");
+  if (B > h->cfg.max_batch)
+    return fail(h, YFV2_ERR_BATCH, w_ + ": batch " + std::to_string(B) + " above max_batch=" + std::to_string(h->cfg.max_batch));
+  const int H = h->cfg.height, W = h->cfg.width;
+  const int limit = (160 * 1024 - 3 * W) / 6 - 2;
+  t.assign((size_t)B, ResizeFrame{});
+  int mw = 1;
+  for (int32_t b = 0; b < B; ++b) {
+    const yfv2_frame& f = frames[b];
+    const std::string at = w_ + ": frame " + std::to_string(b) + ": ";
+    if (int rc = check_frame(h, at, f)) return rc;
+    if (f.width > limit || yfv2_resize_lds_bytes(f.width, W) > 160 * 1024)
+      return fail(h, YFV2_ERR_ARG, at + "frames wider than " + std::to_string(limit) + " pixels are not supported");
+    if (f.row_pitch > (1ll << 40) || (long long)(f.height - 1) * f.row_pitch > (1ll << 52))
+      return fail(h, YFV2_ERR_ARG, at + "row_pitch out of range");
+    ResizeFrame& r = t[(size_t)b];
+    r.data = f.data; r.pitch = f.row_pitch; r.h = f.height; r.w = f.width;
+    r.scale_x = 1.0 / ((double)W / (double)f.width);      // exactly yfv2_resize_u8's scales
+    r.scale_y = 1.0 / ((double)H / (double)f.height);
+    r.box_x = (double)f.width / (double)W;                // test.py:58  scale_w = w / cfg["width"]
+    r.box_y = (double)f.height / (double)H;
+    mw = std::max(mw, (int)f.width);
+  }
+  if ((long long)B * H > 0x7fffffffll) return fail(h, YFV2_ERR_ARG, w_ + ": batch too large");
+  *max_w = mw;
+  return YFV2_OK;
+}
+
+int yfv2_resize_frames_u8(yfv2_handle h, const yfv2_frame* frames, int32_t B, uint8_t* dst, void* stream) {
+  if (!h) return fail(nullptr, YFV2_ERR_ARG, "null handle");
+  if (!dst) return fail(h, YFV2_ERR_ARG, "yfv2_resize_frames_u8: null pointer");
+  if ((reinterpret_cast<uintptr_t>(dst) & 3) != 0) return fail(h, YFV2_ERR_ARG, "yfv2_resize_frames_u8: dst must be 4-byte aligned");
+  std::vector<ResizeFrame> t;
+  int max_w = 0;
+  int rc = check_frames(h, "yfv2_resize_frames_u8", frames, B, t, &max_w);
+  if (rc) return rc;
+  DeviceGuard guard(h->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  HIP_TRY(h, hipMemcpyAsync(h->d_frames, t.data(), sizeof(ResizeFrame) * (size_t)B, hipMemcpyHostToDevice, s));
+  yfv2_launch_resize_frames(h->d_frames, B, max_w, dst, h->cfg.height, h->cfg.width, s);
+  HIP_TRY(h, hipGetLastError());
+  return YFV2_OK;
+}
+
+int yfv2_detect_frames_u8(yfv2_handle h, const yfv2_frame* frames, int32_t B, float conf_thres, double iou_thres, float* dets,
+                          int32_t* idx, int32_t* count, void* stream) {
+  int rc = check_call(h, B, true);
+  if (rc) return rc;
+  if (!dets || !idx || !count) return fail(h, YFV2_ERR_ARG, "yfv2_detect_frames_u8: null pointer");
+  std::vector<ResizeFrame> t;
+  int max_w = 0;
+  rc = check_frames(h, "yfv2_detect_frames_u8", frames, B, t, &max_w);
+  if (rc) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DeviceGuard guard(h->device);
+  if (int rc2 = h->frames_u8.reserve(h, (size_t)h->cfg.height * h->cfg.width * 3 * (size_t)h->cfg.max_batch, true)) return rc2;   // the resized batch
+  HIP_TRY(h, hipMemcpyAsync(h->d_frames, t.data(), sizeof(ResizeFrame) * (size_t)B, hipMemcpyHostToDevice, s));
+  yfv2_launch_resize_frames(h->d_frames, B, max_w, h->frames_u8.as<uint8_t>(), h->cfg.height, h->cfg.width, s);
+  HIP_TRY(h, hipGetLastError());
+  rc = yfv2_detect_u8(h, h->frames_u8.as<uint8_t>(), B, conf_thres, iou_thres, dets, idx, count, stream);
+  if (rc) return rc;
+  yfv2_launch_frame_boxes(dets, count, h->d_frames, B, s);
+  HIP_TRY(h, hipGetLastError());
+  return YFV2_OK;
+}
+
+// ---- tiled detection ----------------------------------------------------------------------------------
+
+// One axis of the tile plan: L <= t is the single interval [0, L); otherwise tiles of length t at min(i * (t - o), L - t).
+static int64_t tile_axis_count(int32_t L, int32_t t, int32_t o) {
+  if (L <= t) return 1;
+  const int64_t s = (int64_t)t - o;
+  return ((int64_t)L - t + s - 1) / s + 1;
+}
+
+int yfv2_tile_plan(int32_t frame_h, int32_t frame_w, int32_t tile_h, int32_t tile_w, int32_t overlap_h, int32_t overlap_w,
+                   int32_t include_full, yfv2_tile* tiles, int32_t cap) {
+  if (frame_h < 1 || frame_w < 1 || tile_h < 1 || tile_w < 1) return fail(nullptr, YFV2_ERR_ARG, "yfv2_tile_plan: frame and tile sizes must be >= 1");
+  if (overlap_h < 0 || overlap_h >= tile_h || overlap_w < 0 || overlap_w >= tile_w)
+    return fail(nullptr, YFV2_ERR_ARG, "yfv2_tile_plan: overlap must be in [0, tile)");
+  const int64_t ny = tile_axis_count(frame_h, tile_h, overlap_h), nx = tile_axis_count(frame_w, tile_w, overlap_w);
+  const int64_t total = ny * nx + (include_full && ny * nx > 1 ? 1 : 0);
+  if (total > 0x7fffffffll) return fail(nullptr, YFV2_ERR_ARG, "yfv2_tile_plan: more than 2^31 - 1 tiles");
+  if (!tiles) return (int)total;
+  if (cap < total) return fail(nullptr, YFV2_ERR_ARG, "yfv2_tile_plan: cap " + std::to_string(cap) + " < " + std::to_string(total) + " tiles");
+  const int32_t th = std::min(tile_h, frame_h), tw = std::min(tile_w, frame_w);     // L <= t: the one interval is [0, L)
+  const int64_t sy = (int64_t)tile_h - overlap_h, sx = (int64_t)tile_w - overlap_w;
+  yfv2_tile* o = tiles;
+  for (int64_t iy = 0; iy < ny; ++iy)
+    for (int64_t ix = 0; ix < nx; ++ix, ++o) {
+      o->frame = 0;
+      o->y0 = (int32_t)std::min<int64_t>(iy * sy, frame_h - th);
+      o->x0 = (int32_t)std::min<int64_t>(ix * sx, frame_w - tw);
+      o->height = th; o->width = tw;
+    }
+  if (total > ny * nx) { o->frame = 0; o->x0 = 0; o->y0 = 0; o->width = frame_w; o->height = frame_h; }
+  return (int)total;
+}
+
+constexpr int TILE_MAX_T = 65536, TILE_MAX_F = 65536, TILE_MAX_OUT = 4096;
+
+// What both entry points check of the merge itself; fills the device table's host image: [T][4] x0, y0, k0, k1, then [F][2] k0, k1.
+static int check_merge(yfv2_handle h, const char* what, const yfv2_tile* tiles, int32_t T, int32_t F, double merge_thres, int32_t merge_metric,
+                       int32_t max_out, std::vector<int32_t>& table) {
+  const std::string w_ = what;
+  if (!tiles) return fail(h, YFV2_ERR_ARG, w_ + ": null pointer");
+  if (T < 1 || T > TILE_MAX_T) return fail(h, YFV2_ERR_ARG, w_ + ": T must be in 1.." + std::to_string(TILE_MAX_T));
+  if (F < 1 || F > TILE_MAX_F) return fail(h, YFV2_ERR_ARG, w_ + ": F must be in 1.." + std::to_string(TILE_MAX_F));
+  if (merge_metric != 0 && merge_metric != 1) return fail(h, YFV2_ERR_ARG, w_ + ": merge_metric must be 0 (IoU) or 1 (intersection over the smaller box)");
+  if (max_out < 1 || max_out > TILE_MAX_OUT) return fail(h, YFV2_ERR_ARG, w_ + ": max_out must be in 1.." + std::to_string(TILE_MAX_OUT));
+  if (!std::isfinite(merge_thres)) return fail(h, YFV2_ERR_ARG, w_ + ": merge_thres must be a finite number");
+  table.assign((size_t)4 * T + (size_t)2 * F, 0);
+  int32_t* fr = table.data() + (size_t)4 * T;
+  for (int32_t k = 0; k < T; ++k) {
+    const int32_t f = tiles[k].frame;
+    if (f < 0 || f >= F) return fail(h, YFV2_ERR_ARG, w_ + ": tile " + std::to_string(k) + ": frame " + std::to_string(f) + " outside [0, F)");
+    if (k > 0 && f < tiles[k - 1].frame)
+      return fail(h, YFV2_ERR_ARG, w_ + ": tile " + std::to_string(k) + ": frame index decreases (a frame's tiles must be one contiguous range)");
+    if (fr[2 * f + 1] == 0) fr[2 * f] = k;      // first tile of frame f
+    fr[2 * f + 1] = k + 1;
+  }
+  for (int32_t k = 0; k < T; ++k) {
+    int32_t* e = table.data() + (size_t)4 * k;
+    e[0] = tiles[k].x0; e[1] = tiles[k].y0; e[2] = fr[2 * tiles[k].frame]; e[3] = fr[2 * tiles[k].frame + 1];
+  }
+  return YFV2_OK;
+}
+
+// the tile workspace holds the largest T and the largest F seen so far: it grows exactly when one of the two does
+static int ensure_tile_ws(yfv2_handle h, int T, int F) {
+  const int ct = std::max(T, h->tile_cap_t), cf = std::max(F, h->tile_cap_f);
+  if (int rc = h->tile_ws.reserve(h, (size_t)ct * YFV2_MAX_DET * 32 + sizeof(int32_t) * ((size_t)4 * ct + (size_t)2 * cf), true)) return rc;
+  h->tile_cap_t = ct; h->tile_cap_f = cf;
+  return YFV2_OK;
+}
+
+// uploads the table and enqueues the two launches; everything was checked
+static int enqueue_merge(yfv2_handle h, const float* tile_dets, const int32_t* tile_count, const std::vector<int32_t>& table, int32_t T, int32_t F,
+                         double merge_thres, int32_t merge_metric, int32_t max_out, float* dets, int32_t* src, int32_t* count, hipStream_t s) {
+  char* base = h->tile_ws.as<char>();
+  const size_t list = (size_t)h->tile_cap_t * YFV2_MAX_DET * 16;
+  int32_t* d_table = reinterpret_cast<int32_t*>(base + 2 * list);
+  HIP_TRY(h, hipMemcpyAsync(d_table, table.data(), sizeof(int32_t) * table.size(), hipMemcpyHostToDevice, s));
+  TileMergeArgs a{};
+  a.tile_dets = tile_dets; a.tile_count = tile_count; a.table = d_table; a.T = T; a.F = F;
+  a.geo = reinterpret_cast<float*>(base); a.meta = reinterpret_cast<float*>(base + list);
+  a.thres = merge_thres; a.metric = merge_metric; a.max_out = max_out; a.dets = dets; a.src = src; a.count = count;
+  yfv2_launch_tile_merge(a, s);
+  HIP_TRY(h, hipGetLastError());
+  return YFV2_OK;
+}
+
+int yfv2_merge_tiles(yfv2_handle h, const float* tile_dets, const int32_t* tile_count, const yfv2_tile* tiles, int32_t T, int32_t F,
+                     double merge_thres, int32_t merge_metric, int32_t max_out, float* dets, int32_t* src, int32_t* count, void* stream) {
+  if (!h) return fail(nullptr, YFV2_ERR_ARG, "null handle");
+  if (!tile_dets || !tile_count || !dets || !count) return fail(h, YFV2_ERR_ARG, "yfv2_merge_tiles: null pointer");
+  std::vector<int32_t> table;
+  if (int rc = check_merge(h, "yfv2_merge_tiles", tiles, T, F, merge_thres, merge_metric, max_out, table)) return rc;
+  DeviceGuard guard(h->device);
+  if (int rc = ensure_tile_ws(h, T, F)) return rc;
+  return enqueue_merge(h, tile_dets, tile_count, table, T, F, merge_thres, merge_metric, max_out, dets, src, count, static_cast<hipStream_t>(stream));
+}
+
+int yfv2_detect_tiled_u8(yfv2_handle h, const yfv2_frame* frames, int32_t F, const yfv2_tile* tiles, int32_t T, float conf_thres, double iou_thres,
+                         double merge_thres, int32_t merge_metric, int32_t max_out, float* dets, int32_t* src, int32_t* count, void* stream) {
+  if (!h) return fail(nullptr, YFV2_ERR_ARG, "null handle");
+  if (!frames || !tiles || !dets || !count) return fail(h, YFV2_ERR_ARG, "yfv2_detect_tiled_u8: null pointer");
+  if (T > h->cfg.max_batch)
+    return fail(h, YFV2_ERR_BATCH, "yfv2_detect_tiled_u8: " + std::to_string(T) + " tiles above max_batch=" + std::to_string(h->cfg.max_batch));
+  std::vector<int32_t> table;
+  if (int rc = check_merge(h, "yfv2_detect_tiled_u8", tiles, T, F, merge_thres, merge_metric, max_out, table)) return rc;
+  for (int32_t f = 0; f < F; ++f)
+    if (int rc = check_frame(h, "yfv2_detect_tiled_u8: frame " + std::to_string(f) + ": ", frames[f])) return rc;
+  std::vector<yfv2_frame> crops((size_t)T);
+  for (int32_t k = 0; k < T; ++k) {
+    const yfv2_tile& t = tiles[k];
+    const yfv2_frame& fr = frames[t.frame];
+    if (t.width < 1 || t.height < 1 || t.x0 < 0 || t.y0 < 0 || (int64_t)t.x0 + t.width > fr.width || (int64_t)t.y0 + t.height > fr.height)
+      return fail(h, YFV2_ERR_ARG, "yfv2_detect_tiled_u8: tile " + std::to_string(k) + ": [" + std::to_string(t.x0) + ", " + std::to_string((int64_t)t.x0 + t.width) +
+                                       ") x [" + std::to_string(t.y0) + ", " + std::to_string((int64_t)t.y0 + t.height) + ") is not a rectangle of at least one pixel inside its " +
+                                       std::to_string(fr.width) + " x " + std::to_string(fr.height) + " frame");
+    crops[(size_t)k] = yfv2_frame{fr.data + (int64_t)t.y0 * fr.row_pitch + 3ll * t.x0, t.height, t.width, fr.row_pitch};
+  }
+  // everything yfv2_detect_frames_u8 checks, per crop, before the workspaces are touched (it checks again: host work only)
+  if (int rc = check_call(h, T, true)) return rc;
+  {
+    std::vector<ResizeFrame> t;
+    int max_w = 0;
+    if (int rc = check_frames(h, "yfv2_detect_tiled_u8", crops.data(), T, t, &max_w)) return rc;
+  }
+  DeviceGuard guard(h->device);
+  const size_t mb = (size_t)h->cfg.max_batch;
+  if (int rc = h->tile_out.reserve(h, sizeof(float) * mb * YFV2_MAX_DET * 6 + sizeof(int32_t) * (mb * YFV2_MAX_DET + mb), true)) return rc;
+  if (int rc = ensure_tile_ws(h, h->cfg.max_batch, F)) return rc;    // for max_batch tiles: no later call on this handle grows it for its tiles
+  float* t_dets = h->tile_out.as<float>();
+  int32_t* t_idx = reinterpret_cast<int32_t*>(t_dets + mb * YFV2_MAX_DET * 6);
+  int32_t* t_count = t_idx + mb * YFV2_MAX_DET;
+  if (int rc = yfv2_detect_frames_u8(h, crops.data(), T, conf_thres, iou_thres, t_dets, t_idx, t_count, stream)) return rc;
+  return enqueue_merge(h, t_dets, t_count, table, T, F, merge_thres, merge_metric, max_out, dets, src, count, static_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"

@@ -504,7 +504,7 @@ struct ClockProbeArgs {
 };
 bool yfv2_launch_clock_probe(const ClockProbeArgs& a, int workgroups, hipStream_t s);
 
-// ---- training path (yfv2_train.hip): its state hangs off the handle through an opaque slot owned by yfv2_api.hip
+// ---- training path (yfv2_train.hip): its state hangs off the handle through an opaque slot of the handle (yfv2_ctx.h)
 struct yfv2_ctx;
 struct yfv2_config;
 void** yfv2_ctx_train_slot(yfv2_ctx* h);                       // null handle -> null

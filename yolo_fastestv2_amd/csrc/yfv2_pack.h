@@ -15,16 +15,20 @@
 
 struct Folded { size_t w = 0, scale = 0, shift = 0; };  // offsets (floats) into the param blob
 
+// name -> element count of every floating-point state_dict entry of the architecture for this configuration: what a weight load
+// (WeightPacker::index) and a training bind (yfv2_train.hip) hold the caller's tensors against
+std::map<std::string, int64_t> expected_numels(const yfv2_config& cfg);
+
 struct WeightPacker {
   std::map<std::string, const yfv2_tensor_desc*> byname;
   std::vector<float> blob;
-  std::string missing;   // the first missing / mis-sized tensor (empty: none)
+  std::string missing;   // why index() refused: the first entry of the table that is missing or mis-sized
 
-  void index(const yfv2_tensor_desc* tensors, int32_t n) {
-    for (int i = 0; i < n; ++i)
-      if (tensors[i].name) byname[tensors[i].name] = &tensors[i];
-  }
-  const float* get(const std::string& name, int64_t numel);
+  // Indexes the caller's tensors and checks them against expected_numels(cfg): false (and `missing`) at the first entry, in the
+  // table's order, that is absent, has null data or another element count.  Nothing below may run before this has returned true:
+  // the folds read every tensor they name without looking again.
+  bool index(const yfv2_config& cfg, const yfv2_tensor_desc* tensors, int32_t n);
+  const float* get(const std::string& name) const { return byname.find(name)->second->data; }
   size_t reserve(size_t n) {  // 16-byte aligned slots
     size_t off = (blob.size() + 3) & ~size_t(3);
     blob.resize(off + n, 0.f);
@@ -40,12 +44,12 @@ struct WeightPacker {
   static void push_bits(std::vector<float>& im, int v) { push_bits(im, (uint32_t)v); }
 
   // ---- folded layers: raw arrays in the blob (BatchNorm -> scale / shift)
-  bool bn(const std::string& name, int c, Folded* f);
-  bool pw(const std::string& conv, const std::string& bnname, int co, int ci, Folded* f);
-  bool dw(const std::string& conv, const std::string& bnname, int c, int k, Folded* f);
-  bool stem(const std::string& conv, const std::string& bnname, Folded* f);
-  bool heads(const std::vector<std::pair<std::string, int>>& parts, int ci, Folded* f);
-  bool heads_range(const std::string& name, int rows_total, int r0, int n, int ci, Folded* f);
+  void bn(const std::string& name, int c, Folded* f);
+  void pw(const std::string& conv, const std::string& bnname, int co, int ci, Folded* f);
+  void dw(const std::string& conv, const std::string& bnname, int c, int k, Folded* f);
+  void stem(const std::string& conv, const std::string& bnname, Folded* f);
+  void heads(const std::vector<std::pair<std::string, int>>& parts, int ci, Folded* f);
+  void heads_range(const std::string& name, int r0, int n, int ci, Folded* f);   // rows [r0, r0 + n) of the conv's rows
   Folded pw_columns(const Folded& f, int co, int ci, int c0, int n);
   Folded permuted_pw_inputs(const Folded& f, int co, int ci, const int* label);
   Folded permuted_pw_outputs(const Folded& f, int co, int ci, const int* label);

@@ -213,27 +213,60 @@ void push_lane_pairs(std::vector<float>& im, Fn value) {
 // ---------------------------------------------------------------------------
 // weights: reference state_dict -> one blob of kernel-ready parameters
 // ---------------------------------------------------------------------------
-const float* WeightPacker::get(const std::string& name, int64_t numel) {
-  auto it = byname.find(name);
-  if (it == byname.end() || it->second->data == nullptr) {
-    if (missing.empty()) missing = "missing tensor '" + name + "'";
-    return nullptr;
+// element count of every floating-point state_dict entry of the architecture (model/detector.py:8-19 and the modules it builds:
+// shufflenetv2.py:19-46,66-100, fpn.py:5-49) for this configuration
+std::map<std::string, int64_t> expected_numels(const yfv2_config& cfg) {
+  std::map<std::string, int64_t> m;
+  auto conv = [&](const std::string& n, int co, int ci_per_group, int k) { m[n + ".weight"] = (int64_t)co * ci_per_group * k * k; };
+  auto bn = [&](const std::string& n, int c) { for (const char* leaf : {".weight", ".bias", ".running_mean", ".running_var"}) m[n + leaf] = c; };
+  conv("backbone.first_conv.0", 24, 3, 3); bn("backbone.first_conv.1", 24);
+  const int repeats[3] = {4, 8, 4}, chans[4] = {24, 48, 96, 192};
+  int cin = 24;
+  for (int si = 0; si < 3; ++si) {
+    const int cout = chans[si + 1], mid = cout / 2;
+    for (int i = 0; i < repeats[si]; ++i) {
+      const std::string p = "backbone.stage" + std::to_string(si + 2) + "." + std::to_string(i);
+      const int inp = i == 0 ? cin : cin / 2;
+      conv(p + ".branch_main.0", mid, inp, 1); bn(p + ".branch_main.1", mid);
+      conv(p + ".branch_main.3", mid, 1, 3); bn(p + ".branch_main.4", mid);
+      conv(p + ".branch_main.5", cout - inp, mid, 1); bn(p + ".branch_main.6", cout - inp);
+      if (i == 0) {
+        conv(p + ".branch_proj.0", inp, 1, 3); bn(p + ".branch_proj.1", inp);
+        conv(p + ".branch_proj.2", inp, inp, 1); bn(p + ".branch_proj.3", inp);
+      }
+      cin = cout;
+    }
   }
-  if (it->second->numel != numel) {
-    if (missing.empty())
-      missing = "tensor '" + name + "' has " + std::to_string(it->second->numel) + " elements, expected " +
-                std::to_string(numel);
-    return nullptr;
+  conv("fpn.conv1x1_2.0", 72, 288, 1); bn("fpn.conv1x1_2.1", 72);
+  conv("fpn.conv1x1_3.0", 72, 192, 1); bn("fpn.conv1x1_3.1", 72);
+  for (const char* head : {"cls_head_2", "reg_head_2", "reg_head_3", "cls_head_3"}) {
+    const std::string p = std::string("fpn.") + head + ".block";
+    conv(p + ".0", 72, 1, 5); bn(p + ".1", 72); conv(p + ".3", 72, 72, 1); bn(p + ".4", 72);
+    conv(p + ".5", 72, 1, 5); bn(p + ".6", 72); conv(p + ".8", 72, 72, 1); bn(p + ".9", 72);
   }
-  return it->second->data;
+  const int A = cfg.anchor_num;
+  const std::pair<const char*, int> outs[3] = {{"output_reg_layers", 4 * A}, {"output_obj_layers", A}, {"output_cls_layers", cfg.classes}};
+  for (const auto& o : outs) { m[std::string(o.first) + ".weight"] = (int64_t)o.second * 72; m[std::string(o.first) + ".bias"] = o.second; }
+  return m;
+}
+bool WeightPacker::index(const yfv2_config& cfg, const yfv2_tensor_desc* tensors, int32_t n) {
+  for (int i = 0; i < n; ++i)
+    if (tensors[i].name) byname[tensors[i].name] = &tensors[i];
+  for (const auto& [name, numel] : expected_numels(cfg)) {
+    auto it = byname.find(name);
+    if (it == byname.end() || it->second->data == nullptr) missing = "missing tensor '" + name + "'";
+    else if (it->second->numel != numel)
+      missing = "tensor '" + name + "' has " + std::to_string(it->second->numel) + " elements, expected " + std::to_string(numel);
+    if (!missing.empty()) return false;
+  }
+  return true;
 }
 // eval-mode BatchNorm2d -> y = x*scale + shift  (ATen: alpha = gamma*invstd, beta = bias - mean*alpha)
-bool WeightPacker::bn(const std::string& name, int c, Folded* f) {
-  const float* g = get(name + ".weight", c);
-  const float* b = get(name + ".bias", c);
-  const float* m = get(name + ".running_mean", c);
-  const float* v = get(name + ".running_var", c);
-  if (!g || !b || !m || !v) return false;
+void WeightPacker::bn(const std::string& name, int c, Folded* f) {
+  const float* g = get(name + ".weight");
+  const float* b = get(name + ".bias");
+  const float* m = get(name + ".running_mean");
+  const float* v = get(name + ".running_var");
   f->scale = reserve(c);
   f->shift = reserve(c);
   for (int i = 0; i < c; ++i) {
@@ -242,36 +275,32 @@ bool WeightPacker::bn(const std::string& name, int c, Folded* f) {
     blob[f->scale + i] = alpha;
     blob[f->shift + i] = b[i] - m[i] * alpha;
   }
-  return true;
 }
 // pointwise conv weight (co, ci, 1, 1) is already the [M][K] row-major A operand
-bool WeightPacker::pw(const std::string& conv, const std::string& bnname, int co, int ci, Folded* f) {
-  const float* w = get(conv + ".weight", (int64_t)co * ci);
-  if (!w) return false;
+void WeightPacker::pw(const std::string& conv, const std::string& bnname, int co, int ci, Folded* f) {
+  const float* w = get(conv + ".weight");
   f->w = reserve((size_t)co * ci);
   std::memcpy(&blob[f->w], w, sizeof(float) * co * ci);
-  return bn(bnname, co, f);
+  bn(bnname, co, f);
 }
 // depthwise weight (C,1,k,k) -> [k*k][C] so that a channel quad is one 16-byte load
-bool WeightPacker::dw(const std::string& conv, const std::string& bnname, int c, int k, Folded* f) {
-  const float* w = get(conv + ".weight", (int64_t)c * k * k);
-  if (!w) return false;
+void WeightPacker::dw(const std::string& conv, const std::string& bnname, int c, int k, Folded* f) {
+  const float* w = get(conv + ".weight");
   f->w = reserve((size_t)c * k * k);
   for (int ch = 0; ch < c; ++ch)
     for (int t = 0; t < k * k; ++t) blob[f->w + (size_t)t * c + ch] = w[(size_t)ch * k * k + t];
-  return bn(bnname, c, f);
+  bn(bnname, c, f);
 }
 // stem weight (24,3,3,3) -> [27 taps][24 co]
-bool WeightPacker::stem(const std::string& conv, const std::string& bnname, Folded* f) {
-  const float* w = get(conv + ".weight", 24 * 27);
-  if (!w) return false;
+void WeightPacker::stem(const std::string& conv, const std::string& bnname, Folded* f) {
+  const float* w = get(conv + ".weight");
   f->w = reserve(24 * 27);
   for (int co = 0; co < 24; ++co)
     for (int t = 0; t < 27; ++t) blob[f->w + (size_t)t * 24 + co] = w[co * 27 + t];
-  return bn(bnname, 24, f);
+  bn(bnname, 24, f);
 }
 // biased output convs: rows of several (co_i, 72) matrices stacked; scale = 1, shift = bias
-bool WeightPacker::heads(const std::vector<std::pair<std::string, int>>& parts, int ci, Folded* f) {
+void WeightPacker::heads(const std::vector<std::pair<std::string, int>>& parts, int ci, Folded* f) {
   int total = 0;
   for (auto& p : parts) total += p.second;
   f->w = reserve((size_t)total * ci);
@@ -279,9 +308,8 @@ bool WeightPacker::heads(const std::vector<std::pair<std::string, int>>& parts, 
   f->shift = reserve(total);
   int row = 0;
   for (auto& p : parts) {
-    const float* w = get(p.first + ".weight", (int64_t)p.second * ci);
-    const float* b = get(p.first + ".bias", p.second);
-    if (!w || !b) return false;
+    const float* w = get(p.first + ".weight");
+    const float* b = get(p.first + ".bias");
     std::memcpy(&blob[f->w + (size_t)row * ci], w, sizeof(float) * p.second * ci);
     for (int i = 0; i < p.second; ++i) {
       blob[f->scale + row + i] = 1.0f;
@@ -289,17 +317,14 @@ bool WeightPacker::heads(const std::vector<std::pair<std::string, int>>& parts, 
     }
     row += p.second;
   }
-  return true;
 }
 // rows [r0, r0 + n) of one biased output conv (the class head of a model with more classes than one launch's 96 rows)
-bool WeightPacker::heads_range(const std::string& name, int rows_total, int r0, int n, int ci, Folded* f) {
-  const float* w = get(name + ".weight", (int64_t)rows_total * ci);
-  const float* b = get(name + ".bias", rows_total);
-  if (!w || !b || r0 < 0 || r0 + n > rows_total) return false;
+void WeightPacker::heads_range(const std::string& name, int r0, int n, int ci, Folded* f) {
+  const float* w = get(name + ".weight");
+  const float* b = get(name + ".bias");
   f->w = reserve((size_t)n * ci); f->scale = reserve(n); f->shift = reserve(n);
   std::memcpy(&blob[f->w], w + (size_t)r0 * ci, sizeof(float) * n * ci);
   for (int i = 0; i < n; ++i) { blob[f->scale + i] = 1.0f; blob[f->shift + i] = b[r0 + i]; }
-  return true;
 }
 // columns [c0, c0 + n) of a folded conv's filter as a conv of its own (same BN scale / shift)
 Folded WeightPacker::pw_columns(const Folded& f, int co, int ci, int c0, int n) {

@@ -1,6 +1,6 @@
 // yfv2_plan.h - the forward launch plan of libyfv2.so: what a handle launches for one forward, in order, built once per
 // weight load from the model configuration (yfv2_plan.hip: PlanBuilder) and enqueued on the caller's stream by plan_run.
-// Host only: no kernel.  The handle, the workspace's memory and the entry points are yfv2_api.hip's.  Not part of the public ABI.
+// Host only: no kernel.  The handle (yfv2_ctx.h), the workspace's memory and the entry points are the API units'.  Not part of the public ABI.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -138,8 +138,8 @@ struct Plan {
   struct Activation { float* p = nullptr; size_t per_img = 0; int c = 0; } dbg[6];
 };
 
-// Builds the plan of a configuration and packs its images into wp (already indexed).  False: a tensor is missing or mis-sized
-// (wp.missing) or a layout rule did not hold; *out is then untouched.
+// Builds the plan of a configuration and packs its images into wp, whose index() has accepted the caller's tensors (no fold can
+// fail after that).  False: a layout rule did not hold; *out is then untouched.
 bool plan_build(const yfv2_config& cfg, const PlanSwitches& sw, const Workspace& ws, WeightPacker& wp, Plan* out);
 
 // kernel (family) a step launches, as it appears in a rocprofv3 kernel trace (prefix of the symbol name)

@@ -39,7 +39,7 @@ struct PlanBuilder {
 
   void add_stem(const Buf& out, bool pp_out) {
     Folded f;
-    ok &= wp.stem("backbone.first_conv.0", "backbone.first_conv.1", &f);
+    wp.stem("backbone.first_conv.0", "backbone.first_conv.1", &f);
     Step s;
     StemStep kd;
     kd.args.out = out.p;
@@ -110,11 +110,11 @@ struct PlanBuilder {
     const int rfused = (cin == 24 || cin == 48 || (cin == 96 && !pp_label && sw.bf6)) ? yfv2_block_s2_rows(cin, H, W) : 0;   // 96: block_s2w_kernel (its pw1 is bf16x6 only)
     if (!layer_plan && rfused > 0) {
       Folded f1, fd, f2, fpd, fpp;
-      ok &= wp.dw(p + ".branch_proj.0", p + ".branch_proj.1", cin, 3, &fpd);
-      ok &= wp.pw(p + ".branch_proj.2", p + ".branch_proj.3", cin, cin, &fpp);
-      ok &= wp.pw(p + ".branch_main.0", p + ".branch_main.1", cin, cin, &f1);
-      ok &= wp.dw(p + ".branch_main.3", p + ".branch_main.4", cin, 3, &fd);
-      ok &= wp.pw(p + ".branch_main.5", p + ".branch_main.6", cin, cin, &f2);
+      wp.dw(p + ".branch_proj.0", p + ".branch_proj.1", cin, 3, &fpd);
+      wp.pw(p + ".branch_proj.2", p + ".branch_proj.3", cin, cin, &fpp);
+      wp.pw(p + ".branch_main.0", p + ".branch_main.1", cin, cin, &f1);
+      wp.dw(p + ".branch_main.3", p + ".branch_main.4", cin, 3, &fd);
+      wp.pw(p + ".branch_main.5", p + ".branch_main.6", cin, cin, &f2);
       Step s;
       S2Step kd;
       kd.cin = cin;
@@ -144,18 +144,18 @@ struct PlanBuilder {
       push(s, kd);
       return;
     }
-    ok &= wp.dw(p + ".branch_proj.0", p + ".branch_proj.1", cin, 3, &f);
+    wp.dw(p + ".branch_proj.0", p + ".branch_proj.1", cin, 3, &f);
     if (in_label && ok) f = wp.permuted_dw_channels(f, cin, 9, in_label);
     add_dw(p + ".proj.dw3x3s2+bn", 3, 2, cin, H, W, x.p, cin, ws.t3.p, cin, false, f);
-    ok &= wp.pw(p + ".branch_proj.2", p + ".branch_proj.3", cin, cin, &f);
+    wp.pw(p + ".branch_proj.2", p + ".branch_proj.3", cin, cin, &f);
     if (in_label && ok) f = wp.permuted_pw_inputs(f, cin, cin, in_label);
     add_pw(p + ".proj.pw+bn+relu", cin, PW_PLAIN, cin, oh * ow, ws.t3.p, cin, 0, y.p, co, 0, true, f);
-    ok &= wp.pw(p + ".branch_main.0", p + ".branch_main.1", cin, cin, &f);
+    wp.pw(p + ".branch_main.0", p + ".branch_main.1", cin, cin, &f);
     if (in_label && ok) f = wp.permuted_pw_inputs(f, cin, cin, in_label);
     add_pw(p + ".main.pw1+bn+relu", cin, PW_PLAIN, cin, H * W, x.p, cin, 0, ws.t1.p, cin, 0, true, f);
-    ok &= wp.dw(p + ".branch_main.3", p + ".branch_main.4", cin, 3, &f);
+    wp.dw(p + ".branch_main.3", p + ".branch_main.4", cin, 3, &f);
     add_dw(p + ".main.dw3x3s2+bn", 3, 2, cin, H, W, ws.t1.p, cin, ws.t2.p, cin, false, f);
-    ok &= wp.pw(p + ".branch_main.5", p + ".branch_main.6", cin, cin, &f);
+    wp.pw(p + ".branch_main.5", p + ".branch_main.6", cin, cin, &f);
     add_pw(p + ".main.pw2+bn+relu", cin, PW_PLAIN, cin, oh * ow, ws.t2.p, cin, 0, y.p, co, cin, true, f);
   }
 
@@ -174,11 +174,11 @@ struct PlanBuilder {
   // stage2.0 in lane-per-pixel form: reads the stem's pair planes, writes logical channel c to slot(c) of buffer 0
   void s2px_block(const std::string& p, int IH, int IW) {
     Folded f1, fd, f2, fpd, fpp;
-    ok &= wp.dw(p + ".branch_proj.0", p + ".branch_proj.1", 24, 3, &fpd);
-    ok &= wp.pw(p + ".branch_proj.2", p + ".branch_proj.3", 24, 24, &fpp);
-    ok &= wp.pw(p + ".branch_main.0", p + ".branch_main.1", 24, 24, &f1);
-    ok &= wp.dw(p + ".branch_main.3", p + ".branch_main.4", 24, 3, &fd);
-    ok &= wp.pw(p + ".branch_main.5", p + ".branch_main.6", 24, 24, &f2);
+    wp.dw(p + ".branch_proj.0", p + ".branch_proj.1", 24, 3, &fpd);
+    wp.pw(p + ".branch_proj.2", p + ".branch_proj.3", 24, 24, &fpp);
+    wp.pw(p + ".branch_main.0", p + ".branch_main.1", 24, 24, &f1);
+    wp.dw(p + ".branch_main.3", p + ".branch_main.4", 24, 3, &fd);
+    wp.pw(p + ".branch_main.5", p + ".branch_main.6", 24, 24, &f2);
     const int OH = IH / 2, OW = IW / 2;
     int slot_of[48];
     for (int k = 0; k < 48; ++k) slot_of[yfv2_stage2_channel(k)] = k;
@@ -216,9 +216,9 @@ struct PlanBuilder {
   }
   void s1px_block(const std::string& p, int H, int W, Stage2Layout& L, long long bufstride) {
     Folded f1, fd, f2;
-    ok &= wp.pw(p + ".branch_main.0", p + ".branch_main.1", 24, 24, &f1);
-    ok &= wp.dw(p + ".branch_main.3", p + ".branch_main.4", 24, 3, &fd);
-    ok &= wp.pw(p + ".branch_main.5", p + ".branch_main.6", 24, 24, &f2);
+    wp.pw(p + ".branch_main.0", p + ".branch_main.1", 24, 24, &f1);
+    wp.dw(p + ".branch_main.3", p + ".branch_main.4", 24, 3, &fd);
+    wp.pw(p + ".branch_main.5", p + ".branch_main.6", 24, 24, &f2);
     Step s;
     S1PxStep kd;
     int order[24], kk = 0;
@@ -272,9 +272,9 @@ struct PlanBuilder {
     const int c2 = c / 2, NB = (int)names.size();
     std::vector<Folded> f1(NB), fd(NB), f2(NB);
     for (int k = 0; k < NB; ++k) {
-      ok &= wp.pw(names[k] + ".branch_main.0", names[k] + ".branch_main.1", c2, c2, &f1[k]);
-      ok &= wp.dw(names[k] + ".branch_main.3", names[k] + ".branch_main.4", c2, 3, &fd[k]);
-      ok &= wp.pw(names[k] + ".branch_main.5", names[k] + ".branch_main.6", c2, c2, &f2[k]);
+      wp.pw(names[k] + ".branch_main.0", names[k] + ".branch_main.1", c2, c2, &f1[k]);
+      wp.dw(names[k] + ".branch_main.3", names[k] + ".branch_main.4", c2, 3, &fd[k]);
+      wp.pw(names[k] + ".branch_main.5", names[k] + ".branch_main.6", c2, c2, &f2[k]);
     }
     std::vector<float> im;
     if (ok && c2 == 48 && NB >= 3 && NB <= 7) {
@@ -455,9 +455,9 @@ struct PlanBuilder {
     std::vector<Folded> f1, fd, f2;
     for (int k = 0; k < NB && ok; ++k) {
       Folded a, d, b;
-      ok &= wp.pw(names[k] + ".branch_main.0", names[k] + ".branch_main.1", c2, c2, &a);
-      ok &= wp.dw(names[k] + ".branch_main.3", names[k] + ".branch_main.4", c2, 3, &d);
-      ok &= wp.pw(names[k] + ".branch_main.5", names[k] + ".branch_main.6", c2, c2, &b);
+      wp.pw(names[k] + ".branch_main.0", names[k] + ".branch_main.1", c2, c2, &a);
+      wp.dw(names[k] + ".branch_main.3", names[k] + ".branch_main.4", c2, 3, &d);
+      wp.pw(names[k] + ".branch_main.5", names[k] + ".branch_main.6", c2, c2, &b);
       if (ok) { f1.push_back(a); fd.push_back(d); f2.push_back(b); }
     }
     Step s;
@@ -480,13 +480,13 @@ struct PlanBuilder {
   void block_s1(const std::string& p, int c, int H, int W, const Buf& x, const Buf& y) {
     Folded f;
     const int c2 = c / 2;
-    ok &= wp.pw(p + ".branch_main.0", p + ".branch_main.1", c2, c2, &f);
+    wp.pw(p + ".branch_main.0", p + ".branch_main.1", c2, c2, &f);
     Step& s = add_pw(p + ".shuffle+pass+main.pw1+bn+relu", c2, PW_SHUFFLE, c2, H * W, x.p, c, 0, ws.t1.p, c2, 0, true, f);
     pw(s).args.copy = y.p; pw(s).args.copy_stride = c; pw(s).args.copy_off = 0;
     s.bytes = 4.0 * H * W * (c + c2 + c2);  // reads both halves, writes pass-through half + pw1 output
-    ok &= wp.dw(p + ".branch_main.3", p + ".branch_main.4", c2, 3, &f);
+    wp.dw(p + ".branch_main.3", p + ".branch_main.4", c2, 3, &f);
     add_dw(p + ".main.dw3x3+bn", 3, 1, c2, H, W, ws.t1.p, c2, ws.t2.p, c2, false, f);
-    ok &= wp.pw(p + ".branch_main.5", p + ".branch_main.6", c2, c2, &f);
+    wp.pw(p + ".branch_main.5", p + ".branch_main.6", c2, c2, &f);
     add_pw(p + ".main.pw2+bn+relu", c2, PW_PLAIN, c2, H * W, ws.t2.p, c2, 0, y.p, c, c2, true, f);
   }
 
@@ -534,14 +534,14 @@ struct PlanBuilder {
   void wide_cls_heads(const std::string& p, int px, int scale_idx) {
     const int A = cfg.anchor_num, nc = cfg.classes;
     Folded f;
-    ok &= wp.heads({{"output_obj_layers", A}}, 72, &f);
+    wp.heads({{"output_obj_layers", A}}, 72, &f);
     {
       Step& s = add_pw(p + " -> output_obj (bias, NCHW)", 72, PW_HEAD, A, px, ws.tb.p, 72, 0, nullptr, 0, 0, false, f);
       pw(s).args.split = A; pw(s).head0 = scale_idx * 3 + 1; pw(s).head1 = -1;
     }
     for (int c0 = 0; c0 < nc; c0 += 96) {
       const int n = std::min(96, nc - c0);
-      ok &= wp.heads_range("output_cls_layers", nc, c0, n, 72, &f);
+      wp.heads_range("output_cls_layers", c0, n, 72, &f);
       Step& s = add_pw(p + " -> output_cls channels " + std::to_string(c0) + ".." + std::to_string(c0 + n - 1) + " (bias, NCHW)", 72, PW_HEAD, n, px,
                        ws.tb.p, 72, 0, nullptr, 0, 0, false, f);
       pw(s).args.split = n; pw(s).args.ctot0 = nc; pw(s).args.coff0 = c0; pw(s).head0 = scale_idx * 3 + 2; pw(s).head1 = -1;
@@ -554,10 +554,10 @@ struct PlanBuilder {
     {
       if (!sw.plan.layer_by_layer && yfv2_tower2_supported(H, W)) {
         Folded fd1, fp1, fd2, fp2, fh;
-        ok &= wp.dw(p + ".0", p + ".1", 72, 5, &fd1);
-        ok &= wp.pw(p + ".3", p + ".4", 72, 72, &fp1);
-        ok &= wp.dw(p + ".5", p + ".6", 72, 5, &fd2);
-        ok &= wp.pw(p + ".8", p + ".9", 72, 72, &fp2);
+        wp.dw(p + ".0", p + ".1", 72, 5, &fd1);
+        wp.pw(p + ".3", p + ".4", 72, 72, &fp1);
+        wp.dw(p + ".5", p + ".6", 72, 5, &fd2);
+        wp.pw(p + ".8", p + ".9", 72, 72, &fp2);
         const int A = cfg.anchor_num, nc = cfg.classes;
         float* mid = (!is_cls && pair_level(H, W)) ? ws.tb.p : ws.ta.p;   // (paired level: both towers' a halves are alive at once)
         tower_half(p + " half a: dw5x5+bn+relu -> pw+bn", H, W, s_in.p, mid, fd1, fp1, nullptr, 0, 0, -1, -1);
@@ -565,37 +565,37 @@ struct PlanBuilder {
           tower_half(p + " half b: dw5x5+bn+relu -> pw+bn", H, W, mid, ws.tb.p, fd2, fp2, nullptr, 0, 0, -1, -1);
           wide_cls_heads(p, px, scale_idx);
         } else if (is_cls) {
-          ok &= wp.heads({{"output_obj_layers", A}, {"output_cls_layers", nc}}, 72, &fh);
+          wp.heads({{"output_obj_layers", A}, {"output_cls_layers", nc}}, 72, &fh);
           tower_half(p + " half b: dw5x5+bn+relu -> pw+bn -> output_obj+output_cls (bias, NCHW)", H, W, mid, nullptr, fd2,
                      fp2, &fh, A + nc, A, scale_idx * 3 + 1, scale_idx * 3 + 2);
         } else {
-          ok &= wp.heads({{"output_reg_layers", 4 * A}}, 72, &fh);
+          wp.heads({{"output_reg_layers", 4 * A}}, 72, &fh);
           tower_half(p + " half b: dw5x5+bn+relu -> pw+bn -> output_reg (bias, NCHW)", H, W, mid, nullptr, fd2, fp2, &fh,
                      4 * A, 4 * A, scale_idx * 3 + 0, -1);
         }
         return;
       }
     }
-    ok &= wp.dw(p + ".0", p + ".1", 72, 5, &f);
+    wp.dw(p + ".0", p + ".1", 72, 5, &f);
     add_dw(p + ".dw5x5+bn+relu(a)", 5, 1, 72, H, W, s_in.p, 72, ws.ta.p, 72, true, f);
-    ok &= wp.pw(p + ".3", p + ".4", 72, 72, &f);
+    wp.pw(p + ".3", p + ".4", 72, 72, &f);
     add_pw(p + ".pw+bn(a)", 72, PW_PLAIN, 72, px, ws.ta.p, 72, 0, ws.tb.p, 72, 0, false, f);
-    ok &= wp.dw(p + ".5", p + ".6", 72, 5, &f);
+    wp.dw(p + ".5", p + ".6", 72, 5, &f);
     add_dw(p + ".dw5x5+bn+relu(b)", 5, 1, 72, H, W, ws.tb.p, 72, ws.ta.p, 72, true, f);
-    ok &= wp.pw(p + ".8", p + ".9", 72, 72, &f);
+    wp.pw(p + ".8", p + ".9", 72, 72, &f);
     add_pw(p + ".pw+bn(b)", 72, PW_PLAIN, 72, px, ws.ta.p, 72, 0, ws.tb.p, 72, 0, false, f);
     const int A = cfg.anchor_num, nc = cfg.classes;
     if (is_cls && A + nc > 96) {
       wide_cls_heads(p, px, scale_idx);
     } else if (is_cls) {
-      ok &= wp.heads({{"output_obj_layers", A}, {"output_cls_layers", nc}}, 72, &f);
+      wp.heads({{"output_obj_layers", A}, {"output_cls_layers", nc}}, 72, &f);
       Step& s = add_pw(p + " -> output_obj+output_cls (bias, NCHW)", 72, PW_HEAD, A + nc, px, ws.tb.p, 72, 0, nullptr,
                        0, 0, false, f);
       pw(s).args.split = A;
       pw(s).head0 = scale_idx * 3 + 1;
       pw(s).head1 = scale_idx * 3 + 2;
     } else {
-      ok &= wp.heads({{"output_reg_layers", 4 * A}}, 72, &f);
+      wp.heads({{"output_reg_layers", 4 * A}}, 72, &f);
       Step& s = add_pw(p + " -> output_reg (bias, NCHW)", 72, PW_HEAD, 4 * A, px, ws.tb.p, 72, 0, nullptr, 0, 0, false, f);
       pw(s).args.split = 4 * A;
       pw(s).head0 = scale_idx * 3 + 0;
@@ -741,9 +741,9 @@ struct PlanBuilder {
     const Buf* c3 = x;
     const int h3 = H / 32, w3 = W / 32, h2 = H / 16, w2 = W / 16;
     Folded f;
-    ok &= wp.pw("fpn.conv1x1_3.0", "fpn.conv1x1_3.1", 72, 192, &f);
+    wp.pw("fpn.conv1x1_3.0", "fpn.conv1x1_3.1", 72, 192, &f);
     add_pw("fpn.conv1x1_3 pw192->72+bn+relu", 192, PW_PLAIN, 72, h3 * w3, c3->p, 192, 0, ws.f3.p, 72, 0, true, f);
-    ok &= wp.pw("fpn.conv1x1_2.0", "fpn.conv1x1_2.1", 72, 288, &f);
+    wp.pw("fpn.conv1x1_2.0", "fpn.conv1x1_2.1", 72, 288, &f);
     if (plan.c2_permuted && ok) {   // columns 192.. read C2 in the chain kernel's channel order
       int lab[288];
       for (int k = 0; k < 192; ++k) lab[k] = k;
@@ -760,7 +760,7 @@ struct PlanBuilder {
       Step& s3 = plan.steps.back();                                     // conv1x1_3 just added: it becomes the dual launch
       Folded fa = wp.pw_columns(f, 72, 288, 0, 192), fb = wp.pw_columns(f, 72, 288, 192, 96);
       Folded f3;
-      ok &= wp.pw("fpn.conv1x1_3.0", "fpn.conv1x1_3.1", 72, 192, &f3);
+      wp.pw("fpn.conv1x1_3.0", "fpn.conv1x1_3.1", 72, 192, &f3);
       pw(s3).mode = PW_DUAL;
       pw(s3).args.copy = ws.fq.p; pw(s3).args.copy_stride = 72; pw(s3).args.copy_off = 0;
       pw(s3).args.presplit = 1;
@@ -925,7 +925,7 @@ const char* launch(const TowerStep& st, const RunCtx& c) {
 bool plan_build(const yfv2_config& cfg, const PlanSwitches& sw, const Workspace& ws, WeightPacker& wp, Plan* out) {
   PlanBuilder pb{cfg, sw, ws, wp};
   pb.build();
-  if (!pb.ok || !wp.missing.empty()) return false;
+  if (!pb.ok) return false;
   *out = std::move(pb.plan);
   return true;
 }
