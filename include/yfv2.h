@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define YFV2_ABI_VERSION 7 /* 2: yfv2_stage_info reports external bytes as well; 3: yfv2_train_*, yfv2_sgd_step; 4: yfv2_nonfinite, lanes; 5: yfv2_nonfinite_peek, yfv2_clock_probe_*; 6: yfv2_plan / yfv2_create_ex (the library reads no environment variable); 7: yfv2_debug_post; still 7 with the additive yfv2_frame, yfv2_resize_frames_u8, yfv2_detect_frames_u8 and the additive yfv2_anchor_kmeans, yfv2_kmeans_info, yfv2_debug_kmeans_group; still 7 with the additive yfv2_tile, yfv2_tile_plan, yfv2_merge_tiles, yfv2_detect_tiled_u8 (old callers are unaffected) */
+#define YFV2_ABI_VERSION 7 /* 2: yfv2_stage_info reports external bytes as well; 3: yfv2_train_*, yfv2_sgd_step; 4: yfv2_nonfinite, lanes; 5: yfv2_nonfinite_peek, yfv2_clock_probe_*; 6: yfv2_plan / yfv2_create_ex (the library reads no environment variable); 7: yfv2_debug_post; still 7 with the additive yfv2_frame, yfv2_resize_frames_u8, yfv2_detect_frames_u8 and the additive yfv2_anchor_kmeans, yfv2_kmeans_info, yfv2_debug_kmeans_group; still 7 with the additive yfv2_tile, yfv2_tile_plan, yfv2_merge_tiles, yfv2_detect_tiled_u8 and the additive yfv2_target_box, yfv2_export_maps, yfv2_deploy_post, yfv2_deploy_dropped, yfv2_detect_deploy_frames_u8 (old callers are unaffected) */
 #define YFV2_API __attribute__((visibility("default")))
 #define YFV2_MAX_DET 300 /* utils/utils.py:243 max_det */
 
@@ -260,6 +260,62 @@ YFV2_API int yfv2_merge_tiles(yfv2_handle h, const float* tile_dets /* (T,300,6)
 YFV2_API int yfv2_detect_tiled_u8(yfv2_handle h, const yfv2_frame* frames, int32_t F, const yfv2_tile* tiles, int32_t T,
                                   float conf_thres, double iou_thres, double merge_thres, int32_t merge_metric, int32_t max_out,
                                   float* dets, int32_t* src, int32_t* count, void* stream);
+
+/* ---- the ncnn sample's deployment path (sample/ncnn/src/yolo-fastestv2.cpp) ----
+ * The reference's only native component post-processes differently from its Python path in every step that decides which boxes
+ * come out: no objectness pre-filter (score = cls * obj > thresh only), boxes scaled to the source frame and TRUNCATED TO int
+ * before the NMS, the overlap of intersection_area (touching boxes intersect, with area 0), classes compared explicitly, no
+ * limit of 300, default thresholds 0.3 / 0.25.  The entry points below compute exactly that; yfv2_decode / yfv2_nms /
+ * yfv2_detect* stay the Python path's arithmetic. */
+typedef struct yfv2_target_box { int32_t x1, y1, x2, y2, cate; float score; } yfv2_target_box;   /* yolo-fastestv2.h:9-25 TargetBox */
+
+/* replaces: model/detector.py:33-44, the export layout of Detector(export_onnx=True), on the six NCHW logit maps of yfv2_forward:
+ * map0 (B, H/16, W/16, 5A + classes), map1 (B, H/32, W/32, 5A + classes), NHWC fp32 on the device, 4-byte aligned; channels
+ * sigmoid(4A reg) | sigmoid(A obj) | softmax(classes).  The obj and class channels of pixel (y, x) are bit-identical to columns 4
+ * and 5.. of yfv2_decode's rows (y, x, a) (the same device functions); the reg channels are that sigmoid of the logits.  One
+ * launch, every logit read once.  Needs no weights. */
+YFV2_API int yfv2_export_maps(yfv2_handle h, const float* const out6[6], int32_t B, float* map0, float* map1, void* stream);
+
+/* replaces: yolo-fastestv2.cpp:113-183 getCategory + predHandle and :58-110 intersection_area + nmsHandle, for B images at once,
+ * on two maps in yfv2_export_maps' layout (from any producer).  One workgroup per image; enqueue only.  THE RULE, bit for bit
+ * (tests/deploy_model.py restates it in numpy; tests/golden/golden_deploy.npz holds the compiled sample's own results):
+ *   rows         scale 0 then 1; h, w, anchor b - the sample's loop order.  v = the pixel's 5A + classes floats
+ *   score, cate  objScore = v[4A + b]; over the classes i in ascending order fl32(v[5A + i] * objScore), running maximum with
+ *                strict > from 0: the FIRST maximum wins; nothing above 0 (or only NaN): score -1, cate -1, never a candidate
+ *   candidate    score > thresh in fp32
+ *   box          bcx = fl32(((v[4b] * 2. - 0.5) + w) * stride) in double, stride = cfg.height / map height (integer); bcy likewise;
+ *                bw = fl32((v[4b + 2] * 2.)^2 * anchor) in double with the handle's anchor (yfv2_set_anchors) ROUNDED TO float, as
+ *                the sample's std::vector<float> holds it; x1 = (int)((bcx - 0.5 * bw) * scaleW) in double, truncated toward zero
+ *   order        score descending; TIES BY CANDIDATE ORDER (the row order above).  The sample calls std::sort, which leaves the
+ *                order of equal scores unspecified: this is the ONLY place where the result may differ from a build of the sample
+ *   greedy walk  a candidate is dropped if an already kept one has the same cate and IoU > nms_thresh with it, in fp32:
+ *                inter = 0 if a.x1 > b.x2 || a.x2 < b.x1 || a.y1 > b.y2 || a.y2 < b.y1, else float(min x2 - max x1) *
+ *                float(min y2 - max y1) (int differences); area = float(x2 - x1) * float(y2 - y1); IoU = inter / ((area_a +
+ *                area_b) - inter), IEEE division - 0 / 0 = NaN keeps the box
+ *   scale        device (B, 2) fp32 scaleW, scaleH per image, or NULL = 1, 1
+ *   boxes        device (B, max_out) records: the kept candidates of image b in walk order; count[b] is the FULL number of
+ *                survivors (there is no cap of 300: the sample has none), only the first max_out are stored and the records from
+ *                min(count[b], max_out) on are zero.  max_out in 1..yfv2_num_rows
+ * DELIBERATE DIFFERENCE: the sample's (int) of a value that is NaN or outside int32 is undefined behaviour (a candidate whose reg
+ * values are not finite).  Such a candidate is dropped here and counted: yfv2_deploy_dropped waits for `stream` and returns the
+ * number of candidates the LAST yfv2_deploy_post / yfv2_detect_deploy_frames_u8 on this handle dropped (0 for sane maps).
+ * thresh < 0 or NaN is YFV2_ERR_ARG (a score is never negative; the order keys rely on it), as are NULL pointers and max_out out
+ * of range - before anything is enqueued; B outside 1..max_batch is YFV2_ERR_BATCH.  Needs no weights.  The first post call on a
+ * handle allocates a few bytes (one device wait). */
+YFV2_API int yfv2_deploy_post(yfv2_handle h, const float* map0, const float* map1, int32_t B,
+                              const float* scale /* device (B,2) fp32 scaleW,scaleH; NULL = 1,1 */, float thresh, float nms_thresh,
+                              yfv2_target_box* boxes /* (B,max_out) */, int32_t* count /* (B) */, int32_t max_out, void* stream);
+YFV2_API int yfv2_deploy_dropped(yfv2_handle h, int32_t* dropped /* host */, void* stream);
+
+/* replaces: yolo-fastestv2.cpp:185-221 yoloFastestv2::detection for a batch of frames of any sizes: yfv2_resize_frames_u8 ->
+ * yfv2_forward_u8 (on the handle's lanes where the plan has them) -> yfv2_export_maps into a workspace of the handle ->
+ * yfv2_deploy_post with scaleW = (float)width_b / (float)cfg.width, scaleH = (float)height_b / (float)cfg.height (:189-190).  Bit-identical
+ * to those four calls one after the other.  The resize is the library's cv2-arithmetic bilinear (yfv2_resize_u8), NOT ncnn's
+ * from_pixels_resize (:193): pixel values, and with them scores, differ slightly from an ncnn run on the same frame; the
+ * post-process on given maps does not.  Same checks as yfv2_detect_frames_u8 and yfv2_deploy_post.  Enqueue only (the first call
+ * allocates the resize buffer and the maps for max_batch images and waits for the device once). */
+YFV2_API int yfv2_detect_deploy_frames_u8(yfv2_handle h, const yfv2_frame* frames, int32_t B, float thresh, float nms_thresh,
+                                          yfv2_target_box* boxes, int32_t* count, int32_t max_out, void* stream);
 
 /* replaces: utils/utils.py:194-230 get_batch_statistics (with bbox_iou :76-108), the per-detection loop of
  * evaluation() (:361-395).  dets/count: the padded output of yfv2_nms / yfv2_detect; targets: (T,6) fp32 device rows

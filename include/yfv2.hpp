@@ -1,15 +1,21 @@
 /* yfv2.hpp - C++ host class over the C ABI of libyfv2.so (include/yfv2.h): no Python, no torch.
  *
- * Counterpart of the reference's only native component, the ncnn sample class
- * `yoloFastestv2` (sample/ncnn/src/yolo-fastestv2.cpp:185-221: loadModel(param, bin) /
- * detection(srcImg, dstBoxes, thresh)), SURVEY.md section 8(f) row 4: same call shape, same TargetBox
- * record, but the arithmetic is the Python path's (utils/utils.py handel_preds + non_max_suppression at
- * conf/IoU thresholds 0.3/0.4, test.py:48-49) because that is what libyfv2 implements and pins - the ncnn
- * sample's own integer NMS (IoU 0.25, explicit class compare) is a different algorithm.
+ * Counterpart of the reference's only native component, the ncnn sample class `yoloFastestv2`
+ * (sample/ncnn/src/yolo-fastestv2.cpp:185-221: loadModel(param, bin) / detection(srcImg, dstBoxes, thresh)), SURVEY.md section
+ * 8(f) row 4: same call shape, same TargetBox record.  The reference has TWO post-processes that give different detection
+ * sets, and the class offers both - pick the one whose results you are comparing against:
  *
- * detection() = one upload of the source frame as it is (uint8 HWC) -> yfv2_resize_u8 (cv2.resize INTER_LINEAR's 8-bit
- * arithmetic on the device, skipped when the frame already has the network size) -> yfv2_detect_u8 -> one download of
- * the padded rows -> boxes scaled back to the source image.
+ *   detectionNcnn()  the ncnn SAMPLE's own arithmetic (yolo-fastestv2.cpp:58-183 predHandle + nmsHandle; yfv2.h
+ *                    yfv2_detect_deploy_frames_u8): score = cls * obj > thresh with no objectness pre-filter, boxes scaled to the
+ *                    source frame and truncated to int BEFORE the NMS, intersection_area's overlap on the integer boxes, explicit
+ *                    class compare, IoU threshold 0.25, no limit on the number of boxes.  What a user of the sample expects.
+ *   detection()      the PYTHON path's arithmetic (utils/utils.py handel_preds + non_max_suppression at conf / IoU thresholds
+ *                    0.3 / 0.4, test.py:48-49; yfv2.h yfv2_detect_u8): objectness pre-filter, fp32 boxes in network pixels with the
+ *                    class-offset trick, torchvision IoU, at most 300 boxes, truncated to int only for the TargetBox record.
+ *
+ * Both = one upload of the source frame as it is (uint8 HWC) -> the library's resize (cv2.resize INTER_LINEAR's 8-bit arithmetic on
+ * the device - not ncnn's from_pixels_resize; skipped by detection() when the frame already has the network size) -> the network ->
+ * the post-process -> one download of the records.
  *
  * Weights come from a flat container written by `yolo_fastestv2_amd.export_weights(state_dict, path)`:
  *   "YFV2W1\0\0" | int32 n | n x { int32 name_len | name bytes | int64 numel | numel x float32 }.
@@ -58,6 +64,7 @@ class Detector {
     if (d_dets_) (void)hipFree(d_dets_);
     if (d_idx_) (void)hipFree(d_idx_);
     if (d_cnt_) (void)hipFree(d_cnt_);
+    if (d_box_) (void)hipFree(d_box_);
     if (stream_) (void)hipStreamDestroy(stream_);
     if (h_) yfv2_destroy(h_);
   }
@@ -145,6 +152,40 @@ class Detector {
     return YFV2_OK;
   }
 
+  /* yoloFastestv2::detection(srcImg, dstBoxes, thresh) with the SAMPLE's own post-process (yolo-fastestv2.cpp:185-221; yfv2.h
+     yfv2_detect_deploy_frames_u8): bgr = rows x cols x 3 uint8.  dst = every survivor, score descending (equal scores: row order) */
+  int detectionNcnn(const unsigned char* bgr, int cols, int rows, std::vector<TargetBox>& dst, float thresh = 0.3f, float nmsThresh = 0.25f) {
+    dst.clear();
+    if (!ok()) return rc_;
+    if (!bgr || cols <= 0 || rows <= 0) return fail(YFV2_ERR_ARG, "detectionNcnn: bad image");
+    const int max_out = yfv2_num_rows(h_);
+    if (!d_box_ && hipMalloc(&d_box_, (size_t)max_out * sizeof(yfv2_target_box)) != hipSuccess) return fail(YFV2_ERR_DEVICE, "hipMalloc for the boxes failed");
+    const size_t src_bytes = (size_t)cols * rows * 3;
+    if (src_bytes > src_cap_) {
+      if (d_src_) (void)hipFree(d_src_);
+      d_src_ = nullptr; src_cap_ = 0;
+      if (hipMalloc(&d_src_, src_bytes) != hipSuccess) return fail(YFV2_ERR_DEVICE, "hipMalloc for the source frame failed");
+      src_cap_ = src_bytes;
+    }
+    if (hipMemcpyAsync(d_src_, bgr, src_bytes, hipMemcpyHostToDevice, stream_) != hipSuccess) return fail(YFV2_ERR_DEVICE, "upload failed");
+    const yfv2_frame fr{static_cast<const uint8_t*>(d_src_), rows, cols, 3ll * cols};
+    const int rc = yfv2_detect_deploy_frames_u8(h_, &fr, 1, thresh, nmsThresh, static_cast<yfv2_target_box*>(d_box_), static_cast<int32_t*>(d_cnt_),
+                                                max_out, stream_);
+    if (rc != YFV2_OK) return fail(rc, yfv2_last_error(h_));
+    int32_t cnt = 0;
+    if (hipMemcpyAsync(&cnt, d_cnt_, sizeof(cnt), hipMemcpyDeviceToHost, stream_) != hipSuccess || hipStreamSynchronize(stream_) != hipSuccess)
+      return fail(YFV2_ERR_DEVICE, "download failed");
+    int32_t tripped = 0;                             /* the range guard of the default plan, as in detection() */
+    const int gr = yfv2_nonfinite(h_, &tripped, stream_);
+    if (gr != YFV2_OK) return fail(gr, yfv2_last_error(h_));
+    if (tripped) return fail(YFV2_ERR_RANGE, "detectionNcnn: an activation left the range of the default (fp16x3) plan; the result is invalid (see detection())");
+    static_assert(sizeof(TargetBox) == sizeof(yfv2_target_box), "TargetBox is filled straight from the records");
+    dst.resize((size_t)(cnt < 0 ? 0 : (cnt > max_out ? max_out : cnt)));
+    if (!dst.empty() && hipMemcpy(dst.data(), d_box_, dst.size() * sizeof(TargetBox), hipMemcpyDeviceToHost) != hipSuccess)
+      return fail(YFV2_ERR_DEVICE, "download failed");
+    return YFV2_OK;
+  }
+
   /* utils.py:136-192 ap_per_class over HOST arrays (yfv2.h yfv2_ap_per_class: equal confidences rank by input index): one upload,
      the device call, `out` filled on return.  Needs no weights.  out.bad_input = 1: a target class outside 0..254 or a conf that is not finite. */
   int apPerClass(const int32_t* tp, const float* conf, const float* pred_cls, int64_t n, const float* target_cls, int64_t t, yfv2_ap_result& out) {
@@ -196,6 +237,7 @@ class Detector {
   hipStream_t stream_ = nullptr;
   void* d_src_ = nullptr;
   size_t src_cap_ = 0;
+  void* d_box_ = nullptr;   /* detectionNcnn: yfv2_num_rows records */
 };
 
 }  // namespace yfv2

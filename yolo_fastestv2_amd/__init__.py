@@ -27,6 +27,7 @@ from .weights import export_weights, random_state_dict  # noqa: F401
 from .pipeline import DetectPipeline  # noqa: F401
 from . import genanchors  # noqa: F401
 from . import tiling  # noqa: F401
+from . import ncnn_sample  # noqa: F401
 from .tiling import plan_tiles  # noqa: F401
 from .sharded import average_gradients_, detect_sharded, gather_decoded, gather_detections, shard_range  # noqa: F401
 

@@ -143,6 +143,12 @@ _PROTOTYPES = {
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "yfv2_detect_tiled_u8": (C.c_int, [C.c_void_p, C.POINTER(Frame), C.c_int32, C.POINTER(Tile), C.c_int32, C.c_float, C.c_double, C.c_double,
                                        C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "yfv2_export_maps": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "yfv2_deploy_post": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
+                                   C.c_int32, C.c_void_p]),
+    "yfv2_deploy_dropped": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),
+    "yfv2_detect_deploy_frames_u8": (C.c_int, [C.c_void_p, C.POINTER(Frame), C.c_int32, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
+                                               C.c_int32, C.c_void_p]),
     "yfv2_anchor_kmeans": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                      C.POINTER(KmeansInfo), C.c_void_p]),
     "yfv2_debug_kmeans_group": (C.c_int, [C.c_void_p, C.c_int32]),

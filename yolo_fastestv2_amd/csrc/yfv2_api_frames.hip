@@ -239,4 +239,117 @@ int yfv2_detect_tiled_u8(yfv2_handle h, const yfv2_frame* frames, int32_t F, con
   return enqueue_merge(h, t_dets, t_count, table, T, F, merge_thres, merge_metric, max_out, dets, src, count, static_cast<hipStream_t>(stream));
 }
 
+// ---- the ncnn sample's path (kernels: yfv2_deploy.hip) ----------------------------------------------------
+
+// floats of export map `sc` per image
+static size_t map_elems(const yfv2_ctx* h, int sc) { return (size_t)h->fh[sc] * h->fw[sc] * (size_t)(15 + h->cfg.classes); }
+
+static int export_impl(yfv2_handle h, const float* const out6[6], int32_t B, float* map0, float* map1, hipStream_t s) {
+  ExportMapsArgs a{};
+  for (int sc = 0; sc < 2; ++sc) {
+    a.reg[sc] = out6[sc * 3 + 0]; a.obj[sc] = out6[sc * 3 + 1]; a.cls[sc] = out6[sc * 3 + 2];
+    a.fh[sc] = h->fh[sc]; a.fw[sc] = h->fw[sc];
+  }
+  a.map[0] = map0; a.map[1] = map1; a.B = B; a.classes = h->cfg.classes;
+  yfv2_launch_export_maps(a, s);
+  HIP_TRY(h, hipGetLastError());
+  return YFV2_OK;
+}
+
+int yfv2_export_maps(yfv2_handle h, const float* const out6[6], int32_t B, float* map0, float* map1, void* stream) {
+  if (int rc = check_call(h, B, false)) return rc;
+  if (!out6 || !map0 || !map1) return fail(h, YFV2_ERR_ARG, "yfv2_export_maps: null pointer");
+  for (int i = 0; i < 6; ++i)
+    if (!out6[i]) return fail(h, YFV2_ERR_ARG, "yfv2_export_maps: null logit tensor");
+  if (((reinterpret_cast<uintptr_t>(map0) | reinterpret_cast<uintptr_t>(map1)) & 3) != 0)
+    return fail(h, YFV2_ERR_ARG, "yfv2_export_maps: the maps must be 4-byte aligned");
+  DeviceGuard guard(h->device);
+  return export_impl(h, out6, B, map0, map1, static_cast<hipStream_t>(stream));
+}
+
+// what both post entry points check of their own arguments, before anything is enqueued
+static int check_deploy(yfv2_handle h, const char* what, float thresh, const void* boxes, const void* count, int32_t max_out) {
+  const std::string w_ = what;
+  if (!boxes || !count) return fail(h, YFV2_ERR_ARG, w_ + ": null pointer");
+  if (!(thresh >= 0.0f)) return fail(h, YFV2_ERR_ARG, w_ + ": thresh must be a number >= 0");
+  if (max_out < 1 || max_out > h->rows) return fail(h, YFV2_ERR_ARG, w_ + ": max_out must be in 1.." + std::to_string(h->rows));
+  return YFV2_OK;
+}
+
+// zeroes the call's `dropped` word and enqueues the post launch; everything was checked
+static int post_deploy(yfv2_handle h, const float* map0, const float* map1, int32_t B, const float* scale, float thresh, float nms_thresh,
+                       yfv2_target_box* boxes, int32_t* count, int32_t max_out, hipStream_t s) {
+  DeployPostArgs a{};
+  a.map[0] = map0; a.map[1] = map1; a.scale = scale; a.B = B; a.classes = h->cfg.classes;
+  for (int sc = 0; sc < 2; ++sc) {
+    a.fh[sc] = h->fh[sc]; a.fw[sc] = h->fw[sc];
+    a.stride[sc] = h->cfg.height / h->fh[sc];                              // yolo-fastestv2.cpp:146, integer
+  }
+  for (int i = 0; i < 12; ++i) a.anchors[i] = (float)h->cfg.anchors[i];   // :34-37 std::vector<float>
+  a.rows = h->rows; a.thresh = thresh; a.nms_thresh = nms_thresh;
+  a.boxes = reinterpret_cast<int32_t*>(boxes); a.count = count; a.max_out = max_out;
+  a.dropped = h->deploy_word.as<int32_t>();
+  HIP_TRY(h, hipMemsetAsync(a.dropped, 0, sizeof(int32_t), s));
+  yfv2_launch_deploy_post(a, s);
+  HIP_TRY(h, hipGetLastError());
+  return YFV2_OK;
+}
+
+static int reserve_deploy_word(yfv2_handle h) { return h->deploy_word.reserve(h, 16 + sizeof(float) * 2 * (size_t)h->cfg.max_batch, true); }
+
+int yfv2_deploy_post(yfv2_handle h, const float* map0, const float* map1, int32_t B, const float* scale, float thresh, float nms_thresh,
+                     yfv2_target_box* boxes, int32_t* count, int32_t max_out, void* stream) {
+  if (int rc = check_call(h, B, false)) return rc;
+  if (!map0 || !map1) return fail(h, YFV2_ERR_ARG, "yfv2_deploy_post: null pointer");
+  if (int rc = check_deploy(h, "yfv2_deploy_post", thresh, boxes, count, max_out)) return rc;
+  DeviceGuard guard(h->device);
+  if (int rc = reserve_deploy_word(h)) return rc;
+  return post_deploy(h, map0, map1, B, scale, thresh, nms_thresh, boxes, count, max_out, static_cast<hipStream_t>(stream));
+}
+
+int yfv2_deploy_dropped(yfv2_handle h, int32_t* dropped, void* stream) {
+  if (!h) return fail(nullptr, YFV2_ERR_ARG, "null handle");
+  if (!dropped) return fail(h, YFV2_ERR_ARG, "yfv2_deploy_dropped: null pointer");
+  *dropped = 0;
+  if (!h->deploy_word.p) return YFV2_OK;      // no post call has run on this handle
+  DeviceGuard guard(h->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  HIP_TRY(h, hipMemcpyAsync(dropped, h->deploy_word.p, sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  HIP_TRY(h, hipStreamSynchronize(s));
+  return YFV2_OK;
+}
+
+int yfv2_detect_deploy_frames_u8(yfv2_handle h, const yfv2_frame* frames, int32_t B, float thresh, float nms_thresh, yfv2_target_box* boxes,
+                                 int32_t* count, int32_t max_out, void* stream) {
+  int rc = check_call(h, B, true);
+  if (rc) return rc;
+  if ((rc = check_deploy(h, "yfv2_detect_deploy_frames_u8", thresh, boxes, count, max_out))) return rc;
+  std::vector<ResizeFrame> t;
+  int max_w = 0;
+  if ((rc = check_frames(h, "yfv2_detect_deploy_frames_u8", frames, B, t, &max_w))) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DeviceGuard guard(h->device);
+  const size_t mb = (size_t)h->cfg.max_batch;
+  if ((rc = h->frames_u8.reserve(h, (size_t)h->cfg.height * h->cfg.width * 3 * mb, true))) return rc;   // the resized batch
+  if ((rc = h->deploy_maps.reserve(h, sizeof(float) * mb * (map_elems(h, 0) + map_elems(h, 1)), true))) return rc;
+  if ((rc = reserve_deploy_word(h))) return rc;
+  std::vector<float> sc((size_t)2 * B);
+  for (int32_t b = 0; b < B; ++b) {                                       // yolo-fastestv2.cpp:189-190, float / float
+    sc[(size_t)2 * b] = (float)frames[b].width / (float)h->cfg.width;
+    sc[(size_t)2 * b + 1] = (float)frames[b].height / (float)h->cfg.height;
+  }
+  float* d_scale = reinterpret_cast<float*>(h->deploy_word.as<char>() + 16);
+  HIP_TRY(h, hipMemcpyAsync(h->d_frames, t.data(), sizeof(ResizeFrame) * (size_t)B, hipMemcpyHostToDevice, s));
+  HIP_TRY(h, hipMemcpyAsync(d_scale, sc.data(), sizeof(float) * sc.size(), hipMemcpyHostToDevice, s));
+  yfv2_launch_resize_frames(h->d_frames, B, max_w, h->frames_u8.as<uint8_t>(), h->cfg.height, h->cfg.width, s);
+  HIP_TRY(h, hipGetLastError());
+  float* out6[6];
+  for (int i = 0; i < 6; ++i) out6[i] = h->ws.logits[i].p;
+  if ((rc = yfv2_forward_u8(h, h->frames_u8.as<uint8_t>(), B, out6, stream))) return rc;   // (on the handle's lanes where the plan has them)
+  float* map0 = h->deploy_maps.as<float>();
+  float* map1 = map0 + mb * map_elems(h, 0);
+  if ((rc = export_impl(h, out6, B, map0, map1, s))) return rc;
+  return post_deploy(h, map0, map1, B, d_scale, thresh, nms_thresh, boxes, count, max_out, s);
+}
+
 }  // extern "C"

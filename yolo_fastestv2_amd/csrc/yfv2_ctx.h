@@ -124,6 +124,11 @@ struct yfv2_ctx {
   DeviceBlock tile_ws;
   int tile_cap_t = 0, tile_cap_f = 0;
   DeviceBlock tile_out;
+  // the ncnn sample's path (yfv2_deploy_post / yfv2_detect_deploy_frames_u8).  deploy_word: int32 `dropped` of the last call, then
+  // max_batch (scaleW, scaleH) float pairs; deploy_maps: yfv2_detect_deploy_frames_u8's two export maps for max_batch images.  Both
+  // are allocated by the first call that needs them (one device wait).
+  DeviceBlock deploy_word;
+  DeviceBlock deploy_maps;
   // the sticky range-guard word of the fp16x3 plan (yfv2_nonfinite): ONE int32.  The kernels store 1 into it (the rare path); the
   // host reads it after waiting for a stream (yfv2_nonfinite: exact) or without waiting (yfv2_nonfinite_peek: what has landed so far).
   MappedWord nonfinite;

@@ -314,6 +314,48 @@ struct TowerArgs {
   int* nonfinite;      // range-guard word (Yfv2Watch), or null
 };
 
+// ---- the device sigmoid and class softmax of the post-process (decode_kernel, yfv2_post.hip; export_maps_kernel, yfv2_deploy.hip).
+// ONE definition: the two kernels must agree bit for bit.  Units that use them are built with -ffp-contract=off.
+#ifdef __HIPCC__
+// fp32 sigmoid as ATen's CPU kernel evaluates it: 1 / (1 + exp(-x)), true division
+__device__ __forceinline__ float sigmoid_f32(float x) { return __fdiv_rn(1.0f, __fadd_rn(1.0f, expf(-x))); }
+// fp32 softmax over the `nc` class logits cls[c * hw + cc] of one grid cell, shared by 4 CONSECUTIVE, CONVERGED lanes: lane
+// `part` (0..3) owns classes [part * per, min(nc, (part + 1) * per)), per = ceil(nc / 4), and gets their probabilities
+// exp(x - max) / sum in ev[0 .. per) (slots beyond its slice: 0).  The sum is added slice by slice in class order, then
+// (s0 + s1) + (s2 + s3) by two xor exchanges: the summation tree is part of the result.  The lane's logits are fetched with
+// one batch of independent loads (fixed trip count, masked) instead of a load per loop turn.
+template <int MAXPER>
+__device__ __forceinline__ void yfv2_softmax_quad(const float* cls, int nc, int hw, int cc, int part, float (&ev)[MAXPER]) {
+  const int per = (nc + 3) >> 2;
+  const int c_lo = part * per, c_hi = min(nc, c_lo + per);
+  float lv[MAXPER];
+#pragma unroll
+  for (int i = 0; i < MAXPER; ++i) {
+    const int c = c_lo + i;
+    lv[i] = cls[(unsigned)((c < c_hi ? c : (c_lo < nc ? c_lo : 0)) * hw + cc)];   // masked slots re-read a valid class (fewer than 4 classes: quarters 1-3 are empty)
+  }
+  float m = -INFINITY;
+#pragma unroll
+  for (int i = 0; i < MAXPER; ++i)
+    if (c_lo + i < c_hi) m = fmaxf(m, lv[i]);
+  m = fmaxf(m, __shfl_xor(m, 1));
+  m = fmaxf(m, __shfl_xor(m, 2));
+  float sum = 0.f;
+#pragma unroll
+  for (int i = 0; i < MAXPER; ++i) {
+    ev[i] = 0.f;
+    if (c_lo + i < c_hi) {
+      ev[i] = expf(__fsub_rn(lv[i], m));
+      sum = __fadd_rn(sum, ev[i]);
+    }
+  }
+  sum = __fadd_rn(sum, __shfl_xor(sum, 1));
+  sum = __fadd_rn(sum, __shfl_xor(sum, 2));
+#pragma unroll
+  for (int i = 0; i < MAXPER; ++i) ev[i] = __fdiv_rn(ev[i], sum);  // class probabilities of this lane's slice
+}
+#endif
+
 // ---- decode (handel_preds) and NMS
 struct DecodeArgs {
   const float* reg[2];
@@ -447,6 +489,29 @@ struct TileMergeArgs {
   int32_t* count;              // (F)
 };
 void yfv2_launch_tile_merge(const TileMergeArgs& a, hipStream_t s);   // two launches: rank + scatter, then one workgroup per frame
+// ---- the ncnn sample's deployment path (yfv2_deploy.hip; sample/ncnn/src/yolo-fastestv2.cpp)
+struct ExportMapsArgs {
+  const float* reg[2]; const float* obj[2]; const float* cls[2];   // the six NCHW logit maps
+  float* map[2];               // (B, fh, fw, 15 + classes) NHWC: sigmoid(12 reg) | sigmoid(3 obj) | softmax(classes)
+  int B, classes;
+  int fh[2], fw[2];
+};
+void yfv2_launch_export_maps(const ExportMapsArgs& a, hipStream_t s);
+struct DeployPostArgs {
+  const float* map[2];         // the two maps of ExportMapsArgs (any producer)
+  const float* scale;          // device (B, 2) fp32 scaleW, scaleH, or null = 1, 1
+  int B, classes;
+  int fh[2], fw[2];
+  int stride[2];               // inputHeight / outH, integer (yolo-fastestv2.cpp:146)
+  float anchors[12];           // the handle's anchors as the sample's std::vector<float> holds them
+  int rows;                    // 3 * (fh0 fw0 + fh1 fw1) <= 4096
+  float thresh, nms_thresh;
+  int32_t* boxes;              // (B, max_out) records of 6 words: x1, y1, x2, y2, cate, score bits (yfv2_target_box)
+  int32_t* count;              // (B): all survivors, also beyond max_out
+  int max_out;                 // 1 .. rows
+  int32_t* dropped;            // one device word, zeroed before the launch: candidates whose box is not representable
+};
+void yfv2_launch_deploy_post(const DeployPostArgs& a, hipStream_t s);
 // ---- anchor k-means (yfv2_anchors.hip; genanchors.py:67-102): one pass = assign + partial sums, then finalise
 constexpr int YFV2_KM_CH = 1024;    // points per chunk: part of the RESULT's definition (the summation tree), never tuned per device
 constexpr int YFV2_KM_MAXK = 32;

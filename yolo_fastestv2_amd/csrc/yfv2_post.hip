@@ -6,8 +6,8 @@
 // torchvision.ops.nms (called at :286).
 #include "yfv2_internal.h"
 
-// fp32 sigmoid as ATen's CPU kernel evaluates it: 1 / (1 + exp(-x)), true division
-__device__ __forceinline__ float sigmoid_f32(float x) { return __fdiv_rn(1.0f, __fadd_rn(1.0f, expf(-x))); }
+// (sigmoid_f32 and the class softmax of decode_kernel, yfv2_softmax_quad, live in yfv2_internal.h: yfv2_deploy.hip's export_maps_kernel
+// must produce the same bits)
 
 // Lane exchanges that move bits only (no arithmetic), for a wave whose lanes are all active.  Within a group of four
 // lanes: DPP quad_perm.  Across a wave: xor_lane64 below.
@@ -187,37 +187,12 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_kernel(DecodeArgs a, int b
   const bool ok = lc < ncell;
   const int cc = ok ? cell : cell0;  // clamp so that shuffles stay convergent
 
-  // ---- class softmax (fp32): exp(x - max) / sum.  The lane's logits are fetched with one
-  // batch of independent loads (fixed trip count, masked) instead of a load per loop turn.
+  // ---- class softmax (fp32): exp(x - max) / sum (yfv2_internal.h: the one definition export_maps_kernel shares)
   const int per = (nc + 3) >> 2;
   const int c_lo = part * per, c_hi = min(nc, c_lo + per);
   const float* cls = a.cls[sc] + (size_t)b * nc * hw;   // wave-uniform base: the per-lane part stays a 32-bit offset (24 addresses live)
-  float lv[MAXPER];
-#pragma unroll
-  for (int i = 0; i < MAXPER; ++i) {
-    const int c = c_lo + i;
-    lv[i] = cls[(unsigned)((c < c_hi ? c : (c_lo < nc ? c_lo : 0)) * hw + cc)];   // masked slots re-read a valid class (fewer than 4 classes: quarters 1-3 are empty)
-  }
-  float m = -INFINITY;
-#pragma unroll
-  for (int i = 0; i < MAXPER; ++i)
-    if (c_lo + i < c_hi) m = fmaxf(m, lv[i]);
-  m = fmaxf(m, __shfl_xor(m, 1));
-  m = fmaxf(m, __shfl_xor(m, 2));
-  float sum = 0.f;
   float ev[MAXPER];
-#pragma unroll
-  for (int i = 0; i < MAXPER; ++i) {
-    ev[i] = 0.f;
-    if (c_lo + i < c_hi) {
-      ev[i] = expf(__fsub_rn(lv[i], m));
-      sum = __fadd_rn(sum, ev[i]);
-    }
-  }
-  sum = __fadd_rn(sum, __shfl_xor(sum, 1));
-  sum = __fadd_rn(sum, __shfl_xor(sum, 2));
-#pragma unroll
-  for (int i = 0; i < MAXPER; ++i) ev[i] = __fdiv_rn(ev[i], sum);  // class probabilities of this lane's slice
+  yfv2_softmax_quad<MAXPER>(cls, nc, hw, cc, part, ev);
 
   // ---- box + objectness of anchor `an` at this cell (App. B steps 2-4)
   auto box_of = [&](int an, float (&o)[5]) {

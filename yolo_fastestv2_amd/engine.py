@@ -364,6 +364,93 @@ class Engine:
                                                    _ptr(dets), _ptr(src) if src is not None else None, _ptr(cnt), _stream(self.device)), self._h)
         return dets, src, cnt
 
+    # ---- the ncnn sample's deployment path (include/yfv2.h yfv2_export_maps / yfv2_deploy_post) ------------------
+    def map_shapes(self, B):
+        C5 = 5 * self.anchor_num + self.classes
+        return [(B, self.height // 16, self.width // 16, C5), (B, self.height // 32, self.width // 32, C5)]
+
+    def export_maps(self, preds, out=None):
+        """The six NCHW logit maps of forward() -> the two NHWC maps of Detector(export_onnx=True) (model/detector.py:33-44):
+        (B, H/16, W/16, 15 + classes) and (B, H/32, W/32, 15 + classes), sigmoid(reg) | sigmoid(obj) | softmax(classes), in one launch.
+        The obj and class channels are bit-identical to decode()'s columns 4 and 5.. .  Enqueue only."""
+        preds = [p.contiguous() for p in preds]
+        B = preds[0].shape[0]
+        for p, s in zip(preds, self.logit_shapes(B)):
+            if tuple(p.shape) != s or p.dtype != torch.float32 or p.device != self.device:
+                raise ValueError("logit tensor %s %s on %s, expected fp32 %s on %s" % (p.dtype, tuple(p.shape), p.device, s, self.device))
+        self.ensure_batch(B)
+        if out is None:
+            out = [torch.empty(s, device=self.device, dtype=torch.float32) for s in self.map_shapes(B)]
+        for m, s in zip(out, self.map_shapes(B)):
+            if tuple(m.shape) != s or m.dtype != torch.float32 or m.device != self.device or not m.is_contiguous():
+                raise ValueError("out must be two contiguous fp32 tensors %s on %s" % (self.map_shapes(B), self.device))
+        ptrs = (C.c_void_p * 6)(*[t.data_ptr() for t in preds])
+        check(_lib.lib().yfv2_export_maps(self._h, ptrs, B, _ptr(out[0]), _ptr(out[1]), _stream(self.device)), self._h)
+        return tuple(out)
+
+    def new_deploy_buffers(self, B, max_out=None):
+        """(boxes (B, max_out, 6) int32, count (B) int32) for deploy_post / detect_deploy_frames.  A record is yfv2_target_box: x1, y1,
+        x2, y2, cate as int32 and the fp32 score's bits in column 5 (boxes[..., 5].view(torch.float32))."""
+        max_out = self.rows if max_out is None else int(max_out)
+        return (torch.empty((B, max_out, 6), device=self.device, dtype=torch.int32), torch.empty((B,), device=self.device, dtype=torch.int32))
+
+    def _deploy_out(self, out, B, max_out):
+        max_out = self.rows if max_out is None else int(max_out)
+        if not 1 <= max_out <= self.rows:
+            raise ValueError("max_out must be in 1..%d, got %d" % (self.rows, max_out))
+        if out is None:
+            return self.new_deploy_buffers(B, max_out) + (max_out,)
+        boxes, cnt = out
+        for t, shape in ((boxes, (B, max_out, 6)), (cnt, (B,))):
+            if not torch.is_tensor(t) or tuple(t.shape) != shape or t.dtype != torch.int32 or t.device != self.device or not t.is_contiguous():
+                raise ValueError("out must be contiguous int32 (boxes %s, count %s) on %s" % ((B, max_out, 6), (B,), self.device))
+        return boxes, cnt, max_out
+
+    def deploy_post(self, map0, map1, thresh=0.3, nms_thresh=0.25, scale=None, max_out=None, out=None):
+        """The ncnn sample's predHandle + nmsHandle (sample/ncnn/src/yolo-fastestv2.cpp:58-183) on two export maps, for the whole
+        batch in one launch: score = cls * obj > thresh, boxes scaled by `scale` ((B, 2) fp32 scaleW, scaleH on the device; None = 1)
+        and truncated to int, greedy NMS on the integer boxes per class, no limit of 300; equal scores rank by row order.  Returns
+        (boxes (B, max_out, 6) int32, count (B)): count is the full number of survivors, records beyond min(count, max_out) are
+        zero.  Uses the engine's anchors (rounded to fp32, as the sample holds them).  Enqueue only; dropped() afterwards."""
+        self._need_anchors("deploy_post")
+        B = int(map0.shape[0])
+        for m, s in zip((map0, map1), self.map_shapes(B)):
+            if not torch.is_tensor(m) or tuple(m.shape) != s or m.dtype != torch.float32 or m.device != self.device:
+                raise ValueError("maps must be fp32 %s on %s" % (self.map_shapes(B), self.device))
+        map0, map1 = map0.contiguous(), map1.contiguous()
+        if scale is not None:
+            if not torch.is_tensor(scale) or tuple(scale.shape) != (B, 2) or scale.dtype != torch.float32 or scale.device != self.device:
+                raise ValueError("scale must be an fp32 (%d, 2) tensor on %s" % (B, self.device))
+            scale = scale.contiguous()
+        self.ensure_batch(B)
+        boxes, cnt, max_out = self._deploy_out(out, B, max_out)
+        check(_lib.lib().yfv2_deploy_post(self._h, _ptr(map0), _ptr(map1), B, _ptr(scale) if scale is not None else None, float(thresh),
+                                          float(nms_thresh), _ptr(boxes), _ptr(cnt), max_out, _stream(self.device)), self._h)
+        return boxes, cnt
+
+    def deploy_dropped(self):
+        """Waits for the stream; the number of candidates the LAST deploy_post / detect_deploy_frames dropped because their box is
+        not representable as int32 (non-finite reg values: the sample's (int) is undefined there).  0 for sane maps."""
+        n = C.c_int32(0)
+        check(_lib.lib().yfv2_deploy_dropped(self._h, C.byref(n), _stream(self.device)), self._h)
+        return int(n.value)
+
+    def detect_deploy_frames(self, frames, thresh=0.3, nms_thresh=0.25, max_out=None, out=None, check=True):
+        """The ncnn sample's detection() (yolo-fastestv2.cpp:185-221) for a list of uint8 (h_i, w_i, 3) device frames of any sizes:
+        resize_frames -> forward -> export_maps -> deploy_post with scaleW = fp32(w_i) / fp32(width), scaleH likewise, in one call and
+        bit-identical to those four.  The resize is cv2's bilinear arithmetic, not ncnn's from_pixels_resize.  Returns (boxes, count)
+        like deploy_post.  Enqueue only (the first call on a handle allocates its workspaces and waits once); check= as in detect()."""
+        self._need_anchors("detect_deploy_frames")
+        if check and self.peek_nonfinite():
+            self.check_finite("detect_deploy_frames (an earlier call on this handle)")
+        arr, keep = self._frame_table(frames)
+        B = len(keep)
+        self.ensure_batch(B)
+        boxes, cnt, max_out = self._deploy_out(out, B, max_out)
+        _lib.check(_lib.lib().yfv2_detect_deploy_frames_u8(self._h, arr, B, float(thresh), float(nms_thresh), _ptr(boxes), _ptr(cnt), max_out,
+                                                           _stream(self.device)), self._h)
+        return boxes, cnt
+
     def batch_statistics(self, dets, cnt, targets, iou_threshold, sync=True):
         """True-positive flags (B, 300) int32 for the padded detections of nms()/detect() against targets (T,6)
         [image index, label, x1, y1, x2, y2] - utils/utils.py:194-230 get_batch_statistics on the device.

@@ -46,6 +46,7 @@ class DetectPipeline:
         self._last = [None] * self.depth          # serial of the ticket that owns each slot's buffers
         self._readers = [[] for _ in range(self.depth)]   # events recorded on the consumer streams result() ordered behind a slot
         self._tiled_buffers = [None] * self.depth         # (dets, src, count) of submit_tiled, per slot
+        self._deploy_buffers = [None] * self.depth        # (boxes, count) of submit_deploy_frames, per slot
 
     def load_state_dict(self, state_dict):
         for e in self.engines:
@@ -123,6 +124,38 @@ class DetectPipeline:
                 for f in frames:
                     f.record_stream(self.streams[j])
             out = eng.detect_frames(frames, conf_thres, iou_thres, out=(dets[:B], idx[:B], cnt[:B]), check=False)
+            ev = torch.cuda.Event()
+            ev.record(self.streams[j])
+        return Ticket(j, ev, out, self._serial)
+
+    def submit_deploy_frames(self, frames, thresh=0.3, nms_thresh=0.25, max_out=None, wait_for_input=True):
+        """`submit_frames` on the ncnn sample's path (Engine.detect_deploy_frames: resize, forward, export maps, the sample's integer-box
+        post-process) on the next slot.  The ticket's tensors are (boxes (B, max_out, 6) int32, count (B)), owned by the slot."""
+        B = len(frames)
+        if B > self.max_batch:
+            raise ValueError("batch %d exceeds max_batch %d" % (B, self.max_batch))
+        cur = torch.cuda.current_stream(self.device)
+        jn = self._serial % self.depth
+        if self.engines[jn].peek_nonfinite():     # as in submit(): the slot's previous batch, before the rotation advances
+            try:
+                with torch.cuda.stream(self.streams[jn]):
+                    self.engines[jn].check_finite("DetectPipeline.submit_deploy_frames: the batch of ticket #%s (slot %d), the last one run on this slot" % (self._last[jn], jn))
+            except Exception as e:
+                e.slot, e.serial = jn, self._last[jn]
+                raise
+        with self.slot() as (j, eng, _):
+            for ev in self._readers[j]:
+                self.streams[j].wait_event(ev)
+            self._readers[j] = []
+            if wait_for_input:
+                self.streams[j].wait_stream(cur)
+                for f in frames:
+                    f.record_stream(self.streams[j])
+            max_out = eng.rows if max_out is None else int(max_out)
+            if self._deploy_buffers[j] is None or self._deploy_buffers[j][0].shape[1] != max_out:
+                self._deploy_buffers[j] = eng.new_deploy_buffers(self.max_batch, max_out)
+            boxes, cnt = self._deploy_buffers[j]
+            out = eng.detect_deploy_frames(frames, thresh, nms_thresh, max_out=max_out, out=(boxes[:B], cnt[:B]), check=False)
             ev = torch.cuda.Event()
             ev.record(self.streams[j])
         return Ticket(j, ev, out, self._serial)
