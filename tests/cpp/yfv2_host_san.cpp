@@ -46,6 +46,11 @@ struct StateDict {
   }
 };
 
+// towerp_kernel's lane -> patch table and the maps that take it.  Declared by hand because yfv2_internal.h needs the HIP headers: keep
+// the two lines in step with their declarations there (next to yfv2_towerh_supported)
+void towerp_lane_patches(int H, int W, unsigned char (&tbl)[128]);
+bool yfv2_towerp_map(int H, int W);
+
 static int dryrun(const yfv2_config& cfg, const yfv2_plan& plan, const std::vector<yfv2_tensor_desc>& descs, int32_t* steps, int64_t* blob) {
   return yfv2_debug_plan_dryrun_ex(&cfg, &plan, descs.data(), (int32_t)descs.size(), steps, blob);
 }
@@ -93,6 +98,30 @@ int main() {
     CHECK(tiles[n_tiles - 1].width == 1500 && tiles[n_tiles - 1].height == 1000, "the whole-frame tile comes last");
     CHECK(yfv2_tile_plan(1000, 1500, 352, 352, 64, 64, 1, tiles.get(), n_tiles - 1) == YFV2_ERR_ARG, "cap below the count");
   }
+
+  // towerp_kernel's lane table (the plan computes it once per tower step): on every map the kernel takes - even, up to 22x22, not both
+  // sides <= 11, at most 128 2x2 patches - every patch sits on exactly one (round, lane) and every other entry says "none"
+  int n_maps = 0;
+  for (int H = 1; H <= 24; ++H)
+    for (int W = 1; W <= 24; ++W) {
+      const int patches = ((H + 1) / 2) * ((W + 1) / 2);
+      const bool takes = !(H & 1) && !(W & 1) && H <= 22 && W <= 22 && (H > 11 || W > 11) && patches <= 128;
+      CHECK(yfv2_towerp_map(H, W) == takes, "yfv2_towerp_map(%d, %d)", H, W);
+      if (!takes) continue;
+      ++n_maps;
+      unsigned char tbl[128];
+      std::memset(tbl, 0, sizeof(tbl));
+      towerp_lane_patches(H, W, tbl);
+      int seen[128] = {}, none = 0;
+      for (int i = 0; i < 128; ++i) {
+        if (tbl[i] == 255) { ++none; continue; }
+        CHECK(tbl[i] < patches, "%dx%d: entry %d = %d of %d patches", H, W, i, tbl[i], patches);
+        ++seen[tbl[i]];
+      }
+      for (int pid = 0; pid < patches; ++pid) CHECK(seen[pid] == 1, "%dx%d: patch %d occurs %d times", H, W, pid, seen[pid]);
+      CHECK(none == 128 - patches, "%dx%d: %d empty entries", H, W, none);
+    }
+  CHECK(n_maps == 96, "%d maps", n_maps);
 
   // the null-handle path of every entry point that takes a handle: a code (or 0 / -1 where the return value is a count), no access
   const yfv2_handle h = nullptr;

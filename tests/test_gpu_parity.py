@@ -126,6 +126,25 @@ def test_forward_random_weights_odd_batches(yfv2, dev):
         _assert_logits_within_noise_floor(m(x.to(dev)), w, x, "B=%d" % B)
 
 
+def test_forward_batches_around_the_cu_count_are_bit_identical(yfv2, dev):
+    """Two launch decisions read the device's CU count: with more images than CUs a workgroup of the 6x6 towers launch has more than
+    one image and the a half -> b half tensor no longer stays in LDS (chain off), and with 2 B > CUs the 12x12 towers run as one
+    launch instead of two.  192x192 is the smallest square input with both maps (towers_kernel at 6x6, towerp_kernel at 12x12).  The
+    batches on either side of both decisions must give every image the bits it has in one batch of CUs + 1."""
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    e = yfv2.Engine(dev, 192, 192, 5, 3, max_batch=cus + 1, plan={})
+    e.load_state_dict(yfv2.random_state_dict(11, classes=5))
+    x = torch.rand(cus + 1, 3, 192, 192, generator=torch.Generator().manual_seed(192)).to(dev)
+    big = [t.cpu() for t in e.forward(x)]
+    assert len(big) == 6 and all(bool(torch.isfinite(t).all()) for t in big) and not e.nonfinite()
+    for n in (cus, cus - 1, cus // 2 + 1, cus // 2):
+        small = [t.cpu() for t in e.forward(x[:n])]
+        for k, (s, b) in zip(LOGIT_KEYS, zip(small, big)):
+            assert s.shape[0] == n and torch.equal(s.view(torch.int32), b[:n].view(torch.int32)), \
+                "%s: a batch of %d differs from the first %d images of a batch of %d (%d CUs)" % (k, n, n, cus + 1, cus)
+    e.close()
+
+
 def _quirky_state_dict(yfv2, seed):
     """What fine-tuned / pruned checkpoints of the reference look like and random_state_dict never does: BatchNorm gains that went
     to exactly zero (network slimming), running variances collapsed to ~0 (a dead input: scale = gamma / sqrt(0 + 1e-5) = 316 gamma),

@@ -495,10 +495,8 @@ bool yfv2_s1chain_supported(int c2, int H, int W) {
 bool yfv2_launch_block_s1chain(const BlockS1Args& a, hipStream_t s) {
   if (!yfv2_s1chain_supported(48, a.H, a.W) || a.nblk < 2) return false;
   const size_t lds = sizeof(float) * (size_t)s1chain_lds_floats(a.H, a.W);
-  const int blocks = a.B < 256 ? a.B : 256;
-  static std::atomic<unsigned long long> lds_ok{0};
-  yfv2_allow_full_lds(reinterpret_cast<const void*>(&block_s1chain6_kernel<512>), lds_ok);
-  YFV2_LAUNCH((block_s1chain6_kernel<512>), dim3(blocks), dim3(512), lds, s, a);
+  const Yfv2Device dev = yfv2_device();
+  YFV2_LAUNCH_LDS(dev, (block_s1chain6_kernel<512>), YFV2_LDS_FULL, dim3(yfv2_image_grid(a.B, dev)), dim3(512), lds, s, a);
   return true;
 }
 
@@ -821,15 +819,10 @@ bool yfv2_s1pool_supported(int c2, int H, int W) {
 bool yfv2_launch_block_s1pool(const BlockS1Args& a, hipStream_t s) {
   if (!yfv2_s1pool_supported(P96_C2, a.H, a.W) || a.nblk < 1) return false;
   const size_t lds = sizeof(float) * (size_t)s1pool_lds_floats(a.H, a.W, a.presplit != 0);
-  const int blocks = a.B < 256 ? a.B : 256;
-  static std::atomic<unsigned long long> lds_ok0{0}, lds_ok1{0};
-  if (a.presplit) {
-    yfv2_allow_full_lds(reinterpret_cast<const void*>(&block_s1pool_kernel<512, true>), lds_ok1);
-    YFV2_LAUNCH((block_s1pool_kernel<512, true>), dim3(blocks), dim3(512), lds, s, a);
-  } else {
-    yfv2_allow_full_lds(reinterpret_cast<const void*>(&block_s1pool_kernel<512, false>), lds_ok0);
-    YFV2_LAUNCH((block_s1pool_kernel<512, false>), dim3(blocks), dim3(512), lds, s, a);
-  }
+  const Yfv2Device dev = yfv2_device();
+  const int blocks = yfv2_image_grid(a.B, dev);
+  if (a.presplit) YFV2_LAUNCH_LDS(dev, (block_s1pool_kernel<512, true>), YFV2_LDS_FULL, dim3(blocks), dim3(512), lds, s, a);
+  else YFV2_LAUNCH_LDS(dev, (block_s1pool_kernel<512, false>), YFV2_LDS_FULL, dim3(blocks), dim3(512), lds, s, a);
   return true;
 }
 
@@ -1185,21 +1178,19 @@ static int yfv2_block_s2_rows_small(int cin, int H, int W) {
 }
 
 template <int CIN>
-static void launch_s2(const BlockS2Args& a, hipStream_t s) {
+static bool launch_s2(const BlockS2Args& a, hipStream_t s) {
   const size_t lds = s2_lds_floats<CIN>(a.R, a.W) * sizeof(float);
   const int tiles = (a.H / 2 + a.R - 1) / a.R;
-  int blocks = a.B * tiles;
-  if (blocks > 256) blocks = 256;
-  static std::atomic<unsigned long long> lds_ok0{0}, lds_ok1{0}, lds_ok2{0};
-  yfv2_allow_full_lds(reinterpret_cast<const void*>(&block_s2_kernel<CIN, 512, false>), lds_ok0);
+  const Yfv2Device dev = yfv2_device();
+  const int blocks = yfv2_image_grid(a.B * tiles, dev);
   if constexpr (CIN == 48) {   // the pair-plane input forms: stage3.0 behind the lane-per-pixel stage 2 (stage2.0 reads the stem's planes in s2px / s2h / front2)
     // (fp32 MFMA whatever the handle's arithmetic: with fp16x3 this block is s3h2_kernel's - the staged form is reached only by the
     // fp32-matrix plan and by stage-2 maps wider than 480 columns, where it is correct at any range.  Its bf16x6 variant is gone.)
-    yfv2_allow_full_lds(reinterpret_cast<const void*>(&block_s2_kernel<CIN, 512, true>), lds_ok1);
-    if (a.pp_in) { YFV2_LAUNCH((block_s2_kernel<CIN, 512, true>), dim3(blocks), dim3(512), lds, s, a); return; }
+    if (a.pp_in) { YFV2_LAUNCH_LDS(dev, (block_s2_kernel<CIN, 512, true>), YFV2_LDS_FULL, dim3(blocks), dim3(512), lds, s, a); return true; }
   }
-  if (a.pp_in) return;   // (never planned: WeightPacker sets pp_in for the 48-channel block only)
-  YFV2_LAUNCH((block_s2_kernel<CIN, 512, false>), dim3(blocks), dim3(512), lds, s, a);
+  if (a.pp_in) return false;   // (never planned: WeightPacker sets pp_in for the 48-channel block only)
+  YFV2_LAUNCH_LDS(dev, (block_s2_kernel<CIN, 512, false>), YFV2_LDS_FULL, dim3(blocks), dim3(512), lds, s, a);
+  return true;
 }
 
 // ============================================================================
@@ -1576,16 +1567,13 @@ int yfv2_block_s2_rows(int cin, int H, int W) {
 static void launch_s2w(const BlockS2Args& a, hipStream_t s) {
   const size_t lds = s2w_lds_floats(a.R, a.W) * sizeof(float);
   const int tiles = (a.H / 2 + a.R - 1) / a.R;
-  int blocks = a.B * tiles;
-  if (blocks > 256) blocks = 256;
-  static std::atomic<unsigned long long> lds_ok{0};
-  yfv2_allow_full_lds(reinterpret_cast<const void*>(&block_s2w_kernel<512>), lds_ok);
-  YFV2_LAUNCH((block_s2w_kernel<512>), dim3(blocks), dim3(512), lds, s, a);
+  const Yfv2Device dev = yfv2_device();
+  YFV2_LAUNCH_LDS(dev, (block_s2w_kernel<512>), YFV2_LDS_FULL, dim3(yfv2_image_grid(a.B * tiles, dev)), dim3(512), lds, s, a);
 }
 
 bool yfv2_launch_block_s2(int cin, const BlockS2Args& a, hipStream_t s) {
-  if (cin == 24) { launch_s2<24>(a, s); return true; }
-  if (cin == 48) { launch_s2<48>(a, s); return true; }
+  if (cin == 24) return launch_s2<24>(a, s);
+  if (cin == 48) return launch_s2<48>(a, s);
   if (cin == 96 && !a.pp_in && a.bf6) { launch_s2w(a, s); return true; }   // planned only with bf16x6 on (image_s2w)
   return false;
 }
@@ -1859,15 +1847,10 @@ template <int MH, int THREADS, int NT, int NPF>
 static void launch_tower2(const TowerArgs& a, hipStream_t s) {
   const size_t lds = sizeof(float) * ((size_t)TW_WP_FL + (size_t)MH * TW_WH_FL + 25 * TW_KC * 16 + 5 * 96 +
                                       (size_t)16 * tw2_plane_slots(a.H, a.W));
-  int blocks = a.B < 256 ? a.B : 256;
-  static std::atomic<unsigned long long> lds_ok0{0}, lds_ok1{0};
-  if (a.bf6) {
-    yfv2_allow_full_lds(reinterpret_cast<const void*>(&tower2_kernel<MH, THREADS, NT, NPF, true>), lds_ok1);
-    YFV2_LAUNCH((tower2_kernel<MH, THREADS, NT, NPF, true>), dim3(blocks), dim3(THREADS), lds, s, a);
-    return;
-  }
-  yfv2_allow_full_lds(reinterpret_cast<const void*>(&tower2_kernel<MH, THREADS, NT, NPF, false>), lds_ok0);
-  YFV2_LAUNCH((tower2_kernel<MH, THREADS, NT, NPF, false>), dim3(blocks), dim3(THREADS), lds, s, a);
+  const Yfv2Device dev = yfv2_device();
+  const int blocks = yfv2_image_grid(a.B, dev);
+  if (a.bf6) YFV2_LAUNCH_LDS(dev, (tower2_kernel<MH, THREADS, NT, NPF, true>), YFV2_LDS_FULL, dim3(blocks), dim3(THREADS), lds, s, a);
+  else YFV2_LAUNCH_LDS(dev, (tower2_kernel<MH, THREADS, NT, NPF, false>), YFV2_LDS_FULL, dim3(blocks), dim3(THREADS), lds, s, a);
 }
 
 bool yfv2_tower2_supported(int H, int W) { return H * W <= 16 * 4 * 8; }

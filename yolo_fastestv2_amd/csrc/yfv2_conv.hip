@@ -403,37 +403,29 @@ static void pw_launch(const PwArgs& a, hipStream_t s) {
   const size_t lds = (size_t)MT * 16 * K * sizeof(float);   // K/16 fragments of 256 floats + (K%16 == 8) 128 per M tile
   const int n_super = (a.P + NT * 16 - 1) / (NT * 16);
   int blocks = (n_super + THREADS / 64 - 1) / (THREADS / 64);
-  // persistent-ish grid: enough blocks to fill 256 CUs a few times over, few
-  // enough that the per-block weight staging (L2 -> LDS) stays amortised
+  // persistent-ish grid, capped by how much filter every block stages (L2 -> LDS): tuned block counts (measured on an MI355X),
+  // not multiples of a CU count
   const int cap = lds > 64 * 1024 ? 256 : (lds > 32 * 1024 ? 512 : 1024);
   if (blocks > cap) blocks = cap;
   if (blocks < 1) blocks = 1;
-  static std::atomic<unsigned long long> lds_ok0{0}, lds_ok1{0};
   // bf16x6 for the instantiations the default plans use (the streamed large-K forms and the small biased heads); the fully
   // unrolled 6-tile forms of the layer-by-layer fallback would spill with the split operands and stay on the fp32 MFMA
   constexpr bool kBf6 = STREAM || (MT * (K / 16 + 1) <= 12);
   if constexpr (FORMS == 1) {   // only the pre-split fp16x3 form (yfv2_launch_pw asks for nothing else)
-    static std::atomic<unsigned long long> lds_ok2{0};
-    yfv2_allow_full_lds(reinterpret_cast<const void*>(&pw_kernel<K, MT, NT, MODE, THREADS, STREAM, true, true>), lds_ok2);
-    YFV2_LAUNCH((pw_kernel<K, MT, NT, MODE, THREADS, STREAM, true, true>), dim3(blocks), dim3(THREADS), lds, s, a);
+    YFV2_LAUNCH_LDS(yfv2_device(), (pw_kernel<K, MT, NT, MODE, THREADS, STREAM, true, true>), YFV2_LDS_FULL, dim3(blocks), dim3(THREADS), lds, s, a);
   } else if constexpr (FORMS == 2) {
-    yfv2_allow_full_lds(reinterpret_cast<const void*>(&pw_kernel<K, MT, NT, MODE, THREADS, STREAM>), lds_ok0);
-    YFV2_LAUNCH((pw_kernel<K, MT, NT, MODE, THREADS, STREAM>), dim3(blocks), dim3(THREADS), lds, s, a);
+    YFV2_LAUNCH_LDS(yfv2_device(), (pw_kernel<K, MT, NT, MODE, THREADS, STREAM>), YFV2_LDS_FULL, dim3(blocks), dim3(THREADS), lds, s, a);
   } else {
   if constexpr (STREAM && K % 32 == 0 && K >= 192) if (a.bf6) {   // (the planner packs these filters pre-split whenever the handle runs fp16x3)
-    static std::atomic<unsigned long long> lds_ok2{0};
-    const size_t lds_pre = lds;   // two fp16 terms: the size of the fp32 image
-    yfv2_allow_full_lds(reinterpret_cast<const void*>(&pw_kernel<K, MT, NT, MODE, THREADS, STREAM, true, true>), lds_ok2);
-    YFV2_LAUNCH((pw_kernel<K, MT, NT, MODE, THREADS, STREAM, true, true>), dim3(blocks), dim3(THREADS), lds_pre, s, a);
+    // (two fp16 terms: the size of the fp32 image)
+    YFV2_LAUNCH_LDS(yfv2_device(), (pw_kernel<K, MT, NT, MODE, THREADS, STREAM, true, true>), YFV2_LDS_FULL, dim3(blocks), dim3(THREADS), lds, s, a);
     return;
   }
   if constexpr (kBf6 && !(STREAM && K % 32 == 0 && K >= 192)) if (a.bf6) {
-    yfv2_allow_full_lds(reinterpret_cast<const void*>(&pw_kernel<K, MT, NT, MODE, THREADS, STREAM, true>), lds_ok1);
-    YFV2_LAUNCH((pw_kernel<K, MT, NT, MODE, THREADS, STREAM, true>), dim3(blocks), dim3(THREADS), lds, s, a);
+    YFV2_LAUNCH_LDS(yfv2_device(), (pw_kernel<K, MT, NT, MODE, THREADS, STREAM, true>), YFV2_LDS_FULL, dim3(blocks), dim3(THREADS), lds, s, a);
     return;
   }
-  yfv2_allow_full_lds(reinterpret_cast<const void*>(&pw_kernel<K, MT, NT, MODE, THREADS, STREAM>), lds_ok0);
-  YFV2_LAUNCH((pw_kernel<K, MT, NT, MODE, THREADS, STREAM>), dim3(blocks), dim3(THREADS), lds, s, a);
+  YFV2_LAUNCH_LDS(yfv2_device(), (pw_kernel<K, MT, NT, MODE, THREADS, STREAM>), YFV2_LDS_FULL, dim3(blocks), dim3(THREADS), lds, s, a);
   }
 }
 
@@ -532,7 +524,8 @@ __global__ __launch_bounds__(256) void dw_kernel(DwArgs a) {
 bool yfv2_launch_dw(int ksize, int stride, const DwArgs& a, hipStream_t s) {
   const size_t total = (size_t)a.B * a.OH * a.OW * (a.C >> 2);
   size_t blocks = (total + 255) / 256;
-  if (blocks > 256 * 16) blocks = 256 * 16;  // grid-stride the rest
+  const size_t cap = 16 * (size_t)yfv2_device_cus();
+  if (blocks > cap) blocks = cap;  // grid-stride the rest
   if (blocks < 1) blocks = 1;
   if (ksize == 3 && stride == 1) { YFV2_LAUNCH((dw_kernel<3, 1>), dim3(blocks), dim3(256), 0, s, a); return true; }
   if (ksize == 3 && stride == 2) { YFV2_LAUNCH((dw_kernel<3, 2>), dim3(blocks), dim3(256), 0, s, a); return true; }

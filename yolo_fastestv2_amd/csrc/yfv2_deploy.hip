@@ -227,8 +227,6 @@ __global__ __launch_bounds__(DP_THREADS) void deploy_post_kernel(DeployPostArgs 
   }
 }
 
-std::atomic<unsigned long long> post_lds_ok{0};
-
 }  // namespace
 
 void yfv2_launch_export_maps(const ExportMapsArgs& a, hipStream_t s) {
@@ -246,11 +244,5 @@ void yfv2_launch_deploy_post(const DeployPostArgs& a, hipStream_t s) {
   while (cap < a.rows) cap <<= 1;
   const size_t lds = (size_t)cap * 8 + (size_t)a.rows * 24 + (((size_t)a.rows + 15) & ~(size_t)15);
   // up to 132 KB of dynamic LDS next to the two static counters: raise the function's limit to exactly the 4096-row need, once per device
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 63) dev = 0;
-  if (!(post_lds_ok.load(std::memory_order_relaxed) & (1ull << dev))) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&deploy_post_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, DP_MAX_ROWS * (8 + 24 + 1));
-    post_lds_ok.fetch_or(1ull << dev, std::memory_order_relaxed);
-  }
-  YFV2_LAUNCH(deploy_post_kernel, dim3((unsigned)a.B), dim3(DP_THREADS), lds, s, a, cap);
+  YFV2_LAUNCH_LDS(yfv2_device(), deploy_post_kernel, DP_MAX_ROWS * (8 + 24 + 1), dim3((unsigned)a.B), dim3(DP_THREADS), lds, s, a, cap);
 }

@@ -17,8 +17,6 @@ typedef unsigned int u32x3 __attribute__((ext_vector_type(3)));
 __device__ __forceinline__ int yfv2_fdiv(int n, float inv_d) { return (int)(((float)n + 0.5f) * inv_d); }
 #endif
 
-// hipFuncAttributeMaxDynamicSharedMemorySize is a per-(function, device) attribute: raise it to the 160 KiB cap the first
-// time a function is launched on each device (`done` = the call site's bit mask of devices already served).
 #include <atomic>
 
 // Every launch of the forward path goes through YFV2_LAUNCH.  Normally a plain launch; while yfv2_profile_forward runs a plan step, the
@@ -33,14 +31,37 @@ extern thread_local Yfv2LaunchProbe yfv2_launch_probe;
     hipExtLaunchKernelGGL(kernel, grid, block, lds, stream, yfv2_lp_.launches++ == 0 ? yfv2_lp_.start : nullptr, yfv2_lp_.stop, 0, \
                           __VA_ARGS__);                                                                                            \
   } while (0)
-inline void yfv2_allow_full_lds(const void* fn, std::atomic<unsigned long long>& done) {
+// ---- device facts of the launchers: the ONE place that asks which device is current and how many CUs it has.  A launcher (or the
+// plan step above it) asks ONCE per launch and hands the value to its grid and to YFV2_LAUNCH_LDS: one hipGetDevice per launch
+struct Yfv2Device { int index, cus; };   // index into 64-entry per-device caches; compute units (256, an MI355X, if the query fails)
+inline Yfv2Device yfv2_device() {
+  static std::atomic<int> cus_of[64];
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 63) dev = 0;
-  const unsigned long long bit = 1ull << dev;
+  int cus = cus_of[dev].load(std::memory_order_relaxed);
+  if (cus <= 0) { if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256; cus_of[dev].store(cus, std::memory_order_relaxed); }
+  return {dev, cus};
+}
+inline int yfv2_device_cus() { return yfv2_device().cus; }
+// grid of a persistent launch over n work items (images, mostly), one workgroup per CU at most: with n <= CUs every workgroup has
+// exactly ONE item - which launch(const TowerStep&) (yfv2_plan.hip) relies on, through this very function
+inline int yfv2_image_grid(int n, const Yfv2Device& dev) { return n < dev.cus ? n : dev.cus; }
+// hipFuncAttributeMaxDynamicSharedMemorySize is a per-(function, device) attribute: raise it to `bytes` the first time a function
+// is launched on each device (`done` = the call site's bit mask of devices already served).  YFV2_LAUNCH_LDS = that + YFV2_LAUNCH,
+// and owns the call site's word; YFV2_LDS_FULL = a CU's whole LDS, for kernels without static LDS of their own.
+constexpr int YFV2_LDS_FULL = 160 * 1024;
+inline void yfv2_allow_lds(const Yfv2Device& dev, const void* fn, int bytes, std::atomic<unsigned long long>& done) {
+  const unsigned long long bit = 1ull << dev.index;
   if (done.load(std::memory_order_relaxed) & bit) return;
-  (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+  (void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
   done.fetch_or(bit, std::memory_order_relaxed);
 }
+#define YFV2_LAUNCH_LDS(dev, kernel, limit, grid, block, lds, stream, ...)            \
+  do {                                                                                \
+    static std::atomic<unsigned long long> yfv2_lds_done_{0};                         \
+    yfv2_allow_lds(dev, reinterpret_cast<const void*>(&kernel), limit, yfv2_lds_done_); \
+    YFV2_LAUNCH(kernel, grid, block, lds, stream, __VA_ARGS__);                       \
+  } while (0)
 
 // ---- fp32 pointwise convs on the bf16 matrix cores ("bf16x6")
 // gfx950's fp32 MFMA runs at the fp32 VECTOR rate (16x16x4: 32 cycles per 1024 MACs per SIMD); its bf16 MFMA is 16x
@@ -398,15 +419,17 @@ bool yfv2_tower2_supported(int H, int W);                    // whole-image towe
 bool yfv2_launch_tower2(const TowerArgs& a, hipStream_t s);
 bool yfv2_towerh_supported(int H, int W);
 bool yfv2_towerh_multi(int H, int W);
+bool yfv2_towerp_map(int H, int W);   // a supported map whose single halves and side-by-side jobs are towerp_kernel's (even, beyond 11x11)
+void towerp_lane_patches(int H, int W, unsigned char (&tbl)[128]);   // host: TowerJobs::lane_patch of such a map, a pure function of (H, W)
 struct TowerJobs {   // up to four tower halves of one map size in ONE launch
   TowerArgs j[4];
   int n;
   int par;   // 0: a job LIST - every workgroup runs the jobs one after the other on its image (towers_kernel, maps up to 11x11);
              // 1: INDEPENDENT jobs side by side - workgroups [k gpj, (k + 1) gpj) run job k (towerh_kernel)
   int gpj;   // par: workgroups per job (set by the launcher)
-  unsigned char lane_patch[128];   // towerp_kernel: the 2x2 patch of lane l in depthwise round r at [64 r + l] (255: none); set by the launcher
+  unsigned char lane_patch[128];   // towerp_kernel: the 2x2 patch of lane l in depthwise round r at [64 r + l] (255: none); the plan's (towerp_lane_patches)
 };
-bool yfv2_launch_towerh(const TowerJobs& jobs, int mh_tiles, hipStream_t s);
+bool yfv2_launch_towerh(const TowerJobs& jobs, int mh_tiles, const Yfv2Device& dev, hipStream_t s);   // dev: the caller's yfv2_device()
 // ---- evaluation statistics (get_batch_statistics): which detections are true positives
 struct StatsArgs {
   const float* dets;     // (B, 300, 6) x1,y1,x2,y2,conf,cls rows of yfv2_nms / yfv2_detect

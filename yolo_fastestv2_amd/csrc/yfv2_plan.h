@@ -111,6 +111,8 @@ struct TowerStep {
   std::vector<TowerHalf> halves;   // 1, 2 or 4: the halves this ONE launch runs one after the other ...
   bool par = false;                // ... or (par) side by side: independent halves (cls a | reg a, cls b | reg b) as workgroup ranges
   int tiles = 0;                   // the launch's output-conv tiles
+  unsigned char lane_patch[128] = {};   // TowerJobs::lane_patch where the step is towerp_kernel's (yfv2_towerp_map), set once by PlanBuilder
+  bool has_lane_patch = false;          // ... which launch() insists on: an all-zero table would compute silently wrong logits
 };
 
 struct Step {

@@ -18,6 +18,8 @@ const TowerHalf* lone_half(const Step& s) {
   const TowerStep* t = kind_of<TowerStep>(s);
   return t && t->halves.size() == 1 ? &t->halves[0] : nullptr;
 }
+// the step is towerp_kernel's under the default arithmetic (yfv2_launch_towerh routes by the same predicate)
+bool towerp_step(const TowerStep& k) { return k.halves[0].img16 && yfv2_towerp_map(k.halves[0].args.H, k.halves[0].args.W); }
 double half_flops(const TowerHalf& t) { return 2.0 * t.args.H * t.args.W * (25.0 * 72 + 72.0 * 72 + (t.has_head ? 72.0 * t.args.mh : 0.0)); }
 double half_bytes(const TowerHalf& t) { return 4.0 * t.args.H * t.args.W * (72.0 + (t.has_head ? t.args.mh : 72.0)); }
 
@@ -640,6 +642,11 @@ struct PlanBuilder {
       }
       i += 4;
     }
+    for (Step& s : out)
+      if (TowerStep* k = kind_of<TowerStep>(s); k && towerp_step(*k)) {
+        towerp_lane_patches(k->halves[0].args.H, k->halves[0].args.W, k->lane_patch);
+        k->has_lane_patch = true;
+      }
     plan.steps.swap(out);
   }
   // one step from tower halves of one map size; own_scratch: what passes from an a half to its b half never leaves the launch
@@ -785,7 +792,7 @@ struct PlanBuilder {
     tower("fpn.reg_head_3.block", h3, w3, ws.f3, false, 1);
     tower("fpn.cls_head_2.block", h2, w2, ws.f2, true, 0);
     tower("fpn.reg_head_2.block", h2, w2, ws.f2, false, 0);
-    merge_tower_launches();
+    merge_tower_launches();   // (also the pass that gives every towerp_kernel step its lane table: no TowerStep is created after it)
     const StemStep* stem = plan.steps.empty() ? nullptr : kind_of<StemStep>(plan.steps[0]);
     S2PxStep* s20 = plan.steps.size() > 1 ? kind_of<S2PxStep>(plan.steps[1]) : nullptr;
     if (plan.front_fused && ok && stem && s20 && s20->img16) {
@@ -908,12 +915,17 @@ const char* launch(const TowerStep& st, const RunCtx& c) {
     TowerJobs jobs{};
     jobs.n = (int)st.halves.size();
     for (int k = 0; k < jobs.n; ++k) jobs.j[k] = half_args(st.halves[k], c);
+    if (towerp_step(st) && !st.has_lane_patch) return "tower lane table";
+    std::copy(st.lane_patch, st.lane_patch + 128, jobs.lane_patch);
     // half a -> half b of a tower inside one launch: the tensor between them stays in the workgroup's LDS - as long as every
-    // workgroup has ONE image (the job loop is outside the image loop)
+    // workgroup has ONE image (the job loop is outside the image loop: a second image's half a would overwrite the first's before
+    // its half b has read it).  That is: as long as the launch's grid, which launch_towers takes from the same function, is B
     jobs.par = st.par ? 1 : 0;
+    const Yfv2Device dev = yfv2_device();   // (the step's one look at the device: the launchers below take it from here)
+    const bool one_image = yfv2_image_grid(c.B, dev) == c.B;
     for (int k = 0; k + 1 < jobs.n && !st.par; ++k)
-      if (c.B <= 256 && !jobs.j[k].has_head && jobs.j[k].out == jobs.j[k + 1].in) { jobs.j[k].chain |= 2; jobs.j[k + 1].chain |= 1; }
-    if (yfv2_launch_towerh(jobs, st.tiles, c.stream)) return nullptr;
+      if (one_image && !jobs.j[k].has_head && jobs.j[k].out == jobs.j[k + 1].in) { jobs.j[k].chain |= 2; jobs.j[k + 1].chain |= 1; }
+    if (yfv2_launch_towerh(jobs, st.tiles, dev, c.stream)) return nullptr;
   }
   for (const TowerHalf& t : st.halves)   // tower2_kernel, one launch per half
     if (!yfv2_launch_tower2(half_args(t, c), c.stream)) return "tower";
@@ -946,7 +958,7 @@ std::string step_kernel(const Step& st) {
       const TowerHalf& t = k.halves[0];
       const int H = t.args.H, W = t.args.W;
       if (t.img16 && k.halves.size() > 1 && !k.par) return "towers_kernel<" + std::to_string(k.tiles) + ">";   // default plan, maps up to 11x11
-      if (t.img16 && (H > 11 || W > 11) && !((H | W) & 1))   // default plan, even maps up to 22x22
+      if (towerp_step(k))   // default plan, even maps up to 22x22
         return "towerp_kernel<" + std::to_string(k.tiles) + (k.par && k.halves.size() == 4 ? ", true>" : ", false>");
       if (t.img16) return "towerh_kernel<" + std::to_string(k.tiles) + ", " + (H > 11 || W > 11 ? "2, 4>" : "1, 1>");
       return "tower2_kernel<" + std::to_string(!t.has_head ? 0 : ((t.args.mh + 15) / 16 <= 1 ? 1 : 6)) + ", 512, " + (H * W > 128 ? "4, 4," : "1, 1,");

@@ -252,21 +252,17 @@ void yfv2_launch_decode(const DecodeArgs& a, hipStream_t s) {
   const int b0 = (a.fh[0] * a.fw[0] + cells - 1) / cells;
   const int b1 = (a.fh[1] * a.fw[1] + cells - 1) / cells;
   const size_t lds = (size_t)cells * 3 * (5 + a.classes) * sizeof(float);
-  static std::atomic<unsigned long long> lds_ok0{0}, lds_ok1{0}, lds_ok2{0}, lds_ok3{0};
+  // (the compact forms keep no rows in LDS)
   if (a.classes <= 96) {
-    yfv2_allow_full_lds(reinterpret_cast<const void*>(&decode_kernel<false>), lds_ok0);
-    yfv2_allow_full_lds(reinterpret_cast<const void*>(&decode_kernel<true>), lds_ok1);
     if (a.cand)
       YFV2_LAUNCH(decode_kernel<true>, dim3(a.B * (b0 + b1)), dim3(DEC_THREADS), 0, s, a, b0, b1);
     else
-      YFV2_LAUNCH(decode_kernel<false>, dim3(a.B * (b0 + b1)), dim3(DEC_THREADS), lds, s, a, b0, b1);
+      YFV2_LAUNCH_LDS(yfv2_device(), decode_kernel<false>, YFV2_LDS_FULL, dim3(a.B * (b0 + b1)), dim3(DEC_THREADS), lds, s, a, b0, b1);
   } else {   // up to 255 classes: 64 class slots per lane, 32 cells per workgroup ([32][3][260] floats of LDS)
-    yfv2_allow_full_lds(reinterpret_cast<const void*>(&decode_kernel<false, 64>), lds_ok2);
-    yfv2_allow_full_lds(reinterpret_cast<const void*>(&decode_kernel<true, 64>), lds_ok3);
     if (a.cand)
       YFV2_LAUNCH((decode_kernel<true, 64>), dim3(a.B * (b0 + b1)), dim3(4 * cells), 0, s, a, b0, b1);
     else
-      YFV2_LAUNCH((decode_kernel<false, 64>), dim3(a.B * (b0 + b1)), dim3(4 * cells), lds, s, a, b0, b1);
+      YFV2_LAUNCH_LDS(yfv2_device(), (decode_kernel<false, 64>), YFV2_LDS_FULL, dim3(a.B * (b0 + b1)), dim3(4 * cells), lds, s, a, b0, b1);
   }
 }
 // the fused decode + NMS launch (nms_kernel<2>) holds a lane's class slice in 24 registers and the image's rows in LDS
@@ -708,15 +704,8 @@ void yfv2_launch_nms(const NmsArgs& a, hipStream_t s) {
 // handel_preds + non_max_suppression of yfv2_detect as ONE launch: a.boxes is unused, the rows are decoded into LDS
 void yfv2_launch_decode_nms(const DecodeArgs& d, const NmsArgs& a, hipStream_t s) {
   // 85 KB of static LDS (sort keys, box arrays, masks) + up to 64 KB of candidate rows: the dynamic part's cap is what
-  // is left of the CU's 160 KB, not 160 KB (yfv2_allow_full_lds would be refused)
-  static std::atomic<unsigned long long> done{0};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 63) dev = 0;
-  if (!(done.load() & (1ull << dev))) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&nms_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, NMS_CAP * 8 * (int)sizeof(float));
-    done.fetch_or(1ull << dev);
-  }
-  YFV2_LAUNCH(nms_kernel<2>, dim3(a.B), dim3(NMS_THREADS), (size_t)a.rows * 8 * sizeof(float), s, a, d);
+  // is left of the CU's 160 KB, not 160 KB (YFV2_LDS_FULL would be refused)
+  YFV2_LAUNCH_LDS(yfv2_device(), nms_kernel<2>, NMS_CAP * 8 * (int)sizeof(float), dim3(a.B), dim3(NMS_THREADS), (size_t)a.rows * 8 * sizeof(float), s, a, d);
 }
 
 // ============================================================================

@@ -159,13 +159,13 @@ size_t yfv2_resize_lds_bytes(int SW, int W) { return 2 * (size_t)((SW * 3 + 6) &
 void yfv2_launch_resize(const ResizeArgs& a, hipStream_t s) {
   const size_t lds = yfv2_resize_lds_bytes(a.SW, a.W);
   static std::atomic<unsigned long long> lds_ok0{0};
-  yfv2_allow_full_lds(reinterpret_cast<const void*>(&resize_u8_kernel), lds_ok0);
+  yfv2_allow_lds(yfv2_device(), reinterpret_cast<const void*>(&resize_u8_kernel), YFV2_LDS_FULL, lds_ok0);
   hipLaunchKernelGGL(resize_u8_kernel, dim3((unsigned)(a.B * a.H)), dim3(256), lds, s, a);
 }
 
 void yfv2_launch_resize_frames(const ResizeFrame* frames, int B, int max_w, unsigned char* dst, int H, int W, hipStream_t s) {
   const size_t lds = yfv2_resize_lds_bytes(max_w, W);
   static std::atomic<unsigned long long> lds_ok0{0};
-  yfv2_allow_full_lds(reinterpret_cast<const void*>(&resize_frames_u8_kernel), lds_ok0);
+  yfv2_allow_lds(yfv2_device(), reinterpret_cast<const void*>(&resize_frames_u8_kernel), YFV2_LDS_FULL, lds_ok0);
   hipLaunchKernelGGL(resize_frames_u8_kernel, dim3((unsigned)(B * H)), dim3(RF_THREADS), lds, s, frames, dst, H, W);
 }

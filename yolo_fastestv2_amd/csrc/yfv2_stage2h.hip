@@ -871,12 +871,7 @@ void yfv2_launch_front(const FrontArgs& a0, hipStream_t s) {
   // again), so fewer bands are less work - but the launch is bound by instruction issue and wants two waves on every SIMD for
   // most of its duration: 1.5 x (two 4-wave workgroups per CU) workgroups or more.  256 images: 4 bands (768 workgroups; 5 bands
   // measured the same 130 us, 768 workgroups being three per CU either way); 512 images: 2; one image: 16 bands (47 -> 19.5 us).
-  static std::atomic<int> cus_of[64];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 63) dev = 0;
-  int cus = cus_of[dev].load(std::memory_order_relaxed);
-  if (cus <= 0) { if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256; cus_of[dev].store(cus, std::memory_order_relaxed); }
-  const long long want = 3LL * cus;
+  const long long want = 3LL * yfv2_device_cus();
   int best_nb = 1;
   for (int nb = 1; nb <= OH && nb <= 16; ++nb) {
     const int R = (OH + nb - 1) / nb, nbe = (OH + R - 1) / R;
@@ -1119,9 +1114,7 @@ void yfv2_launch_s3h(const BlockS2Args& a0, hipStream_t s) {
   a.R = (OH + nb - 1) / nb;
   nb = (OH + a.R - 1) / a.R;
   const int units = nstrips * nb;
-  static std::atomic<unsigned long long> lds_ok{0};
-  yfv2_allow_full_lds(reinterpret_cast<const void*>(&s3h2_kernel), lds_ok);
-  YFV2_LAUNCH(s3h2_kernel, dim3(a.B * ((units + 3) / 4)), dim3(256), S3H2_FLOATS * sizeof(float), s, a);
+  YFV2_LAUNCH_LDS(yfv2_device(), s3h2_kernel, YFV2_LDS_FULL, dim3(a.B * ((units + 3) / 4)), dim3(256), S3H2_FLOATS * sizeof(float), s, a);
 }
 
 // ============================================================================
@@ -1335,9 +1328,6 @@ void yfv2_launch_s4h(const BlockS2Args& a0, hipStream_t s) {
   a.R = (OH + nb - 1) / nb;
   nb = (OH + a.R - 1) / a.R;
   const int units = nstrips * nb;
-  static std::atomic<unsigned long long> lds_ok{0};
-  yfv2_allow_full_lds(reinterpret_cast<const void*>(&s4h_kernel), lds_ok);
   a.s4_main_bands = (nstrips == 1 && OH >= 6) ? 3 : 0;   // (wider or very low maps: two bands x two roles per workgroup, round 4's form)
-  if (a.s4_main_bands) { YFV2_LAUNCH(s4h_kernel, dim3(a.B), dim3(256), 3 * S4H_WFL * sizeof(float), s, a); return; }
-  YFV2_LAUNCH(s4h_kernel, dim3(a.B * ((units + 1) / 2)), dim3(256), 3 * S4H_WFL * sizeof(float), s, a);
+  YFV2_LAUNCH_LDS(yfv2_device(), s4h_kernel, YFV2_LDS_FULL, dim3(a.s4_main_bands ? a.B : a.B * ((units + 1) / 2)), dim3(256), 3 * S4H_WFL * sizeof(float), s, a);
 }

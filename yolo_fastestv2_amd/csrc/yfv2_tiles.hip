@@ -187,18 +187,10 @@ __global__ __launch_bounds__(MG_THREADS) void tile_merge_kernel(TileMergeArgs a)
   if (tid == 0) a.count[f] = n_keep;
 }
 
-std::atomic<unsigned long long> merge_lds_ok{0};
-
 }  // namespace
 
 void yfv2_launch_tile_merge(const TileMergeArgs& a, hipStream_t s) {
   YFV2_LAUNCH(tile_rank_kernel, dim3((unsigned)a.T), dim3(RK_THREADS), 0, s, a);
   // the kept set of 4096 rows is 96 KB of dynamic LDS next to 12 KB of static: raise the function's limit to exactly that, once per device
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev > 63) dev = 0;
-  if (!(merge_lds_ok.load(std::memory_order_relaxed) & (1ull << dev))) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&tile_merge_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, MG_MAX_OUT * 6 * (int)sizeof(float));
-    merge_lds_ok.fetch_or(1ull << dev, std::memory_order_relaxed);
-  }
-  YFV2_LAUNCH(tile_merge_kernel, dim3((unsigned)a.F), dim3(MG_THREADS), (size_t)a.max_out * 6 * sizeof(float), s, a);
+  YFV2_LAUNCH_LDS(yfv2_device(), tile_merge_kernel, MG_MAX_OUT * 6 * (int)sizeof(float), dim3((unsigned)a.F), dim3(MG_THREADS), (size_t)a.max_out * 6 * sizeof(float), s, a);
 }

@@ -32,12 +32,8 @@
 // Two barriers per chunk (input slice ready / exchange ready); the next chunk's slice is in flight in registers during
 // the pointwise phase, the next image's first slice during the last chunk.
 #include "yfv2_internal.h"
-#include <atomic>
 #include <algorithm>
-#include <array>
 #include <cstddef>
-#include <map>
-#include <mutex>
 #include <vector>
 
 typedef _Float16 yfv2_h4 __attribute__((ext_vector_type(4)));
@@ -1143,29 +1139,24 @@ __global__ __launch_bounds__(512) void towerp_kernel(TowerJobs jobs) {
 }
 
 template <int MH>
-static void launch_towers(const TowerJobs& jobs, hipStream_t s) {
+static void launch_towers(const TowerJobs& jobs, const Yfv2Device& dev, hipStream_t s) {
   const int B = jobs.j[0].B;
   const size_t lds = sizeof(float) * ((size_t)th_lds_img(MH) + (TH_C / 4) * 27 * 4 + 15 * 11 * TH_C + 128 * TS_CP + 256);   // (+ 1 KB where unwanted stores go)
-  static std::atomic<unsigned long long> lds_ok{0};
-  yfv2_allow_full_lds(reinterpret_cast<const void*>(&towers_kernel<MH>), lds_ok);
-  YFV2_LAUNCH((towers_kernel<MH>), dim3(B < 256 ? B : 256), dim3(512), lds, s, jobs);
+  YFV2_LAUNCH_LDS(dev, (towers_kernel<MH>), YFV2_LDS_FULL, dim3(yfv2_image_grid(B, dev)), dim3(512), lds, s, jobs);
 }
 
 template <int MH, int PS, int NT>
-static void launch_towerh(TowerJobs jobs, hipStream_t s) {
+static void launch_towerh(TowerJobs jobs, const Yfv2Device& dev, hipStream_t s) {
   const size_t lds = sizeof(float) * ((size_t)th_lds_img(MH) + 4 * (4 * 16 * NT * 8 + ThGeom<PS>::TIN_SLOTS));
-  static std::atomic<unsigned long long> lds_ok{0};
-  yfv2_allow_full_lds(reinterpret_cast<const void*>(&towerh_kernel<MH, PS, NT>), lds_ok);
-  const int B = jobs.j[0].B;
-  jobs.gpj = B < 256 ? B : 256;
-  YFV2_LAUNCH((towerh_kernel<MH, PS, NT>), dim3(jobs.gpj * (jobs.par ? jobs.n : 1)), dim3(512), lds, s, jobs);
+  jobs.gpj = yfv2_image_grid(jobs.j[0].B, dev);
+  YFV2_LAUNCH_LDS(dev, (towerh_kernel<MH, PS, NT>), YFV2_LDS_FULL, dim3(jobs.gpj * (jobs.par ? jobs.n : 1)), dim3(512), lds, s, jobs);
 }
 
 // towerp_kernel's lane -> patch table.  ds_read_b128 is serviced in four groups of 16 lanes, one LDS cycle per group when the 16
 // slots are distinct mod 16 (64 banks x 4 bytes).  A patch (py, px) reads slots py * TP_P + px + const: patches are dealt to the
 // eight groups of the two rounds so that no group holds two patches of one residue class (a class has at most ceil(patches / 16)
 // + 1 members; with more than eight the extra one costs its group one cycle).
-static void towerp_lane_patches(int H, int W, unsigned char (&tbl)[128]) {
+void towerp_lane_patches(int H, int W, unsigned char (&tbl)[128]) {
   static const int grp[4][16] = {{0, 1, 2, 3, 12, 13, 14, 15, 20, 21, 22, 23, 24, 25, 26, 27}, {4, 5, 6, 7, 8, 9, 10, 11, 16, 17, 18, 19, 28, 29, 30, 31},
                                  {32, 33, 34, 35, 44, 45, 46, 47, 52, 53, 54, 55, 56, 57, 58, 59}, {36, 37, 38, 39, 40, 41, 42, 43, 48, 49, 50, 51, 60, 61, 62, 63}};
   const int PWn = (W + 1) / 2, PHn = (H + 1) / 2, NP = PWn * PHn;
@@ -1221,31 +1212,14 @@ static void towerp_lane_patches(int H, int W, unsigned char (&tbl)[128]) {
 }
 
 template <int MH, bool BOTH>
-static void launch_towerp(TowerJobs jobs, hipStream_t s) {
+static void launch_towerp(TowerJobs jobs, const Yfv2Device& dev, hipStream_t s) {
   const size_t lds = sizeof(float) * (size_t)tp_lds_floats(MH);
-  static std::atomic<unsigned long long> lds_ok{0};
-  yfv2_allow_full_lds(reinterpret_cast<const void*>(&towerp_kernel<MH, BOTH>), lds_ok);
   const int B = jobs.j[0].B;
   // a workgroup runs every side-by-side job of its images (one prologue, the next item's data requested under the current one) - unless
   // there are fewer items than CUs: then one workgroup per item
   const int njobs = jobs.par ? jobs.n : 1;
-  jobs.gpj = (!BOTH && njobs > 1 && njobs * B <= 256) ? njobs * B : (B < 256 ? B : 256);
-  {
-    static std::mutex mu;
-    static std::map<int, std::array<unsigned char, 128>> cache;
-    std::lock_guard<std::mutex> lk(mu);
-    const int key = jobs.j[0].H * 64 + jobs.j[0].W;
-    auto it = cache.find(key);
-    if (it == cache.end()) {
-      unsigned char t[128];
-      towerp_lane_patches(jobs.j[0].H, jobs.j[0].W, t);
-      std::array<unsigned char, 128> arr;
-      std::copy(t, t + 128, arr.begin());
-      it = cache.emplace(key, arr).first;
-    }
-    std::copy(it->second.begin(), it->second.end(), jobs.lane_patch);
-  }
-  YFV2_LAUNCH((towerp_kernel<MH, BOTH>), dim3(jobs.gpj), dim3(512), lds, s, jobs);
+  jobs.gpj = (!BOTH && njobs > 1 && njobs * B <= dev.cus) ? njobs * B : yfv2_image_grid(B, dev);   // (jobs.lane_patch: the plan's, towerp_lane_patches)
+  YFV2_LAUNCH_LDS(dev, (towerp_kernel<MH, BOTH>), YFV2_LDS_FULL, dim3(jobs.gpj), dim3(512), lds, s, jobs);
 }
 
 // 2x2 patches: up to 22x22 with at most 128 patches; single pixels: up to 11x11
@@ -1254,12 +1228,15 @@ bool yfv2_towerh_supported(int H, int W) {
   if (H <= 11 && W <= 11) return true;
   return H <= 22 && W <= 22 && ((H + 1) / 2) * ((W + 1) / 2) <= 128;
 }
+// ... of which towerp_kernel's: even maps beyond 11x11 (its 16-byte patch-row records want even sizes).  The plan gives every such step its
+// lane table (towerp_lane_patches), yfv2_launch_towerh routes by it and step_kernel names by it
+bool yfv2_towerp_map(int H, int W) { return yfv2_towerh_supported(H, W) && (H > 11 || W > 11) && !((H | W) & 1); }
 // several tower halves in one launch: maps up to 11x11 only (towers_kernel)
 bool yfv2_towerh_multi(int H, int W) { return H >= 1 && W >= 1 && H <= 11 && W <= 11; }
 
 // The kernel is instantiated for 0, 1 or 6 output-conv tiles; every job's image must be packed for `mh_tiles` of them
 // (WeightPacker::image_towerh pads with zero tiles) - the LDS layout depends on it.
-bool yfv2_launch_towerh(const TowerJobs& jobs, int mh_tiles, hipStream_t s) {
+bool yfv2_launch_towerh(const TowerJobs& jobs, int mh_tiles, const Yfv2Device& dev, hipStream_t s) {
   if (jobs.n < 1 || jobs.n > 4) return false;
   const TowerArgs& a = jobs.j[0];
   for (int i = 0; i < jobs.n; ++i)
@@ -1267,36 +1244,36 @@ bool yfv2_launch_towerh(const TowerJobs& jobs, int mh_tiles, hipStream_t s) {
   if (!yfv2_towerh_supported(a.H, a.W) || (mh_tiles != 0 && mh_tiles != 1 && mh_tiles != 6)) return false;
   if (jobs.n > 1 && !jobs.par) {
     if (!yfv2_towerh_multi(a.H, a.W) || mh_tiles == 0) return false;
-    if (mh_tiles == 1) launch_towers<1>(jobs, s);
-    else launch_towers<6>(jobs, s);
+    if (mh_tiles == 1) launch_towers<1>(jobs, dev, s);
+    else launch_towers<6>(jobs, dev, s);
   } else if (a.H <= 11 && a.W <= 11) {
     // single halves of a small map: only what the planner leaves unmerged - a class head wider than 96 channels (its b half without merged
     // matrix: 0 tiles, the output convs as pointwise launches) beside the reg tower (1 tile).  Everything else at this size is towers_kernel's
-    if (mh_tiles == 0) launch_towerh<0, 1, 1>(jobs, s);
-    else if (mh_tiles == 1) launch_towerh<1, 1, 1>(jobs, s);
+    if (mh_tiles == 0) launch_towerh<0, 1, 1>(jobs, dev, s);
+    else if (mh_tiles == 1) launch_towerh<1, 1, 1>(jobs, dev, s);
     else return false;
-  } else if ((a.H & 1) || (a.W & 1)) {   // odd maps (13x13 at 416x416): towerh_kernel<.., 2, 4> (towerp_kernel's 16-byte patch-row records want even sizes)
-    if (mh_tiles == 0) launch_towerh<0, 2, 4>(jobs, s);
-    else if (mh_tiles == 1) launch_towerh<1, 2, 4>(jobs, s);
-    else launch_towerh<6, 2, 4>(jobs, s);
+  } else if (!yfv2_towerp_map(a.H, a.W)) {   // the odd larger maps (13x13 at 416x416): towerh_kernel<.., 2, 4>
+    if (mh_tiles == 0) launch_towerh<0, 2, 4>(jobs, dev, s);
+    else if (mh_tiles == 1) launch_towerh<1, 2, 4>(jobs, dev, s);
+    else launch_towerh<6, 2, 4>(jobs, dev, s);
   } else if (jobs.par && jobs.n == 4 && mh_tiles != 0 && !jobs.j[0].has_head && !jobs.j[1].has_head && jobs.j[2].has_head && jobs.j[3].has_head) {
     // a whole level: {cls a, reg a, cls b, reg b}.  Batches that fill the chip (two workgroups' worth of items per CU and more): ONE launch, a
     // workgroup runs its image's four halves back to back; smaller batches: the a halves and the b halves as two launches of independent
     // items (one workgroup per item - a single image's four halves in sequence would take twice as long as two rounds of two)
-    if (2 * a.B > 256) {
-      if (mh_tiles == 1) launch_towerp<1, true>(jobs, s);
-      else launch_towerp<6, true>(jobs, s);
+    if (2 * a.B > dev.cus) {
+      if (mh_tiles == 1) launch_towerp<1, true>(jobs, dev, s);
+      else launch_towerp<6, true>(jobs, dev, s);
     } else {
       TowerJobs ja = jobs, jb = jobs;
       ja.n = 2; jb.n = 2; jb.j[0] = jobs.j[2]; jb.j[1] = jobs.j[3];
-      launch_towerp<0, false>(ja, s);
-      if (mh_tiles == 1) launch_towerp<1, false>(jb, s);
-      else launch_towerp<6, false>(jb, s);
+      launch_towerp<0, false>(ja, dev, s);
+      if (mh_tiles == 1) launch_towerp<1, false>(jb, dev, s);
+      else launch_towerp<6, false>(jb, dev, s);
     }
   } else {
-    if (mh_tiles == 0) launch_towerp<0, false>(jobs, s);
-    else if (mh_tiles == 1) launch_towerp<1, false>(jobs, s);
-    else launch_towerp<6, false>(jobs, s);
+    if (mh_tiles == 0) launch_towerp<0, false>(jobs, dev, s);
+    else if (mh_tiles == 1) launch_towerp<1, false>(jobs, dev, s);
+    else launch_towerp<6, false>(jobs, dev, s);
   }
   return true;
 }
