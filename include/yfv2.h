@@ -261,6 +261,62 @@ YFV2_API int yfv2_detect_tiled_u8(yfv2_handle h, const yfv2_frame* frames, int32
                                   float conf_thres, double iou_thres, double merge_thres, int32_t merge_metric, int32_t max_out,
                                   float* dets, int32_t* src, int32_t* count, void* stream);
 
+/* ---- decoder-format frames: YUV 4:2:0 planes read in place ----
+ * Video and JPEG decoders write a luma plane and half-resolution chroma - one interleaved plane (NV12 / NV21) or two planes
+ * (I420; YV12 = I420 with u and v swapped by the caller) - each with a row pitch of its own.  The entry points below take those
+ * planes as they are.  THE RULE: the result for a YUV frame is bit-identical to converting the frame to packed B, G, R with the
+ * integer formula below and passing that to the _u8 entry point of the same name.
+ *   pixel (r, c)   R = y0 + r, C = x0 + c; luma y[R * pitch_y + C]; chroma at (R >> 1, C >> 1), replicated, no interpolation (as
+ *                  cv2 and the decoders' own sample converters do): NV12 u[(R>>1) * pitch_c + 2 * (C>>1)] is U and the byte after
+ *                  it V; NV21 the same two bytes swapped; I420 u[(R>>1) * pitch_c + (C>>1)] is U and v[...] is V
+ *   colour         int32 throughout, SHIFT = 20, coefficients rint(k * 2^20) (limited range: luma * 255/219, chroma * 255/224):
+ *                                        off  CY       CVR      CVG      CUG      CUB
+ *                    YFV2_BT601_LIMITED  16   1220542  1673527  -852492  -409993  2116026   (OpenCV's COLOR_YUV2BGR_NV12 / _I420 literals)
+ *                    YFV2_BT709_LIMITED  16   1220945  1879825  -558796  -223607  2215014
+ *                    YFV2_BT601_FULL     0    1048576  1470104  -748826  -360853  1858077   (JPEG)
+ *                    YFV2_BT709_FULL     0    1048576  1651297  -490864  -196424  1945738
+ *                  yy = max(Y - off, 0) * CY; u = U - 128; v = V - 128
+ *                  R = clamp((yy + (1 << 19) + CVR * v) >> 20, 0, 255)              (arithmetic shift: floor for negatives)
+ *                  G = clamp((yy + (1 << 19) + CVG * v + CUG * u) >> 20, 0, 255)
+ *                  B = clamp((yy + (1 << 19) + CUB * u) >> 20, 0, 255)              stored B, G, R: the network's channel order
+ * OpenCV is not in this image: the tests compare with a numpy statement of this published arithmetic (tests/yuv_model.py) - parity
+ * with cv2 proper is unpinned, exactly as for the resize. */
+enum { YFV2_YUV_NV12 = 0, YFV2_YUV_NV21 = 1, YFV2_YUV_I420 = 2 };
+enum { YFV2_BT601_LIMITED = 0, YFV2_BT709_LIMITED = 1, YFV2_BT601_FULL = 2, YFV2_BT709_FULL = 3 };
+typedef struct yfv2_frame_yuv {
+  const uint8_t* y;        /* DEVICE: luma plane, any alignment */
+  const uint8_t* u;        /* NV12/NV21: the interleaved chroma plane; I420: the U plane */
+  const uint8_t* v;        /* I420: the V plane; ignored for NV12/NV21 */
+  int64_t pitch_y, pitch_c;/* bytes per row of the luma / chroma plane(s) */
+  int32_t x0, y0;          /* top-left pixel of the frame inside the planes (any parity): a crop needs no copy */
+  int32_t width, height;   /* pixels, >= 1, any parity */
+  int32_t format, colour;  /* YFV2_YUV_*, YFV2_BT* */
+} yfv2_frame_yuv;
+
+/* yfv2_resize_frames_u8 for B YUV 4:2:0 frames of any sizes: dst is bit-identical to yfv2_resize_frames_u8 of the frames converted
+ * by the rule above; the conversion happens at the four taps of each output pixel, from planes staged in LDS, so the planes are
+ * read once and no B, G, R frame exists in memory.  Only bytes of the frame's own rectangle of each plane are read (and the chroma
+ * samples it shares with its neighbours).  Checked before anything is enqueued (YFV2_ERR_ARG with a message naming the frame and
+ * the field): NULL frames, y or u; NULL v with I420; width or height < 1; x0 or y0 < 0; pitch_y < x0 + width; pitch_c smaller
+ * than the last chroma byte a row of the frame reads; unknown format or colour; a frame wider than the widest whose two luma rows,
+ * chroma rows and output row fit 160 KiB of LDS (40 689 at cfg.width 352); pitches out of range; dst not 4-byte aligned.
+ * B > max_batch is YFV2_ERR_BATCH: the descriptors go to a table of max_batch entries the handle owns, in one copy on `stream`. */
+YFV2_API int yfv2_resize_frames_yuv(yfv2_handle h, const yfv2_frame_yuv* frames, int32_t B, uint8_t* dst, void* stream);
+
+/* yfv2_detect_frames_u8 with the resize launch exchanged for yfv2_resize_frames_yuv's: the same handle-owned resize buffer, the
+ * same yfv2_detect_u8 and the same frame-coordinate scaling by width_b / cfg.width, height_b / cfg.height.  Bit-identical to
+ * yfv2_detect_frames_u8 on the converted frames.  Same checks as yfv2_resize_frames_yuv plus those of yfv2_detect_u8. */
+YFV2_API int yfv2_detect_frames_yuv(yfv2_handle h, const yfv2_frame_yuv* frames, int32_t B, float conf_thres, double iou_thres,
+                                    float* dets, int32_t* idx, int32_t* count, void* stream);
+
+/* yfv2_detect_tiled_u8 on YUV frames: tile k is frames[tiles[k].frame]'s descriptor with x0 += tile.x0, y0 += tile.y0 and the
+ * tile's size (which is why x0 and y0 may be odd); the T descriptors go through yfv2_detect_frames_yuv, then the same merge.
+ * Bit-identical to yfv2_detect_tiled_u8 on the converted frames.  Checked before anything is enqueued: everything
+ * yfv2_detect_frames_yuv checks, per frame and per tile; everything yfv2_merge_tiles checks; each rectangle inside its frame. */
+YFV2_API int yfv2_detect_tiled_yuv(yfv2_handle h, const yfv2_frame_yuv* frames, int32_t F, const yfv2_tile* tiles, int32_t T,
+                                   float conf_thres, double iou_thres, double merge_thres, int32_t merge_metric, int32_t max_out,
+                                   float* dets, int32_t* src, int32_t* count, void* stream);
+
 /* ---- the ncnn sample's deployment path (sample/ncnn/src/yolo-fastestv2.cpp) ----
  * The reference's only native component post-processes differently from its Python path in every step that decides which boxes
  * come out: no objectness pre-filter (score = cls * obj > thresh only), boxes scaled to the source frame and TRUNCATED TO int

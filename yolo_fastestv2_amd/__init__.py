@@ -28,6 +28,8 @@ from .pipeline import DetectPipeline  # noqa: F401
 from . import genanchors  # noqa: F401
 from . import tiling  # noqa: F401
 from . import ncnn_sample  # noqa: F401
+from . import yuv  # noqa: F401
+from .yuv import YuvFrame  # noqa: F401
 from .tiling import plan_tiles  # noqa: F401
 from .sharded import average_gradients_, detect_sharded, gather_decoded, gather_detections, shard_range  # noqa: F401
 

@@ -73,6 +73,12 @@ class Frame(C.Structure):
     _fields_ = [("data", C.c_void_p), ("height", C.c_int32), ("width", C.c_int32), ("row_pitch", C.c_int64)]
 
 
+class FrameYuv(C.Structure):
+    """yfv2_frame_yuv (include/yfv2.h): one YUV 4:2:0 frame of a ragged batch, planes read in place; y, u, v are DEVICE pointers."""
+    _fields_ = [("y", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("pitch_y", C.c_int64), ("pitch_c", C.c_int64),
+                ("x0", C.c_int32), ("y0", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("format", C.c_int32), ("colour", C.c_int32)]
+
+
 class Tile(C.Structure):
     """yfv2_tile (include/yfv2.h): a rectangle inside frames[frame]."""
     _fields_ = [("frame", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("width", C.c_int32), ("height", C.c_int32)]
@@ -143,6 +149,11 @@ _PROTOTYPES = {
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "yfv2_detect_tiled_u8": (C.c_int, [C.c_void_p, C.POINTER(Frame), C.c_int32, C.POINTER(Tile), C.c_int32, C.c_float, C.c_double, C.c_double,
                                        C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "yfv2_resize_frames_yuv": (C.c_int, [C.c_void_p, C.POINTER(FrameYuv), C.c_int32, C.c_void_p, C.c_void_p]),
+    "yfv2_detect_frames_yuv": (C.c_int, [C.c_void_p, C.POINTER(FrameYuv), C.c_int32, C.c_float, C.c_double, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p]),
+    "yfv2_detect_tiled_yuv": (C.c_int, [C.c_void_p, C.POINTER(FrameYuv), C.c_int32, C.POINTER(Tile), C.c_int32, C.c_float, C.c_double, C.c_double,
+                                        C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "yfv2_export_maps": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "yfv2_deploy_post": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
                                    C.c_int32, C.c_void_p]),

@@ -242,6 +242,8 @@ int yfv2_create_ex(yfv2_handle* out, const yfv2_config* cfg, const yfv2_plan* pl
     rc = fail(h, YFV2_ERR_DEVICE, "hipMalloc(class filter) failed");
   if (rc == YFV2_OK && hipMalloc(reinterpret_cast<void**>(&h->d_frames), sizeof(ResizeFrame) * (size_t)cfg->max_batch) != hipSuccess)
     rc = fail(h, YFV2_ERR_DEVICE, "hipMalloc(frame table) failed");
+  if (rc == YFV2_OK && hipMalloc(reinterpret_cast<void**>(&h->d_frames_yuv), sizeof(ResizeFrameYuv) * (size_t)cfg->max_batch) != hipSuccess)
+    rc = fail(h, YFV2_ERR_DEVICE, "hipMalloc(YUV frame table) failed");
   if (rc == YFV2_OK) {
     h->d_stats_flag = h->d_classes + 256;
     if (hipMemset(h->d_stats_flag, 0, 2 * sizeof(int32_t)) != hipSuccess) rc = fail(h, YFV2_ERR_DEVICE, "hipMemset(flags) failed");
@@ -272,6 +274,7 @@ void yfv2_destroy(yfv2_handle h) {
   h->ws.for_each(h->cfg, h->rows, [](Buf& b, size_t) { free_buf(&b); });
   if (h->d_classes) (void)hipFree(h->d_classes);
   if (h->d_frames) (void)hipFree(h->d_frames);
+  if (h->d_frames_yuv) (void)hipFree(h->d_frames_yuv);
   if (h->d_probe) (void)hipFree(h->d_probe);
   if (h->train) { yfv2_train_release(h->train); h->train = nullptr; }
   if (h->d_params) (void)hipFree(h->d_params);

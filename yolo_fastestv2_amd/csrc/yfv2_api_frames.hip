@@ -82,6 +82,29 @@ int yfv2_resize_frames_u8(yfv2_handle h, const yfv2_frame* frames, int32_t B, ui
   return YFV2_OK;
 }
 
+// What yfv2_detect_frames_u8 and yfv2_detect_frames_yuv share once their frames are checked and expanded: the handle's resized
+// batch, the descriptor upload(s), ONE resize launch - the YUV one when `yuv` is given, which then reads its own table while
+// frame_boxes_kernel reads box_x / box_y from t - then yfv2_detect_u8 and the frame-coordinate epilogue.
+static int detect_frames_tail(yfv2_handle h, const std::vector<ResizeFrame>& t, const std::vector<ResizeFrameYuv>* yuv, int max_w, int32_t B,
+                              float conf_thres, double iou_thres, float* dets, int32_t* idx, int32_t* count, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DeviceGuard guard(h->device);
+  if (int rc2 = h->frames_u8.reserve(h, (size_t)h->cfg.height * h->cfg.width * 3 * (size_t)h->cfg.max_batch, true)) return rc2;   // the resized batch
+  HIP_TRY(h, hipMemcpyAsync(h->d_frames, t.data(), sizeof(ResizeFrame) * (size_t)B, hipMemcpyHostToDevice, s));
+  if (yuv) {
+    HIP_TRY(h, hipMemcpyAsync(h->d_frames_yuv, yuv->data(), sizeof(ResizeFrameYuv) * (size_t)B, hipMemcpyHostToDevice, s));
+    yfv2_launch_resize_frames_yuv(h->d_frames_yuv, B, max_w, h->frames_u8.as<uint8_t>(), h->cfg.height, h->cfg.width, s);
+  } else {
+    yfv2_launch_resize_frames(h->d_frames, B, max_w, h->frames_u8.as<uint8_t>(), h->cfg.height, h->cfg.width, s);
+  }
+  HIP_TRY(h, hipGetLastError());
+  int rc = yfv2_detect_u8(h, h->frames_u8.as<uint8_t>(), B, conf_thres, iou_thres, dets, idx, count, stream);
+  if (rc) return rc;
+  yfv2_launch_frame_boxes(dets, count, h->d_frames, B, s);
+  HIP_TRY(h, hipGetLastError());
+  return YFV2_OK;
+}
+
 int yfv2_detect_frames_u8(yfv2_handle h, const yfv2_frame* frames, int32_t B, float conf_thres, double iou_thres, float* dets,
                           int32_t* idx, int32_t* count, void* stream) {
   int rc = check_call(h, B, true);
@@ -91,17 +114,102 @@ int yfv2_detect_frames_u8(yfv2_handle h, const yfv2_frame* frames, int32_t B, fl
   int max_w = 0;
   rc = check_frames(h, "yfv2_detect_frames_u8", frames, B, t, &max_w);
   if (rc) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  DeviceGuard guard(h->device);
-  if (int rc2 = h->frames_u8.reserve(h, (size_t)h->cfg.height * h->cfg.width * 3 * (size_t)h->cfg.max_batch, true)) return rc2;   // the resized batch
-  HIP_TRY(h, hipMemcpyAsync(h->d_frames, t.data(), sizeof(ResizeFrame) * (size_t)B, hipMemcpyHostToDevice, s));
-  yfv2_launch_resize_frames(h->d_frames, B, max_w, h->frames_u8.as<uint8_t>(), h->cfg.height, h->cfg.width, s);
-  HIP_TRY(h, hipGetLastError());
-  rc = yfv2_detect_u8(h, h->frames_u8.as<uint8_t>(), B, conf_thres, iou_thres, dets, idx, count, stream);
+  return detect_frames_tail(h, t, nullptr, max_w, B, conf_thres, iou_thres, dets, idx, count, stream);
+}
+
+// ---- YUV 4:2:0 frames (kernel: resize_frames_yuv_kernel, yfv2_pre.hip) -------------------------------------------
+
+// what every YUV entry point checks of one caller's frame - a whole frame of yfv2_detect_tiled_yuv or a frame of a batch; `at` as in
+// check_frame.  The width limit is not here: it binds what is resized, which for a tiled frame are its tiles.
+static int check_frame_yuv(yfv2_handle h, const std::string& at, const yfv2_frame_yuv& f) {
+  if (f.format != YFV2_YUV_NV12 && f.format != YFV2_YUV_NV21 && f.format != YFV2_YUV_I420)
+    return fail(h, YFV2_ERR_ARG, at + "unknown format " + std::to_string(f.format));
+  if (f.colour < YFV2_BT601_LIMITED || f.colour > YFV2_BT709_FULL) return fail(h, YFV2_ERR_ARG, at + "unknown colour " + std::to_string(f.colour));
+  if (f.height < 1 || f.width < 1) return fail(h, YFV2_ERR_ARG, at + "height and width must be >= 1");
+  if (f.x0 < 0 || f.y0 < 0) return fail(h, YFV2_ERR_ARG, at + "x0 and y0 must be >= 0");
+  if (!f.y) return fail(h, YFV2_ERR_ARG, at + "null y");
+  if (!f.u) return fail(h, YFV2_ERR_ARG, at + "null u");
+  const bool planar = f.format == YFV2_YUV_I420;
+  if (planar && !f.v) return fail(h, YFV2_ERR_ARG, at + "null v (I420)");
+  const long long xe = (long long)f.x0 + f.width, ye = (long long)f.y0 + f.height;     // one past the frame's last column / row in the planes
+  if (xe > 0x7fffffffll || ye > 0x7fffffffll) return fail(h, YFV2_ERR_ARG, at + "x0 + width and y0 + height must be below 2^31");
+  if (f.pitch_y < xe) return fail(h, YFV2_ERR_ARG, at + "pitch_y " + std::to_string(f.pitch_y) + " < x0 + width");
+  const long long crow = (((xe - 1) >> 1) + 1) * (planar ? 1 : 2);                       // chroma bytes of a row up to the frame's last sample
+  if (f.pitch_c < crow) return fail(h, YFV2_ERR_ARG, at + "pitch_c " + std::to_string(f.pitch_c) + " < " + std::to_string(crow) + ", the last chroma byte of a row");
+  if (f.pitch_y > (1ll << 40) || (ye - 1) * f.pitch_y > (1ll << 52)) return fail(h, YFV2_ERR_ARG, at + "pitch_y out of range");
+  if (f.pitch_c > (1ll << 40) || ((ye - 1) >> 1) * f.pitch_c > (1ll << 52)) return fail(h, YFV2_ERR_ARG, at + "pitch_c out of range");
+  return YFV2_OK;
+}
+
+// check_frames for yfv2_frame_yuv: every frame is checked here, before anything is enqueued, and expanded into the kernel's
+// descriptor (origin folded into the plane pointers, the scales of yfv2_resize_u8) and into t, of which frame_boxes_kernel reads
+// box_x / box_y; *max_w = the widest frame (it sizes the launch's LDS).
+static int check_frames_yuv(yfv2_handle h, const char* what, const yfv2_frame_yuv* frames, int32_t B, std::vector<ResizeFrame>& t,
+                            std::vector<ResizeFrameYuv>& ty, int* max_w) {
+  const std::string w_ = what;
+  if (!frames) return fail(h, YFV2_ERR_ARG, w_ + ": null pointer");
+  if (B < 1) return fail(h, YFV2_ERR_ARG, w_ + ": B < 1");
+  if (B > h->cfg.max_batch)
+    return fail(h, YFV2_ERR_BATCH, w_ + ": batch " + std::to_string(B) + " above max_batch=" + std::to_string(h->cfg.max_batch));
+  const int H = h->cfg.height, W = h->cfg.width;
+  const int limit = yfv2_resize_yuv_max_width(W);
+  t.assign((size_t)B, ResizeFrame{});
+  ty.assign((size_t)B, ResizeFrameYuv{});
+  int mw = 1;
+  for (int32_t b = 0; b < B; ++b) {
+    const yfv2_frame_yuv& f = frames[b];
+    const std::string at = w_ + ": frame " + std::to_string(b) + ": ";
+    if (int rc = check_frame_yuv(h, at, f)) return rc;
+    if (f.width > limit) return fail(h, YFV2_ERR_ARG, at + "frames wider than " + std::to_string(limit) + " pixels are not supported");
+    const bool planar = f.format == YFV2_YUV_I420;
+    ResizeFrameYuv& r = ty[(size_t)b];
+    const long long coff = (long long)(f.y0 >> 1) * f.pitch_c + (long long)(f.x0 >> 1) * (planar ? 1 : 2);
+    r.y = f.y + (long long)f.y0 * f.pitch_y + f.x0;
+    r.ca = f.u + coff;
+    r.cb = planar ? f.v + coff : nullptr;
+    r.pitch_y = f.pitch_y; r.pitch_c = f.pitch_c; r.h = f.height; r.w = f.width;
+    r.px = f.x0 & 1; r.py = f.y0 & 1; r.format = f.format; r.coef = yfv2_yuv_coef(f.colour);
+    r.scale_x = 1.0 / ((double)W / (double)f.width);      // exactly yfv2_resize_u8's scales
+    r.scale_y = 1.0 / ((double)H / (double)f.height);
+    ResizeFrame& q = t[(size_t)b];
+    q.h = f.height; q.w = f.width; q.scale_x = r.scale_x; q.scale_y = r.scale_y;
+    q.box_x = (double)f.width / (double)W;                // test.py:58  scale_w = w / cfg["width"]
+    q.box_y = (double)f.height / (double)H;
+    mw = std::max(mw, (int)f.width);
+  }
+  if ((long long)B * H > 0x7fffffffll) return fail(h, YFV2_ERR_ARG, w_ + ": batch too large");
+  *max_w = mw;
+  return YFV2_OK;
+}
+
+int yfv2_resize_frames_yuv(yfv2_handle h, const yfv2_frame_yuv* frames, int32_t B, uint8_t* dst, void* stream) {
+  if (!h) return fail(nullptr, YFV2_ERR_ARG, "null handle");
+  if (!dst) return fail(h, YFV2_ERR_ARG, "yfv2_resize_frames_yuv: null pointer");
+  if ((reinterpret_cast<uintptr_t>(dst) & 3) != 0) return fail(h, YFV2_ERR_ARG, "yfv2_resize_frames_yuv: dst must be 4-byte aligned");
+  std::vector<ResizeFrame> t;
+  std::vector<ResizeFrameYuv> ty;
+  int max_w = 0;
+  int rc = check_frames_yuv(h, "yfv2_resize_frames_yuv", frames, B, t, ty, &max_w);
   if (rc) return rc;
-  yfv2_launch_frame_boxes(dets, count, h->d_frames, B, s);
+  DeviceGuard guard(h->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  HIP_TRY(h, hipMemcpyAsync(h->d_frames_yuv, ty.data(), sizeof(ResizeFrameYuv) * (size_t)B, hipMemcpyHostToDevice, s));
+  yfv2_launch_resize_frames_yuv(h->d_frames_yuv, B, max_w, dst, h->cfg.height, h->cfg.width, s);
   HIP_TRY(h, hipGetLastError());
   return YFV2_OK;
+}
+
+int yfv2_detect_frames_yuv(yfv2_handle h, const yfv2_frame_yuv* frames, int32_t B, float conf_thres, double iou_thres, float* dets,
+                           int32_t* idx, int32_t* count, void* stream) {
+  int rc = check_call(h, B, true);
+  if (rc) return rc;
+  if (!dets || !idx || !count) return fail(h, YFV2_ERR_ARG, "yfv2_detect_frames_yuv: null pointer");
+  std::vector<ResizeFrame> t;
+  std::vector<ResizeFrameYuv> ty;
+  int max_w = 0;
+  rc = check_frames_yuv(h, "yfv2_detect_frames_yuv", frames, B, t, ty, &max_w);
+  if (rc) return rc;
+  return detect_frames_tail(h, t, &ty, max_w, B, conf_thres, iou_thres, dets, idx, count, stream);
 }
 
 // ---- tiled detection ----------------------------------------------------------------------------------
@@ -201,33 +309,35 @@ int yfv2_merge_tiles(yfv2_handle h, const float* tile_dets, const int32_t* tile_
   return enqueue_merge(h, tile_dets, tile_count, table, T, F, merge_thres, merge_metric, max_out, dets, src, count, static_cast<hipStream_t>(stream));
 }
 
-int yfv2_detect_tiled_u8(yfv2_handle h, const yfv2_frame* frames, int32_t F, const yfv2_tile* tiles, int32_t T, float conf_thres, double iou_thres,
-                         double merge_thres, int32_t merge_metric, int32_t max_out, float* dets, int32_t* src, int32_t* count, void* stream) {
+// yfv2_detect_tiled_u8 and yfv2_detect_tiled_yuv: the frame type and four things that depend on it - the check of one frame, its
+// size, the crop of it that a tile is, and the check + detection of the T crops (check_only: everything the detect entry point
+// checks, before the workspaces are touched; it checks again when it runs: host work only).
+extern "C++" template <class Frame, class CheckFrame, class SizeOf, class CropOf, class DetectCrops>
+static int detect_tiled_impl(yfv2_handle h, const std::string& w_, const Frame* frames, int32_t F, const yfv2_tile* tiles, int32_t T, float conf_thres,
+                             double iou_thres, double merge_thres, int32_t merge_metric, int32_t max_out, float* dets, int32_t* src, int32_t* count,
+                             void* stream, CheckFrame check_one, SizeOf size_of, CropOf crop_of, DetectCrops detect_crops) {
   if (!h) return fail(nullptr, YFV2_ERR_ARG, "null handle");
-  if (!frames || !tiles || !dets || !count) return fail(h, YFV2_ERR_ARG, "yfv2_detect_tiled_u8: null pointer");
+  if (!frames || !tiles || !dets || !count) return fail(h, YFV2_ERR_ARG, w_ + ": null pointer");
   if (T > h->cfg.max_batch)
-    return fail(h, YFV2_ERR_BATCH, "yfv2_detect_tiled_u8: " + std::to_string(T) + " tiles above max_batch=" + std::to_string(h->cfg.max_batch));
+    return fail(h, YFV2_ERR_BATCH, w_ + ": " + std::to_string(T) + " tiles above max_batch=" + std::to_string(h->cfg.max_batch));
   std::vector<int32_t> table;
-  if (int rc = check_merge(h, "yfv2_detect_tiled_u8", tiles, T, F, merge_thres, merge_metric, max_out, table)) return rc;
+  if (int rc = check_merge(h, w_.c_str(), tiles, T, F, merge_thres, merge_metric, max_out, table)) return rc;
   for (int32_t f = 0; f < F; ++f)
-    if (int rc = check_frame(h, "yfv2_detect_tiled_u8: frame " + std::to_string(f) + ": ", frames[f])) return rc;
-  std::vector<yfv2_frame> crops((size_t)T);
+    if (int rc = check_one(w_ + ": frame " + std::to_string(f) + ": ", frames[f])) return rc;
+  std::vector<Frame> crops((size_t)T);
   for (int32_t k = 0; k < T; ++k) {
     const yfv2_tile& t = tiles[k];
-    const yfv2_frame& fr = frames[t.frame];
-    if (t.width < 1 || t.height < 1 || t.x0 < 0 || t.y0 < 0 || (int64_t)t.x0 + t.width > fr.width || (int64_t)t.y0 + t.height > fr.height)
-      return fail(h, YFV2_ERR_ARG, "yfv2_detect_tiled_u8: tile " + std::to_string(k) + ": [" + std::to_string(t.x0) + ", " + std::to_string((int64_t)t.x0 + t.width) +
+    const Frame& fr = frames[t.frame];
+    int32_t fw = 0, fh = 0;
+    size_of(fr, &fw, &fh);
+    if (t.width < 1 || t.height < 1 || t.x0 < 0 || t.y0 < 0 || (int64_t)t.x0 + t.width > fw || (int64_t)t.y0 + t.height > fh)
+      return fail(h, YFV2_ERR_ARG, w_ + ": tile " + std::to_string(k) + ": [" + std::to_string(t.x0) + ", " + std::to_string((int64_t)t.x0 + t.width) +
                                        ") x [" + std::to_string(t.y0) + ", " + std::to_string((int64_t)t.y0 + t.height) + ") is not a rectangle of at least one pixel inside its " +
-                                       std::to_string(fr.width) + " x " + std::to_string(fr.height) + " frame");
-    crops[(size_t)k] = yfv2_frame{fr.data + (int64_t)t.y0 * fr.row_pitch + 3ll * t.x0, t.height, t.width, fr.row_pitch};
+                                       std::to_string(fw) + " x " + std::to_string(fh) + " frame");
+    crops[(size_t)k] = crop_of(fr, t);
   }
-  // everything yfv2_detect_frames_u8 checks, per crop, before the workspaces are touched (it checks again: host work only)
   if (int rc = check_call(h, T, true)) return rc;
-  {
-    std::vector<ResizeFrame> t;
-    int max_w = 0;
-    if (int rc = check_frames(h, "yfv2_detect_tiled_u8", crops.data(), T, t, &max_w)) return rc;
-  }
+  if (int rc = detect_crops(crops.data(), true, nullptr, nullptr, nullptr)) return rc;
   DeviceGuard guard(h->device);
   const size_t mb = (size_t)h->cfg.max_batch;
   if (int rc = h->tile_out.reserve(h, sizeof(float) * mb * YFV2_MAX_DET * 6 + sizeof(int32_t) * (mb * YFV2_MAX_DET + mb), true)) return rc;
@@ -235,8 +345,49 @@ int yfv2_detect_tiled_u8(yfv2_handle h, const yfv2_frame* frames, int32_t F, con
   float* t_dets = h->tile_out.as<float>();
   int32_t* t_idx = reinterpret_cast<int32_t*>(t_dets + mb * YFV2_MAX_DET * 6);
   int32_t* t_count = t_idx + mb * YFV2_MAX_DET;
-  if (int rc = yfv2_detect_frames_u8(h, crops.data(), T, conf_thres, iou_thres, t_dets, t_idx, t_count, stream)) return rc;
+  if (int rc = detect_crops(crops.data(), false, t_dets, t_idx, t_count)) return rc;
   return enqueue_merge(h, t_dets, t_count, table, T, F, merge_thres, merge_metric, max_out, dets, src, count, static_cast<hipStream_t>(stream));
+}
+
+int yfv2_detect_tiled_u8(yfv2_handle h, const yfv2_frame* frames, int32_t F, const yfv2_tile* tiles, int32_t T, float conf_thres, double iou_thres,
+                         double merge_thres, int32_t merge_metric, int32_t max_out, float* dets, int32_t* src, int32_t* count, void* stream) {
+  const char* what = "yfv2_detect_tiled_u8";
+  return detect_tiled_impl(
+      h, what, frames, F, tiles, T, conf_thres, iou_thres, merge_thres, merge_metric, max_out, dets, src, count, stream,
+      [&](const std::string& at, const yfv2_frame& f) { return check_frame(h, at, f); },
+      [](const yfv2_frame& f, int32_t* w, int32_t* hh) { *w = f.width; *hh = f.height; },
+      [](const yfv2_frame& fr, const yfv2_tile& t) { return yfv2_frame{fr.data + (int64_t)t.y0 * fr.row_pitch + 3ll * t.x0, t.height, t.width, fr.row_pitch}; },
+      [&](const yfv2_frame* crops, bool check_only, float* t_dets, int32_t* t_idx, int32_t* t_count) {
+        if (!check_only) return yfv2_detect_frames_u8(h, crops, T, conf_thres, iou_thres, t_dets, t_idx, t_count, stream);
+        std::vector<ResizeFrame> t;
+        int max_w = 0;
+        return check_frames(h, what, crops, T, t, &max_w);
+      });
+}
+
+int yfv2_detect_tiled_yuv(yfv2_handle h, const yfv2_frame_yuv* frames, int32_t F, const yfv2_tile* tiles, int32_t T, float conf_thres, double iou_thres,
+                          double merge_thres, int32_t merge_metric, int32_t max_out, float* dets, int32_t* src, int32_t* count, void* stream) {
+  const char* what = "yfv2_detect_tiled_yuv";
+  auto check_crops = [&](const yfv2_frame_yuv* crops, int32_t n) {
+    std::vector<ResizeFrame> t;
+    std::vector<ResizeFrameYuv> ty;
+    int max_w = 0;
+    return check_frames_yuv(h, what, crops, n, t, ty, &max_w);
+  };
+  return detect_tiled_impl(
+      h, what, frames, F, tiles, T, conf_thres, iou_thres, merge_thres, merge_metric, max_out, dets, src, count, stream,
+      [&](const std::string& at, const yfv2_frame_yuv& f) { return check_frame_yuv(h, at, f); },
+      [](const yfv2_frame_yuv& f, int32_t* w, int32_t* hh) { *w = f.width; *hh = f.height; },
+      [](const yfv2_frame_yuv& fr, const yfv2_tile& t) {
+        yfv2_frame_yuv c = fr;
+        c.x0 = fr.x0 + t.x0; c.y0 = fr.y0 + t.y0;     // (inside the frame, whose far corner is below 2^31)
+        c.width = t.width; c.height = t.height;
+        return c;
+      },
+      [&](const yfv2_frame_yuv* crops, bool check_only, float* t_dets, int32_t* t_idx, int32_t* t_count) {
+        if (!check_only) return yfv2_detect_frames_yuv(h, crops, T, conf_thres, iou_thres, t_dets, t_idx, t_count, stream);
+        return check_crops(crops, T);
+      });
 }
 
 // ---- the ncnn sample's path (kernels: yfv2_deploy.hip) ----------------------------------------------------

@@ -489,6 +489,25 @@ struct ResizeFrame {
   double box_x, box_y;        // frame-coordinate epilogue: w / W, h / H (test.py:58)
 };
 void yfv2_launch_resize_frames(const ResizeFrame* frames, int B, int max_w, unsigned char* dst, int H, int W, hipStream_t s);
+// one YUV 4:2:0 frame of a ragged batch (yfv2_resize_frames_yuv / yfv2_detect_frames_yuv): the caller's yfv2_frame_yuv with its
+// origin folded into the plane pointers on the host - pixel (r, c) of the frame has its luma at y[r * pitch_y + c] and its chroma
+// at row (r + py) >> 1, sample (c + px) >> 1 of ca / cb - so the kernel sees every frame, crop or not, as a plane set of its own
+struct YuvCoef { int off, cy, cvr, cvg, cug, cub; };   // one row of the colour table (yfv2_pre.hip)
+struct ResizeFrameYuv {
+  const unsigned char* y;     // luma of pixel (0, 0): plane + y0 * pitch_y + x0 (any alignment), device
+  const unsigned char* ca;    // NV12 / NV21: the interleaved plane at chroma row y0 >> 1, byte 2 * (x0 >> 1); I420: the U plane at (y0 >> 1, x0 >> 1)
+  const unsigned char* cb;    // I420: the V plane likewise; NV12 / NV21: null
+  long long pitch_y, pitch_c; // bytes from one row to the next
+  int h, w;
+  int px, py;                 // x0 & 1, y0 & 1: the parity of the origin decides which pixels share a chroma sample
+  int format;                 // YFV2_YUV_*
+  YuvCoef coef;               // the colour standard's row, copied in by the host: the kernel does not wait for a second, dependent load
+  double scale_x, scale_y;    // resize: 1 / (W / w), 1 / (H / h), as ResizeArgs
+};
+size_t yfv2_resize_yuv_lds_bytes(int w, int W);   // LDS of one workgroup of the YUV resize for a frame w pixels wide
+int yfv2_resize_yuv_max_width(int W);             // the widest frame whose workgroup fits YFV2_LDS_FULL
+YuvCoef yfv2_yuv_coef(int colour);                // YFV2_BT601_LIMITED .. YFV2_BT709_FULL -> its row
+void yfv2_launch_resize_frames_yuv(const ResizeFrameYuv* frames, int B, int max_w, unsigned char* dst, int H, int W, hipStream_t s);
 // dets columns 0-3 of the first count[b] rows of frame b times frames[b].box_x / box_y (yfv2_post.hip)
 void yfv2_launch_frame_boxes(float* dets, const int32_t* count, const ResizeFrame* frames, int B, hipStream_t s);
 void yfv2_launch_decode(const DecodeArgs& a, hipStream_t s);

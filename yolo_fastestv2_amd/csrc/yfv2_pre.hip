@@ -12,6 +12,9 @@
 // with aligned 4-byte loads (source row starts are arbitrary byte addresses), the blend reads LDS bytes, the output row
 // is assembled in LDS and leaves as aligned 4-byte stores (width % 4 == 0, so every output row starts 4-byte aligned).
 // Built with -ffp-contract=off: the coefficient arithmetic must round like the separate C operations it restates.
+#include <algorithm>
+
+#include "../../include/yfv2.h"
 #include "yfv2_internal.h"
 
 struct RowCoef { int s0, s1, c0, c1; };
@@ -154,7 +157,176 @@ __global__ __launch_bounds__(RF_THREADS, 6) void resize_frames_u8_kernel(const R
   for (int i = tid; i < (W * 3) >> 2; i += RF_THREADS) drow[i] = reinterpret_cast<const unsigned*>(OUT)[i];
 }
 
+// ---- the same ragged batch from decoder-format frames: YUV 4:2:0 planes read in place (yfv2_resize_frames_yuv) ----
+// THE COLOUR FORMULA (the specification; include/yfv2.h states it for callers, tests/yuv_model.py in numpy).  All int32, SHIFT = 20,
+// every coefficient rint(k * 2^20); the limited-range rows carry 255/219 in the luma and 255/224 in the chroma coefficients:
+//                         off  CY       CVR      CVG      CUG      CUB
+//   YFV2_BT601_LIMITED    16   1220542  1673527  -852492  -409993  2116026     OpenCV's COLOR_YUV2BGR_NV12 / _I420 literals
+//   YFV2_BT709_LIMITED    16   1220945  1879825  -558796  -223607  2215014     Kr / Kb = 0.2126 / 0.0722
+//   YFV2_BT601_FULL       0    1048576  1470104  -748826  -360853  1858077     JPEG; Kr / Kb = 0.299 / 0.114
+//   YFV2_BT709_FULL       0    1048576  1651297  -490864  -196424  1945738
+//   yy = max(Y - off, 0) * CY;  u = U - 128;  v = V - 128
+//   R = clamp((yy + (1 << 19) + CVR * v) >> 20, 0, 255)               (arithmetic shift: floor for negatives)
+//   G = clamp((yy + (1 << 19) + CVG * v + CUG * u) >> 20, 0, 255)
+//   B = clamp((yy + (1 << 19) + CUB * u) >> 20, 0, 255)               output order B, G, R: the network's channel order
+// The accumulators stay below 5.8e8 in magnitude over all 2^24 (Y, U, V) (tests/test_yuv_host.py sweeps them).  Chroma is replicated,
+// not interpolated.  OpenCV is not in this image: parity with cv2 proper is unpinned, exactly as for the resize above.
+static const YuvCoef YUV_COEF[4] = {
+    {16, 1220542, 1673527, -852492, -409993, 2116026},
+    {16, 1220945, 1879825, -558796, -223607, 2215014},
+    {0, 1048576, 1470104, -748826, -360853, 1858077},
+    {0, 1048576, 1651297, -490864, -196424, 1945738},
+};
+
+// Every factor fits 24 bits (|coefficient| < 2^23, |Y - off|, |u|, |v| <= 255) and every product int32, so the multiplies are
+// __mul24: full-rate v_mul_i32_i24 / v_mad_i32_i24 where a 32-bit integer multiply runs at a quarter of the rate - the same values.
+__device__ __forceinline__ void yfv2_yuv_to_bgr(int Y, int U, int V, const YuvCoef& k, int (&p)[3]) {
+  const int yy = __mul24(max(Y - k.off, 0), k.cy) + (1 << 19), u = U - 128, v = V - 128;
+  p[0] = min(max((yy + __mul24(k.cub, u)) >> 20, 0), 255);
+  p[1] = min(max((yy + __mul24(k.cvg, v) + __mul24(k.cug, u)) >> 20, 0), 255);
+  p[2] = min(max((yy + __mul24(k.cvr, v)) >> 20, 0), 255);
+}
+
+// One workgroup per (frame, output row), the scheme of resize_frames_u8_kernel.  Staged in LDS, as aligned dwords with the same
+// guard - a dword is loaded whole only when its four bytes lie in the frame's own extent OF THAT PLANE (first row's first needed byte
+// to last row's last needed byte), otherwise byte by byte from those that do: luma rows s0 and s1, w bytes each, and the chroma rows
+// (s0 + py) >> 1 and (s1 + py) >> 1 - ONCE when the two coincide (every other output row of an up-scale, most rows near 1:1) -
+// which are cw = ((w - 1 + px) >> 1) + 1 samples: 2 cw bytes of the interleaved plane, or cw bytes of each of U and V.  That is
+// 3 w to 4 w bytes per output row where the B, G, R kernel stages 6 w.  Each output pixel converts its four taps (s0 / s1 x sx0 /
+// sx1) to B, G, R and blends them with resize_frames_u8_kernel's expression: convert-then-blend is the only order that is
+// bit-identical to converting the frame and resizing it (the clamps and the rounding do not commute with the blend).
+// LDS per workgroup: two luma slots of (w + 6) & ~3, two chroma rows of two half-slots of ((w >> 1) + 7) & ~3 each (a half-slot
+// holds one I420 plane row at any misalignment, the two together one interleaved row), the output row 3 W.
+// Threads and occupancy: a 1920-wide frame takes 2 * 1924 + 4 * 964 + 1056 = 8760 bytes, so 18 workgroups per CU fit the LDS -
+// more than the 16 that two-wave workgroups reach under the CU's 32-wave limit, so LDS does not bound this kernel (it bounds the
+// B, G, R one at 12-13).  Two waves keep the 352 output pixels' 5.5 waves of blend work at 6 wave-iterations (four waves would run
+// 8).  The kernel needs 59 VGPRs, so the launch bound asks for all 8 waves per SIMD = those 16 workgroups: like its neighbour the
+// launch is a chain of round trips per workgroup (descriptor, staging loads, barrier, blend, barrier, stores), and what hides them is
+// workgroups in flight - measured 258 us at 8 waves per SIMD against 283 us at 6 on the probe's mix.
+constexpr int RY_THREADS = 128;
+__global__ __launch_bounds__(RY_THREADS, 8) void resize_frames_yuv_kernel(const ResizeFrameYuv* __restrict__ frames, unsigned char* __restrict__ dst, int H, int W) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int tid = threadIdx.x;
+  const int b = blockIdx.x / H, oy = blockIdx.x - b * H;
+  const ResizeFrameYuv f = frames[b];
+  const RowCoef ry = yfv2_axis_coef(oy, f.scale_y, f.h, false);
+  const bool planar = f.format == YFV2_YUV_I420;
+  const int cw = ((f.w - 1 + f.px) >> 1) + 1, ch = ((f.h - 1 + f.py) >> 1) + 1;   // chroma samples per row, chroma rows of the frame
+  const int cbytes = planar ? cw : 2 * cw;
+  const int cr0 = (ry.s0 + f.py) >> 1, cr1 = (ry.s1 + f.py) >> 1;
+  const bool one_chroma_row = cr0 == cr1;
+  const int yslot = (f.w + 6) & ~3, chalf = ((f.w >> 1) + 7) & ~3;
+  unsigned char* LY0 = smem;
+  unsigned char* LY1 = smem + yslot;
+  unsigned char* LC0 = smem + 2 * yslot;
+  unsigned char* LC1 = LC0 + 2 * chalf;
+  unsigned char* OUT = LC0 + 4 * chalf;
+  const long long extent_y = (long long)(f.h - 1) * f.pitch_y + f.w;
+  const long long extent_c = (long long)(ch - 1) * f.pitch_c + cbytes;
+  // Six row segments: luma s0, s1; chroma plane a rows cr0, cr1; chroma plane b (I420's V) rows cr0, cr1.  A segment that is not
+  // staged (the second chroma row when it is the first, plane b of an interleaved format) has no dwords.  Everything about a segment
+  // is wave-uniform, the guard included once it is counted in bytes from the segment's dword 0 (sptr, 4-byte aligned): the bytes
+  // [blo, bhi) of that stream lie in the plane's extent, so dword i is loaded whole iff blo <= 4 i and 4 i + 4 <= bhi.
+  const unsigned char* sbase[6] = {f.y, f.y, f.ca, f.ca, f.cb, f.cb};
+  unsigned char* slds[6] = {LY0, LY1, LC0, LC1, LC0 + chalf, LC1 + chalf};
+  const unsigned char* sptr[6];
+  int smis[6], snd[6], sblo[6], sbhi[6];
+  int maxnd = 0;
+#pragma unroll
+  for (int k = 0; k < 6; ++k) {
+    const long long g = k < 2 ? (long long)(k == 0 ? ry.s0 : ry.s1) * f.pitch_y : (long long)((k & 1) ? cr1 : cr0) * f.pitch_c;
+    const int n = k < 2 ? f.w : (((k & 1) && one_chroma_row) || (k >= 4 && !planar) ? 0 : cbytes);
+    smis[k] = (int)((reinterpret_cast<uintptr_t>(sbase[k]) + g) & 3);
+    const long long first = g - smis[k];                  // offset of the segment's dword 0 from its plane's base
+    sptr[k] = sbase[k] + first;
+    snd[k] = n ? (smis[k] + n + 3) >> 2 : 0;
+    sblo[k] = first < 0 ? (int)-first : 0;
+    sbhi[k] = (int)min((k < 2 ? extent_y : extent_c) - first, 4ll * snd[k]);
+    maxnd = max(maxnd, snd[k]);
+  }
+  // as resize_frames_u8_kernel: each thread issues its loads - up to STAGE_U per segment, 16 for the four or six segments of a
+  // 1920-wide frame, which one trip covers - before it writes any of them to LDS.  Only a segment's first and last dword can
+  // straddle an end of the extent (the row itself lies inside it): twelve threads gather those byte by byte, in the same flight.
+  constexpr int STAGE_U = 4;
+  for (int i0 = tid; i0 < maxnd; i0 += RY_THREADS * STAGE_U) {
+    unsigned v[6][STAGE_U];
+#pragma unroll
+    for (int k = 0; k < 6; ++k)
+#pragma unroll
+      for (int u = 0; u < STAGE_U; ++u) {
+        const int o = 4 * (i0 + RY_THREADS * u);
+        if (o >= sblo[k] && o + 4 <= sbhi[k]) v[k][u] = *reinterpret_cast<const unsigned*>(sptr[k] + o);
+      }
+#pragma unroll
+    for (int k = 0; k < 6; ++k)
+#pragma unroll
+      for (int u = 0; u < STAGE_U; ++u) {
+        const int o = 4 * (i0 + RY_THREADS * u);
+        if (o >= sblo[k] && o + 4 <= sbhi[k]) *reinterpret_cast<unsigned*>(slds[k] + o) = v[k][u];
+      }
+  }
+#pragma unroll
+  for (int k = 0; k < 6; ++k)
+    if ((tid >> 1) == k && snd[k] > 0) {
+      const int o = (tid & 1) ? 4 * (snd[k] - 1) : 0;
+      if (o < sblo[k] || o + 4 > sbhi[k]) {               // a dword that straddles an end of the plane's extent: only its bytes inside
+        unsigned e = 0;
+        for (int j = 0; j < 4; ++j)
+          if (o + j >= sblo[k] && o + j < sbhi[k]) e |= (unsigned)sptr[k][o + j] << (8 * j);
+        *reinterpret_cast<unsigned*>(slds[k] + o) = e;
+      }
+    }
+  __syncthreads();
+  // U and V of chroma sample j of blended row 0 / 1: pu[j * cstep], pv[j * cstep]
+  const int cstep = planar ? 1 : 2;
+  const unsigned char* a0 = LC0 + smis[2];
+  const unsigned char* a1 = one_chroma_row ? a0 : LC1 + smis[3];
+  const unsigned char* b0 = planar ? LC0 + chalf + smis[4] : a0 + 1;
+  const unsigned char* b1 = planar ? (one_chroma_row ? b0 : LC1 + chalf + smis[5]) : a1 + 1;
+  const bool swapped = f.format == YFV2_YUV_NV21;
+  const unsigned char* pu0 = swapped ? b0 : a0;
+  const unsigned char* pv0 = swapped ? a0 : b0;
+  const unsigned char* pu1 = swapped ? b1 : a1;
+  const unsigned char* pv1 = swapped ? a1 : b1;
+  const unsigned char* y0 = LY0 + smis[0];
+  const unsigned char* y1 = LY1 + smis[1];
+  const YuvCoef kc = f.coef;
+  for (int ox = tid; ox < W; ox += RY_THREADS) {
+    const RowCoef rx = yfv2_axis_coef(ox, f.scale_x, f.w, true);
+    const int j0 = ((rx.s0 + f.px) >> 1) * cstep, j1 = ((rx.s1 + f.px) >> 1) * cstep;
+    int p00[3], p01[3], p10[3], p11[3];      // B, G, R of the taps (row s0 / s1, column sx0 / sx1)
+    yfv2_yuv_to_bgr(y0[rx.s0], pu0[j0], pv0[j0], kc, p00);
+    yfv2_yuv_to_bgr(y0[rx.s1], pu0[j1], pv0[j1], kc, p01);
+    yfv2_yuv_to_bgr(y1[rx.s0], pu1[j0], pv1[j0], kc, p10);
+    yfv2_yuv_to_bgr(y1[rx.s1], pu1[j1], pv1[j1], kc, p11);
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const int S0 = (int)p00[c] * rx.c0 + (int)p01[c] * rx.c1;
+      const int S1 = (int)p10[c] * rx.c0 + (int)p11[c] * rx.c1;
+      const int v = (((ry.c0 * (S0 >> 4)) >> 16) + ((ry.c1 * (S1 >> 4)) >> 16) + 2) >> 2;
+      OUT[ox * 3 + c] = (unsigned char)min(max(v, 0), 255);
+    }
+  }
+  __syncthreads();
+  unsigned* drow = reinterpret_cast<unsigned*>(dst + ((size_t)b * H + oy) * W * 3);
+  for (int i = tid; i < (W * 3) >> 2; i += RY_THREADS) drow[i] = reinterpret_cast<const unsigned*>(OUT)[i];
+}
+
 size_t yfv2_resize_lds_bytes(int SW, int W) { return 2 * (size_t)((SW * 3 + 6) & ~3) + (size_t)W * 3; }
+
+// resize_frames_yuv_kernel's LDS for a frame w pixels wide: two luma slots, two chroma rows of two half-slots, the output row
+size_t yfv2_resize_yuv_lds_bytes(int w, int W) { return 2 * (size_t)((w + 6) & ~3) + 4 * (size_t)(((w >> 1) + 7) & ~3) + (size_t)W * 3; }
+
+YuvCoef yfv2_yuv_coef(int colour) { return YUV_COEF[colour]; }
+
+// the widest frame whose workgroup fits a CU's LDS: the function above grows by about 4 bytes per pixel and never falls, so the
+// answer is next to (YFV2_LDS_FULL - 3 W) / 4 and two short walks find it exactly
+int yfv2_resize_yuv_max_width(int W) {
+  int w = (int)std::max<long long>(1, ((long long)YFV2_LDS_FULL - 3ll * W) / 4);
+  while (w > 1 && yfv2_resize_yuv_lds_bytes(w, W) > (size_t)YFV2_LDS_FULL) --w;
+  while (yfv2_resize_yuv_lds_bytes(w + 1, W) <= (size_t)YFV2_LDS_FULL) ++w;
+  return w;
+}
 
 void yfv2_launch_resize(const ResizeArgs& a, hipStream_t s) {
   const size_t lds = yfv2_resize_lds_bytes(a.SW, a.W);
@@ -168,4 +340,11 @@ void yfv2_launch_resize_frames(const ResizeFrame* frames, int B, int max_w, unsi
   static std::atomic<unsigned long long> lds_ok0{0};
   yfv2_allow_lds(yfv2_device(), reinterpret_cast<const void*>(&resize_frames_u8_kernel), YFV2_LDS_FULL, lds_ok0);
   hipLaunchKernelGGL(resize_frames_u8_kernel, dim3((unsigned)(B * H)), dim3(RF_THREADS), lds, s, frames, dst, H, W);
+}
+
+void yfv2_launch_resize_frames_yuv(const ResizeFrameYuv* frames, int B, int max_w, unsigned char* dst, int H, int W, hipStream_t s) {
+  const size_t lds = yfv2_resize_yuv_lds_bytes(max_w, W);
+  static std::atomic<unsigned long long> lds_ok0{0};
+  yfv2_allow_lds(yfv2_device(), reinterpret_cast<const void*>(&resize_frames_yuv_kernel), YFV2_LDS_FULL, lds_ok0);
+  hipLaunchKernelGGL(resize_frames_yuv_kernel, dim3((unsigned)(B * H)), dim3(RY_THREADS), lds, s, frames, dst, H, W);
 }

@@ -5,7 +5,7 @@ import ctypes as C
 
 import torch
 
-from . import _lib, tiling
+from . import _lib, tiling, yuv
 from ._lib import MAX_DET, Config, TensorDesc, check
 
 LOGIT_ORDER = ("reg_2", "obj_2", "cls_2", "reg_3", "obj_3", "cls_3")  # detector.py:47
@@ -362,6 +362,60 @@ class Engine:
         dets, src, cnt = self._tiled_out(out, F, max_out)
         _lib.check(_lib.lib().yfv2_detect_tiled_u8(self._h, farr, F, tarr, T, float(conf_thres), float(iou_thres), float(merge_thres), code, max_out,
                                                    _ptr(dets), _ptr(src) if src is not None else None, _ptr(cnt), _stream(self.device)), self._h)
+        return dets, src, cnt
+
+    # ---- decoder-format frames: YUV 4:2:0 planes read in place (include/yfv2.h yfv2_*_yuv) -----------------------
+    def resize_frames_yuv(self, frames, out=None):
+        """`resize_frames` for a list of yuv.YuvFrame (NV12 / NV21 / I420 planes on the GPU, any sizes, crops by x0 / y0 / width / height;
+        a bare (y, uv) or (y, u, v) tuple is NV12 / I420 in BT.601 limited range).  The output is bit-identical to resize_frames of the
+        frames converted to B, G, R by the integer formula of include/yfv2.h; no converted frame is ever written."""
+        arr, keep = yuv.frame_table(frames, self.device)
+        B = len(keep)
+        self.ensure_batch(B)
+        if out is None:
+            out = torch.empty((B, self.height, self.width, 3), device=self.device, dtype=torch.uint8)
+        elif out.dtype != torch.uint8 or tuple(out.shape) != (B, self.height, self.width, 3) or out.device != self.device or not out.is_contiguous():
+            raise ValueError("out must be a contiguous uint8 (%d,%d,%d,3) tensor on %s" % (B, self.height, self.width, self.device))
+        check(_lib.lib().yfv2_resize_frames_yuv(self._h, arr, B, _ptr(out), _stream(self.device)), self._h)
+        return out
+
+    def detect_frames_yuv(self, frames, conf_thres, iou_thres, out=None, check=True):
+        """`detect_frames` for a list of yuv.YuvFrame: the same path with the resize launch reading the YUV planes.  Bit-identical to
+        detect_frames on the converted frames.  Enqueue only; check= as in detect()."""
+        self._need_anchors("detect_frames_yuv")
+        if check and self.peek_nonfinite():
+            self.check_finite("detect_frames_yuv (an earlier call on this handle)")
+        arr, keep = yuv.frame_table(frames, self.device)
+        B = len(keep)
+        self.ensure_batch(B)
+        dets, idx, cnt = out if out is not None else self.new_det_buffers(B)
+        _lib.check(_lib.lib().yfv2_detect_frames_yuv(self._h, arr, B, float(conf_thres), float(iou_thres), _ptr(dets), _ptr(idx), _ptr(cnt),
+                                                     _stream(self.device)), self._h)
+        return dets, idx, cnt
+
+    def detect_tiled_yuv(self, frames, tiles=None, conf_thres=0.3, iou_thres=0.4, merge_thres=None, metric="iou", max_out=MAX_DET,
+                         tile=(352, 352), overlap=(64, 64), include_full=False, out=None, check=True):
+        """`detect_tiled` for a list of yuv.YuvFrame: a tile is its frame's descriptor moved by the tile's origin, so tiles of any
+        parity are read in place.  Bit-identical to detect_tiled on the converted frames; same arguments and results."""
+        self._need_anchors("detect_tiled_yuv")
+        code = tiling.metric_code(metric)
+        max_out = int(max_out)
+        if not 1 <= max_out <= 4096:
+            raise ValueError("max_out must be in 1..4096, got %d" % max_out)
+        if merge_thres is None:
+            merge_thres = iou_thres
+        if check and self.peek_nonfinite():
+            self.check_finite("detect_tiled_yuv (an earlier call on this handle)")
+        farr, keep = yuv.frame_table(frames, self.device)
+        F = len(keep)
+        if tiles is None:
+            tiles = [t for f, fr in enumerate(keep) for t in tiling.plan_tiles(fr.height, fr.width, tile, overlap, include_full, frame=f)]
+        tarr = tiling.tile_table(tiles)
+        T = len(tarr)
+        self.ensure_batch(T)
+        dets, src, cnt = self._tiled_out(out, F, max_out)
+        _lib.check(_lib.lib().yfv2_detect_tiled_yuv(self._h, farr, F, tarr, T, float(conf_thres), float(iou_thres), float(merge_thres), code, max_out,
+                                                    _ptr(dets), _ptr(src) if src is not None else None, _ptr(cnt), _stream(self.device)), self._h)
         return dets, src, cnt
 
     # ---- the ncnn sample's deployment path (include/yfv2.h yfv2_export_maps / yfv2_deploy_post; DESIGN.md 4.14) ------------------

@@ -21,7 +21,7 @@ import contextlib
 
 import torch
 
-from . import tiling
+from . import tiling, yuv
 from .engine import Engine
 
 
@@ -124,6 +124,36 @@ class DetectPipeline:
                 for f in frames:
                     f.record_stream(self.streams[j])
             out = eng.detect_frames(frames, conf_thres, iou_thres, out=(dets[:B], idx[:B], cnt[:B]), check=False)
+            ev = torch.cuda.Event()
+            ev.record(self.streams[j])
+        return Ticket(j, ev, out, self._serial)
+
+    def submit_frames_yuv(self, frames, conf_thres, iou_thres, wait_for_input=True):
+        """`submit_frames` for a list of yuv.YuvFrame (Engine.detect_frames_yuv: the planes a decoder wrote, read in place) on the next
+        slot; len(frames) <= max_batch."""
+        frames = [yuv.as_frame(f) for f in frames]
+        B = len(frames)
+        if B > self.max_batch:
+            raise ValueError("batch %d exceeds max_batch %d" % (B, self.max_batch))
+        cur = torch.cuda.current_stream(self.device)
+        jn = self._serial % self.depth
+        if self.engines[jn].peek_nonfinite():     # as in submit(): the slot's previous batch, before the rotation advances
+            try:
+                with torch.cuda.stream(self.streams[jn]):
+                    self.engines[jn].check_finite("DetectPipeline.submit_frames_yuv: the batch of ticket #%s (slot %d), the last one run on this slot" % (self._last[jn], jn))
+            except Exception as e:
+                e.slot, e.serial = jn, self._last[jn]
+                raise
+        with self.slot() as (j, eng, (dets, idx, cnt)):
+            for ev in self._readers[j]:
+                self.streams[j].wait_event(ev)
+            self._readers[j] = []
+            if wait_for_input:
+                self.streams[j].wait_stream(cur)
+                for f in frames:
+                    for p in f.planes:
+                        p.record_stream(self.streams[j])
+            out = eng.detect_frames_yuv(frames, conf_thres, iou_thres, out=(dets[:B], idx[:B], cnt[:B]), check=False)
             ev = torch.cuda.Event()
             ev.record(self.streams[j])
         return Ticket(j, ev, out, self._serial)

@@ -1,0 +1,113 @@
+"""Decoder-format frames: YUV 4:2:0 planes read in place (include/yfv2.h yfv2_frame_yuv).
+
+    frame = YuvFrame((y, uv), "nv12", "bt709")                     # the two planes a video decoder wrote, as device tensors
+    dets, idx, cnt = engine.detect_frames_yuv([frame, ...], 0.3, 0.4)
+    crop = YuvFrame((y, uv), "nv12", "bt709", x0=101, y0=37, width=352, height=352)    # a rectangle of the same planes, no copy
+
+``planes`` are uint8 device tensors: ``(y, uv)`` for NV12 / NV21 - uv either (rows, bytes) or (rows, samples, 2) - and
+``(y, u, v)`` for I420 (YV12: pass ``(y, v, u)``).  A plane's row pitch is its ``stride(0)``; its bytes within a row must be
+contiguous.  Nothing here needs a device; the table goes to libyfv2.so as it is.
+"""
+import torch
+
+from . import _lib
+
+FORMATS = {"nv12": 0, "nv21": 1, "i420": 2, 0: 0, 1: 1, 2: 2}
+COLOURS = {"bt601": 0, "bt601_limited": 0, "bt709": 1, "bt709_limited": 1, "bt601_full": 2, "jpeg": 2, "bt709_full": 3, 0: 0, 1: 1, 2: 2, 3: 3}
+LDS_FULL = 160 * 1024
+
+
+def resize_lds_bytes(w, W):
+    """LDS of one workgroup of the YUV resize for a frame w pixels wide and an output row of W pixels (yfv2_pre.hip
+    yfv2_resize_yuv_lds_bytes): two luma slots, two chroma rows of two half-slots each, the output row."""
+    return 2 * ((w + 6) & ~3) + 4 * (((w >> 1) + 7) & ~3) + 3 * W
+
+
+def max_width(W):
+    """the widest YUV frame the resize admits at network width W (yfv2_resize_yuv_max_width)"""
+    w = max(1, (LDS_FULL - 3 * W) // 4)
+    while w > 1 and resize_lds_bytes(w, W) > LDS_FULL:
+        w -= 1
+    while resize_lds_bytes(w + 1, W) <= LDS_FULL:
+        w += 1
+    return w
+
+
+class YuvFrame:
+    """One YUV 4:2:0 frame: planes + format ("nv12", "nv21", "i420") + colour ("bt601", "bt709" - limited range - "bt601_full" alias
+    "jpeg", "bt709_full") and the rectangle of the planes that is the frame (default: all of the luma plane from (x0, y0) on)."""
+    __slots__ = ("planes", "format", "colour", "x0", "y0", "width", "height")
+
+    def __init__(self, planes, format="nv12", colour="bt601", x0=0, y0=0, width=None, height=None):
+        self.planes = tuple(planes)
+        if format not in FORMATS or isinstance(format, bool):
+            raise ValueError("format must be one of 'nv12', 'nv21', 'i420', got %r" % (format,))
+        if colour not in COLOURS or isinstance(colour, bool):
+            raise ValueError("colour must be one of 'bt601', 'bt709', 'bt601_full' ('jpeg'), 'bt709_full', got %r" % (colour,))
+        self.format, self.colour = FORMATS[format], COLOURS[colour]
+        self.x0, self.y0 = int(x0), int(y0)
+        if not self.planes or not torch.is_tensor(self.planes[0]) or self.planes[0].dim() != 2:
+            raise ValueError("planes[0] must be the 2-D luma plane")
+        self.width = int(self.planes[0].shape[1]) - self.x0 if width is None else int(width)
+        self.height = int(self.planes[0].shape[0]) - self.y0 if height is None else int(height)
+
+    def crop(self, x0, y0, width, height):
+        """the rectangle (x0, y0, width, height) of this frame as a frame of the same planes"""
+        return YuvFrame(self.planes, self.format, self.colour, self.x0 + int(x0), self.y0 + int(y0), width, height)
+
+    @property
+    def shape(self):
+        return (self.height, self.width)
+
+
+def as_frame(f):
+    """YuvFrame, or a bare tuple of planes: (y, uv) is NV12, (y, u, v) I420, both BT.601 limited range"""
+    if isinstance(f, YuvFrame):
+        return f
+    if isinstance(f, (tuple, list)) and len(f) in (2, 3) and all(torch.is_tensor(p) for p in f):
+        return YuvFrame(f, "nv12" if len(f) == 2 else "i420")
+    raise ValueError("expected a YuvFrame or a tuple of plane tensors (y, uv) / (y, u, v), got %s" % type(f).__name__)
+
+
+def _plane(i, name, p, device, rows, row_bytes):
+    """checks one plane against what the frame reads of it: `rows` rows of `row_bytes` bytes from its first byte -> pitch"""
+    if not torch.is_tensor(p) or p.dtype != torch.uint8 or p.device != device:
+        raise ValueError("frame %d: plane %s must be a uint8 tensor on %s" % (i, name, device))
+    if p.dim() == 3 and p.shape[2] == 2 and name == "uv" and (p.shape[1] <= 1 or p.stride(1) == 2) and p.stride(2) == 1:
+        have = 2 * int(p.shape[1])
+    elif p.dim() == 2 and (p.shape[1] <= 1 or p.stride(1) == 1):
+        have = int(p.shape[1])
+    else:
+        raise ValueError("frame %d: plane %s must be 2-D with contiguous rows (uv may be (rows, samples, 2))" % (i, name))
+    if p.shape[0] < rows or have < row_bytes:
+        raise ValueError("frame %d: plane %s is %d rows x %d bytes, the frame reads %d x %d of it" % (i, name, p.shape[0], have, rows, row_bytes))
+    return int(p.stride(0)) if p.shape[0] > 1 else max(have, 1)
+
+
+def frame_table(frames, device):
+    """list / tuple of YuvFrame (or plane tuples) -> (yfv2_frame_yuv array, the frames).  Every plane must hold what its frame's
+    rectangle reads: the native library sees pointers and pitches only and cannot check that."""
+    if not isinstance(frames, (list, tuple)) or not frames or torch.is_tensor(frames[0]):
+        raise ValueError("frames must be a non-empty list or tuple of YuvFrame")
+    frames = [as_frame(f) for f in frames]
+    arr = (_lib.FrameYuv * len(frames))()
+    for i, f in enumerate(frames):
+        planar = f.format == FORMATS["i420"]
+        if len(f.planes) != (3 if planar else 2):
+            raise ValueError("frame %d: %s takes %d planes, got %d" % (i, "i420" if planar else "nv12 / nv21", 3 if planar else 2, len(f.planes)))
+        if f.x0 < 0 or f.y0 < 0:
+            raise ValueError("frame %d: x0 and y0 must be >= 0" % i)
+        a = arr[i]
+        a.x0, a.y0, a.width, a.height, a.format, a.colour = f.x0, f.y0, f.width, f.height, f.format, f.colour
+        if f.width >= 1 and f.height >= 1:      # (a frame without pixels is the native check's to report)
+            crows, csamples = ((f.y0 + f.height - 1) >> 1) + 1, ((f.x0 + f.width - 1) >> 1) + 1
+            a.pitch_y = _plane(i, "y", f.planes[0], device, f.y0 + f.height, f.x0 + f.width)
+            if planar:
+                a.pitch_c = _plane(i, "u", f.planes[1], device, crows, csamples)
+                if _plane(i, "v", f.planes[2], device, crows, csamples) != a.pitch_c:
+                    raise ValueError("frame %d: planes u and v must have the same row pitch" % i)
+                a.v = f.planes[2].data_ptr()
+            else:
+                a.pitch_c = _plane(i, "uv", f.planes[1], device, crows, 2 * csamples)
+        a.y, a.u = f.planes[0].data_ptr(), f.planes[1].data_ptr()
+    return arr, frames
