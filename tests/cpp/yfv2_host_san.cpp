@@ -140,8 +140,11 @@ int main() {
   CHECK(yfv2_resize_u8(h, nullptr, 1, 1, 1, nullptr, nullptr) == YFV2_ERR_ARG, "resize_u8");
   CHECK(yfv2_resize_frames_u8(h, nullptr, 1, nullptr, nullptr) == YFV2_ERR_ARG, "resize_frames_u8");
   CHECK(yfv2_detect_frames_u8(h, nullptr, 1, 0.3f, 0.4, nullptr, nullptr, nullptr, nullptr) == YFV2_ERR_ARG, "detect_frames_u8");
+  CHECK(yfv2_resize_frames_yuv(h, nullptr, 1, nullptr, nullptr) == YFV2_ERR_ARG, "resize_frames_yuv");
+  CHECK(yfv2_detect_frames_yuv(h, nullptr, 1, 0.3f, 0.4, nullptr, nullptr, nullptr, nullptr) == YFV2_ERR_ARG, "detect_frames_yuv");
   CHECK(yfv2_merge_tiles(h, nullptr, nullptr, nullptr, 1, 1, 0.5, 0, 300, nullptr, nullptr, nullptr, nullptr) == YFV2_ERR_ARG, "merge_tiles");
   CHECK(yfv2_detect_tiled_u8(h, nullptr, 1, nullptr, 1, 0.3f, 0.4, 0.5, 0, 300, nullptr, nullptr, nullptr, nullptr) == YFV2_ERR_ARG, "detect_tiled_u8");
+  CHECK(yfv2_detect_tiled_yuv(h, nullptr, 1, nullptr, 1, 0.3f, 0.4, 0.5, 0, 300, nullptr, nullptr, nullptr, nullptr) == YFV2_ERR_ARG, "detect_tiled_yuv");
   CHECK(yfv2_batch_statistics(h, nullptr, nullptr, 1, nullptr, 0, 0.5f, nullptr, nullptr) == YFV2_ERR_ARG, "batch_statistics");
   CHECK(yfv2_batch_statistics_async(h, nullptr, nullptr, 1, nullptr, 0, 0.5f, nullptr, nullptr) == YFV2_ERR_ARG, "batch_statistics_async");
   CHECK(yfv2_batch_statistics_overflow(h, nullptr, nullptr) == YFV2_ERR_ARG, "batch_statistics_overflow");

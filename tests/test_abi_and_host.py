@@ -656,6 +656,26 @@ def test_detect_pipeline_slot_rotation_and_ticket_rules(monkeypatch):
             log.append(("detect", self, current[0], tuple(o.shape[0] for o in out)))
             out[2][:] = int(x.sum())
             return out
+        # the other four calls the pipeline makes on a slot: each logs (its name, engine, current stream, rows of every out tensor)
+        rows = 7
+        def _enqueued(self, name, out, check):
+            assert check is False
+            log.append((name, self, current[0], tuple(o.shape[0] for o in out)))
+            return out
+        def detect_frames(self, frames, conf, iou, out=None, check=True): return self._enqueued("detect_frames", out, check)
+        def detect_frames_yuv(self, frames, conf, iou, out=None, check=True):
+            assert all(isinstance(f, P.yuv.YuvFrame) for f in frames)
+            return self._enqueued("detect_frames_yuv", out, check)
+        def new_deploy_buffers(self, B, max_out=None):
+            return (torch.zeros(B, self.rows if max_out is None else max_out, 6, dtype=torch.int32), torch.zeros(B, dtype=torch.int32))
+        def detect_deploy_frames(self, frames, thresh=0.3, nms_thresh=0.25, max_out=None, out=None, check=True):
+            assert max_out == out[0].shape[1]
+            return self._enqueued("detect_deploy_frames", out, check)
+        def new_tiled_buffers(self, F, max_out=300):
+            return (torch.zeros(F, max_out, 6), torch.zeros(F, max_out, dtype=torch.int32), torch.zeros(F, dtype=torch.int32))
+        def detect_tiled(self, frames, tiles=None, conf_thres=0.3, iou_thres=0.4, max_out=300, out=None, check=True, **kw):
+            assert tiles is not None and max_out == out[0].shape[1]
+            return self._enqueued("detect_tiled", out, check)
 
     current = [None]
     main = FakeStream()
@@ -714,6 +734,44 @@ def test_detect_pipeline_slot_rotation_and_ticket_rules(monkeypatch):
     pipe2.result(t0); pipe2.result(t1)                             # both earlier tickets still own their slots
     t2 = pipe2.submit(torch.ones(1, 1), 0.3, 0.4)                  # the word is cleared: the slot takes the next batch
     assert t2.slot == 0 and t2.serial == t1.serial + 1
+    # ... and the same three rules for every other submit*: `call(pipe, n)` submits a batch of n (frames; for submit_tiled n tiles of
+    # one frame, given or planned there: 8x8 in 4x4 tiles is 4 without overlap and 9 with 2 pixels of it)
+    frame = lambda: torch.zeros(8, 8, 3, dtype=torch.uint8)
+    planes = lambda: (torch.zeros(8, 8, dtype=torch.uint8), torch.zeros(4, 8, dtype=torch.uint8))
+    others = {
+        "submit_frames": ("detect_frames", lambda p, n: p.submit_frames([frame() for _ in range(n)], 0.3, 0.4), lambda n: (n, n, n)),
+        "submit_frames_yuv": ("detect_frames_yuv", lambda p, n: p.submit_frames_yuv([planes() for _ in range(n)], 0.3, 0.4), lambda n: (n, n, n)),
+        "submit_deploy_frames": ("detect_deploy_frames", lambda p, n: p.submit_deploy_frames([frame() for _ in range(n)], max_out=5), lambda n: (n, n)),
+        "submit_tiled": ("detect_tiled", lambda p, n: p.submit_tiled([frame()], 0.3, 0.4, tiles=[(0, 0, 0, 4, 4)] * n, max_out=9), lambda n: (1, 1, 1)),
+    }
+    for method, (native, call, rows_of) in others.items():
+        calls = lambda: [l for l in log if l[0] == native]
+        p3 = P.DetectPipeline("cpu", 352, 352, 80, 3, anchors=[1.0] * 12, max_batch=4, depth=2)
+        n0 = len(calls())
+        ts = [call(p3, n) for n in (2, 4, 1)]
+        assert [(t.slot, t.serial) for t in ts] == [(0, 1), (1, 2), (0, 3)], method
+        assert [p3.engines.index(l[1]) for l in calls()[n0:]] == [0, 1, 0], method                   # rotation
+        assert [p3.streams.index(l[2]) for l in calls()[n0:]] == [0, 1, 0], method                   # the slot's stream was current
+        assert [l[3] for l in calls()[n0:]] == [rows_of(2), rows_of(4), rows_of(1)], method          # the slot's buffers, one row per frame
+        assert all(s.waited and s.waited[0] == ("stream", main) for s in p3.streams), method
+        n_calls, last = len(calls()), list(p3._last)
+        with pytest.raises(ValueError, match="max_batch 4"):
+            call(p3, 5)                                                # above max_batch: refused ...
+        assert len(calls()) == n_calls and p3._last == last, method    # ... nothing enqueued, the rotation unmoved
+        p3.engines[1].tripped = True                                   # the next slot, 1 = ticket ts[1]'s batch
+        with pytest.raises(RuntimeError, match=r"DetectPipeline\.%s: the batch of ticket #%d " % (method, ts[1].serial)) as ei:
+            call(p3, 1)
+        assert ei.value.slot == 1 and ei.value.serial == ts[1].serial, method
+        assert len(calls()) == n_calls and p3._last == last, method
+        p3.result(ts[1]); p3.result(ts[2])                             # both tickets still own their slots
+        t3 = call(p3, 1)                                               # the word is cleared: the slot takes the next batch
+        assert (t3.slot, t3.serial) == (1, ts[2].serial + 1) and len(calls()) == n_calls + 1, method
+    p4 = P.DetectPipeline("cpu", 352, 352, 80, 3, anchors=[1.0] * 12, max_batch=4, depth=2)
+    n_tiled = sum(1 for l in log if l[0] == "detect_tiled")
+    assert p4.submit_tiled([frame()], 0.3, 0.4, tile=4, overlap=0).serial == 1        # planned in submit_tiled: 4 tiles fit max_batch
+    with pytest.raises(ValueError, match="9 tiles exceed max_batch 4"):
+        p4.submit_tiled([frame()], 0.3, 0.4, tile=4, overlap=2)
+    assert sum(1 for l in log if l[0] == "detect_tiled") == n_tiled + 1 and p4._last == [1, None]
 
 
 def test_bench_gpus_2_launches_itself(tmp_path):

@@ -1,27 +1,23 @@
 // yfv2_api_frames.hip - host side of libyfv2.so, the entry points that take caller frames: the resize, detection on ragged
 // batches of frames, and tiled detection (tile plan, merge, both in one call).  The handle and the shared plumbing: yfv2_ctx.h.
+// Frames come in two kinds, yfv2_frame (packed B, G, R) and yfv2_frame_yuv (4:2:0 planes).  Each kind is described once
+// (BgrFrames, YuvFrames: what differs); check_frames<Kind> turns a caller's batch into a FrameBatch, enqueue_resize resizes
+// one, and resize_frames / detect_frames / detect_tiled are one template each.  The extern "C" functions pass their names.
 #include <algorithm>
 #include <cmath>
 
 #include "yfv2_ctx.h"
 
-extern "C" {
-
-int yfv2_resize_u8(yfv2_handle h, const uint8_t* src, int32_t B, int32_t src_h, int32_t src_w, uint8_t* dst, void* stream) {
-  if (!h) return fail(nullptr, YFV2_ERR_ARG, "null handle");
-  if (!src || !dst || B < 1 || src_h < 1 || src_w < 1) return fail(h, YFV2_ERR_ARG, "yfv2_resize_u8: bad argument");
-  if ((reinterpret_cast<uintptr_t>(dst) & 3) != 0) return fail(h, YFV2_ERR_ARG, "yfv2_resize_u8: dst must be 4-byte aligned");
-  if (yfv2_resize_lds_bytes(src_w, h->cfg.width) > 160 * 1024 || (long long)B * h->cfg.height > 0x7fffffffll)
-    return fail(h, YFV2_ERR_ARG, "yfv2_resize_u8: source rows wider than " + std::to_string((160 * 1024 - 3 * h->cfg.width) / 6 - 2) + " pixels are not supported");
-  DeviceGuard guard(h->device);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  ResizeArgs a{};
-  a.src = src; a.dst = dst; a.B = B; a.SH = src_h; a.SW = src_w; a.H = h->cfg.height; a.W = h->cfg.width;
-  a.scale_x = 1.0 / ((double)a.W / (double)src_w);      // cv::resize: inv_scale = dsize / ssize, scale = 1 / inv_scale
-  a.scale_y = 1.0 / ((double)a.H / (double)src_h);
-  yfv2_launch_resize(a, s);
-  HIP_TRY(h, hipGetLastError());
-  return YFV2_OK;
+// The host doubles of a w x h frame resized to W x H, written once: every entry point, yfv2_resize_u8 included, takes them from
+// here, so a frame of a batch is resized bit for bit like that frame alone.  (This unit is built with the plain flags.)
+struct FrameScales { double scale_x, scale_y, box_x, box_y; };
+static FrameScales frame_scales(int w, int h, int W, int H) {
+  FrameScales s;
+  s.scale_x = 1.0 / ((double)W / (double)w);      // cv::resize: inv_scale = dsize / ssize, scale = 1 / inv_scale
+  s.scale_y = 1.0 / ((double)H / (double)h);
+  s.box_x = (double)w / (double)W;                // test.py:58  scale_w = w / cfg["width"]
+  s.box_y = (double)h / (double)H;
+  return s;
 }
 
 // what every entry point checks of a caller's frame; `at` = "<entry point>: frame <i>: "
@@ -31,93 +27,6 @@ static int check_frame(yfv2_handle h, const std::string& at, const yfv2_frame& f
   if (f.row_pitch < 3ll * f.width) return fail(h, YFV2_ERR_ARG, at + "row_pitch " + std::to_string(f.row_pitch) + " < 3 * width");
   return YFV2_OK;
 }
-
-// Ragged batches (yfv2_resize_frames_u8 / yfv2_detect_frames_u8): every frame is checked here, before anything is enqueued,
-// and expanded by its scales into t; *max_w = the widest frame (it sizes the resize launch's LDS).  The table is B entries of
-// the handle's max_batch, so B is bound by max_batch on both entry points.
-static int check_frames(yfv2_handle h, const char* what, const yfv2_frame* frames, int32_t B, std::vector<ResizeFrame>& t, int* max_w) {
-  const std::string w_ = what;
-  if (!frames) return fail(h, YFV2_ERR_ARG, w_ + ": null pointer");
-  if (B < 1) return fail(h, YFV2_ERR_ARG, w_ + ": B < 1");
-  if (B > h->cfg.max_batch)
-    return fail(h, YFV2_ERR_BATCH, w_ + ": batch " + std::to_string(B) + " above max_batch=" + std::to_string(h->cfg.max_batch));
-  const int H = h->cfg.height, W = h->cfg.width;
-  const int limit = (160 * 1024 - 3 * W) / 6 - 2;
-  t.assign((size_t)B, ResizeFrame{});
-  int mw = 1;
-  for (int32_t b = 0; b < B; ++b) {
-    const yfv2_frame& f = frames[b];
-    const std::string at = w_ + ": frame " + std::to_string(b) + ": ";
-    if (int rc = check_frame(h, at, f)) return rc;
-    if (f.width > limit || yfv2_resize_lds_bytes(f.width, W) > 160 * 1024)
-      return fail(h, YFV2_ERR_ARG, at + "frames wider than " + std::to_string(limit) + " pixels are not supported");
-    if (f.row_pitch > (1ll << 40) || (long long)(f.height - 1) * f.row_pitch > (1ll << 52))
-      return fail(h, YFV2_ERR_ARG, at + "row_pitch out of range");
-    ResizeFrame& r = t[(size_t)b];
-    r.data = f.data; r.pitch = f.row_pitch; r.h = f.height; r.w = f.width;
-    r.scale_x = 1.0 / ((double)W / (double)f.width);      // exactly yfv2_resize_u8's scales
-    r.scale_y = 1.0 / ((double)H / (double)f.height);
-    r.box_x = (double)f.width / (double)W;                // test.py:58  scale_w = w / cfg["width"]
-    r.box_y = (double)f.height / (double)H;
-    mw = std::max(mw, (int)f.width);
-  }
-  if ((long long)B * H > 0x7fffffffll) return fail(h, YFV2_ERR_ARG, w_ + ": batch too large");
-  *max_w = mw;
-  return YFV2_OK;
-}
-
-int yfv2_resize_frames_u8(yfv2_handle h, const yfv2_frame* frames, int32_t B, uint8_t* dst, void* stream) {
-  if (!h) return fail(nullptr, YFV2_ERR_ARG, "null handle");
-  if (!dst) return fail(h, YFV2_ERR_ARG, "yfv2_resize_frames_u8: null pointer");
-  if ((reinterpret_cast<uintptr_t>(dst) & 3) != 0) return fail(h, YFV2_ERR_ARG, "yfv2_resize_frames_u8: dst must be 4-byte aligned");
-  std::vector<ResizeFrame> t;
-  int max_w = 0;
-  int rc = check_frames(h, "yfv2_resize_frames_u8", frames, B, t, &max_w);
-  if (rc) return rc;
-  DeviceGuard guard(h->device);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  HIP_TRY(h, hipMemcpyAsync(h->d_frames, t.data(), sizeof(ResizeFrame) * (size_t)B, hipMemcpyHostToDevice, s));
-  yfv2_launch_resize_frames(h->d_frames, B, max_w, dst, h->cfg.height, h->cfg.width, s);
-  HIP_TRY(h, hipGetLastError());
-  return YFV2_OK;
-}
-
-// What yfv2_detect_frames_u8 and yfv2_detect_frames_yuv share once their frames are checked and expanded: the handle's resized
-// batch, the descriptor upload(s), ONE resize launch - the YUV one when `yuv` is given, which then reads its own table while
-// frame_boxes_kernel reads box_x / box_y from t - then yfv2_detect_u8 and the frame-coordinate epilogue.
-static int detect_frames_tail(yfv2_handle h, const std::vector<ResizeFrame>& t, const std::vector<ResizeFrameYuv>* yuv, int max_w, int32_t B,
-                              float conf_thres, double iou_thres, float* dets, int32_t* idx, int32_t* count, void* stream) {
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  DeviceGuard guard(h->device);
-  if (int rc2 = h->frames_u8.reserve(h, (size_t)h->cfg.height * h->cfg.width * 3 * (size_t)h->cfg.max_batch, true)) return rc2;   // the resized batch
-  HIP_TRY(h, hipMemcpyAsync(h->d_frames, t.data(), sizeof(ResizeFrame) * (size_t)B, hipMemcpyHostToDevice, s));
-  if (yuv) {
-    HIP_TRY(h, hipMemcpyAsync(h->d_frames_yuv, yuv->data(), sizeof(ResizeFrameYuv) * (size_t)B, hipMemcpyHostToDevice, s));
-    yfv2_launch_resize_frames_yuv(h->d_frames_yuv, B, max_w, h->frames_u8.as<uint8_t>(), h->cfg.height, h->cfg.width, s);
-  } else {
-    yfv2_launch_resize_frames(h->d_frames, B, max_w, h->frames_u8.as<uint8_t>(), h->cfg.height, h->cfg.width, s);
-  }
-  HIP_TRY(h, hipGetLastError());
-  int rc = yfv2_detect_u8(h, h->frames_u8.as<uint8_t>(), B, conf_thres, iou_thres, dets, idx, count, stream);
-  if (rc) return rc;
-  yfv2_launch_frame_boxes(dets, count, h->d_frames, B, s);
-  HIP_TRY(h, hipGetLastError());
-  return YFV2_OK;
-}
-
-int yfv2_detect_frames_u8(yfv2_handle h, const yfv2_frame* frames, int32_t B, float conf_thres, double iou_thres, float* dets,
-                          int32_t* idx, int32_t* count, void* stream) {
-  int rc = check_call(h, B, true);
-  if (rc) return rc;
-  if (!dets || !idx || !count) return fail(h, YFV2_ERR_ARG, "yfv2_detect_frames_u8: null pointer");
-  std::vector<ResizeFrame> t;
-  int max_w = 0;
-  rc = check_frames(h, "yfv2_detect_frames_u8", frames, B, t, &max_w);
-  if (rc) return rc;
-  return detect_frames_tail(h, t, nullptr, max_w, B, conf_thres, iou_thres, dets, idx, count, stream);
-}
-
-// ---- YUV 4:2:0 frames (kernel: resize_frames_yuv_kernel, yfv2_pre.hip) -------------------------------------------
 
 // what every YUV entry point checks of one caller's frame - a whole frame of yfv2_detect_tiled_yuv or a frame of a batch; `at` as in
 // check_frame.  The width limit is not here: it binds what is resized, which for a tiled frame are its tiles.
@@ -141,75 +50,168 @@ static int check_frame_yuv(yfv2_handle h, const std::string& at, const yfv2_fram
   return YFV2_OK;
 }
 
-// check_frames for yfv2_frame_yuv: every frame is checked here, before anything is enqueued, and expanded into the kernel's
-// descriptor (origin folded into the plane pointers, the scales of yfv2_resize_u8) and into t, of which frame_boxes_kernel reads
-// box_x / box_y; *max_w = the widest frame (it sizes the launch's LDS).
-static int check_frames_yuv(yfv2_handle h, const char* what, const yfv2_frame_yuv* frames, int32_t B, std::vector<ResizeFrame>& t,
-                            std::vector<ResizeFrameYuv>& ty, int* max_w) {
-  const std::string w_ = what;
-  if (!frames) return fail(h, YFV2_ERR_ARG, w_ + ": null pointer");
-  if (B < 1) return fail(h, YFV2_ERR_ARG, w_ + ": B < 1");
-  if (B > h->cfg.max_batch)
-    return fail(h, YFV2_ERR_BATCH, w_ + ": batch " + std::to_string(B) + " above max_batch=" + std::to_string(h->cfg.max_batch));
-  const int H = h->cfg.height, W = h->cfg.width;
-  const int limit = yfv2_resize_yuv_max_width(W);
-  t.assign((size_t)B, ResizeFrame{});
-  ty.assign((size_t)B, ResizeFrameYuv{});
-  int mw = 1;
-  for (int32_t b = 0; b < B; ++b) {
-    const yfv2_frame_yuv& f = frames[b];
-    const std::string at = w_ + ": frame " + std::to_string(b) + ": ";
-    if (int rc = check_frame_yuv(h, at, f)) return rc;
-    if (f.width > limit) return fail(h, YFV2_ERR_ARG, at + "frames wider than " + std::to_string(limit) + " pixels are not supported");
+// A checked and expanded batch: t for every kind (frame_boxes_kernel reads box_x / box_y from it; for B, G, R frames it is the
+// resize kernel's table too), yuv for YUV frames only (the resize kernel's table then); max_w sizes the resize launch's LDS.
+struct FrameBatch {
+  std::vector<ResizeFrame> t;
+  std::vector<ResizeFrameYuv> yuv;
+  int max_w = 1;
+};
+
+// ---- the two kinds: only what differs.  check = one caller frame (a whole frame of a tiled call too); max_width = the limit of
+// what is resized; expand = frame b of the batch into its device descriptor(s), after its own last check; crop = the frame that
+// a tile of `fr` is (the rectangle was checked).
+struct BgrFrames {
+  using Frame = yfv2_frame;
+  static int check(yfv2_handle h, const std::string& at, const Frame& f) { return check_frame(h, at, f); }
+  static int max_width(int W) { return yfv2_resize_max_width(W); }
+  static int expand(yfv2_handle h, const std::string& at, const Frame& f, FrameBatch& fb, size_t b) {
+    if (f.row_pitch > (1ll << 40) || (long long)(f.height - 1) * f.row_pitch > (1ll << 52))
+      return fail(h, YFV2_ERR_ARG, at + "row_pitch out of range");
+    fb.t[b].data = f.data; fb.t[b].pitch = f.row_pitch;
+    return YFV2_OK;
+  }
+  static Frame crop(const Frame& fr, const yfv2_tile& t) { return Frame{fr.data + (int64_t)t.y0 * fr.row_pitch + 3ll * t.x0, t.height, t.width, fr.row_pitch}; }
+};
+
+// (kernel: resize_frames_yuv_kernel, yfv2_pre.hip)  The descriptor has the origin folded into the plane pointers.
+struct YuvFrames {
+  using Frame = yfv2_frame_yuv;
+  static int check(yfv2_handle h, const std::string& at, const Frame& f) { return check_frame_yuv(h, at, f); }
+  static int max_width(int W) { return yfv2_resize_yuv_max_width(W); }
+  static int expand(yfv2_handle, const std::string&, const Frame& f, FrameBatch& fb, size_t b) {
+    if (fb.yuv.empty()) fb.yuv.assign(fb.t.size(), ResizeFrameYuv{});
     const bool planar = f.format == YFV2_YUV_I420;
-    ResizeFrameYuv& r = ty[(size_t)b];
+    ResizeFrameYuv& r = fb.yuv[b];
     const long long coff = (long long)(f.y0 >> 1) * f.pitch_c + (long long)(f.x0 >> 1) * (planar ? 1 : 2);
     r.y = f.y + (long long)f.y0 * f.pitch_y + f.x0;
     r.ca = f.u + coff;
     r.cb = planar ? f.v + coff : nullptr;
     r.pitch_y = f.pitch_y; r.pitch_c = f.pitch_c; r.h = f.height; r.w = f.width;
     r.px = f.x0 & 1; r.py = f.y0 & 1; r.format = f.format; r.coef = yfv2_yuv_coef(f.colour);
-    r.scale_x = 1.0 / ((double)W / (double)f.width);      // exactly yfv2_resize_u8's scales
-    r.scale_y = 1.0 / ((double)H / (double)f.height);
-    ResizeFrame& q = t[(size_t)b];
-    q.h = f.height; q.w = f.width; q.scale_x = r.scale_x; q.scale_y = r.scale_y;
-    q.box_x = (double)f.width / (double)W;                // test.py:58  scale_w = w / cfg["width"]
-    q.box_y = (double)f.height / (double)H;
-    mw = std::max(mw, (int)f.width);
+    r.scale_x = fb.t[b].scale_x; r.scale_y = fb.t[b].scale_y;
+    return YFV2_OK;
+  }
+  static Frame crop(const Frame& fr, const yfv2_tile& t) {
+    Frame c = fr;
+    c.x0 = fr.x0 + t.x0; c.y0 = fr.y0 + t.y0;     // (inside the frame, whose far corner is below 2^31)
+    c.width = t.width; c.height = t.height;
+    return c;
+  }
+};
+
+// Ragged batches: every frame is checked here, before anything is enqueued, and expanded by its scales into fb.  The tables are
+// B entries of the handle's max_batch, so B is bound by max_batch on every entry point.
+template <class Kind>
+static int check_frames(yfv2_handle h, const char* what, const typename Kind::Frame* frames, int32_t B, FrameBatch& fb) {
+  const std::string w_ = what;
+  if (!frames) return fail(h, YFV2_ERR_ARG, w_ + ": null pointer");
+  if (B < 1) return fail(h, YFV2_ERR_ARG, w_ + ": B < 1");
+  if (B > h->cfg.max_batch)
+    return fail(h, YFV2_ERR_BATCH, w_ + ": batch " + std::to_string(B) + " above max_batch=" + std::to_string(h->cfg.max_batch));
+  const int H = h->cfg.height, W = h->cfg.width;
+  const int limit = Kind::max_width(W);
+  fb.t.assign((size_t)B, ResizeFrame{});
+  for (int32_t b = 0; b < B; ++b) {
+    const typename Kind::Frame& f = frames[b];
+    const std::string at = w_ + ": frame " + std::to_string(b) + ": ";
+    if (int rc = Kind::check(h, at, f)) return rc;
+    if (f.width > limit) return fail(h, YFV2_ERR_ARG, at + "frames wider than " + std::to_string(limit) + " pixels are not supported");
+    const FrameScales s = frame_scales(f.width, f.height, W, H);
+    ResizeFrame& r = fb.t[(size_t)b];
+    r.h = f.height; r.w = f.width; r.scale_x = s.scale_x; r.scale_y = s.scale_y; r.box_x = s.box_x; r.box_y = s.box_y;
+    if (int rc = Kind::expand(h, at, f, fb, (size_t)b)) return rc;
+    fb.max_w = std::max(fb.max_w, (int)f.width);
   }
   if ((long long)B * H > 0x7fffffffll) return fail(h, YFV2_ERR_ARG, w_ + ": batch too large");
-  *max_w = mw;
   return YFV2_OK;
 }
 
-int yfv2_resize_frames_yuv(yfv2_handle h, const yfv2_frame_yuv* frames, int32_t B, uint8_t* dst, void* stream) {
-  if (!h) return fail(nullptr, YFV2_ERR_ARG, "null handle");
-  if (!dst) return fail(h, YFV2_ERR_ARG, "yfv2_resize_frames_yuv: null pointer");
-  if ((reinterpret_cast<uintptr_t>(dst) & 3) != 0) return fail(h, YFV2_ERR_ARG, "yfv2_resize_frames_yuv: dst must be 4-byte aligned");
-  std::vector<ResizeFrame> t;
-  std::vector<ResizeFrameYuv> ty;
-  int max_w = 0;
-  int rc = check_frames_yuv(h, "yfv2_resize_frames_yuv", frames, B, t, ty, &max_w);
-  if (rc) return rc;
-  DeviceGuard guard(h->device);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  HIP_TRY(h, hipMemcpyAsync(h->d_frames_yuv, ty.data(), sizeof(ResizeFrameYuv) * (size_t)B, hipMemcpyHostToDevice, s));
-  yfv2_launch_resize_frames_yuv(h->d_frames_yuv, B, max_w, dst, h->cfg.height, h->cfg.width, s);
+// Uploads the table the resize kernel of the batch's kind reads and enqueues that ONE launch into dst; everything was checked.
+static int enqueue_resize(yfv2_handle h, const FrameBatch& fb, int32_t B, uint8_t* dst, hipStream_t s) {
+  if (fb.yuv.empty()) {
+    HIP_TRY(h, hipMemcpyAsync(h->d_frames, fb.t.data(), sizeof(ResizeFrame) * (size_t)B, hipMemcpyHostToDevice, s));
+    yfv2_launch_resize_frames(h->d_frames, B, fb.max_w, dst, h->cfg.height, h->cfg.width, s);
+  } else {
+    HIP_TRY(h, hipMemcpyAsync(h->d_frames_yuv, fb.yuv.data(), sizeof(ResizeFrameYuv) * (size_t)B, hipMemcpyHostToDevice, s));
+    yfv2_launch_resize_frames_yuv(h->d_frames_yuv, B, fb.max_w, dst, h->cfg.height, h->cfg.width, s);
+  }
   HIP_TRY(h, hipGetLastError());
   return YFV2_OK;
 }
 
+template <class Kind>
+static int resize_frames(yfv2_handle h, const char* what, const typename Kind::Frame* frames, int32_t B, uint8_t* dst, void* stream) {
+  if (!h) return fail(nullptr, YFV2_ERR_ARG, "null handle");
+  if (!dst) return fail(h, YFV2_ERR_ARG, std::string(what) + ": null pointer");
+  if ((reinterpret_cast<uintptr_t>(dst) & 3) != 0) return fail(h, YFV2_ERR_ARG, std::string(what) + ": dst must be 4-byte aligned");
+  FrameBatch fb;
+  if (int rc = check_frames<Kind>(h, what, frames, B, fb)) return rc;
+  DeviceGuard guard(h->device);
+  return enqueue_resize(h, fb, B, dst, static_cast<hipStream_t>(stream));
+}
+
+// What every detection on frames does once they are checked and expanded: the handle's resized batch, the resize, then
+// yfv2_detect_u8 and the frame-coordinate epilogue.  frame_boxes_kernel reads box_x / box_y from d_frames: the B, G, R resize
+// has uploaded that table as its own, the YUV resize reads another, so a YUV batch uploads it here.
+static int detect_frames_tail(yfv2_handle h, const FrameBatch& fb, int32_t B, float conf_thres, double iou_thres, float* dets, int32_t* idx,
+                              int32_t* count, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DeviceGuard guard(h->device);
+  if (int rc = h->frames_u8.reserve(h, (size_t)h->cfg.height * h->cfg.width * 3 * (size_t)h->cfg.max_batch, true)) return rc;   // the resized batch
+  if (!fb.yuv.empty()) HIP_TRY(h, hipMemcpyAsync(h->d_frames, fb.t.data(), sizeof(ResizeFrame) * (size_t)B, hipMemcpyHostToDevice, s));
+  if (int rc = enqueue_resize(h, fb, B, h->frames_u8.as<uint8_t>(), s)) return rc;
+  if (int rc = yfv2_detect_u8(h, h->frames_u8.as<uint8_t>(), B, conf_thres, iou_thres, dets, idx, count, stream)) return rc;
+  yfv2_launch_frame_boxes(dets, count, h->d_frames, B, s);
+  HIP_TRY(h, hipGetLastError());
+  return YFV2_OK;
+}
+
+template <class Kind>
+static int detect_frames(yfv2_handle h, const char* what, const typename Kind::Frame* frames, int32_t B, float conf_thres, double iou_thres,
+                         float* dets, int32_t* idx, int32_t* count, void* stream) {
+  if (int rc = check_call(h, B, true)) return rc;
+  if (!dets || !idx || !count) return fail(h, YFV2_ERR_ARG, std::string(what) + ": null pointer");
+  FrameBatch fb;
+  if (int rc = check_frames<Kind>(h, what, frames, B, fb)) return rc;
+  return detect_frames_tail(h, fb, B, conf_thres, iou_thres, dets, idx, count, stream);
+}
+
+extern "C" {
+
+int yfv2_resize_u8(yfv2_handle h, const uint8_t* src, int32_t B, int32_t src_h, int32_t src_w, uint8_t* dst, void* stream) {
+  if (!h) return fail(nullptr, YFV2_ERR_ARG, "null handle");
+  if (!src || !dst || B < 1 || src_h < 1 || src_w < 1) return fail(h, YFV2_ERR_ARG, "yfv2_resize_u8: bad argument");
+  if ((reinterpret_cast<uintptr_t>(dst) & 3) != 0) return fail(h, YFV2_ERR_ARG, "yfv2_resize_u8: dst must be 4-byte aligned");
+  if (yfv2_resize_lds_bytes(src_w, h->cfg.width) > (size_t)YFV2_LDS_FULL || (long long)B * h->cfg.height > 0x7fffffffll)
+    return fail(h, YFV2_ERR_ARG, "yfv2_resize_u8: source rows wider than " + std::to_string(yfv2_resize_max_width(h->cfg.width)) + " pixels are not supported");
+  DeviceGuard guard(h->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const FrameScales sc = frame_scales(src_w, src_h, h->cfg.width, h->cfg.height);
+  ResizeArgs a{};
+  a.src = src; a.dst = dst; a.B = B; a.SH = src_h; a.SW = src_w; a.H = h->cfg.height; a.W = h->cfg.width;
+  a.scale_x = sc.scale_x; a.scale_y = sc.scale_y;
+  yfv2_launch_resize(a, s);
+  HIP_TRY(h, hipGetLastError());
+  return YFV2_OK;
+}
+
+int yfv2_resize_frames_u8(yfv2_handle h, const yfv2_frame* frames, int32_t B, uint8_t* dst, void* stream) {
+  return resize_frames<BgrFrames>(h, "yfv2_resize_frames_u8", frames, B, dst, stream);
+}
+
+int yfv2_resize_frames_yuv(yfv2_handle h, const yfv2_frame_yuv* frames, int32_t B, uint8_t* dst, void* stream) {
+  return resize_frames<YuvFrames>(h, "yfv2_resize_frames_yuv", frames, B, dst, stream);
+}
+
+int yfv2_detect_frames_u8(yfv2_handle h, const yfv2_frame* frames, int32_t B, float conf_thres, double iou_thres, float* dets,
+                          int32_t* idx, int32_t* count, void* stream) {
+  return detect_frames<BgrFrames>(h, "yfv2_detect_frames_u8", frames, B, conf_thres, iou_thres, dets, idx, count, stream);
+}
+
 int yfv2_detect_frames_yuv(yfv2_handle h, const yfv2_frame_yuv* frames, int32_t B, float conf_thres, double iou_thres, float* dets,
                            int32_t* idx, int32_t* count, void* stream) {
-  int rc = check_call(h, B, true);
-  if (rc) return rc;
-  if (!dets || !idx || !count) return fail(h, YFV2_ERR_ARG, "yfv2_detect_frames_yuv: null pointer");
-  std::vector<ResizeFrame> t;
-  std::vector<ResizeFrameYuv> ty;
-  int max_w = 0;
-  rc = check_frames_yuv(h, "yfv2_detect_frames_yuv", frames, B, t, ty, &max_w);
-  if (rc) return rc;
-  return detect_frames_tail(h, t, &ty, max_w, B, conf_thres, iou_thres, dets, idx, count, stream);
+  return detect_frames<YuvFrames>(h, "yfv2_detect_frames_yuv", frames, B, conf_thres, iou_thres, dets, idx, count, stream);
 }
 
 // ---- tiled detection ----------------------------------------------------------------------------------
@@ -309,35 +311,37 @@ int yfv2_merge_tiles(yfv2_handle h, const float* tile_dets, const int32_t* tile_
   return enqueue_merge(h, tile_dets, tile_count, table, T, F, merge_thres, merge_metric, max_out, dets, src, count, static_cast<hipStream_t>(stream));
 }
 
-// yfv2_detect_tiled_u8 and yfv2_detect_tiled_yuv: the frame type and four things that depend on it - the check of one frame, its
-// size, the crop of it that a tile is, and the check + detection of the T crops (check_only: everything the detect entry point
-// checks, before the workspaces are touched; it checks again when it runs: host work only).
-extern "C++" template <class Frame, class CheckFrame, class SizeOf, class CropOf, class DetectCrops>
-static int detect_tiled_impl(yfv2_handle h, const std::string& w_, const Frame* frames, int32_t F, const yfv2_tile* tiles, int32_t T, float conf_thres,
-                             double iou_thres, double merge_thres, int32_t merge_metric, int32_t max_out, float* dets, int32_t* src, int32_t* count,
-                             void* stream, CheckFrame check_one, SizeOf size_of, CropOf crop_of, DetectCrops detect_crops) {
+}  // extern "C"
+
+// yfv2_detect_tiled_u8 and yfv2_detect_tiled_yuv.  Every check comes first, in this order: the pointers, T, the merge arguments,
+// each whole frame, each tile rectangle, the call, then the crops as the batch they are - checked and expanded ONCE, and handed
+// to the detect tail as that batch.  Only then are the workspaces touched and anything enqueued.
+template <class Kind>
+static int detect_tiled(yfv2_handle h, const char* what, const typename Kind::Frame* frames, int32_t F, const yfv2_tile* tiles, int32_t T, float conf_thres,
+                        double iou_thres, double merge_thres, int32_t merge_metric, int32_t max_out, float* dets, int32_t* src, int32_t* count, void* stream) {
+  const std::string w_ = what;
   if (!h) return fail(nullptr, YFV2_ERR_ARG, "null handle");
   if (!frames || !tiles || !dets || !count) return fail(h, YFV2_ERR_ARG, w_ + ": null pointer");
   if (T > h->cfg.max_batch)
     return fail(h, YFV2_ERR_BATCH, w_ + ": " + std::to_string(T) + " tiles above max_batch=" + std::to_string(h->cfg.max_batch));
   std::vector<int32_t> table;
-  if (int rc = check_merge(h, w_.c_str(), tiles, T, F, merge_thres, merge_metric, max_out, table)) return rc;
+  if (int rc = check_merge(h, what, tiles, T, F, merge_thres, merge_metric, max_out, table)) return rc;
   for (int32_t f = 0; f < F; ++f)
-    if (int rc = check_one(w_ + ": frame " + std::to_string(f) + ": ", frames[f])) return rc;
-  std::vector<Frame> crops((size_t)T);
+    if (int rc = Kind::check(h, w_ + ": frame " + std::to_string(f) + ": ", frames[f])) return rc;
+  std::vector<typename Kind::Frame> crops((size_t)T);
   for (int32_t k = 0; k < T; ++k) {
     const yfv2_tile& t = tiles[k];
-    const Frame& fr = frames[t.frame];
-    int32_t fw = 0, fh = 0;
-    size_of(fr, &fw, &fh);
+    const typename Kind::Frame& fr = frames[t.frame];
+    const int32_t fw = fr.width, fh = fr.height;
     if (t.width < 1 || t.height < 1 || t.x0 < 0 || t.y0 < 0 || (int64_t)t.x0 + t.width > fw || (int64_t)t.y0 + t.height > fh)
       return fail(h, YFV2_ERR_ARG, w_ + ": tile " + std::to_string(k) + ": [" + std::to_string(t.x0) + ", " + std::to_string((int64_t)t.x0 + t.width) +
                                        ") x [" + std::to_string(t.y0) + ", " + std::to_string((int64_t)t.y0 + t.height) + ") is not a rectangle of at least one pixel inside its " +
                                        std::to_string(fw) + " x " + std::to_string(fh) + " frame");
-    crops[(size_t)k] = crop_of(fr, t);
+    crops[(size_t)k] = Kind::crop(fr, t);
   }
   if (int rc = check_call(h, T, true)) return rc;
-  if (int rc = detect_crops(crops.data(), true, nullptr, nullptr, nullptr)) return rc;
+  FrameBatch fb;
+  if (int rc = check_frames<Kind>(h, what, crops.data(), T, fb)) return rc;
   DeviceGuard guard(h->device);
   const size_t mb = (size_t)h->cfg.max_batch;
   if (int rc = h->tile_out.reserve(h, sizeof(float) * mb * YFV2_MAX_DET * 6 + sizeof(int32_t) * (mb * YFV2_MAX_DET + mb), true)) return rc;
@@ -345,49 +349,20 @@ static int detect_tiled_impl(yfv2_handle h, const std::string& w_, const Frame* 
   float* t_dets = h->tile_out.as<float>();
   int32_t* t_idx = reinterpret_cast<int32_t*>(t_dets + mb * YFV2_MAX_DET * 6);
   int32_t* t_count = t_idx + mb * YFV2_MAX_DET;
-  if (int rc = detect_crops(crops.data(), false, t_dets, t_idx, t_count)) return rc;
+  if (int rc = detect_frames_tail(h, fb, T, conf_thres, iou_thres, t_dets, t_idx, t_count, stream)) return rc;
   return enqueue_merge(h, t_dets, t_count, table, T, F, merge_thres, merge_metric, max_out, dets, src, count, static_cast<hipStream_t>(stream));
 }
 
+extern "C" {
+
 int yfv2_detect_tiled_u8(yfv2_handle h, const yfv2_frame* frames, int32_t F, const yfv2_tile* tiles, int32_t T, float conf_thres, double iou_thres,
                          double merge_thres, int32_t merge_metric, int32_t max_out, float* dets, int32_t* src, int32_t* count, void* stream) {
-  const char* what = "yfv2_detect_tiled_u8";
-  return detect_tiled_impl(
-      h, what, frames, F, tiles, T, conf_thres, iou_thres, merge_thres, merge_metric, max_out, dets, src, count, stream,
-      [&](const std::string& at, const yfv2_frame& f) { return check_frame(h, at, f); },
-      [](const yfv2_frame& f, int32_t* w, int32_t* hh) { *w = f.width; *hh = f.height; },
-      [](const yfv2_frame& fr, const yfv2_tile& t) { return yfv2_frame{fr.data + (int64_t)t.y0 * fr.row_pitch + 3ll * t.x0, t.height, t.width, fr.row_pitch}; },
-      [&](const yfv2_frame* crops, bool check_only, float* t_dets, int32_t* t_idx, int32_t* t_count) {
-        if (!check_only) return yfv2_detect_frames_u8(h, crops, T, conf_thres, iou_thres, t_dets, t_idx, t_count, stream);
-        std::vector<ResizeFrame> t;
-        int max_w = 0;
-        return check_frames(h, what, crops, T, t, &max_w);
-      });
+  return detect_tiled<BgrFrames>(h, "yfv2_detect_tiled_u8", frames, F, tiles, T, conf_thres, iou_thres, merge_thres, merge_metric, max_out, dets, src, count, stream);
 }
 
 int yfv2_detect_tiled_yuv(yfv2_handle h, const yfv2_frame_yuv* frames, int32_t F, const yfv2_tile* tiles, int32_t T, float conf_thres, double iou_thres,
                           double merge_thres, int32_t merge_metric, int32_t max_out, float* dets, int32_t* src, int32_t* count, void* stream) {
-  const char* what = "yfv2_detect_tiled_yuv";
-  auto check_crops = [&](const yfv2_frame_yuv* crops, int32_t n) {
-    std::vector<ResizeFrame> t;
-    std::vector<ResizeFrameYuv> ty;
-    int max_w = 0;
-    return check_frames_yuv(h, what, crops, n, t, ty, &max_w);
-  };
-  return detect_tiled_impl(
-      h, what, frames, F, tiles, T, conf_thres, iou_thres, merge_thres, merge_metric, max_out, dets, src, count, stream,
-      [&](const std::string& at, const yfv2_frame_yuv& f) { return check_frame_yuv(h, at, f); },
-      [](const yfv2_frame_yuv& f, int32_t* w, int32_t* hh) { *w = f.width; *hh = f.height; },
-      [](const yfv2_frame_yuv& fr, const yfv2_tile& t) {
-        yfv2_frame_yuv c = fr;
-        c.x0 = fr.x0 + t.x0; c.y0 = fr.y0 + t.y0;     // (inside the frame, whose far corner is below 2^31)
-        c.width = t.width; c.height = t.height;
-        return c;
-      },
-      [&](const yfv2_frame_yuv* crops, bool check_only, float* t_dets, int32_t* t_idx, int32_t* t_count) {
-        if (!check_only) return yfv2_detect_frames_yuv(h, crops, T, conf_thres, iou_thres, t_dets, t_idx, t_count, stream);
-        return check_crops(crops, T);
-      });
+  return detect_tiled<YuvFrames>(h, "yfv2_detect_tiled_yuv", frames, F, tiles, T, conf_thres, iou_thres, merge_thres, merge_metric, max_out, dets, src, count, stream);
 }
 
 // ---- the ncnn sample's path (kernels: yfv2_deploy.hip) ----------------------------------------------------
@@ -475,9 +450,8 @@ int yfv2_detect_deploy_frames_u8(yfv2_handle h, const yfv2_frame* frames, int32_
   int rc = check_call(h, B, true);
   if (rc) return rc;
   if ((rc = check_deploy(h, "yfv2_detect_deploy_frames_u8", thresh, boxes, count, max_out))) return rc;
-  std::vector<ResizeFrame> t;
-  int max_w = 0;
-  if ((rc = check_frames(h, "yfv2_detect_deploy_frames_u8", frames, B, t, &max_w))) return rc;
+  FrameBatch fb;
+  if ((rc = check_frames<BgrFrames>(h, "yfv2_detect_deploy_frames_u8", frames, B, fb))) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   DeviceGuard guard(h->device);
   const size_t mb = (size_t)h->cfg.max_batch;
@@ -490,10 +464,8 @@ int yfv2_detect_deploy_frames_u8(yfv2_handle h, const yfv2_frame* frames, int32_
     sc[(size_t)2 * b + 1] = (float)frames[b].height / (float)h->cfg.height;
   }
   float* d_scale = reinterpret_cast<float*>(h->deploy_word.as<char>() + 16);
-  HIP_TRY(h, hipMemcpyAsync(h->d_frames, t.data(), sizeof(ResizeFrame) * (size_t)B, hipMemcpyHostToDevice, s));
   HIP_TRY(h, hipMemcpyAsync(d_scale, sc.data(), sizeof(float) * sc.size(), hipMemcpyHostToDevice, s));
-  yfv2_launch_resize_frames(h->d_frames, B, max_w, h->frames_u8.as<uint8_t>(), h->cfg.height, h->cfg.width, s);
-  HIP_TRY(h, hipGetLastError());
+  if ((rc = enqueue_resize(h, fb, B, h->frames_u8.as<uint8_t>(), s))) return rc;
   float* out6[6];
   for (int i = 0; i < 6; ++i) out6[i] = h->ws.logits[i].p;
   if ((rc = yfv2_forward_u8(h, h->frames_u8.as<uint8_t>(), B, out6, stream))) return rc;   // (on the handle's lanes where the plan has them)

@@ -489,7 +489,7 @@ bool yfv2_s1chain_supported(int c2, int H, int W) {
   if (c2 != 48 || H < 2 || (H & 1) || (W & 1)) return false;
   if ((H / 2) * (W / 2) > 16 * 8) return false;            // one 2x2 patch per (wave, lane & 15): 8 waves
   if (yfv2_s1chain_park_floats(H, W, 7) > 24L * (4 * H) * (4 * W)) return false;   // the park scratch is a stem-sized temporary (yfv2_plan.h: Workspace::t1)
-  return s1chain_lds_floats(H, W) * 4 <= 160 * 1024;
+  return s1chain_lds_floats(H, W) * 4 <= YFV2_LDS_FULL;
 }
 
 bool yfv2_launch_block_s1chain(const BlockS1Args& a, hipStream_t s) {
@@ -813,7 +813,7 @@ static long s1pool_lds_floats(int H, int W, bool pre) { return (long)H * W * P96
 int yfv2_s1pool_image_floats(bool presplit) { return presplit ? P96_IMGP_FL : P96_IMG_FL; }
 bool yfv2_s1pool_supported(int c2, int H, int W) {
   if (c2 != P96_C2 || H * W > P96_MAXPX || H * W < 1) return false;
-  return s1pool_lds_floats(H, W, true) * 4 <= 160 * 1024;
+  return s1pool_lds_floats(H, W, true) * 4 <= YFV2_LDS_FULL;
 }
 
 bool yfv2_launch_block_s1pool(const BlockS1Args& a, hipStream_t s) {

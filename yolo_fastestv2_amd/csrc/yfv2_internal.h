@@ -479,6 +479,7 @@ struct ResizeArgs {
   double scale_x, scale_y;   // 1 / (W / SW), 1 / (H / SH) in double, like cv::resize derives them
 };
 size_t yfv2_resize_lds_bytes(int SW, int W);
+int yfv2_resize_max_width(int W);   // the width limit of the ragged B, G, R entry points: (YFV2_LDS_FULL - 3 W) / 6 - 2
 void yfv2_launch_resize(const ResizeArgs& a, hipStream_t s);
 // one frame of a ragged batch (yfv2_resize_frames_u8 / yfv2_detect_frames_u8), expanded on the host and uploaded as a table
 struct ResizeFrame {

@@ -36,6 +36,23 @@ __device__ __forceinline__ RowCoef yfv2_axis_coef(int d, double scale, int n, bo
   return r;
 }
 
+// One channel of one output pixel from its four taps (row s0 / s1 x column sx0 / sx1): the horizontal pass of each row, then the
+// vertical pass and the clamp.  Every kernel below blends with this one expression.
+__device__ __forceinline__ unsigned char yfv2_blend(int t00, int t01, int t10, int t11, const RowCoef& rx, const RowCoef& ry) {
+  const int S0 = t00 * rx.c0 + t01 * rx.c1;
+  const int S1 = t10 * rx.c0 + t11 * rx.c1;
+  const int v = (((ry.c0 * (S0 >> 4)) >> 16) + ((ry.c1 * (S1 >> 4)) >> 16) + 2) >> 2;
+  return (unsigned char)min(max(v, 0), 255);
+}
+
+// The output row assembled in OUT (LDS) leaves as aligned dwords: the barrier behind the blend, then row oy of image b of dst.
+template <int THREADS>
+__device__ __forceinline__ void yfv2_emit_row(const unsigned char* OUT, unsigned char* dst, int b, int oy, int H, int W) {
+  __syncthreads();
+  unsigned* drow = reinterpret_cast<unsigned*>(dst + ((size_t)b * H + oy) * W * 3);
+  for (int i = threadIdx.x; i < (W * 3) >> 2; i += THREADS) drow[i] = reinterpret_cast<const unsigned*>(OUT)[i];
+}
+
 __global__ __launch_bounds__(256) void resize_u8_kernel(ResizeArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x;
@@ -78,16 +95,10 @@ __global__ __launch_bounds__(256) void resize_u8_kernel(ResizeArgs a) {
   for (int ox = tid; ox < a.W; ox += 256) {
     const RowCoef rx = yfv2_axis_coef(ox, a.scale_x, a.SW, true);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const int S0 = (int)r0[rx.s0 * 3 + c] * rx.c0 + (int)r0[rx.s1 * 3 + c] * rx.c1;
-      const int S1 = (int)r1[rx.s0 * 3 + c] * rx.c0 + (int)r1[rx.s1 * 3 + c] * rx.c1;
-      const int v = (((ry.c0 * (S0 >> 4)) >> 16) + ((ry.c1 * (S1 >> 4)) >> 16) + 2) >> 2;
-      OUT[ox * 3 + c] = (unsigned char)min(max(v, 0), 255);
-    }
+    for (int c = 0; c < 3; ++c)
+      OUT[ox * 3 + c] = yfv2_blend(r0[rx.s0 * 3 + c], r0[rx.s1 * 3 + c], r1[rx.s0 * 3 + c], r1[rx.s1 * 3 + c], rx, ry);
   }
-  __syncthreads();
-  unsigned* drow = reinterpret_cast<unsigned*>(a.dst + ((size_t)b * a.H + oy) * a.W * 3);
-  for (int i = tid; i < (a.W * 3) >> 2; i += 256) drow[i] = reinterpret_cast<const unsigned*>(OUT)[i];
+  yfv2_emit_row<256>(OUT, a.dst, b, oy, a.H, a.W);
 }
 
 // The same resize for a batch of frames of DIFFERENT sizes (yfv2_resize_frames_u8): frame b's descriptor (pointer, size, row
@@ -145,16 +156,10 @@ __global__ __launch_bounds__(RF_THREADS, 6) void resize_frames_u8_kernel(const R
   for (int ox = tid; ox < W; ox += RF_THREADS) {
     const RowCoef rx = yfv2_axis_coef(ox, f.scale_x, f.w, true);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const int S0 = (int)r0[rx.s0 * 3 + c] * rx.c0 + (int)r0[rx.s1 * 3 + c] * rx.c1;
-      const int S1 = (int)r1[rx.s0 * 3 + c] * rx.c0 + (int)r1[rx.s1 * 3 + c] * rx.c1;
-      const int v = (((ry.c0 * (S0 >> 4)) >> 16) + ((ry.c1 * (S1 >> 4)) >> 16) + 2) >> 2;
-      OUT[ox * 3 + c] = (unsigned char)min(max(v, 0), 255);
-    }
+    for (int c = 0; c < 3; ++c)
+      OUT[ox * 3 + c] = yfv2_blend(r0[rx.s0 * 3 + c], r0[rx.s1 * 3 + c], r1[rx.s0 * 3 + c], r1[rx.s1 * 3 + c], rx, ry);
   }
-  __syncthreads();
-  unsigned* drow = reinterpret_cast<unsigned*>(dst + ((size_t)b * H + oy) * W * 3);
-  for (int i = tid; i < (W * 3) >> 2; i += RF_THREADS) drow[i] = reinterpret_cast<const unsigned*>(OUT)[i];
+  yfv2_emit_row<RF_THREADS>(OUT, dst, b, oy, H, W);
 }
 
 // ---- the same ragged batch from decoder-format frames: YUV 4:2:0 planes read in place (yfv2_resize_frames_yuv) ----
@@ -300,19 +305,17 @@ __global__ __launch_bounds__(RY_THREADS, 8) void resize_frames_yuv_kernel(const 
     yfv2_yuv_to_bgr(y1[rx.s0], pu1[j0], pv1[j0], kc, p10);
     yfv2_yuv_to_bgr(y1[rx.s1], pu1[j1], pv1[j1], kc, p11);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const int S0 = (int)p00[c] * rx.c0 + (int)p01[c] * rx.c1;
-      const int S1 = (int)p10[c] * rx.c0 + (int)p11[c] * rx.c1;
-      const int v = (((ry.c0 * (S0 >> 4)) >> 16) + ((ry.c1 * (S1 >> 4)) >> 16) + 2) >> 2;
-      OUT[ox * 3 + c] = (unsigned char)min(max(v, 0), 255);
-    }
+    for (int c = 0; c < 3; ++c) OUT[ox * 3 + c] = yfv2_blend(p00[c], p01[c], p10[c], p11[c], rx, ry);
   }
-  __syncthreads();
-  unsigned* drow = reinterpret_cast<unsigned*>(dst + ((size_t)b * H + oy) * W * 3);
-  for (int i = tid; i < (W * 3) >> 2; i += RY_THREADS) drow[i] = reinterpret_cast<const unsigned*>(OUT)[i];
+  yfv2_emit_row<RY_THREADS>(OUT, dst, b, oy, H, W);
 }
 
 size_t yfv2_resize_lds_bytes(int SW, int W) { return 2 * (size_t)((SW * 3 + 6) & ~3) + (size_t)W * 3; }
+
+// The width limit the ragged B, G, R entry points enforce and yfv2_resize_u8's message names, in closed form.  For W % 4 == 0 it is
+// one pixel below the widest row whose yfv2_resize_lds_bytes fits YFV2_LDS_FULL (27128 against 27129 at W = 352); yfv2_resize_u8
+// itself tests the bytes, so it admits that one pixel more than its message says.
+int yfv2_resize_max_width(int W) { return (YFV2_LDS_FULL - 3 * W) / 6 - 2; }
 
 // resize_frames_yuv_kernel's LDS for a frame w pixels wide: two luma slots, two chroma rows of two half-slots, the output row
 size_t yfv2_resize_yuv_lds_bytes(int w, int W) { return 2 * (size_t)((w + 6) & ~3) + 4 * (size_t)(((w >> 1) + 7) & ~3) + (size_t)W * 3; }
@@ -329,22 +332,15 @@ int yfv2_resize_yuv_max_width(int W) {
 }
 
 void yfv2_launch_resize(const ResizeArgs& a, hipStream_t s) {
-  const size_t lds = yfv2_resize_lds_bytes(a.SW, a.W);
-  static std::atomic<unsigned long long> lds_ok0{0};
-  yfv2_allow_lds(yfv2_device(), reinterpret_cast<const void*>(&resize_u8_kernel), YFV2_LDS_FULL, lds_ok0);
-  hipLaunchKernelGGL(resize_u8_kernel, dim3((unsigned)(a.B * a.H)), dim3(256), lds, s, a);
+  YFV2_LAUNCH_LDS(yfv2_device(), resize_u8_kernel, YFV2_LDS_FULL, dim3((unsigned)(a.B * a.H)), dim3(256), yfv2_resize_lds_bytes(a.SW, a.W), s, a);
 }
 
 void yfv2_launch_resize_frames(const ResizeFrame* frames, int B, int max_w, unsigned char* dst, int H, int W, hipStream_t s) {
-  const size_t lds = yfv2_resize_lds_bytes(max_w, W);
-  static std::atomic<unsigned long long> lds_ok0{0};
-  yfv2_allow_lds(yfv2_device(), reinterpret_cast<const void*>(&resize_frames_u8_kernel), YFV2_LDS_FULL, lds_ok0);
-  hipLaunchKernelGGL(resize_frames_u8_kernel, dim3((unsigned)(B * H)), dim3(RF_THREADS), lds, s, frames, dst, H, W);
+  YFV2_LAUNCH_LDS(yfv2_device(), resize_frames_u8_kernel, YFV2_LDS_FULL, dim3((unsigned)(B * H)), dim3(RF_THREADS), yfv2_resize_lds_bytes(max_w, W), s,
+                  frames, dst, H, W);
 }
 
 void yfv2_launch_resize_frames_yuv(const ResizeFrameYuv* frames, int B, int max_w, unsigned char* dst, int H, int W, hipStream_t s) {
-  const size_t lds = yfv2_resize_yuv_lds_bytes(max_w, W);
-  static std::atomic<unsigned long long> lds_ok0{0};
-  yfv2_allow_lds(yfv2_device(), reinterpret_cast<const void*>(&resize_frames_yuv_kernel), YFV2_LDS_FULL, lds_ok0);
-  hipLaunchKernelGGL(resize_frames_yuv_kernel, dim3((unsigned)(B * H)), dim3(RY_THREADS), lds, s, frames, dst, H, W);
+  YFV2_LAUNCH_LDS(yfv2_device(), resize_frames_yuv_kernel, YFV2_LDS_FULL, dim3((unsigned)(B * H)), dim3(RY_THREADS), yfv2_resize_yuv_lds_bytes(max_w, W), s,
+                  frames, dst, H, W);
 }

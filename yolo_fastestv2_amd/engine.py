@@ -263,19 +263,62 @@ class Engine:
             arr[i].row_pitch = f.stride(0) if h > 1 else 3 * w
         return arr, keep
 
-    def resize_frames(self, frames, out=None):
-        """A list of uint8 (h_i, w_i, 3) frames of any sizes on the GPU -> uint8 (B, height, width, 3): `resize` for a batch whose frames
-        differ in size (test.py:34-35 per frame, include/yfv2.h yfv2_resize_frames_u8).  Frame b's output is bit-identical to
-        resize() of that frame alone.  Grows max_batch like every batched call (the descriptor table has max_batch entries)."""
-        arr, keep = self._frame_table(frames)
+    def _yuv_table(self, frames):
+        return yuv.frame_table(frames, self.device)
+
+    # The bodies of the frame entry points, one per operation.  `table`: self._frame_table or self._yuv_table, frames -> (the native
+    # array, what it points into); `native`: the library function of that frame kind; `name`: the public method, for messages.
+    def _resize_frames(self, table, native, frames, out):
+        arr, keep = table(frames)
         B = len(keep)
         self.ensure_batch(B)
         if out is None:
             out = torch.empty((B, self.height, self.width, 3), device=self.device, dtype=torch.uint8)
         elif out.dtype != torch.uint8 or tuple(out.shape) != (B, self.height, self.width, 3) or out.device != self.device or not out.is_contiguous():
             raise ValueError("out must be a contiguous uint8 (%d,%d,%d,3) tensor on %s" % (B, self.height, self.width, self.device))
-        check(_lib.lib().yfv2_resize_frames_u8(self._h, arr, B, _ptr(out), _stream(self.device)), self._h)
+        check(native(self._h, arr, B, _ptr(out), _stream(self.device)), self._h)
         return out
+
+    def _detect_frames(self, name, table, native, frames, conf_thres, iou_thres, out, check):
+        self._need_anchors(name)
+        if check and self.peek_nonfinite():
+            self.check_finite("%s (an earlier call on this handle)" % name)
+        arr, keep = table(frames)
+        B = len(keep)
+        self.ensure_batch(B)
+        dets, idx, cnt = out if out is not None else self.new_det_buffers(B)
+        _lib.check(native(self._h, arr, B, float(conf_thres), float(iou_thres), _ptr(dets), _ptr(idx), _ptr(cnt), _stream(self.device)), self._h)
+        return dets, idx, cnt
+
+    def _detect_tiled(self, name, table, native, size_of, frames, tiles, conf_thres, iou_thres, merge_thres, metric, max_out, tile, overlap,
+                      include_full, out, check):
+        """size_of: a kept frame -> (height, width), what the tile plan needs"""
+        self._need_anchors(name)
+        code = tiling.metric_code(metric)
+        max_out = int(max_out)
+        if not 1 <= max_out <= 4096:
+            raise ValueError("max_out must be in 1..4096, got %d" % max_out)
+        if merge_thres is None:
+            merge_thres = iou_thres
+        if check and self.peek_nonfinite():
+            self.check_finite("%s (an earlier call on this handle)" % name)
+        farr, keep = table(frames)
+        F = len(keep)
+        if tiles is None:
+            tiles = [t for f, fr in enumerate(keep) for t in tiling.plan_tiles(*size_of(fr), tile, overlap, include_full, frame=f)]
+        tarr = tiling.tile_table(tiles)
+        T = len(tarr)
+        self.ensure_batch(T)
+        dets, src, cnt = self._tiled_out(out, F, max_out)
+        _lib.check(native(self._h, farr, F, tarr, T, float(conf_thres), float(iou_thres), float(merge_thres), code, max_out,
+                          _ptr(dets), _ptr(src) if src is not None else None, _ptr(cnt), _stream(self.device)), self._h)
+        return dets, src, cnt
+
+    def resize_frames(self, frames, out=None):
+        """A list of uint8 (h_i, w_i, 3) frames of any sizes on the GPU -> uint8 (B, height, width, 3): `resize` for a batch whose frames
+        differ in size (test.py:34-35 per frame, include/yfv2.h yfv2_resize_frames_u8).  Frame b's output is bit-identical to
+        resize() of that frame alone.  Grows max_batch like every batched call (the descriptor table has max_batch entries)."""
+        return self._resize_frames(self._frame_table, _lib.lib().yfv2_resize_frames_u8, frames, out)
 
     def detect_frames(self, frames, conf_thres, iou_thres, out=None, check=True):
         """test.py:34-35,58-68 for a batch of frames of any sizes: resize each uint8 (h_i, w_i, 3) device frame to (height, width)
@@ -283,16 +326,7 @@ class Engine:
         in double and rounded to fp32, as test.py:58-68 does with its Python floats (no clipping).  Returns (dets, idx, cnt) like
         detect(), dets in frame coordinates; conf, class, idx, cnt are what detect() returns for the resized batch.  Enqueue only:
         nothing waits for the device (the first call on a handle allocates its resize buffer and waits once); check= as in detect()."""
-        self._need_anchors("detect_frames")
-        if check and self.peek_nonfinite():
-            self.check_finite("detect_frames (an earlier call on this handle)")
-        arr, keep = self._frame_table(frames)
-        B = len(keep)
-        self.ensure_batch(B)
-        dets, idx, cnt = out if out is not None else self.new_det_buffers(B)
-        _lib.check(_lib.lib().yfv2_detect_frames_u8(self._h, arr, B, float(conf_thres), float(iou_thres), _ptr(dets), _ptr(idx), _ptr(cnt),
-                                                    _stream(self.device)), self._h)
-        return dets, idx, cnt
+        return self._detect_frames("detect_frames", self._frame_table, _lib.lib().yfv2_detect_frames_u8, frames, conf_thres, iou_thres, out, check)
 
     # ---- tiled detection of large frames (include/yfv2.h yfv2_merge_tiles / yfv2_detect_tiled_u8; DESIGN.md 4.11) ----------------
     def new_tiled_buffers(self, F, max_out=MAX_DET):
@@ -343,80 +377,27 @@ class Engine:
         object cut by a tile edge with its whole view next door).  Returns (dets (F, max_out, 6), src (F, max_out), count (F));
         src = tile * 300 + row in that tile's detections.  The number of tiles is this call's batch: max_batch grows to it.
         Enqueue only (the first call on a handle allocates its tile workspaces and waits once); check= as in detect()."""
-        self._need_anchors("detect_tiled")
-        code = tiling.metric_code(metric)
-        max_out = int(max_out)
-        if not 1 <= max_out <= 4096:
-            raise ValueError("max_out must be in 1..4096, got %d" % max_out)
-        if merge_thres is None:
-            merge_thres = iou_thres
-        if check and self.peek_nonfinite():
-            self.check_finite("detect_tiled (an earlier call on this handle)")
-        farr, keep = self._frame_table(frames)
-        F = len(keep)
-        if tiles is None:
-            tiles = [t for f, fr in enumerate(keep) for t in tiling.plan_tiles(int(fr.shape[0]), int(fr.shape[1]), tile, overlap, include_full, frame=f)]
-        tarr = tiling.tile_table(tiles)
-        T = len(tarr)
-        self.ensure_batch(T)
-        dets, src, cnt = self._tiled_out(out, F, max_out)
-        _lib.check(_lib.lib().yfv2_detect_tiled_u8(self._h, farr, F, tarr, T, float(conf_thres), float(iou_thres), float(merge_thres), code, max_out,
-                                                   _ptr(dets), _ptr(src) if src is not None else None, _ptr(cnt), _stream(self.device)), self._h)
-        return dets, src, cnt
+        return self._detect_tiled("detect_tiled", self._frame_table, _lib.lib().yfv2_detect_tiled_u8, lambda fr: (int(fr.shape[0]), int(fr.shape[1])),
+                                  frames, tiles, conf_thres, iou_thres, merge_thres, metric, max_out, tile, overlap, include_full, out, check)
 
     # ---- decoder-format frames: YUV 4:2:0 planes read in place (include/yfv2.h yfv2_*_yuv; DESIGN.md 4.15) -----------------------
     def resize_frames_yuv(self, frames, out=None):
         """`resize_frames` for a list of yuv.YuvFrame (NV12 / NV21 / I420 planes on the GPU, any sizes, crops by x0 / y0 / width / height;
         a bare (y, uv) or (y, u, v) tuple is NV12 / I420 in BT.601 limited range).  The output is bit-identical to resize_frames of the
         frames converted to B, G, R by the integer formula of include/yfv2.h; no converted frame is ever written."""
-        arr, keep = yuv.frame_table(frames, self.device)
-        B = len(keep)
-        self.ensure_batch(B)
-        if out is None:
-            out = torch.empty((B, self.height, self.width, 3), device=self.device, dtype=torch.uint8)
-        elif out.dtype != torch.uint8 or tuple(out.shape) != (B, self.height, self.width, 3) or out.device != self.device or not out.is_contiguous():
-            raise ValueError("out must be a contiguous uint8 (%d,%d,%d,3) tensor on %s" % (B, self.height, self.width, self.device))
-        check(_lib.lib().yfv2_resize_frames_yuv(self._h, arr, B, _ptr(out), _stream(self.device)), self._h)
-        return out
+        return self._resize_frames(self._yuv_table, _lib.lib().yfv2_resize_frames_yuv, frames, out)
 
     def detect_frames_yuv(self, frames, conf_thres, iou_thres, out=None, check=True):
         """`detect_frames` for a list of yuv.YuvFrame: the same path with the resize launch reading the YUV planes.  Bit-identical to
         detect_frames on the converted frames.  Enqueue only; check= as in detect()."""
-        self._need_anchors("detect_frames_yuv")
-        if check and self.peek_nonfinite():
-            self.check_finite("detect_frames_yuv (an earlier call on this handle)")
-        arr, keep = yuv.frame_table(frames, self.device)
-        B = len(keep)
-        self.ensure_batch(B)
-        dets, idx, cnt = out if out is not None else self.new_det_buffers(B)
-        _lib.check(_lib.lib().yfv2_detect_frames_yuv(self._h, arr, B, float(conf_thres), float(iou_thres), _ptr(dets), _ptr(idx), _ptr(cnt),
-                                                     _stream(self.device)), self._h)
-        return dets, idx, cnt
+        return self._detect_frames("detect_frames_yuv", self._yuv_table, _lib.lib().yfv2_detect_frames_yuv, frames, conf_thres, iou_thres, out, check)
 
     def detect_tiled_yuv(self, frames, tiles=None, conf_thres=0.3, iou_thres=0.4, merge_thres=None, metric="iou", max_out=MAX_DET,
                          tile=(352, 352), overlap=(64, 64), include_full=False, out=None, check=True):
         """`detect_tiled` for a list of yuv.YuvFrame: a tile is its frame's descriptor moved by the tile's origin, so tiles of any
         parity are read in place.  Bit-identical to detect_tiled on the converted frames; same arguments and results."""
-        self._need_anchors("detect_tiled_yuv")
-        code = tiling.metric_code(metric)
-        max_out = int(max_out)
-        if not 1 <= max_out <= 4096:
-            raise ValueError("max_out must be in 1..4096, got %d" % max_out)
-        if merge_thres is None:
-            merge_thres = iou_thres
-        if check and self.peek_nonfinite():
-            self.check_finite("detect_tiled_yuv (an earlier call on this handle)")
-        farr, keep = yuv.frame_table(frames, self.device)
-        F = len(keep)
-        if tiles is None:
-            tiles = [t for f, fr in enumerate(keep) for t in tiling.plan_tiles(fr.height, fr.width, tile, overlap, include_full, frame=f)]
-        tarr = tiling.tile_table(tiles)
-        T = len(tarr)
-        self.ensure_batch(T)
-        dets, src, cnt = self._tiled_out(out, F, max_out)
-        _lib.check(_lib.lib().yfv2_detect_tiled_yuv(self._h, farr, F, tarr, T, float(conf_thres), float(iou_thres), float(merge_thres), code, max_out,
-                                                    _ptr(dets), _ptr(src) if src is not None else None, _ptr(cnt), _stream(self.device)), self._h)
-        return dets, src, cnt
+        return self._detect_tiled("detect_tiled_yuv", self._yuv_table, _lib.lib().yfv2_detect_tiled_yuv, lambda fr: (fr.height, fr.width),
+                                  frames, tiles, conf_thres, iou_thres, merge_thres, metric, max_out, tile, overlap, include_full, out, check)
 
     # ---- the ncnn sample's deployment path (include/yfv2.h yfv2_export_maps / yfv2_deploy_post; DESIGN.md 4.14) ------------------
     def map_shapes(self, B):

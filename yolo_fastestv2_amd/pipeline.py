@@ -66,13 +66,13 @@ class DetectPipeline:
         with torch.cuda.stream(self.streams[j]):
             yield j, self.engines[j], self.buffers[j]
 
-    def submit(self, x, conf_thres, iou_thres, wait_for_input=True):
-        """Enqueue forward + decode + NMS of one batch (fp32 (B,3,H,W) or uint8 (B,H,W,3) on the device, B <= max_batch) on the next
-        slot.  wait_for_input: order the slot's stream behind the CURRENT stream first (x was produced there); pass False for an
-        input that is already complete - the wait costs a few microseconds of bubble per batch."""
-        B = int(x.shape[0])
-        if B > self.max_batch:
-            raise ValueError("batch %d exceeds max_batch %d" % (B, self.max_batch))
+    def _submit(self, name, n, too_many, inputs, wait_for_input, run):
+        """What every submit* does around its engine call: bound the batch (n <= max_batch, else ValueError(too_many % (n, max_batch))),
+        look at the next slot's range guard, take the slot, order its stream behind the readers of its buffers and - wait_for_input -
+        behind the current stream, on which `inputs` (tensors) were produced, then run(j, engine, buffers) -> the ticket's tensors
+        with the slot's stream current, and mark the end with an event.  `name`: the public method, for messages."""
+        if n > self.max_batch:
+            raise ValueError(too_many % (n, self.max_batch))
         cur = torch.cuda.current_stream(self.device)
         # The slot's previous batch may have tripped the range guard.  Looked at BEFORE the rotation advances: the error then names that
         # batch's ticket, which stays valid (its buffers are not overwritten - nothing is enqueued for the new batch), and the caller
@@ -82,11 +82,11 @@ class DetectPipeline:
         if self.engines[jn].peek_nonfinite():
             try:
                 with torch.cuda.stream(self.streams[jn]):
-                    self.engines[jn].check_finite("DetectPipeline.submit: the batch of ticket #%s (slot %d), the last one run on this slot" % (self._last[jn], jn))
+                    self.engines[jn].check_finite("DetectPipeline.%s: the batch of ticket #%s (slot %d), the last one run on this slot" % (name, self._last[jn], jn))
             except Exception as e:
                 e.slot, e.serial = jn, self._last[jn]
                 raise
-        with self.slot() as (j, eng, (dets, idx, cnt)):
+        with self.slot() as (j, eng, bufs):
             # write-after-read: streams that result() ordered behind this slot's previous batch may still be reading its
             # detection buffers - the slot's stream waits for the marks they left before it overwrites them
             for ev in self._readers[j]:
@@ -94,101 +94,48 @@ class DetectPipeline:
             self._readers[j] = []
             if wait_for_input:
                 self.streams[j].wait_stream(cur)
-                x.record_stream(self.streams[j])
-            out = eng.detect(x, conf_thres, iou_thres, out=(dets[:B], idx[:B], cnt[:B]), check=False)
+                for t in inputs:
+                    t.record_stream(self.streams[j])
+            out = run(j, eng, bufs)
             ev = torch.cuda.Event()
             ev.record(self.streams[j])
         return Ticket(j, ev, out, self._serial)
+
+    def submit(self, x, conf_thres, iou_thres, wait_for_input=True):
+        """Enqueue forward + decode + NMS of one batch (fp32 (B,3,H,W) or uint8 (B,H,W,3) on the device, B <= max_batch) on the next
+        slot.  wait_for_input: order the slot's stream behind the CURRENT stream first (x was produced there); pass False for an
+        input that is already complete - the wait costs a few microseconds of bubble per batch."""
+        B = int(x.shape[0])
+        return self._submit("submit", B, "batch %d exceeds max_batch %d", [x], wait_for_input,
+                            lambda j, eng, bufs: eng.detect(x, conf_thres, iou_thres, out=tuple(b[:B] for b in bufs), check=False))
 
     def submit_frames(self, frames, conf_thres, iou_thres, wait_for_input=True):
         """`submit` for a list of uint8 (h_i, w_i, 3) device frames of any sizes (Engine.detect_frames: resize, detect, boxes in frame
         coordinates) on the next slot; len(frames) <= max_batch."""
         B = len(frames)
-        if B > self.max_batch:
-            raise ValueError("batch %d exceeds max_batch %d" % (B, self.max_batch))
-        cur = torch.cuda.current_stream(self.device)
-        jn = self._serial % self.depth
-        if self.engines[jn].peek_nonfinite():     # as in submit(): the slot's previous batch, before the rotation advances
-            try:
-                with torch.cuda.stream(self.streams[jn]):
-                    self.engines[jn].check_finite("DetectPipeline.submit_frames: the batch of ticket #%s (slot %d), the last one run on this slot" % (self._last[jn], jn))
-            except Exception as e:
-                e.slot, e.serial = jn, self._last[jn]
-                raise
-        with self.slot() as (j, eng, (dets, idx, cnt)):
-            for ev in self._readers[j]:
-                self.streams[j].wait_event(ev)
-            self._readers[j] = []
-            if wait_for_input:
-                self.streams[j].wait_stream(cur)
-                for f in frames:
-                    f.record_stream(self.streams[j])
-            out = eng.detect_frames(frames, conf_thres, iou_thres, out=(dets[:B], idx[:B], cnt[:B]), check=False)
-            ev = torch.cuda.Event()
-            ev.record(self.streams[j])
-        return Ticket(j, ev, out, self._serial)
+        return self._submit("submit_frames", B, "batch %d exceeds max_batch %d", frames, wait_for_input,
+                            lambda j, eng, bufs: eng.detect_frames(frames, conf_thres, iou_thres, out=tuple(b[:B] for b in bufs), check=False))
 
     def submit_frames_yuv(self, frames, conf_thres, iou_thres, wait_for_input=True):
         """`submit_frames` for a list of yuv.YuvFrame (Engine.detect_frames_yuv: the planes a decoder wrote, read in place) on the next
         slot; len(frames) <= max_batch."""
         frames = [yuv.as_frame(f) for f in frames]
         B = len(frames)
-        if B > self.max_batch:
-            raise ValueError("batch %d exceeds max_batch %d" % (B, self.max_batch))
-        cur = torch.cuda.current_stream(self.device)
-        jn = self._serial % self.depth
-        if self.engines[jn].peek_nonfinite():     # as in submit(): the slot's previous batch, before the rotation advances
-            try:
-                with torch.cuda.stream(self.streams[jn]):
-                    self.engines[jn].check_finite("DetectPipeline.submit_frames_yuv: the batch of ticket #%s (slot %d), the last one run on this slot" % (self._last[jn], jn))
-            except Exception as e:
-                e.slot, e.serial = jn, self._last[jn]
-                raise
-        with self.slot() as (j, eng, (dets, idx, cnt)):
-            for ev in self._readers[j]:
-                self.streams[j].wait_event(ev)
-            self._readers[j] = []
-            if wait_for_input:
-                self.streams[j].wait_stream(cur)
-                for f in frames:
-                    for p in f.planes:
-                        p.record_stream(self.streams[j])
-            out = eng.detect_frames_yuv(frames, conf_thres, iou_thres, out=(dets[:B], idx[:B], cnt[:B]), check=False)
-            ev = torch.cuda.Event()
-            ev.record(self.streams[j])
-        return Ticket(j, ev, out, self._serial)
+        return self._submit("submit_frames_yuv", B, "batch %d exceeds max_batch %d", [p for f in frames for p in f.planes], wait_for_input,
+                            lambda j, eng, bufs: eng.detect_frames_yuv(frames, conf_thres, iou_thres, out=tuple(b[:B] for b in bufs), check=False))
 
     def submit_deploy_frames(self, frames, thresh=0.3, nms_thresh=0.25, max_out=None, wait_for_input=True):
         """`submit_frames` on the ncnn sample's path (Engine.detect_deploy_frames: resize, forward, export maps, the sample's integer-box
         post-process) on the next slot.  The ticket's tensors are (boxes (B, max_out, 6) int32, count (B)), owned by the slot."""
         B = len(frames)
-        if B > self.max_batch:
-            raise ValueError("batch %d exceeds max_batch %d" % (B, self.max_batch))
-        cur = torch.cuda.current_stream(self.device)
-        jn = self._serial % self.depth
-        if self.engines[jn].peek_nonfinite():     # as in submit(): the slot's previous batch, before the rotation advances
-            try:
-                with torch.cuda.stream(self.streams[jn]):
-                    self.engines[jn].check_finite("DetectPipeline.submit_deploy_frames: the batch of ticket #%s (slot %d), the last one run on this slot" % (self._last[jn], jn))
-            except Exception as e:
-                e.slot, e.serial = jn, self._last[jn]
-                raise
-        with self.slot() as (j, eng, _):
-            for ev in self._readers[j]:
-                self.streams[j].wait_event(ev)
-            self._readers[j] = []
-            if wait_for_input:
-                self.streams[j].wait_stream(cur)
-                for f in frames:
-                    f.record_stream(self.streams[j])
-            max_out = eng.rows if max_out is None else int(max_out)
-            if self._deploy_buffers[j] is None or self._deploy_buffers[j][0].shape[1] != max_out:
-                self._deploy_buffers[j] = eng.new_deploy_buffers(self.max_batch, max_out)
+
+        def run(j, eng, _):
+            n_out = eng.rows if max_out is None else int(max_out)
+            if self._deploy_buffers[j] is None or self._deploy_buffers[j][0].shape[1] != n_out:
+                self._deploy_buffers[j] = eng.new_deploy_buffers(self.max_batch, n_out)
             boxes, cnt = self._deploy_buffers[j]
-            out = eng.detect_deploy_frames(frames, thresh, nms_thresh, max_out=max_out, out=(boxes[:B], cnt[:B]), check=False)
-            ev = torch.cuda.Event()
-            ev.record(self.streams[j])
-        return Ticket(j, ev, out, self._serial)
+            return eng.detect_deploy_frames(frames, thresh, nms_thresh, max_out=n_out, out=(boxes[:B], cnt[:B]), check=False)
+        return self._submit("submit_deploy_frames", B, "batch %d exceeds max_batch %d", frames, wait_for_input, run)
 
     def submit_tiled(self, frames, conf_thres, iou_thres, wait_for_input=True, **tiled):
         """`submit` for large frames cut into tiles (Engine.detect_tiled; `tiled`: its keyword arguments tiles, merge_thres, metric, max_out,
@@ -199,33 +146,13 @@ class DetectPipeline:
         if tiled.get("tiles") is None:      # planned here: the number of tiles is the batch, and a slot's handle does not grow
             plan = {k: tiled.pop(k) for k in ("tile", "overlap", "include_full") if k in tiled}
             tiled["tiles"] = [t for f, fr in enumerate(frames) for t in tiling.plan_tiles(int(fr.shape[0]), int(fr.shape[1]), frame=f, **plan)]
-        T = len(tiled["tiles"])
-        if T > self.max_batch:
-            raise ValueError("%d tiles exceed max_batch %d" % (T, self.max_batch))
-        cur = torch.cuda.current_stream(self.device)
-        jn = self._serial % self.depth
-        if self.engines[jn].peek_nonfinite():     # as in submit(): the slot's previous batch, before the rotation advances
-            try:
-                with torch.cuda.stream(self.streams[jn]):
-                    self.engines[jn].check_finite("DetectPipeline.submit_tiled: the batch of ticket #%s (slot %d), the last one run on this slot" % (self._last[jn], jn))
-            except Exception as e:
-                e.slot, e.serial = jn, self._last[jn]
-                raise
-        with self.slot() as (j, eng, _):
-            for ev in self._readers[j]:
-                self.streams[j].wait_event(ev)
-            self._readers[j] = []
-            if wait_for_input:
-                self.streams[j].wait_stream(cur)
-                for f in frames:
-                    f.record_stream(self.streams[j])
+
+        def run(j, eng, _):
             F, max_out = len(frames), int(tiled.pop("max_out", 300))
             if self._tiled_buffers[j] is None or tuple(self._tiled_buffers[j][0].shape[:2]) != (F, max_out):
                 self._tiled_buffers[j] = eng.new_tiled_buffers(F, max_out)      # (allocated on the slot's stream, reused while the shape repeats)
-            out = eng.detect_tiled(frames, conf_thres=conf_thres, iou_thres=iou_thres, max_out=max_out, out=self._tiled_buffers[j], check=False, **tiled)
-            ev = torch.cuda.Event()
-            ev.record(self.streams[j])
-        return Ticket(j, ev, out, self._serial)
+            return eng.detect_tiled(frames, conf_thres=conf_thres, iou_thres=iou_thres, max_out=max_out, out=self._tiled_buffers[j], check=False, **tiled)
+        return self._submit("submit_tiled", len(tiled["tiles"]), "%d tiles exceed max_batch %d", frames, wait_for_input, run)
 
     def result(self, ticket, host=False):
         """(dets, idx, cnt) of a ticket.  Orders the current stream behind the batch (host=True: blocks the host instead)."""
