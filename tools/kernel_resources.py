@@ -1,16 +1,16 @@
 #!/usr/bin/env python3
-"""Register / spill table of every kernel of one or more translation units (hipcc -Rpass-analysis=kernel-resource-usage):
-usage: python tools/kernel_resources.py yfv2_block yfv2_stage2h ... [--filter substring]"""
-import re, subprocess, sys, os
+"""Register / spill table of every kernel of one or more translation units (hipcc -Rpass-analysis=kernel-resource-usage), compiled
+with the unit's own flags: the command line is the one csrc/Makefile's %.s rule prints (make -n), plus the remark flag.
+usage: python tools/kernel_resources.py yfv2_block yfv2_stage2h ... [--filter=substring]"""
+import re, shlex, subprocess, sys, os
 CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "yolo_fastestv2_amd", "csrc")
 args = [a for a in sys.argv[1:] if not a.startswith("--")]
 flt = [a.split("=", 1)[1] for a in sys.argv[1:] if a.startswith("--filter=")]
 for unit in args:
-    extra = ["-ffp-contract=off"] if unit in ("yfv2_post", "yfv2_loss", "yfv2_train") else []
-    cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++20", "-fPIC", "-fvisibility=hidden", "-Wno-unused-variable",
-           "-Wno-unused-but-set-variable", "-Wno-cuda-compat", *extra, "-c", os.path.join(CSRC, unit + ".hip"), "-o", "/dev/null",
-           "-Rpass-analysis=kernel-resource-usage"]
-    out = subprocess.run(cmd, capture_output=True, text=True).stderr
+    dry = subprocess.run(["make", "-C", CSRC, "--no-print-directory", "-n", "-B", unit + ".s"], capture_output=True, text=True, check=True).stdout
+    cmd = shlex.split([l for l in dry.splitlines() if " -S " in l][-1])
+    cmd[cmd.index("-o") + 1] = "/dev/null"
+    out = subprocess.run(cmd + ["-Rpass-analysis=kernel-resource-usage"], capture_output=True, text=True, cwd=CSRC).stderr
     cur = None
     rows = {}
     for line in out.splitlines():

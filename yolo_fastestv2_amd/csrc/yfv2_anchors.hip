@@ -15,7 +15,7 @@
 // restatement of this tree that the GPU results are compared with bit for bit.
 #include <float.h>
 
-#include "yfv2_internal.h"
+#include "yfv2_device.h"
 
 namespace {
 
@@ -25,14 +25,7 @@ constexpr int KM_MAXK = YFV2_KM_MAXK;
 
 typedef double f64x2u __attribute__((ext_vector_type(2), aligned(8)));   // a (w, h) pair at any 8-byte address: one 16-byte load
 
-// the fold of 64 lane values described above.  Lane l adds the value of lane l ^ off; addition commutes bit for bit, so the two
-// partners hold the same number after every step and lane 0 ends with the tree over (l, l + off)
-template <typename T>
-__device__ __forceinline__ T km_wave_fold(T v) {
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
+// (the fold of 64 lane values described above is wave_fold, yfv2_device.h)
 
 // 1 - IoU of two boxes that share a corner, evaluated through the reference's four cases in its order of tests, each with its
 // own formula (genanchors.py:23-30): the box inside the centroid, the two ways of crossing, the centroid inside the box.
@@ -86,7 +79,7 @@ __global__ __launch_bounds__(KM_THREADS) void km_assign_kernel(KmArgs a, int fir
     double v = best_s[0];
 #pragma unroll
     for (int i = 1; i < KM_PER; ++i) v += best_s[i];
-    v = km_wave_fold(v);
+    v = wave_fold(v);
     if (lane == 0) s_sum[2 * k][wave] = v;
   }
   for (int j = 0; j < k; ++j) {
@@ -98,8 +91,8 @@ __global__ __launch_bounds__(KM_THREADS) void km_assign_kernel(KmArgs a, int fir
       sh += asg[i] == j ? h[i] : 0.0;
       cnt += __popcll(__ballot(asg[i] == j));
     }
-    sw = km_wave_fold(sw);
-    sh = km_wave_fold(sh);
+    sw = wave_fold(sw);
+    sh = wave_fold(sh);
     if (lane == 0) { s_sum[j][wave] = sw; s_sum[k + j][wave] = sh; s_cnt[j][wave] = cnt; }
   }
   {
@@ -125,7 +118,7 @@ __global__ __launch_bounds__(KM_THREADS) void km_final_kernel(KmArgs a, int pass
     const double* src = a.part_sum + (int64_t)q * nch;
     double v = 0.0;
     for (int64_t c = tid; c < nch; c += KM_THREADS) v += src[c];
-    v = km_wave_fold(v);
+    v = wave_fold(v);
     if (lane == 0) s_sum[q][wave] = v;
   }
   for (int q = 0; q < k + 2; ++q) {
@@ -137,7 +130,7 @@ __global__ __launch_bounds__(KM_THREADS) void km_final_kernel(KmArgs a, int pass
       const int bit = q == k ? 1 : 2;
       for (int64_t c = tid; c < nch; c += KM_THREADS) v += (a.part_flag[c] & bit) ? 1 : 0;
     }
-    v = km_wave_fold(v);
+    v = wave_fold(v);
     if (lane == 0) s_int[q][wave] = v;
   }
   __syncthreads();

@@ -28,7 +28,7 @@
 // template parameter selects where the bit comes from and which result block and chunk-sum set are written, nothing else, so
 // slice k is what the single-threshold call computes from tp = bit k.  n_gt and the bad-input word exist once, in block 0.
 #include "../../include/yfv2.h"
-#include "yfv2_internal.h"
+#include "yfv2_device.h"
 
 namespace {
 
@@ -202,12 +202,6 @@ __global__ __launch_bounds__(AP_THREADS) void ap_scatter_kernel(ApArgs a, int pa
   }
 }
 
-template <typename T>
-__device__ __forceinline__ T ap_wave_fold(T v) {   // yfv2_anchors.hip's fold: lane 0 ends with the tree over (l, l + off)
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 // ---- K thresholds: the callers' masks in rank order, bits at and above K cleared
 __global__ __launch_bounds__(AP_THREADS) void ap_permute_kernel(ApArgs a) {
@@ -243,7 +237,7 @@ __global__ __launch_bounds__(AP_THREADS) void ap_curve_kernel(ApArgs a) {
 
   long long total = 0;
   for (int64_t i = tid; i < n_p; i += AP_THREADS) total += (v[i] >> sh) & 1u;
-  total = ap_wave_fold(total);
+  total = wave_fold(total);
   if (lane == 0) s_tp[wave] = total;
   __syncthreads();
   total = s_tp[0] + s_tp[1] + s_tp[2] + s_tp[3];
@@ -307,7 +301,7 @@ __global__ __launch_bounds__(AP_THREADS) void ap_curve_kernel(ApArgs a) {
     double t = term[0];
 #pragma unroll
     for (int r = 1; r < AP_ROWS; ++r) t += term[r];
-    t = ap_wave_fold(t);
+    t = wave_fold(t);
     if (lane == 0) s_sum[wave] = t;
     carry_env = fmax(carry_env, chunk_max);
     after = before;

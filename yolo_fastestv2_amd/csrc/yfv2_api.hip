@@ -442,7 +442,7 @@ static int post_impl(yfv2_handle h, const float* const out6[6], int32_t B, float
   return YFV2_OK;
 }
 
-// the sticky range-guard word of the fp16x3 plan (yfv2_internal.h Yfv2Watch): waits for `stream`, reports and clears it
+// the sticky range-guard word of the fp16x3 plan (Yfv2Watch, yfv2_device.h): waits for `stream`, reports and clears it
 int yfv2_nonfinite(yfv2_handle h, int32_t* flag, void* stream) {
   if (!h || !flag) return fail(h, YFV2_ERR_ARG, "yfv2_nonfinite: null argument");
   if (!h->nonfinite.host) return fail(h, YFV2_ERR_STATE, "yfv2_nonfinite: this handle owns no guard word");

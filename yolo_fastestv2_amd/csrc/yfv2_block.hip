@@ -18,11 +18,7 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "yfv2_internal.h"
-
-typedef _Float16 yfv2_h4c __attribute__((ext_vector_type(4)));
-typedef _Float16 yfv2_h8c __attribute__((ext_vector_type(8)));
-typedef unsigned yfv2_u2c __attribute__((ext_vector_type(2)));
+#include "yfv2_device.h"
 
 template <int C2>
 struct S1Cfg {
@@ -30,10 +26,6 @@ struct S1Cfg {
   static constexpr int DW_FL = 9 * KC * 16;  // depthwise taps [9][KC*16]
   static constexpr int CST_FL = 6 * KC * 16; // sc1, sh1, scd, shd, sc2, sh2
 };
-
-#define YFV2_STAMP(i) do { if (a.trace && blockIdx.x == 0 && threadIdx.x == 0) a.trace[i] = (long long)__builtin_readcyclecounter(); } while (0)
-// per-wave stamps of workgroup 0 (YFV2_TRACE=1, tools/trace_waves.py): trace[64 + 32 * wave + i]
-#define YFV2_WSTAMP(i) do { if (a.trace && blockIdx.x == 0 && (threadIdx.x & 63) == 0) a.trace[64 + 32 * (threadIdx.x >> 6) + (i)] = (long long)__builtin_readcyclecounter(); } while (0)
 
 // ============================================================================
 // A CHAIN of stride-1 blocks in one launch (C2 = 48, whole image, plane-per-quad tile): stage 3's blocks 1..7
@@ -149,7 +141,7 @@ __global__ __launch_bounds__(THREADS, 2) void block_s1chain6_kernel(BlockS1Args 
   // program order): its barriers wait for the LDS counter, not for the global stores in flight - __syncthreads() would
   // also drain vmcnt, i.e. stall every block's exchange phase until its park stores are acknowledged by L2.
   auto lds_barrier = []() __attribute__((always_inline)) { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
-  Yfv2Watch watch;   // range guard of the fp16x3 products (yfv2_internal.h): one accumulator element per pixel tile and pointwise conv
+  Yfv2Watch watch;   // range guard of the fp16x3 products (yfv2_device.h): one accumulator element per pixel tile and pointwise conv
 
   // fp16x3 (round 3; yfv2_stem16.hip): every operand = two fp16 terms, w1 x2 + w2 x1 + w1 x1 with fp32 accumulation.
   // B operands of one pixel tile from its three chunk fragments (x 2^4 first): the pair (chunks 0, 1) as {x1, x1} and
@@ -157,21 +149,19 @@ __global__ __launch_bounds__(THREADS, 2) void block_s1chain6_kernel(BlockS1Args 
   // v_mfma_f32_16x16x32_f16 per (output tile, pixel tile): the pair's two cross products, chunk 2's cross products in ONE
   // instruction, the pair's main product, chunk 2's main product ({0, w1} against the same {x2, x1}).  Round 2's bf16x6 form
   // took nine, a three-term split per activation quad and twice the filter image.
-  struct BOps { yfv2_h8c p1, p2, s; };
+  struct BOps { yfv2_h8 p1, p2, s; };
   auto make_b = [&](f32x4 c0, f32x4 c1, f32x4 c2v) __attribute__((always_inline)) {
     unsigned h[3][2], l[3][2];
     const f32x4 cs[3] = {c0 * 16.0f, c1 * 16.0f, c2v * 16.0f};
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
-      const yfv2_h4c t1 = __builtin_convertvector(cs[k], yfv2_h4c);                                   // v_cvt_pk_f16_f32 (RN)
-      const yfv2_h4c t2 = __builtin_convertvector(cs[k] - __builtin_convertvector(t1, f32x4), yfv2_h4c);   // the difference is exact
-      const yfv2_u2c a1 = __builtin_bit_cast(yfv2_u2c, t1), a2 = __builtin_bit_cast(yfv2_u2c, t2);
-      h[k][0] = a1[0]; h[k][1] = a1[1]; l[k][0] = a2[0]; l[k][1] = a2[1];
+      const u32x4 t = split_f16x2(cs[k]);
+      h[k][0] = t[0]; h[k][1] = t[1]; l[k][0] = t[2]; l[k][1] = t[3];
     }
     BOps b;
-    b.p1 = __builtin_bit_cast(yfv2_h8c, (u32x4){h[0][0], h[0][1], h[1][0], h[1][1]});
-    b.p2 = __builtin_bit_cast(yfv2_h8c, (u32x4){l[0][0], l[0][1], l[1][0], l[1][1]});
-    b.s = __builtin_bit_cast(yfv2_h8c, (u32x4){l[2][0], l[2][1], h[2][0], h[2][1]});
+    b.p1 = __builtin_bit_cast(yfv2_h8, (u32x4){h[0][0], h[0][1], h[1][0], h[1][1]});
+    b.p2 = __builtin_bit_cast(yfv2_h8, (u32x4){l[0][0], l[0][1], l[1][0], l[1][1]});
+    b.s = __builtin_bit_cast(yfv2_h8, (u32x4){l[2][0], l[2][1], h[2][0], h[2][1]});
     return b;
   };
   // acc[n] += W[mt] x B[n] for the lane's four pixel tiles: five products, the small ones first, the tiles interleaved (the
@@ -179,8 +169,8 @@ __global__ __launch_bounds__(THREADS, 2) void block_s1chain6_kernel(BlockS1Args 
   auto mfma9 = [&](const float* WP, int mt, const BOps (&b)[NT], f32x4 (&acc)[NT]) __attribute__((always_inline)) {
     const float* wq = WP + ((mt * 3) * 64 + lane) * 4;
     const u32x4 q1 = *reinterpret_cast<const u32x4*>(wq), q2 = *reinterpret_cast<const u32x4*>(wq + 256), qs = *reinterpret_cast<const u32x4*>(wq + 512);
-    const yfv2_h8c w1p = __builtin_bit_cast(yfv2_h8c, q1), w2p = __builtin_bit_cast(yfv2_h8c, q2), ws = __builtin_bit_cast(yfv2_h8c, qs);
-    const yfv2_h8c wm = __builtin_bit_cast(yfv2_h8c, (u32x4){0u, 0u, qs[0], qs[1]});
+    const yfv2_h8 w1p = __builtin_bit_cast(yfv2_h8, q1), w2p = __builtin_bit_cast(yfv2_h8, q2), ws = __builtin_bit_cast(yfv2_h8, qs);
+    const yfv2_h8 wm = __builtin_bit_cast(yfv2_h8, (u32x4){0u, 0u, qs[0], qs[1]});
 #define CH6_EACH(EXPR) _Pragma("unroll") for (int n = 0; n < NT; ++n) acc[n] = EXPR;
     CH6_EACH(__builtin_amdgcn_mfma_f32_16x16x32_f16(w1p, b[n].p2, acc[n], 0, 0, 0))
     CH6_EACH(__builtin_amdgcn_mfma_f32_16x16x32_f16(w2p, b[n].p1, acc[n], 0, 0, 0))
@@ -540,7 +530,7 @@ __global__ __launch_bounds__(THREADS, 2) void block_s1pool_kernel(BlockS1Args a)
   float* POOL = lds;                                   // [H * W][P96_CPP]
   float* T = POOL + a.H * a.W * P96_CPP;               // [(H+2)][(W+2)][P96_TP], border zero
   float* IMG = T + (a.H + 2) * (a.W + 2) * P96_TP;     // one third's image
-  Yfv2Watch watch;                                     // range guard of the fp16x3 products (yfv2_internal.h)
+  Yfv2Watch watch;                                     // range guard of the fp16x3 products (yfv2_device.h)
   const int H = a.H, W = a.W, HW = H * W, WP = W + 2, NB = a.nblk;
   const float invW = 1.0f / (float)W;
   const int tid = threadIdx.x, lane = tid & 63, p = lane & 15, g = lane >> 4, wave = tid >> 6;
@@ -593,18 +583,16 @@ __global__ __launch_bounds__(THREADS, 2) void block_s1pool_kernel(BlockS1Args a)
       for (int mt = 0; mt < P96_KC; ++mt) acc2[mt] = (f32x4){0.f, 0.f, 0.f, 0.f};
       // PRE: pw1's B operands for the whole block - the 96 odd pool channels of this lane's pixel, per chunk pair
       // (fp16x3, round 3: x 2^4, two fp16 terms; round 2's form was bf16x6 - three terms, six products)
-      yfv2_h8c b1a[PRE ? P96_KC / 2 : 1], b1b[PRE ? P96_KC / 2 : 1];
-      auto split_pair = [&](f32x4 c0, f32x4 c1, yfv2_h8c& t1, yfv2_h8c& t2) __attribute__((always_inline)) {
+      yfv2_h8 b1a[PRE ? P96_KC / 2 : 1], b1b[PRE ? P96_KC / 2 : 1];
+      auto split_pair = [&](f32x4 c0, f32x4 c1, yfv2_h8& t1, yfv2_h8& t2) __attribute__((always_inline)) {
         u32x4 u1, u2;
         const f32x4 cs[2] = {c0 * 16.0f, c1 * 16.0f};
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
-          const yfv2_h4c h1 = __builtin_convertvector(cs[e], yfv2_h4c);
-          const yfv2_h4c h2 = __builtin_convertvector(cs[e] - __builtin_convertvector(h1, f32x4), yfv2_h4c);
-          const yfv2_u2c a1 = __builtin_bit_cast(yfv2_u2c, h1), a2 = __builtin_bit_cast(yfv2_u2c, h2);
-          u1[2 * e] = a1[0]; u1[2 * e + 1] = a1[1]; u2[2 * e] = a2[0]; u2[2 * e + 1] = a2[1];
+          const u32x4 t = split_f16x2(cs[e]);
+          u1[2 * e] = t[0]; u1[2 * e + 1] = t[1]; u2[2 * e] = t[2]; u2[2 * e + 1] = t[3];
         }
-        t1 = __builtin_bit_cast(yfv2_h8c, u1); t2 = __builtin_bit_cast(yfv2_h8c, u2);
+        t1 = __builtin_bit_cast(yfv2_h8, u1); t2 = __builtin_bit_cast(yfv2_h8, u2);
       };
       if constexpr (PRE) {
 #pragma unroll
@@ -641,12 +629,12 @@ __global__ __launch_bounds__(THREADS, 2) void block_s1pool_kernel(BlockS1Args a)
           if constexpr (PRE) {
 #pragma unroll
             for (int sp = 0; sp < P96_KC / 2; ++sp) {
-              yfv2_h8c a1[2], a2[2];
+              yfv2_h8 a1[2], a2[2];
 #pragma unroll
               for (int mt = 0; mt < 2; ++mt) {
                 const float* wq2 = W1t + (((mt * (P96_KC / 2) + sp) * 2) * 64 + lane) * 4;
-                a1[mt] = __builtin_bit_cast(yfv2_h8c, *reinterpret_cast<const u32x4*>(wq2));
-                a2[mt] = __builtin_bit_cast(yfv2_h8c, *reinterpret_cast<const u32x4*>(wq2 + 256));
+                a1[mt] = __builtin_bit_cast(yfv2_h8, *reinterpret_cast<const u32x4*>(wq2));
+                a2[mt] = __builtin_bit_cast(yfv2_h8, *reinterpret_cast<const u32x4*>(wq2 + 256));
               }
 #define P96_PROD(A_, B_) _Pragma("unroll") for (int mt = 0; mt < 2; ++mt) acc1[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A_[mt], B_, acc1[mt], 0, 0, 0);
               P96_PROD(a1, b1b[sp]) P96_PROD(a2, b1a[sp]) P96_PROD(a1, b1a[sp])
@@ -705,14 +693,14 @@ __global__ __launch_bounds__(THREADS, 2) void block_s1pool_kernel(BlockS1Args a)
 #pragma unroll
             for (int c = 0; c < 4; ++c) bfr2[c2][c] = __builtin_fmaf(d[c], dsc[c], dsh[c]);
           }
-          yfv2_h8c x1, x2;
+          yfv2_h8 x1, x2;
           split_pair(bfr2[0], bfr2[1], x1, x2);
-          yfv2_h8c a1[P96_KC], a2[P96_KC];
+          yfv2_h8 a1[P96_KC], a2[P96_KC];
 #pragma unroll
           for (int mt = 0; mt < P96_KC; ++mt) {
             const float* wq2 = W2t + ((mt * 2) * 64 + lane) * 4;
-            a1[mt] = __builtin_bit_cast(yfv2_h8c, *reinterpret_cast<const u32x4*>(wq2));
-            a2[mt] = __builtin_bit_cast(yfv2_h8c, *reinterpret_cast<const u32x4*>(wq2 + 256));
+            a1[mt] = __builtin_bit_cast(yfv2_h8, *reinterpret_cast<const u32x4*>(wq2));
+            a2[mt] = __builtin_bit_cast(yfv2_h8, *reinterpret_cast<const u32x4*>(wq2 + 256));
           }
 #define P96_PROD(A_, B_) _Pragma("unroll") for (int mt = 0; mt < P96_KC; ++mt) acc2[mt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(A_[mt], B_, acc2[mt], 0, 0, 0);
           P96_PROD(a1, x2) P96_PROD(a2, x1) P96_PROD(a1, x1)
@@ -1208,7 +1196,7 @@ static bool launch_s2(const BlockS2Args& a, hipStream_t s) {
 //  * pw1 takes whole 16-pixel tiles, the tile's six B fragments in registers before its first write (in place without a
 //    barrier); it shares its phase with the proj pointwise.  (Two tiles per wave on four waves with the proj pointwise on
 //    their SIMD partners was slower: 70 us against 64 - the pw1 waves then bound the phase.)  pw1 is 70 % of the block's MFMA work and runs as bf16x6
-//    (yfv2_internal.h) with W1 PRE-SPLIT on the host (WeightPacker::image_s2w): per (output tile, chunk pair, term) one
+//    (yfv2_device.h) with W1 PRE-SPLIT on the host (WeightPacker::image_s2w): per (output tile, chunk pair, term) one
 //    16-byte operand whose 32 k-slots are the two chunks, so the six products hi.hi hi.mid mid.hi hi.lo lo.hi mid.mid are
 //    six MFMAs per chunk pair with no operand duplication and no VALU work on the filter side (splitting W1's 36
 //    fragments per tile on the fly cost more VALU time than the fp32 MFMAs it replaced: first version, 85 us).  The two
@@ -1721,7 +1709,7 @@ __global__ __launch_bounds__(THREADS) void tower2_kernel(TowerArgs a) {
           bfr[nt][k] = (cb < C && u > 0.f) ? u : 0.f;
         }
       if constexpr (BF6) {
-        // bf16x6 (yfv2_internal.h): the depthwise result is split once per pixel tile, each filter fragment once per
+        // bf16x6 (yfv2_device.h): the depthwise result is split once per pixel tile, each filter fragment once per
         // output-channel tile; three MFMAs per (mt, nt) - the NT accumulators of one mt are independent of each other
         Bf3B b3[NT];
 #pragma unroll

@@ -14,11 +14,7 @@
 // six logit maps).
 #include <cstdlib>
 
-#include "yfv2_internal.h"
-
-typedef _Float16 yfv2_h4 __attribute__((ext_vector_type(4)));
-typedef _Float16 yfv2_h8 __attribute__((ext_vector_type(8)));
-typedef unsigned yfv2_u2 __attribute__((ext_vector_type(2)));
+#include "yfv2_device.h"
 
 // ============================================================================
 // pointwise 1x1 conv on the fp32 matrix cores
@@ -97,7 +93,7 @@ __global__ __launch_bounds__(THREADS) void pw_kernel(PwArgs a) {
     sh[mt] = *reinterpret_cast<const f32x4*>(img + FILT_FL + MT * 16 + 16 * mt + 4 * g);
   }
 
-  Yfv2Watch watch;   // range guard of the fp16x3 form (yfv2_internal.h)
+  Yfv2Watch watch;   // range guard of the fp16x3 form (yfv2_device.h)
   const int n_super = (a.P + NT * 16 - 1) / (NT * 16);
   for (int st = blockIdx.x * nwaves + wave; st < n_super; st += gridDim.x * nwaves) {
     const int pix0 = st * (NT * 16);
@@ -153,12 +149,9 @@ __global__ __launch_bounds__(THREADS) void pw_kernel(PwArgs a) {
             u32x4 t1, t2;
 #pragma unroll
             for (int e = 0; e < 2; ++e) {
-              const f32x4 v = bq[nt][e] * 16.0f;                                          // fp16's absolute floor: 2^-25 -> 2^-29
-              const yfv2_h4 h1 = __builtin_convertvector(v, yfv2_h4);                       // v_cvt_pk_f16_f32 (RN)
-              const yfv2_h4 h2 = __builtin_convertvector(v - __builtin_convertvector(h1, f32x4), yfv2_h4);   // the difference is exact
-              const yfv2_u2 u1 = __builtin_bit_cast(yfv2_u2, h1), u2 = __builtin_bit_cast(yfv2_u2, h2);
-              t1[2 * e] = u1[0]; t1[2 * e + 1] = u1[1];
-              t2[2 * e] = u2[0]; t2[2 * e + 1] = u2[1];
+              const u32x4 h = split_f16x2(bq[nt][e] * 16.0f);                               // fp16's absolute floor: 2^-25 -> 2^-29
+              t1[2 * e] = h[0]; t1[2 * e + 1] = h[1];
+              t2[2 * e] = h[2]; t2[2 * e + 1] = h[3];
             }
             b1[nt] = __builtin_bit_cast(yfv2_h8, t1);
             b2[nt] = __builtin_bit_cast(yfv2_h8, t2);

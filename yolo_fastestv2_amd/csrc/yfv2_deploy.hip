@@ -7,7 +7,7 @@
 //   export_maps_kernel  six NCHW logit maps -> two NHWC maps (B, fh, fw, 15 + classes): sigmoid(12 reg) | sigmoid(3 obj) |
 //                       softmax(classes).  The geometry is decode_kernel's (yfv2_post.hip): up to 64 consecutive cells of one
 //                       (image, scale) per workgroup, 4 lanes per cell for the softmax - the same device functions
-//                       (yfv2_internal.h), so obj and cls are the bits of yfv2_decode's columns 4 and 5.. - and the NCHW -> NHWC
+//                       (yfv2_device.h), so obj and cls are the bits of yfv2_decode's columns 4 and 5.. - and the NCHW -> NHWC
 //                       turn goes through LDS: every logit is read once, along the map (consecutive lanes = consecutive cells of a
 //                       channel), the workgroup's cells are assembled as [cell][15 + classes] rows (row pitch made odd: the
 //                       channel-major writes then spread over the banks) and leave as ONE contiguous span of the output.  95
@@ -31,7 +31,7 @@
 //   (1815 rows), 132 KB at the handle's limit of 4096 rows.
 #include <hip/hip_runtime.h>
 
-#include "yfv2_internal.h"
+#include "yfv2_device.h"
 
 namespace {
 

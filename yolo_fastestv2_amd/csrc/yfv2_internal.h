@@ -1,21 +1,10 @@
-// yfv2_internal.h - launch-argument structs shared by the kernel translation
-// units, the host-side weight packer (yfv2_pack.hip) and the host-side plan (yfv2_plan.hip).  Not part of the public ABI.
+// yfv2_internal.h - launch-argument structs, launcher declarations and the launch macros shared by the kernel translation
+// units, the host-side weight packer (yfv2_pack.hip) and the host-side plan (yfv2_plan.hip).  No device-only code: what only runs on
+// the device and is shared between kernel units lives in yfv2_device.h.  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 #include <stdint.h>
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef float f32x3u __attribute__((ext_vector_type(3), aligned(4)));   // three floats at any dword address (global_load/store_dwordx3)
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x3 __attribute__((ext_vector_type(3)));
-
-// n / d for 0 <= n < 2^16 and 8 <= d <= 1024 through the float pipe (cvt, fma, cvt instead of the ~25-instruction
-// integer division): (n + 0.5) / d is at least 0.5/d away from an integer, far more than the fp32 error of the product.
-#ifdef __HIPCC__
-__device__ __forceinline__ int yfv2_fdiv(int n, float inv_d) { return (int)(((float)n + 0.5f) * inv_d); }
-#endif
 
 #include <atomic>
 
@@ -62,97 +51,6 @@ inline void yfv2_allow_lds(const Yfv2Device& dev, const void* fn, int bytes, std
     yfv2_allow_lds(dev, reinterpret_cast<const void*>(&kernel), limit, yfv2_lds_done_); \
     YFV2_LAUNCH(kernel, grid, block, lds, stream, __VA_ARGS__);                       \
   } while (0)
-
-// ---- fp32 pointwise convs on the bf16 matrix cores ("bf16x6")
-// gfx950's fp32 MFMA runs at the fp32 VECTOR rate (16x16x4: 32 cycles per 1024 MACs per SIMD); its bf16 MFMA is 16x
-// faster (16x16x32: ~17 cycles per 8192 MACs).  An fp32 value is EXACTLY the sum of three bf16 terms (truncation: 8 + 8 + 8
-// significant bits), so w * x = sum of nine bf16 x bf16 products, each exact in fp32; the six largest (everything above
-// 2^-23 of |w x|, i.e. below one fp32 rounding of the product) are accumulated in fp32 by three MFMAs whose eight k-slots
-// per lane group are the lane's 4 channels x 2 terms:
-//     A {w.hi, w.hi} x B {x.hi, x.mid}      A {w.mid, w.mid} x B {x.hi, x.mid}      A {w.hi, w.lo} x B {x.lo, x.hi}
-// Same fragment maps as v_mfma_f32_16x16x4_f32 (A lane l: row l&15; B lane l: pixel l&15; lane group l>>4 owns 4 channels of
-// the 16-channel chunk; D lane l reg r: row 4(l>>4)+r, column l&15), so it drops into the existing loops: split the A
-// fragment once per (tile of output channels, chunk), the B fragment once per (pixel tile, chunk), then mfma6().
-// Measured (tools/ubench/bf16x6.hip, K = 192, 5 x 2 tiles): max error vs float64 7.1e-6 against 8.6e-6 for the fp32 MFMA on
-// the same data; 30 MFMAs in ~520 cycles against 40 in 1280; the whole network's logits: 1.39e-5 vs 1.41e-5 from float64.
-#ifdef __HIPCC__
-typedef __bf16 yfv2_bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-struct Bf3A { u32x4 hh, mm, hl; };   // {hi,hi}, {mid,mid}, {hi,lo}
-struct Bf3B { u32x4 hm, lh; };       // {hi,mid}, {lo,hi}
-__device__ __forceinline__ unsigned yfv2_pack_hi16(float a, float b) {   // high halves of a (low 16 bits) and b (high 16 bits): two truncated bf16
-  return __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, b), __builtin_bit_cast(unsigned, a), 0x07060302u);
-}
-__device__ __forceinline__ float yfv2_trunc_bf16(float a) { return __builtin_bit_cast(float, __builtin_bit_cast(unsigned, a) & 0xffff0000u); }
-__device__ __forceinline__ void yfv2_split3(f32x4 v, unsigned (&h)[2], unsigned (&m)[2], unsigned (&l)[2]) {
-  float r1[4], r2[4];
-#pragma unroll
-  for (int c = 0; c < 4; ++c) { r1[c] = v[c] - yfv2_trunc_bf16(v[c]); r2[c] = r1[c] - yfv2_trunc_bf16(r1[c]); }   // exact subtractions
-  h[0] = yfv2_pack_hi16(v[0], v[1]); h[1] = yfv2_pack_hi16(v[2], v[3]);
-  m[0] = yfv2_pack_hi16(r1[0], r1[1]); m[1] = yfv2_pack_hi16(r1[2], r1[3]);
-  l[0] = yfv2_pack_hi16(r2[0], r2[1]); l[1] = yfv2_pack_hi16(r2[2], r2[3]);
-}
-__device__ __forceinline__ Bf3A yfv2_split_a(f32x4 w) {
-  unsigned h[2], m[2], l[2];
-  yfv2_split3(w, h, m, l);
-  return {(u32x4){h[0], h[1], h[0], h[1]}, (u32x4){m[0], m[1], m[0], m[1]}, (u32x4){h[0], h[1], l[0], l[1]}};
-}
-__device__ __forceinline__ Bf3B yfv2_split_b(f32x4 x) {
-  unsigned h[2], m[2], l[2];
-  yfv2_split3(x, h, m, l);
-  return {(u32x4){h[0], h[1], m[0], m[1]}, (u32x4){l[0], l[1], h[0], h[1]}};
-}
-// one of the three MFMAs (k = 0: the small terms, 1: w.mid, 2: w.hi): call sites run k outermost over their independent
-// accumulators so that no MFMA waits for the one before it
-template <int k>
-__device__ __forceinline__ f32x4 yfv2_mfma6_step(const Bf3A& a, const Bf3B& b, f32x4 acc) {
-  if constexpr (k == 0) return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(yfv2_bf16x8, a.hl), __builtin_bit_cast(yfv2_bf16x8, b.lh), acc, 0, 0, 0);
-  else if constexpr (k == 1) return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(yfv2_bf16x8, a.mm), __builtin_bit_cast(yfv2_bf16x8, b.hm), acc, 0, 0, 0);
-  else return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(yfv2_bf16x8, a.hh), __builtin_bit_cast(yfv2_bf16x8, b.hm), acc, 0, 0, 0);
-}
-// acc[mt][nt] += A[mt] x B[nt] for all tiles of a 16-channel chunk
-template <int MT_, int NT_>
-__device__ __forceinline__ void yfv2_mfma6_tiles(const Bf3A (&a)[MT_], const Bf3B (&b)[NT_], f32x4 (&acc)[MT_][NT_]) {
-#pragma unroll
-  for (int mt = 0; mt < MT_; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < NT_; ++nt) acc[mt][nt] = yfv2_mfma6_step<0>(a[mt], b[nt], acc[mt][nt]);
-#pragma unroll
-  for (int mt = 0; mt < MT_; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < NT_; ++nt) acc[mt][nt] = yfv2_mfma6_step<1>(a[mt], b[nt], acc[mt][nt]);
-#pragma unroll
-  for (int mt = 0; mt < MT_; ++mt)
-#pragma unroll
-    for (int nt = 0; nt < NT_; ++nt) acc[mt][nt] = yfv2_mfma6_step<2>(a[mt], b[nt], acc[mt][nt]);
-}
-#endif
-
-// ---- range guard of the fp16x3 arithmetic (include/yfv2.h yfv2_nonfinite)
-// An operand beyond fp16's range (|activation| * 2^4 or |pixel| * 2^8 >= 65520) splits into (+Inf, -Inf); the three
-// products of ANY filter entry with it are +-Inf or NaN and sum to NaN, for every output channel of that pixel - and the ReLU
-// behind almost every pointwise conv (v_max_f32 / v_med3_f32 return the non-NaN operand) would turn that NaN into a clean,
-// silent 0.  So every kernel of the fp16x3 plan looks at ONE accumulator element per lane of every pointwise product before
-// its ReLU: a shift and an unsigned compare into a scalar register pair OR-ed into a sticky wave-uniform mask (no branch),
-// and reports once at its end.  Non-finite INPUT values are caught by the same test.
-#ifdef __HIPCC__
-struct Yfv2Watch {
-  unsigned long long m = 0;
-  // an integer test of the exponent field (all ones: NaN or Inf), two VALU instructions: the kernel files are compiled with
-  // -fno-honor-nans (bare v_max for the ReLUs), under which `v != v` and the class intrinsics fold to false
-  __device__ __forceinline__ void see(float v) {
-    const unsigned b = __builtin_bit_cast(unsigned, v);
-    m |= __builtin_amdgcn_ballot_w64((b << 1) >= 0xff000000u);
-  }
-  __device__ __forceinline__ void report(int* flag) const {
-    // the rare path.  A plain store of the constant 1 (every writer stores the same value): the word lives in host-mapped,
-    // coherent memory (yfv2_create), where a store needs no PCIe atomic - the host can then LOOK at it without waiting for
-    // any stream (yfv2_nonfinite_peek)
-    if (m != 0 && flag != nullptr) *reinterpret_cast<volatile int*>(flag) = 1;
-  }
-};
-#endif
-
 
 // ---- stem: conv3x3 s2 (3->24) + BN + ReLU + maxpool3x3 s2, NCHW in -> NHWC out
 struct StemArgs {
@@ -334,48 +232,6 @@ struct TowerArgs {
   int chain;           // towers_kernel job list: bit 0 = the input is what the previous job left in LDS, bit 1 = the output stays in LDS for the next job (no global round trip)
   int* nonfinite;      // range-guard word (Yfv2Watch), or null
 };
-
-// ---- the device sigmoid and class softmax of the post-process (decode_kernel, yfv2_post.hip; export_maps_kernel, yfv2_deploy.hip).
-// ONE definition: the two kernels must agree bit for bit.  Units that use them are built with -ffp-contract=off.
-#ifdef __HIPCC__
-// fp32 sigmoid as ATen's CPU kernel evaluates it: 1 / (1 + exp(-x)), true division
-__device__ __forceinline__ float sigmoid_f32(float x) { return __fdiv_rn(1.0f, __fadd_rn(1.0f, expf(-x))); }
-// fp32 softmax over the `nc` class logits cls[c * hw + cc] of one grid cell, shared by 4 CONSECUTIVE, CONVERGED lanes: lane
-// `part` (0..3) owns classes [part * per, min(nc, (part + 1) * per)), per = ceil(nc / 4), and gets their probabilities
-// exp(x - max) / sum in ev[0 .. per) (slots beyond its slice: 0).  The sum is added slice by slice in class order, then
-// (s0 + s1) + (s2 + s3) by two xor exchanges: the summation tree is part of the result.  The lane's logits are fetched with
-// one batch of independent loads (fixed trip count, masked) instead of a load per loop turn.
-template <int MAXPER>
-__device__ __forceinline__ void yfv2_softmax_quad(const float* cls, int nc, int hw, int cc, int part, float (&ev)[MAXPER]) {
-  const int per = (nc + 3) >> 2;
-  const int c_lo = part * per, c_hi = min(nc, c_lo + per);
-  float lv[MAXPER];
-#pragma unroll
-  for (int i = 0; i < MAXPER; ++i) {
-    const int c = c_lo + i;
-    lv[i] = cls[(unsigned)((c < c_hi ? c : (c_lo < nc ? c_lo : 0)) * hw + cc)];   // masked slots re-read a valid class (fewer than 4 classes: quarters 1-3 are empty)
-  }
-  float m = -INFINITY;
-#pragma unroll
-  for (int i = 0; i < MAXPER; ++i)
-    if (c_lo + i < c_hi) m = fmaxf(m, lv[i]);
-  m = fmaxf(m, __shfl_xor(m, 1));
-  m = fmaxf(m, __shfl_xor(m, 2));
-  float sum = 0.f;
-#pragma unroll
-  for (int i = 0; i < MAXPER; ++i) {
-    ev[i] = 0.f;
-    if (c_lo + i < c_hi) {
-      ev[i] = expf(__fsub_rn(lv[i], m));
-      sum = __fadd_rn(sum, ev[i]);
-    }
-  }
-  sum = __fadd_rn(sum, __shfl_xor(sum, 1));
-  sum = __fadd_rn(sum, __shfl_xor(sum, 2));
-#pragma unroll
-  for (int i = 0; i < MAXPER; ++i) ev[i] = __fdiv_rn(ev[i], sum);  // class probabilities of this lane's slice
-}
-#endif
 
 // ---- decode (handel_preds) and NMS
 struct DecodeArgs {

@@ -11,11 +11,9 @@
 //   loss_match_kernel    one thread per slot: CIoU (float64, forward-mode derivatives), class cross-entropy, gradients
 //   loss_obj_kernel      every objectness cell: BCE-with-logits sum and gradient
 //   loss_final_kernel    one thread: means, balances, gains -> lbox, lobj, lcls, total
-#include "yfv2_internal.h"
+#include "yfv2_device.h"
 
 namespace {
-
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.0f / (1.0f + expf(-x)); }
 
 // value + gradient w.r.t. the predicted box (px, py, pw, ph), float64
 struct D4 {
@@ -108,7 +106,7 @@ __global__ __launch_bounds__(128) void loss_match_kernel(LossArgs a) {
       const float* reg = a.reg[l] + ((size_t)m.b * 12 + m.a * 4) * HW + cell;
       float s[4];
 #pragma unroll
-      for (int c = 0; c < 4; ++c) s[c] = sigmoidf_(reg[(size_t)c * HW]);
+      for (int c = 0; c < 4; ++c) s[c] = sigmoid_f32(reg[(size_t)c * HW]);
       const float pxf = s[0] * 2.0f - 0.5f, pyf = s[1] * 2.0f - 0.5f;   // :152 fp32
       const float qw = s[2] * 2.0f, qh = s[3] * 2.0f;
       const double pw = (double)(qw * qw) * m.aw, ph = (double)(qh * qh) * m.ah;   // :153: fp32 square, float64 anchor product
@@ -164,7 +162,7 @@ __global__ __launch_bounds__(256) void loss_obj_kernel(LossArgs a) {
     const int l = i >= n0 ? 1 : 0, j = l ? i - n0 : i;
     const float x = a.obj[l][j], t = a.tobj[l][j] ? 1.0f : 0.0f;
     acc[l] += (double)((1.0f - t) * x + (log1pf(expf(-fabsf(x))) + fmaxf(-x, 0.0f)));
-    if (a.grad_obj[l]) a.grad_obj[l][j] = (64.0f * (l ? 0.4f : 1.0f) / (float)(l ? n1 : n0)) * (sigmoidf_(x) - t);
+    if (a.grad_obj[l]) a.grad_obj[l][j] = (64.0f * (l ? 0.4f : 1.0f) / (float)(l ? n1 : n0)) * (sigmoid_f32(x) - t);
   }
   __shared__ double sb[2];
   if (threadIdx.x < 2) sb[threadIdx.x] = 0.0;

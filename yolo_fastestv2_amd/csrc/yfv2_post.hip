@@ -4,9 +4,9 @@
 // SURVEY.md App. B.  Reference behaviour: utils/utils.py:67-74 (xywh2xyxy),
 // :232-296 (non_max_suppression), :298-358 (make_grid, handel_preds) and
 // torchvision.ops.nms (called at :286).
-#include "yfv2_internal.h"
+#include "yfv2_device.h"
 
-// (sigmoid_f32 and the class softmax of decode_kernel, yfv2_softmax_quad, live in yfv2_internal.h: yfv2_deploy.hip's export_maps_kernel
+// (sigmoid_f32 and the class softmax of decode_kernel, yfv2_softmax_quad, live in yfv2_device.h: yfv2_deploy.hip's export_maps_kernel
 // must produce the same bits)
 
 // Lane exchanges that move bits only (no arithmetic), for a wave whose lanes are all active.  Within a group of four
@@ -187,7 +187,7 @@ __global__ __launch_bounds__(DEC_THREADS) void decode_kernel(DecodeArgs a, int b
   const bool ok = lc < ncell;
   const int cc = ok ? cell : cell0;  // clamp so that shuffles stay convergent
 
-  // ---- class softmax (fp32): exp(x - max) / sum (yfv2_internal.h: the one definition export_maps_kernel shares)
+  // ---- class softmax (fp32): exp(x - max) / sum (yfv2_device.h: the one definition export_maps_kernel shares)
   const int per = (nc + 3) >> 2;
   const int c_lo = part * per, c_hi = min(nc, c_lo + per);
   const float* cls = a.cls[sc] + (size_t)b * nc * hw;   // wave-uniform base: the per-lane part stays a 32-bit offset (24 addresses live)
@@ -390,7 +390,6 @@ __device__ __forceinline__ unsigned conf_key(float c) {
 // SRC 0: the (B, rows, 5 + classes) decoded tensor (yfv2_nms); 1: compact candidate rows in global memory (decode_kernel<true>);
 // 2: the logits themselves - the workgroup decodes its image into compact rows in LDS first (yfv2_detect: one launch for
 // handel_preds + non_max_suppression, the candidate rows never exist in HBM)
-#define NMS_STAMP(i) do { if (a.trace && blockIdx.x == 0 && threadIdx.x == 0) a.trace[i] = (long long)__builtin_readcyclecounter(); } while (0)
 // KPT = sort keys per thread: 2 (up to 2048 rows: everything the notes below measured) or 4 (up to 4096 rows - inputs beyond
 // 352x352, e.g. 416x416 = 2535 rows, 512x512 = 3840; the sort's second exchange buffer then shares LDS with the box arrays,
 // which are written after it, so that 4096 candidates fit into 132 KB)
@@ -416,7 +415,7 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(NmsArgs a, DecodeArgs 
   const int rowlen = COMPACT ? 8 : 5 + a.nc;  // COMPACT rows: cx,cy,w,h,obj,conf,cls,0 (decode_kernel<true>)
   const float* img = SRC == 2 ? crow : a.boxes + (size_t)b * a.rows * rowlen;
   const float ct = a.conf_thres;
-  NMS_STAMP(0);
+  YFV2_STAMP(0);
   if constexpr (SRC == 2) {
     // decode this image: 4 lanes per grid cell (yfv2_compact_row), 16 cells per wave.  The waves are numbered across both
     // scales (scale 0's last wave is padded, so that a wave's scale and base pointers stay uniform): at 352 x 352, 31 + 8
@@ -452,7 +451,7 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(NmsArgs a, DecodeArgs 
     }
     __syncthreads();
   }
-  NMS_STAMP(1);   // decoded
+  YFV2_STAMP(1);   // decoded
   unsigned short* cand_row = reinterpret_cast<unsigned short*>(bx1);  // step 1 only; bx1 is written in step 3
   if (tid == 0) { n_cand = 0; n_keep = 0; n_obj = 0; }
   __syncthreads();
@@ -528,7 +527,7 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(NmsArgs a, DecodeArgs 
     }
   }
   __syncthreads();
-  NMS_STAMP(2);   // filtered
+  YFV2_STAMP(2);   // filtered
   const int n = n_cand;
   if (n == 0) {
     if (tid == 0) a.count[b] = 0;
@@ -544,7 +543,7 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(NmsArgs a, DecodeArgs 
   if (np2 <= NMS_THREADS) bitonic_sort<1>(key, key2, np2, tid);
   else bitonic_sort<KPT>(key, key2, np2, tid);
 
-  NMS_STAMP(3);   // sorted
+  YFV2_STAMP(3);   // sorted
   // ---- 3. per-candidate geometry in sorted order
   for (int i = tid; i < n; i += NMS_THREADS) {
     const unsigned row = 0xFFFFFFFFu - (unsigned)(key[i] & 0xFFFFFFFFull);
@@ -559,7 +558,7 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(NmsArgs a, DecodeArgs 
   }
   __syncthreads();
 
-  NMS_STAMP(4);   // geometry
+  YFV2_STAMP(4);   // geometry
   // ---- 4. greedy suppression, one wave width (64 sorted candidates) at a time.
   // A candidate is kept iff no EARLIER KEPT candidate overlaps it by more than the
   // threshold (torchvision's loop).  Per chunk:  (a) all threads test the chunk
@@ -664,7 +663,7 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(NmsArgs a, DecodeArgs 
   }
   if (tr) { a.trace[9] = n_chunks; a.trace[10] = t_tests; a.trace[11] = t_walk; a.trace[12] = t_bar; }
   __syncthreads();
-  NMS_STAMP(5);   // greedy
+  YFV2_STAMP(5);   // greedy
   const int kept = n_keep;
 
   // ---- output rows: un-offset box, conf, float(cls); idx = decode row
@@ -682,7 +681,7 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(NmsArgs a, DecodeArgs 
     a.idx[(size_t)b * NMS_MAX_DET + k] = (int)row;
   }
   if (tid == 0) a.count[b] = kept;
-  NMS_STAMP(6);   // output
+  YFV2_STAMP(6);   // output
   if (a.trace && blockIdx.x == 0 && tid == 0) { a.trace[7] = n; a.trace[8] = kept; }
 }
 

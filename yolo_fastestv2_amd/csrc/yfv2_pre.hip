@@ -15,7 +15,7 @@
 #include <algorithm>
 
 #include "../../include/yfv2.h"
-#include "yfv2_internal.h"
+#include "yfv2_device.h"
 
 struct RowCoef { int s0, s1, c0, c1; };
 

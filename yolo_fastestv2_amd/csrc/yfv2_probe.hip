@@ -13,7 +13,7 @@
 //              the main one and reports the clock the forward's kernels actually saw.
 #include <hip/hip_runtime.h>
 
-#include "yfv2_internal.h"
+#include "yfv2_device.h"
 
 namespace {
 

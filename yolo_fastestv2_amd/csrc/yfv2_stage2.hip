@@ -21,53 +21,12 @@
 // (branch) channels and writes the branch result into the other buffer's copy of the same 12 pairs; the
 // even (pass-through) channels are never touched, channel_shuffle / concat are pure bookkeeping that is
 // folded into the order of the filter columns / rows when the weights are packed.
-#include "yfv2_internal.h"
+#include "yfv2_device.h"
 #include <utility>
 
 namespace {
 
-__device__ __forceinline__ float row_shr1(float v) {   // lane l <- lane l-1 inside its 16-lane row, 0 at l = 0
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x111, 0xf, 0xf, true));
-}
-// tap k (0..3) of the lane's quad: the depthwise taps live four to a register in the lanes of every quad
-// (all quads identical), DPP quad_perm:[k,k,k,k] hands tap k to all lanes without touching SGPRs or LDS
-template <int K>
-__device__ __forceinline__ float quad_mul(float tap4, float v) {   // tap4[quad lane K] * v
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, tap4), K * 0x55, 0xf, 0xf, false)) * v;
-}
-// acc += tap4[quad lane K] * v as ONE v_fmac_f32_dpp (hipcc folds the DPP into v_mul but not into v_fmac: it
-// emits v_mov 0 + v_mov_dpp + v_fmac).  Inline asm hides two gfx9 hazards from the compiler's hazard recognizer,
-// both met in practice (wrong depthwise sums in one wave role only):
-//   * the tap register may just have been written by a VALU op the compiler inserted (a v_accvgpr_read of a
-//     spilled tap): "VALU writes VGPR -> DPP reads it" needs 2 wait states -> every asm block starts with s_nop 1;
-//   * the asm WRITES acc with a VALU op, and a compiler-generated DPP (row_shr1/row_shl1 of a column sum) may
-//     read it next -> dpp_src_ready() below.
-// Groups of FMAs share one block (one s_nop).  KA.. are the quad lanes of the taps (immediates).
-#define YFV2_QP(n) "quad_perm:[%" #n ",%" #n ",%" #n ",%" #n "] row_mask:0xf bank_mask:0xf\n\t"
-template <int KA>
-__device__ __forceinline__ void quad_fmac1(float& s, float ta, float v) {
-  asm("s_nop 1\n\tv_fmac_f32_dpp %0, %1, %2 " YFV2_QP(3) : "+v"(s) : "v"(ta), "v"(v), "n"(KA));
-}
-// s += ta*v0; q += tb*v1; s += tc*v1   (one vertical tap row of a stride-2 window: dx = 1, 0, 2)
-template <int KA, int KB, int KC>
-__device__ __forceinline__ void quad_fmac3(float& s, float& q, float ta, float tb, float tc, float v0, float v1) {
-  asm("s_nop 1\n\tv_fmac_f32_dpp %0, %2, %5 " YFV2_QP(7) "v_fmac_f32_dpp %1, %3, %6 " YFV2_QP(8) "v_fmac_f32_dpp %0, %4, %6 " YFV2_QP(9)
-      : "+v"(s), "+v"(q) : "v"(ta), "v"(tb), "v"(tc), "v"(v0), "v"(v1), "n"(KA), "n"(KB), "n"(KC));
-}
-// a0 += t3*u + t6*w; a1 += t4*u + t7*w; a2 += t5*u + t8*w   (rows dy = 1, 2 of a stride-1 window, all three dx)
-template <int K3, int K4, int K5, int K6, int K7, int K8>
-__device__ __forceinline__ void quad_fmac6(float& a0, float& a1, float& a2, float t3, float t4, float t5, float t6, float t7, float t8,
-                                           float u, float w) {
-  asm("s_nop 1\n\tv_fmac_f32_dpp %0, %3, %9 " YFV2_QP(11) "v_fmac_f32_dpp %1, %4, %9 " YFV2_QP(12) "v_fmac_f32_dpp %2, %5, %9 " YFV2_QP(13)
-      "v_fmac_f32_dpp %0, %6, %10 " YFV2_QP(14) "v_fmac_f32_dpp %1, %7, %10 " YFV2_QP(15) "v_fmac_f32_dpp %2, %8, %10 " YFV2_QP(16)
-      : "+v"(a0), "+v"(a1), "+v"(a2)
-      : "v"(t3), "v"(t4), "v"(t5), "v"(t6), "v"(t7), "v"(t8), "v"(u), "v"(w), "n"(K3), "n"(K4), "n"(K5), "n"(K6), "n"(K7), "n"(K8));
-}
-// 2 wait states between an inline-asm VALU write of v and a DPP read of v (gfx9 "VALU writes VGPR -> DPP reads it")
-__device__ __forceinline__ void dpp_src_ready(float& v) { asm volatile("s_nop 1" : "+v"(v)); }
-__device__ __forceinline__ float row_shl1(float v) {   // lane l <- lane l+1 inside its 16-lane row, 0 at l = 15
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x101, 0xf, 0xf, true));
-}
+// (lane moves and the depthwise tap forms - row_shr1 / row_shl1, quad_mul, quad_fmac1/3/6, dpp_src_ready - are yfv2_device.h's)
 
 // 24 -> 24 pointwise conv of the lane's pixel: acc[m] (4 consecutive output positions) = sum_k W[4m+i][k] * in[k]
 // + shift, as 6 x 25 MFMAs: input "channel" 24 is the constant 1 and carries the BN shift, so the
@@ -363,7 +322,6 @@ __device__ __forceinline__ void s2px_body(const S2PxArgs& a, int wid) {
 #undef YFV2_TQ
 #undef YFV2_TK
 }
-#undef YFV2_QP
 #undef YFV2_WAIT_ROW
 
 // The two roles are two kernels launched back to back, each with its own decomposition (main: 5 row bands per image

@@ -17,68 +17,23 @@
 //   * BN: scale folded into the filters / taps, shift = the accumulators' initial value; ReLU = v_med3 against a per-lane
 //     0 / +inf limit that also zeroes pw1's output outside the image (the depthwise's padding);
 //   * depthwise taps: four to a register across the lanes of a quad (all quads of a lane group alike), applied with
-//     v_fmac_f32_dpp quad_perm broadcasts as in yfv2_stage2.hip - 18 registers instead of 72;
+//     v_fmac_f32_dpp quad_perm broadcasts (quad_fmac*, yfv2_device.h) - 18 registers instead of 72;
 //   * powers of two: filters carry 2^sw (largest entry near 2^14), activations are scaled by 2^4 before the split (fp16's
 //     absolute floor 2^-25 -> 2^-29; valid for |x| < 4094, an order of magnitude above anything this network produces:
 //     stage-2 activations are < 10 with the COCO weights and with random-init ones), all undone exactly: pw1's inside the
 //     taps, pw2's after its ReLU.
-#include "yfv2_internal.h"
+#include "yfv2_device.h"
 #include <atomic>
 #include <utility>
 
-typedef _Float16 yfv2_h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 yfv2_h2 __attribute__((ext_vector_type(2)));
-
 namespace {
 
-__device__ __forceinline__ float row_shr1(float v) {   // lane l <- lane l-1 inside its 16-lane row, 0 at l = 0
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x111, 0xf, 0xf, true));
-}
-__device__ __forceinline__ float row_shl1(float v) {   // lane l <- lane l+1 inside its 16-lane row, 0 at l = 15
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x101, 0xf, 0xf, true));
-}
-// tap K of the lane's quad times v (see yfv2_stage2.hip for the two gfx9 hazards the asm forms guard against)
-template <int K>
-__device__ __forceinline__ float quad_mul(float tap4, float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, tap4), K * 0x55, 0xf, 0xf, false)) * v;
-}
-#define YFV2_QP(n) "quad_perm:[%" #n ",%" #n ",%" #n ",%" #n "] row_mask:0xf bank_mask:0xf\n\t"
-// a0 += t3*u + t6*w; a1 += t4*u + t7*w; a2 += t5*u + t8*w   (rows dy = 1, 2 of a stride-1 window, all three dx)
-template <int K3, int K4, int K5, int K6, int K7, int K8>
-__device__ __forceinline__ void quad_fmac6(float& a0, float& a1, float& a2, float t3, float t4, float t5, float t6, float t7, float t8,
-                                           float u, float w) {
-  asm("s_nop 1\n\tv_fmac_f32_dpp %0, %3, %9 " YFV2_QP(11) "v_fmac_f32_dpp %1, %4, %9 " YFV2_QP(12) "v_fmac_f32_dpp %2, %5, %9 " YFV2_QP(13)
-      "v_fmac_f32_dpp %0, %6, %10 " YFV2_QP(14) "v_fmac_f32_dpp %1, %7, %10 " YFV2_QP(15) "v_fmac_f32_dpp %2, %8, %10 " YFV2_QP(16)
-      : "+v"(a0), "+v"(a1), "+v"(a2)
-      : "v"(t3), "v"(t4), "v"(t5), "v"(t6), "v"(t7), "v"(t8), "v"(u), "v"(w), "n"(K3), "n"(K4), "n"(K5), "n"(K6), "n"(K7), "n"(K8));
-}
-// s += ta*v0; q += tb*v1; s += tc*v1   (one vertical tap row of a stride-2 window: dx = 1, 0, 2)
-template <int KA, int KB, int KC>
-__device__ __forceinline__ void quad_fmac3(float& s, float& q, float ta, float tb, float tc, float v0, float v1) {
-  asm("s_nop 1\n\tv_fmac_f32_dpp %0, %2, %5 " YFV2_QP(7) "v_fmac_f32_dpp %1, %3, %6 " YFV2_QP(8) "v_fmac_f32_dpp %0, %4, %6 " YFV2_QP(9)
-      : "+v"(s), "+v"(q) : "v"(ta), "v"(tb), "v"(tc), "v"(v0), "v"(v1), "n"(KA), "n"(KB), "n"(KC));
-}
-template <int KA>
-__device__ __forceinline__ void quad_fmac1(float& s, float ta, float v) {
-  asm("s_nop 1\n\tv_fmac_f32_dpp %0, %1, %2 " YFV2_QP(3) : "+v"(s) : "v"(ta), "v"(v), "n"(KA));
-}
-#undef YFV2_QP
-__device__ __forceinline__ void dpp_src_ready(float& v) { asm volatile("s_nop 1" : "+v"(v)); }
-
-// (a, b) -> packed fp16 pairs h1, h2 with h1 + h2 = (a, b) to 2^-24
-__device__ __forceinline__ void split2(f32x2 v, unsigned& h1, unsigned& h2) {
-  const yfv2_h2 t1 = __builtin_convertvector(v, yfv2_h2);                       // v_cvt_pk_f16_f32 (RN)
-  const f32x2 r = v - __builtin_convertvector(t1, f32x2);                       // exact
-  const yfv2_h2 t2 = __builtin_convertvector(r, yfv2_h2);
-  h1 = __builtin_bit_cast(unsigned, t1);
-  h2 = __builtin_bit_cast(unsigned, t2);
-}
 // 24 -> 24 pointwise conv of 16 pixels: in = the lane's eight K slots as four pairs (already carrying their 2^4), init = BN
 // shift (scaled) of the lane's output channels; w[tile][term].  w1 x2, w2 x1, w1 x1: smallest terms first.
 __device__ __forceinline__ void pw_h3(const yfv2_h8 (&w)[2][2], const f32x2 (&in)[4], const f32x4 (&init)[2], f32x4 (&acc)[2], Yfv2Watch& watch) {
   u32x4 b1, b2;
 #pragma unroll
-  for (int k = 0; k < 4; ++k) { unsigned h1, h2; split2(in[k], h1, h2); b1[k] = h1; b2[k] = h2; }
+  for (int k = 0; k < 4; ++k) { const u32x2 h = split_f16x2(in[k]); b1[k] = h[0]; b2[k] = h[1]; }
   const yfv2_h8 x1 = __builtin_bit_cast(yfv2_h8, b1), x2 = __builtin_bit_cast(yfv2_h8, b2);
 #pragma unroll
   for (int t = 0; t < 2; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[t][0], x2, init[t], 0, 0, 0);
@@ -86,7 +41,7 @@ __device__ __forceinline__ void pw_h3(const yfv2_h8 (&w)[2][2], const f32x2 (&in
   for (int t = 0; t < 2; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[t][1], x1, acc[t], 0, 0, 0);
 #pragma unroll
   for (int t = 0; t < 2; ++t) acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(w[t][0], x1, acc[t], 0, 0, 0);
-  watch.see(acc[0][0]);   // range guard (yfv2_internal.h): an operand beyond fp16's range makes every output channel of its pixel NaN
+  watch.see(acc[0][0]);   // range guard (yfv2_device.h): an operand beyond fp16's range makes every output channel of its pixel NaN
 }
 
 }  // namespace
@@ -438,33 +393,14 @@ void yfv2_launch_s2h(const S2PxArgs& a0, hipStream_t s) {
 // instructions on the same operands in the same order as in stem_h3_kernel + s2h_kernel: the results are bit-identical
 // (tests/test_gpu_parity.py compares the two plans).
 namespace {
-struct FCol { unsigned p01[2], p23[2], m[2]; };   // a 16-byte run of one input row, both fp16 terms: (v0, v1), (v2, v3); m: high half = the column left of v0
-__device__ __forceinline__ unsigned f_dpp_shr1_u(unsigned v) { return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true); }
-__device__ __forceinline__ float f_dpp_shr1_f(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x111, 0xf, 0xf, true)); }
-__device__ __forceinline__ int f_f2i(float v) { return __builtin_bit_cast(int, v); }
-__device__ __forceinline__ float f_i2f(int v) { return __builtin_bit_cast(float, v); }
-__device__ __forceinline__ void f_split2(float a, float b, unsigned& h1, unsigned& h2) {   // the stem's split: x 2^8 first (yfv2_stem16.hip)
-  const f32x2 v = (f32x2){a, b} * 256.0f;
-  const yfv2_h2 t1 = __builtin_convertvector(v, yfv2_h2);
-  const f32x2 r = v - __builtin_convertvector(t1, f32x2);
-  const yfv2_h2 t2 = __builtin_convertvector(r, yfv2_h2);
-  h1 = __builtin_bit_cast(unsigned, t1);
-  h2 = __builtin_bit_cast(unsigned, t2);
-}
-__device__ __forceinline__ unsigned f_hi_hi(unsigned a, unsigned b) { return __builtin_amdgcn_perm(b, a, 0x07060302u); }   // {a.hi, b.hi}
-__device__ __forceinline__ unsigned f_hi_lo(unsigned a, unsigned b) { return __builtin_amdgcn_perm(b, a, 0x05040302u); }   // {a.hi, b.lo}
-__device__ __forceinline__ void f_split(const f32x4 v, FCol& o) {
-  f_split2(v[0], v[1], o.p01[0], o.p01[1]);
-  f_split2(v[2], v[3], o.p23[0], o.p23[1]);
-}
 // one pooled column's two conv columns (tile E: even, tile O: odd) of one conv row: rows x0 (carried), x1, x2 - stem_h3_kernel's K slots
-__device__ __forceinline__ void f_conv_col(const FCol& x0, const FCol& x1, const FCol& x2, const yfv2_h8 (&wa)[2][2], const f32x4 sh0, const f32x4 sh1,
+__device__ __forceinline__ void f_conv_col(const Row16& x0, const Row16& x1, const Row16& x2, const yfv2_h8 (&wa)[2][2], const f32x4 sh0, const f32x4 sh1,
                                            f32x4 (&ae)[2], f32x4 (&ao)[2]) {
   yfv2_h8 be[2], bo[2];
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
-    const u32x4 e = {x0.p01[k], x1.p01[k], f_hi_hi(x0.m[k], x1.m[k]), f_hi_lo(x2.m[k], x2.p01[k])};
-    const u32x4 o = {x0.p23[k], x1.p23[k], f_hi_hi(x0.p01[k], x1.p01[k]), f_hi_lo(x2.p01[k], x2.p23[k])};
+    const u32x4 e = {x0.p01[k], x1.p01[k], pack_hi_hi(x0.m[k], x1.m[k]), pack_hi_lo(x2.m[k], x2.p01[k])};
+    const u32x4 o = {x0.p23[k], x1.p23[k], pack_hi_hi(x0.p01[k], x1.p01[k]), pack_hi_lo(x2.p01[k], x2.p23[k])};
     be[k] = __builtin_bit_cast(yfv2_h8, e);
     bo[k] = __builtin_bit_cast(yfv2_h8, o);
   }
@@ -492,22 +428,11 @@ constexpr int F2_WA = 0, F2_S2 = 1024, F2_TAPS = F2_S2 + 3072, F2_CST = F2_TAPS 
 // load - a lane's two pooled columns are 24 consecutive bytes - lane group g picks its channel's bytes with v_perm_b32, lane group 3
 // picks tap (2,2)'s values out of its own load (no ds_bpermute), the 1 / 255 rides in the final unscale.  Bit-identical to
 // stem_h3u_kernel + s2h_kernel.
-typedef unsigned yfv2_u3x __attribute__((ext_vector_type(3)));
 namespace {
-struct FCol8 { unsigned p01, p23, m; };
-__device__ __forceinline__ unsigned f_u8pair(unsigned hi, unsigned lo, unsigned sel) {
-  const unsigned v = __builtin_amdgcn_perm(hi, lo, sel) | 0x64006400u;
-  const yfv2_h2 h = __builtin_bit_cast(yfv2_h2, v) - (yfv2_h2){(_Float16)1024.0f, (_Float16)1024.0f};
-  return __builtin_bit_cast(unsigned, h);
-}
-__device__ __forceinline__ void f_split_u8(const yfv2_u3x d, unsigned sel_a, unsigned sel_b, FCol8& o) {
-  o.p01 = f_u8pair(d[1], d[0], sel_a);
-  o.p23 = f_u8pair(d[2], d[1], sel_b);
-}
-__device__ __forceinline__ void f_conv_col8(const FCol8& x0, const FCol8& x1, const FCol8& x2, const yfv2_h8 (&wa)[2][2], const f32x4 sh0, const f32x4 sh1,
+__device__ __forceinline__ void f_conv_col8(const Row8& x0, const Row8& x1, const Row8& x2, const yfv2_h8 (&wa)[2][2], const f32x4 sh0, const f32x4 sh1,
                                             f32x4 (&ae)[2], f32x4 (&ao)[2]) {
-  const u32x4 e = {x0.p01, x1.p01, f_hi_hi(x0.m, x1.m), f_hi_lo(x2.m, x2.p01)};
-  const u32x4 o = {x0.p23, x1.p23, f_hi_hi(x0.p01, x1.p01), f_hi_lo(x2.p01, x2.p23)};
+  const u32x4 e = {x0.p01, x1.p01, pack_hi_hi(x0.m, x1.m), pack_hi_lo(x2.m, x2.p01)};
+  const u32x4 o = {x0.p23, x1.p23, pack_hi_hi(x0.p01, x1.p01), pack_hi_lo(x2.p01, x2.p23)};
   const yfv2_h8 be = __builtin_bit_cast(yfv2_h8, e), bo = __builtin_bit_cast(yfv2_h8, o);
   ae[0] = sh0; ae[1] = sh1; ao[0] = sh0; ao[1] = sh1;
 #pragma unroll
@@ -608,8 +533,8 @@ __global__ __launch_bounds__(256, 2) void front2_kernel(FrontArgs fa) {
   struct InSet { f32x4 a[4], b[4]; };                 // (uint8: the first three dwords of each hold the 12-byte load)
   auto load_ab = [&](int off, f32x4& va, f32x4& vb) {
     if constexpr (U8) {
-      const yfv2_u3x ua = __builtin_bit_cast(yfv2_u3x, __builtin_amdgcn_raw_buffer_load_b96(rx, off, 0, 0));
-      const yfv2_u3x ub = __builtin_bit_cast(yfv2_u3x, __builtin_amdgcn_raw_buffer_load_b96(rx, off, 12, 0));
+      const u32x3 ua = __builtin_bit_cast(u32x3, __builtin_amdgcn_raw_buffer_load_b96(rx, off, 0, 0));
+      const u32x3 ub = __builtin_bit_cast(u32x3, __builtin_amdgcn_raw_buffer_load_b96(rx, off, 12, 0));
       va = __builtin_bit_cast(f32x4, (u32x4){ua[0], ua[1], ua[2], 0u}); vb = __builtin_bit_cast(f32x4, (u32x4){ub[0], ub[1], ub[2], 0u});
     } else {
       va = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rx, off, 0, 0));
@@ -632,15 +557,15 @@ __global__ __launch_bounds__(256, 2) void front2_kernel(FrontArgs fa) {
   };
   // one conv row of both pooled columns from the carried rows (cA, cB) and the fresh rows r1 (2c), r2 (2c + 1) -> horizontally
   // pooled raw values (BN shift inside, pre-ReLU, x 2^(sw+8)); cA, cB <- the split row 2c + 1
-  auto conv_row2 = [&](FCol& cA, FCol& cB, f32x4 r1A, f32x4 r2A, f32x4 r1B, f32x4 r2B, f32x4 (&hA)[2], f32x4 (&hB)[2]) {
+  auto conv_row2 = [&](Row16& cA, Row16& cB, f32x4 r1A, f32x4 r2A, f32x4 r1B, f32x4 r2B, f32x4 (&hA)[2], f32x4 (&hB)[2]) {
     if constexpr (U8) {
       // (the carried columns live in the first term's slots of cA / cB: p01[0], p23[0], m[0])
       const u32x4 q1A = __builtin_bit_cast(u32x4, r1A), q2A = __builtin_bit_cast(u32x4, r2A), q1B = __builtin_bit_cast(u32x4, r1B), q2B = __builtin_bit_cast(u32x4, r2B);
-      const yfv2_u3x d1A = {q1A[0], q1A[1], q1A[2]}, d2A = {q2A[0], q2A[1], q2A[2]}, d1B = {q1B[0], q1B[1], q1B[2]}, d2B = {q2B[0], q2B[1], q2B[2]};
-      FCol8 x0A = {cA.p01[0], cA.p23[0], cA.m[0]}, x0B = {cB.p01[0], cB.p23[0], cB.m[0]}, x1A, x2A, x1B, x2B;
-      f_split_u8(g == 3 ? d2A : d1A, sel1a, sel1b, x1A); f_split_u8(d2A, sel2a, sel2b, x2A);
-      f_split_u8(g == 3 ? d2B : d1B, sel1a, sel1b, x1B); f_split_u8(d2B, sel2a, sel2b, x2B);
-      x1A.m = f_dpp_shr1_u(x1B.p23); x2A.m = f_dpp_shr1_u(x2B.p23);
+      const u32x3 d1A = {q1A[0], q1A[1], q1A[2]}, d2A = {q2A[0], q2A[1], q2A[2]}, d1B = {q1B[0], q1B[1], q1B[2]}, d2B = {q2B[0], q2B[1], q2B[2]};
+      Row8 x0A = {cA.p01[0], cA.p23[0], cA.m[0]}, x0B = {cB.p01[0], cB.p23[0], cB.m[0]}, x1A, x2A, x1B, x2B;
+      split_cols_u8(g == 3 ? d2A : d1A, sel1a, sel1b, x1A); split_cols_u8(d2A, sel2a, sel2b, x2A);
+      split_cols_u8(g == 3 ? d2B : d1B, sel1a, sel1b, x1B); split_cols_u8(d2B, sel2a, sel2b, x2B);
+      x1A.m = row_shr1(x1B.p23); x2A.m = row_shr1(x2B.p23);
       x1B.m = x1A.p23; x2B.m = x2A.p23;
       f32x4 aeA[2], aoA[2], aeB[2], aoB[2];
       {
@@ -654,29 +579,29 @@ __global__ __launch_bounds__(256, 2) void front2_kernel(FrontArgs fa) {
       for (int t = 0; t < 2; ++t)
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          hA[t][e] = __builtin_fmaxf(__builtin_fmaxf(f_dpp_shr1_f(aoB[t][e]), aeA[t][e]), aoA[t][e]);
+          hA[t][e] = __builtin_fmaxf(__builtin_fmaxf(row_shr1(aoB[t][e]), aeA[t][e]), aoA[t][e]);
           hB[t][e] = __builtin_fmaxf(__builtin_fmaxf(aoA[t][e], aeB[t][e]), aoB[t][e]);
         }
       return;
     }
     {   // lane group 3: tap (2, 2) of the three channels = columns + 1 | + 3 of row 2c + 1, out of the registers of lanes (l, 0..2)
-      const int a1 = f_f2i(r2A[1]), a3 = f_f2i(r2A[3]), b1 = f_f2i(r2B[1]), b3 = f_f2i(r2B[3]);
+      const int a1 = f2i(r2A[1]), a3 = f2i(r2A[3]), b1 = f2i(r2B[1]), b3 = f2i(r2B[3]);
       const int e0 = __builtin_amdgcn_ds_bpermute(src0, a1), e1 = __builtin_amdgcn_ds_bpermute(src1, a1), e2 = __builtin_amdgcn_ds_bpermute(src2, a1);
       const int q0 = __builtin_amdgcn_ds_bpermute(src0, a3), q1 = __builtin_amdgcn_ds_bpermute(src1, a3), q2 = __builtin_amdgcn_ds_bpermute(src2, a3);
       const int f0 = __builtin_amdgcn_ds_bpermute(src0, b1), f1 = __builtin_amdgcn_ds_bpermute(src1, b1), f2 = __builtin_amdgcn_ds_bpermute(src2, b1);
       const int u0 = __builtin_amdgcn_ds_bpermute(src0, b3), u1 = __builtin_amdgcn_ds_bpermute(src1, b3), u2 = __builtin_amdgcn_ds_bpermute(src2, b3);
       if (g == 3) {
-        r1A = (f32x4){f_i2f(e0), f_i2f(e1), f_i2f(q0), f_i2f(q1)};
-        r2A = (f32x4){f_i2f(e2), 0.f, f_i2f(q2), 0.f};
-        r1B = (f32x4){f_i2f(f0), f_i2f(f1), f_i2f(u0), f_i2f(u1)};
-        r2B = (f32x4){f_i2f(f2), 0.f, f_i2f(u2), 0.f};
+        r1A = (f32x4){i2f(e0), i2f(e1), i2f(q0), i2f(q1)};
+        r2A = (f32x4){i2f(e2), 0.f, i2f(q2), 0.f};
+        r1B = (f32x4){i2f(f0), i2f(f1), i2f(u0), i2f(u1)};
+        r2B = (f32x4){i2f(f2), 0.f, i2f(u2), 0.f};
       }
     }
-    FCol x1A, x2A, x1B, x2B;
-    f_split(r1A, x1A); f_split(r2A, x2A); f_split(r1B, x1B); f_split(r2B, x2B);
+    Row16 x1A, x2A, x1B, x2B;
+    split_cols(r1A, x1A); split_cols(r2A, x2A); split_cols(r1B, x1B); split_cols(r2B, x2B);
 #pragma unroll
     for (int k = 0; k < 2; ++k) {
-      x1A.m[k] = f_dpp_shr1_u(x1B.p23[k]); x2A.m[k] = f_dpp_shr1_u(x2B.p23[k]);   // the column left of A: the left lane's B
+      x1A.m[k] = row_shr1(x1B.p23[k]); x2A.m[k] = row_shr1(x2B.p23[k]);   // the column left of A: the left lane's B
       x1B.m[k] = x1A.p23[k]; x2B.m[k] = x2A.p23[k];                               // the column left of B: this lane's A
     }
     f32x4 aeA[2], aoA[2], aeB[2], aoB[2];
@@ -692,11 +617,11 @@ __global__ __launch_bounds__(256, 2) void front2_kernel(FrontArgs fa) {
     for (int t = 0; t < 2; ++t)
 #pragma unroll
       for (int e = 0; e < 4; ++e) {   // 0 from the DPP at the image's left edge stands for the -inf padding: ReLU follows the pooling
-        hA[t][e] = __builtin_fmaxf(__builtin_fmaxf(f_dpp_shr1_f(aoB[t][e]), aeA[t][e]), aoA[t][e]);
+        hA[t][e] = __builtin_fmaxf(__builtin_fmaxf(row_shr1(aoB[t][e]), aeA[t][e]), aoA[t][e]);
         hB[t][e] = __builtin_fmaxf(__builtin_fmaxf(aoA[t][e], aeB[t][e]), aoB[t][e]);
       }
   };
-  FCol cA, cB;
+  Row16 cA, cB;
   f32x4 upA[2], upB[2];
   // pooled row from its input set -> X[2 t + c] as s2h_kernel's load_row delivers it
   auto pooled = [&](InSet& s, f32x4 (&X)[4], int rnext) {
@@ -767,15 +692,15 @@ __global__ __launch_bounds__(256, 2) void front2_kernel(FrontArgs fa) {
       issue(r0 - 1, s0);                            // rows 4 r0 - 4 .. 4 r0 - 1 (the first of them is not needed)
       if constexpr (U8) {                           // a carried row is an X2 (stem_h3u_kernel)
         const u32x4 qa = __builtin_bit_cast(u32x4, s0.a[1]), qb = __builtin_bit_cast(u32x4, s0.b[1]);
-        FCol8 ta, tb;
-        f_split_u8((yfv2_u3x){qa[0], qa[1], qa[2]}, sel2a, sel2b, ta); f_split_u8((yfv2_u3x){qb[0], qb[1], qb[2]}, sel2a, sel2b, tb);
-        ta.m = f_dpp_shr1_u(tb.p23); tb.m = ta.p23;
+        Row8 ta, tb;
+        split_cols_u8((u32x3){qa[0], qa[1], qa[2]}, sel2a, sel2b, ta); split_cols_u8((u32x3){qb[0], qb[1], qb[2]}, sel2a, sel2b, tb);
+        ta.m = row_shr1(tb.p23); tb.m = ta.p23;
         cA.p01[0] = ta.p01; cA.p23[0] = ta.p23; cA.m[0] = ta.m; cB.p01[0] = tb.p01; cB.p23[0] = tb.p23; cB.m[0] = tb.m;
         cA.p01[1] = cA.p23[1] = cA.m[1] = 0u; cB.p01[1] = cB.p23[1] = cB.m[1] = 0u;
       } else {
-        f_split(s0.a[1], cA); f_split(s0.b[1], cB);
+        split_cols(s0.a[1], cA); split_cols(s0.b[1], cB);
 #pragma unroll
-        for (int k = 0; k < 2; ++k) { cA.m[k] = f_dpp_shr1_u(cB.p23[k]); cB.m[k] = cA.p23[k]; }
+        for (int k = 0; k < 2; ++k) { cA.m[k] = row_shr1(cB.p23[k]); cB.m[k] = cA.p23[k]; }
       }
       conv_row2(cA, cB, s0.a[2], s0.a[3], s0.b[2], s0.b[3], upA, upB);
       __builtin_amdgcn_sched_barrier(0);
@@ -788,7 +713,7 @@ __global__ __launch_bounds__(256, 2) void front2_kernel(FrontArgs fa) {
       // band 0: pooled row -1 is the block's zero padding; the stem starts above the image (zero carried row, zero maxima: the
       // post-ReLU equivalent of the max-pool's padding)
       issue(0, s0);
-      f_split((f32x4){0.f, 0.f, 0.f, 0.f}, cA); cB = cA;
+      split_cols((f32x4){0.f, 0.f, 0.f, 0.f}, cA); cB = cA;
 #pragma unroll
       for (int k = 0; k < 2; ++k) { cA.m[k] = 0u; cB.m[k] = 0u; }
 #pragma unroll
@@ -908,7 +833,7 @@ namespace {
 __device__ __forceinline__ void pw_h3_48(const float* W, int lane, const f32x2 (&in)[6], const f32x4 (&init)[3], f32x4 (&acc)[3], Yfv2Watch& watch) {
   u32x4 b1[2] = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}}, b2[2] = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}};
 #pragma unroll
-  for (int k = 0; k < 6; ++k) { unsigned h1, h2; split2(in[k], h1, h2); b1[k >> 2][k & 3] = h1; b2[k >> 2][k & 3] = h2; }
+  for (int k = 0; k < 6; ++k) { const u32x2 h = split_f16x2(in[k]); b1[k >> 2][k & 3] = h[0]; b2[k >> 2][k & 3] = h[1]; }
   const u32x4* Wq = reinterpret_cast<const u32x4*>(W) + lane;
 #pragma unroll
   for (int t = 0; t < 3; ++t) acc[t] = init[t];
@@ -1142,7 +1067,7 @@ __device__ __forceinline__ void pw_h3_96(const float* W, int lane, const f32x2 (
   for (int c = 0; c < 3; ++c) {
     u32x4 b1, b2;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) { unsigned h1, h2; split2(in[4 * c + k], h1, h2); b1[k] = h1; b2[k] = h2; }
+    for (int k = 0; k < 4; ++k) { const u32x2 h = split_f16x2(in[4 * c + k]); b1[k] = h[0]; b2[k] = h[1]; }
     const yfv2_h8 x1 = __builtin_bit_cast(yfv2_h8, b1), x2 = __builtin_bit_cast(yfv2_h8, b2);
     yfv2_h8 wa[6][2];
 #pragma unroll

@@ -14,14 +14,8 @@
 //
 // This file is compiled with -fno-honor-nans: max-pooling is v_max3_f32 chains on MFMA results and
 // the default NaN-quieting canonicalisation (v_max x, x, x before every max) doubles their cost.
-#include "yfv2_internal.h"
+#include "yfv2_device.h"
 #include <utility>
-
-// NB: pass the value through a by-value float parameter: __builtin_bit_cast applied directly to a vector
-// ELEMENT lvalue (bit_cast(int, q[3])) reads element 0 with this compiler (seen in tools/ubench/dpp.hip).
-__device__ __forceinline__ float yfv2_row_shr1(float v) {   // lane l <- lane l-1 inside its 16-lane row, 0 at r = 0
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x111, 0xf, 0xf, true));
-}
 
 // ----------------------------------------------------------------------------
 // lane = pooled column (two conv columns per lane), 16-lane rows = independent strips
@@ -134,7 +128,7 @@ __global__ __launch_bounds__(64, 1) void stem_px_kernel(StemArgs a) {
       } else {
         v[0] = raw.f[ci][0]; v[1] = raw.f[ci][1]; v[2] = raw.f[ci][2]; v[3] = raw.f[ci][3];
       }
-      o.v[ci][0] = yfv2_row_shr1(v[3]);
+      o.v[ci][0] = row_shr1(v[3]);
       o.v[ci][1] = v[0]; o.v[ci][2] = v[1]; o.v[ci][3] = v[2]; o.v[ci][4] = v[3];
     }
   };
@@ -180,7 +174,7 @@ __global__ __launch_bounds__(64, 1) void stem_px_kernel(StemArgs a) {
       for (int e = 0; e < 4; ++e) {
         const float m1 = __builtin_fmaxf(__builtin_fmaxf(cv1[m][e], A[m][e]), B[m][e]);
         cv1[m][e] = B[m][e];
-        const float lf = yfv2_row_shr1(m1);
+        const float lf = row_shr1(m1);
         const float hm = __builtin_fmaxf(__builtin_fmaxf(m0[m][e], m1), lf);
         o[e] = __builtin_amdgcn_fmed3f(hm, 0.f, __builtin_inff());   // ReLU
       }

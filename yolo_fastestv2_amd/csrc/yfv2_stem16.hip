@@ -48,46 +48,16 @@
 // register cap spills (258 us); by buffer stores with 32-bit offsets instead of 64-bit pointers (124 VGPRs, no spills): no
 // change (131-133 against 128-132 us, same box) - bytes in flight are not what limits it; 4, 2 or 11 bands per image
 // instead of 8: 126-131.
-#include "yfv2_internal.h"
-
-typedef _Float16 yfv2_h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 yfv2_h2 __attribute__((ext_vector_type(2)));
-typedef unsigned yfv2_u3 __attribute__((ext_vector_type(3)));
-typedef unsigned yfv2_u2 __attribute__((ext_vector_type(2)));
+#include "yfv2_device.h"
 
 namespace {
-
-__device__ __forceinline__ unsigned dpp_row_shr1_u(unsigned v) {   // lane l <- lane l-1 inside its 16-lane row, 0 at p = 0
-  return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xf, 0xf, true);
-}
-__device__ __forceinline__ int f2i(float v) { return __builtin_bit_cast(int, v); }
-__device__ __forceinline__ float i2f(int v) { return __builtin_bit_cast(float, v); }
-__device__ __forceinline__ float dpp_row_shr1_f(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x111, 0xf, 0xf, true));
-}
-// two fp32 -> (h1, h2) packed pairs; h1 + h2 reproduces each value to 2^-24 (see header)
-__device__ __forceinline__ void split2(float a, float b, unsigned& h1, unsigned& h2) {
-  const f32x2 v = (f32x2){a, b} * 256.0f;                                        // exact; undone with the filter's 2^-sw
-  const yfv2_h2 t1 = __builtin_convertvector(v, yfv2_h2);                       // v_cvt_pk_f16_f32 (RN)
-  const f32x2 r = v - __builtin_convertvector(t1, f32x2);                       // exact
-  const yfv2_h2 t2 = __builtin_convertvector(r, yfv2_h2);
-  h1 = __builtin_bit_cast(unsigned, t1);
-  h2 = __builtin_bit_cast(unsigned, t2);
-}
-// low halves / high halves / mixed picks of two packed registers
-__device__ __forceinline__ unsigned pack_hi_hi(unsigned a, unsigned b) { return __builtin_amdgcn_perm(b, a, 0x07060302u); }   // {a.hi, b.hi}
-__device__ __forceinline__ unsigned pack_hi_lo(unsigned a, unsigned b) { return __builtin_amdgcn_perm(b, a, 0x05040302u); }   // {a.hi, b.lo}
-
-struct Row16 {          // one input row of the lane, both terms: pairs (v0,v1), (v2,v3) and the left neighbour's v3 (in the HIGH half of m)
-  unsigned p01[2], p23[2], m[2];
-};
+// Row16 / Row8, split_cols and the two-term split itself are yfv2_device.h's (front2_kernel, yfv2_stage2h.hip, shares them); here a
+// row's left column comes from the left lane
 __device__ __forceinline__ void split_row(const f32x4 v, Row16& o) {
-  split2(v[0], v[1], o.p01[0], o.p01[1]);
-  split2(v[2], v[3], o.p23[0], o.p23[1]);
-  o.m[0] = dpp_row_shr1_u(o.p23[0]);     // high half = the neighbour's v3 = this lane's column 4px-1
-  o.m[1] = dpp_row_shr1_u(o.p23[1]);
+  split_cols(v, o);
+  o.m[0] = row_shr1(o.p23[0]);     // high half = the neighbour's v3 = this lane's column 4px-1
+  o.m[1] = row_shr1(o.p23[1]);
 }
-
 }  // namespace
 
 __global__ __launch_bounds__(64, 3) void stem_h3_kernel(StemArgs a) {
@@ -175,7 +145,7 @@ __global__ __launch_bounds__(64, 3) void stem_h3_kernel(StemArgs a) {
     for (int t = 0; t < 2; ++t)
 #pragma unroll
       for (int e = 0; e < 4; ++e)     // 0 from the DPP at the image's left edge stands for the -inf padding: ReLU follows the pooling
-        hp[t][e] = __builtin_fmaxf(__builtin_fmaxf(dpp_row_shr1_f(ao[t][e]), ae[t][e]), ao[t][e]);
+        hp[t][e] = __builtin_fmaxf(__builtin_fmaxf(row_shr1(ao[t][e]), ae[t][e]), ao[t][e]);
   };
 
   // carried: hp of the odd conv row above the current pooled row (0 above the image: post-ReLU equivalent of the padding),
@@ -243,17 +213,9 @@ __global__ __launch_bounds__(64, 3) void stem_h3_kernel(StemArgs a) {
 // conversion instruction: 0x6400 | n is the fp16 number 1024 + n, one packed subtract gives n.  381 MB of input become 95.
 
 namespace {
-struct Row8 { unsigned p01, p23, m; };   // (v0,v1), (v2,v3) as fp16 pairs; m: high half = the left neighbour's v3
-// bytes sel.b0 and sel.b2 of the eight bytes {hi, lo} -> two exact fp16 integers
-__device__ __forceinline__ unsigned u8pair(unsigned hi, unsigned lo, unsigned sel) {
-  const unsigned v = __builtin_amdgcn_perm(hi, lo, sel) | 0x64006400u;
-  const yfv2_h2 h = __builtin_bit_cast(yfv2_h2, v) - (yfv2_h2){(_Float16)1024.0f, (_Float16)1024.0f};
-  return __builtin_bit_cast(unsigned, h);
-}
-__device__ __forceinline__ void split_row_u8(const yfv2_u3 d, unsigned sel_a, unsigned sel_b, Row8& o) {
-  o.p01 = u8pair(d[1], d[0], sel_a);
-  o.p23 = u8pair(d[2], d[1], sel_b);
-  o.m = dpp_row_shr1_u(o.p23);
+__device__ __forceinline__ void split_row_u8(const u32x3 d, unsigned sel_a, unsigned sel_b, Row8& o) {
+  split_cols_u8(d, sel_a, sel_b, o);
+  o.m = row_shr1(o.p23);
 }
 }  // namespace
 
@@ -298,14 +260,14 @@ __global__ __launch_bounds__(64, 4) void stem_h3u_kernel(StemArgs a) {
   const f32x4 sh0 = *reinterpret_cast<const f32x4*>(cst + 4 * g), sh1 = *reinterpret_cast<const f32x4*>(cst + 16 + 4 * g);
   const float unscale = cst[32];
 
-  auto load_row = [&](int r) -> yfv2_u3 {
+  auto load_row = [&](int r) -> u32x3 {
     const int off = (lane_off != OOB && r >= 0) ? lane_off + r * rowb : OOB;
-    return __builtin_bit_cast(yfv2_u3, __builtin_amdgcn_raw_buffer_load_b96(rsrc, off, 0, 0));
+    return __builtin_bit_cast(u32x3, __builtin_amdgcn_raw_buffer_load_b96(rsrc, off, 0, 0));
   };
-  auto load2 = [&](int y, yfv2_u3 (&raw)[2]) { raw[0] = load_row(2 * y); raw[1] = load_row(2 * y + 1); };
+  auto load2 = [&](int y, u32x3 (&raw)[2]) { raw[0] = load_row(2 * y); raw[1] = load_row(2 * y + 1); };
 
-  auto conv_row = [&](Row8& x0, const yfv2_u3 (&raw)[2], f32x4 (&hp)[2]) {
-    const yfv2_u3 s1 = g == 3 ? raw[1] : raw[0];
+  auto conv_row = [&](Row8& x0, const u32x3 (&raw)[2], f32x4 (&hp)[2]) {
+    const u32x3 s1 = g == 3 ? raw[1] : raw[0];
     Row8 x1, x2;
     split_row_u8(s1, sel1a, sel1b, x1);
     split_row_u8(raw[1], sel2a, sel2b, x2);
@@ -322,15 +284,15 @@ __global__ __launch_bounds__(64, 4) void stem_h3u_kernel(StemArgs a) {
     for (int t = 0; t < 2; ++t)
 #pragma unroll
       for (int e2 = 0; e2 < 4; ++e2)
-        hp[t][e2] = __builtin_fmaxf(__builtin_fmaxf(dpp_row_shr1_f(ao[t][e2]), ae[t][e2]), ao[t][e2]);
+        hp[t][e2] = __builtin_fmaxf(__builtin_fmaxf(row_shr1(ao[t][e2]), ae[t][e2]), ao[t][e2]);
   };
 
   f32x4 up[2] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
   Row8 carry;
-  yfv2_u3 re0[2], ro0[2], re1[2], ro1[2];
+  u32x3 re0[2], ro0[2], re1[2], ro1[2];
   if (py0 > 0) {
-    yfv2_u3 hb[2];
-    const yfv2_u3 top = load_row(4 * py0 - 3);
+    u32x3 hb[2];
+    const u32x3 top = load_row(4 * py0 - 3);
     load2(2 * py0 - 1, hb);
     load2(2 * py0, re0);
     load2(2 * py0 + 1, ro0);
@@ -343,7 +305,7 @@ __global__ __launch_bounds__(64, 4) void stem_h3u_kernel(StemArgs a) {
   }
   float* __restrict__ ob = a.out + (((size_t)b * PH + py0) * PW + (st_ok ? px : 0)) * 24;
   const int ylast = (H >> 1) - 1;
-  auto step = [&](int t, const yfv2_u3 (&ce)[2], const yfv2_u3 (&co)[2], yfv2_u3 (&ne)[2], yfv2_u3 (&no)[2]) {
+  auto step = [&](int t, const u32x3 (&ce)[2], const u32x3 (&co)[2], u32x3 (&ne)[2], u32x3 (&no)[2]) {
     const int y = 2 * (py0 + t);
     load2(min(y + 2, ylast - 1), ne);
     load2(min(y + 3, ylast), no);

@@ -30,7 +30,7 @@
 // the workspace: every position stays below the frame's candidate count; the order is then simply not the stable sort.
 #include <hip/hip_runtime.h>
 
-#include "yfv2_internal.h"
+#include "yfv2_device.h"
 
 namespace {
 

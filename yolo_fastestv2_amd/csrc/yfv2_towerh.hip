@@ -31,36 +31,24 @@
 //     lane group) cost 33 k of the 84 k cycles of the 22x22 obj+cls launch.
 // Two barriers per chunk (input slice ready / exchange ready); the next chunk's slice is in flight in registers during
 // the pointwise phase, the next image's first slice during the last chunk.
-#include "yfv2_internal.h"
+#include "yfv2_device.h"
 #include <algorithm>
 #include <cstddef>
 #include <vector>
 
-typedef _Float16 yfv2_h4 __attribute__((ext_vector_type(4)));
-typedef _Float16 yfv2_h8 __attribute__((ext_vector_type(8)));
-typedef unsigned yfv2_u2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(4))) const f32x4 yfv2_cf4;   // constant address space: uniform loads become s_load
-
-#define YFV2_WSTAMP(i) do { if (a.trace && blockIdx.x == 0 && (threadIdx.x & 63) == 0) a.trace[64 + 32 * (threadIdx.x >> 6) + (i)] = (long long)__builtin_readcyclecounter(); } while (0)
 
 namespace {
 
-// f32x4 -> {h1.lo, h1.hi, h2.lo, h2.hi}: two fp16 terms per element, h1 + h2 = v to 2^-24 relative (v already carries 2^4)
-__device__ __forceinline__ u32x4 split4(f32x4 v) {
-  const yfv2_h4 t1 = __builtin_convertvector(v, yfv2_h4);                       // v_cvt_pk_f16_f32 (RN)
-  const f32x4 r = v - __builtin_convertvector(t1, f32x4);                       // exact
-  const yfv2_h4 t2 = __builtin_convertvector(r, yfv2_h4);
-  const yfv2_u2 a = __builtin_bit_cast(yfv2_u2, t1), b = __builtin_bit_cast(yfv2_u2, t2);
-  return (u32x4){a[0], a[1], b[0], b[1]};
-}
-// One 16-byte entry = {first fp16 term x4, second term x4} of four consecutive K positions.  v_mfma_f32_16x16x32_f16 gives a
+// One 16-byte entry = {first fp16 term x4, second term x4} of four consecutive K positions (split_f16x2's quad form, yfv2_device.h,
+// of values that already carry their 2^4).  v_mfma_f32_16x16x32_f16 gives a
 // lane 8 K slots: with the filter entry {w1, w2} as A and the data entry swapped to {x2, x1} as B, ONE instruction adds the
 // two cross products w1 x2 + w2 x1 of a 16-channel chunk; the main products w1 x1 of TWO chunks share another one.
 __device__ __forceinline__ yfv2_h8 pack8(unsigned a0, unsigned a1, unsigned b0, unsigned b1) { return __builtin_bit_cast(yfv2_h8, (u32x4){a0, a1, b0, b1}); }
 __device__ __forceinline__ f32x4 mfma_cross(u32x4 w, u32x4 x, f32x4 acc) {
   return __builtin_amdgcn_mfma_f32_16x16x32_f16(pack8(w[0], w[1], w[2], w[3]), pack8(x[2], x[3], x[0], x[1]), acc, 0, 0, 0);
 }
-__device__ __forceinline__ f32x4 mfma_main2(u32x4 wa, u32x4 wb, yfv2_u2 xa, u32x4 xb, f32x4 acc) {
+__device__ __forceinline__ f32x4 mfma_main2(u32x4 wa, u32x4 wb, u32x2 xa, u32x4 xb, f32x4 acc) {
   return __builtin_amdgcn_mfma_f32_16x16x32_f16(pack8(wa[0], wa[1], wb[0], wb[1]), pack8(xa[0], xa[1], xb[0], xb[1]), acc, 0, 0, 0);
 }
 __device__ __forceinline__ f32x4 mfma_main1(u32x4 w, u32x4 x, f32x4 acc) {    // the odd chunk out: upper K half of A = 0 (B's is finite)
@@ -181,7 +169,7 @@ __global__ __launch_bounds__(512) void towerh_kernel(TowerJobs jobs) {   // runs
   const __attribute__((address_space(4))) TowerArgs& ja = ((const __attribute__((address_space(4))) TowerArgs*)__builtin_amdgcn_kernarg_segment_ptr())[jidx];
   const yfv2_cf4* taps = (const yfv2_cf4*)(ja.img16 + th_lds_img(MH));
   int b = bid - jidx * gpj;
-  Yfv2Watch watch;                                             // range guard of the fp16x3 products (yfv2_internal.h)
+  Yfv2Watch watch;                                             // range guard of the fp16x3 products (yfv2_device.h)
   f32x4 pre[NPF];
   stage_load(ja.in, b < a.B ? b : 0, 0, pre);                  // the first slice flies during the job's prologue
 
@@ -238,9 +226,9 @@ __global__ __launch_bounds__(512) void towerh_kernel(TowerJobs jobs) {   // runs
     for (int mt = 0; mt < NA; ++mt)
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    yfv2_u2 xprev[NT];                                                     // first terms of the even chunk, for the pair's main-product MFMA
+    u32x2 xprev[NT];                                                     // first terms of the even chunk, for the pair's main-product MFMA
 #pragma unroll
-    for (int nt = 0; nt < NT; ++nt) xprev[nt] = (yfv2_u2){0u, 0u};
+    for (int nt = 0; nt < NT; ++nt) xprev[nt] = (u32x2){0u, 0u};
 #pragma unroll 1
     for (int s = 0; s < KC; ++s) {
       const bool dw_on = 4 * s + qq < C / 4;
@@ -288,7 +276,7 @@ __global__ __launch_bounds__(512) void towerh_kernel(TowerJobs jobs) {   // runs
           f32x4 u = __builtin_elementwise_fma(d[k / PS][k % PS], sc, sh);
 #pragma unroll
           for (int e = 0; e < 4; ++e) u[e] = u[e] > 0.f ? u[e] : 0.f;                    // (the BN constants carry the 2^4)
-          if (xdst[k] >= 0) *reinterpret_cast<u32x4*>(XB + xdst[k]) = split4(u);
+          if (xdst[k] >= 0) *reinterpret_cast<u32x4*>(XB + xdst[k]) = split_f16x2(u);
         }
       }
       if (DEFER && image_pending) {                                         // first chunk of the job's first image only
@@ -336,7 +324,7 @@ __global__ __launch_bounds__(512) void towerh_kernel(TowerJobs jobs) {   // runs
             const u32x4 w0 = *reinterpret_cast<const u32x4*>(WH + ((m * KC + s - 1) * 64 + lane) * 4);
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt)
-              acc[m][nt] = mfma_main2((u32x4){xprev[nt][0], xprev[nt][1], 0u, 0u}, xb[nt], (yfv2_u2){w0[0], w0[1]}, wf, acc[m][nt]);
+              acc[m][nt] = mfma_main2((u32x4){xprev[nt][0], xprev[nt][1], 0u, 0u}, xb[nt], (u32x2){w0[0], w0[1]}, wf, acc[m][nt]);
           } else if (s == KC - 1) {
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) acc[m][nt] = mfma_main1(xb[nt], wf, acc[m][nt]);
@@ -346,7 +334,7 @@ __global__ __launch_bounds__(512) void towerh_kernel(TowerJobs jobs) {   // runs
       }
       if (!(s & 1)) {
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) xprev[nt] = (yfv2_u2){xb[nt][0], xb[nt][1]};
+        for (int nt = 0; nt < NT; ++nt) xprev[nt] = (u32x2){xb[nt][0], xb[nt][1]};
       }
       YFV2_WSTAMP(4 + 3 * s);
     }
@@ -455,7 +443,7 @@ __global__ __launch_bounds__(512) void towers_kernel(TowerJobs jobs) {
   const bool pv = opix < HW;
   constexpr int N4 = LDS_IMG / 4, NIT = (N4 + 511) / 512;
   const __attribute__((address_space(4))) TowerArgs* kj = (const __attribute__((address_space(4))) TowerArgs*)__builtin_amdgcn_kernarg_segment_ptr();
-  Yfv2Watch watch;                                                // range guard of the fp16x3 products (yfv2_internal.h)
+  Yfv2Watch watch;                                                // range guard of the fp16x3 products (yfv2_device.h)
   f32x4 tmp[NIT];                                                 // the NEXT job's filter image, in flight while this job computes
   {
     const f32x4* src = reinterpret_cast<const f32x4*>(kj[0].img16);
@@ -586,7 +574,7 @@ __global__ __launch_bounds__(512) void towers_kernel(TowerJobs jobs) {
 #pragma unroll
     for (int sc = 0; sc < KC; ++sc) {
       const f32x4 v = 16 * sc + 4 * g < C ? *reinterpret_cast<const f32x4*>(X32 + opix * CP + 16 * sc + 4 * g) : (f32x4){0.f, 0.f, 0.f, 0.f};
-      xb[sc] = split4(v);
+      xb[sc] = split_f16x2(v);
     }
     if (MH == 0 || !ja.has_head) {
     f32x4 acc[KC];
@@ -601,7 +589,7 @@ __global__ __launch_bounds__(512) void towers_kernel(TowerJobs jobs) {
 #pragma unroll
         for (int sc = 0; sc < KC; ++sc) acc[mt] = mfma_cross(wf[sc], xb[sc], acc[mt]);
 #pragma unroll
-        for (int sc = 0; sc + 1 < KC; sc += 2) acc[mt] = mfma_main2(wf[sc], wf[sc + 1], (yfv2_u2){xb[sc][0], xb[sc][1]}, xb[sc + 1], acc[mt]);
+        for (int sc = 0; sc + 1 < KC; sc += 2) acc[mt] = mfma_main2(wf[sc], wf[sc + 1], (u32x2){xb[sc][0], xb[sc][1]}, xb[sc + 1], acc[mt]);
         acc[mt] = mfma_main1(wf[KC - 1], xb[KC - 1], acc[mt]);
       }
     }
@@ -651,7 +639,7 @@ __global__ __launch_bounds__(512) void towers_kernel(TowerJobs jobs) {
 #pragma unroll
         for (int sc = 0; sc + 1 < KC; sc += 2)
 #pragma unroll
-          for (int t = 0; t < TW; ++t) hacc[t] = mfma_main2(xb[sc], xb[sc + 1], (yfv2_u2){wf[t][sc][0], wf[t][sc][1]}, wf[t][sc + 1], hacc[t]);
+          for (int t = 0; t < TW; ++t) hacc[t] = mfma_main2(xb[sc], xb[sc + 1], (u32x2){wf[t][sc][0], wf[t][sc][1]}, wf[t][sc + 1], hacc[t]);
 #pragma unroll
         for (int t = 0; t < TW; ++t) hacc[t] = mfma_main1(xb[KC - 1], wf[t][KC - 1], hacc[t]);
 #pragma unroll
@@ -903,9 +891,9 @@ __global__ __launch_bounds__(512) void towerp_kernel(TowerJobs jobs) {
     for (int mt = 0; mt < NF; ++mt)
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt) acc[mt][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    yfv2_u2 xprev[NT];
+    u32x2 xprev[NT];
 #pragma unroll
-    for (int nt = 0; nt < NT; ++nt) xprev[nt] = (yfv2_u2){0u, 0u};
+    for (int nt = 0; nt < NT; ++nt) xprev[nt] = (u32x2){0u, 0u};
 
     // One chunk: [barrier] depthwise of slice s (both rounds of this wave's channel pair) [barrier] pointwise of slice s
     auto chunk = [&]<bool ODD, bool LAST>(int s, int stamp0) __attribute__((always_inline)) {
@@ -968,12 +956,9 @@ __global__ __launch_bounds__(512) void towerp_kernel(TowerJobs jobs) {
           for (int dx = 0; dx < 2; ++dx) {
             f32x2 u = __builtin_elementwise_fma(d[dy][dx], sc, sh);
             u[0] = u[0] > 0.f ? u[0] : 0.f; u[1] = u[1] > 0.f ? u[1] : 0.f;           // (the BN constants carry the 2^4)
-            typedef _Float16 h2_t __attribute__((ext_vector_type(2)));
-            const h2_t h1 = __builtin_convertvector(u, h2_t);
-            const f32x2 rr = u - __builtin_convertvector(h1, f32x2);                   // exact
-            const h2_t h2 = __builtin_convertvector(rr, h2_t);
-            rec[2 * dx] = __builtin_bit_cast(unsigned, h1);
-            rec[2 * dx + 1] = __builtin_bit_cast(unsigned, h2);
+            const u32x2 h = split_f16x2(u);
+            rec[2 * dx] = h[0];
+            rec[2 * dx + 1] = h[1];
           }
           const int q = (2 * py + dy) * W + 2 * pxx;
           *reinterpret_cast<u32x4*>(XB + (pvalid ? pair * TP_XS + 2 * q : xdump)) = rec;
@@ -1039,7 +1024,7 @@ __global__ __launch_bounds__(512) void towerp_kernel(TowerJobs jobs) {
           if constexpr (ODD) {
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt)
-              acc[m][nt] = mfma_main2((u32x4){xprev[nt][0], xprev[nt][1], 0u, 0u}, xb[nt], (yfv2_u2){w0[0], w0[1]}, wf, acc[m][nt]);
+              acc[m][nt] = mfma_main2((u32x4){xprev[nt][0], xprev[nt][1], 0u, 0u}, xb[nt], (u32x2){w0[0], w0[1]}, wf, acc[m][nt]);
           } else if constexpr (LAST) {
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) acc[m][nt] = mfma_main1(xb[nt], wf, acc[m][nt]);
@@ -1048,7 +1033,7 @@ __global__ __launch_bounds__(512) void towerp_kernel(TowerJobs jobs) {
       }
       if constexpr (!ODD) {
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt) xprev[nt] = (yfv2_u2){xb[nt][0], xb[nt][1]};
+        for (int nt = 0; nt < NT; ++nt) xprev[nt] = (u32x2){xb[nt][0], xb[nt][1]};
       }
       // the NEXT chunk's taps (of the next image's first chunk behind the last): requested here, behind this phase's last LDS
       // wait - scalar loads and LDS reads share one counter, a scalar load in flight turns every LDS wait into "wait for everything" -

@@ -24,7 +24,7 @@
 #include <vector>
 
 #include "../../include/yfv2.h"
-#include "yfv2_internal.h"
+#include "yfv2_device.h"
 #include "yfv2_pack.h"   // expected_numels
 
 namespace {
@@ -338,7 +338,6 @@ __global__ __launch_bounds__(256) void upsample2_bwd_kernel(V dsrc, V ddst, int 
 // Round 3 ran them on conv_fwd / conv_bwd_data / conv_bwd_weight_kernel above: one thread per output element looping over the
 // channels, one BLOCK per filter entry for the weight gradient (every block re-read the whole activation and gradient: 250-300 us
 // per layer whatever its size) - 13.6 + 21.2 ms of the 42 ms iteration at batch 64 (rocprofv3, tools/train_probe.py).
-typedef float yfv2_f4 __attribute__((ext_vector_type(4)));
 
 // out[b][r][p] (+)= sum_k Wm(r, k) in[b][k][p] (+ bias[r]);  Wm(r, k) = TRANS ? w[k * wld + r] : w[r * wld + k]
 //   forward:        in = x,     out = y,      w = (Cout, Cin), wld = Cin
@@ -353,11 +352,11 @@ __global__ __launch_bounds__(256) void pw_gemm_kernel(V in, V out, const float* 
   const int lane = threadIdx.x & 63, l = lane & 15, g = lane >> 4, wave = threadIdx.x >> 6;
   const int p0 = (blockIdx.x * 4 + wave) * 64, b = blockIdx.y, r0 = blockIdx.z * (16 * MT);
   if (p0 >= HW) return;
-  yfv2_f4 acc[MT][4];
+  f32x4 acc[MT][4];
 #pragma unroll
   for (int t = 0; t < MT; ++t)
 #pragma unroll
-    for (int e = 0; e < 4; ++e) acc[t][e] = (yfv2_f4){0.f, 0.f, 0.f, 0.f};
+    for (int e = 0; e < 4; ++e) acc[t][e] = (f32x4){0.f, 0.f, 0.f, 0.f};
   const float* inb = in.p + ((size_t)b * in.Ctot + in.coff) * HW;
   const size_t kstride = (size_t)in.cstride * HW;
   // A round = the operands of KS MFMA steps (16 input channels), requested before the MFMAs of the round before it run.  The
@@ -445,11 +444,11 @@ __global__ __launch_bounds__(64) void pw_wgrad_kernel(V x, V dy, double* __restr
 #pragma unroll 1
   for (int u = blockIdx.x * upw; u < min(units, (int)(blockIdx.x + 1) * upw); ++u) {
   const int b = u / nseg, q0 = (u - b * nseg) * seg, q1 = min(HW, q0 + seg);
-  yfv2_f4 acc[T][T];
+  f32x4 acc[T][T];
 #pragma unroll
   for (int i = 0; i < T; ++i)
 #pragma unroll
-    for (int j = 0; j < T; ++j) acc[i][j] = (yfv2_f4){0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < T; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
   const float* xb = x.p + ((size_t)b * x.Ctot + x.coff) * HW;
   const float* gb = dy.p + ((size_t)b * dy.Ctot + dy.coff) * HW;
   auto fetch = [&](int q, float (&av)[T][4], float (&bv)[T][4]) {
