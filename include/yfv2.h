@@ -317,6 +317,33 @@ YFV2_API int yfv2_detect_tiled_yuv(yfv2_handle h, const yfv2_frame_yuv* frames, 
                                    float conf_thres, double iou_thres, double merge_thres, int32_t merge_metric, int32_t max_out,
                                    float* dets, int32_t* src, int32_t* count, void* stream);
 
+/* ---- training batches from decoded frames: resize, contrast / brightness, NCHW fp32 in one launch ----
+ * replaces: utils/datasets.py:107-111 (cv2.resize, img_aug, transpose(2,0,1)) with :10-16 contrast_and_brightness - the only
+ * augmentation img_aug runs - and train.py:101 imgs.to(device).float() / 255.0, for B decoded frames of any sizes: dst is the
+ * (B, 3, cfg.height, cfg.width) fp32 tensor yfv2_train_forward takes.  No uint8 batch exists in memory.
+ * THE RULE, for both entry points: dst is bit-identical to yfv2_resize_frames_u8 / yfv2_resize_frames_yuv of the same frames,
+ * followed per byte a of frame b by
+ *     t = fl32(fl32(float(a) * alpha[b]) + beta[b])       two fp32 roundings, no fused multiply-add
+ *     q = rint_half_even(min(max(t, 0.f), 255.f))
+ *     x = fl32(float(q) / 255.f)                           IEEE-correct fp32 division = torch's .float() / 255.0
+ * and permute(0, 3, 1, 2): dst[b][c][y][x] is that of byte (b, y, x, c), c = 0, 1, 2 = B, G, R (tests/train_batch_model.py states
+ * it in numpy).  alpha = 1, beta = 0 is the identity (imgaug=False, the validation loader); alpha == beta == NULL means that for
+ * every frame.  The three lines are OpenCV's scalar saturate_cast<uchar>(a * alpha + 0 * (1 - alpha) + beta) for 8-bit
+ * addWeighted with the zero image of datasets.py:13.  OpenCV's own vector body fuses the multiply-add and its tail does not, so
+ * cv2 itself is not one function of the byte, and OpenCV is not in this image: parity with cv2 proper is unpinned, exactly as for
+ * the resize and the YUV conversion.  The draws of alpha and beta (random.uniform(0.25, 1.75) twice per image) stay the caller's.
+ * alpha, beta: HOST, B floats each; they travel with the frame descriptors in their one copy on `stream`.  dst: DEVICE, 16-byte
+ * aligned.  Checked before anything is enqueued (YFV2_ERR_ARG with a message): everything yfv2_resize_frames_u8 / _yuv checks of
+ * the frames, under a lower width limit - the row is staged in LDS as fp32: (160 KiB - 1024 - 12 cfg.width) / 6 - 6 pixels for
+ * B, G, R frames (26 426 at width 352), 39 641 for YUV frames at width 352; exactly one of alpha / beta NULL; an alpha or beta that is
+ * not finite (the message names the frame); dst NULL or not 16-byte aligned.  B > max_batch is YFV2_ERR_BATCH.  Enqueue only: no
+ * workspace, no device wait. */
+YFV2_API int yfv2_train_batch_frames_u8(yfv2_handle h, const yfv2_frame* frames, int32_t B,
+                                        const float* alpha, const float* beta /* HOST, B each, or both NULL */,
+                                        float* dst /* DEVICE (B,3,H,W), 16-byte aligned */, void* stream);
+YFV2_API int yfv2_train_batch_frames_yuv(yfv2_handle h, const yfv2_frame_yuv* frames, int32_t B,
+                                         const float* alpha, const float* beta, float* dst, void* stream);
+
 /* ---- the ncnn sample's deployment path (sample/ncnn/src/yolo-fastestv2.cpp) ----
  * The reference's only native component post-processes differently from its Python path in every step that decides which boxes
  * come out: no objectness pre-filter (score = cls * obj > thresh only), boxes scaled to the source frame and TRUNCATED TO int

@@ -10,6 +10,8 @@ anchor decode and class-aware NMS as hand-written HIP kernels behind a C ABI
     compute_loss(preds, targets, cfg, device)                       utils/loss.py:130   (training loss + its gradient w.r.t. the logits)
     ap_per_class_device(tp, conf, pred_cls, target_cls)              utils/utils.py:136  (the same 4-tuple, ranked and summed on the device)
     ap_per_class_multi_device(tpmask, conf, pred_cls, target_cls, K), evaluation_multi(...)  (the same at K IoU thresholds in one device pass)
+    datasets.TrainBatcher(engine, imgaug, rng)(frames, labels)      utils/datasets.py:70-75,107-120 + train.py:101 (decoded frames -> the
+                                                                                         training batch and its targets, on the device)
     genanchors.kmeans(X, centroids, eps, anchor_file, width, height) genanchors.py:67    (anchor k-means over a label set, + write_anchors_to_file,
                                                                                          read_label_dims, anchors_for_cfg, main)
 
@@ -29,6 +31,8 @@ from . import genanchors  # noqa: F401
 from . import tiling  # noqa: F401
 from . import ncnn_sample  # noqa: F401
 from . import yuv  # noqa: F401
+from . import datasets  # noqa: F401
+from .datasets import TrainBatcher, collate_targets, draw_contrast_brightness, read_label_file  # noqa: F401
 from .yuv import YuvFrame  # noqa: F401
 from .tiling import plan_tiles  # noqa: F401
 from .sharded import average_gradients_, detect_sharded, gather_decoded, gather_detections, shard_range  # noqa: F401

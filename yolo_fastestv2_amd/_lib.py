@@ -154,6 +154,8 @@ _PROTOTYPES = {
                                          C.c_void_p, C.c_void_p]),
     "yfv2_detect_tiled_yuv": (C.c_int, [C.c_void_p, C.POINTER(FrameYuv), C.c_int32, C.POINTER(Tile), C.c_int32, C.c_float, C.c_double, C.c_double,
                                         C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "yfv2_train_batch_frames_u8": (C.c_int, [C.c_void_p, C.POINTER(Frame), C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_void_p]),
+    "yfv2_train_batch_frames_yuv": (C.c_int, [C.c_void_p, C.POINTER(FrameYuv), C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_void_p]),
     "yfv2_export_maps": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "yfv2_deploy_post": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
                                    C.c_int32, C.c_void_p]),

@@ -240,9 +240,9 @@ int yfv2_create_ex(yfv2_handle* out, const yfv2_config* cfg, const yfv2_plan* pl
   int rc = setup_ctx(h, cfg, rows, alloc_buf);
   if (rc == YFV2_OK && hipMalloc(reinterpret_cast<void**>(&h->d_classes), 258 * sizeof(int32_t)) != hipSuccess)
     rc = fail(h, YFV2_ERR_DEVICE, "hipMalloc(class filter) failed");
-  if (rc == YFV2_OK && hipMalloc(reinterpret_cast<void**>(&h->d_frames), sizeof(ResizeFrame) * (size_t)cfg->max_batch) != hipSuccess)
+  if (rc == YFV2_OK && hipMalloc(reinterpret_cast<void**>(&h->d_frames), sizeof(TrainFrame) * (size_t)cfg->max_batch) != hipSuccess)
     rc = fail(h, YFV2_ERR_DEVICE, "hipMalloc(frame table) failed");
-  if (rc == YFV2_OK && hipMalloc(reinterpret_cast<void**>(&h->d_frames_yuv), sizeof(ResizeFrameYuv) * (size_t)cfg->max_batch) != hipSuccess)
+  if (rc == YFV2_OK && hipMalloc(reinterpret_cast<void**>(&h->d_frames_yuv), sizeof(TrainFrameYuv) * (size_t)cfg->max_batch) != hipSuccess)
     rc = fail(h, YFV2_ERR_DEVICE, "hipMalloc(YUV frame table) failed");
   if (rc == YFV2_OK) {
     h->d_stats_flag = h->d_classes + 256;

@@ -2,7 +2,8 @@
 // batches of frames, and tiled detection (tile plan, merge, both in one call).  The handle and the shared plumbing: yfv2_ctx.h.
 // Frames come in two kinds, yfv2_frame (packed B, G, R) and yfv2_frame_yuv (4:2:0 planes).  Each kind is described once
 // (BgrFrames, YuvFrames: what differs); check_frames<Kind> turns a caller's batch into a FrameBatch, enqueue_resize resizes
-// one, and resize_frames / detect_frames / detect_tiled are one template each.  The extern "C" functions pass their names.
+// one, enqueue_train_batch makes the training batch of one, and resize_frames / train_batch_frames / detect_frames /
+// detect_tiled are one template each.  The extern "C" functions pass their names.
 #include <algorithm>
 #include <cmath>
 
@@ -100,6 +101,10 @@ struct YuvFrames {
   }
 };
 
+// The training entry points take the same frames under the training kernels' own width limit (their LDS holds the row in fp32).
+struct TrainBgrFrames : BgrFrames { static int max_width(int W) { return yfv2_train_batch_max_width(W); } };
+struct TrainYuvFrames : YuvFrames { static int max_width(int W) { return yfv2_train_batch_yuv_max_width(W); } };
+
 // Ragged batches: every frame is checked here, before anything is enqueued, and expanded by its scales into fb.  The tables are
 // B entries of the handle's max_batch, so B is bound by max_batch on every entry point.
 template <class Kind>
@@ -127,17 +132,43 @@ static int check_frames(yfv2_handle h, const char* what, const typename Kind::Fr
   return YFV2_OK;
 }
 
-// Uploads the table the resize kernel of the batch's kind reads and enqueues that ONE launch into dst; everything was checked.
-static int enqueue_resize(yfv2_handle h, const FrameBatch& fb, int32_t B, uint8_t* dst, hipStream_t s) {
-  if (fb.yuv.empty()) {
-    HIP_TRY(h, hipMemcpyAsync(h->d_frames, fb.t.data(), sizeof(ResizeFrame) * (size_t)B, hipMemcpyHostToDevice, s));
-    yfv2_launch_resize_frames(h->d_frames, B, fb.max_w, dst, h->cfg.height, h->cfg.width, s);
-  } else {
-    HIP_TRY(h, hipMemcpyAsync(h->d_frames_yuv, fb.yuv.data(), sizeof(ResizeFrameYuv) * (size_t)B, hipMemcpyHostToDevice, s));
-    yfv2_launch_resize_frames_yuv(h->d_frames_yuv, B, fb.max_w, dst, h->cfg.height, h->cfg.width, s);
-  }
+// The submit of every frame batch: ONE copy of the descriptor table into the handle's table of its kind, ONE launch reading it.
+template <class D, class Launch>
+static int submit_frames(yfv2_handle h, const std::vector<D>& table, void* d_table, int32_t B, hipStream_t s, Launch launch) {
+  HIP_TRY(h, hipMemcpyAsync(d_table, table.data(), sizeof(D) * (size_t)B, hipMemcpyHostToDevice, s));
+  launch(static_cast<const D*>(d_table));
   HIP_TRY(h, hipGetLastError());
   return YFV2_OK;
+}
+
+// Uploads the table the resize kernel of the batch's kind reads and enqueues that ONE launch into dst; everything was checked.
+static int enqueue_resize(yfv2_handle h, const FrameBatch& fb, int32_t B, uint8_t* dst, hipStream_t s) {
+  const int H = h->cfg.height, W = h->cfg.width;
+  if (fb.yuv.empty())
+    return submit_frames(h, fb.t, h->d_frames, B, s, [&](const ResizeFrame* d) { yfv2_launch_resize_frames(d, B, fb.max_w, dst, H, W, s); });
+  return submit_frames(h, fb.yuv, h->d_frames_yuv, B, s, [&](const ResizeFrameYuv* d) { yfv2_launch_resize_frames_yuv(d, B, fb.max_w, dst, H, W, s); });
+}
+
+// The training batch of a checked frame batch: each descriptor with its frame's (alpha, beta) behind it (NULL, NULL: the identity),
+// through the same submit - the pair travels in the one descriptor copy.
+template <class T, class D>
+static std::vector<T> with_augment(const std::vector<D>& src, const float* alpha, const float* beta) {
+  std::vector<T> t(src.size());
+  for (size_t b = 0; b < src.size(); ++b) {
+    static_cast<D&>(t[b]) = src[b];
+    t[b].alpha = alpha ? alpha[b] : 1.0f;
+    t[b].beta = beta ? beta[b] : 0.0f;
+  }
+  return t;
+}
+
+static int enqueue_train_batch(yfv2_handle h, const FrameBatch& fb, int32_t B, const float* alpha, const float* beta, float* dst, hipStream_t s) {
+  const int H = h->cfg.height, W = h->cfg.width;
+  if (fb.yuv.empty())
+    return submit_frames(h, with_augment<TrainFrame>(fb.t, alpha, beta), h->d_frames, B, s,
+                         [&](const TrainFrame* d) { yfv2_launch_train_batch_frames(d, B, fb.max_w, dst, H, W, s); });
+  return submit_frames(h, with_augment<TrainFrameYuv>(fb.yuv, alpha, beta), h->d_frames_yuv, B, s,
+                       [&](const TrainFrameYuv* d) { yfv2_launch_train_batch_frames_yuv(d, B, fb.max_w, dst, H, W, s); });
 }
 
 template <class Kind>
@@ -149,6 +180,24 @@ static int resize_frames(yfv2_handle h, const char* what, const typename Kind::F
   if (int rc = check_frames<Kind>(h, what, frames, B, fb)) return rc;
   DeviceGuard guard(h->device);
   return enqueue_resize(h, fb, B, dst, static_cast<hipStream_t>(stream));
+}
+
+// yfv2_train_batch_frames_u8 / _yuv: its own arguments first, then check_frames, then each frame's pair; then the one submit.
+template <class Kind>
+static int train_batch_frames(yfv2_handle h, const char* what, const typename Kind::Frame* frames, int32_t B, const float* alpha, const float* beta,
+                              float* dst, void* stream) {
+  const std::string w_ = what;
+  if (!h) return fail(nullptr, YFV2_ERR_ARG, "null handle");
+  if (!dst) return fail(h, YFV2_ERR_ARG, w_ + ": null pointer");
+  if ((reinterpret_cast<uintptr_t>(dst) & 15) != 0) return fail(h, YFV2_ERR_ARG, w_ + ": dst must be 16-byte aligned");
+  if (!alpha != !beta) return fail(h, YFV2_ERR_ARG, w_ + ": alpha and beta must both be given or both be NULL");
+  FrameBatch fb;
+  if (int rc = check_frames<Kind>(h, what, frames, B, fb)) return rc;
+  for (int32_t b = 0; alpha && b < B; ++b)
+    if (!std::isfinite(alpha[b]) || !std::isfinite(beta[b]))
+      return fail(h, YFV2_ERR_ARG, w_ + ": frame " + std::to_string(b) + ": alpha and beta must be finite numbers");
+  DeviceGuard guard(h->device);
+  return enqueue_train_batch(h, fb, B, alpha, beta, dst, static_cast<hipStream_t>(stream));
 }
 
 // What every detection on frames does once they are checked and expanded: the handle's resized batch, the resize, then
@@ -202,6 +251,14 @@ int yfv2_resize_frames_u8(yfv2_handle h, const yfv2_frame* frames, int32_t B, ui
 
 int yfv2_resize_frames_yuv(yfv2_handle h, const yfv2_frame_yuv* frames, int32_t B, uint8_t* dst, void* stream) {
   return resize_frames<YuvFrames>(h, "yfv2_resize_frames_yuv", frames, B, dst, stream);
+}
+
+int yfv2_train_batch_frames_u8(yfv2_handle h, const yfv2_frame* frames, int32_t B, const float* alpha, const float* beta, float* dst, void* stream) {
+  return train_batch_frames<TrainBgrFrames>(h, "yfv2_train_batch_frames_u8", frames, B, alpha, beta, dst, stream);
+}
+
+int yfv2_train_batch_frames_yuv(yfv2_handle h, const yfv2_frame_yuv* frames, int32_t B, const float* alpha, const float* beta, float* dst, void* stream) {
+  return train_batch_frames<TrainYuvFrames>(h, "yfv2_train_batch_frames_yuv", frames, B, alpha, beta, dst, stream);
 }
 
 int yfv2_detect_frames_u8(yfv2_handle h, const yfv2_frame* frames, int32_t B, float conf_thres, double iou_thres, float* dets,

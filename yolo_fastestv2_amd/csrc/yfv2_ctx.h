@@ -115,8 +115,8 @@ struct yfv2_ctx {
   bool postfuse = true;     // yfv2_detect: decode + NMS as one launch (yfv2_plan.post_two_launches: two launches)
   int32_t* d_classes = nullptr;  // class filter scratch (<= 256 entries), then one int32 of its own for the statistics overflow flag
   int32_t* d_stats_flag = nullptr;  // = d_classes + 256
-  ResizeFrame* d_frames = nullptr;   // frame descriptors of yfv2_resize_frames_u8 / yfv2_detect_frames_u8 (max_batch entries)
-  ResizeFrameYuv* d_frames_yuv = nullptr;   // ... and of yfv2_resize_frames_yuv / yfv2_detect_frames_yuv (max_batch entries)
+  ResizeFrame* d_frames = nullptr;   // frame descriptors of yfv2_resize_frames_u8 / yfv2_detect_frames_u8 (max_batch entries of the widest form, TrainFrame)
+  ResizeFrameYuv* d_frames_yuv = nullptr;   // ... and of yfv2_resize_frames_yuv / yfv2_detect_frames_yuv (max_batch entries of TrainFrameYuv)
   DeviceBlock frames_u8;             // yfv2_detect_frames_u8's resized batch (max_batch, H, W, 3): allocated by its first call
   // tiled detection (yfv2_merge_tiles / yfv2_detect_tiled_u8).  tile_ws: the ordered candidate lists of tile_cap_t tiles (two float4
   // per row) and the tile / frame table of tile_cap_t + tile_cap_f entries; allocated by the first call, grown (one device wait) only by

@@ -365,6 +365,17 @@ size_t yfv2_resize_yuv_lds_bytes(int w, int W);   // LDS of one workgroup of the
 int yfv2_resize_yuv_max_width(int W);             // the widest frame whose workgroup fits YFV2_LDS_FULL
 YuvCoef yfv2_yuv_coef(int colour);                // YFV2_BT601_LIMITED .. YFV2_BT709_FULL -> its row
 void yfv2_launch_resize_frames_yuv(const ResizeFrameYuv* frames, int B, int max_w, unsigned char* dst, int H, int W, hipStream_t s);
+// The training entry points (yfv2_train_batch_frames_u8 / _yuv): a frame's resize descriptor with its contrast / brightness pair
+// behind it, in the same table and the same one copy (the handle's tables are sized for these).  The resize kernels keep their own
+// descriptors and strides; the training kernels run the same body on the base part.
+struct TrainFrame : ResizeFrame { float alpha, beta; };
+struct TrainFrameYuv : ResizeFrameYuv { float alpha, beta; };
+size_t yfv2_train_batch_lds_bytes(int SW, int W);   // LDS of one workgroup: the resize's staging slots, the 256-entry fp32 table, three fp32 planes of W
+int yfv2_train_batch_max_width(int W);              // (YFV2_LDS_FULL - 1024 - 12 W) / 6 - 6, below yfv2_resize_max_width(W)
+size_t yfv2_train_batch_yuv_lds_bytes(int w, int W);
+int yfv2_train_batch_yuv_max_width(int W);          // the widest YUV frame that fits, <= yfv2_resize_yuv_max_width(W)
+void yfv2_launch_train_batch_frames(const TrainFrame* frames, int B, int max_w, float* dst /* (B,3,H,W), 16-byte aligned */, int H, int W, hipStream_t s);
+void yfv2_launch_train_batch_frames_yuv(const TrainFrameYuv* frames, int B, int max_w, float* dst, int H, int W, hipStream_t s);
 // dets columns 0-3 of the first count[b] rows of frame b times frames[b].box_x / box_y (yfv2_post.hip)
 void yfv2_launch_frame_boxes(float* dets, const int32_t* count, const ResizeFrame* frames, int B, hipStream_t s);
 void yfv2_launch_decode(const DecodeArgs& a, hipStream_t s);

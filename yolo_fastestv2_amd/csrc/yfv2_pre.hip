@@ -53,6 +53,65 @@ __device__ __forceinline__ void yfv2_emit_row(const unsigned char* OUT, unsigned
   for (int i = threadIdx.x; i < (W * 3) >> 2; i += THREADS) drow[i] = reinterpret_cast<const unsigned*>(OUT)[i];
 }
 
+// ---- where a blended row of a ragged batch goes: the two epilogues of resize_frames_u8_kernel / resize_frames_yuv_kernel ----
+// Those kernels are templates over their frame descriptor and a Row.  The kernel hands the Row the LDS behind its staging slots
+// (ALIGN-byte aligned; the slots are rounded to it): begin, before the staging barrier; put, every blended byte (output column ox,
+// channel c); end, the row is complete.  Everything in front of the Row - staging, guards, coefficients, blend - is the one body.
+//
+// RowU8: the uint8 (B, H, W, 3) batch of the resize entry points.  The row is assembled in LDS and leaves through yfv2_emit_row.
+template <int THREADS>
+struct RowU8 {
+  using Out = unsigned char;
+  static constexpr int ALIGN = 4;
+  static constexpr bool AUGMENT = false;
+  unsigned char* dst;
+  __device__ __forceinline__ void put(unsigned char* lds, int ox, int c, int W, unsigned char v) { lds[ox * 3 + c] = v; }
+  __device__ __forceinline__ void end(const unsigned char* lds, int b, int oy, int H, int W) { yfv2_emit_row<THREADS>(lds, dst, b, oy, H, W); }
+};
+
+// THE AUGMENTATION TABLE (the specification; include/yfv2.h states it for callers, tests/train_batch_model.py in numpy): what
+// utils/datasets.py:10-16 contrast_and_brightness, then train.py:101's .float() / 255.0, make of byte a with the frame's (alpha, beta):
+//   t = fl32(fl32(float(a) * alpha) + beta)          two roundings, never an fma
+//   q = rint_half_even(min(max(t, 0), 255))
+//   table[a] = fl32(float(q) / 255)                  IEEE-correct fp32 division
+// which is OpenCV's scalar saturate_cast<uchar>(a * alpha + 0 * (1 - alpha) + beta) for 8-bit addWeighted (the zero image makes the
+// middle term exactly 0).  OpenCV's own vector body fuses the multiply-add and its tail does not, and OpenCV is not in this image:
+// parity with cv2 proper is unpinned, exactly as for the resize above.  alpha = 1, beta = 0 is the identity (imgaug=False).
+constexpr int YFV2_AUG_TABLE_BYTES = 256 * (int)sizeof(float);
+__device__ __forceinline__ float yfv2_aug_entry(int a, float alpha, float beta) {
+  const float t = __fadd_rn(__fmul_rn((float)a, alpha), beta);
+  const int q = __float2int_rn(fminf(fmaxf(t, 0.f), 255.f));
+  return __fdiv_rn((float)q, 255.f);
+}
+
+// RowTrain: the fp32 (B, 3, H, W) batch of the training entry points (train_batch_frames_u8_kernel / _yuv_kernel below).  Its LDS:
+// the frame's table, filled by the workgroup itself before the staging barrier, then the row as three planes of W floats - the
+// byte -> plane transposition: a thread's B, G, R of column ox go to planes[c][ox] (consecutive lanes, consecutive words).  After
+// a barrier the planes leave as 16-byte stores, three contiguous runs of W floats out[b][c][oy][0 .. W): W % 32 == 0 and dst is
+// 16-byte aligned, so every run is.
+template <int THREADS>
+struct RowTrain {
+  using Out = float;
+  static constexpr int ALIGN = 16;
+  static constexpr bool AUGMENT = true;
+  float* dst;
+  __device__ __forceinline__ void begin(unsigned char* lds, float alpha, float beta) {
+    for (int a = threadIdx.x; a < 256; a += THREADS) reinterpret_cast<float*>(lds)[a] = yfv2_aug_entry(a, alpha, beta);
+  }
+  __device__ __forceinline__ void put(unsigned char* lds, int ox, int c, int W, unsigned char byte) {
+    reinterpret_cast<float*>(lds + YFV2_AUG_TABLE_BYTES)[c * W + ox] = reinterpret_cast<const float*>(lds)[byte];
+  }
+  __device__ __forceinline__ void end(const unsigned char* lds, int b, int oy, int H, int W) {
+    __syncthreads();
+    const float4* planes = reinterpret_cast<const float4*>(lds + YFV2_AUG_TABLE_BYTES);
+    const int quads = W >> 2;                         // per plane
+    for (int i = threadIdx.x; i < 3 * quads; i += THREADS) {
+      const int c = i / quads, q = i - c * quads;
+      reinterpret_cast<float4*>(dst + (((size_t)b * 3 + c) * H + oy) * W)[q] = planes[i];
+    }
+  }
+};
+
 __global__ __launch_bounds__(256) void resize_u8_kernel(ResizeArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x;
@@ -108,18 +167,26 @@ __global__ __launch_bounds__(256) void resize_u8_kernel(ResizeArgs a) {
 // view (pitch > 3w) starting at any byte, and the bytes around it may belong to no allocation, so a dword is loaded whole only
 // when all four of its bytes lie in the frame's own extent [data, data + (h-1) pitch + 3w); any other dword is gathered byte by
 // byte from the bytes of it that do (tests/test_frames_host.py models this guard).  LDS is sized for the widest frame.
+// The kernel is a template over the descriptor and the epilogue (Row, above) - a template, not a shared function called by two
+// kernels: a function boundary alone reorders the uint8 instantiation's blend (profiles/train_batch_isa.txt), and the uint8
+// instantiation <ResizeFrame, RowU8> must stay the instruction stream it was.  <TrainFrame, RowTrain> is the training entry point's
+// launch (train_batch_frames_u8_kernel below): the same staging, guards, coefficients and blend, so its batch is the resize's
+// bytes looked up in the frame's table.
 constexpr int RF_THREADS = 128;   // 2 waves: 12 workgroups (rows) per CU fit the LDS of 1920-wide frames, 8 of 4 waves would
-__global__ __launch_bounds__(RF_THREADS, 6) void resize_frames_u8_kernel(const ResizeFrame* __restrict__ frames, unsigned char* __restrict__ dst, int H, int W) {
+template <class Frame, class Row>
+__global__ __launch_bounds__(RF_THREADS, 6) void resize_frames_u8_kernel(const Frame* __restrict__ frames, typename Row::Out* __restrict__ dst, int H, int W) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  Row row{dst};
   const int tid = threadIdx.x;
   const int b = blockIdx.x / H, oy = blockIdx.x - b * H;
-  const ResizeFrame f = frames[b];
+  const Frame f = frames[b];
   const RowCoef ry = yfv2_axis_coef(oy, f.scale_y, f.h, false);
   const int row_bytes = f.w * 3;
-  const int slot = (row_bytes + 3 + 3) & ~3;
+  const int slot = (row_bytes + 3 + Row::ALIGN - 1) & ~(Row::ALIGN - 1);
   unsigned char* R0 = smem;
   unsigned char* R1 = smem + slot;
   unsigned char* OUT = smem + 2 * slot;
+  if constexpr (Row::AUGMENT) row.begin(OUT, f.alpha, f.beta);
   const long long extent = (long long)(f.h - 1) * f.pitch + row_bytes;   // bytes of the frame from f.data on
   const long long g0 = (long long)ry.s0 * f.pitch, g1 = (long long)ry.s1 * f.pitch;
   const uintptr_t base = reinterpret_cast<uintptr_t>(f.data);
@@ -157,10 +224,13 @@ __global__ __launch_bounds__(RF_THREADS, 6) void resize_frames_u8_kernel(const R
     const RowCoef rx = yfv2_axis_coef(ox, f.scale_x, f.w, true);
 #pragma unroll
     for (int c = 0; c < 3; ++c)
-      OUT[ox * 3 + c] = yfv2_blend(r0[rx.s0 * 3 + c], r0[rx.s1 * 3 + c], r1[rx.s0 * 3 + c], r1[rx.s1 * 3 + c], rx, ry);
+      row.put(OUT, ox, c, W, yfv2_blend(r0[rx.s0 * 3 + c], r0[rx.s1 * 3 + c], r1[rx.s0 * 3 + c], r1[rx.s1 * 3 + c], rx, ry));
   }
-  yfv2_emit_row<RF_THREADS>(OUT, dst, b, oy, H, W);
+  row.end(OUT, b, oy, H, W);
 }
+
+// yfv2_train_batch_frames_u8's launch (a trace names it resize_frames_u8_kernel<TrainFrame, RowTrain<128>>)
+constexpr auto& train_batch_frames_u8_kernel = resize_frames_u8_kernel<TrainFrame, RowTrain<RF_THREADS>>;
 
 // ---- the same ragged batch from decoder-format frames: YUV 4:2:0 planes read in place (yfv2_resize_frames_yuv) ----
 // THE COLOUR FORMULA (the specification; include/yfv2.h states it for callers, tests/yuv_model.py in numpy).  All int32, SHIFT = 20,
@@ -208,24 +278,29 @@ __device__ __forceinline__ void yfv2_yuv_to_bgr(int Y, int U, int V, const YuvCo
 // 8).  The kernel needs 59 VGPRs, so the launch bound asks for all 8 waves per SIMD = those 16 workgroups: like its neighbour the
 // launch is a chain of round trips per workgroup (descriptor, staging loads, barrier, blend, barrier, stores), and what hides them is
 // workgroups in flight - measured 258 us at 8 waves per SIMD against 283 us at 6 on the probe's mix.
+// Like its neighbour a template over descriptor and epilogue: <ResizeFrameYuv, RowU8> is the resize, <TrainFrameYuv, RowTrain> the
+// training batch (train_batch_frames_yuv_kernel below; 43 VGPRs - the fp32 row goes to LDS where the uint8 row went).
 constexpr int RY_THREADS = 128;
-__global__ __launch_bounds__(RY_THREADS, 8) void resize_frames_yuv_kernel(const ResizeFrameYuv* __restrict__ frames, unsigned char* __restrict__ dst, int H, int W) {
+template <class Frame, class Row>
+__global__ __launch_bounds__(RY_THREADS, 8) void resize_frames_yuv_kernel(const Frame* __restrict__ frames, typename Row::Out* __restrict__ dst, int H, int W) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  Row row{dst};
   const int tid = threadIdx.x;
   const int b = blockIdx.x / H, oy = blockIdx.x - b * H;
-  const ResizeFrameYuv f = frames[b];
+  const Frame f = frames[b];
   const RowCoef ry = yfv2_axis_coef(oy, f.scale_y, f.h, false);
   const bool planar = f.format == YFV2_YUV_I420;
   const int cw = ((f.w - 1 + f.px) >> 1) + 1, ch = ((f.h - 1 + f.py) >> 1) + 1;   // chroma samples per row, chroma rows of the frame
   const int cbytes = planar ? cw : 2 * cw;
   const int cr0 = (ry.s0 + f.py) >> 1, cr1 = (ry.s1 + f.py) >> 1;
   const bool one_chroma_row = cr0 == cr1;
-  const int yslot = (f.w + 6) & ~3, chalf = ((f.w >> 1) + 7) & ~3;
+  const int yslot = (f.w + 3 + Row::ALIGN - 1) & ~(Row::ALIGN - 1), chalf = ((f.w >> 1) + 4 + Row::ALIGN - 1) & ~(Row::ALIGN - 1);
   unsigned char* LY0 = smem;
   unsigned char* LY1 = smem + yslot;
   unsigned char* LC0 = smem + 2 * yslot;
   unsigned char* LC1 = LC0 + 2 * chalf;
   unsigned char* OUT = LC0 + 4 * chalf;
+  if constexpr (Row::AUGMENT) row.begin(OUT, f.alpha, f.beta);
   const long long extent_y = (long long)(f.h - 1) * f.pitch_y + f.w;
   const long long extent_c = (long long)(ch - 1) * f.pitch_c + cbytes;
   // Six row segments: luma s0, s1; chroma plane a rows cr0, cr1; chroma plane b (I420's V) rows cr0, cr1.  A segment that is not
@@ -305,12 +380,22 @@ __global__ __launch_bounds__(RY_THREADS, 8) void resize_frames_yuv_kernel(const 
     yfv2_yuv_to_bgr(y1[rx.s0], pu1[j0], pv1[j0], kc, p10);
     yfv2_yuv_to_bgr(y1[rx.s1], pu1[j1], pv1[j1], kc, p11);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) OUT[ox * 3 + c] = yfv2_blend(p00[c], p01[c], p10[c], p11[c], rx, ry);
+    for (int c = 0; c < 3; ++c) row.put(OUT, ox, c, W, yfv2_blend(p00[c], p01[c], p10[c], p11[c], rx, ry));
   }
-  yfv2_emit_row<RY_THREADS>(OUT, dst, b, oy, H, W);
+  row.end(OUT, b, oy, H, W);
 }
 
+// yfv2_train_batch_frames_yuv's launch
+constexpr auto& train_batch_frames_yuv_kernel = resize_frames_yuv_kernel<TrainFrameYuv, RowTrain<RY_THREADS>>;
+
 size_t yfv2_resize_lds_bytes(int SW, int W) { return 2 * (size_t)((SW * 3 + 6) & ~3) + (size_t)W * 3; }
+
+// train_batch_frames_u8_kernel's LDS (RowTrain): the two staging slots rounded to 16 bytes, the table, the row as three fp32 planes
+size_t yfv2_train_batch_lds_bytes(int SW, int W) { return 2 * (size_t)((SW * 3 + 18) & ~15) + YFV2_AUG_TABLE_BYTES + (size_t)W * 12; }
+
+// ... and the width limit of yfv2_train_batch_frames_u8 in closed form: every row up to it fits (at W = 352 the widest, 26 426, fills
+// YFV2_LDS_FULL to the byte).  Below yfv2_resize_max_width(W) for every W: each frame the training entry point takes, the resize takes.
+int yfv2_train_batch_max_width(int W) { return (YFV2_LDS_FULL - YFV2_AUG_TABLE_BYTES - 12 * W) / 6 - 6; }
 
 // The width limit the ragged B, G, R entry points enforce and yfv2_resize_u8's message names, in closed form.  For W % 4 == 0 it is
 // one pixel below the widest row whose yfv2_resize_lds_bytes fits YFV2_LDS_FULL (27128 against 27129 at W = 352); yfv2_resize_u8
@@ -331,16 +416,38 @@ int yfv2_resize_yuv_max_width(int W) {
   return w;
 }
 
+// train_batch_frames_yuv_kernel's LDS, likewise: slots and half-slots rounded to 16 bytes, the table, the fp32 planes; and the
+// widest frame that fits, walked down from the resize's own limit (so never a frame that yfv2_resize_frames_yuv refuses)
+size_t yfv2_train_batch_yuv_lds_bytes(int w, int W) {
+  return 2 * (size_t)((w + 18) & ~15) + 4 * (size_t)(((w >> 1) + 19) & ~15) + YFV2_AUG_TABLE_BYTES + (size_t)W * 12;
+}
+
+int yfv2_train_batch_yuv_max_width(int W) {
+  int w = yfv2_resize_yuv_max_width(W);
+  while (w > 1 && yfv2_train_batch_yuv_lds_bytes(w, W) > (size_t)YFV2_LDS_FULL) --w;
+  return w;
+}
+
 void yfv2_launch_resize(const ResizeArgs& a, hipStream_t s) {
   YFV2_LAUNCH_LDS(yfv2_device(), resize_u8_kernel, YFV2_LDS_FULL, dim3((unsigned)(a.B * a.H)), dim3(256), yfv2_resize_lds_bytes(a.SW, a.W), s, a);
 }
 
 void yfv2_launch_resize_frames(const ResizeFrame* frames, int B, int max_w, unsigned char* dst, int H, int W, hipStream_t s) {
-  YFV2_LAUNCH_LDS(yfv2_device(), resize_frames_u8_kernel, YFV2_LDS_FULL, dim3((unsigned)(B * H)), dim3(RF_THREADS), yfv2_resize_lds_bytes(max_w, W), s,
+  YFV2_LAUNCH_LDS(yfv2_device(), (resize_frames_u8_kernel<ResizeFrame, RowU8<RF_THREADS>>), YFV2_LDS_FULL, dim3((unsigned)(B * H)), dim3(RF_THREADS), yfv2_resize_lds_bytes(max_w, W), s,
                   frames, dst, H, W);
 }
 
 void yfv2_launch_resize_frames_yuv(const ResizeFrameYuv* frames, int B, int max_w, unsigned char* dst, int H, int W, hipStream_t s) {
-  YFV2_LAUNCH_LDS(yfv2_device(), resize_frames_yuv_kernel, YFV2_LDS_FULL, dim3((unsigned)(B * H)), dim3(RY_THREADS), yfv2_resize_yuv_lds_bytes(max_w, W), s,
+  YFV2_LAUNCH_LDS(yfv2_device(), (resize_frames_yuv_kernel<ResizeFrameYuv, RowU8<RY_THREADS>>), YFV2_LDS_FULL, dim3((unsigned)(B * H)), dim3(RY_THREADS), yfv2_resize_yuv_lds_bytes(max_w, W), s,
+                  frames, dst, H, W);
+}
+
+void yfv2_launch_train_batch_frames(const TrainFrame* frames, int B, int max_w, float* dst, int H, int W, hipStream_t s) {
+  YFV2_LAUNCH_LDS(yfv2_device(), train_batch_frames_u8_kernel, YFV2_LDS_FULL, dim3((unsigned)(B * H)), dim3(RF_THREADS), yfv2_train_batch_lds_bytes(max_w, W), s,
+                  frames, dst, H, W);
+}
+
+void yfv2_launch_train_batch_frames_yuv(const TrainFrameYuv* frames, int B, int max_w, float* dst, int H, int W, hipStream_t s) {
+  YFV2_LAUNCH_LDS(yfv2_device(), train_batch_frames_yuv_kernel, YFV2_LDS_FULL, dim3((unsigned)(B * H)), dim3(RY_THREADS), yfv2_train_batch_yuv_lds_bytes(max_w, W), s,
                   frames, dst, H, W);
 }

@@ -279,6 +279,26 @@ class Engine:
         check(native(self._h, arr, B, _ptr(out), _stream(self.device)), self._h)
         return out
 
+    def _train_batch_frames(self, name, table, native, frames, alpha, beta, out):
+        arr, keep = table(frames)
+        B = len(keep)
+        if (alpha is None) != (beta is None):
+            raise ValueError("%s: alpha and beta must both be given or both be None" % name)
+        pair = [None, None]
+        for k, v in enumerate((alpha, beta)):
+            if v is not None:
+                v = [float(a) for a in (v.tolist() if hasattr(v, "tolist") else v)]
+                if len(v) != B:
+                    raise ValueError("%s: %s has %d entries for %d frames" % (name, ("alpha", "beta")[k], len(v), B))
+                pair[k] = (C.c_float * B)(*v)
+        self.ensure_batch(B)
+        if out is None:
+            out = torch.empty((B, 3, self.height, self.width), device=self.device, dtype=torch.float32)
+        elif out.dtype != torch.float32 or tuple(out.shape) != (B, 3, self.height, self.width) or out.device != self.device or not out.is_contiguous():
+            raise ValueError("out must be a contiguous fp32 (%d,3,%d,%d) tensor on %s" % (B, self.height, self.width, self.device))
+        check(native(self._h, arr, B, pair[0], pair[1], _ptr(out), _stream(self.device)), self._h)
+        return out
+
     def _detect_frames(self, name, table, native, frames, conf_thres, iou_thres, out, check):
         self._need_anchors(name)
         if check and self.peek_nonfinite():
@@ -319,6 +339,20 @@ class Engine:
         differ in size (test.py:34-35 per frame, include/yfv2.h yfv2_resize_frames_u8).  Frame b's output is bit-identical to
         resize() of that frame alone.  Grows max_batch like every batched call (the descriptor table has max_batch entries)."""
         return self._resize_frames(self._frame_table, _lib.lib().yfv2_resize_frames_u8, frames, out)
+
+    def train_batch_frames(self, frames, alpha=None, beta=None, out=None):
+        """The training batch of a list of decoded frames (what resize_frames takes): utils/datasets.py:107-111 and train.py:101 in one
+        launch - each frame resized, its contrast / brightness pair applied (alpha[b], beta[b]: datasets.py:10-16, see
+        datasets.draw_contrast_brightness; None, None: the identity, imgaug=False), transposed and divided by 255: the fp32
+        (B, 3, height, width) tensor train_forward takes.  Bit-identical to resize_frames(frames) followed by the per-byte table of
+        include/yfv2.h yfv2_train_batch_frames_u8 and permute(0, 3, 1, 2); no uint8 batch is written.  alpha / beta: B numbers each
+        (sequence, numpy array or CPU tensor), finite.  Grows max_batch like resize_frames.  Enqueue only."""
+        return self._train_batch_frames("train_batch_frames", self._frame_table, _lib.lib().yfv2_train_batch_frames_u8, frames, alpha, beta, out)
+
+    def train_batch_frames_yuv(self, frames, alpha=None, beta=None, out=None):
+        """`train_batch_frames` for a list of yuv.YuvFrame (what resize_frames_yuv takes): bit-identical to resize_frames_yuv(frames)
+        followed by the same table and permute."""
+        return self._train_batch_frames("train_batch_frames_yuv", self._yuv_table, _lib.lib().yfv2_train_batch_frames_yuv, frames, alpha, beta, out)
 
     def detect_frames(self, frames, conf_thres, iou_thres, out=None, check=True):
         """test.py:34-35,58-68 for a batch of frames of any sizes: resize each uint8 (h_i, w_i, 3) device frame to (height, width)
