@@ -144,6 +144,41 @@ def test_gradient_accumulation_over_subdivisions():
         assert torch.allclose(p.grad, 2 * g1[k], rtol=1e-5, atol=1e-7 * float(g1[k].abs().max() + 1e-12)), k
 
 
+def test_training_on_a_second_device_leaves_the_current_device_alone():
+    """Every entry point of the training path runs under the handle's device, not the thread's: with device 0 current, one iteration
+    on cuda:1 (forward, loss, backward, SGD.step) leaves device 0 current after each call, and its gradients are the ones the same
+    iteration computes on cuda:0 (to the accumulation tolerance of the float atomics, as below)."""
+    if torch.cuda.device_count() < 2:
+        pytest.skip("needs two visible devices")
+    import yolo_fastestv2_amd as yfv2
+    classes, B, T, seed, lr = make_golden.TRAIN_CASES[1]
+    w, x, t = make_golden.train_case_inputs(classes, B, T, seed)
+    anchors = [float(a) for a in np.load(os.path.join(GOLDEN, "cfg_coco.npz"))["anchors"]]
+    cfg = {"anchor_num": 3, "classes": classes, "width": 352, "height": 352, "anchors": anchors}
+    torch.cuda.set_device(0)
+    grads = {}
+    for d in (1, 0):
+        dev = torch.device("cuda:%d" % d)
+        model = yfv2.Detector(classes, 3, True).to(dev)
+        model.load_state_dict({k: v.clone() for k, v in w.items()})
+        model.train()
+        opt = yfv2.SGD(params=model.parameters(), lr=lr, momentum=0.949, weight_decay=0.0005)
+        xs, ts = torch.from_numpy(x).to(dev), torch.from_numpy(t).to(dev)
+        preds = model(xs)
+        assert torch.cuda.current_device() == 0
+        loss = yfv2.compute_loss(preds, ts, cfg, dev)[3]
+        assert torch.cuda.current_device() == 0
+        loss.backward()
+        assert torch.cuda.current_device() == 0
+        grads[d] = {k: p.grad.detach().cpu() for k, p in model.named_parameters()}
+        opt.step()
+        assert torch.cuda.current_device() == 0
+        torch.cuda.synchronize(dev)
+    for k, g0 in grads[0].items():
+        assert torch.isfinite(grads[1][k]).all(), k
+        assert torch.allclose(grads[1][k], g0, rtol=1e-4, atol=1e-4 * float(g0.abs().max())), k
+
+
 def test_eval_after_training_runs_the_current_weights_every_time():
     """yfv2.SGD and the train-mode forward write parameters / BatchNorm statistics through raw pointers; the
     packed inference copy of the weights must be refreshed after EVERY such write, not only at the first evaluation.  train ->

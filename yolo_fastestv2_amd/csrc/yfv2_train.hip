@@ -8,7 +8,9 @@
 // Behaviour only was read from the reference; autograd's derivatives are restated from the layer definitions.
 //
 // This is the correctness-first slice of the row: plain NCHW fp32 kernels, one thread per output element (reductions: one
-// block per channel / filter entry, float64 accumulators), a tape of closures instead of an autograd engine.  It is NOT the
+// block per channel / filter entry, float64 accumulators).  Instead of an autograd engine, the host half below the kernels walks
+// the topology once per batch size and binding (Train::record) into a list of Op records, which yfv2_train_forward runs in order
+// and yfv2_train_backward in reverse, and from which the arenas and both scratch blocks are sized.  It is NOT the
 // throughput path (BASELINE.json's metric is inference); it exists so that the reference's training loop runs end to end
 // on the MI355X through this library and matches tests/golden/golden_train.npz (the reference's own modules on CPU):
 // gradients to 1e-5 of each tensor's largest entry, updated weights to 1e-6.  Parameters, gradients and BatchNorm buffers are
@@ -18,14 +20,13 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
-#include <functional>
 #include <map>
 #include <string>
 #include <vector>
 
 #include "../../include/yfv2.h"
+#include "yfv2_ctx.h"    // DeviceGuard, DeviceBlock (and yfv2_pack.h: expected_numels)
 #include "yfv2_device.h"
-#include "yfv2_pack.h"   // expected_numels
 
 namespace {
 
@@ -621,152 +622,259 @@ __global__ __launch_bounds__(256) void sgd_multi_kernel(SgdChunk c, float lr, fl
 inline unsigned blocks_for(size_t n) { return (unsigned)((n + 255) / 256); }
 inline unsigned bn_blocks(size_t n) { return (unsigned)((n + BN_EPB - 1) / BN_EPB); }
 
-struct Tens { size_t off = 0; int C = 0, H = 0, W = 0; };   // offset (floats) into the activation arena; its gradient sits at the same offset of the gradient arena
+// A V with an offset (floats) in place of the pointer: a tensor of the arenas, or a channel window of one.  The activation sits at `off`
+// of the activation arena, its gradient at `off` of the gradient arena; at() makes the V over either, or over a caller's dense tensor
+struct Tens { size_t off = 0; int Ctot = 0, coff = 0, cstride = 1, C = 0, H = 0, W = 0; };
+inline Tens dense(int C, int H, int W) { Tens t; t.Ctot = t.C = C; t.H = H; t.W = W; return t; }
+inline Tens slice(Tens t, int coff, int cstride, int C) { t.coff = coff; t.cstride = cstride; t.C = C; return t; }   // of a whole tensor
+inline V at(const Tens& t, const float* base) { return V{const_cast<float*>(base) + t.off, t.Ctot, t.coff, t.cstride, t.C, t.H, t.W}; }
+
+// The kernels that serve a conv + BatchNorm op, decided when the op is recorded; kernel size, stride, padding and depthwise follow from it
+enum class Conv { Pointwise, Dw3s1, Dw3s2, Dw5s1, Stem };
+struct ConvGeom { int k, stride, pad, dw; };
+constexpr ConvGeom GEOM[] = {{1, 1, 0, 0}, {3, 1, 1, 1}, {3, 2, 1, 1}, {5, 1, 2, 1}, {3, 2, 1, 0}};
+
+// One step of the network, as data: Train::record writes the list, Train::run_forward / run_backward launch one step of it.  Offsets,
+// not pointers, into everything this unit allocates (the blocks are sized from the finished list); the caller's tensors are resolved
+enum class OpKind { ConvBn, MaxPool, Pass, UpCat, Head };
+struct Op {
+  OpKind kind = OpKind::ConvBn;
+  Conv conv = Conv::Pointwise;   // ConvBn: its kernels (a Head is pointwise)
+  Tens in, in2, out, y;          // Stem: `in` is the caller's image.  UpCat: out = cat(upsample2x(in), in2).  Head: `out` is the caller's logit tensor `slot`.  y: a conv's output before BatchNorm
+  bool relu = false;
+  int slot = 0;
+  size_t stat = 0, bn_scr = 0, wg_scr = 0;   // ConvBn: mean | invstd in the activation arena; the op's range (doubles) of the BatchNorm scratch, of the weight-gradient scratch
+  float *w = nullptr, *gw = nullptr, *bias = nullptr, *gbias = nullptr;            // conv weight, BatchNorm's (or the Head's) bias, and their gradients
+  float *gam = nullptr, *ggam = nullptr, *rm = nullptr, *rv = nullptr;             // BatchNorm weight, its gradient, running statistics
+  std::string name;              // the conv's state-dict name (yfv2_debug_train_relu_output)
+};
+struct Finish { size_t scr; float* dw; int n; };   // a weight gradient: its range of the scratch -> the bound tensor
 
 struct Train {
   yfv2_config cfg{};
-  int B = 0;
-  float* acts = nullptr; float* grads = nullptr; size_t arena_floats = 0, used = 0;
-  int* pool_arg = nullptr; size_t pool_arg_n = 0;
-  double* dscr = nullptr; size_t dscr_n = 0, dscr_used = 0;   // four doubles per BatchNorm channel: sum, sum of squares, the two backward sums (zeroed per forward)
-  std::map<std::string, float*> param, pgrad;
-  double* wscr = nullptr; size_t wscr_n = 0, wscr_used = 0;   // double partial sums of every layer's weight gradient (zeroed per backward)
-  std::vector<FinishItem> fin;                                // what wgrad_finish_multi_kernel adds where, collected while the tape runs
-  // a layer's range of the scratch; a tensor used twice in one backward (the output convs serve both scales) keeps ONE range
-  double* wgrad_scratch(float* dw, int n) {
-    for (const auto& f : fin) if (f.dw == dw) return const_cast<double*>(f.scr);
-    if (wscr_used + (size_t)n > wscr_n) { if (err.empty()) err = "yfv2_train: weight-gradient scratch exhausted"; return nullptr; }
-    double* p = wscr + wscr_used; wscr_used += ((size_t)n + 1) & ~(size_t)1;
-    fin.push_back(FinishItem{p, dw, n, 0});
-    return p;
-  }
-  std::vector<std::function<void(hipStream_t)>> tape;
-  std::map<std::string, V> relu_out;   // conv name -> the view its ReLU wrote (yfv2_debug_train_relu_output)
+  std::map<std::string, float*> param, pgrad;   // the binding
+  int B = 0; std::vector<Op> ops; size_t n_body = 0;   // the list recorded for batch B (empty after a new binding); ops[n_body ..] are the six output convs
+  std::vector<Finish> fin;                      // in the order the backward first meets them (wgrad_finish_multi_kernel's chunks)
+  size_t arena_floats = 0, pool_ints = 0, bn_doubles = 0, wg_doubles = 0;   // what the list uses of the blocks below
+  DeviceBlock acts, grads, pool_arg;            // the two arenas; the max-pool's winners
+  DeviceBlock dscr;                             // four doubles per BatchNorm channel: sum, sum of squares, the two backward sums (zeroed per forward)
+  DeviceBlock wscr;                             // double partial sums of every layer's weight gradient (zeroed per backward)
+  const float* x = nullptr;                     // the last forward's input (a raw caller pointer: the stem's weight gradient re-reads it)
+  bool forward_done = false;                    // a forward since the last backward
   std::string err;
-  bool sizing = false;
-  size_t per_image_floats = 0;
 
+  // ---- recording: ONE walk of the topology, which launches nothing
   Tens alloc(int C, int H, int W) {
-    Tens t; t.off = used; t.C = C; t.H = H; t.W = W;
-    used += (((size_t)B * C * H * W) + 63) & ~(size_t)63;
+    Tens t = dense(C, H, W); t.off = arena_floats;
+    arena_floats += (((size_t)B * C * H * W) + 63) & ~(size_t)63;
     return t;
-  }
-  V view(const Tens& t, bool grad, int coff = 0, int cstride = 1, int C = -1) const {
-    return V{(grad ? grads : acts) + t.off, t.C, coff, cstride, C < 0 ? t.C : C, t.H, t.W};
   }
   float* P(const std::string& n) { auto it = param.find(n); if (it == param.end() || !it->second) { if (err.empty()) err = "yfv2_train: tensor '" + n + "' is not bound"; return nullptr; } return it->second; }
   float* G(const std::string& n) { auto it = pgrad.find(n); if (it == pgrad.end() || !it->second) { if (err.empty()) err = "yfv2_train: gradient of '" + n + "' is not bound"; return nullptr; } return it->second; }
+  void plain(OpKind kind, const Tens& in, const Tens& in2, const Tens& out) { Op o; o.kind = kind; o.in = in; o.in2 = in2; o.out = out; ops.push_back(o); }
+  // conv (no bias) `prefix.i` + BatchNorm `prefix.(i + 1)` on batch statistics [+ ReLU]: `in` -> `out`, a channel window of a tensor
+  void conv_bn(Conv conv, const Tens& in, const Tens& out, const std::string& prefix, int i, bool relu) {
+    Op o; o.conv = conv; o.in = in; o.out = out; o.relu = relu; o.name = prefix + "." + std::to_string(i);
+    const std::string bn = prefix + "." + std::to_string(i + 1);
+    o.y = alloc(out.C, out.H, out.W);
+    o.stat = alloc(1, 1, 4 * out.C).off;   // mean | invstd | (2 per channel unused)
+    o.bn_scr = bn_doubles; bn_doubles += 4 * (size_t)out.C;
+    o.w = P(o.name + ".weight"); o.gam = P(bn + ".weight"); o.bias = P(bn + ".bias"); o.rm = P(bn + ".running_mean"); o.rv = P(bn + ".running_var");
+    o.gw = G(o.name + ".weight"); o.ggam = G(bn + ".weight"); o.gbias = G(bn + ".bias");
+    ops.push_back(o);
+  }
+  Tens conv_bn(Conv conv, const Tens& in, int Cout, const std::string& prefix, int i, bool relu) {   // ... -> a new tensor of Cout channels
+    const ConvGeom g = GEOM[(int)conv];
+    const Tens out = alloc(Cout, (in.H + 2 * g.pad - g.k) / g.stride + 1, (in.W + 2 * g.pad - g.k) / g.stride + 1);
+    conv_bn(conv, in, out, prefix, i, relu);
+    return out;
+  }
+  Tens tower(const std::string& p, const Tens& in) {   // fpn.py: two DWConvblocks
+    const Tens a = conv_bn(Conv::Dw5s1, in, 72, p, 0, true), b = conv_bn(Conv::Pointwise, a, 72, p, 3, false), c = conv_bn(Conv::Dw5s1, b, 72, p, 5, true);
+    return conv_bn(Conv::Pointwise, c, 72, p, 8, false);
+  }
+  // biased 1x1 output conv (detector.py:25-31): tower -> the caller's NCHW logit tensor `slot`; its gradient arrives from the caller
+  void head(const Tens& in, const std::string& name, int Cout, int slot) {
+    Op o; o.kind = OpKind::Head; o.in = in; o.out = dense(Cout, in.H, in.W); o.slot = slot; o.name = name;
+    o.w = P(name + ".weight"); o.bias = P(name + ".bias"); o.gw = G(name + ".weight"); o.gbias = G(name + ".bias");
+    ops.push_back(o);
+  }
+  // the order yfv2_train_backward launches in: the six output convs as recorded, then everything before them in reverse
+  template <class F> void for_each_backward(F f) {
+    for (size_t i = n_body; i < ops.size(); ++i) f(ops[i]);
+    for (size_t i = n_body; i-- > 0;) f(ops[i]);
+  }
+  // shufflenetv2.py:19-63,102-109, fpn.py, detector.py:21-47 for `batch` images: the list, every arena offset, both scratch ranges.
+  // A tensor missing from the binding: `err`, and the list is not to be run
+  void record(int batch) {
+    B = batch; ops.clear(); fin.clear(); err.clear();
+    arena_floats = bn_doubles = wg_doubles = 0;
+    const int H = cfg.height, W = cfg.width, A = cfg.anchor_num;
+    // the input is NOT copied: the stem reads the caller's tensor (it needs no gradient)
+    const Tens stem = conv_bn(Conv::Stem, dense(3, H, W), 24, "backbone.first_conv", 0, true);
+    Tens cur = alloc(24, H / 4, W / 4), c2;
+    plain(OpKind::MaxPool, stem, {}, cur);
+    pool_ints = (size_t)B * 24 * cur.H * cur.W;
+    const int repeats[3] = {4, 8, 4}, chans[4] = {24, 48, 96, 192};
+    for (int si = 0; si < 3; ++si) {
+      const int cin = chans[si], cout = chans[si + 1], mid = cout / 2;
+      for (int i = 0; i < repeats[si]; ++i) {
+        const std::string p = "backbone.stage" + std::to_string(si + 2) + "." + std::to_string(i);
+        const Tens out = alloc(cout, i ? cur.H : cur.H / 2, i ? cur.W : cur.W / 2);
+        if (i == 0) {   // stride 2: out = cat(proj(x), main(x))
+          const Tens pd = conv_bn(Conv::Dw3s2, cur, cin, p + ".branch_proj", 0, false);
+          conv_bn(Conv::Pointwise, pd, slice(out, 0, 1, cin), p + ".branch_proj", 2, true);
+          const Tens m1 = conv_bn(Conv::Pointwise, cur, mid, p + ".branch_main", 0, true), m2 = conv_bn(Conv::Dw3s2, m1, mid, p + ".branch_main", 3, false);
+          conv_bn(Conv::Pointwise, m2, slice(out, cin, 1, cout - cin), p + ".branch_main", 5, true);
+        } else {        // stride 1: even channels pass, odd channels -> main; out = cat(pass, main)
+          plain(OpKind::Pass, slice(cur, 0, 2, mid), {}, slice(out, 0, 1, mid));
+          const Tens m1 = conv_bn(Conv::Pointwise, slice(cur, 1, 2, mid), mid, p + ".branch_main", 0, true), m2 = conv_bn(Conv::Dw3s1, m1, mid, p + ".branch_main", 3, false);
+          conv_bn(Conv::Pointwise, m2, slice(out, mid, 1, mid), p + ".branch_main", 5, true);
+        }
+        cur = out;
+      }
+      if (si == 1) c2 = cur;
+    }
+    const Tens c3 = cur, s3 = conv_bn(Conv::Pointwise, c3, 72, "fpn.conv1x1_3", 0, true);
+    const Tens cls3 = tower("fpn.cls_head_3.block", s3), reg3 = tower("fpn.reg_head_3.block", s3);
+    const Tens p2 = alloc(c3.C + c2.C, c2.H, c2.W);
+    plain(OpKind::UpCat, c3, c2, p2);
+    const Tens s2 = conv_bn(Conv::Pointwise, p2, 72, "fpn.conv1x1_2", 0, true);
+    const Tens cls2 = tower("fpn.cls_head_2.block", s2), reg2 = tower("fpn.reg_head_2.block", s2);
+    n_body = ops.size();
+    head(reg2, "output_reg_layers", 4 * A, 0);
+    head(cls2, "output_obj_layers", A, 1);
+    head(cls2, "output_cls_layers", cfg.classes, 2);
+    head(reg3, "output_reg_layers", 4 * A, 3);
+    head(cls3, "output_obj_layers", A, 4);
+    head(cls3, "output_cls_layers", cfg.classes, 5);
+    // weight-gradient scratch, in the backward's order.  An output conv serves both scales with ONE tensor and keeps ONE range, where its
+    // gradients accumulate (the output convs come first: `fin` holds at most three entries when it is searched)
+    for_each_backward([&](Op& o) {
+      if (o.kind != OpKind::ConvBn && o.kind != OpKind::Head) return;
+      if (o.kind == OpKind::Head) for (const Finish& f : fin) if (f.dw == o.gw) { o.wg_scr = f.scr; return; }
+      const ConvGeom g = GEOM[(int)o.conv];
+      const int n = (g.dw ? o.out.C : o.out.C * o.in.C) * g.k * g.k;
+      o.wg_scr = wg_doubles; wg_doubles += ((size_t)n + 1) & ~(size_t)1;
+      fin.push_back(Finish{o.wg_scr, o.gw, n});
+    });
+  }
 
+  // ---- running the list
+  V act(const Tens& t) const { return at(t, acts.as<float>()); }
+  V grad(const Tens& t) const { return at(t, grads.as<float>()); }
+  V src(const Op& o) const { return o.conv == Conv::Stem ? at(o.in, x) : act(o.in); }   // what a conv reads: the stem, the caller's image
   // pointwise conv launchers (round 4): forward / data gradient as one GEMM, weight gradient = GEMM into the double scratch + finish
   void pw_forward(const V& in, const V& out, const float* w, const float* bias, hipStream_t s) const {
     const int HW = out.H * out.W;
     if (out.C <= 32) hipLaunchKernelGGL((pw_gemm_kernel<false, false, 2>), dim3((HW + 255) / 256, B, 1), dim3(256), 0, s, in, out, w, bias, in.C, B);   // (stage 2's 24 channels: two row tiles)
     else hipLaunchKernelGGL((pw_gemm_kernel<false, false, 4>), dim3((HW + 255) / 256, B, (out.C + 63) / 64), dim3(256), 0, s, in, out, w, bias, in.C, B);
   }
-  void pw_data_grad(const V& din, const V& dout, const float* w, int Bc, hipStream_t s) const {   // din += w^T dout
+  void pw_data_grad(const V& din, const V& dout, const float* w, hipStream_t s) const {   // din += w^T dout
     const int HW = din.H * din.W;
-    if (din.C <= 32) hipLaunchKernelGGL((pw_gemm_kernel<true, true, 2>), dim3((HW + 255) / 256, Bc, 1), dim3(256), 0, s, dout, din, w, (const float*)nullptr, din.C, Bc);
-    else hipLaunchKernelGGL((pw_gemm_kernel<true, true, 4>), dim3((HW + 255) / 256, Bc, (din.C + 63) / 64), dim3(256), 0, s, dout, din, w, (const float*)nullptr, din.C, Bc);
+    if (din.C <= 32) hipLaunchKernelGGL((pw_gemm_kernel<true, true, 2>), dim3((HW + 255) / 256, B, 1), dim3(256), 0, s, dout, din, w, (const float*)nullptr, din.C, B);
+    else hipLaunchKernelGGL((pw_gemm_kernel<true, true, 4>), dim3((HW + 255) / 256, B, (din.C + 63) / 64), dim3(256), 0, s, dout, din, w, (const float*)nullptr, din.C, B);
   }
-  void pw_weight_grad(const V& x, const V& dout, float* dw, int Bc, hipStream_t s) {
+  void pw_weight_grad(const V& x, const V& dout, double* scr, hipStream_t s) const {
     const int HW = x.H * x.W, cob = (dout.C + 47) / 48, cib = (x.C + 47) / 48;
     int seg = 256;                                     // pixels per wave: enough waves for the machine, fp32 partial sums over few terms
-    while (seg > 64 && (long long)((HW + seg - 1) / seg) * Bc * cob * cib < 2048) seg >>= 1;
-    double* scr = wgrad_scratch(dw, dout.C * x.C);
-    const int nseg = (HW + seg - 1) / seg, units = nseg * Bc;
+    while (seg > 64 && (long long)((HW + seg - 1) / seg) * B * cob * cib < 2048) seg >>= 1;
+    const int nseg = (HW + seg - 1) / seg, units = nseg * B;
     int upw = (int)(((long long)units * cob * cib) / 512);     // about 512 waves per layer (a launch below ~256 waves leaves CUs idle)
     if (upw < 1) upw = 1;
     if (upw > 16) upw = 16;
-    if (scr) hipLaunchKernelGGL(pw_wgrad_kernel, dim3((units + upw - 1) / upw, 1, cob * cib), dim3(64), 0, s, x, dout, scr, seg, cib, nseg, units, upw);
+    hipLaunchKernelGGL(pw_wgrad_kernel, dim3((units + upw - 1) / upw, 1, cob * cib), dim3(64), 0, s, x, dout, scr, seg, cib, nseg, units, upw);
   }
 
-  // conv (no bias) + BatchNorm (batch statistics) [+ ReLU]: in view -> zout view (a channel slice of some tensor)
-  void conv_bn(const Tens& tin, int in_coff, int in_cstride, int Cin, const Tens& tout, int out_coff, int Cout, const std::string& conv, const std::string& bn,
-               int k, int stride, int pad, bool dw, bool relu, bool need_din, hipStream_t s) {
-    const int OH = (tin.H + 2 * pad - k) / stride + 1, OW = (tin.W + 2 * pad - k) / stride + 1;
-    Tens y = alloc(Cout, OH, OW);
-    Tens st = alloc(1, 1, 4 * Cout);   // mean | invstd | the two backward sums (2 per channel)
-    if (sizing) return;
-    float* w = P(conv + ".weight"); float* gam = P(bn + ".weight"); float* bet = P(bn + ".bias"); float* rm = P(bn + ".running_mean"); float* rv = P(bn + ".running_var");
-    float* gw = G(conv + ".weight"); float* gg = G(bn + ".weight"); float* gb = G(bn + ".bias");
-    if (!w || !gam || !bet || !rm || !rv || !gw || !gg || !gb) return;
-    float* mean = acts + st.off; float* invstd = mean + Cout; float* sums = invstd + Cout;
-    ConvP c{view(tin, false, in_coff, in_cstride, Cin), view(y, false), w, nullptr, k, stride, pad, dw ? 1 : 0, B};
-    const bool pw = k == 1 && stride == 1 && pad == 0 && !dw;
-    if (pw) pw_forward(c.in, c.out, w, nullptr, s);
-    else if (dw && pad == k / 2 && (k == 3 || k == 5) && (stride == 1 || stride == 2)) {
-      const dim3 grid((OH * OW + 255) / 256, B * Cout);
-      if (k == 3 && stride == 1) hipLaunchKernelGGL((dw_fwd_kernel<3, 1>), grid, dim3(256), 0, s, c);
-      else if (k == 3) hipLaunchKernelGGL((dw_fwd_kernel<3, 2>), grid, dim3(256), 0, s, c);
-      else if (stride == 1) hipLaunchKernelGGL((dw_fwd_kernel<5, 1>), grid, dim3(256), 0, s, c);
-      else { if (err.empty()) err = "yfv2_train: no kernel for a 5x5 stride-2 depthwise conv (" + conv + ")"; return; }
-    } else { if (err.empty()) err = "yfv2_train: no kernel for conv " + conv + " (pointwise, depthwise 3x3 / 5x5 and the stem only)"; return; }   // (round 3's
-    // one-thread-per-output conv_fwd / conv_bwd_data / conv_bwd_weight kernels served every layer; nothing of this network reaches them since round 4)
-    double* ds = dscr + dscr_used; dscr_used += 4 * (size_t)Cout;
-    if (dscr_used > dscr_n) { if (err.empty()) err = "yfv2_train: BatchNorm scratch exhausted"; return; }
-    const unsigned nseg = reduce_segments((size_t)B * OH * OW, Cout);
-    hipLaunchKernelGGL(bn_stats_part_kernel, dim3(Cout, nseg), dim3(256), 0, s, acts + y.off, B, Cout, OH * OW, ds);
-    const V z = view(tout, false, out_coff, 1, Cout), dz = view(tout, true, out_coff, 1, Cout);
-    hipLaunchKernelGGL(bn_apply_kernel, dim3(bn_blocks((size_t)B * Cout * OH * OW)), dim3(256), 0, s, acts + y.off, z, B, ds, mean, invstd, rm, rv, gam, bet, relu ? 1 : 0);
-    if (relu) relu_out[conv] = z;
-    const int Bc = B;
-    tape.push_back([=, this](hipStream_t st2) {
-      float* yv = acts + y.off; float* dy = grads + y.off;
-      hipLaunchKernelGGL(bn_bwd_part_kernel, dim3(Cout, nseg), dim3(256), 0, st2, yv, z, dz, Bc, mean, invstd, relu ? 1 : 0, ds);
-      hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(bn_blocks((size_t)Bc * Cout * OH * OW)), dim3(256), 0, st2, yv, z, dz, dy, Bc, mean, invstd, gam, relu ? 1 : 0, ds, gg, gb);
-      ConvP cw{view(tin, false, in_coff, in_cstride, Cin), view(y, true), nullptr, nullptr, k, stride, pad, dw ? 1 : 0, Bc};
-      if (pw) pw_weight_grad(cw.in, cw.out, gw, Bc, st2);
-      else if (dw && (k == 3 || k == 5)) {
-        const dim3 grid((unsigned)(((size_t)Bc * OH * OW + 4095) / 4096), Cout);
-        double* scr = wgrad_scratch(gw, Cout * k * k);
-        if (scr && k == 3) hipLaunchKernelGGL((dw_wgrad_kernel<3>), grid, dim3(256), 0, st2, cw, scr);
-        else if (scr) hipLaunchKernelGGL((dw_wgrad_kernel<5>), grid, dim3(256), 0, st2, cw, scr);
-      }
-      if (need_din) {
-        ConvP cd{view(tin, true, in_coff, in_cstride, Cin), view(y, true), w, nullptr, k, stride, pad, dw ? 1 : 0, Bc};
-        if (pw) pw_data_grad(cd.in, cd.out, w, Bc, st2);
-        else if (dw && pad == k / 2 && (k == 3 || k == 5) && (stride == 1 || stride == 2)) {
-          const dim3 grid((tin.H * tin.W + 255) / 256, Bc * Cin);
-          if (k == 3 && stride == 1) hipLaunchKernelGGL((dw_bwd_data_kernel<3, 1>), grid, dim3(256), 0, st2, cd);
-          else if (k == 3) hipLaunchKernelGGL((dw_bwd_data_kernel<3, 2>), grid, dim3(256), 0, st2, cd);
-          else hipLaunchKernelGGL((dw_bwd_data_kernel<5, 1>), grid, dim3(256), 0, st2, cd);
-        }
-      }
-    });
+  void conv_bn_forward(const Op& o, hipStream_t s) const {
+    const ConvGeom g = GEOM[(int)o.conv];
+    const int C = o.y.C, HW = o.y.H * o.y.W;
+    const ConvP c{src(o), act(o.y), o.w, nullptr, g.k, g.stride, g.pad, g.dw, B};
+    const dim3 planes((HW + 255) / 256, B * C);
+    switch (o.conv) {
+      case Conv::Pointwise: pw_forward(c.in, c.out, o.w, nullptr, s); break;
+      case Conv::Dw3s1: hipLaunchKernelGGL((dw_fwd_kernel<3, 1>), planes, dim3(256), 0, s, c); break;
+      case Conv::Dw3s2: hipLaunchKernelGGL((dw_fwd_kernel<3, 2>), planes, dim3(256), 0, s, c); break;
+      case Conv::Dw5s1: hipLaunchKernelGGL((dw_fwd_kernel<5, 1>), planes, dim3(256), 0, s, c); break;
+      case Conv::Stem: hipLaunchKernelGGL(stem_fwd_kernel, dim3(blocks_for((size_t)B * HW)), dim3(256), 0, s, c); break;
+    }
+    float* mean = acts.as<float>() + o.stat;
+    double* ds = dscr.as<double>() + o.bn_scr;
+    hipLaunchKernelGGL(bn_stats_part_kernel, dim3(C, reduce_segments((size_t)B * HW, C)), dim3(256), 0, s, c.out.p, B, C, HW, ds);
+    hipLaunchKernelGGL(bn_apply_kernel, dim3(bn_blocks((size_t)B * C * HW)), dim3(256), 0, s, c.out.p, act(o.out), B, ds, mean, mean + C, o.rm, o.rv, o.gam, o.bias, o.relu ? 1 : 0);
+  }
+  void conv_bn_backward(const Op& o, hipStream_t s) const {
+    const ConvGeom g = GEOM[(int)o.conv];
+    const int C = o.y.C, HW = o.y.H * o.y.W, relu = o.relu ? 1 : 0;
+    const V y = act(o.y), dy = grad(o.y), z = act(o.out), dz = grad(o.out);
+    float* mean = acts.as<float>() + o.stat;
+    double* ds = dscr.as<double>() + o.bn_scr; double* scr = wscr.as<double>() + o.wg_scr;
+    hipLaunchKernelGGL(bn_bwd_part_kernel, dim3(C, reduce_segments((size_t)B * HW, C)), dim3(256), 0, s, y.p, z, dz, B, mean, mean + C, relu, ds);
+    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(bn_blocks((size_t)B * C * HW)), dim3(256), 0, s, y.p, z, dz, dy.p, B, mean, mean + C, o.gam, relu, ds, o.ggam, o.gbias);
+    const ConvP cw{src(o), dy, nullptr, nullptr, g.k, g.stride, g.pad, g.dw, B};
+    const unsigned chunks = (unsigned)(((size_t)B * HW + 4095) / 4096);   // of 4096 output pixels
+    switch (o.conv) {
+      case Conv::Pointwise: pw_weight_grad(cw.in, dy, scr, s); break;
+      case Conv::Dw3s1:
+      case Conv::Dw3s2: hipLaunchKernelGGL((dw_wgrad_kernel<3>), dim3(chunks, C), dim3(256), 0, s, cw, scr); break;
+      case Conv::Dw5s1: hipLaunchKernelGGL((dw_wgrad_kernel<5>), dim3(chunks, C), dim3(256), 0, s, cw, scr); break;
+      case Conv::Stem: hipLaunchKernelGGL(stem_wgrad_kernel, dim3(chunks, 3, 3), dim3(256), 0, s, cw, scr); break;
+    }
+    const ConvP cd{grad(o.in), dy, o.w, nullptr, g.k, g.stride, g.pad, g.dw, B};
+    const dim3 planes((o.in.H * o.in.W + 255) / 256, B * o.in.C);
+    switch (o.conv) {
+      case Conv::Pointwise: pw_data_grad(cd.in, dy, o.w, s); break;
+      case Conv::Dw3s1: hipLaunchKernelGGL((dw_bwd_data_kernel<3, 1>), planes, dim3(256), 0, s, cd); break;
+      case Conv::Dw3s2: hipLaunchKernelGGL((dw_bwd_data_kernel<3, 2>), planes, dim3(256), 0, s, cd); break;
+      case Conv::Dw5s1: hipLaunchKernelGGL((dw_bwd_data_kernel<5, 1>), planes, dim3(256), 0, s, cd); break;
+      case Conv::Stem: break;   // the image needs no gradient
+    }
   }
 
-  // biased 1x1 output conv (detector.py:25-31): tower -> caller's NCHW logit tensor; its gradient arrives from the caller
-  struct HeadUse { Tens tin; std::string name; int Cout; float* out; const float* dout; };
-  std::vector<HeadUse> heads;
-  void head(const Tens& tin, const std::string& name, int Cout, float* out, hipStream_t s) {
-    if (sizing) return;
-    float* w = P(name + ".weight"); float* bi = P(name + ".bias");
-    if (!w || !bi) return;
-    V o{out, Cout, 0, 1, Cout, tin.H, tin.W};
-    pw_forward(view(tin, false), o, w, bi, s);
-    heads.push_back(HeadUse{tin, name, Cout, out, nullptr});
+  void run_forward(const Op& o, float* const out6[6], hipStream_t s) const {
+    const size_t n_out = (size_t)B * o.out.C * o.out.H * o.out.W;
+    switch (o.kind) {
+      case OpKind::ConvBn: conv_bn_forward(o, s); break;
+      case OpKind::MaxPool: hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(blocks_for(n_out)), dim3(256), 0, s, act(o.in).p, act(o.out).p, pool_arg.as<int>(), B, o.in.C, o.in.H, o.in.W); break;
+      case OpKind::Pass: hipLaunchKernelGGL(view_copy_kernel, dim3(blocks_for(n_out)), dim3(256), 0, s, act(o.out), act(o.in), B, 0); break;
+      case OpKind::UpCat:
+        hipLaunchKernelGGL(upsample2_kernel, dim3(blocks_for((size_t)B * o.in.C * o.out.H * o.out.W)), dim3(256), 0, s, act(slice(o.out, 0, 1, o.in.C)), act(o.in), B);
+        hipLaunchKernelGGL(view_copy_kernel, dim3(blocks_for((size_t)B * o.in2.C * o.out.H * o.out.W)), dim3(256), 0, s, act(slice(o.out, o.in.C, 1, o.in2.C)), act(o.in2), B, 0);
+        break;
+      case OpKind::Head: pw_forward(act(o.in), at(o.out, out6[o.slot]), o.w, o.bias, s); break;
+    }
+  }
+  void run_backward(const Op& o, const float* const grad6[6], hipStream_t s) const {
+    const size_t n_in = (size_t)B * o.in.C * o.in.H * o.in.W;
+    switch (o.kind) {
+      case OpKind::ConvBn: conv_bn_backward(o, s); break;
+      case OpKind::MaxPool: hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(blocks_for(n_in)), dim3(256), 0, s, grad(o.out).p, pool_arg.as<int>(), grad(o.in).p, B, o.in.C, o.in.H, o.in.W); break;
+      case OpKind::Pass: hipLaunchKernelGGL(view_copy_kernel, dim3(blocks_for(n_in)), dim3(256), 0, s, grad(o.in), grad(o.out), B, 1); break;
+      case OpKind::UpCat:
+        hipLaunchKernelGGL(upsample2_bwd_kernel, dim3(blocks_for(n_in)), dim3(256), 0, s, grad(o.in), grad(slice(o.out, 0, 1, o.in.C)), B);
+        hipLaunchKernelGGL(view_copy_kernel, dim3(blocks_for((size_t)B * o.in2.C * o.in2.H * o.in2.W)), dim3(256), 0, s, grad(o.in2), grad(slice(o.out, o.in.C, 1, o.in2.C)), B, 1);
+        break;
+      case OpKind::Head: {   // weights shared by the two scales -> their gradients accumulate (the caller zeroed the parameter gradients)
+        const V go = at(o.out, grad6[o.slot]);
+        hipLaunchKernelGGL(bias_bwd_kernel, dim3(go.C), dim3(256), 0, s, go, B, o.gbias);
+        pw_weight_grad(act(o.in), go, wscr.as<double>() + o.wg_scr, s);
+        pw_data_grad(grad(o.in), go, o.w, s);
+        break;
+      }
+    }
   }
 };
 
 }  // namespace
 
-// the training state hangs off the handle through an opaque slot (the handle is yfv2_ctx.h's; this unit sees it through three accessors)
+// the training state hangs off the handle through an opaque slot (the handle is yfv2_ctx.h's; this unit reaches it through three accessors)
 static Train* train_of(yfv2_handle h, bool create) {
   void** slot = yfv2_ctx_train_slot(h);
   if (!slot) return nullptr;
   if (!*slot && create) { Train* t = new Train(); t->cfg = *yfv2_ctx_config(h); *slot = t; }
   return static_cast<Train*>(*slot);
 }
-void yfv2_train_release(void* p) {
-  Train* t = static_cast<Train*>(p);
-  if (!t) return;
-  if (t->acts) (void)hipFree(t->acts);
-  if (t->grads) (void)hipFree(t->grads);
-  if (t->pool_arg) (void)hipFree(t->pool_arg);
-  if (t->dscr) (void)hipFree(t->dscr);
-  if (t->wscr) (void)hipFree(t->wscr);
-  delete t;
-}
+void yfv2_train_release(void* p) { delete static_cast<Train*>(p); }
 
 extern "C" {
 
@@ -789,6 +897,7 @@ int yfv2_train_bind(yfv2_handle h, const yfv2_tensor_desc* tensors, int32_t n, c
   t->param.clear(); t->pgrad.clear();
   for (int i = 0; i < n; ++i) if (tensors[i].name) t->param[tensors[i].name] = const_cast<float*>(tensors[i].data);
   for (int i = 0; i < ng; ++i) if (grads[i].name) t->pgrad[grads[i].name] = const_cast<float*>(grads[i].data);
+  t->ops.clear(); t->forward_done = false;   // the list holds the OLD binding's pointers: the next forward records it again
   return YFV2_OK;
 }
 
@@ -797,194 +906,48 @@ int yfv2_train_forward(yfv2_handle h, const float* x, int32_t B, float* const ou
   Train* t = train_of(h, false);
   if (!t || t->param.empty()) return yfv2_ctx_fail(h, YFV2_ERR_STATE, "yfv2_train_forward: yfv2_train_bind has not been called");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  (void)hipSetDevice(t->cfg.device);
-  const int H = t->cfg.height, W = t->cfg.width, A = t->cfg.anchor_num, nc = t->cfg.classes;
-  t->B = B; t->err.clear(); t->tape.clear(); t->heads.clear(); t->relu_out.clear();
-
-  auto build = [&](bool sizing) {
-    t->sizing = sizing; t->used = 0;
-    // the input is NOT copied: a view over the caller's tensor (it needs no gradient)
-    Tens stem = t->alloc(24, H / 2, W / 2), pooled = t->alloc(24, H / 4, W / 4);
-    {
-      // stem conv reads the caller's x directly
-      if (!sizing) {
-        Tens y = t->alloc(24, H / 2, W / 2); Tens st = t->alloc(1, 1, 4 * 24);
-        float* w = t->P("backbone.first_conv.0.weight"); float* gam = t->P("backbone.first_conv.1.weight"); float* bet = t->P("backbone.first_conv.1.bias");
-        float* rm = t->P("backbone.first_conv.1.running_mean"); float* rv = t->P("backbone.first_conv.1.running_var");
-        float* gw = t->G("backbone.first_conv.0.weight"); float* gg = t->G("backbone.first_conv.1.weight"); float* gb = t->G("backbone.first_conv.1.bias");
-        if (w && gam && bet && rm && rv && gw && gg && gb) {
-          const int OH = H / 2, OW = W / 2;
-          float* mean = t->acts + st.off; float* invstd = mean + 24; float* sums = invstd + 24;
-          V xin{const_cast<float*>(x), 3, 0, 1, 3, H, W};
-          ConvP c{xin, t->view(y, false), w, nullptr, 3, 2, 1, 0, B};
-          hipLaunchKernelGGL(stem_fwd_kernel, dim3(blocks_for((size_t)B * OH * OW)), dim3(256), 0, s, c);
-          double* ds = t->dscr + t->dscr_used; t->dscr_used += 4 * 24;
-          const unsigned nseg = reduce_segments((size_t)B * OH * OW, 24);
-          hipLaunchKernelGGL(bn_stats_part_kernel, dim3(24, nseg), dim3(256), 0, s, t->acts + y.off, B, 24, OH * OW, ds);
-          const V z = t->view(stem, false), dz = t->view(stem, true);
-          hipLaunchKernelGGL(bn_apply_kernel, dim3(bn_blocks((size_t)B * 24 * OH * OW)), dim3(256), 0, s, t->acts + y.off, z, B, ds, mean, invstd, rm, rv, gam, bet, 1);
-          t->relu_out["backbone.first_conv.0"] = z;
-          Train* tt = t;
-          t->tape.push_back([=](hipStream_t st2) {
-            float* yv = tt->acts + y.off; float* dy = tt->grads + y.off;
-            hipLaunchKernelGGL(bn_bwd_part_kernel, dim3(24, nseg), dim3(256), 0, st2, yv, z, dz, B, mean, invstd, 1, ds);
-            hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(bn_blocks((size_t)B * 24 * OH * OW)), dim3(256), 0, st2, yv, z, dz, dy, B, mean, invstd, gam, 1, ds, gg, gb);
-            ConvP cw{xin, tt->view(y, true), nullptr, nullptr, 3, 2, 1, 0, B};
-            double* scr = tt->wgrad_scratch(gw, 24 * 3 * 9);
-            if (scr) hipLaunchKernelGGL(stem_wgrad_kernel, dim3((unsigned)(((size_t)B * OH * OW + 4095) / 4096), 3, 3), dim3(256), 0, st2, cw, scr);
-          });
-          // maxpool
-          const size_t np = (size_t)B * 24 * (H / 4) * (W / 4);
-          int* arg = t->pool_arg;
-          hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(blocks_for(np)), dim3(256), 0, s, t->acts + stem.off, t->acts + pooled.off, arg, B, 24, H / 2, W / 2);
-          t->tape.push_back([=](hipStream_t st2) {
-            hipLaunchKernelGGL(maxpool_bwd_kernel, dim3(blocks_for((size_t)B * 24 * (H / 2) * (W / 2))), dim3(256), 0, st2, tt->grads + pooled.off, arg, tt->grads + stem.off, B, 24,
-                               H / 2, W / 2);
-          });
-        }
-      } else {
-        t->alloc(24, H / 2, W / 2); t->alloc(1, 1, 4 * 24);
-      }
-    }
-    Tens cur = pooled;
-    Tens feats[3];
-    const int repeats[3] = {4, 8, 4}, chans[4] = {24, 48, 96, 192};
-    int cin = 24;
-    for (int si = 0; si < 3; ++si) {
-      const int cout = chans[si + 1], mid = cout / 2;
-      for (int i = 0; i < repeats[si]; ++i) {
-        const std::string p = "backbone.stage" + std::to_string(si + 2) + "." + std::to_string(i);
-        if (i == 0) {   // stride 2: out = cat(proj(x), main(x))
-          const int inp = cin, oh = cur.H / 2, ow = cur.W / 2;
-          Tens out = t->alloc(cout, oh, ow);
-          Tens pd = t->alloc(inp, oh, ow);
-          t->conv_bn(cur, 0, 1, inp, pd, 0, inp, p + ".branch_proj.0", p + ".branch_proj.1", 3, 2, 1, true, false, true, s);
-          t->conv_bn(pd, 0, 1, inp, out, 0, inp, p + ".branch_proj.2", p + ".branch_proj.3", 1, 1, 0, false, true, true, s);
-          Tens m1 = t->alloc(mid, cur.H, cur.W), m2 = t->alloc(mid, oh, ow);
-          t->conv_bn(cur, 0, 1, inp, m1, 0, mid, p + ".branch_main.0", p + ".branch_main.1", 1, 1, 0, false, true, true, s);
-          t->conv_bn(m1, 0, 1, mid, m2, 0, mid, p + ".branch_main.3", p + ".branch_main.4", 3, 2, 1, true, false, true, s);
-          t->conv_bn(m2, 0, 1, mid, out, inp, cout - inp, p + ".branch_main.5", p + ".branch_main.6", 1, 1, 0, false, true, true, s);
-          cur = out;
-        } else {        // stride 1: even channels pass, odd channels -> main; out = cat(pass, main)
-          const int c = cout, c2 = c / 2;
-          Tens out = t->alloc(c, cur.H, cur.W);
-          if (!sizing) {
-            const V dst = t->view(out, false, 0, 1, c2), src = t->view(cur, false, 0, 2, c2);
-            hipLaunchKernelGGL(view_copy_kernel, dim3(blocks_for((size_t)B * c2 * cur.H * cur.W)), dim3(256), 0, s, dst, src, B, 0);
-            const V gdst = t->view(cur, true, 0, 2, c2), gsrc = t->view(out, true, 0, 1, c2);
-            const int hh = cur.H, ww = cur.W;
-            t->tape.push_back([=](hipStream_t st2) { hipLaunchKernelGGL(view_copy_kernel, dim3(blocks_for((size_t)B * c2 * hh * ww)), dim3(256), 0, st2, gdst, gsrc, B, 1); });
-          }
-          Tens m1 = t->alloc(c2, cur.H, cur.W), m2 = t->alloc(c2, cur.H, cur.W);
-          t->conv_bn(cur, 1, 2, c2, m1, 0, c2, p + ".branch_main.0", p + ".branch_main.1", 1, 1, 0, false, true, true, s);
-          t->conv_bn(m1, 0, 1, c2, m2, 0, c2, p + ".branch_main.3", p + ".branch_main.4", 3, 1, 1, true, false, true, s);
-          t->conv_bn(m2, 0, 1, c2, out, c2, c2, p + ".branch_main.5", p + ".branch_main.6", 1, 1, 0, false, true, true, s);
-          cur = out;
-        }
-      }
-      feats[si] = cur;
-      cin = cout;
-    }
-    const Tens c2 = feats[1], c3 = feats[2];
-    Tens s3 = t->alloc(72, c3.H, c3.W);
-    t->conv_bn(c3, 0, 1, 192, s3, 0, 72, "fpn.conv1x1_3.0", "fpn.conv1x1_3.1", 1, 1, 0, false, true, true, s);
-    auto tower = [&](const std::string& p, const Tens& in) {
-      Tens a1 = t->alloc(72, in.H, in.W), a2 = t->alloc(72, in.H, in.W), a3 = t->alloc(72, in.H, in.W), a4 = t->alloc(72, in.H, in.W);
-      t->conv_bn(in, 0, 1, 72, a1, 0, 72, p + ".0", p + ".1", 5, 1, 2, true, true, true, s);
-      t->conv_bn(a1, 0, 1, 72, a2, 0, 72, p + ".3", p + ".4", 1, 1, 0, false, false, true, s);
-      t->conv_bn(a2, 0, 1, 72, a3, 0, 72, p + ".5", p + ".6", 5, 1, 2, true, true, true, s);
-      t->conv_bn(a3, 0, 1, 72, a4, 0, 72, p + ".8", p + ".9", 1, 1, 0, false, false, true, s);
-      return a4;
-    };
-    const Tens cls3 = tower("fpn.cls_head_3.block", s3), reg3 = tower("fpn.reg_head_3.block", s3);
-    Tens p2 = t->alloc(288, c2.H, c2.W);
-    if (!sizing) {
-      const V up = t->view(p2, false, 0, 1, 192), src3 = t->view(c3, false);
-      hipLaunchKernelGGL(upsample2_kernel, dim3(blocks_for((size_t)B * 192 * c2.H * c2.W)), dim3(256), 0, s, up, src3, B);
-      const V dst2 = t->view(p2, false, 192, 1, 96), src2 = t->view(c2, false);
-      hipLaunchKernelGGL(view_copy_kernel, dim3(blocks_for((size_t)B * 96 * c2.H * c2.W)), dim3(256), 0, s, dst2, src2, B, 0);
-      const V gup = t->view(p2, true, 0, 1, 192), g3 = t->view(c3, true), g2 = t->view(c2, true), gp2 = t->view(p2, true, 192, 1, 96);
-      const int h3 = c3.H, w3 = c3.W, h2 = c2.H, w2 = c2.W;
-      t->tape.push_back([=](hipStream_t st2) {
-        hipLaunchKernelGGL(upsample2_bwd_kernel, dim3(blocks_for((size_t)B * 192 * h3 * w3)), dim3(256), 0, st2, g3, gup, B);
-        hipLaunchKernelGGL(view_copy_kernel, dim3(blocks_for((size_t)B * 96 * h2 * w2)), dim3(256), 0, st2, g2, gp2, B, 1);
-      });
-    }
-    Tens s2 = t->alloc(72, c2.H, c2.W);
-    t->conv_bn(p2, 0, 1, 288, s2, 0, 72, "fpn.conv1x1_2.0", "fpn.conv1x1_2.1", 1, 1, 0, false, true, true, s);
-    const Tens cls2 = tower("fpn.cls_head_2.block", s2), reg2 = tower("fpn.reg_head_2.block", s2);
-    t->head(reg2, "output_reg_layers", 4 * A, out6[0], s);
-    t->head(cls2, "output_obj_layers", A, out6[1], s);
-    t->head(cls2, "output_cls_layers", nc, out6[2], s);
-    t->head(reg3, "output_reg_layers", 4 * A, out6[3], s);
-    t->head(cls3, "output_obj_layers", A, out6[4], s);
-    t->head(cls3, "output_cls_layers", nc, out6[5], s);
-  };
-
-  build(true);
-  const size_t need = t->used;
-  if (need > t->arena_floats) {
-    if (hipDeviceSynchronize() != hipSuccess) return yfv2_ctx_fail(h, YFV2_ERR_DEVICE, "yfv2_train_forward: device error before growing the workspace");
-    if (t->acts) (void)hipFree(t->acts);
-    if (t->grads) (void)hipFree(t->grads);
-    t->acts = t->grads = nullptr; t->arena_floats = 0;
-    if (hipMalloc(reinterpret_cast<void**>(&t->acts), need * sizeof(float)) != hipSuccess || hipMalloc(reinterpret_cast<void**>(&t->grads), need * sizeof(float)) != hipSuccess)
-      return yfv2_ctx_fail(h, YFV2_ERR_DEVICE, "yfv2_train_forward: out of device memory for the training workspace");
-    t->arena_floats = need;
+  DeviceGuard guard(t->cfg.device);
+  t->forward_done = false;
+  if (t->ops.empty() || t->B != B) {
+    t->record(B);
+    if (!t->err.empty()) { t->ops.clear(); return yfv2_ctx_fail(h, YFV2_ERR_WEIGHTS, t->err.c_str()); }
   }
-  const size_t npool = (size_t)B * 24 * (H / 4) * (W / 4);
-  if (npool > t->pool_arg_n) {
-    if (t->pool_arg) { (void)hipDeviceSynchronize(); (void)hipFree(t->pool_arg); }
-    if (hipMalloc(reinterpret_cast<void**>(&t->pool_arg), npool * sizeof(int)) != hipSuccess) return yfv2_ctx_fail(h, YFV2_ERR_DEVICE, "yfv2_train_forward: out of device memory");
-    t->pool_arg_n = npool;
-  }
-  if (!t->dscr) {
-    t->dscr_n = 1 << 16;   // 4 doubles x 16 K BatchNorm channels (the network has ~5 K)
-    if (hipMalloc(reinterpret_cast<void**>(&t->dscr), t->dscr_n * sizeof(double)) != hipSuccess) { t->dscr = nullptr; return yfv2_ctx_fail(h, YFV2_ERR_DEVICE, "yfv2_train_forward: out of device memory"); }
-  }
-  if (hipMemsetAsync(t->dscr, 0, t->dscr_n * sizeof(double), s) != hipSuccess) return yfv2_ctx_fail(h, YFV2_ERR_DEVICE, "yfv2_train_forward: memset failed");
-  t->dscr_used = 0;
-  if (!t->wscr) {
-    t->wscr_n = (size_t)1 << 19;   // every conv weight of the network (~0.24 M entries; the class head: classes (<= 255) x 72) in double
-    if (hipMalloc(reinterpret_cast<void**>(&t->wscr), t->wscr_n * sizeof(double)) != hipSuccess) { t->wscr = nullptr; return yfv2_ctx_fail(h, YFV2_ERR_DEVICE, "yfv2_train_forward: out of device memory"); }
-  }
-  build(false);
-  if (!t->err.empty()) { t->tape.clear(); return yfv2_ctx_fail(h, YFV2_ERR_WEIGHTS, t->err.c_str()); }
+  // the five blocks, exactly as large as the list says (a block that grows waits for the device before it frees)
+  if (int rc = t->acts.reserve(h, t->arena_floats * sizeof(float), true)) return rc;
+  if (int rc = t->grads.reserve(h, t->arena_floats * sizeof(float), true)) return rc;
+  if (int rc = t->pool_arg.reserve(h, t->pool_ints * sizeof(int), true)) return rc;
+  if (int rc = t->dscr.reserve(h, t->bn_doubles * sizeof(double), true)) return rc;
+  if (int rc = t->wscr.reserve(h, t->wg_doubles * sizeof(double), true)) return rc;
+  if (hipMemsetAsync(t->dscr.p, 0, t->bn_doubles * sizeof(double), s) != hipSuccess) return yfv2_ctx_fail(h, YFV2_ERR_DEVICE, "yfv2_train_forward: memset failed");
+  t->x = x;
+  for (const Op& o : t->ops) t->run_forward(o, out6, s);
   if (hipGetLastError() != hipSuccess) return yfv2_ctx_fail(h, YFV2_ERR_DEVICE, "yfv2_train_forward: launch failed");
+  t->forward_done = true;
   return YFV2_OK;
 }
 
 int yfv2_train_backward(yfv2_handle h, const float* const grad6[6], void* stream) {
   Train* t = h ? train_of(h, false) : nullptr;
-  if (!t || t->tape.empty() || t->heads.size() != 6) return yfv2_ctx_fail(h, YFV2_ERR_STATE, "yfv2_train_backward: no recorded yfv2_train_forward");
+  if (!t || !t->forward_done) return yfv2_ctx_fail(h, YFV2_ERR_STATE, "yfv2_train_backward: no recorded yfv2_train_forward");
   if (!grad6) return yfv2_ctx_fail(h, YFV2_ERR_ARG, "yfv2_train_backward: null pointer");
   for (int i = 0; i < 6; ++i) if (!grad6[i]) return yfv2_ctx_fail(h, YFV2_ERR_ARG, "yfv2_train_backward: null gradient tensor");
   hipStream_t s = static_cast<hipStream_t>(stream);
-  const int B = t->B;
-  if (hipMemsetAsync(t->grads, 0, t->used * sizeof(float), s) != hipSuccess) return yfv2_ctx_fail(h, YFV2_ERR_DEVICE, "yfv2_train_backward: memset failed");
-  if (hipMemsetAsync(t->wscr, 0, t->wscr_n * sizeof(double), s) != hipSuccess) return yfv2_ctx_fail(h, YFV2_ERR_DEVICE, "yfv2_train_backward: memset failed");
-  t->wscr_used = 0; t->fin.clear();
-  // the output convs: weights shared by the two scales -> their gradients accumulate (the caller zeroed the parameter gradients)
-  for (int i = 0; i < 6; ++i) {
-    const auto& u = t->heads[i];
-    float* w = t->P(u.name + ".weight"); float* gw = t->G(u.name + ".weight"); float* gb = t->G(u.name + ".bias");
-    if (!w || !gw || !gb) return yfv2_ctx_fail(h, YFV2_ERR_WEIGHTS, t->err.c_str());
-    V go{const_cast<float*>(grad6[i]), u.Cout, 0, 1, u.Cout, u.tin.H, u.tin.W};
-    hipLaunchKernelGGL(bias_bwd_kernel, dim3(u.Cout), dim3(256), 0, s, go, B, gb);
-    t->pw_weight_grad(t->view(u.tin, false), go, gw, B, s);
-    t->pw_data_grad(t->view(u.tin, true), go, w, B, s);
-  }
-  for (size_t i = t->tape.size(); i-- > 0;) t->tape[i](s);
-  t->tape.clear(); t->heads.clear();
-  if (!t->err.empty()) return yfv2_ctx_fail(h, YFV2_ERR_STATE, t->err.c_str());
+  DeviceGuard guard(t->cfg.device);
+  if (hipMemsetAsync(t->grads.p, 0, t->arena_floats * sizeof(float), s) != hipSuccess) return yfv2_ctx_fail(h, YFV2_ERR_DEVICE, "yfv2_train_backward: memset failed");
+  if (hipMemsetAsync(t->wscr.p, 0, t->wg_doubles * sizeof(double), s) != hipSuccess) return yfv2_ctx_fail(h, YFV2_ERR_DEVICE, "yfv2_train_backward: memset failed");
+  t->forward_done = false;
+  t->for_each_backward([&](const Op& o) { t->run_backward(o, grad6, s); });
   for (size_t i0 = 0; i0 < t->fin.size(); i0 += 96) {   // every weight gradient: scratch (double) -> the bound tensors
     FinishChunk c{};
     const int m = (int)std::min<size_t>(96, t->fin.size() - i0);
     int nmax = 0;
-    for (int k = 0; k < m; ++k) { c.it[k] = t->fin[i0 + k]; nmax = std::max(nmax, c.it[k].n); }
+    for (int k = 0; k < m; ++k) {
+      const Finish& f = t->fin[i0 + k];
+      c.it[k] = FinishItem{t->wscr.as<double>() + f.scr, f.dw, f.n, 0};
+      nmax = std::max(nmax, f.n);
+    }
     hipLaunchKernelGGL(wgrad_finish_multi_kernel, dim3(blocks_for((size_t)nmax), m), dim3(256), 0, s, c);
   }
-  t->fin.clear();
   if (hipGetLastError() != hipSuccess) return yfv2_ctx_fail(h, YFV2_ERR_DEVICE, "yfv2_train_backward: launch failed");
   return YFV2_OK;
 }
@@ -992,9 +955,10 @@ int yfv2_train_backward(yfv2_handle h, const float* const grad6[6], void* stream
 int64_t yfv2_debug_train_relu_output(yfv2_handle h, const char* conv_name, float* host_dst, int64_t capacity) {
   Train* t = h ? train_of(h, false) : nullptr;
   if (!t || !conv_name) { (void)yfv2_ctx_fail(h, YFV2_ERR_ARG, "yfv2_debug_train_relu_output: bad argument"); return -1; }
-  const auto it = t->relu_out.find(conv_name);
-  if (it == t->relu_out.end()) { (void)yfv2_ctx_fail(h, YFV2_ERR_STATE, "yfv2_debug_train_relu_output: no such ReLU output in the last yfv2_train_forward"); return -1; }
-  const V z = it->second;
+  const auto it = std::find_if(t->ops.begin(), t->ops.end(), [&](const Op& o) { return o.kind == OpKind::ConvBn && o.relu && o.name == conv_name; });
+  if (it == t->ops.end() || !t->acts.p) { (void)yfv2_ctx_fail(h, YFV2_ERR_STATE, "yfv2_debug_train_relu_output: no such ReLU output in the last yfv2_train_forward"); return -1; }
+  DeviceGuard guard(t->cfg.device);
+  const V z = t->act(it->out);
   const int64_t n = (int64_t)t->B * z.C * z.H * z.W;
   if (!host_dst || capacity < n) return n;
   float* dense = nullptr;
@@ -1019,6 +983,7 @@ int yfv2_sgd_step(yfv2_handle h, float* param, const float* grad, float* momentu
 
 int yfv2_sgd_step_multi(yfv2_handle h, const yfv2_sgd_item* items, int32_t n_items, float lr, float momentum, float weight_decay, void* stream) {
   if (!h || !items || n_items < 0) return yfv2_ctx_fail(h, YFV2_ERR_ARG, "yfv2_sgd_step_multi: bad argument");
+  DeviceGuard guard(yfv2_ctx_config(h)->device);
   for (int i0 = 0; i0 < n_items; i0 += 96) {
     SgdChunk c{};
     const int m = n_items - i0 < 96 ? n_items - i0 : 96;
