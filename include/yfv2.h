@@ -344,6 +344,67 @@ YFV2_API int yfv2_train_batch_frames_u8(yfv2_handle h, const yfv2_frame* frames,
 YFV2_API int yfv2_train_batch_frames_yuv(yfv2_handle h, const yfv2_frame_yuv* frames, int32_t B,
                                          const float* alpha, const float* beta, float* dst, void* stream);
 
+/* ---- second-stage crops: detections to resized crops, on the device ----
+ * A detector this small usually runs first in a cascade: every box is cut out of its frame, resized to a fixed size and handed to
+ * a second network.  These entry points do that without the host learning the boxes or their number: a plan launch turns the
+ * detection rows into the resize kernels' own frame descriptors, and the resize launch covers the output's capacity.
+ * THE RULE, bit for bit (tests/crops_model.py restates it; the library's one function of it is yfv2_crop_row_rect, yfv2_internal.h).
+ * Row r of frame b is fp32 x1, y1, x2, y2, conf, cls in frame coordinates (yfv2_detect_frames_* / yfv2_detect_tiled_* output), the
+ * frame is h x w pixels, px = double(pad_x), py = double(pad_y).  All arithmetic is IEEE double, every operation rounded on its
+ * own (no fused multiply-add).
+ *   candidate    r < min(max(count[b], 0), R), and cls is finite, equals an integer in 0..254 and that integer is one of
+ *                `classes` (NULL: every class)
+ *   skipped      a candidate with a coordinate that is not finite, or bw = x2 - x1 or bh = y2 - y1 not > 0; or, with
+ *                ax1 = x1 - px * bw, ax2 = x2 + px * bw, cx1 = max(ax1, 0), cx2 = min(ax2, w), one for which cx2 > cx1 fails; the
+ *                same in y with py, bh and h.  Counted per frame in crop_skipped, before and after the cut below; takes no slot.
+ *   rectangle    X0 = floor(cx1), X1 = ceil(cx2), Y0, Y1 likewise: rect = (X0, Y0, X1 - X0, Y1 - Y0).  The rule gives
+ *                0 <= X0 < X1 <= w, so nothing is clamped after the conversion to int and every rectangle has a pixel.
+ *   selection    frame b's crops are its first max_per_frame candidates that are not skipped, in row order (rows are conf-descending:
+ *                the top max_per_frame); n_b of them.  crop_offset = the exclusive prefix sum of n_b, crop_offset[B] the total.
+ *   numbering    crop k = crop_offset[b] + j is the j-th selected row of frame b; only crops k < min(crop_offset[B], cap) are written
+ *   pixels       crop k is the bilinear resize to (out_h, out_w) of the view {data + Y0 * row_pitch + 3 * X0, height, width,
+ *                row_pitch} of its frame: bit-identical to what yfv2_resize_frames_u8 writes for that view on a handle whose network
+ *                size is (out_h, out_w).  The two scales 1 / (out_w / width), 1 / (out_h / height) are the same two correctly
+ *                rounded double divisions, computed on the device. */
+typedef struct yfv2_crop_rule {
+  int32_t out_h, out_w;      /* the size of every crop; out_w a multiple of 4 */
+  float pad_x, pad_y;        /* each side of the box grows by pad * its extent on that axis; in [0, 16] */
+  int32_t max_per_frame;     /* >= 1 */
+  const int32_t* classes;    /* HOST: n_classes ints in 0..254, or NULL for every class */
+  int32_t n_classes;
+} yfv2_crop_rule;
+
+/* The rectangle of one box: host only, no handle, no device, like yfv2_tile_plan.  box: x1, y1, x2, y2.  Returns 1 and writes
+ * rect = X0, Y0, width, height; 0 when the rule skips the box (rect untouched); YFV2_ERR_ARG (negative) for a NULL pointer, a frame
+ * size < 1 or a pad that is not finite or outside [0, 16].  It calls the function the plan kernel calls. */
+YFV2_API int yfv2_crop_rect(const float box[4], int32_t frame_h, int32_t frame_w, float pad_x, float pad_y, int32_t rect[4]);
+
+/* frames: HOST array of B descriptors (the frames the rows were detected on); dets (B, R, 6) and count (B) on the device - R = 300
+ * for yfv2_detect_frames_* output, max_out for yfv2_detect_tiled_* output.  Outputs, all on the device: crops (cap, out_h, out_w,
+ * 3) uint8, 4-byte aligned; crop_src (cap) = b * R + r of each crop; crop_rect (cap, 4); crop_offset (B + 1); crop_skipped (B) or
+ * NULL.  Nothing is written beyond slot min(total, cap) of crops, crop_src and crop_rect; crop_offset[B] is the untruncated
+ * total, which is how a caller sees that cap was too small.  Enqueue only: two small plan launches and the resize launch (grid cap *
+ * out_h; a workgroup beyond the live crops returns at once), no host wait - except that the first call, or a call with a larger cap
+ * than any before, allocates the handle's crop descriptor table and waits for the device once.  No output depends on the launch
+ * geometry: slots come from ballots and integer prefix sums.  Checked before anything is enqueued (YFV2_ERR_ARG with a message):
+ * NULL pointers; B < 1; R outside 1..4096; cap < 1 or cap * out_h > 2^31 - 1; out_h < 1; out_w < 4 or not a multiple of 4; crops
+ * not 4-byte aligned; a pad that is not finite or outside [0, 16]; max_per_frame < 1; a class outside 0..254; everything
+ * yfv2_resize_frames_u8 checks per frame, with the width limit taken at out_w: (160 KiB - 3 out_w) / 6 - 2 pixels.  B > max_batch
+ * is YFV2_ERR_BATCH. */
+YFV2_API int yfv2_crop_detections_u8(yfv2_handle h, const yfv2_frame* frames /* HOST, B */, int32_t B,
+                                     const float* dets /* (B,R,6) */, const int32_t* count /* (B) */, int32_t R, const yfv2_crop_rule* rule,
+                                     uint8_t* crops /* (cap,out_h,out_w,3) */, int32_t* crop_src /* (cap) */, int32_t* crop_rect /* (cap,4) */,
+                                     int32_t* crop_offset /* (B+1) */, int32_t* crop_skipped /* (B) or NULL */, int32_t cap, void* stream);
+
+/* The same for YUV 4:2:0 frames: rectangles are relative to the frame's own rectangle (x0, y0, width, height of yfv2_frame_yuv),
+ * and the result is bit-identical to converting each frame with the integer colour formula above and calling
+ * yfv2_crop_detections_u8.  A crop's descriptor is its frame's with the origin moved by (X0, Y0) - any parity.  Checks: as above
+ * with everything yfv2_resize_frames_yuv checks per frame, its width limit taken at out_w. */
+YFV2_API int yfv2_crop_detections_yuv(yfv2_handle h, const yfv2_frame_yuv* frames /* HOST, B */, int32_t B,
+                                      const float* dets, const int32_t* count, int32_t R, const yfv2_crop_rule* rule,
+                                      uint8_t* crops, int32_t* crop_src, int32_t* crop_rect, int32_t* crop_offset, int32_t* crop_skipped,
+                                      int32_t cap, void* stream);
+
 /* ---- the ncnn sample's deployment path (sample/ncnn/src/yolo-fastestv2.cpp) ----
  * The reference's only native component post-processes differently from its Python path in every step that decides which boxes
  * come out: no objectness pre-filter (score = cls * obj > thresh only), boxes scaled to the source frame and TRUNCATED TO int

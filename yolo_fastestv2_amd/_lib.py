@@ -84,6 +84,12 @@ class Tile(C.Structure):
     _fields_ = [("frame", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("width", C.c_int32), ("height", C.c_int32)]
 
 
+class CropRule(C.Structure):
+    """yfv2_crop_rule (include/yfv2.h): the size, pad, cut and class filter of second-stage crops; classes is a HOST pointer."""
+    _fields_ = [("out_h", C.c_int32), ("out_w", C.c_int32), ("pad_x", C.c_float), ("pad_y", C.c_float), ("max_per_frame", C.c_int32),
+                ("classes", C.POINTER(C.c_int32)), ("n_classes", C.c_int32)]
+
+
 class KmeansInfo(C.Structure):
     """yfv2_kmeans_info (include/yfv2.h): what ended yfv2_anchor_kmeans' loop."""
     _fields_ = [("struct_size", C.c_int32), ("iterations", C.c_int32), ("converged", C.c_int32), ("empty_cluster", C.c_int32),
@@ -156,6 +162,11 @@ _PROTOTYPES = {
                                         C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "yfv2_train_batch_frames_u8": (C.c_int, [C.c_void_p, C.POINTER(Frame), C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_void_p]),
     "yfv2_train_batch_frames_yuv": (C.c_int, [C.c_void_p, C.POINTER(FrameYuv), C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_void_p, C.c_void_p]),
+    "yfv2_crop_rect": (C.c_int, [C.POINTER(C.c_float), C.c_int32, C.c_int32, C.c_float, C.c_float, C.POINTER(C.c_int32)]),
+    "yfv2_crop_detections_u8": (C.c_int, [C.c_void_p, C.POINTER(Frame), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(CropRule),
+                                          C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "yfv2_crop_detections_yuv": (C.c_int, [C.c_void_p, C.POINTER(FrameYuv), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(CropRule),
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "yfv2_export_maps": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "yfv2_deploy_post": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
                                    C.c_int32, C.c_void_p]),

@@ -3,7 +3,7 @@
 // Frames come in two kinds, yfv2_frame (packed B, G, R) and yfv2_frame_yuv (4:2:0 planes).  Each kind is described once
 // (BgrFrames, YuvFrames: what differs); check_frames<Kind> turns a caller's batch into a FrameBatch, enqueue_resize resizes
 // one, enqueue_train_batch makes the training batch of one, and resize_frames / train_batch_frames / detect_frames /
-// detect_tiled are one template each.  The extern "C" functions pass their names.
+// crop_detections / detect_tiled are one template each.  The extern "C" functions pass their names.
 #include <algorithm>
 #include <cmath>
 
@@ -14,8 +14,8 @@
 struct FrameScales { double scale_x, scale_y, box_x, box_y; };
 static FrameScales frame_scales(int w, int h, int W, int H) {
   FrameScales s;
-  s.scale_x = 1.0 / ((double)W / (double)w);      // cv::resize: inv_scale = dsize / ssize, scale = 1 / inv_scale
-  s.scale_y = 1.0 / ((double)H / (double)h);
+  s.scale_x = yfv2_resize_scale(W, w);            // cv::resize: inv_scale = dsize / ssize, scale = 1 / inv_scale
+  s.scale_y = yfv2_resize_scale(H, h);
   s.box_x = (double)w / (double)W;                // test.py:58  scale_w = w / cfg["width"]
   s.box_y = (double)h / (double)H;
   return s;
@@ -82,14 +82,11 @@ struct YuvFrames {
   static int max_width(int W) { return yfv2_resize_yuv_max_width(W); }
   static int expand(yfv2_handle, const std::string&, const Frame& f, FrameBatch& fb, size_t b) {
     if (fb.yuv.empty()) fb.yuv.assign(fb.t.size(), ResizeFrameYuv{});
-    const bool planar = f.format == YFV2_YUV_I420;
     ResizeFrameYuv& r = fb.yuv[b];
-    const long long coff = (long long)(f.y0 >> 1) * f.pitch_c + (long long)(f.x0 >> 1) * (planar ? 1 : 2);
-    r.y = f.y + (long long)f.y0 * f.pitch_y + f.x0;
-    r.ca = f.u + coff;
-    r.cb = planar ? f.v + coff : nullptr;
+    r.y = f.y; r.ca = f.u; r.cb = f.format == YFV2_YUV_I420 ? f.v : nullptr;      // the planes at their own origin ...
     r.pitch_y = f.pitch_y; r.pitch_c = f.pitch_c; r.h = f.height; r.w = f.width;
-    r.px = f.x0 & 1; r.py = f.y0 & 1; r.format = f.format; r.coef = yfv2_yuv_coef(f.colour);
+    r.px = 0; r.py = 0; r.format = f.format; r.coef = yfv2_yuv_coef(f.colour);
+    yfv2_yuv_move(r, f.x0, f.y0);                                                 // ... moved to the frame's (the fold, yfv2_internal.h)
     r.scale_x = fb.t[b].scale_x; r.scale_y = fb.t[b].scale_y;
     return YFV2_OK;
   }
@@ -107,14 +104,14 @@ struct TrainYuvFrames : YuvFrames { static int max_width(int W) { return yfv2_tr
 
 // Ragged batches: every frame is checked here, before anything is enqueued, and expanded by its scales into fb.  The tables are
 // B entries of the handle's max_batch, so B is bound by max_batch on every entry point.
+// (H, W): what the frames are resized to - the network's size on every entry point but the crops', whose caller names it.
 template <class Kind>
-static int check_frames(yfv2_handle h, const char* what, const typename Kind::Frame* frames, int32_t B, FrameBatch& fb) {
+static int check_frames(yfv2_handle h, const char* what, const typename Kind::Frame* frames, int32_t B, FrameBatch& fb, int H, int W) {
   const std::string w_ = what;
   if (!frames) return fail(h, YFV2_ERR_ARG, w_ + ": null pointer");
   if (B < 1) return fail(h, YFV2_ERR_ARG, w_ + ": B < 1");
   if (B > h->cfg.max_batch)
     return fail(h, YFV2_ERR_BATCH, w_ + ": batch " + std::to_string(B) + " above max_batch=" + std::to_string(h->cfg.max_batch));
-  const int H = h->cfg.height, W = h->cfg.width;
   const int limit = Kind::max_width(W);
   fb.t.assign((size_t)B, ResizeFrame{});
   for (int32_t b = 0; b < B; ++b) {
@@ -130,6 +127,10 @@ static int check_frames(yfv2_handle h, const char* what, const typename Kind::Fr
   }
   if ((long long)B * H > 0x7fffffffll) return fail(h, YFV2_ERR_ARG, w_ + ": batch too large");
   return YFV2_OK;
+}
+template <class Kind>
+static int check_frames(yfv2_handle h, const char* what, const typename Kind::Frame* frames, int32_t B, FrameBatch& fb) {
+  return check_frames<Kind>(h, what, frames, B, fb, h->cfg.height, h->cfg.width);
 }
 
 // The submit of every frame batch: ONE copy of the descriptor table into the handle's table of its kind, ONE launch reading it.
@@ -226,7 +227,89 @@ static int detect_frames(yfv2_handle h, const char* what, const typename Kind::F
   return detect_frames_tail(h, fb, B, conf_thres, iou_thres, dets, idx, count, stream);
 }
 
+// ---- second-stage crops (kernels: yfv2_crops.hip and the counted instantiations of yfv2_pre.hip) -----------------
+// yfv2_crop_detections_u8 / _yuv.  Every check first - the call's own arguments, then the frames under the width limit of the
+// CROPS' width - then the workspace (the first call, or a larger cap: one device wait), the frame table's one copy, the two plan
+// launches and the resize launch over the table's capacity.  The host never reads a count.
+constexpr int CROP_MAX_R = 4096;
+constexpr double CROP_MAX_PAD = 16.0;
+
+template <class Kind>
+static int crop_detections(yfv2_handle h, const char* what, const typename Kind::Frame* frames, int32_t B, const float* dets, const int32_t* count, int32_t R,
+                           const yfv2_crop_rule* rule, uint8_t* crops, int32_t* crop_src, int32_t* crop_rect, int32_t* crop_offset, int32_t* crop_skipped,
+                           int32_t cap, void* stream) {
+  const std::string w_ = what;
+  if (!h) return fail(nullptr, YFV2_ERR_ARG, "null handle");
+  if (!frames || !dets || !count || !rule || !crops || !crop_src || !crop_rect || !crop_offset) return fail(h, YFV2_ERR_ARG, w_ + ": null pointer");
+  if (B < 1) return fail(h, YFV2_ERR_ARG, w_ + ": B < 1");
+  if (R < 1 || R > CROP_MAX_R) return fail(h, YFV2_ERR_ARG, w_ + ": R must be in 1.." + std::to_string(CROP_MAX_R));
+  const yfv2_crop_rule& q = *rule;
+  if (q.out_h < 1) return fail(h, YFV2_ERR_ARG, w_ + ": out_h must be >= 1");
+  if (q.out_w < 4 || q.out_w % 4 != 0) return fail(h, YFV2_ERR_ARG, w_ + ": out_w must be a multiple of 4, at least 4");
+  if (cap < 1 || (long long)cap * q.out_h > 0x7fffffffll) return fail(h, YFV2_ERR_ARG, w_ + ": cap must be >= 1 and cap * out_h at most 2^31 - 1");
+  if ((reinterpret_cast<uintptr_t>(crops) & 3) != 0) return fail(h, YFV2_ERR_ARG, w_ + ": crops must be 4-byte aligned");
+  if (!std::isfinite(q.pad_x) || !std::isfinite(q.pad_y) || q.pad_x < 0.f || q.pad_y < 0.f || q.pad_x > CROP_MAX_PAD || q.pad_y > CROP_MAX_PAD)
+    return fail(h, YFV2_ERR_ARG, w_ + ": pad_x and pad_y must be finite numbers in [0, 16]");
+  if (q.max_per_frame < 1) return fail(h, YFV2_ERR_ARG, w_ + ": max_per_frame must be >= 1");
+  if (q.n_classes < 0 || (q.n_classes > 0 && !q.classes)) return fail(h, YFV2_ERR_ARG, w_ + ": n_classes < 0, or classes NULL with n_classes > 0");
+  CropPlanArgs a{};
+  if (!q.classes) {
+    for (int i = 0; i < 8; ++i) a.classes[i] = i < 7 ? 0xffffffffu : 0x7fffffffu;     // classes 0..254
+  } else {
+    for (int32_t i = 0; i < q.n_classes; ++i) {
+      const int32_t c = q.classes[i];
+      if (c < 0 || c > 254) return fail(h, YFV2_ERR_ARG, w_ + ": class " + std::to_string(c) + " outside 0..254");
+      a.classes[c >> 5] |= 1u << (c & 31);
+    }
+  }
+  FrameBatch fb;
+  if (int rc = check_frames<Kind>(h, what, frames, B, fb, q.out_h, q.out_w)) return rc;
+  if ((long long)B * R > 0x7fffffffll) return fail(h, YFV2_ERR_ARG, w_ + ": B * R above 2^31 - 1");
+  DeviceGuard guard(h->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  // the workspace: n_sel (max_batch int32, rounded to 16 bytes), the table's head, the table: cap entries of the wider kind
+  const size_t n_bytes = (sizeof(int32_t) * (size_t)h->cfg.max_batch + 15) & ~(size_t)15;
+  const int ws_cap = std::max(cap, h->crop_cap);
+  if (int rc = h->crop_ws.reserve(h, n_bytes + sizeof(CountedHead) + sizeof(CropFrameYuv) * (size_t)ws_cap, true)) return rc;
+  h->crop_cap = ws_cap;
+  char* base = h->crop_ws.as<char>();
+  a.dets = dets; a.count = count; a.B = B; a.R = R; a.out_h = q.out_h; a.out_w = q.out_w; a.pad_x = q.pad_x; a.pad_y = q.pad_y;
+  a.max_per_frame = q.max_per_frame; a.n_sel = reinterpret_cast<int32_t*>(base); a.src = crop_src; a.rect = crop_rect; a.offset = crop_offset;
+  a.skipped = crop_skipped; a.cap = cap; a.head = reinterpret_cast<CountedHead*>(base + n_bytes);
+  void* table = base + n_bytes + sizeof(CountedHead);
+  if (fb.yuv.empty())
+    return submit_frames(h, fb.t, h->d_frames, B, s, [&](const ResizeFrame* d) {
+      yfv2_launch_crop_plan(a, d, static_cast<CropFrame*>(table), s);
+      yfv2_launch_resize_crops(static_cast<const CropFrame*>(table), cap, fb.max_w, crops, q.out_h, q.out_w, s);
+    });
+  return submit_frames(h, fb.yuv, h->d_frames_yuv, B, s, [&](const ResizeFrameYuv* d) {
+    yfv2_launch_crop_plan_yuv(a, d, static_cast<CropFrameYuv*>(table), s);
+    yfv2_launch_resize_crops_yuv(static_cast<const CropFrameYuv*>(table), cap, fb.max_w, crops, q.out_h, q.out_w, s);
+  });
+}
+
 extern "C" {
+
+int yfv2_crop_rect(const float box[4], int32_t frame_h, int32_t frame_w, float pad_x, float pad_y, int32_t rect[4]) {
+  if (!box || !rect) return fail(nullptr, YFV2_ERR_ARG, "yfv2_crop_rect: null pointer");
+  if (frame_h < 1 || frame_w < 1) return fail(nullptr, YFV2_ERR_ARG, "yfv2_crop_rect: frame_h and frame_w must be >= 1");
+  if (!std::isfinite(pad_x) || !std::isfinite(pad_y) || pad_x < 0.f || pad_y < 0.f || pad_x > CROP_MAX_PAD || pad_y > CROP_MAX_PAD)
+    return fail(nullptr, YFV2_ERR_ARG, "yfv2_crop_rect: pad_x and pad_y must be finite numbers in [0, 16]");
+  int rc[4];
+  if (!yfv2_crop_row_rect(box, frame_h, frame_w, pad_x, pad_y, rc)) return 0;
+  for (int i = 0; i < 4; ++i) rect[i] = rc[i];
+  return 1;
+}
+
+int yfv2_crop_detections_u8(yfv2_handle h, const yfv2_frame* frames, int32_t B, const float* dets, const int32_t* count, int32_t R, const yfv2_crop_rule* rule,
+                            uint8_t* crops, int32_t* crop_src, int32_t* crop_rect, int32_t* crop_offset, int32_t* crop_skipped, int32_t cap, void* stream) {
+  return crop_detections<BgrFrames>(h, "yfv2_crop_detections_u8", frames, B, dets, count, R, rule, crops, crop_src, crop_rect, crop_offset, crop_skipped, cap, stream);
+}
+
+int yfv2_crop_detections_yuv(yfv2_handle h, const yfv2_frame_yuv* frames, int32_t B, const float* dets, const int32_t* count, int32_t R, const yfv2_crop_rule* rule,
+                             uint8_t* crops, int32_t* crop_src, int32_t* crop_rect, int32_t* crop_offset, int32_t* crop_skipped, int32_t cap, void* stream) {
+  return crop_detections<YuvFrames>(h, "yfv2_crop_detections_yuv", frames, B, dets, count, R, rule, crops, crop_src, crop_rect, crop_offset, crop_skipped, cap, stream);
+}
 
 int yfv2_resize_u8(yfv2_handle h, const uint8_t* src, int32_t B, int32_t src_h, int32_t src_w, uint8_t* dst, void* stream) {
   if (!h) return fail(nullptr, YFV2_ERR_ARG, "null handle");

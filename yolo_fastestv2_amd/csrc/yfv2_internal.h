@@ -361,6 +361,20 @@ struct ResizeFrameYuv {
   YuvCoef coef;               // the colour standard's row, copied in by the host: the kernel does not wait for a second, dependent load
   double scale_x, scale_y;    // resize: 1 / (W / w), 1 / (H / h), as ResizeArgs
 };
+// THE FOLD of an origin into the plane pointers, written once for the host (a caller's x0, y0; a tile's) and the device (a crop's
+// rectangle, yfv2_crops.hip): the descriptor's pixel (dy, dx) becomes its pixel (0, 0).  h and w stay the caller's to set.
+__host__ __device__ inline void yfv2_yuv_move(ResizeFrameYuv& r, int dx, int dy) {
+  const bool planar = r.cb != nullptr;
+  const int cx = (dx + r.px) >> 1, cy = (dy + r.py) >> 1;      // chroma sample / row of the new origin, from the old one's
+  const long long coff = (long long)cy * r.pitch_c + (long long)cx * (planar ? 1 : 2);
+  r.y += (long long)dy * r.pitch_y + dx;
+  r.ca += coff;
+  if (planar) r.cb += coff;
+  r.px = (dx + r.px) & 1; r.py = (dy + r.py) & 1;
+}
+// The resize scale of one axis, `in` source pixels to `out`: cv::resize's inv_scale = dsize / ssize, scale = 1 / inv_scale, two
+// correctly rounded fp64 divisions on either side (no unit that calls it has a fast-math flag).
+__host__ __device__ inline double yfv2_resize_scale(int out, int in) { return 1.0 / ((double)out / (double)in); }
 size_t yfv2_resize_yuv_lds_bytes(int w, int W);   // LDS of one workgroup of the YUV resize for a frame w pixels wide
 int yfv2_resize_yuv_max_width(int W);             // the widest frame whose workgroup fits YFV2_LDS_FULL
 YuvCoef yfv2_yuv_coef(int colour);                // YFV2_BT601_LIMITED .. YFV2_BT709_FULL -> its row
@@ -376,6 +390,59 @@ size_t yfv2_train_batch_yuv_lds_bytes(int w, int W);
 int yfv2_train_batch_yuv_max_width(int W);          // the widest YUV frame that fits, <= yfv2_resize_yuv_max_width(W)
 void yfv2_launch_train_batch_frames(const TrainFrame* frames, int B, int max_w, float* dst /* (B,3,H,W), 16-byte aligned */, int H, int W, hipStream_t s);
 void yfv2_launch_train_batch_frames_yuv(const TrainFrameYuv* frames, int B, int max_w, float* dst, int H, int W, hipStream_t s);
+// ---- second-stage crops (yfv2_crop_detections_u8 / _yuv; kernels: yfv2_crops.hip, the resize launch: yfv2_pre.hip)
+// THE RECTANGLE RULE, one axis of it, written once: yfv2_crop_rect (host) and the plan kernels (device) both call this function;
+// include/yfv2.h states it for callers, tests/crops_model.py in Python.  a1, a2: the box's two edges on the axis; pad: the factor;
+// n: the frame's length.  IEEE double throughout, every operation rounded on its own (the pragma holds whatever the unit's flags).
+// false: the row is skipped.  true: 0 <= o < o + len <= n, so the conversion to int needs no clamp behind it.
+__host__ __device__ inline bool yfv2_crop_axis(double a1, double a2, double pad, int n, int& o, int& len) {
+#pragma clang fp contract(off)
+  const double b = a2 - a1;
+  if (!(b > 0.0)) return false;
+  const double m = pad * b;
+  const double lo = a1 - m, hi = a2 + m;
+  const double c1 = lo > 0.0 ? lo : 0.0;                 // max(ax1, 0)
+  const double c2 = hi < (double)n ? hi : (double)n;     // min(ax2, n)
+  if (!(c2 > c1)) return false;
+  o = (int)floor(c1);
+  len = (int)ceil(c2) - o;
+  return true;
+}
+// ... and the whole rule for one row: the four coordinates finite, both extents > 0, then each axis.  rect = X0, Y0, width, height.
+__host__ __device__ inline bool yfv2_crop_row_rect(const float box[4], int frame_h, int frame_w, float pad_x, float pad_y, int rect[4]) {
+  for (int i = 0; i < 4; ++i)
+    if (!(fabsf(box[i]) <= 3.402823466e38f)) return false;   // NaN or an infinity
+  const double x1 = box[0], y1 = box[1], x2 = box[2], y2 = box[3];
+  if (!(x2 - x1 > 0.0) || !(y2 - y1 > 0.0)) return false;
+  return yfv2_crop_axis(x1, x2, (double)pad_x, frame_w, rect[0], rect[2]) && yfv2_crop_axis(y1, y2, (double)pad_y, frame_h, rect[1], rect[3]);
+}
+// A descriptor table the DEVICE writes: the resize kernels' descriptors with a head of 16 bytes directly in front of entry 0 whose
+// first int32 is the number of live entries.  A workgroup of a counted instantiation whose entry is not live returns at once.
+template <class D> struct Counted : D { static constexpr bool COUNTED = true; };
+struct CountedHead { int32_t live; int32_t pad[3]; };
+using CropFrame = Counted<ResizeFrame>;
+using CropFrameYuv = Counted<ResizeFrameYuv>;
+struct CropPlanArgs {
+  const float* dets;           // (B, R, 6): x1, y1, x2, y2, conf, cls in frame coordinates
+  const int32_t* count;        // (B)
+  int B, R;
+  int out_h, out_w;
+  float pad_x, pad_y;
+  int max_per_frame;
+  uint32_t classes[8];         // bit c: class c passes (0..254); all 255 set = no filter
+  int32_t* n_sel;              // workspace (B): the frame's selected rows, written by the count launch, read by the write launch
+  int32_t* src;                // (cap) b * R + r
+  int32_t* rect;               // (cap, 4)
+  int32_t* offset;             // (B + 1)
+  int32_t* skipped;            // (B) or null
+  int cap;
+  CountedHead* head;           // directly in front of the descriptor table
+};
+void yfv2_launch_crop_plan(const CropPlanArgs& a, const ResizeFrame* frames, CropFrame* table, hipStream_t s);          // two launches
+void yfv2_launch_crop_plan_yuv(const CropPlanArgs& a, const ResizeFrameYuv* frames, CropFrameYuv* table, hipStream_t s);
+// the resize of the live entries of a counted table into crops (cap, H, W, 3): grid cap * H, LDS for a source row of max_w pixels
+void yfv2_launch_resize_crops(const CropFrame* table, int cap, int max_w, unsigned char* crops, int H, int W, hipStream_t s);
+void yfv2_launch_resize_crops_yuv(const CropFrameYuv* table, int cap, int max_w, unsigned char* crops, int H, int W, hipStream_t s);
 // dets columns 0-3 of the first count[b] rows of frame b times frames[b].box_x / box_y (yfv2_post.hip)
 void yfv2_launch_frame_boxes(float* dets, const int32_t* count, const ResizeFrame* frames, int B, hipStream_t s);
 void yfv2_launch_decode(const DecodeArgs& a, hipStream_t s);

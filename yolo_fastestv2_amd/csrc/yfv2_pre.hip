@@ -172,6 +172,17 @@ __global__ __launch_bounds__(256) void resize_u8_kernel(ResizeArgs a) {
 // instantiation <ResizeFrame, RowU8> must stay the instruction stream it was.  <TrainFrame, RowTrain> is the training entry point's
 // launch (train_batch_frames_u8_kernel below): the same staging, guards, coefficients and blend, so its batch is the resize's
 // bytes looked up in the frame's table.
+// A third pair of instantiations reads a table the DEVICE wrote (second-stage crops, yfv2_crops.hip): descriptors
+// Counted<...> with a CountedHead in front of entry 0.  The host does not know how many entries are live, so the grid covers the
+// table's capacity and a workgroup whose entry is not live returns here - before the descriptor load and before any barrier, on a
+// value every thread of the workgroup reads alike.  For a descriptor without COUNTED the test is no code at all: the four host-table
+// instantiations are the instruction streams they were (profiles/crops_isa.txt).
+template <class Frame>
+__device__ __forceinline__ bool yfv2_not_live(const Frame* frames, int b) {
+  if constexpr (requires { Frame::COUNTED; }) return b >= reinterpret_cast<const CountedHead*>(frames)[-1].live;
+  else return false;
+}
+
 constexpr int RF_THREADS = 128;   // 2 waves: 12 workgroups (rows) per CU fit the LDS of 1920-wide frames, 8 of 4 waves would
 template <class Frame, class Row>
 __global__ __launch_bounds__(RF_THREADS, 6) void resize_frames_u8_kernel(const Frame* __restrict__ frames, typename Row::Out* __restrict__ dst, int H, int W) {
@@ -179,6 +190,7 @@ __global__ __launch_bounds__(RF_THREADS, 6) void resize_frames_u8_kernel(const F
   Row row{dst};
   const int tid = threadIdx.x;
   const int b = blockIdx.x / H, oy = blockIdx.x - b * H;
+  if (yfv2_not_live(frames, b)) return;
   const Frame f = frames[b];
   const RowCoef ry = yfv2_axis_coef(oy, f.scale_y, f.h, false);
   const int row_bytes = f.w * 3;
@@ -287,6 +299,7 @@ __global__ __launch_bounds__(RY_THREADS, 8) void resize_frames_yuv_kernel(const 
   Row row{dst};
   const int tid = threadIdx.x;
   const int b = blockIdx.x / H, oy = blockIdx.x - b * H;
+  if (yfv2_not_live(frames, b)) return;
   const Frame f = frames[b];
   const RowCoef ry = yfv2_axis_coef(oy, f.scale_y, f.h, false);
   const bool planar = f.format == YFV2_YUV_I420;
@@ -440,6 +453,18 @@ void yfv2_launch_resize_frames(const ResizeFrame* frames, int B, int max_w, unsi
 void yfv2_launch_resize_frames_yuv(const ResizeFrameYuv* frames, int B, int max_w, unsigned char* dst, int H, int W, hipStream_t s) {
   YFV2_LAUNCH_LDS(yfv2_device(), (resize_frames_yuv_kernel<ResizeFrameYuv, RowU8<RY_THREADS>>), YFV2_LDS_FULL, dim3((unsigned)(B * H)), dim3(RY_THREADS), yfv2_resize_yuv_lds_bytes(max_w, W), s,
                   frames, dst, H, W);
+}
+
+// The crops of a counted table: one workgroup per (entry of the table's capacity, output row); LDS for the widest FRAME of the call,
+// an upper bound of every crop of it (the crops' own widths exist on the device only).
+void yfv2_launch_resize_crops(const CropFrame* table, int cap, int max_w, unsigned char* crops, int H, int W, hipStream_t s) {
+  YFV2_LAUNCH_LDS(yfv2_device(), (resize_frames_u8_kernel<CropFrame, RowU8<RF_THREADS>>), YFV2_LDS_FULL, dim3((unsigned)(cap * H)), dim3(RF_THREADS), yfv2_resize_lds_bytes(max_w, W), s,
+                  table, crops, H, W);
+}
+
+void yfv2_launch_resize_crops_yuv(const CropFrameYuv* table, int cap, int max_w, unsigned char* crops, int H, int W, hipStream_t s) {
+  YFV2_LAUNCH_LDS(yfv2_device(), (resize_frames_yuv_kernel<CropFrameYuv, RowU8<RY_THREADS>>), YFV2_LDS_FULL, dim3((unsigned)(cap * H)), dim3(RY_THREADS), yfv2_resize_yuv_lds_bytes(max_w, W), s,
+                  table, crops, H, W);
 }
 
 void yfv2_launch_train_batch_frames(const TrainFrame* frames, int B, int max_w, float* dst, int H, int W, hipStream_t s) {

@@ -433,6 +433,69 @@ class Engine:
         return self._detect_tiled("detect_tiled_yuv", self._yuv_table, _lib.lib().yfv2_detect_tiled_yuv, lambda fr: (fr.height, fr.width),
                                   frames, tiles, conf_thres, iou_thres, merge_thres, metric, max_out, tile, overlap, include_full, out, check)
 
+    # ---- second-stage crops (include/yfv2.h yfv2_crop_detections_u8 / _yuv) ---------------------------------------
+    def _crop_detections(self, name, table, native, frames, dets, count, out_size, pad, max_per_frame, classes, cap, out):
+        arr, keep = table(frames)
+        B = len(keep)
+        if (not torch.is_tensor(dets) or dets.dim() != 3 or dets.shape[0] != B or dets.shape[2] != 6 or dets.dtype != torch.float32 or dets.device != self.device
+                or not dets.is_contiguous() or not torch.is_tensor(count) or tuple(count.shape) != (B,) or count.dtype != torch.int32
+                or count.device != self.device or not count.is_contiguous()):
+            raise ValueError("%s: dets must be contiguous fp32 (%d,R,6) and count contiguous int32 (%d,) on %s" % (name, B, B, self.device))
+        R = int(dets.shape[1])
+        out_h, out_w = (int(v) for v in out_size)
+        pad_y, pad_x = (float(v) for v in pad) if isinstance(pad, (tuple, list)) else (float(pad), float(pad))
+        max_per_frame = int(max_per_frame)
+        rule = _lib.CropRule()
+        rule.out_h, rule.out_w, rule.pad_x, rule.pad_y, rule.max_per_frame = out_h, out_w, pad_x, pad_y, max_per_frame
+        if classes is not None:
+            cl = [int(c) for c in classes]
+            carr = (C.c_int32 * max(len(cl), 1))(*cl)
+            rule.classes, rule.n_classes = C.cast(carr, C.POINTER(C.c_int32)), len(cl)
+        if cap is None:
+            cap = B * min(R, max(max_per_frame, 1))
+        cap = int(cap)
+        shapes = ((cap, out_h, out_w, 3), (cap,), (cap, 4), (B + 1,), (B,))
+        if out is None:
+            if cap < 1 or out_h < 1 or out_w < 1:
+                raise ValueError("%s: cap and out_size must be >= 1" % name)
+            out = tuple(torch.empty(sh, device=self.device, dtype=torch.uint8 if i == 0 else torch.int32) for i, sh in enumerate(shapes))
+        else:
+            if len(out) != 5:
+                raise ValueError("%s: out must be (crops, crop_src, crop_rect, crop_offset, crop_skipped)" % name)
+            for i, (t, sh) in enumerate(zip(out, shapes)):
+                if t is None and i == 4:
+                    continue            # crop_skipped is optional
+                dt = torch.uint8 if i == 0 else torch.int32
+                if not torch.is_tensor(t) or tuple(t.shape) != sh or t.dtype != dt or t.device != self.device or not t.is_contiguous():
+                    raise ValueError("%s: out must be contiguous (crops %s uint8, crop_src %s, crop_rect %s, crop_offset %s, crop_skipped %s or None, "
+                                     "int32) on %s" % ((name,) + shapes + (self.device,)))
+        self.ensure_batch(B)
+        crops, src, rect, offset, skipped = out
+        check(native(self._h, arr, B, _ptr(dets), _ptr(count), R, C.byref(rule), _ptr(crops), _ptr(src), _ptr(rect), _ptr(offset),
+                     _ptr(skipped) if skipped is not None else None, cap, _stream(self.device)), self._h)
+        return crops, src, rect, offset, skipped
+
+    def crop_detections(self, frames, dets, count, out_size, pad=0.0, max_per_frame=MAX_DET, classes=None, cap=None, out=None):
+        """The step behind detect_frames / detect_tiled in a cascade, on the device: every detection's box, grown by `pad` times its
+        extent on each side and clipped to its frame, is cut out of the frame and resized to out_size = (h, w), w a multiple of 4.
+        frames: the list of uint8 (h_i, w_i, 3) device tensors the rows were detected on; dets (B, R, 6) fp32 / count (B) int32 in
+        frame coordinates (R = 300 from detect_frames, max_out from detect_tiled).  pad: one number or (pad_y, pad_x), in [0, 16];
+        max_per_frame: at most that many crops per frame, the first in row order; classes: None or the classes to crop; cap: the
+        capacity of the outputs, default B * min(R, max_per_frame).  Returns (crops (cap, h, w, 3) uint8, crop_src (cap) = b * R + r,
+        crop_rect (cap, 4) = x0, y0, width, height, crop_offset (B + 1), crop_skipped (B)): frame b's crops are slots crop_offset[b]
+        .. crop_offset[b + 1]; slots from min(crop_offset[B], cap) on are not written, and crop_offset[B] > cap says cap was too small.
+        The rule, bit for bit: include/yfv2.h; each crop equals resize_frames of its view on an engine of size out_size.  Enqueue
+        only (the first call, or a larger cap, allocates the handle's descriptor table and waits once); grows max_batch like every
+        batched call."""
+        return self._crop_detections("crop_detections", self._frame_table, _lib.lib().yfv2_crop_detections_u8, frames, dets, count, out_size, pad,
+                                     max_per_frame, classes, cap, out)
+
+    def crop_detections_yuv(self, frames, dets, count, out_size, pad=0.0, max_per_frame=MAX_DET, classes=None, cap=None, out=None):
+        """`crop_detections` for a list of yuv.YuvFrame: rectangles are relative to each frame's own rectangle, and the result is
+        bit-identical to crop_detections on the converted frames."""
+        return self._crop_detections("crop_detections_yuv", self._yuv_table, _lib.lib().yfv2_crop_detections_yuv, frames, dets, count, out_size, pad,
+                                     max_per_frame, classes, cap, out)
+
     # ---- the ncnn sample's deployment path (include/yfv2.h yfv2_export_maps / yfv2_deploy_post; DESIGN.md 4.14) ------------------
     def map_shapes(self, B):
         C5 = 5 * self.anchor_num + self.classes
