@@ -405,6 +405,67 @@ YFV2_API int yfv2_crop_detections_yuv(yfv2_handle h, const yfv2_frame_yuv* frame
                                       uint8_t* crops, int32_t* crop_src, int32_t* crop_rect, int32_t* crop_offset, int32_t* crop_skipped,
                                       int32_t cap, void* stream);
 
+/* ---- identity across frames: a per-stream IoU tracker on the device ----
+ * The inputs of the entry points above are video: many streams, one frame of each per batch.  A tracker gives every detection an
+ * identity that lasts across frames, so that a second stage runs once per object: its state lives on the device, one launch updates
+ * it from a batch of detection rows, and the launch can emit - compacted, in the (dets, count) layout yfv2_crop_detections_* takes -
+ * exactly the rows whose track was confirmed in this frame.  No motion model: an unmatched track keeps its last box.
+ * THE RULE, bit for bit (tests/track_model.py restates it; the one function of the IoU is behind yfv2_track_iou).
+ * A tracker has S streams, each a table of M = max_tracks slots.
+ *   state        one caller-owned device buffer of S * (8 + 10 * M) int32 words; all zero = empty.  Per stream 8 header words - ids
+ *                issued, live tracks, frames seen, births, deaths, dropped births, 0, 0 - then M slots of 10 words: the fp32 bits of
+ *                x1, y1, x2, y2, conf, cls, then int32 id, hits, misses, age.  id == 0: the slot is free and all ten words are zero.
+ *   a call       B frames; frame b belongs to stream stream_of[b], the streams of one call are distinct; its rows are dets[b, 0..n),
+ *                n = min(max(count[b], 0), R), fp32 x1, y1, x2, y2, conf, cls (yfv2_detect_frames_* / yfv2_detect_tiled_* output).
+ * For each frame, in this order:
+ *   1 valid      a row is valid when all six floats are finite and x2 > x1, y2 > y1.  Invalid rows never match, never start a track.
+ *   2 edges      valid row r - live slot s when (class_aware: the two class floats compare equal) and, with v = the IoU in fp32 as
+ *                yfv2_merge_tiles computes it - xx1 = max(x1, x1'), xx2 = min(x2, x2'), w = max(0, xx2 - xx1), h likewise, inter =
+ *                w * h, v = inter / ((area + area') - inter), area = (x2 - x1) * (y2 - y1); every operation a separate fp32 one -
+ *                double(v) > match_thres.  A NaN v gives no edge.
+ *   3 matching   greedy: the edges in the order v descending, then r ascending, then s ascending; an edge is taken if its row and
+ *                its slot are both still free.
+ *   4 matched    the slot's box, conf and cls become the row's; hits += 1, misses = 0, age += 1; track_id[b, r] = id,
+ *                track_hits[b, r] = hits.
+ *   5 unmatched  live slot: misses += 1, age += 1; if misses > max_misses the slot is zeroed and deaths += 1.
+ *   6 births     the valid unmatched rows with conf >= init_conf (fp32), in row order, after the deaths of step 5: the k-th takes
+ *                the k-th lowest free slot (slots freed in step 5 included) with id = issued + 1, issued += 1, hits = 1, misses = 0,
+ *                age = 1, births += 1; track_id / track_hits of the row are the new id and 1.  No free slot: dropped += 1, id 0.
+ *   7 header     frames += 1; live = the number of live slots.  track_id and track_hits are written for every r in [0, R): 0 where
+ *                no track is assigned, 0 beyond n.
+ *   8 fresh      (optional outputs) a row is fresh when track_hits[b, r] == confirm_hits - hits only grows, so each track is fresh
+ *                once.  The fresh rows in row order: fresh_dets[b, j] = the row's six floats untouched, fresh_src[b, j] = r,
+ *                fresh_count[b] their number; rows beyond fresh_count[b] are not written.
+ * No output bit depends on the launch geometry, on the other frames of the call or on the run: slots and compaction come from
+ * ballots and integer prefix sums, and nothing is accumulated in floating point. */
+typedef struct yfv2_track_rule {
+  int32_t max_tracks;        /* M: slots per stream, 1..1024 */
+  double  match_thres;       /* an edge needs double(IoU) > match_thres; finite, >= 0 */
+  int32_t class_aware;       /* != 0: a row matches only a track of an equal class float */
+  float   init_conf;         /* a birth needs conf >= init_conf; not NaN */
+  int32_t max_misses;        /* a track dies at its (max_misses + 1)-th consecutive miss; >= 0 */
+  int32_t confirm_hits;      /* a row is fresh when its track's hits equal this; >= 1 */
+} yfv2_track_rule;
+
+/* int32 words of ONE stream's state: 8 + 10 * max_tracks; YFV2_ERR_ARG (negative) for max_tracks outside 1..1024.  Host only. */
+YFV2_API int64_t yfv2_track_state_words(int32_t max_tracks);
+
+/* The IoU of step 2 for two boxes x1, y1, x2, y2: host only, no handle, like yfv2_crop_rect; it calls the function the kernel
+ * calls.  Returns YFV2_OK and writes *v (which may be NaN), YFV2_ERR_ARG for a NULL pointer. */
+YFV2_API int yfv2_track_iou(const float a[4], const float b[4], float* v);
+
+/* One update of the streams stream_of[0..B) from dets (B, R, 6) / count (B), all device pointers but stream_of.  state: S *
+ * yfv2_track_state_words(M) int32; track_id (B, R); track_hits (B, R) or NULL; fresh_dets (B, R, 6), fresh_src (B, R), fresh_count
+ * (B): all three or none.  Enqueue only: one workgroup per frame, one launch (per 768 frames - stream_of travels in the launch's own
+ * arguments), no host wait, no handle workspace.  Checked before anything is enqueued (YFV2_ERR_ARG with a message, the state
+ * untouched): NULL pointers; B < 1; S < 1; R outside 1..4096; max_tracks outside 1..1024; a stream outside [0, S) or named twice;
+ * match_thres not finite or negative; init_conf NaN; max_misses < 0; confirm_hits < 1; the three fresh outputs not all given or
+ * all NULL. */
+YFV2_API int yfv2_track_update(yfv2_handle h, const float* dets /* (B,R,6) */, const int32_t* count /* (B) */, int32_t R, int32_t B,
+                               const int32_t* stream_of /* HOST, B */, int32_t* state, int32_t S, const yfv2_track_rule* rule,
+                               int32_t* track_id /* (B,R) */, int32_t* track_hits /* (B,R) or NULL */, float* fresh_dets /* (B,R,6) or NULL */,
+                               int32_t* fresh_src, int32_t* fresh_count, void* stream);
+
 /* ---- the ncnn sample's deployment path (sample/ncnn/src/yolo-fastestv2.cpp) ----
  * The reference's only native component post-processes differently from its Python path in every step that decides which boxes
  * come out: no objectness pre-filter (score = cls * obj > thresh only), boxes scaled to the source frame and TRUNCATED TO int

@@ -1,0 +1,147 @@
+#!/usr/bin/env python3
+"""The per-stream IoU tracker (tracking.Tracker, include/yfv2.h yfv2_track_update) against the round trip it replaces and against
+the detect call it follows, in ONE process.
+
+Workload: --streams video streams (default 256), R = 300 rows per frame, M = 256 slots per stream, --frames frames (default 30) of
+seeded boxes that drift a few pixels per frame; each frame a tenth of the objects is not seen and the rows come in a new order.  Two
+runs: every row of the frame live (count = 300, of 333 objects) and a tenth of that (count = 30 of 33, as after NMS on real video).
+  track_update   one call per frame on a fresh tracker, after one whole sequence as a warm-up: device events around every call,
+                 the median / min / max over the frames and the first frame's time (births only)
+  round trip     what a caller does without it: dets and count to the host (which waits for the device) and the numpy model's
+                 update (tests/track_model.py: the edges vectorised, the walk over the edges in Python); wall-clock over the first
+                 --host-frames frames, whose state and outputs are compared with the device's bit for bit
+  detect_frames  the call that produces such a batch: --streams frames of a 1080p / 720p / 480p / 352 mix through Engine.detect_frames
+                 (random weights; the time does not depend on them), device events, median of --iters
+Prints one JSON line and writes it to --json (default profiles/track_probe.json).
+usage: python tools/track_probe.py [--streams 256] [--frames 30] [--host-frames 2] [--iters 20]
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+sys.path.insert(0, os.path.join(REPO, "tests"))
+import yolo_fastestv2_amd as yfv2  # noqa: E402
+
+ANCHORS = [12.64, 19.39, 37.88, 51.48, 55.71, 138.31, 126.91, 78.23, 131.57, 214.55, 279.92, 258.87]  # data/coco.data:17
+SIZES = [(1080, 1920), (720, 1280), (480, 640), (352, 352)]   # (h, w)
+R, M = 300, 256
+
+
+def sequence(rng, S, T, live, seen_n):
+    """T arrays (S, R, 6) and counts (S): `live` objects per stream on a 1920 x 1080 canvas, drifting up to 3 pixels per frame, a
+    random `seen_n` of them in each frame"""
+    pos = rng.uniform(0, [1800, 1000], (S, live, 2))
+    size = rng.uniform(30, 120, (S, live, 2))
+    cls = rng.integers(0, 80, (S, live)).astype(np.float32)
+    out = []
+    for _ in range(T):
+        pos += rng.uniform(-3, 3, pos.shape)
+        dets = np.zeros((S, R, 6), np.float32)
+        count = np.zeros(S, np.int32)
+        for s in range(S):
+            seen = rng.permutation(live)[:seen_n]
+            conf = np.sort(rng.uniform(0.3, 1.0, len(seen)))[::-1]
+            dets[s, :len(seen)] = np.concatenate([pos[s, seen], pos[s, seen] + size[s, seen], conf[:, None], cls[s, seen, None]], axis=1)
+            count[s] = len(seen)
+        out.append((dets, count))
+    return out
+
+
+def spread(ms):
+    return {"median": round(statistics.median(ms), 4), "min": round(min(ms), 4), "max": round(max(ms), 4)}
+
+
+def run(eng, dev, seq, host_frames):
+    import track_model
+    S = seq[0][0].shape[0]
+    rule = dict(max_tracks=M, match_thres=0.3, class_aware=True, init_conf=0.0, max_misses=30, confirm_hits=3)
+    dseq = [(torch.from_numpy(d).to(dev), torch.from_numpy(c).to(dev)) for d, c in seq]
+    out = (torch.empty((S, R), device=dev, dtype=torch.int32), torch.empty((S, R), device=dev, dtype=torch.int32), torch.empty((S, R, 6), device=dev),
+           torch.empty((S, R), device=dev, dtype=torch.int32), torch.empty((S,), device=dev, dtype=torch.int32))
+    warm = yfv2.Tracker(eng, S, **rule)
+    for d, c in dseq:
+        warm.update(d, c, fresh=True, out=out)
+    torch.cuda.synchronize()
+    tr = yfv2.Tracker(eng, S, **rule)
+    ms, fresh = [], 0
+    for d, c in dseq:
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        tr.update(d, c, fresh=True, out=out)
+        e1.record()
+        torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1))
+        fresh += int(out[4].sum())
+    same = bool(torch.equal(tr.state, warm.state))
+    # the round trip on the first frames, compared with a third tracker stepped alongside
+    model, chk = track_model.Model(S, **rule), yfv2.Tracker(eng, S, **rule)
+    host_ms = []
+    for d, c in dseq[:host_frames]:
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        want = model.update(d.cpu().numpy(), c.cpu().numpy())
+        host_ms.append((time.perf_counter() - t0) * 1e3)
+        got = chk.update(d, c, fresh=True, out=out)
+        same = (same and bool(torch.equal(chk.state.cpu(), torch.from_numpy(model.state))) and bool(torch.equal(got[0].cpu(), torch.from_numpy(want["track_id"])))
+                and bool(torch.equal(got[1].cpu(), torch.from_numpy(want["track_hits"]))) and bool(torch.equal(got[4].cpu(), torch.from_numpy(want["fresh_count"]))))
+    head = tr.state[:, :6].sum(0).tolist()
+    return {"rows_per_frame": int(round(float(np.mean([c.mean() for _d, c in seq])))), "track_update_ms": spread(ms), "first_frame_ms": round(ms[0], 4),
+            "round_trip_ms": round(statistics.median(host_ms), 2), "equals_model": same, "fresh_rows": fresh,
+            "issued": head[0], "live": head[1], "deaths": head[4], "dropped": head[5],
+            "speedup": round(statistics.median(host_ms) / statistics.median(ms), 1)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--streams", type=int, default=256)
+    ap.add_argument("--frames", type=int, default=30)
+    ap.add_argument("--host-frames", type=int, default=2)
+    ap.add_argument("--iters", type=int, default=20)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--json", default=os.path.join(REPO, "profiles", "track_probe.json"))
+    args = ap.parse_args()
+
+    dev = torch.device("cuda:0")
+    S = args.streams
+    eng = yfv2.Engine(dev, 352, 352, 80, 3, anchors=ANCHORS, max_batch=S, plan={})
+    eng.load_state_dict(yfv2.random_state_dict(0))
+    rng = np.random.default_rng(args.seed)
+    res = {"tool": "track_probe", "streams": S, "R": R, "M": M, "frames": args.frames, "host_frames": args.host_frames,
+           "full": run(eng, dev, sequence(rng, S, args.frames, 333, 300), args.host_frames),
+           "sparse": run(eng, dev, sequence(rng, S, args.frames, 33, 30), args.host_frames)}
+    # the call that produces such a batch
+    gen = torch.Generator(device=dev).manual_seed(args.seed)
+    order = np.random.default_rng(args.seed).permutation(np.arange(S) % len(SIZES))
+    frames = [torch.randint(0, 256, SIZES[k] + (3,), generator=gen, device=dev, dtype=torch.uint8) for k in order]
+    bufs = eng.new_det_buffers(S)
+    for _ in range(3):
+        eng.detect_frames(frames, 0.3, 0.4, out=bufs, check=False)
+    torch.cuda.synchronize()
+    det_ms = []
+    for _ in range(args.iters):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        eng.detect_frames(frames, 0.3, 0.4, out=bufs, check=False)
+        e1.record()
+        torch.cuda.synchronize()
+        det_ms.append(e0.elapsed_time(e1))
+    res["detect_frames_ms"] = spread(det_ms)
+    for k in ("full", "sparse"):
+        res[k]["fraction_of_detect"] = round(res[k]["track_update_ms"]["median"] / res["detect_frames_ms"]["median"], 3)
+    line = json.dumps(res)
+    print(line)
+    os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
+    with open(args.json, "w") as f:
+        f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()

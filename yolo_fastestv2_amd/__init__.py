@@ -35,6 +35,8 @@ from . import datasets  # noqa: F401
 from .datasets import TrainBatcher, collate_targets, draw_contrast_brightness, read_label_file  # noqa: F401
 from .yuv import YuvFrame  # noqa: F401
 from .tiling import plan_tiles  # noqa: F401
+from . import tracking  # noqa: F401
+from .tracking import Tracker  # noqa: F401
 from .sharded import average_gradients_, detect_sharded, gather_decoded, gather_detections, shard_range  # noqa: F401
 
 

@@ -90,6 +90,12 @@ class CropRule(C.Structure):
                 ("classes", C.POINTER(C.c_int32)), ("n_classes", C.c_int32)]
 
 
+class TrackRule(C.Structure):
+    """yfv2_track_rule (include/yfv2.h): the parameters of the per-stream IoU tracker."""
+    _fields_ = [("max_tracks", C.c_int32), ("match_thres", C.c_double), ("class_aware", C.c_int32), ("init_conf", C.c_float),
+                ("max_misses", C.c_int32), ("confirm_hits", C.c_int32)]
+
+
 class KmeansInfo(C.Structure):
     """yfv2_kmeans_info (include/yfv2.h): what ended yfv2_anchor_kmeans' loop."""
     _fields_ = [("struct_size", C.c_int32), ("iterations", C.c_int32), ("converged", C.c_int32), ("empty_cluster", C.c_int32),
@@ -167,6 +173,10 @@ _PROTOTYPES = {
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "yfv2_crop_detections_yuv": (C.c_int, [C.c_void_p, C.POINTER(FrameYuv), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(CropRule),
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "yfv2_track_state_words": (C.c_int64, [C.c_int32]),
+    "yfv2_track_iou": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "yfv2_track_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_int32,
+                                    C.POINTER(TrackRule), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "yfv2_export_maps": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "yfv2_deploy_post": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
                                    C.c_int32, C.c_void_p]),

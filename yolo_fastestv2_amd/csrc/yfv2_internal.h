@@ -443,6 +443,27 @@ void yfv2_launch_crop_plan_yuv(const CropPlanArgs& a, const ResizeFrameYuv* fram
 // the resize of the live entries of a counted table into crops (cap, H, W, 3): grid cap * H, LDS for a source row of max_w pixels
 void yfv2_launch_resize_crops(const CropFrame* table, int cap, int max_w, unsigned char* crops, int H, int W, hipStream_t s);
 void yfv2_launch_resize_crops_yuv(const CropFrameYuv* table, int cap, int max_w, unsigned char* crops, int H, int W, hipStream_t s);
+// ---- the per-stream IoU tracker (yfv2_track_update; kernel and the IoU's one function: yfv2_track.hip)
+constexpr int TRACK_MAX_R = 4096, TRACK_MAX_M = 1024;
+constexpr int TRACK_HEADER = 8, TRACK_SLOT = 10;     // int32 words of a stream's header and of one slot (include/yfv2.h)
+constexpr int TRACK_CHUNK = 768;                     // frames of one launch: their streams are 3 KB of the launch's arguments
+struct TrackArgs {
+  const float* dets;           // (B, R, 6), offset to the launch's first frame
+  const int32_t* count;        // (B), likewise
+  int R, M;
+  int32_t* state;              // S * (TRACK_HEADER + TRACK_SLOT * M) words
+  double thres;
+  int class_aware;
+  float init_conf;
+  int max_misses, confirm_hits;
+  int32_t* track_id;           // (B, R), offset like dets
+  int32_t* track_hits;         // (B, R) or null
+  float* fresh_dets;           // (B, R, 6) or null; fresh_src (B, R) and fresh_count (B) with it
+  int32_t* fresh_src;
+  int32_t* fresh_count;
+  int32_t stream_of[TRACK_CHUNK];   // workgroup g updates stream stream_of[g]
+};
+void yfv2_launch_track(const TrackArgs& a, int frames, hipStream_t s);   // one workgroup per frame, frames <= TRACK_CHUNK
 // dets columns 0-3 of the first count[b] rows of frame b times frames[b].box_x / box_y (yfv2_post.hip)
 void yfv2_launch_frame_boxes(float* dets, const int32_t* count, const ResizeFrame* frames, int B, hipStream_t s);
 void yfv2_launch_decode(const DecodeArgs& a, hipStream_t s);

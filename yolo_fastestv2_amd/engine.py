@@ -496,6 +496,51 @@ class Engine:
         return self._crop_detections("crop_detections_yuv", self._yuv_table, _lib.lib().yfv2_crop_detections_yuv, frames, dets, count, out_size, pad,
                                      max_per_frame, classes, cap, out)
 
+    # ---- identity across frames: the per-stream IoU tracker (include/yfv2.h yfv2_track_update) -------------------
+    def track_update(self, dets, count, streams, state, max_tracks, match_thres=0.3, class_aware=True, init_conf=0.0, max_misses=30,
+                     confirm_hits=3, fresh=False, out=None):
+        """One update of a tracker's device state from a batch of detection rows (tracking.Tracker owns the state and calls this).
+        dets (B, R, 6) fp32 / count (B) int32 on the device, in detect_frames' / detect_tiled's layout; streams: B distinct stream
+        indices (host ints), frame b belongs to stream streams[b]; state: contiguous int32 (S, 8 + 10 * max_tracks) on the device,
+        all zero = empty, updated in place.  Returns (track_id (B, R), track_hits (B, R)) int32 - 0 where a row has no track - and,
+        with fresh=True, also (fresh_dets (B, R, 6), fresh_src (B, R), fresh_count (B)): the rows whose track reached confirm_hits in
+        this frame, compacted in row order, which is the (dets, count) pair crop_detections takes.  out: the same tuple, preallocated.
+        The rule, bit for bit: include/yfv2.h.  Enqueue only: one launch, no host wait."""
+        if (not torch.is_tensor(dets) or dets.dim() != 3 or dets.shape[2] != 6 or dets.dtype != torch.float32 or dets.device != self.device
+                or not dets.is_contiguous()):
+            raise ValueError("track_update: dets must be contiguous fp32 (B,R,6) on %s" % (self.device,))
+        B, R = int(dets.shape[0]), int(dets.shape[1])
+        if not torch.is_tensor(count) or tuple(count.shape) != (B,) or count.dtype != torch.int32 or count.device != self.device or not count.is_contiguous():
+            raise ValueError("track_update: count must be contiguous int32 (%d,) on %s" % (B, self.device))
+        streams = [int(s) for s in streams]
+        if len(streams) != B:
+            raise ValueError("track_update: %d streams for %d frames" % (len(streams), B))
+        max_tracks = int(max_tracks)
+        if not 1 <= max_tracks <= 1024:
+            raise ValueError("track_update: max_tracks must be in 1..1024")
+        words = 8 + 10 * max_tracks
+        if (not torch.is_tensor(state) or state.dim() != 2 or state.shape[1] != words or state.dtype != torch.int32 or state.device != self.device
+                or not state.is_contiguous()):
+            raise ValueError("track_update: state must be contiguous int32 (S,%d) on %s" % (words, self.device))
+        S = int(state.shape[0])
+        shapes = ((B, R), (B, R)) + (((B, R, 6), (B, R), (B,)) if fresh else ())
+        dtypes = (torch.int32, torch.int32, torch.float32, torch.int32, torch.int32)
+        if out is None:
+            out = tuple(torch.empty(sh, device=self.device, dtype=dt) for sh, dt in zip(shapes, dtypes))
+        else:
+            if len(out) != len(shapes):
+                raise ValueError("track_update: out must hold %d tensors" % len(shapes))
+            for t, sh, dt in zip(out, shapes, dtypes):
+                if not torch.is_tensor(t) or tuple(t.shape) != sh or t.dtype != dt or t.device != self.device or not t.is_contiguous():
+                    raise ValueError("track_update: out must be contiguous tensors of shapes %s on %s" % (shapes, self.device))
+        rule = _lib.TrackRule()
+        rule.max_tracks, rule.match_thres, rule.class_aware = max_tracks, float(match_thres), 1 if class_aware else 0
+        rule.init_conf, rule.max_misses, rule.confirm_hits = float(init_conf), int(max_misses), int(confirm_hits)
+        arr = (C.c_int32 * max(B, 1))(*streams)
+        ptrs = [_ptr(t) for t in out] + [None] * (5 - len(out))
+        check(_lib.lib().yfv2_track_update(self._h, _ptr(dets), _ptr(count), R, B, arr, _ptr(state), S, C.byref(rule), *ptrs, _stream(self.device)), self._h)
+        return out
+
     # ---- the ncnn sample's deployment path (include/yfv2.h yfv2_export_maps / yfv2_deploy_post; DESIGN.md 4.14) ------------------
     def map_shapes(self, B):
         C5 = 5 * self.anchor_num + self.classes

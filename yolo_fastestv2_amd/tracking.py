@@ -1,0 +1,57 @@
+"""Identity across frames: a per-stream IoU tracker whose state lives on the device (include/yfv2.h yfv2_track_update; DESIGN.md
+4.18).  `Tracker` owns the state tensor and the rule's parameters; every update is one enqueue-only launch, and with fresh=True it
+hands back exactly the rows whose track was confirmed in this frame, in the (dets, count) layout Engine.crop_detections takes:
+
+    tr = Tracker(engine, streams=256)
+    dets, idx, count = engine.detect_frames(frames, 0.3, 0.4)
+    track_id, track_hits, fresh_dets, fresh_src, fresh_count = tr.update(dets, count, fresh=True)
+    crops, *_ = engine.crop_detections(frames, fresh_dets, fresh_count, (128, 128))      # once per object, not once per frame
+"""
+import torch
+
+HEADER_WORDS, SLOT_WORDS = 8, 10
+HEADER_FIELDS = ("issued", "live", "frames", "births", "deaths", "dropped")
+
+
+class Tracker:
+    def __init__(self, engine, streams, max_tracks=64, match_thres=0.3, class_aware=True, init_conf=0.0, max_misses=30, confirm_hits=3):
+        """engine: the Engine whose device and stream the updates run on; streams: S, the number of video streams; max_tracks:
+        slots per stream (1..1024).  An edge between a row and a track needs IoU > match_thres (and equal classes if class_aware);
+        an unmatched row with conf >= init_conf starts a track; a track dies at its (max_misses + 1)-th consecutive miss; a row is
+        fresh in the frame in which its track's hits reach confirm_hits.  The rule, bit for bit: include/yfv2.h."""
+        self.engine = engine
+        self.streams, self.max_tracks = int(streams), int(max_tracks)
+        if self.streams < 1 or not 1 <= self.max_tracks <= 1024:
+            raise ValueError("Tracker: streams must be >= 1 and max_tracks in 1..1024")
+        self.rule = dict(match_thres=float(match_thres), class_aware=bool(class_aware), init_conf=float(init_conf), max_misses=int(max_misses),
+                         confirm_hits=int(confirm_hits))
+        self.state = torch.zeros((self.streams, HEADER_WORDS + SLOT_WORDS * self.max_tracks), dtype=torch.int32, device=engine.device)
+
+    def update(self, dets, count, streams=None, fresh=False, out=None):
+        """dets (B, R, 6) fp32 / count (B) int32 on the device; streams: the stream of each frame, B distinct indices (None: frame b
+        is stream b).  Returns (track_id, track_hits) and, with fresh=True, (.., fresh_dets, fresh_src, fresh_count)."""
+        if streams is None:
+            streams = range(int(dets.shape[0]))
+        return self.engine.track_update(dets, count, streams, self.state, self.max_tracks, fresh=fresh, out=out, **self.rule)
+
+    def _slots(self, stream):
+        return self.state[int(stream), HEADER_WORDS:].view(self.max_tracks, SLOT_WORDS)
+
+    def tracks(self, stream):
+        """The live tracks of a stream, in slot order: a dict of tensors box (n, 4), conf (n), cls (n) fp32 and id, hits, misses, age
+        (n) int32, gathered from the state (this reads the device: it waits for the updates enqueued so far)."""
+        slots = self._slots(stream)
+        live = slots[slots[:, 6] != 0]
+        fl = live[:, :6].contiguous().view(torch.float32)
+        return {"box": fl[:, :4], "conf": fl[:, 4], "cls": fl[:, 5], "id": live[:, 6], "hits": live[:, 7], "misses": live[:, 8], "age": live[:, 9]}
+
+    def header(self, stream):
+        """The stream's counters as a dict of ints: issued, live, frames, births, deaths, dropped (waits for the device)."""
+        return dict(zip(HEADER_FIELDS, (int(v) for v in self.state[int(stream), :len(HEADER_FIELDS)].tolist())))
+
+    def reset(self, stream=None):
+        """Forget every track of one stream, or of all of them (ids start again at 1)."""
+        if stream is None:
+            self.state.zero_()
+        else:
+            self.state[int(stream)].zero_()
