@@ -409,7 +409,8 @@ YFV2_API int yfv2_crop_detections_yuv(yfv2_handle h, const yfv2_frame_yuv* frame
  * The inputs of the entry points above are video: many streams, one frame of each per batch.  A tracker gives every detection an
  * identity that lasts across frames, so that a second stage runs once per object: its state lives on the device, one launch updates
  * it from a batch of detection rows, and the launch can emit - compacted, in the (dets, count) layout yfv2_crop_detections_* takes -
- * exactly the rows whose track was confirmed in this frame.  No motion model: an unmatched track keeps its last box.
+ * exactly the rows whose track was confirmed in this frame.  This form has no motion model: an unmatched track keeps its last box
+ * (yfv2_track_update_motion, below, is the form with one).
  * THE RULE, bit for bit (tests/track_model.py restates it; the one function of the IoU is behind yfv2_track_iou).
  * A tracker has S streams, each a table of M = max_tracks slots.
  *   state        one caller-owned device buffer of S * (8 + 10 * M) int32 words; all zero = empty.  Per stream 8 header words - ids
@@ -465,6 +466,65 @@ YFV2_API int yfv2_track_update(yfv2_handle h, const float* dets /* (B,R,6) */, c
                                const int32_t* stream_of /* HOST, B */, int32_t* state, int32_t S, const yfv2_track_rule* rule,
                                int32_t* track_id /* (B,R) */, int32_t* track_hits /* (B,R) or NULL */, float* fresh_dets /* (B,R,6) or NULL */,
                                int32_t* fresh_src, int32_t* fresh_count, void* stream);
+
+/* ---- identity across frames with a motion model: a constant-velocity Kalman filter per track ----
+ * The rule above matches a row against a track's LAST box, so an object hidden for a few frames comes back under a new id (and is
+ * fresh a second time).  The motion form is opt-in and changes nothing above: the same kernel, the same walk, a state of its own
+ * layout.  Each track carries four independent one-dimensional constant-velocity Kalman filters, one per coordinate cx, cy, w, h -
+ * exact, not an approximation: with diagonal process and measurement noise and the transition ByteTrack and BoT-SORT use, the 8 x 8
+ * covariance stays block-diagonal in (position, velocity) pairs - so a coordinate is five fp32 numbers x, v, p00, p01, p11.
+ * THE RULE, bit for bit (tests/track_motion_model.py restates it; the one function of the filter is behind yfv2_track_filter_step
+ * and yfv2_track_birth).  Every fp32 operation is one separately rounded operation in the order written; divisions round to
+ * nearest.  sp, sv, sm = std_pos, std_vel, std_meas.  The scale l is the track's w for cx and w, its h for cy and h: predict uses
+ * the posterior w.x / h.x from before the predict, update the predicted w.x / h.x.
+ *   predict      tp = sp * l; tv = sv * l; x' = x + v; p00' = (((p00 + p01) + p01) + p11) + tp * tp; p01' = p01 + p11;
+ *                p11' = p11 + tv * tv; v is unchanged.
+ *   update (z)   tm = sm * l'; s = p00' + tm * tm; k0 = p00' / s; k1 = p01' / s; y = z - x'; x = x' + k0 * y; v = v + k1 * y;
+ *                p00 = p00' - k0 * p00'; p01 = p01' - k0 * p01'; p11 = p11' - k1 * p01'.
+ *   birth        x = z, v = 0, p01 = 0, p00 = t * t with t = (2.0f * sp) * l, p11 = t * t with t = (10.0f * sv) * l; l from the row's
+ *                own w / h.
+ *   measurement  of a row: cx = (x1 + x2) * 0.5f, w = x2 - x1, and likewise for y.
+ *   corners      of a filter state: x1 = cx - w * 0.5f, x2 = cx + w * 0.5f, and likewise for y.
+ *   NaN          which NaN an invalid operation makes depends on the processor; every NaN among the five results of a predict or an
+ *                update, or among four corners, is replaced by the quiet NaN 0x7fc00000 before it is stored, used or written out.
+ *   state        S * (8 + 32 * M) int32 words; the header as above; a slot is 32 words: 0..9 as above, 10..29 the four filters in the
+ *                order cx, cy, w, h, each x, v, p00, p01, p11 (fp32 bits), 30..31 zero.  All zero = empty.  One update is one time
+ *                step; a stream absent from a call is not advanced.
+ * Per frame the order above changes in these places only:
+ *   0 predict    (new) every live slot is predicted and its 20 filter words are replaced by the predicted ones.  A slot is BLIND for
+ *                this frame if any of its 20 words is not finite or its predicted w or h is not > 0: it has no edges, so it misses.
+ *   1 valid      a row is also invalid if any of its four measurement values is not finite.
+ *   2 edges      v is the IoU between the row and the slot's PREDICTED CORNERS, not its last box.
+ *   4 matched    the filter is updated with the row's measurement; words 0..5 become the row; track_box[b, r] = the posterior corners.
+ *   5 unmatched  the filter words stay as predicted (the track coasts), words 0..5 keep the last matched row; a dead slot zeroes all
+ *                its words.
+ *   6 births     as above, plus the filter initialised from the row; track_box[b, r] = the corners of the born state.
+ *   7 header     track_box (optional) is zero where no track is assigned and zero beyond n.
+ * Defaults (documented, not applied by the C ABI): std_pos = 1/20, std_vel = 1/160, std_meas = 1/20. */
+typedef struct yfv2_track_motion {
+  float std_pos, std_vel, std_meas;   /* all three finite and > 0 */
+} yfv2_track_motion;
+
+/* int32 words of ONE stream's state in the motion form: 8 + 32 * max_tracks; errors as yfv2_track_state_words.  Host only. */
+YFV2_API int64_t yfv2_track_motion_state_words(int32_t max_tracks);
+
+/* One filter, host only, no handle, like yfv2_track_iou: it calls the function the kernel calls.  out = in predicted one step with
+ * scale_predict and then, if z is not NULL, updated with *z and scale_update.  YFV2_ERR_ARG for a NULL in / out / motion or a
+ * motion value that is not finite and > 0. */
+YFV2_API int yfv2_track_filter_step(const float in[5], const float* z /* NULL: predict only */, float scale_predict, float scale_update,
+                                    const yfv2_track_motion* motion, float out[5]);
+
+/* The 20 filter words of a track born from a row's box x1, y1, x2, y2.  Host only; errors likewise. */
+YFV2_API int yfv2_track_birth(const float row_box[4], const yfv2_track_motion* motion, float out[20]);
+
+/* yfv2_track_update in the motion form: state is S * yfv2_track_motion_state_words(M) int32; track_box (B, R, 4) fp32 or NULL.
+ * Every check of yfv2_track_update, plus motion not NULL and its three values finite and > 0.  Enqueue only: one workgroup per
+ * frame, one launch per 768 frames, no host wait, no handle workspace. */
+YFV2_API int yfv2_track_update_motion(yfv2_handle h, const float* dets /* (B,R,6) */, const int32_t* count /* (B) */, int32_t R, int32_t B,
+                                      const int32_t* stream_of /* HOST, B */, int32_t* state, int32_t S, const yfv2_track_rule* rule,
+                                      const yfv2_track_motion* motion, int32_t* track_id /* (B,R) */, int32_t* track_hits /* (B,R) or NULL */,
+                                      float* track_box /* (B,R,4) or NULL */, float* fresh_dets /* (B,R,6) or NULL */, int32_t* fresh_src,
+                                      int32_t* fresh_count, void* stream);
 
 /* ---- the ncnn sample's deployment path (sample/ncnn/src/yolo-fastestv2.cpp) ----
  * The reference's only native component post-processes differently from its Python path in every step that decides which boxes

@@ -13,7 +13,13 @@ runs: every row of the frame live (count = 300, of 333 objects) and a tenth of t
   detect_frames  the call that produces such a batch: --streams frames of a 1080p / 720p / 480p / 352 mix through Engine.detect_frames
                  (random weights; the time does not depend on them), device events, median of --iters
 Prints one JSON line and writes it to --json (default profiles/track_probe.json).
-usage: python tools/track_probe.py [--streams 256] [--frames 30] [--host-frames 2] [--iters 20]
+
+--motion: the motion form (Tracker(motion=True), yfv2_track_update_motion) NEXT TO the plain one on the same two sequences in this
+process: --reps passes over the sequence, the two forms alternating, a fresh tracker each pass, device events around every call;
+per form the median / min / max over all frames of all passes, and motion / plain of the medians.  The motion form's state and
+outputs of the first --host-frames frames are compared with tests/track_motion_model.py bit for bit.  Default --json:
+profiles/track_motion_probe.json.
+usage: python tools/track_probe.py [--streams 256] [--frames 30] [--host-frames 2] [--iters 20] [--motion [--reps 5]]
 """
 import argparse
 import json
@@ -99,6 +105,45 @@ def run(eng, dev, seq, host_frames):
             "speedup": round(statistics.median(host_ms) / statistics.median(ms), 1)}
 
 
+def run_motion(eng, dev, seq, host_frames, reps):
+    import track_motion_model
+    S = seq[0][0].shape[0]
+    rule = dict(max_tracks=M, match_thres=0.3, class_aware=True, init_conf=0.0, max_misses=30, confirm_hits=3)
+    dseq = [(torch.from_numpy(d).to(dev), torch.from_numpy(c).to(dev)) for d, c in seq]
+    outs = {False: (torch.empty((S, R), device=dev, dtype=torch.int32), torch.empty((S, R), device=dev, dtype=torch.int32), torch.empty((S, R, 6), device=dev),
+                    torch.empty((S, R), device=dev, dtype=torch.int32), torch.empty((S,), device=dev, dtype=torch.int32))}
+    outs[True] = outs[False] + (torch.empty((S, R, 4), device=dev),)
+    ms, states = {False: [], True: []}, {}
+    for rep in range(reps + 1):                             # pass 0 is the warm-up of both forms
+        for motion in (False, True):
+            tr = yfv2.Tracker(eng, S, motion=motion or None, **rule)
+            for d, c in dseq:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                tr.update(d, c, fresh=True, box=motion, out=outs[motion])
+                e1.record()
+                torch.cuda.synchronize()
+                if rep:
+                    ms[motion].append(e0.elapsed_time(e1))
+            same = motion not in states or bool(torch.equal(states[motion], tr.state))
+            states[motion] = tr.state.clone()
+            assert same, "two passes over one sequence left different states"
+    # the motion form against its model on the first frames
+    model, chk = track_motion_model.Model(S, **rule), yfv2.Tracker(eng, S, motion=True, **rule)
+    same = True
+    for d, c in dseq[:host_frames]:
+        want = model.update(d.cpu().numpy(), c.cpu().numpy())
+        got = chk.update(d, c, fresh=True, box=True, out=outs[True])
+        same = (same and bool(torch.equal(chk.state.cpu(), torch.from_numpy(model.state))) and bool(torch.equal(got[0].cpu(), torch.from_numpy(want["track_id"])))
+                and bool(torch.equal(got[5].cpu().view(torch.int32), torch.from_numpy(want["track_box"]).view(torch.int32)))
+                and bool(torch.equal(got[4].cpu(), torch.from_numpy(want["fresh_count"]))))
+    heads = {k: states[k][:, :6].sum(0).tolist() for k in states}
+    return {"rows_per_frame": int(round(float(np.mean([c.mean() for _d, c in seq])))), "reps": reps,
+            "track_update_ms": spread(ms[False]), "track_update_motion_ms": spread(ms[True]),
+            "ratio": round(statistics.median(ms[True]) / statistics.median(ms[False]), 3), "motion_equals_model": same,
+            "issued": {"plain": heads[False][0], "motion": heads[True][0]}, "live": {"plain": heads[False][1], "motion": heads[True][1]}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", type=int, default=256)
@@ -106,14 +151,28 @@ def main():
     ap.add_argument("--host-frames", type=int, default=2)
     ap.add_argument("--iters", type=int, default=20)
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--json", default=os.path.join(REPO, "profiles", "track_probe.json"))
+    ap.add_argument("--motion", action="store_true")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--json", default=None)
     args = ap.parse_args()
+    if args.json is None:
+        args.json = os.path.join(REPO, "profiles", "track_motion_probe.json" if args.motion else "track_probe.json")
 
     dev = torch.device("cuda:0")
     S = args.streams
     eng = yfv2.Engine(dev, 352, 352, 80, 3, anchors=ANCHORS, max_batch=S, plan={})
     eng.load_state_dict(yfv2.random_state_dict(0))
     rng = np.random.default_rng(args.seed)
+    if args.motion:
+        res = {"tool": "track_probe --motion", "streams": S, "R": R, "M": M, "frames": args.frames, "host_frames": args.host_frames,
+               "full": run_motion(eng, dev, sequence(rng, S, args.frames, 333, 300), args.host_frames, args.reps),
+               "sparse": run_motion(eng, dev, sequence(rng, S, args.frames, 33, 30), args.host_frames, args.reps)}
+        line = json.dumps(res)
+        print(line)
+        os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
+        with open(args.json, "w") as f:
+            f.write(line + "\n")
+        return
     res = {"tool": "track_probe", "streams": S, "R": R, "M": M, "frames": args.frames, "host_frames": args.host_frames,
            "full": run(eng, dev, sequence(rng, S, args.frames, 333, 300), args.host_frames),
            "sparse": run(eng, dev, sequence(rng, S, args.frames, 33, 30), args.host_frames)}

@@ -96,6 +96,11 @@ class TrackRule(C.Structure):
                 ("max_misses", C.c_int32), ("confirm_hits", C.c_int32)]
 
 
+class TrackMotion(C.Structure):
+    """yfv2_track_motion (include/yfv2.h): the noise scales of the tracker's constant-velocity filters."""
+    _fields_ = [("std_pos", C.c_float), ("std_vel", C.c_float), ("std_meas", C.c_float)]
+
+
 class KmeansInfo(C.Structure):
     """yfv2_kmeans_info (include/yfv2.h): what ended yfv2_anchor_kmeans' loop."""
     _fields_ = [("struct_size", C.c_int32), ("iterations", C.c_int32), ("converged", C.c_int32), ("empty_cluster", C.c_int32),
@@ -177,6 +182,12 @@ _PROTOTYPES = {
     "yfv2_track_iou": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "yfv2_track_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_int32,
                                     C.POINTER(TrackRule), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "yfv2_track_motion_state_words": (C.c_int64, [C.c_int32]),
+    "yfv2_track_filter_step": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_float, C.c_float, C.POINTER(TrackMotion), C.POINTER(C.c_float)]),
+    "yfv2_track_birth": (C.c_int, [C.POINTER(C.c_float), C.POINTER(TrackMotion), C.POINTER(C.c_float)]),
+    "yfv2_track_update_motion": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_int32,
+                                           C.POINTER(TrackRule), C.POINTER(TrackMotion), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]),
     "yfv2_export_maps": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "yfv2_deploy_post": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
                                    C.c_int32, C.c_void_p]),

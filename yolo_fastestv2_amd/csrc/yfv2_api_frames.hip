@@ -312,7 +312,8 @@ int yfv2_crop_detections_yuv(yfv2_handle h, const yfv2_frame_yuv* frames, int32_
   return crop_detections<YuvFrames>(h, "yfv2_crop_detections_yuv", frames, B, dets, count, R, rule, crops, crop_src, crop_rect, crop_offset, crop_skipped, cap, stream);
 }
 
-// ---- the per-stream IoU tracker (kernel, and yfv2_track_iou beside the IoU's one function: yfv2_track.hip) -------
+// ---- the per-stream IoU tracker (its motion form 4.19; kernel, and yfv2_track_iou / yfv2_track_filter_step beside
+// the one function each of them exposes: yfv2_track.hip) -------
 // Every check first; then one launch per TRACK_CHUNK frames (the streams of a launch travel in its arguments: no table, no copy,
 // no workspace).  The frames of a call are distinct streams, so the launches share nothing.
 int64_t yfv2_track_state_words(int32_t max_tracks) {
@@ -320,12 +321,17 @@ int64_t yfv2_track_state_words(int32_t max_tracks) {
   return (int64_t)TRACK_HEADER + (int64_t)TRACK_SLOT * max_tracks;
 }
 
-int yfv2_track_update(yfv2_handle h, const float* dets, const int32_t* count, int32_t R, int32_t B, const int32_t* stream_of, int32_t* state, int32_t S,
-                      const yfv2_track_rule* rule, int32_t* track_id, int32_t* track_hits, float* fresh_dets, int32_t* fresh_src, int32_t* fresh_count,
-                      void* stream) {
-  const std::string w_ = "yfv2_track_update";
+int64_t yfv2_track_motion_state_words(int32_t max_tracks) {
+  if (max_tracks < 1 || max_tracks > TRACK_MAX_M) return fail(nullptr, YFV2_ERR_ARG, "yfv2_track_motion_state_words: max_tracks must be in 1.." + std::to_string(TRACK_MAX_M));
+  return (int64_t)TRACK_HEADER + (int64_t)TRACK_SLOT_MOTION * max_tracks;
+}
+
+// both forms: motion == nullptr is the plain one (with_motion tells a missing argument from the plain form)
+static int track_update(const std::string& w_, bool with_motion, yfv2_handle h, const float* dets, const int32_t* count, int32_t R, int32_t B,
+                        const int32_t* stream_of, int32_t* state, int32_t S, const yfv2_track_rule* rule, const yfv2_track_motion* motion,
+                        int32_t* track_id, int32_t* track_hits, float* track_box, float* fresh_dets, int32_t* fresh_src, int32_t* fresh_count, void* stream) {
   if (!h) return fail(nullptr, YFV2_ERR_ARG, "null handle");
-  if (!dets || !count || !stream_of || !state || !rule || !track_id) return fail(h, YFV2_ERR_ARG, w_ + ": null pointer");
+  if (!dets || !count || !stream_of || !state || !rule || !track_id || (with_motion && !motion)) return fail(h, YFV2_ERR_ARG, w_ + ": null pointer");
   const int given = (fresh_dets != nullptr) + (fresh_src != nullptr) + (fresh_count != nullptr);
   if (given != 0 && given != 3) return fail(h, YFV2_ERR_ARG, w_ + ": fresh_dets, fresh_src and fresh_count must all be given or all be NULL");
   if (B < 1) return fail(h, YFV2_ERR_ARG, w_ + ": B < 1");
@@ -337,6 +343,9 @@ int yfv2_track_update(yfv2_handle h, const float* dets, const int32_t* count, in
   if (std::isnan(q.init_conf)) return fail(h, YFV2_ERR_ARG, w_ + ": init_conf is not a number");
   if (q.max_misses < 0) return fail(h, YFV2_ERR_ARG, w_ + ": max_misses must be >= 0");
   if (q.confirm_hits < 1) return fail(h, YFV2_ERR_ARG, w_ + ": confirm_hits must be >= 1");
+  if (with_motion)
+    for (const float v : {motion->std_pos, motion->std_vel, motion->std_meas})
+      if (!std::isfinite(v) || !(v > 0.0f)) return fail(h, YFV2_ERR_ARG, w_ + ": std_pos, std_vel and std_meas must be finite and > 0");
   std::vector<int32_t> sorted(stream_of, stream_of + B);
   std::sort(sorted.begin(), sorted.end());
   if (sorted.front() < 0 || sorted.back() >= S)
@@ -345,20 +354,37 @@ int yfv2_track_update(yfv2_handle h, const float* dets, const int32_t* count, in
     if (sorted[b] == sorted[b - 1]) return fail(h, YFV2_ERR_ARG, w_ + ": stream " + std::to_string(sorted[b]) + " named twice (one frame per stream and call)");
   DeviceGuard guard(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  TrackArgs a{};
+  TrackMotionArgs a{};                     // the plain launch takes its TrackArgs part
   a.R = R; a.M = q.max_tracks; a.state = state; a.thres = q.match_thres; a.class_aware = q.class_aware; a.init_conf = q.init_conf;
   a.max_misses = q.max_misses; a.confirm_hits = q.confirm_hits;
+  if (with_motion) a.motion = TrackMotion{motion->std_pos, motion->std_vel, motion->std_meas};
   for (int32_t b0 = 0; b0 < B; b0 += TRACK_CHUNK) {
     const int frames = std::min<int32_t>(TRACK_CHUNK, B - b0);
     const size_t row0 = (size_t)b0 * R;
     a.dets = dets + row0 * 6; a.count = count + b0; a.track_id = track_id + row0; a.track_hits = track_hits ? track_hits + row0 : nullptr;
     a.fresh_dets = fresh_dets ? fresh_dets + row0 * 6 : nullptr; a.fresh_src = fresh_src ? fresh_src + row0 : nullptr;
     a.fresh_count = fresh_count ? fresh_count + b0 : nullptr;
+    a.track_box = track_box ? track_box + row0 * 4 : nullptr;
     std::copy(stream_of + b0, stream_of + b0 + frames, a.stream_of);
-    yfv2_launch_track(a, frames, s);
+    if (with_motion) yfv2_launch_track_motion(a, frames, s);
+    else yfv2_launch_track(a, frames, s);
   }
   HIP_TRY(h, hipGetLastError());
   return YFV2_OK;
+}
+
+int yfv2_track_update(yfv2_handle h, const float* dets, const int32_t* count, int32_t R, int32_t B, const int32_t* stream_of, int32_t* state, int32_t S,
+                      const yfv2_track_rule* rule, int32_t* track_id, int32_t* track_hits, float* fresh_dets, int32_t* fresh_src, int32_t* fresh_count,
+                      void* stream) {
+  return track_update("yfv2_track_update", false, h, dets, count, R, B, stream_of, state, S, rule, nullptr, track_id, track_hits, nullptr, fresh_dets,
+                      fresh_src, fresh_count, stream);
+}
+
+int yfv2_track_update_motion(yfv2_handle h, const float* dets, const int32_t* count, int32_t R, int32_t B, const int32_t* stream_of, int32_t* state,
+                             int32_t S, const yfv2_track_rule* rule, const yfv2_track_motion* motion, int32_t* track_id, int32_t* track_hits,
+                             float* track_box, float* fresh_dets, int32_t* fresh_src, int32_t* fresh_count, void* stream) {
+  return track_update("yfv2_track_update_motion", true, h, dets, count, R, B, stream_of, state, S, rule, motion, track_id, track_hits, track_box, fresh_dets,
+                      fresh_src, fresh_count, stream);
 }
 
 int yfv2_resize_u8(yfv2_handle h, const uint8_t* src, int32_t B, int32_t src_h, int32_t src_w, uint8_t* dst, void* stream) {

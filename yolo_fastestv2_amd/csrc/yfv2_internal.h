@@ -447,6 +447,9 @@ void yfv2_launch_resize_crops_yuv(const CropFrameYuv* table, int cap, int max_w,
 constexpr int TRACK_MAX_R = 4096, TRACK_MAX_M = 1024;
 constexpr int TRACK_HEADER = 8, TRACK_SLOT = 10;     // int32 words of a stream's header and of one slot (include/yfv2.h)
 constexpr int TRACK_CHUNK = 768;                     // frames of one launch: their streams are 3 KB of the launch's arguments
+// the motion form (yfv2_track_update_motion): a slot is 32 words, words 10..29 the filters of cx, cy, w, h (5 each)
+constexpr int TRACK_SLOT_MOTION = 32, TRACK_FILTER = 10;
+struct TrackMotion { float std_pos, std_vel, std_meas; };
 struct TrackArgs {
   const float* dets;           // (B, R, 6), offset to the launch's first frame
   const int32_t* count;        // (B), likewise
@@ -463,7 +466,12 @@ struct TrackArgs {
   int32_t* fresh_count;
   int32_t stream_of[TRACK_CHUNK];   // workgroup g updates stream stream_of[g]
 };
+struct TrackMotionArgs : TrackArgs {   // the plain form's arguments stay what they were: its kernel is the one it was
+  TrackMotion motion;
+  float* track_box;            // (B, R, 4) or null, offset like dets
+};
 void yfv2_launch_track(const TrackArgs& a, int frames, hipStream_t s);   // one workgroup per frame, frames <= TRACK_CHUNK
+void yfv2_launch_track_motion(const TrackMotionArgs& a, int frames, hipStream_t s);   // ... of track_kernel<true>; a.state in 32-word slots
 // dets columns 0-3 of the first count[b] rows of frame b times frames[b].box_x / box_y (yfv2_post.hip)
 void yfv2_launch_frame_boxes(float* dets, const int32_t* count, const ResizeFrame* frames, int B, hipStream_t s);
 void yfv2_launch_decode(const DecodeArgs& a, hipStream_t s);

@@ -20,7 +20,17 @@
 // edge; v = -1: matched), the table as arrays (40 B per slot) and the slot keys (8 B; high word -1: dead or matched, low word the
 // row).  Slots are read as wave-uniform broadcasts, the way tile_merge_kernel reads its kept set; conf and cls of a row come from
 // global memory where they are needed.
+//
+// The motion form (yfv2_track_update_motion) is the SAME kernel, track_kernel<true>: a slot is 32 words, its last 20
+// the four constant-velocity filters of cx, cy, w, h.  They stay in global memory: the thread that owns a slot predicts them where
+// the plain form reads the slot's box (and writes them back), sbox holds the PREDICTED corners, and the words are touched again only
+// by the owner when the slot is matched (update) or dies (zeroed), and by the row's thread when a row is born into it.  A blind slot
+// (a predicted word not finite, predicted w or h not > 0) gets NaN corners: track_iou then gives NaN, which is no edge - no flag,
+// no LDS.  Words 0..3 (the last matched row) are written where they change, since sbox no longer holds them.  The filter is ONE
+// __host__ __device__ function (track_filter_step: the kernel, yfv2_track_filter_step and yfv2_track_birth call it).
 #include <algorithm>
+#include <cmath>
+#include <type_traits>
 
 #include "../../include/yfv2.h"
 #include "yfv2_device.h"
@@ -47,6 +57,64 @@ __host__ __device__ inline float track_iou(float ax1, float ay1, float ax2, floa
 #endif
 }
 
+// ---- the motion form's arithmetic: one constant-velocity Kalman filter per coordinate, x, v and the 2 x 2 covariance p00, p01, p11
+struct TrackFilter { float x, v, p00, p01, p11; };
+
+__host__ __device__ inline float track_div(float a, float b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __fdiv_rn(a, b);
+#else
+  return a / b;
+#endif
+}
+// Which NaN an invalid operation makes differs between processors (the sign bit); what the rule stores or writes out is ONE quiet NaN.
+__host__ __device__ inline float track_canon(float v) { return v != v ? __builtin_bit_cast(float, 0x7fc00000) : v; }
+// one time step (predict, scale lp) and / or one measurement z (update, scale lu) of one filter: include/yfv2.h, operation by operation
+__host__ __device__ __forceinline__ TrackFilter track_filter_step(TrackFilter f, bool predict, bool update, float z, float lp, float lu, const TrackMotion& m) {
+#pragma clang fp contract(off)
+  if (predict) {
+    const float tp = m.std_pos * lp, tv = m.std_vel * lp;
+    f.x = f.x + f.v;
+    f.p00 = (((f.p00 + f.p01) + f.p01) + f.p11) + tp * tp;
+    f.p01 = f.p01 + f.p11;
+    f.p11 = f.p11 + tv * tv;
+  }
+  if (update) {
+    const float tm = m.std_meas * lu;
+    const float s = f.p00 + tm * tm;
+    const float k0 = track_div(f.p00, s), k1 = track_div(f.p01, s), y = z - f.x;
+    const float p00 = f.p00, p01 = f.p01;
+    f.x = f.x + k0 * y;
+    f.v = f.v + k1 * y;
+    f.p00 = p00 - k0 * p00;
+    f.p01 = p01 - k0 * p01;
+    f.p11 = f.p11 - k1 * p01;
+  }
+  f.x = track_canon(f.x); f.v = track_canon(f.v); f.p00 = track_canon(f.p00); f.p01 = track_canon(f.p01); f.p11 = track_canon(f.p11);
+  return f;
+}
+// a row's measurement cx, cy, w, h; a filter state's corners
+__host__ __device__ __forceinline__ void track_measure(float x1, float y1, float x2, float y2, float z[4]) {
+#pragma clang fp contract(off)
+  z[0] = (x1 + x2) * 0.5f; z[1] = (y1 + y2) * 0.5f; z[2] = x2 - x1; z[3] = y2 - y1;
+}
+__host__ __device__ __forceinline__ void track_corners(float cx, float cy, float w, float h, float c[4]) {
+#pragma clang fp contract(off)
+  const float hw = w * 0.5f, hh = h * 0.5f;
+  c[0] = track_canon(cx - hw); c[1] = track_canon(cy - hh); c[2] = track_canon(cx + hw); c[3] = track_canon(cy + hh);
+}
+// the filters of a track born from a row: cx and w scale with the row's w, cy and h with its h
+__host__ __device__ __forceinline__ void track_birth(const float z[4], const TrackMotion& m, TrackFilter f[4]) {
+#pragma clang fp contract(off)
+  const float sp2 = 2.0f * m.std_pos, sv10 = 10.0f * m.std_vel;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    const float l = z[2 + (c & 1)], tp = sp2 * l, tv = sv10 * l;
+    f[c].x = z[c]; f[c].v = 0.0f; f[c].p00 = tp * tp; f[c].p01 = 0.0f; f[c].p11 = tv * tv;
+  }
+}
+__host__ __device__ __forceinline__ bool track_finite(float v) { return (v < 0.0f ? -v : v) <= 3.402823466e38f; }   // NaN or an infinity fails
+
 namespace {
 
 constexpr int TK_MAX_THREADS = 1024;
@@ -69,7 +137,75 @@ __device__ __forceinline__ int block_rank(bool f, int* s_cnt, int& total) {
   return before + __popcll(m & ((1ull << lane) - 1ull));
 }
 
-__global__ __launch_bounds__(TK_MAX_THREADS) void track_kernel(TrackArgs a) {
+// ---- the motion form's slot words 10..29, by the thread that owns them (w: the slot's first word)
+__device__ __forceinline__ void filters_load(const int32_t* w, TrackFilter f[4]) {
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    const int32_t* q = w + TRACK_FILTER + 5 * c;
+    f[c].x = i2f(q[0]); f[c].v = i2f(q[1]); f[c].p00 = i2f(q[2]); f[c].p01 = i2f(q[3]); f[c].p11 = i2f(q[4]);
+  }
+}
+__device__ __forceinline__ void filters_store(int32_t* w, const TrackFilter f[4]) {
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    int32_t* q = w + TRACK_FILTER + 5 * c;
+    q[0] = f2i(f[c].x); q[1] = f2i(f[c].v); q[2] = f2i(f[c].p00); q[3] = f2i(f[c].p01); q[4] = f2i(f[c].p11);
+  }
+}
+__device__ __forceinline__ float4 filters_corners(const TrackFilter f[4]) {
+  float c[4];
+  track_corners(f[0].x, f[1].x, f[2].x, f[3].x, c);
+  return make_float4(c[0], c[1], c[2], c[3]);
+}
+__device__ __forceinline__ void box_store(int32_t* w, float4 g) { w[0] = f2i(g.x); w[1] = f2i(g.y); w[2] = f2i(g.z); w[3] = f2i(g.w); }
+// step 0: a live slot's filters one frame on, written back; -> the predicted corners, NaN for a blind slot (no IoU with it is an edge)
+__device__ __forceinline__ float4 slot_predict(int32_t* w, const TrackMotion& m) {
+  if (w[6] == 0) return make_float4(0.f, 0.f, 0.f, 0.f);
+  TrackFilter f[4];
+  filters_load(w, f);
+  const float lw = f[2].x, lh = f[3].x;
+  bool seen = true;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    f[c] = track_filter_step(f[c], true, false, 0.0f, (c & 1) ? lh : lw, 0.0f, m);
+    seen = seen && track_finite(f[c].x) && track_finite(f[c].v) && track_finite(f[c].p00) && track_finite(f[c].p01) && track_finite(f[c].p11);
+  }
+  filters_store(w, f);
+  seen = seen && f[2].x > 0.0f && f[3].x > 0.0f;
+  const float nan = __builtin_nanf("");
+  return seen ? filters_corners(f) : make_float4(nan, nan, nan, nan);
+}
+// step 4: a matched slot's predicted filters take the row's measurement; -> the posterior corners
+__device__ __forceinline__ float4 slot_update(int32_t* w, float4 g, const TrackMotion& m) {
+  TrackFilter f[4];
+  filters_load(w, f);
+  float z[4];
+  track_measure(g.x, g.y, g.z, g.w, z);
+  const float lw = f[2].x, lh = f[3].x;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) f[c] = track_filter_step(f[c], false, true, z[c], 0.0f, (c & 1) ? lh : lw, m);
+  filters_store(w, f);
+  return filters_corners(f);
+}
+// step 6: a row born into a free slot; -> the born state's corners
+__device__ __forceinline__ float4 slot_birth(int32_t* w, float4 g, const TrackMotion& m) {
+  TrackFilter f[4];
+  float z[4];
+  track_measure(g.x, g.y, g.z, g.w, z);
+  track_birth(z, m, f);
+  filters_store(w, f);
+  return filters_corners(f);
+}
+__device__ __forceinline__ void row_box_store(float* track_box, size_t row, float4 c) {
+  if (!track_box) return;
+  float* o = track_box + row * 4;
+  o[0] = c.x; o[1] = c.y; o[2] = c.z; o[3] = c.w;
+}
+
+// MOTION: the slots are TRACK_SLOT_MOTION words and carry filters (above); everything else is the one kernel
+template <bool MOTION>
+__global__ __launch_bounds__(TK_MAX_THREADS) void track_kernel(std::conditional_t<MOTION, TrackMotionArgs, TrackArgs> a) {
+  constexpr int SLOT = MOTION ? TRACK_SLOT_MOTION : TRACK_SLOT;
   extern __shared__ __attribute__((aligned(16))) unsigned char tk_lds[];
   __shared__ int s_cnt[TK_MAX_THREADS / 64];
   __shared__ int s_deaths;
@@ -86,7 +222,7 @@ __global__ __launch_bounds__(TK_MAX_THREADS) void track_kernel(TrackArgs a) {
   int* const smiss = shits + M;
   int* const sage = smiss + M;
 
-  int32_t* const head = a.state + (size_t)a.stream_of[b] * (size_t)(TRACK_HEADER + TRACK_SLOT * M);
+  int32_t* const head = a.state + (size_t)a.stream_of[b] * (size_t)(TRACK_HEADER + SLOT * M);
   int32_t* const slots = head + TRACK_HEADER;
   const int n = min(max(a.count[b], 0), R);
   const float* const rows = a.dets + (size_t)b * R * 6;
@@ -94,8 +230,9 @@ __global__ __launch_bounds__(TK_MAX_THREADS) void track_kernel(TrackArgs a) {
 
   if (tid == 0) s_deaths = 0;
   for (int s = tid; s < M; s += nt) {
-    const int32_t* w = slots + TRACK_SLOT * s;
-    sbox[s] = make_float4(i2f(w[0]), i2f(w[1]), i2f(w[2]), i2f(w[3]));
+    int32_t* w = slots + SLOT * s;
+    if constexpr (MOTION) sbox[s] = slot_predict(w, a.motion);
+    else sbox[s] = make_float4(i2f(w[0]), i2f(w[1]), i2f(w[2]), i2f(w[3]));
     sconf[s] = i2f(w[4]); scls[s] = i2f(w[5]);
     sid[s] = w[6]; shits[s] = w[7]; smiss[s] = w[8]; sage[s] = w[9];
     skey[s] = w[6] == 0 ? ~0ull : 0ull;
@@ -106,6 +243,11 @@ __global__ __launch_bounds__(TK_MAX_THREADS) void track_kernel(TrackArgs a) {
     bool valid = x2 > x1 && y2 > y1;
 #pragma unroll
     for (int i = 0; i < 6; ++i) valid = valid && fabsf(row[i]) <= 3.402823466e38f;     // NaN or an infinity fails
+    if constexpr (MOTION) {                                  // ... and so does a measurement that overflows
+      float z[4];
+      track_measure(x1, y1, x2, y2, z);
+      valid = valid && track_finite(z[0]) && track_finite(z[1]) && track_finite(z[2]) && track_finite(z[3]);
+    }
     rbox[r] = make_float4(x1, y1, x2, y2);
     rst[r] = valid ? make_int2(-1, 1) : make_int2(-2, 0);   // v word: 0 = done, unmatched; 1 = to be scanned (no IoU's bits)
   }
@@ -165,7 +307,13 @@ __global__ __launch_bounds__(TK_MAX_THREADS) void track_kernel(TrackArgs a) {
       const unsigned long long k = skey[s];
       if ((int)(k >> 32) == TK_TAKEN) {
         const int r = (int)(unsigned)k;
-        sbox[s] = rbox[r];
+        if constexpr (MOTION) {
+          int32_t* w = slots + SLOT * s;
+          box_store(w, rbox[r]);
+          row_box_store(a.track_box, (size_t)b * R + r, slot_update(w, rbox[r], a.motion));
+        } else {
+          sbox[s] = rbox[r];
+        }
         sconf[s] = rows[6 * r + 4]; scls[s] = rows[6 * r + 5];
         shits[s] += 1; smiss[s] = 0; sage[s] += 1;
       } else {
@@ -173,7 +321,14 @@ __global__ __launch_bounds__(TK_MAX_THREADS) void track_kernel(TrackArgs a) {
         smiss[s] = m; sage[s] += 1;
         if (m > a.max_misses) {
           died = true;
-          sbox[s] = make_float4(0.f, 0.f, 0.f, 0.f);
+          if constexpr (MOTION) {
+            int32_t* w = slots + SLOT * s;
+            box_store(w, make_float4(0.f, 0.f, 0.f, 0.f));
+#pragma unroll
+            for (int i = TRACK_FILTER; i < TRACK_FILTER + 20; ++i) w[i] = 0;
+          } else {
+            sbox[s] = make_float4(0.f, 0.f, 0.f, 0.f);
+          }
           sconf[s] = 0.f; scls[s] = 0.f; sid[s] = 0; shits[s] = 0; smiss[s] = 0; sage[s] = 0;
         }
       }
@@ -209,7 +364,13 @@ __global__ __launch_bounds__(TK_MAX_THREADS) void track_kernel(TrackArgs a) {
     const int k = nb + block_rank(want, s_cnt, total);
     if (want && k < nfree) {
       const int s = freel[k];
-      sbox[s] = rbox[r];
+      if constexpr (MOTION) {
+        int32_t* w = slots + SLOT * s;
+        box_store(w, rbox[r]);
+        row_box_store(a.track_box, (size_t)b * R + r, slot_birth(w, rbox[r], a.motion));
+      } else {
+        sbox[s] = rbox[r];
+      }
       sconf[s] = conf; scls[s] = rows[6 * r + 5];
       sid[s] = issued + 1 + k; shits[s] = 1; smiss[s] = 0; sage[s] = 1;
       rst[r] = make_int2(s, TK_TAKEN);
@@ -232,6 +393,8 @@ __global__ __launch_bounds__(TK_MAX_THREADS) void track_kernel(TrackArgs a) {
     if (r < R) {
       a.track_id[(size_t)b * R + r] = id;
       if (a.track_hits) a.track_hits[(size_t)b * R + r] = hits;
+      if constexpr (MOTION)
+        if (id == 0) row_box_store(a.track_box, (size_t)b * R + r, make_float4(0.f, 0.f, 0.f, 0.f));   // an assigned row's was written with its filter
     }
     if (emit) {
       const bool fresh = hits == a.confirm_hits;             // hits >= 1 on an assigned row, 0 elsewhere; confirm_hits >= 1
@@ -250,9 +413,11 @@ __global__ __launch_bounds__(TK_MAX_THREADS) void track_kernel(TrackArgs a) {
 
   // ---- the table and the header go back
   for (int s = tid; s < M; s += nt) {
-    int32_t* w = slots + TRACK_SLOT * s;
-    const float4 t = sbox[s];
-    w[0] = f2i(t.x); w[1] = f2i(t.y); w[2] = f2i(t.z); w[3] = f2i(t.w);
+    int32_t* w = slots + SLOT * s;
+    if constexpr (!MOTION) {
+      const float4 t = sbox[s];
+      w[0] = f2i(t.x); w[1] = f2i(t.y); w[2] = f2i(t.z); w[3] = f2i(t.w);
+    }
     w[4] = f2i(sconf[s]); w[5] = f2i(scls[s]);
     w[6] = sid[s]; w[7] = shits[s]; w[8] = smiss[s]; w[9] = sage[s];
   }
@@ -269,14 +434,46 @@ __global__ __launch_bounds__(TK_MAX_THREADS) void track_kernel(TrackArgs a) {
 
 }  // namespace
 
-void yfv2_launch_track(const TrackArgs& a, int frames, hipStream_t s) {
+template <bool MOTION>
+static void launch_track(const std::conditional_t<MOTION, TrackMotionArgs, TrackArgs>& a, int frames, hipStream_t s) {
   const int threads = std::min(TK_MAX_THREADS, std::max(64, (a.R + 63) / 64 * 64));
   const size_t lds = (size_t)24 * a.R + (size_t)48 * a.M;
-  YFV2_LAUNCH_LDS(yfv2_device(), track_kernel, 24 * TRACK_MAX_R + 48 * TRACK_MAX_M, dim3((unsigned)frames), dim3((unsigned)threads), lds, s, a);
+  YFV2_LAUNCH_LDS(yfv2_device(), track_kernel<MOTION>, 24 * TRACK_MAX_R + 48 * TRACK_MAX_M, dim3((unsigned)frames), dim3((unsigned)threads), lds, s, a);
 }
+void yfv2_launch_track(const TrackArgs& a, int frames, hipStream_t s) { launch_track<false>(a, frames, s); }
+void yfv2_launch_track_motion(const TrackMotionArgs& a,int frames, hipStream_t s) { launch_track<true>(a, frames, s); }
 
 extern "C" int yfv2_track_iou(const float a[4], const float b[4], float* v) {
   if (!a || !b || !v) return yfv2_ctx_fail(nullptr, YFV2_ERR_ARG, "yfv2_track_iou: null pointer");
   *v = track_iou(a[0], a[1], a[2], a[3], track_area(a[0], a[1], a[2], a[3]), b[0], b[1], b[2], b[3], track_area(b[0], b[1], b[2], b[3]));
+  return YFV2_OK;
+}
+
+// ---- the motion form's arithmetic for the host (tests pin it to the model without a device)
+static bool motion_ok(const yfv2_track_motion* m) {
+  return m && std::isfinite(m->std_pos) && m->std_pos > 0.f && std::isfinite(m->std_vel) && m->std_vel > 0.f && std::isfinite(m->std_meas) && m->std_meas > 0.f;
+}
+
+extern "C" int yfv2_track_filter_step(const float in[5], const float* z, float scale_predict, float scale_update, const yfv2_track_motion* motion, float out[5]) {
+  if (!in || !out || !motion) return yfv2_ctx_fail(nullptr, YFV2_ERR_ARG, "yfv2_track_filter_step: null pointer");
+  if (!motion_ok(motion)) return yfv2_ctx_fail(nullptr, YFV2_ERR_ARG, "yfv2_track_filter_step: std_pos, std_vel and std_meas must be finite and > 0");
+  const TrackMotion m{motion->std_pos, motion->std_vel, motion->std_meas};
+  const TrackFilter f = track_filter_step(TrackFilter{in[0], in[1], in[2], in[3], in[4]}, true, z != nullptr, z ? *z : 0.0f, scale_predict, scale_update, m);
+  out[0] = f.x; out[1] = f.v; out[2] = f.p00; out[3] = f.p01; out[4] = f.p11;
+  return YFV2_OK;
+}
+
+extern "C" int yfv2_track_birth(const float row_box[4], const yfv2_track_motion* motion, float out[20]) {
+  if (!row_box || !out || !motion) return yfv2_ctx_fail(nullptr, YFV2_ERR_ARG, "yfv2_track_birth: null pointer");
+  if (!motion_ok(motion)) return yfv2_ctx_fail(nullptr, YFV2_ERR_ARG, "yfv2_track_birth: std_pos, std_vel and std_meas must be finite and > 0");
+  const TrackMotion m{motion->std_pos, motion->std_vel, motion->std_meas};
+  float z[4];
+  TrackFilter f[4];
+  track_measure(row_box[0], row_box[1], row_box[2], row_box[3], z);
+  track_birth(z, m, f);
+  for (int c = 0; c < 4; ++c) {
+    float* o = out + 5 * c;
+    o[0] = f[c].x; o[1] = f[c].v; o[2] = f[c].p00; o[3] = f[c].p01; o[4] = f[c].p11;
+  }
   return YFV2_OK;
 }

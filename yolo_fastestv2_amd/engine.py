@@ -506,39 +506,63 @@ class Engine:
         with fresh=True, also (fresh_dets (B, R, 6), fresh_src (B, R), fresh_count (B)): the rows whose track reached confirm_hits in
         this frame, compacted in row order, which is the (dets, count) pair crop_detections takes.  out: the same tuple, preallocated.
         The rule, bit for bit: include/yfv2.h.  Enqueue only: one launch, no host wait."""
+        return self._track_update("track_update", None, False, dets, count, streams, state, max_tracks, match_thres, class_aware, init_conf, max_misses,
+                                  confirm_hits, fresh, out)
+
+    def track_update_motion(self, dets, count, streams, state, max_tracks, match_thres=0.3, class_aware=True, init_conf=0.0, max_misses=30,
+                            confirm_hits=3, std_pos=1.0 / 20, std_vel=1.0 / 160, std_meas=1.0 / 20, fresh=False, box=False, out=None):
+        """track_update with a motion model (include/yfv2.h yfv2_track_update_motion): every track carries a
+        constant-velocity Kalman filter per coordinate cx, cy, w, h, a row is matched against the box the filter PREDICTS, and a track
+        that is not seen coasts.  state: contiguous int32 (S, 8 + 32 * max_tracks).  std_pos, std_vel, std_meas: the filter's noise
+        scales, relative to the track's width / height (finite, > 0).  Returns what track_update returns and, with box=True, after
+        it track_box (B, R, 4) fp32: the filtered corners of each row's track, zero where a row has none."""
+        motion = dict(std_pos=std_pos, std_vel=std_vel, std_meas=std_meas)
+        return self._track_update("track_update_motion", motion, box, dets, count, streams, state, max_tracks, match_thres, class_aware, init_conf,
+                                  max_misses, confirm_hits, fresh, out)
+
+    def _track_update(self, name, motion, box, dets, count, streams, state, max_tracks, match_thres, class_aware, init_conf, max_misses, confirm_hits,
+                      fresh, out):
+        """the checks and the call of both forms; motion: None or the three stds"""
         if (not torch.is_tensor(dets) or dets.dim() != 3 or dets.shape[2] != 6 or dets.dtype != torch.float32 or dets.device != self.device
                 or not dets.is_contiguous()):
-            raise ValueError("track_update: dets must be contiguous fp32 (B,R,6) on %s" % (self.device,))
+            raise ValueError(name + ": dets must be contiguous fp32 (B,R,6) on %s" % (self.device,))
         B, R = int(dets.shape[0]), int(dets.shape[1])
         if not torch.is_tensor(count) or tuple(count.shape) != (B,) or count.dtype != torch.int32 or count.device != self.device or not count.is_contiguous():
-            raise ValueError("track_update: count must be contiguous int32 (%d,) on %s" % (B, self.device))
+            raise ValueError(name + ": count must be contiguous int32 (%d,) on %s" % (B, self.device))
         streams = [int(s) for s in streams]
         if len(streams) != B:
-            raise ValueError("track_update: %d streams for %d frames" % (len(streams), B))
+            raise ValueError(name + ": %d streams for %d frames" % (len(streams), B))
         max_tracks = int(max_tracks)
         if not 1 <= max_tracks <= 1024:
-            raise ValueError("track_update: max_tracks must be in 1..1024")
-        words = 8 + 10 * max_tracks
+            raise ValueError(name + ": max_tracks must be in 1..1024")
+        words = 8 + (10 if motion is None else 32) * max_tracks
         if (not torch.is_tensor(state) or state.dim() != 2 or state.shape[1] != words or state.dtype != torch.int32 or state.device != self.device
                 or not state.is_contiguous()):
-            raise ValueError("track_update: state must be contiguous int32 (S,%d) on %s" % (words, self.device))
+            raise ValueError(name + ": state must be contiguous int32 (S,%d) on %s" % (words, self.device))
         S = int(state.shape[0])
-        shapes = ((B, R), (B, R)) + (((B, R, 6), (B, R), (B,)) if fresh else ())
-        dtypes = (torch.int32, torch.int32, torch.float32, torch.int32, torch.int32)
+        shapes = ((B, R), (B, R)) + (((B, R, 6), (B, R), (B,)) if fresh else ()) + (((B, R, 4),) if box else ())
+        dtypes = (torch.int32, torch.int32) + ((torch.float32, torch.int32, torch.int32) if fresh else ()) + ((torch.float32,) if box else ())
         if out is None:
             out = tuple(torch.empty(sh, device=self.device, dtype=dt) for sh, dt in zip(shapes, dtypes))
         else:
             if len(out) != len(shapes):
-                raise ValueError("track_update: out must hold %d tensors" % len(shapes))
+                raise ValueError(name + ": out must hold %d tensors" % len(shapes))
             for t, sh, dt in zip(out, shapes, dtypes):
                 if not torch.is_tensor(t) or tuple(t.shape) != sh or t.dtype != dt or t.device != self.device or not t.is_contiguous():
-                    raise ValueError("track_update: out must be contiguous tensors of shapes %s on %s" % (shapes, self.device))
+                    raise ValueError(name + ": out must be contiguous tensors of shapes %s on %s" % (shapes, self.device))
         rule = _lib.TrackRule()
         rule.max_tracks, rule.match_thres, rule.class_aware = max_tracks, float(match_thres), 1 if class_aware else 0
         rule.init_conf, rule.max_misses, rule.confirm_hits = float(init_conf), int(max_misses), int(confirm_hits)
         arr = (C.c_int32 * max(B, 1))(*streams)
-        ptrs = [_ptr(t) for t in out] + [None] * (5 - len(out))
-        check(_lib.lib().yfv2_track_update(self._h, _ptr(dets), _ptr(count), R, B, arr, _ptr(state), S, C.byref(rule), *ptrs, _stream(self.device)), self._h)
+        tid, hits = _ptr(out[0]), _ptr(out[1])
+        fr = [_ptr(t) for t in out[2:5]] if fresh else [None] * 3
+        if motion is None:
+            check(_lib.lib().yfv2_track_update(self._h, _ptr(dets), _ptr(count), R, B, arr, _ptr(state), S, C.byref(rule), tid, hits, *fr, _stream(self.device)),
+                  self._h)
+        else:
+            mo = _lib.TrackMotion(float(motion["std_pos"]), float(motion["std_vel"]), float(motion["std_meas"]))
+            check(_lib.lib().yfv2_track_update_motion(self._h, _ptr(dets), _ptr(count), R, B, arr, _ptr(state), S, C.byref(rule), C.byref(mo), tid, hits,
+                                                      _ptr(out[-1]) if box else None, *fr, _stream(self.device)), self._h)
         return out
 
     # ---- the ncnn sample's deployment path (include/yfv2.h yfv2_export_maps / yfv2_deploy_post; DESIGN.md 4.14) ------------------

@@ -6,44 +6,72 @@ hands back exactly the rows whose track was confirmed in this frame, in the (det
     dets, idx, count = engine.detect_frames(frames, 0.3, 0.4)
     track_id, track_hits, fresh_dets, fresh_src, fresh_count = tr.update(dets, count, fresh=True)
     crops, *_ = engine.crop_detections(frames, fresh_dets, fresh_count, (128, 128))      # once per object, not once per frame
+
+With motion=True (or a dict of std_pos, std_vel, std_meas) every track carries a constant-velocity Kalman filter per coordinate
+(yfv2_track_update_motion): rows are matched against the box the filter predicts, so an object hidden for a few
+frames keeps its id.
 """
 import torch
 
 HEADER_WORDS, SLOT_WORDS = 8, 10
+MOTION_SLOT_WORDS, FILTER_WORD = 32, 10          # the motion form's slot; its filters: words 10..29, cx, cy, w, h as x, v, p00, p01, p11
+MOTION_DEFAULTS = dict(std_pos=1.0 / 20, std_vel=1.0 / 160, std_meas=1.0 / 20)
 HEADER_FIELDS = ("issued", "live", "frames", "births", "deaths", "dropped")
 
 
 class Tracker:
-    def __init__(self, engine, streams, max_tracks=64, match_thres=0.3, class_aware=True, init_conf=0.0, max_misses=30, confirm_hits=3):
+    def __init__(self, engine, streams, max_tracks=64, match_thres=0.3, class_aware=True, init_conf=0.0, max_misses=30, confirm_hits=3, motion=None):
         """engine: the Engine whose device and stream the updates run on; streams: S, the number of video streams; max_tracks:
         slots per stream (1..1024).  An edge between a row and a track needs IoU > match_thres (and equal classes if class_aware);
         an unmatched row with conf >= init_conf starts a track; a track dies at its (max_misses + 1)-th consecutive miss; a row is
-        fresh in the frame in which its track's hits reach confirm_hits.  The rule, bit for bit: include/yfv2.h."""
+        fresh in the frame in which its track's hits reach confirm_hits.  motion: None - the IoU is taken with the track's last box;
+        True or a dict with any of std_pos, std_vel, std_meas - with the box its filter predicts.  The rule, bit for bit:
+        include/yfv2.h."""
         self.engine = engine
         self.streams, self.max_tracks = int(streams), int(max_tracks)
         if self.streams < 1 or not 1 <= self.max_tracks <= 1024:
             raise ValueError("Tracker: streams must be >= 1 and max_tracks in 1..1024")
         self.rule = dict(match_thres=float(match_thres), class_aware=bool(class_aware), init_conf=float(init_conf), max_misses=int(max_misses),
                          confirm_hits=int(confirm_hits))
-        self.state = torch.zeros((self.streams, HEADER_WORDS + SLOT_WORDS * self.max_tracks), dtype=torch.int32, device=engine.device)
+        if motion is None or motion is False:
+            self.motion = None
+        else:
+            given = {} if motion is True else dict(motion)
+            if set(given) - set(MOTION_DEFAULTS):
+                raise ValueError("Tracker: motion takes std_pos, std_vel and std_meas, not %s" % sorted(set(given) - set(MOTION_DEFAULTS)))
+            self.motion = {k: float(given.get(k, v)) for k, v in MOTION_DEFAULTS.items()}
+        self.slot_words = SLOT_WORDS if self.motion is None else MOTION_SLOT_WORDS
+        self.state = torch.zeros((self.streams, HEADER_WORDS + self.slot_words * self.max_tracks), dtype=torch.int32, device=engine.device)
 
-    def update(self, dets, count, streams=None, fresh=False, out=None):
+    def update(self, dets, count, streams=None, fresh=False, out=None, box=False):
         """dets (B, R, 6) fp32 / count (B) int32 on the device; streams: the stream of each frame, B distinct indices (None: frame b
-        is stream b).  Returns (track_id, track_hits) and, with fresh=True, (.., fresh_dets, fresh_src, fresh_count)."""
+        is stream b).  Returns (track_id, track_hits) and, with fresh=True, (.., fresh_dets, fresh_src, fresh_count); with box=True
+        (the motion form only) track_box (B, R, 4), the filtered corners of each row's track, comes last."""
         if streams is None:
             streams = range(int(dets.shape[0]))
-        return self.engine.track_update(dets, count, streams, self.state, self.max_tracks, fresh=fresh, out=out, **self.rule)
+        if self.motion is None:
+            if box:
+                raise ValueError("Tracker.update: box=True needs a tracker with a motion model")
+            return self.engine.track_update(dets, count, streams, self.state, self.max_tracks, fresh=fresh, out=out, **self.rule)
+        return self.engine.track_update_motion(dets, count, streams, self.state, self.max_tracks, fresh=fresh, box=box, out=out, **self.rule, **self.motion)
 
     def _slots(self, stream):
-        return self.state[int(stream), HEADER_WORDS:].view(self.max_tracks, SLOT_WORDS)
+        return self.state[int(stream), HEADER_WORDS:].view(self.max_tracks, self.slot_words)
 
     def tracks(self, stream):
         """The live tracks of a stream, in slot order: a dict of tensors box (n, 4), conf (n), cls (n) fp32 and id, hits, misses, age
-        (n) int32, gathered from the state (this reads the device: it waits for the updates enqueued so far)."""
+        (n) int32, gathered from the state (this reads the device: it waits for the updates enqueued so far).  With a motion model
+        also pred (n, 4), the corners of the current filter state, and vel (n, 4), the velocities of cx, cy, w, h per update."""
         slots = self._slots(stream)
         live = slots[slots[:, 6] != 0]
         fl = live[:, :6].contiguous().view(torch.float32)
-        return {"box": fl[:, :4], "conf": fl[:, 4], "cls": fl[:, 5], "id": live[:, 6], "hits": live[:, 7], "misses": live[:, 8], "age": live[:, 9]}
+        out = {"box": fl[:, :4], "conf": fl[:, 4], "cls": fl[:, 5], "id": live[:, 6], "hits": live[:, 7], "misses": live[:, 8], "age": live[:, 9]}
+        if self.motion is not None:
+            f = live[:, FILTER_WORD:FILTER_WORD + 20].contiguous().view(torch.float32).view(-1, 4, 5)
+            x, half = f[:, :, 0], f[:, 2:, 0] * 0.5
+            out["pred"] = torch.cat([x[:, :2] - half, x[:, :2] + half], dim=1)
+            out["vel"] = f[:, :, 1].contiguous()
+        return out
 
     def header(self, stream):
         """The stream's counters as a dict of ints: issued, live, frames, births, deaths, dropped (waits for the device)."""
