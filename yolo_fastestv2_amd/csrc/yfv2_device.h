@@ -53,6 +53,14 @@ template <int KA>
 __device__ __forceinline__ void quad_fmac1(float& s, float ta, float v) {
   asm("s_nop 1\n\tv_fmac_f32_dpp %0, %1, %2 " YFV2_QP(3) : "+v"(s) : "v"(ta), "v"(v), "n"(KA));
 }
+// s = ta*v0; q = tb*v1; s += tc*v1   (the FIRST vertical tap row of a stride-2 window: two v_mul_f32_dpp and one v_fmac_f32_dpp, the
+// same three operations as quad_mul, quad_mul, quad_fmac1.  As compiler code the second product's tap broadcast can end up in another
+// basic block than its multiply, where it stays a v_mov 0 + v_mov_dpp + v_mul: three instructions for one.)
+template <int KA, int KB, int KC>
+__device__ __forceinline__ void quad_mul2_fmac1(float& s, float& q, float ta, float tb, float tc, float v0, float v1) {
+  asm("s_nop 1\n\tv_mul_f32_dpp %0, %2, %5 " YFV2_QP(7) "v_mul_f32_dpp %1, %3, %6 " YFV2_QP(8) "v_fmac_f32_dpp %0, %4, %6 " YFV2_QP(9)
+      : "=&v"(s), "=&v"(q) : "v"(ta), "v"(tb), "v"(tc), "v"(v0), "v"(v1), "n"(KA), "n"(KB), "n"(KC));
+}
 // s += ta*v0; q += tb*v1; s += tc*v1   (one vertical tap row of a stride-2 window: dx = 1, 0, 2)
 template <int KA, int KB, int KC>
 __device__ __forceinline__ void quad_fmac3(float& s, float& q, float ta, float tb, float tc, float v0, float v1) {

@@ -114,11 +114,13 @@ __global__ __launch_bounds__(64, 3) void s1h_kernel(S1PxArgs a) {
   for (int c = 0; c < 8; ++c) { tA[c] = 0.f; tB[c] = 0.f; tC[c] = 0.f; }
   load_row(y0 - 1, cur);
 
-  // step j: pw1 of row r = y0-1+j into tn; for j >= 2 the block's output row r-1 from the t rows (tp2, tp1, tn)
-  auto step = [&](int j, const float (&tp2)[8], const float (&tp1)[8], float (&tn)[8]) {
+  // step j: pw1 of row r = y0-1+j into tn; for j >= 2 (OUT) the block's output row r-1 from the t rows (tp2, tp1, tn).  Steps 0 and 1
+  // only fill the t rows: row r-1 is no output row of the band yet, so its depthwise, pw2, ReLU and stores are not issued at all.
+  auto step = [&](auto outc, int j, const float (&tp2)[8], const float (&tp1)[8], float (&tn)[8]) {
+    constexpr bool OUT = decltype(outc)::value;
     const int r = y0 - 1 + j;
     // last step's outputs go out first, then this step's prefetch (one in-order vmcnt for loads and stores)
-    {
+    if constexpr (OUT) {
       const bool pok = pend_row >= 0;
 #pragma unroll
       for (int k = 0; k < 4; ++k)
@@ -138,6 +140,11 @@ __global__ __launch_bounds__(64, 3) void s1h_kernel(S1PxArgs a) {
     const float lim = (xok && r >= 0 && r < H) ? __builtin_inff() : 0.f;
 #pragma unroll
     for (int c = 0; c < 8; ++c) tn[c] = __builtin_amdgcn_fmed3f(acc[c >> 2][c & 3], 0.f, lim);   // ReLU, and 0 outside the image
+    if constexpr (!OUT) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) cur[k] = nxt[k];
+      return;
+    }
 
     // depthwise 3x3 (taps carry BN scale, pw1's 2^-(sw1+4) and pw2's 2^4; its BN shift sits in pw2's bias): vertical taps
     // are per-lane FMAs over the three t rows, the dx = 0 / dx = 2 column sums move one lane right / left
@@ -161,16 +168,20 @@ __global__ __launch_bounds__(64, 3) void s1h_kernel(S1PxArgs a) {
       pend[k][0] = __builtin_fmaxf(acc[k >> 1][2 * (k & 1)], 0.f) * unscale2;
       pend[k][1] = __builtin_fmaxf(acc[k >> 1][2 * (k & 1) + 1], 0.f) * unscale2;
     }
-    pend_row = (j >= 2 && r - 1 < y1) ? r - 1 : -1;
+    pend_row = r - 1 < y1 ? r - 1 : -1;
 #pragma unroll
     for (int k = 0; k < 4; ++k) cur[k] = nxt[k];
   };
 
-  const int nsteps = R + 2;
-  for (int j = 0; j < nsteps; j += 3) {
-    step(j, tB, tC, tA);
-    if (j + 1 < nsteps) step(j + 1, tC, tA, tB);
-    if (j + 2 < nsteps) step(j + 2, tA, tB, tC);
+  const int nsteps = R + 2;                        // (R >= 1: at least one output step)
+  constexpr std::false_type fill;
+  constexpr std::true_type out;
+  step(fill, 0, tB, tC, tA);
+  step(fill, 1, tC, tA, tB);
+  for (int j = 2; j < nsteps; j += 3) {
+    step(out, j, tA, tB, tC);
+    if (j + 1 < nsteps) step(out, j + 1, tB, tC, tA);
+    if (j + 2 < nsteps) step(out, j + 2, tC, tA, tB);
   }
   {
     const bool pok = pend_row >= 0;
@@ -516,7 +527,11 @@ __global__ __launch_bounds__(256, 2) void front2_kernel(FrontArgs fa) {
   const int orowb = OW * 8;
   // ---- the stem's state (stem_h3_kernel): filter [tile 2][term 2][64 lanes][4 dwords], shift x 2^(sw+8) [32], 2^-(sw+8)
   const float* cst = fa.img_stem + 2 * 2 * 64 * 4 + (U8 ? 36 : 0);
-  const float sunscale = cst[32];
+  // The stem's unscale and the stride-2 block's 2^4 pre-scale (s2h_kernel's columns(): X * 16) as ONE factor.  16 is a power of two, so
+  // relu(m) * (sunscale * 16) has the bits of (relu(m) * sunscale) * 16 wherever relu(m) * sunscale is a normal number; the only
+  // possible difference is a stem activation below 2^-126, which the two-step form rounds as a subnormal before scaling it up.
+  // 0 in the lanes right of the map: the product is then the +0 the block expects there (relu(m) is finite), no select needed.
+  const float xscale = xok ? cst[32] * 16.0f : 0.f;
   const int rowb = U8 ? W * 3 : W * 4;
   // fp32: lane groups 0..2 = input channel g, columns 8 ox .. 8 ox + 7; uint8: every lane group loads the same 24 bytes (columns 8 ox .. + 7, three channels each)
   const int chan_off = U8 ? (xok ? 24 * ox : OOB) : ((xok && g < 3) ? g * H * rowb + 8 * ox * 4 : OOB);
@@ -545,14 +560,14 @@ __global__ __launch_bounds__(256, 2) void front2_kernel(FrontArgs fa) {
 #pragma unroll
     for (int i = 2 * hf; i < 2 * hf + 2; ++i) {
       const int row = min(4 * r + i, hlast);
-      load_ab(chan_off != OOB ? chan_off + row * rowb : OOB, s.a[i], s.b[i]);
+      load_ab(chan_off + row * rowb, s.a[i], s.b[i]);   // (row * rowb < 2^31: an OOB chan_off stays beyond the buffer's records, the lane reads zeros)
     }
   };
   auto issue = [&](int r, InSet& s) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int row = min(4 * r + i, hlast);          // (a row past the image: a re-read that stays in range, never used)
-      load_ab(chan_off != OOB ? chan_off + row * rowb : OOB, s.a[i], s.b[i]);
+      load_ab(chan_off + row * rowb, s.a[i], s.b[i]);
     }
   };
   // one conv row of both pooled columns from the carried rows (cA, cB) and the fresh rows r1 (2c), r2 (2c + 1) -> horizontally
@@ -623,7 +638,7 @@ __global__ __launch_bounds__(256, 2) void front2_kernel(FrontArgs fa) {
   };
   Row16 cA, cB;
   f32x4 upA[2], upB[2];
-  // pooled row from its input set -> X[2 t + c] as s2h_kernel's load_row delivers it
+  // pooled row from its input set -> X[2 t + c] as s2h_kernel's load_row delivers it, times the block's 2^4 (xscale)
   auto pooled = [&](InSet& s, f32x4 (&X)[4], int rnext) {
     f32x4 h0A[2], h0B[2], h1A[2], h1B[2];
     conv_row2(cA, cB, s.a[0], s.a[1], s.b[0], s.b[1], h0A, h0B);
@@ -634,23 +649,26 @@ __global__ __launch_bounds__(256, 2) void front2_kernel(FrontArgs fa) {
     for (int t = 0; t < 2; ++t) {
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
+        // the ROUNDED product is the block's input: it must not be contracted into the split's v - fl32(h1) behind it (the uint8 unscale is
+        // no power of two; before the fold the exact x 16 stood between the two and was what got contracted)
+#pragma clang fp contract(off)
         const float mA = __builtin_fmaxf(__builtin_fmaxf(upA[t][e], h0A[t][e]), h1A[t][e]);
         const float mB = __builtin_fmaxf(__builtin_fmaxf(upB[t][e], h0B[t][e]), h1B[t][e]);
-        X[2 * t][e] = __builtin_fmaxf(mA, 0.f) * sunscale;
-        X[2 * t + 1][e] = __builtin_fmaxf(mB, 0.f) * sunscale;
+        X[2 * t][e] = __builtin_fmaxf(mA, 0.f) * xscale;
+        X[2 * t + 1][e] = __builtin_fmaxf(mB, 0.f) * xscale;
       }
       upA[t] = h1A[t]; upB[t] = h1B[t];
     }
-    if (g >= 2 || !xok) { X[2] = (f32x4){0.f, 0.f, 0.f, 0.f}; X[3] = X[2]; }   // channel tile 1 holds channels 16..23 in lane groups 0, 1
-    if (!xok) { X[0] = X[2]; X[1] = X[2]; }
+    // Channel tile 1 holds channels 16..23 in lane groups 0, 1.  Lane groups 2, 3 need no zeroing: the packed stem filter's rows and
+    // shifts of channels 24..31 are zero (WeightPacker::image_stem16), so their accumulators are +0 and stay +0 through the maxima.
   };
 
-  // ---- stage2.0's row machinery (s2h_kernel)
+  // ---- stage2.0's row machinery (s2h_kernel; X arrives with the block's 2^4 already on it: xscale above)
   auto columns = [&](const f32x4 (&X)[4], float lim, float (&xe)[8], float (&xo)[8], float (&te)[8], float (&to)[8]) {
     f32x2 ine[4], ino[4];
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-      const f32x4 ve = X[2 * t] * 16.0f, vo = X[2 * t + 1] * 16.0f;
+      const f32x4 ve = X[2 * t], vo = X[2 * t + 1];
       ine[2 * t] = (f32x2){ve[0], ve[1]}; ine[2 * t + 1] = (f32x2){ve[2], ve[3]};
       ino[2 * t] = (f32x2){vo[0], vo[1]}; ino[2 * t + 1] = (f32x2){vo[2], vo[3]};
 #pragma unroll
@@ -674,8 +692,8 @@ __global__ __launch_bounds__(256, 2) void front2_kernel(FrontArgs fa) {
   auto acc_row = [&](auto dyc, const float (&T)[18], const float (&v0)[8], const float (&v1)[8], float (&S)[8], float (&Q)[8]) {
     constexpr int DY = decltype(dyc)::value;
     [&]<int... Cs>(std::integer_sequence<int, Cs...>) {
-      ((DY == 0 ? (void)(S[Cs] = quad_mul<YFV2_TK(Cs, 1)>(YFV2_TQ(T, Cs, 1), v0[Cs]), Q[Cs] = quad_mul<YFV2_TK(Cs, 0)>(YFV2_TQ(T, Cs, 0), v1[Cs]),
-                         quad_fmac1<YFV2_TK(Cs, 2)>(S[Cs], YFV2_TQ(T, Cs, 2), v1[Cs]))
+      ((DY == 0 ? (void)quad_mul2_fmac1<YFV2_TK(Cs, 1), YFV2_TK(Cs, 0), YFV2_TK(Cs, 2)>(
+                      S[Cs], Q[Cs], YFV2_TQ(T, Cs, 1), YFV2_TQ(T, Cs, 0), YFV2_TQ(T, Cs, 2), v0[Cs], v1[Cs])
                 : (void)quad_fmac3<YFV2_TK(Cs, DY * 3 + 1), YFV2_TK(Cs, DY * 3), YFV2_TK(Cs, DY * 3 + 2)>(
                       S[Cs], Q[Cs], YFV2_TQ(T, Cs, DY * 3 + 1), YFV2_TQ(T, Cs, DY * 3), YFV2_TQ(T, Cs, DY * 3 + 2), v0[Cs], v1[Cs])), ...);
     }(std::make_integer_sequence<int, 8>{});
@@ -724,9 +742,8 @@ __global__ __launch_bounds__(256, 2) void front2_kernel(FrontArgs fa) {
       __builtin_amdgcn_sched_barrier(0);
     }
   }
-  // here: the set holds (or awaits) the inputs of pooled row 2 y0
-  for (int j = 0; j < R; ++j) {
-    const int oy = y0 + j;
+  // here: the set holds (or awaits) the inputs of pooled row 2 y0.  The last band may be shorter than R: its rows past the map are not walked.
+  for (int oy = y0; oy < y1; ++oy) {
     float Sm[8], Qm[8], Sp[8], Qp[8], xe[8], xo[8], te[8], to[8];
     {
       float tm[18], tp[18]; ld_taps(tm, tp);
@@ -768,15 +785,14 @@ __global__ __launch_bounds__(256, 2) void front2_kernel(FrontArgs fa) {
       ld_filter(F2_S2 + S2H_W2, w2); ld_c2(F2_CST + 64, bi2);
       pw_h3(w2, dm, bi2, am, watch);
     }
-    const bool rowok = oy < y1;                    // wave-uniform
     f32x4 op[2], om[2];
 #pragma unroll
     for (int t = 0; t < 2; ++t)
 #pragma unroll
       for (int e = 0; e < 4; ++e) { op[t][e] = __builtin_fmaxf(ap[t][e], 0.f) * unscale_p; om[t][e] = __builtin_fmaxf(am[t][e], 0.f) * unscale_2; }
-    const int ro = oy * orowb;
+    const int ro = oy * orowb;                     // < 2^31: OOB + ro is still beyond the buffer's records, so a lane without this pair stores nothing (no select per store)
     auto st = [&](int k, float v0, float v1) {
-      __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, (f32x2){v0, v1}), rout, (rowok && soff[k] != OOB) ? soff[k] + ro : OOB, 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, (f32x2){v0, v1}), rout, soff[k] + ro, 0, 0);
     };
     st(0, op[0][0], op[0][1]); st(1, op[0][2], op[0][3]);
     st(2, om[0][0], om[0][1]); st(3, om[0][2], om[0][3]);
@@ -975,8 +991,7 @@ __global__ __launch_bounds__(256, 2) void s3h2_kernel(BlockS2Args a) {
     load_row(iy + 2, X);
   }
   const float limx = xok ? __builtin_inff() : 0.f;
-  for (int j = 0; j < R; ++j) {
-    const int oy = y0 + j;
+  for (int oy = y0; oy < y1; ++oy) {               // (the last band may be shorter than R: its rows past the map are not walked)
     float Sm[12], Qm[12], Sp[12], Qp[12], xe[12], xo[12], te[12], to[12];
     {
       float tm[27], tp[27]; ld_taps(tm, tp);
@@ -1011,7 +1026,7 @@ __global__ __launch_bounds__(256, 2) void s3h2_kernel(BlockS2Args a) {
     f32x4 am[3], ap[3];
     { f32x4 bip[3]; ld_c3(48, bip); pw_h3_48(WP, lane, dp, bip, ap, watch); }
     { f32x4 bi2[3]; ld_c3(96, bi2); pw_h3_48(W2, lane, dm, bi2, am, watch); }
-    if (st_lane && oy < y1) {
+    if (st_lane) {
       float* o = outp + (size_t)oy * OW * 96;
 #pragma unroll
       for (int t = 0; t < 3; ++t) {
