@@ -526,6 +526,55 @@ YFV2_API int yfv2_track_update_motion(yfv2_handle h, const float* dets /* (B,R,6
                                       float* track_box /* (B,R,4) or NULL */, float* fresh_dets /* (B,R,6) or NULL */, int32_t* fresh_src,
                                       int32_t* fresh_count, void* stream);
 
+/* ---- identity across frames, two association passes: low-score rows keep tracks alive and start none ----
+ * With one detection threshold a caller chooses between losing an object whose score dips for a few frames (occlusion, blur: the
+ * track dies, the object returns under a new id and is fresh a second time) and starting a track from every spurious row.  The
+ * two-pass form (ByteTrack's second association) is opt-in and changes nothing above: the same kernel, the same walk, either state
+ * layout as it is - a state can be handed between the one-pass and the two-pass entry point of its layout from call to call.
+ * Detect at a low threshold; confident rows are matched first; the low-score rows are offered only to the tracks still unmatched;
+ * no track ever starts from a low-score row.
+ * THE RULE, bit for bit (tests/track_two_pass_model.py restates it).  Per frame the order of the rule above changes in these places
+ * only; in the motion form the same changes apply on top of the motion rule (step 0 stays, v is taken against the predicted corners):
+ *   1 valid      as before.  A valid row is additionally HIGH when conf >= high_conf, LOW when low_conf <= conf < high_conf, OUT
+ *                otherwise (fp32 compares).  Invalid rows and OUT rows are treated alike: they never match, never start a track,
+ *                track_id 0.
+ *   2/3 first    the edges and the greedy walk exactly as above, over the HIGH rows only, with match_thres.
+ *   3b second    (new) edges between the LOW rows and the live slots the first pass left unmatched - with tracked_only, only
+ *                those whose misses word was 0 when the frame began: double(v) > match_thres_low, class_aware as in the first
+ *                pass; the same greedy order, v descending, then r ascending, then s ascending.  The first pass is complete
+ *                before the second begins: a LOW row never takes a slot from a HIGH row, whatever its IoU.
+ *   4 matched    identical for both passes (in the motion form: the filter update with the row's measurement, track_box).
+ *   5 unmatched  as before; a slot barred from the second pass by tracked_only is simply unmatched.
+ *   6 births     only HIGH rows that are unmatched and have conf >= init_conf.  A LOW row never starts a track.
+ *   7 header     header word 6 - 0 in the other forms, which do not touch it - counts second-pass matches: += their number in
+ *                this frame.  track_pass (optional) is 1 for a row matched in the first pass or born, 2 for a row matched in the
+ *                second pass, 0 otherwise and beyond n.
+ *   8 fresh      unchanged: a LOW row whose match brings hits to confirm_hits is fresh.
+ * Consequence: with high_conf = -inf every valid row is HIGH, and the form is the one-pass form of its layout bit for bit - state,
+ * header and every output - with track_pass == 1 wherever track_id != 0.
+ * Defaults (documented, not applied by the C ABI): high_conf = 0.5, low_conf = 0.1, match_thres_low = 0.5, tracked_only = 1 -
+ * ByteTrack's track_thresh, its 0.1 floor, its second-pass threshold and its "lost tracks are not offered low rows". */
+typedef struct yfv2_track_second {
+  float   high_conf;        /* a valid row is HIGH when conf >= high_conf (fp32 compare); not NaN */
+  float   low_conf;         /* ... LOW when low_conf <= conf < high_conf; a valid row below low_conf takes no part; not NaN, <= high_conf */
+  double  match_thres_low;  /* a second-pass edge needs double(IoU) > match_thres_low; finite, >= 0 */
+  int32_t tracked_only;     /* != 0: the second pass offers only slots whose misses were 0 when the frame began */
+} yfv2_track_second;
+
+/* One update in the two-pass form, of either layout: motion NULL - state is S * yfv2_track_state_words(M) int32, the plain 10-word
+ * slots; else S * yfv2_track_motion_state_words(M), the 32-word motion slots.  track_pass (B, R) int32 or NULL; track_box (B, R, 4)
+ * or NULL, and only with motion; the other arguments as above.  Every check of yfv2_track_update (and, with motion, of
+ * yfv2_track_update_motion); also YFV2_ERR_ARG with a message, nothing enqueued and the state untouched, for: second NULL;
+ * high_conf or low_conf NaN; low_conf > high_conf; match_thres_low not finite or negative; track_box given without motion.
+ * Enqueue only: one workgroup per frame, one launch per 768 frames, no host wait, no handle workspace.  An addition within ABI 7:
+ * yfv2_abi_version() is unchanged, as for the two tracker forms above. */
+YFV2_API int yfv2_track_update_two_pass(yfv2_handle h, const float* dets /* (B,R,6) */, const int32_t* count /* (B) */, int32_t R, int32_t B,
+                                        const int32_t* stream_of /* HOST, B */, int32_t* state, int32_t S, const yfv2_track_rule* rule,
+                                        const yfv2_track_motion* motion /* NULL: the plain 10-word slots; else the 32-word motion slots */,
+                                        const yfv2_track_second* second, int32_t* track_id /* (B,R) */, int32_t* track_hits /* (B,R) or NULL */,
+                                        int32_t* track_pass /* (B,R) or NULL */, float* track_box /* (B,R,4) or NULL; needs motion */,
+                                        float* fresh_dets /* (B,R,6) or NULL */, int32_t* fresh_src, int32_t* fresh_count, void* stream);
+
 /* ---- the ncnn sample's deployment path (sample/ncnn/src/yolo-fastestv2.cpp) ----
  * The reference's only native component post-processes differently from its Python path in every step that decides which boxes
  * come out: no objectness pre-filter (score = cls * obj > thresh only), boxes scaled to the source frame and TRUNCATED TO int

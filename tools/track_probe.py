@@ -19,7 +19,16 @@ process: --reps passes over the sequence, the two forms alternating, a fresh tra
 per form the median / min / max over all frames of all passes, and motion / plain of the medians.  The motion form's state and
 outputs of the first --host-frames frames are compared with tests/track_motion_model.py bit for bit.  Default --json:
 profiles/track_motion_probe.json.
+
+--two-pass: the two-pass form (Tracker(two_pass=True), yfv2_track_update_two_pass) NEXT TO the one-pass form of the same layout
+(--motion chooses it) on the same two sequences, in which --low-share of the rows (default 0.3) carry a conf in [0.1, 0.5) - LOW
+rows; the others stay in [0.5, 1.0].  Passes, alternation and statistics as for --motion.  The two-pass form's state and outputs of
+the first --host-frames frames are compared with tests/track_two_pass_model.py bit for bit.  The rounds of each pass are the model's
+parallel form's over ALL --frames frames of the first --round-streams streams (default 8; on the host, nothing timed), reported
+without the first frame, which has no tracks and so no round.  Default --json: profiles/track_two_pass_probe.json, with --motion
+profiles/track_two_pass_motion_probe.json.
 usage: python tools/track_probe.py [--streams 256] [--frames 30] [--host-frames 2] [--iters 20] [--motion [--reps 5]]
+                                   [--two-pass [--motion] [--low-share 0.3] [--reps 5] [--round-streams 8]]
 """
 import argparse
 import json
@@ -41,9 +50,9 @@ SIZES = [(1080, 1920), (720, 1280), (480, 640), (352, 352)]   # (h, w)
 R, M = 300, 256
 
 
-def sequence(rng, S, T, live, seen_n):
+def sequence(rng, S, T, live, seen_n, low_share=0.0):
     """T arrays (S, R, 6) and counts (S): `live` objects per stream on a 1920 x 1080 canvas, drifting up to 3 pixels per frame, a
-    random `seen_n` of them in each frame"""
+    random `seen_n` of them in each frame; low_share of a frame's rows get a conf in [0.1, 0.5), the others one in [0.5, 1.0]"""
     pos = rng.uniform(0, [1800, 1000], (S, live, 2))
     size = rng.uniform(30, 120, (S, live, 2))
     cls = rng.integers(0, 80, (S, live)).astype(np.float32)
@@ -55,6 +64,9 @@ def sequence(rng, S, T, live, seen_n):
         for s in range(S):
             seen = rng.permutation(live)[:seen_n]
             conf = np.sort(rng.uniform(0.3, 1.0, len(seen)))[::-1]
+            if low_share > 0.0:
+                n_low = int(round(low_share * len(seen)))
+                conf = np.sort(np.concatenate([rng.uniform(0.5, 1.0, len(seen) - n_low), rng.uniform(0.1, 0.5, n_low)]))[::-1]
             dets[s, :len(seen)] = np.concatenate([pos[s, seen], pos[s, seen] + size[s, seen], conf[:, None], cls[s, seen, None]], axis=1)
             count[s] = len(seen)
         out.append((dets, count))
@@ -144,6 +156,57 @@ def run_motion(eng, dev, seq, host_frames, reps):
             "issued": {"plain": heads[False][0], "motion": heads[True][0]}, "live": {"plain": heads[False][1], "motion": heads[True][1]}}
 
 
+def run_two_pass(eng, dev, seq, host_frames, reps, motion, round_streams):
+    import track_model
+    import track_two_pass_model
+    S = seq[0][0].shape[0]
+    rule = dict(max_tracks=M, match_thres=0.3, class_aware=True, init_conf=0.0, max_misses=30, confirm_hits=3)
+    dseq = [(torch.from_numpy(d).to(dev), torch.from_numpy(c).to(dev)) for d, c in seq]
+    base = (torch.empty((S, R), device=dev, dtype=torch.int32), torch.empty((S, R), device=dev, dtype=torch.int32), torch.empty((S, R, 6), device=dev),
+            torch.empty((S, R), device=dev, dtype=torch.int32), torch.empty((S,), device=dev, dtype=torch.int32))
+    box = (torch.empty((S, R, 4), device=dev),) if motion else ()
+    outs = {False: base + box, True: base + box + (torch.empty((S, R), device=dev, dtype=torch.int32),)}
+    ms, states = {False: [], True: []}, {}
+    for rep in range(reps + 1):                             # pass 0 is the warm-up of both forms
+        for two in (False, True):
+            tr = yfv2.Tracker(eng, S, motion=motion or None, two_pass=two or None, **rule)
+            for d, c in dseq:
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                tr.update(d, c, fresh=True, box=motion, passes=two, out=outs[two])
+                e1.record()
+                torch.cuda.synchronize()
+                if rep:
+                    ms[two].append(e0.elapsed_time(e1))
+            same = two not in states or bool(torch.equal(states[two], tr.state))
+            states[two] = tr.state.clone()
+            assert same, "two passes over one sequence left different states"
+    # the two-pass form against its model on the first frames
+    model, chk = track_two_pass_model.Model(S, motion=motion or None, **rule), yfv2.Tracker(eng, S, motion=motion or None, two_pass=True, **rule)
+    same = True
+    for d, c in dseq[:host_frames]:
+        want = model.update(d.cpu().numpy(), c.cpu().numpy())
+        got = chk.update(d, c, fresh=True, box=motion, passes=True, out=outs[True])
+        same = (same and bool(torch.equal(chk.state.cpu(), torch.from_numpy(model.state))) and bool(torch.equal(got[0].cpu(), torch.from_numpy(want["track_id"])))
+                and bool(torch.equal(got[-1].cpu(), torch.from_numpy(want["track_pass"]))) and bool(torch.equal(got[4].cpu(), torch.from_numpy(want["fresh_count"]))))
+    # the rounds of each pass: the model's parallel form over the whole sequence of the first streams, the trackless first frame left out
+    K = min(round_streams, S)
+    par = track_two_pass_model.Model(K, motion=motion or None, **rule)
+    for d, c in seq:
+        par.update(d[:K], c[:K], match=track_model.mutual_best)
+    rounds = par.stats["rounds"][K:]
+    heads = {k: states[k][:, :7].sum(0).tolist() for k in states}
+    low = float(np.mean([((d[:, :, 4] < 0.5) & (np.arange(R)[None, :] < c[:, None])).sum() / max(int(c.sum()), 1) for d, c in seq]))
+    return {"rows_per_frame": int(round(float(np.mean([c.mean() for _d, c in seq])))), "low_share": round(low, 3), "reps": reps,
+            "one_pass_ms": spread(ms[False]), "two_pass_ms": spread(ms[True]),
+            "ratio": round(statistics.median(ms[True]) / statistics.median(ms[False]), 3), "two_pass_equals_model": same,
+            "model_rounds": {"streams": K, "frames": len(seq) - 1, "of": "every frame but the first of the first streams, host model",
+                             "first_pass": {"max": max(r[0] for r in rounds), "mean": round(float(np.mean([r[0] for r in rounds])), 2)},
+                             "second_pass": {"max": max(r[1] for r in rounds), "mean": round(float(np.mean([r[1] for r in rounds])), 2)}},
+            "second_pass_matches": heads[True][6],
+            "issued": {"one_pass": heads[False][0], "two_pass": heads[True][0]}, "live": {"one_pass": heads[False][1], "two_pass": heads[True][1]}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", type=int, default=256)
@@ -153,16 +216,30 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--motion", action="store_true")
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--two-pass", action="store_true")
+    ap.add_argument("--low-share", type=float, default=0.3)
+    ap.add_argument("--round-streams", type=int, default=8)
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
     if args.json is None:
-        args.json = os.path.join(REPO, "profiles", "track_motion_probe.json" if args.motion else "track_probe.json")
+        args.json = os.path.join(REPO, "profiles", ("track_two_pass_motion_probe.json" if args.motion else "track_two_pass_probe.json") if args.two_pass else "track_motion_probe.json" if args.motion else "track_probe.json")
 
     dev = torch.device("cuda:0")
     S = args.streams
     eng = yfv2.Engine(dev, 352, 352, 80, 3, anchors=ANCHORS, max_batch=S, plan={})
     eng.load_state_dict(yfv2.random_state_dict(0))
     rng = np.random.default_rng(args.seed)
+    if args.two_pass:
+        res = {"tool": "track_probe --two-pass" + (" --motion" if args.motion else ""), "streams": S, "R": R, "M": M, "frames": args.frames,
+               "host_frames": args.host_frames, "layout": "motion" if args.motion else "plain",
+               "full": run_two_pass(eng, dev, sequence(rng, S, args.frames, 333, 300, args.low_share), args.host_frames, args.reps, args.motion, args.round_streams),
+               "sparse": run_two_pass(eng, dev, sequence(rng, S, args.frames, 33, 30, args.low_share), args.host_frames, args.reps, args.motion, args.round_streams)}
+        line = json.dumps(res)
+        print(line)
+        os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
+        with open(args.json, "w") as f:
+            f.write(line + "\n")
+        return
     if args.motion:
         res = {"tool": "track_probe --motion", "streams": S, "R": R, "M": M, "frames": args.frames, "host_frames": args.host_frames,
                "full": run_motion(eng, dev, sequence(rng, S, args.frames, 333, 300), args.host_frames, args.reps),

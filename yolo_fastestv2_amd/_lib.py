@@ -101,6 +101,11 @@ class TrackMotion(C.Structure):
     _fields_ = [("std_pos", C.c_float), ("std_vel", C.c_float), ("std_meas", C.c_float)]
 
 
+class TrackSecond(C.Structure):
+    """yfv2_track_second (include/yfv2.h): the score classes and the threshold of the tracker's second association pass."""
+    _fields_ = [("high_conf", C.c_float), ("low_conf", C.c_float), ("match_thres_low", C.c_double), ("tracked_only", C.c_int32)]
+
+
 class KmeansInfo(C.Structure):
     """yfv2_kmeans_info (include/yfv2.h): what ended yfv2_anchor_kmeans' loop."""
     _fields_ = [("struct_size", C.c_int32), ("iterations", C.c_int32), ("converged", C.c_int32), ("empty_cluster", C.c_int32),
@@ -188,6 +193,9 @@ _PROTOTYPES = {
     "yfv2_track_update_motion": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_int32,
                                            C.POINTER(TrackRule), C.POINTER(TrackMotion), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                            C.c_void_p, C.c_void_p]),
+    "yfv2_track_update_two_pass": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_int32,
+                                             C.POINTER(TrackRule), C.POINTER(TrackMotion), C.POINTER(TrackSecond), C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "yfv2_export_maps": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "yfv2_deploy_post": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
                                    C.c_int32, C.c_void_p]),

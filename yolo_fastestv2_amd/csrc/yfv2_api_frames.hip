@@ -312,8 +312,8 @@ int yfv2_crop_detections_yuv(yfv2_handle h, const yfv2_frame_yuv* frames, int32_
   return crop_detections<YuvFrames>(h, "yfv2_crop_detections_yuv", frames, B, dets, count, R, rule, crops, crop_src, crop_rect, crop_offset, crop_skipped, cap, stream);
 }
 
-// ---- the per-stream IoU tracker (its motion form 4.19; kernel, and yfv2_track_iou / yfv2_track_filter_step beside
-// the one function each of them exposes: yfv2_track.hip) -------
+// ---- the per-stream IoU tracker (its motion form 4.19, its two-pass form 4.20; kernel, and yfv2_track_iou /
+// yfv2_track_filter_step beside the one function each of them exposes: yfv2_track.hip) -------
 // Every check first; then one launch per TRACK_CHUNK frames (the streams of a launch travel in its arguments: no table, no copy,
 // no workspace).  The frames of a call are distinct streams, so the launches share nothing.
 int64_t yfv2_track_state_words(int32_t max_tracks) {
@@ -326,12 +326,15 @@ int64_t yfv2_track_motion_state_words(int32_t max_tracks) {
   return (int64_t)TRACK_HEADER + (int64_t)TRACK_SLOT_MOTION * max_tracks;
 }
 
-// both forms: motion == nullptr is the plain one (with_motion tells a missing argument from the plain form)
-static int track_update(const std::string& w_, bool with_motion, yfv2_handle h, const float* dets, const int32_t* count, int32_t R, int32_t B,
+// all forms: motion == nullptr is a plain table (with_motion tells a missing argument from the plain form); two_pass: second is
+// required and the launch is the two-pass kernel of the table's layout
+static int track_update(const std::string& w_, bool with_motion, bool two_pass, yfv2_handle h, const float* dets, const int32_t* count, int32_t R, int32_t B,
                         const int32_t* stream_of, int32_t* state, int32_t S, const yfv2_track_rule* rule, const yfv2_track_motion* motion,
-                        int32_t* track_id, int32_t* track_hits, float* track_box, float* fresh_dets, int32_t* fresh_src, int32_t* fresh_count, void* stream) {
+                        const yfv2_track_second* second, int32_t* track_id, int32_t* track_hits, int32_t* track_pass, float* track_box, float* fresh_dets,
+                        int32_t* fresh_src, int32_t* fresh_count, void* stream) {
   if (!h) return fail(nullptr, YFV2_ERR_ARG, "null handle");
-  if (!dets || !count || !stream_of || !state || !rule || !track_id || (with_motion && !motion)) return fail(h, YFV2_ERR_ARG, w_ + ": null pointer");
+  if (!dets || !count || !stream_of || !state || !rule || !track_id || (with_motion && !motion) || (two_pass && !second))
+    return fail(h, YFV2_ERR_ARG, w_ + ": null pointer");
   const int given = (fresh_dets != nullptr) + (fresh_src != nullptr) + (fresh_count != nullptr);
   if (given != 0 && given != 3) return fail(h, YFV2_ERR_ARG, w_ + ": fresh_dets, fresh_src and fresh_count must all be given or all be NULL");
   if (B < 1) return fail(h, YFV2_ERR_ARG, w_ + ": B < 1");
@@ -346,6 +349,13 @@ static int track_update(const std::string& w_, bool with_motion, yfv2_handle h, 
   if (with_motion)
     for (const float v : {motion->std_pos, motion->std_vel, motion->std_meas})
       if (!std::isfinite(v) || !(v > 0.0f)) return fail(h, YFV2_ERR_ARG, w_ + ": std_pos, std_vel and std_meas must be finite and > 0");
+  if (two_pass) {
+    if (std::isnan(second->high_conf) || std::isnan(second->low_conf)) return fail(h, YFV2_ERR_ARG, w_ + ": high_conf or low_conf is not a number");
+    if (second->low_conf > second->high_conf) return fail(h, YFV2_ERR_ARG, w_ + ": low_conf must not exceed high_conf");
+    if (!std::isfinite(second->match_thres_low) || second->match_thres_low < 0.0)
+      return fail(h, YFV2_ERR_ARG, w_ + ": match_thres_low must be a finite number >= 0");
+    if (track_box && !with_motion) return fail(h, YFV2_ERR_ARG, w_ + ": track_box needs motion");
+  }
   std::vector<int32_t> sorted(stream_of, stream_of + B);
   std::sort(sorted.begin(), sorted.end());
   if (sorted.front() < 0 || sorted.back() >= S)
@@ -354,10 +364,11 @@ static int track_update(const std::string& w_, bool with_motion, yfv2_handle h, 
     if (sorted[b] == sorted[b - 1]) return fail(h, YFV2_ERR_ARG, w_ + ": stream " + std::to_string(sorted[b]) + " named twice (one frame per stream and call)");
   DeviceGuard guard(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  TrackMotionArgs a{};                     // the plain launch takes its TrackArgs part
+  TrackTwoArgs a{};                        // the motion launch takes its TrackMotionArgs part, the plain launch its TrackArgs part
   a.R = R; a.M = q.max_tracks; a.state = state; a.thres = q.match_thres; a.class_aware = q.class_aware; a.init_conf = q.init_conf;
   a.max_misses = q.max_misses; a.confirm_hits = q.confirm_hits;
   if (with_motion) a.motion = TrackMotion{motion->std_pos, motion->std_vel, motion->std_meas};
+  if (two_pass) { a.high_conf = second->high_conf; a.low_conf = second->low_conf; a.thres_low = second->match_thres_low; a.tracked_only = second->tracked_only; }
   for (int32_t b0 = 0; b0 < B; b0 += TRACK_CHUNK) {
     const int frames = std::min<int32_t>(TRACK_CHUNK, B - b0);
     const size_t row0 = (size_t)b0 * R;
@@ -365,8 +376,10 @@ static int track_update(const std::string& w_, bool with_motion, yfv2_handle h, 
     a.fresh_dets = fresh_dets ? fresh_dets + row0 * 6 : nullptr; a.fresh_src = fresh_src ? fresh_src + row0 : nullptr;
     a.fresh_count = fresh_count ? fresh_count + b0 : nullptr;
     a.track_box = track_box ? track_box + row0 * 4 : nullptr;
+    a.track_pass = track_pass ? track_pass + row0 : nullptr;
     std::copy(stream_of + b0, stream_of + b0 + frames, a.stream_of);
-    if (with_motion) yfv2_launch_track_motion(a, frames, s);
+    if (two_pass) yfv2_launch_track_two_pass(a, with_motion, frames, s);
+    else if (with_motion) yfv2_launch_track_motion(a, frames, s);
     else yfv2_launch_track(a, frames, s);
   }
   HIP_TRY(h, hipGetLastError());
@@ -376,15 +389,23 @@ static int track_update(const std::string& w_, bool with_motion, yfv2_handle h, 
 int yfv2_track_update(yfv2_handle h, const float* dets, const int32_t* count, int32_t R, int32_t B, const int32_t* stream_of, int32_t* state, int32_t S,
                       const yfv2_track_rule* rule, int32_t* track_id, int32_t* track_hits, float* fresh_dets, int32_t* fresh_src, int32_t* fresh_count,
                       void* stream) {
-  return track_update("yfv2_track_update", false, h, dets, count, R, B, stream_of, state, S, rule, nullptr, track_id, track_hits, nullptr, fresh_dets,
-                      fresh_src, fresh_count, stream);
+  return track_update("yfv2_track_update", false, false, h, dets, count, R, B, stream_of, state, S, rule, nullptr, nullptr, track_id, track_hits, nullptr,
+                      nullptr, fresh_dets, fresh_src, fresh_count, stream);
 }
 
 int yfv2_track_update_motion(yfv2_handle h, const float* dets, const int32_t* count, int32_t R, int32_t B, const int32_t* stream_of, int32_t* state,
                              int32_t S, const yfv2_track_rule* rule, const yfv2_track_motion* motion, int32_t* track_id, int32_t* track_hits,
                              float* track_box, float* fresh_dets, int32_t* fresh_src, int32_t* fresh_count, void* stream) {
-  return track_update("yfv2_track_update_motion", true, h, dets, count, R, B, stream_of, state, S, rule, motion, track_id, track_hits, track_box, fresh_dets,
-                      fresh_src, fresh_count, stream);
+  return track_update("yfv2_track_update_motion", true, false, h, dets, count, R, B, stream_of, state, S, rule, motion, nullptr, track_id, track_hits, nullptr,
+                      track_box, fresh_dets, fresh_src, fresh_count, stream);
+}
+
+int yfv2_track_update_two_pass(yfv2_handle h, const float* dets, const int32_t* count, int32_t R, int32_t B, const int32_t* stream_of, int32_t* state,
+                               int32_t S, const yfv2_track_rule* rule, const yfv2_track_motion* motion, const yfv2_track_second* second, int32_t* track_id,
+                               int32_t* track_hits, int32_t* track_pass, float* track_box, float* fresh_dets, int32_t* fresh_src, int32_t* fresh_count,
+                               void* stream) {
+  return track_update("yfv2_track_update_two_pass", motion != nullptr, true, h, dets, count, R, B, stream_of, state, S, rule, motion, second, track_id,
+                      track_hits, track_pass, track_box, fresh_dets, fresh_src, fresh_count, stream);
 }
 
 int yfv2_resize_u8(yfv2_handle h, const uint8_t* src, int32_t B, int32_t src_h, int32_t src_w, uint8_t* dst, void* stream) {

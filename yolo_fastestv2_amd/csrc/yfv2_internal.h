@@ -472,6 +472,14 @@ struct TrackMotionArgs : TrackArgs {   // the plain form's arguments stay what t
 };
 void yfv2_launch_track(const TrackArgs& a, int frames, hipStream_t s);   // one workgroup per frame, frames <= TRACK_CHUNK
 void yfv2_launch_track_motion(const TrackMotionArgs& a, int frames, hipStream_t s);   // ... of track_kernel<true>; a.state in 32-word slots
+// the two-pass form (yfv2_track_update_two_pass): either layout, the rounds run over the HIGH rows and then the LOW
+struct TrackTwoArgs : TrackMotionArgs {   // the other forms' arguments stay what they were: their kernels are the ones they were
+  float high_conf, low_conf;   // a valid row is HIGH at conf >= high_conf, LOW at low_conf <= conf < high_conf, else takes no part
+  double thres_low;            // the second pass's edge: double(IoU) > thres_low
+  int tracked_only;            // != 0: a slot with misses != 0 at the frame's start is not offered to the second pass
+  int32_t* track_pass;         // (B, R) or null, offset like dets
+};
+void yfv2_launch_track_two_pass(const TrackTwoArgs& a, bool motion, int frames, hipStream_t s);   // motion: a.state in 32-word slots
 // dets columns 0-3 of the first count[b] rows of frame b times frames[b].box_x / box_y (yfv2_post.hip)
 void yfv2_launch_frame_boxes(float* dets, const int32_t* count, const ResizeFrame* frames, int B, hipStream_t s);
 void yfv2_launch_decode(const DecodeArgs& a, hipStream_t s);

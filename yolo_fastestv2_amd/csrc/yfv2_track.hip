@@ -28,6 +28,15 @@
 // (a predicted word not finite, predicted w or h not > 0) gets NaN corners: track_iou then gives NaN, which is no edge - no flag,
 // no LDS.  Words 0..3 (the last matched row) are written where they change, since sbox no longer holds them.  The filter is ONE
 // __host__ __device__ function (track_filter_step: the kernel, yfv2_track_filter_step and yfv2_track_birth call it).
+//
+// The two-pass form (yfv2_track_update_two_pass) is the SAME kernel again, track_kernel<MOTION, true>, of either
+// layout: the rounds are one routine, the body of a loop that runs once or twice.  A row's class - HIGH, LOW, OUT - comes from its
+// conf in global memory, the way its cls does: no LDS.  The first run scans the HIGH rows with match_thres; a LOW row waits as (TK_LOW, 0),
+// which every loop of the rounds skips.  Between the runs the unmatched HIGH rows are done as they stand, the LOW rows become "to be
+// scanned", and a live unmatched slot that tracked_only bars gets the key TK_BARRED: the scan skips it like a taken one, the
+// round's reset leaves it, and steps 4 / 5 see a slot that is not TK_TAKEN - unmatched.  The second run scans with match_thres_low.
+// A matched row's pass is its class again (a HIGH row matches in the first run or is born, a LOW row matches in the second run or
+// not at all), so track_pass and header word 6 need no state: a compare, and a ballot's count.
 #include <algorithm>
 #include <cmath>
 #include <type_traits>
@@ -119,6 +128,8 @@ namespace {
 
 constexpr int TK_MAX_THREADS = 1024;
 constexpr int TK_TAKEN = -1;            // a row's v word: matched or born; a slot key's high word: dead or matched
+constexpr int TK_BARRED = -2;           // (two-pass) a slot key's high word: live, unmatched, not offered to the second pass
+constexpr int TK_LOW = -3;              // (two-pass) a row's slot word while the first pass runs: a LOW row, v word 0
 
 // the rank of this thread's flag among the workgroup's set flags, in thread order; every thread of the workgroup calls it
 __device__ __forceinline__ int block_rank(bool f, int* s_cnt, int& total) {
@@ -202,9 +213,13 @@ __device__ __forceinline__ void row_box_store(float* track_box, size_t row, floa
   o[0] = c.x; o[1] = c.y; o[2] = c.z; o[3] = c.w;
 }
 
-// MOTION: the slots are TRACK_SLOT_MOTION words and carry filters (above); everything else is the one kernel
-template <bool MOTION>
-__global__ __launch_bounds__(TK_MAX_THREADS) void track_kernel(std::conditional_t<MOTION, TrackMotionArgs, TrackArgs> a) {
+// MOTION: the slots are TRACK_SLOT_MOTION words and carry filters (above); TWO: the rounds run twice, over the HIGH rows and over
+// the LOW rows (TrackTwoArgs; a plain table leaves its motion part unused); everything else is the one kernel
+template <bool MOTION, bool TWO>
+using track_args_t = std::conditional_t<TWO, TrackTwoArgs, std::conditional_t<MOTION, TrackMotionArgs, TrackArgs>>;
+
+template <bool MOTION, bool TWO>
+__global__ __launch_bounds__(TK_MAX_THREADS) void track_kernel(track_args_t<MOTION, TWO> a) {
   constexpr int SLOT = MOTION ? TRACK_SLOT_MOTION : TRACK_SLOT;
   extern __shared__ __attribute__((aligned(16))) unsigned char tk_lds[];
   __shared__ int s_cnt[TK_MAX_THREADS / 64];
@@ -249,54 +264,84 @@ __global__ __launch_bounds__(TK_MAX_THREADS) void track_kernel(std::conditional_
       valid = valid && track_finite(z[0]) && track_finite(z[1]) && track_finite(z[2]) && track_finite(z[3]);
     }
     rbox[r] = make_float4(x1, y1, x2, y2);
-    rst[r] = valid ? make_int2(-1, 1) : make_int2(-2, 0);   // v word: 0 = done, unmatched; 1 = to be scanned (no IoU's bits)
+    if constexpr (TWO) {                                     // an OUT row is an invalid row; a LOW row waits for the second pass
+      const float conf = row[4];
+      rst[r] = !valid || !(conf >= a.low_conf) ? make_int2(-2, 0) : conf >= a.high_conf ? make_int2(-1, 1) : make_int2(TK_LOW, 0);
+    } else {
+      rst[r] = valid ? make_int2(-1, 1) : make_int2(-2, 0);   // v word: 0 = done, unmatched; 1 = to be scanned (no IoU's bits)
+    }
   }
   __syncthreads();
 
-  // ---- steps 2 and 3: the rounds
-  const double thres = a.thres;
+  // ---- steps 2 and 3: the rounds - ONE routine: the rows whose v word says "to be scanned" against the slots whose key is free,
+  // until no such row has an edge.  The two-pass form runs it twice: over the HIGH rows with match_thres, then (step 3b) over the LOW
+  // rows and the slots still unmatched with match_thres_low; a key's high word may then also be TK_BARRED, which the scan skips like
+  // TK_TAKEN and which, unlike a free key, the round's reset leaves alone.
   const bool aware = a.class_aware != 0;
-  for (;;) {
-    int any = 0;
-    for (int r = tid; r < n; r += nt) {
-      const int2 q = rst[r];
-      if (q.y == 0 || q.y == TK_TAKEN) continue;
-      const float4 g = rbox[r];
-      const float garea = track_area(g.x, g.y, g.z, g.w);
-      const float gcls = rows[6 * r + 5];
-      const unsigned long long low = (unsigned)~r;
-      int best = -1, bv = 0;
-      for (int s = 0; s < M; ++s) {                          // one LDS address for the whole wave
-        if ((int)(skey[s] >> 32) == TK_TAKEN) continue;      // dead or matched: stable during the scan, whatever the atomics do
-        if (aware && !(scls[s] == gcls)) continue;
-        const float4 t = sbox[s];
-        const float v = track_iou(t.x, t.y, t.z, t.w, track_area(t.x, t.y, t.z, t.w), g.x, g.y, g.z, g.w, garea);
-        if ((double)v > thres) {                             // v > 0: its bits order like its value; NaN fails
-          const int vb = f2i(v);
-          atomicMax(&skey[s], ((unsigned long long)(unsigned)vb << 32) | low);
-          if (vb > bv) { bv = vb; best = s; }
+  for (int pass = 0; pass < (TWO ? 2 : 1); ++pass) {
+    double thres = a.thres;
+    if constexpr (TWO) {
+      if (pass == 1) {                                       // the first pass is complete: its unmatched HIGH rows are done as they stand
+        for (int r = tid; r < n; r += nt)
+          if (rst[r].x == TK_LOW) rst[r] = make_int2(-1, 1);
+        if (a.tracked_only != 0)
+          for (int s = tid; s < M; s += nt)                  // smiss is still the frame's first word: steps 4 and 5 come later
+            if ((int)(skey[s] >> 32) != TK_TAKEN && smiss[s] != 0) skey[s] = (unsigned long long)(unsigned)TK_BARRED << 32;
+        __syncthreads();
+        thres = a.thres_low;
+      }
+    }
+    for (;;) {
+      int any = 0;
+      for (int r = tid; r < n; r += nt) {
+        const int2 q = rst[r];
+        if (q.y == 0 || q.y == TK_TAKEN) continue;
+        const float4 g = rbox[r];
+        const float garea = track_area(g.x, g.y, g.z, g.w);
+        const float gcls = rows[6 * r + 5];
+        const unsigned long long low = (unsigned)~r;
+        int best = -1, bv = 0;
+        for (int s = 0; s < M; ++s) {                          // one LDS address for the whole wave
+          if constexpr (TWO) {
+            if ((int)(skey[s] >> 32) < 0) continue;          // ... or barred: every other high word is 0 or a positive fp32's bits
+          } else {
+            if ((int)(skey[s] >> 32) == TK_TAKEN) continue;  // dead or matched: stable during the scan, whatever the atomics do
+          }
+          if (aware && !(scls[s] == gcls)) continue;
+          const float4 t = sbox[s];
+          const float v = track_iou(t.x, t.y, t.z, t.w, track_area(t.x, t.y, t.z, t.w), g.x, g.y, g.z, g.w, garea);
+          if ((double)v > thres) {                           // v > 0: its bits order like its value; NaN fails
+            const int vb = f2i(v);
+            atomicMax(&skey[s], ((unsigned long long)(unsigned)vb << 32) | low);
+            if (vb > bv) { bv = vb; best = s; }
+          }
+        }
+        rst[r] = make_int2(best, bv);                          // no edge: (-1, 0), done
+        any |= best >= 0;
+      }
+      if (!__syncthreads_or(any)) break;
+      for (int r = tid; r < n; r += nt) {
+        const int2 q = rst[r];
+        if (q.y == 0 || q.y == TK_TAKEN) continue;
+        if (skey[q.x] == (((unsigned long long)(unsigned)q.y << 32) | (unsigned)~r)) rst[r].y = TK_TAKEN - 1;   // mutual: marked, taken below
+      }
+      __syncthreads();
+      for (int r = tid; r < n; r += nt) {
+        const int2 q = rst[r];
+        if (q.y != TK_TAKEN - 1) continue;
+        skey[q.x] = ((unsigned long long)(unsigned)TK_TAKEN << 32) | (unsigned)r;
+        rst[r].y = TK_TAKEN;
+      }
+      __syncthreads();
+      for (int s = tid; s < M; s += nt) {                      // the next round's offers start from nothing
+        if constexpr (TWO) {
+          if ((int)(skey[s] >> 32) >= 0) skey[s] = 0ull;
+        } else {
+          if ((int)(skey[s] >> 32) != TK_TAKEN) skey[s] = 0ull;
         }
       }
-      rst[r] = make_int2(best, bv);                          // no edge: (-1, 0), done
-      any |= best >= 0;
+      __syncthreads();
     }
-    if (!__syncthreads_or(any)) break;
-    for (int r = tid; r < n; r += nt) {
-      const int2 q = rst[r];
-      if (q.y == 0 || q.y == TK_TAKEN) continue;
-      if (skey[q.x] == (((unsigned long long)(unsigned)q.y << 32) | (unsigned)~r)) rst[r].y = TK_TAKEN - 1;   // mutual: marked, taken below
-    }
-    __syncthreads();
-    for (int r = tid; r < n; r += nt) {
-      const int2 q = rst[r];
-      if (q.y != TK_TAKEN - 1) continue;
-      skey[q.x] = ((unsigned long long)(unsigned)TK_TAKEN << 32) | (unsigned)r;
-      rst[r].y = TK_TAKEN;
-    }
-    __syncthreads();
-    for (int s = tid; s < M; s += nt)
-      if ((int)(skey[s] >> 32) != TK_TAKEN) skey[s] = 0ull;  // the next round's offers start from nothing
-    __syncthreads();
   }
 
   // ---- steps 4 and 5: matched slots take their row, the others miss and may die
@@ -359,6 +404,7 @@ __global__ __launch_bounds__(TK_MAX_THREADS) void track_kernel(std::conditional_
       const int2 q = rst[r];
       conf = rows[6 * r + 4];
       want = q.x == -1 && q.y == 0 && conf >= a.init_conf;
+      if constexpr (TWO) want = want && conf >= a.high_conf;   // an unmatched LOW row ends as (-1, 0) too: it never starts a track
     }
     int total;
     const int k = nb + block_rank(want, s_cnt, total);
@@ -382,13 +428,20 @@ __global__ __launch_bounds__(TK_MAX_THREADS) void track_kernel(std::conditional_
 
   // ---- steps 7 and 8: the rows' outputs, the fresh rows in row order
   const bool emit = a.fresh_dets != nullptr;
-  int nfresh = 0;
+  int nfresh = 0, nsecond = 0;
   for (int r0 = 0; r0 < R; r0 += nt) {
     const int r = r0 + tid;
     int id = 0, hits = 0;
     if (r < n) {
       const int2 q = rst[r];
       if (q.y == TK_TAKEN) { id = sid[q.x]; hits = shits[q.x]; }
+    }
+    if constexpr (TWO) {                                     // an assigned row's pass is its class: HIGH matched first or was born
+      const int pass = id == 0 ? 0 : rows[6 * r + 4] >= a.high_conf ? 1 : 2;
+      if (r < R && a.track_pass) a.track_pass[(size_t)b * R + r] = pass;
+      int total;
+      block_rank(pass == 2, s_cnt, total);
+      nsecond += total;
     }
     if (r < R) {
       a.track_id[(size_t)b * R + r] = id;
@@ -428,20 +481,25 @@ __global__ __launch_bounds__(TK_MAX_THREADS) void track_kernel(std::conditional_
     head[3] += born;
     head[4] += s_deaths;
     head[5] += nb - born;
+    if constexpr (TWO) head[6] += nsecond;
     if (emit) a.fresh_count[b] = nfresh;
   }
 }
 
 }  // namespace
 
-template <bool MOTION>
-static void launch_track(const std::conditional_t<MOTION, TrackMotionArgs, TrackArgs>& a, int frames, hipStream_t s) {
+template <bool MOTION, bool TWO>
+static void launch_track(const track_args_t<MOTION, TWO>& a, int frames, hipStream_t s) {
   const int threads = std::min(TK_MAX_THREADS, std::max(64, (a.R + 63) / 64 * 64));
   const size_t lds = (size_t)24 * a.R + (size_t)48 * a.M;
-  YFV2_LAUNCH_LDS(yfv2_device(), track_kernel<MOTION>, 24 * TRACK_MAX_R + 48 * TRACK_MAX_M, dim3((unsigned)frames), dim3((unsigned)threads), lds, s, a);
+  YFV2_LAUNCH_LDS(yfv2_device(), (track_kernel<MOTION, TWO>), 24 * TRACK_MAX_R + 48 * TRACK_MAX_M, dim3((unsigned)frames), dim3((unsigned)threads), lds, s, a);
 }
-void yfv2_launch_track(const TrackArgs& a, int frames, hipStream_t s) { launch_track<false>(a, frames, s); }
-void yfv2_launch_track_motion(const TrackMotionArgs& a,int frames, hipStream_t s) { launch_track<true>(a, frames, s); }
+void yfv2_launch_track(const TrackArgs& a, int frames, hipStream_t s) { launch_track<false, false>(a, frames, s); }
+void yfv2_launch_track_motion(const TrackMotionArgs& a,int frames, hipStream_t s) { launch_track<true, false>(a, frames, s); }
+void yfv2_launch_track_two_pass(const TrackTwoArgs& a, bool motion, int frames, hipStream_t s) {
+  if (motion) launch_track<true, true>(a, frames, s);
+  else launch_track<false, true>(a, frames, s);
+}
 
 extern "C" int yfv2_track_iou(const float a[4], const float b[4], float* v) {
   if (!a || !b || !v) return yfv2_ctx_fail(nullptr, YFV2_ERR_ARG, "yfv2_track_iou: null pointer");

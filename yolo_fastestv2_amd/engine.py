@@ -509,6 +509,29 @@ class Engine:
         return self._track_update("track_update", None, False, dets, count, streams, state, max_tracks, match_thres, class_aware, init_conf, max_misses,
                                   confirm_hits, fresh, out)
 
+    def track_update_two_pass(self, dets, count, streams, state, max_tracks, match_thres=0.3, class_aware=True, init_conf=0.0, max_misses=30,
+                              confirm_hits=3, high_conf=0.5, low_conf=0.1, match_thres_low=0.5, tracked_only=True, motion=None, fresh=False,
+                              box=False, passes=False, out=None):
+        """track_update / track_update_motion with two association passes (include/yfv2.h yfv2_track_update_two_pass):
+        the rows with conf >= high_conf are matched first, the rows with low_conf <= conf < high_conf are then offered to the tracks
+        still unmatched (tracked_only: only to those that were matched in their last frame) with IoU > match_thres_low, and start no
+        track; rows below low_conf take no part.  motion: None - state is the plain (S, 8 + 10 * max_tracks); True or a dict with any
+        of std_pos, std_vel, std_meas - the motion form's (S, 8 + 32 * max_tracks), and box=True is allowed.  Returns what the
+        one-pass call of the layout returns and, with passes=True, last of all track_pass (B, R) int32: 1 for a row matched in the
+        first pass or born, 2 for a row matched in the second pass, 0 for a row without a track."""
+        if motion is None or motion is False:
+            motion = None
+            if box:
+                raise ValueError("track_update_two_pass: box=True needs motion")
+        else:
+            given = {} if motion is True else dict(motion)
+            motion = dict(std_pos=given.pop("std_pos", 1.0 / 20), std_vel=given.pop("std_vel", 1.0 / 160), std_meas=given.pop("std_meas", 1.0 / 20))
+            if given:
+                raise ValueError("track_update_two_pass: motion takes std_pos, std_vel and std_meas, not %s" % sorted(given))
+        second = dict(high_conf=high_conf, low_conf=low_conf, match_thres_low=match_thres_low, tracked_only=tracked_only)
+        return self._track_update("track_update_two_pass", motion, box, dets, count, streams, state, max_tracks, match_thres, class_aware, init_conf,
+                                  max_misses, confirm_hits, fresh, out, second=second, passes=passes)
+
     def track_update_motion(self, dets, count, streams, state, max_tracks, match_thres=0.3, class_aware=True, init_conf=0.0, max_misses=30,
                             confirm_hits=3, std_pos=1.0 / 20, std_vel=1.0 / 160, std_meas=1.0 / 20, fresh=False, box=False, out=None):
         """track_update with a motion model (include/yfv2.h yfv2_track_update_motion): every track carries a
@@ -521,8 +544,8 @@ class Engine:
                                   max_misses, confirm_hits, fresh, out)
 
     def _track_update(self, name, motion, box, dets, count, streams, state, max_tracks, match_thres, class_aware, init_conf, max_misses, confirm_hits,
-                      fresh, out):
-        """the checks and the call of both forms; motion: None or the three stds"""
+                      fresh, out, second=None, passes=False):
+        """the checks and the call of every form; motion: None or the three stds; second: None or the two-pass form's four values"""
         if (not torch.is_tensor(dets) or dets.dim() != 3 or dets.shape[2] != 6 or dets.dtype != torch.float32 or dets.device != self.device
                 or not dets.is_contiguous()):
             raise ValueError(name + ": dets must be contiguous fp32 (B,R,6) on %s" % (self.device,))
@@ -540,8 +563,9 @@ class Engine:
                 or not state.is_contiguous()):
             raise ValueError(name + ": state must be contiguous int32 (S,%d) on %s" % (words, self.device))
         S = int(state.shape[0])
-        shapes = ((B, R), (B, R)) + (((B, R, 6), (B, R), (B,)) if fresh else ()) + (((B, R, 4),) if box else ())
-        dtypes = (torch.int32, torch.int32) + ((torch.float32, torch.int32, torch.int32) if fresh else ()) + ((torch.float32,) if box else ())
+        shapes = ((B, R), (B, R)) + (((B, R, 6), (B, R), (B,)) if fresh else ()) + (((B, R, 4),) if box else ()) + (((B, R),) if passes else ())
+        dtypes = ((torch.int32, torch.int32) + ((torch.float32, torch.int32, torch.int32) if fresh else ()) + ((torch.float32,) if box else ())
+                  + ((torch.int32,) if passes else ()))
         if out is None:
             out = tuple(torch.empty(sh, device=self.device, dtype=dt) for sh, dt in zip(shapes, dtypes))
         else:
@@ -556,11 +580,16 @@ class Engine:
         arr = (C.c_int32 * max(B, 1))(*streams)
         tid, hits = _ptr(out[0]), _ptr(out[1])
         fr = [_ptr(t) for t in out[2:5]] if fresh else [None] * 3
-        if motion is None:
+        mo = None if motion is None else _lib.TrackMotion(float(motion["std_pos"]), float(motion["std_vel"]), float(motion["std_meas"]))
+        if second is not None:
+            se = _lib.TrackSecond(float(second["high_conf"]), float(second["low_conf"]), float(second["match_thres_low"]), 1 if second["tracked_only"] else 0)
+            check(_lib.lib().yfv2_track_update_two_pass(self._h, _ptr(dets), _ptr(count), R, B, arr, _ptr(state), S, C.byref(rule),
+                                                        None if mo is None else C.byref(mo), C.byref(se), tid, hits, _ptr(out[-1]) if passes else None,
+                                                        _ptr(out[5 if fresh else 2]) if box else None, *fr, _stream(self.device)), self._h)
+        elif motion is None:
             check(_lib.lib().yfv2_track_update(self._h, _ptr(dets), _ptr(count), R, B, arr, _ptr(state), S, C.byref(rule), tid, hits, *fr, _stream(self.device)),
                   self._h)
         else:
-            mo = _lib.TrackMotion(float(motion["std_pos"]), float(motion["std_vel"]), float(motion["std_meas"]))
             check(_lib.lib().yfv2_track_update_motion(self._h, _ptr(dets), _ptr(count), R, B, arr, _ptr(state), S, C.byref(rule), C.byref(mo), tid, hits,
                                                       _ptr(out[-1]) if box else None, *fr, _stream(self.device)), self._h)
         return out

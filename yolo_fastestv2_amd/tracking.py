@@ -10,22 +10,36 @@ hands back exactly the rows whose track was confirmed in this frame, in the (det
 With motion=True (or a dict of std_pos, std_vel, std_meas) every track carries a constant-velocity Kalman filter per coordinate
 (yfv2_track_update_motion): rows are matched against the box the filter predicts, so an object hidden for a few
 frames keeps its id.
+
+With two_pass=True (or a dict of high_conf, low_conf, match_thres_low, tracked_only) there are two association passes
+(yfv2_track_update_two_pass): detect at a LOW threshold; rows with conf >= high_conf are matched first, the rows
+below it are offered only to the tracks still unmatched and start no track, so an object whose score dips for a few frames keeps its
+id and no spurious row becomes a track.  It combines with motion:
+
+    tr = Tracker(engine, streams=256, two_pass=True, init_conf=0.6)
+    dets, idx, count = engine.detect_frames(frames, 0.1, 0.4)                            # low_conf, iou
+    track_id, track_hits, fresh_dets, fresh_src, fresh_count, track_pass = tr.update(dets, count, fresh=True, passes=True)
 """
 import torch
 
 HEADER_WORDS, SLOT_WORDS = 8, 10
 MOTION_SLOT_WORDS, FILTER_WORD = 32, 10          # the motion form's slot; its filters: words 10..29, cx, cy, w, h as x, v, p00, p01, p11
 MOTION_DEFAULTS = dict(std_pos=1.0 / 20, std_vel=1.0 / 160, std_meas=1.0 / 20)
+TWO_PASS_DEFAULTS = dict(high_conf=0.5, low_conf=0.1, match_thres_low=0.5, tracked_only=True)
 HEADER_FIELDS = ("issued", "live", "frames", "births", "deaths", "dropped")
 
 
 class Tracker:
-    def __init__(self, engine, streams, max_tracks=64, match_thres=0.3, class_aware=True, init_conf=0.0, max_misses=30, confirm_hits=3, motion=None):
+    def __init__(self, engine, streams, max_tracks=64, match_thres=0.3, class_aware=True, init_conf=0.0, max_misses=30, confirm_hits=3, motion=None,
+                 two_pass=None):
         """engine: the Engine whose device and stream the updates run on; streams: S, the number of video streams; max_tracks:
         slots per stream (1..1024).  An edge between a row and a track needs IoU > match_thres (and equal classes if class_aware);
         an unmatched row with conf >= init_conf starts a track; a track dies at its (max_misses + 1)-th consecutive miss; a row is
         fresh in the frame in which its track's hits reach confirm_hits.  motion: None - the IoU is taken with the track's last box;
-        True or a dict with any of std_pos, std_vel, std_meas - with the box its filter predicts.  The rule, bit for bit:
+        True or a dict with any of std_pos, std_vel, std_meas - with the box its filter predicts.  two_pass: None - one association
+        pass over every row; True or a dict with any of high_conf, low_conf, match_thres_low, tracked_only - rows with conf >=
+        high_conf first, then the rows down to low_conf against the tracks still unmatched (tracked_only: those matched in their
+        last frame) with IoU > match_thres_low; only a row with conf >= high_conf starts a track.  The rule, bit for bit:
         include/yfv2.h."""
         self.engine = engine
         self.streams, self.max_tracks = int(streams), int(max_tracks)
@@ -40,18 +54,32 @@ class Tracker:
             if set(given) - set(MOTION_DEFAULTS):
                 raise ValueError("Tracker: motion takes std_pos, std_vel and std_meas, not %s" % sorted(set(given) - set(MOTION_DEFAULTS)))
             self.motion = {k: float(given.get(k, v)) for k, v in MOTION_DEFAULTS.items()}
+        if two_pass is None or two_pass is False:
+            self.two_pass = None
+        else:
+            given = {} if two_pass is True else dict(two_pass)
+            if set(given) - set(TWO_PASS_DEFAULTS):
+                raise ValueError("Tracker: two_pass takes high_conf, low_conf, match_thres_low and tracked_only, not %s"
+                                 % sorted(set(given) - set(TWO_PASS_DEFAULTS)))
+            self.two_pass = {k: type(v)(given.get(k, v)) for k, v in TWO_PASS_DEFAULTS.items()}
         self.slot_words = SLOT_WORDS if self.motion is None else MOTION_SLOT_WORDS
         self.state = torch.zeros((self.streams, HEADER_WORDS + self.slot_words * self.max_tracks), dtype=torch.int32, device=engine.device)
 
-    def update(self, dets, count, streams=None, fresh=False, out=None, box=False):
+    def update(self, dets, count, streams=None, fresh=False, out=None, box=False, passes=False):
         """dets (B, R, 6) fp32 / count (B) int32 on the device; streams: the stream of each frame, B distinct indices (None: frame b
         is stream b).  Returns (track_id, track_hits) and, with fresh=True, (.., fresh_dets, fresh_src, fresh_count); with box=True
-        (the motion form only) track_box (B, R, 4), the filtered corners of each row's track, comes last."""
+        (the motion form only) track_box (B, R, 4), the filtered corners of each row's track, comes after them; with passes=True (a
+        two-pass tracker only) track_pass (B, R) int32 - 1: matched in the first pass or born, 2: matched in the second - comes last."""
         if streams is None:
             streams = range(int(dets.shape[0]))
+        if box and self.motion is None:
+            raise ValueError("Tracker.update: box=True needs a tracker with a motion model")
+        if passes and self.two_pass is None:
+            raise ValueError("Tracker.update: passes=True needs a tracker with two_pass")
+        if self.two_pass is not None:
+            return self.engine.track_update_two_pass(dets, count, streams, self.state, self.max_tracks, motion=self.motion, fresh=fresh, box=box,
+                                                     passes=passes, out=out, **self.rule, **self.two_pass)
         if self.motion is None:
-            if box:
-                raise ValueError("Tracker.update: box=True needs a tracker with a motion model")
             return self.engine.track_update(dets, count, streams, self.state, self.max_tracks, fresh=fresh, out=out, **self.rule)
         return self.engine.track_update_motion(dets, count, streams, self.state, self.max_tracks, fresh=fresh, box=box, out=out, **self.rule, **self.motion)
 
@@ -74,8 +102,10 @@ class Tracker:
         return out
 
     def header(self, stream):
-        """The stream's counters as a dict of ints: issued, live, frames, births, deaths, dropped (waits for the device)."""
-        return dict(zip(HEADER_FIELDS, (int(v) for v in self.state[int(stream), :len(HEADER_FIELDS)].tolist())))
+        """The stream's counters as a dict of ints: issued, live, frames, births, deaths, dropped and, on a two-pass tracker, second,
+        the matches made in the second pass (waits for the device)."""
+        fields = HEADER_FIELDS + (("second",) if self.two_pass is not None else ())
+        return dict(zip(fields, (int(v) for v in self.state[int(stream), :len(fields)].tolist())))
 
     def reset(self, stream=None):
         """Forget every track of one stream, or of all of them (ids start again at 1)."""
