@@ -405,6 +405,70 @@ YFV2_API int yfv2_crop_detections_yuv(yfv2_handle h, const yfv2_frame_yuv* frame
                                       uint8_t* crops, int32_t* crop_src, int32_t* crop_rect, int32_t* crop_offset, int32_t* crop_skipped,
                                       int32_t cap, void* stream);
 
+/* ---- second-stage crops as network input: fp32 / fp16 NCHW, normalised, letterboxed, in the same launch ----
+ * replaces, behind yfv2_crop_detections_*: permute(0, 3, 1, 2).float().div(255).sub(mean).div(std), the channel flip and the cast
+ * to half that every classifier or re-identification network in a cascade asks for, and adds the aspect-preserving form.  The
+ * entry points below do everything yfv2_crop_detections_u8 / _yuv do - same frames, dets, count, R and yfv2_crop_rule, the same
+ * crop_src, crop_rect, crop_offset and crop_skipped from the same plan launches, the same counted launch over cap - and write, in
+ * place of the uint8 crops, out (cap, 3, out_h, out_w).  No uint8 crop exists in memory.
+ * THE RULE, bit for bit (tests/crop_tensors_model.py restates it in numpy; the library's functions of it are
+ * yfv2_crop_letterbox_inner and yfv2_crop_tensor_f32 / _f16, yfv2_internal.h, which the kernels and the two host functions below call).
+ *   1 selection  candidates, skipped rows, rectangles, selection and numbering are yfv2_crop_detections_*'s, above.
+ *   2 geometry   integers, int64 intermediates, / = floor division.  A rectangle of cw x ch pixels, output (H, W) = (out_h, out_w):
+ *                  letterbox = 0                   iw = W, ih = H, ox0 = oy0 = 0                       (the stretch of the uint8 crops)
+ *                  letterbox = 1, W * ch <= H * cw iw = W, ih = max(1, (2 * ch * W + cw) / (2 * cw))   (the box is the wider)
+ *                  letterbox = 1, otherwise        ih = H, iw = max(1, (2 * cw * H + ch) / (2 * ch))
+ *                and with letterbox ox0 = (W - iw) >> 1, oy0 = (H - ih) >> 1: the aspect-preserving size rounded half up, never
+ *                larger than the output, centred with the odd pixel of a margin on the right / below.
+ *   3 bytes      the byte image, which is never written: a (H, W, 3) canvas of `fill` (B, G, R); its rows oy0 .. oy0 + ih, columns
+ *                ox0 .. ox0 + iw hold the bilinear resize of the rectangle's view to (ih, iw) - yfv2_resize_frames_u8's arithmetic
+ *                with the scales 1 / (iw / cw), 1 / (ih / ch).  With letterbox = 0 it is yfv2_crop_detections_*'s crop, byte for byte.
+ *   4 value      out[k][c][y][x] comes from byte a = image[y][x][rgb ? 2 - c : c]:
+ *                    x = fl32(float(a) / 255.f)
+ *                    v = fl32(fl32(x - mean[c]) / std[c])
+ *                every operation rounded to fp32 on its own - no fused multiply-add, IEEE-correct divisions - which is torchvision's
+ *                ToTensor followed by Normalize on the host; mean = 0, std = 1 is plain / 255.  For YFV2_F16 v is rounded once more,
+ *                to binary16, to nearest even (overflow gives an infinity).  Fill pixels go through the same lines. */
+#define YFV2_F32 0
+#define YFV2_F16 1
+typedef struct yfv2_crop_tensor {
+  int32_t dtype;             /* YFV2_F32 or YFV2_F16 */
+  int32_t rgb;               /* 0: planes B, G, R (the frame's order); 1: planes R, G, B */
+  float mean[3], std[3];     /* by OUTPUT plane; finite, std > 0 */
+  int32_t letterbox;         /* 0: stretch; 1: keep the rectangle's aspect ratio, centre, fill the rest */
+  uint8_t fill[3];           /* B, G, R: the frame's order, whatever rgb is */
+} yfv2_crop_tensor;
+
+/* Step 2 for one rectangle: host only, no handle, no device.  inner = ox0, oy0, iw, ih; 1 <= iw <= out_w, 1 <= ih <= out_h.
+ * YFV2_ERR_ARG for a NULL pointer, a size < 1 or letterbox outside 0..1.  It calls the function the plan kernel calls. */
+YFV2_API int yfv2_crop_letterbox(int32_t cw, int32_t ch, int32_t out_h, int32_t out_w, int32_t letterbox, int32_t inner[4]);
+
+/* Step 4 for one byte: host only.  Writes the fp32 value and the bits of its binary16 form (either pointer may be NULL).
+ * YFV2_ERR_ARG for a outside 0..255, a mean that is not finite or a std that is not finite and > 0. */
+YFV2_API int yfv2_crop_tensor_value(int32_t a, float mean, float std, float* f32, uint16_t* f16_bits);
+
+/* out: DEVICE (cap, 3, out_h, out_w) fp32 or fp16, 16-byte aligned; everything else as yfv2_crop_detections_u8.  Nothing is written
+ * beyond slot min(total, cap).  out_w is a multiple of 4 as for the uint8 crops; an fp16 row is stored 16 bytes at a time when
+ * out_w is a multiple of 8 and 8 bytes at a time otherwise.  Enqueue only, like yfv2_crop_detections_u8: two plan launches, one
+ * resize launch; the descriptor table is the same handle-owned workspace.  Checked before anything is enqueued (YFV2_ERR_ARG with
+ * a message): everything yfv2_crop_detections_u8 checks (out in place of crops: NULL, or not 16-byte aligned); tensor NULL; dtype,
+ * rgb or letterbox out of range; a mean that is not finite; a std that is not finite or not > 0; the width limit of the frames,
+ * which is lower than the crops': the row is staged as three fp32 or fp16 planes - (160 KiB - 12 out_w) / 6 - 6 pixels for fp32,
+ * (160 KiB - 6 out_w) / 6 - 6 for fp16. */
+YFV2_API int yfv2_crop_tensors_u8(yfv2_handle h, const yfv2_frame* frames /* HOST, B */, int32_t B,
+                                  const float* dets /* (B,R,6) */, const int32_t* count /* (B) */, int32_t R, const yfv2_crop_rule* rule,
+                                  const yfv2_crop_tensor* tensor, void* out /* (cap,3,out_h,out_w) */, int32_t* crop_src /* (cap) */,
+                                  int32_t* crop_rect /* (cap,4) */, int32_t* crop_offset /* (B+1) */, int32_t* crop_skipped /* (B) or NULL */,
+                                  int32_t cap, void* stream);
+
+/* The same for YUV 4:2:0 frames: bit-identical to yfv2_crop_tensors_u8 on the frames converted with the integer colour formula.
+ * Checks: as above with everything yfv2_resize_frames_yuv checks per frame; the width limit is the widest frame whose two luma rows,
+ * chroma rows (each rounded to 16 bytes) and three planes fit 160 KiB of LDS, never above yfv2_crop_detections_yuv's. */
+YFV2_API int yfv2_crop_tensors_yuv(yfv2_handle h, const yfv2_frame_yuv* frames /* HOST, B */, int32_t B,
+                                   const float* dets, const int32_t* count, int32_t R, const yfv2_crop_rule* rule,
+                                   const yfv2_crop_tensor* tensor, void* out, int32_t* crop_src, int32_t* crop_rect, int32_t* crop_offset,
+                                   int32_t* crop_skipped, int32_t cap, void* stream);
+
 /* ---- identity across frames: a per-stream IoU tracker on the device ----
  * The inputs of the entry points above are video: many streams, one frame of each per batch.  A tracker gives every detection an
  * identity that lasts across frames, so that a second stage runs once per object: its state lives on the device, one launch updates

@@ -90,6 +90,15 @@ class CropRule(C.Structure):
                 ("classes", C.POINTER(C.c_int32)), ("n_classes", C.c_int32)]
 
 
+class CropTensor(C.Structure):
+    """yfv2_crop_tensor (include/yfv2.h): dtype, plane order, mean / std, letterbox and fill of crops written as a network's input."""
+    _fields_ = [("dtype", C.c_int32), ("rgb", C.c_int32), ("mean", C.c_float * 3), ("std", C.c_float * 3), ("letterbox", C.c_int32),
+                ("fill", C.c_uint8 * 3)]
+
+
+F32, F16 = 0, 1
+
+
 class TrackRule(C.Structure):
     """yfv2_track_rule (include/yfv2.h): the parameters of the per-stream IoU tracker."""
     _fields_ = [("max_tracks", C.c_int32), ("match_thres", C.c_double), ("class_aware", C.c_int32), ("init_conf", C.c_float),
@@ -183,6 +192,12 @@ _PROTOTYPES = {
                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "yfv2_crop_detections_yuv": (C.c_int, [C.c_void_p, C.POINTER(FrameYuv), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(CropRule),
                                            C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "yfv2_crop_letterbox": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]),
+    "yfv2_crop_tensor_value": (C.c_int, [C.c_int32, C.c_float, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_uint16)]),
+    "yfv2_crop_tensors_u8": (C.c_int, [C.c_void_p, C.POINTER(Frame), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(CropRule),
+                                       C.POINTER(CropTensor), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "yfv2_crop_tensors_yuv": (C.c_int, [C.c_void_p, C.POINTER(FrameYuv), C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(CropRule),
+                                        C.POINTER(CropTensor), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "yfv2_track_state_words": (C.c_int64, [C.c_int32]),
     "yfv2_track_iou": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "yfv2_track_update": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_int32,

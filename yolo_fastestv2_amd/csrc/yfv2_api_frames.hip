@@ -3,10 +3,13 @@
 // Frames come in two kinds, yfv2_frame (packed B, G, R) and yfv2_frame_yuv (4:2:0 planes).  Each kind is described once
 // (BgrFrames, YuvFrames: what differs); check_frames<Kind> turns a caller's batch into a FrameBatch, enqueue_resize resizes
 // one, enqueue_train_batch makes the training batch of one, and resize_frames / train_batch_frames / detect_frames /
-// crop_detections / detect_tiled are one template each.  The extern "C" functions pass their names.
+// crop_detections (yfv2_crop_tensors_* too: the same template with a yfv2_crop_tensor) / detect_tiled are one template each.  The
+// extern "C" functions pass their names.
 // yfv2_track_update (the per-stream tracker behind the detect calls) takes rows, not frames; its checks and its launch are here too.
 #include <algorithm>
 #include <cmath>
+#include <cstring>
+#include <type_traits>
 
 #include "yfv2_ctx.h"
 
@@ -235,10 +238,21 @@ static int detect_frames(yfv2_handle h, const char* what, const typename Kind::F
 constexpr int CROP_MAX_R = 4096;
 constexpr double CROP_MAX_PAD = 16.0;
 
-template <class Kind>
+// yfv2_crop_tensors_u8 / _yuv are the same template with `tensor` given: `crops` is then the fp32 / fp16 tensor,
+// 16-byte aligned, the frames are held to the tensor rows' width limit (Kind below) and the plan and the resize launch are the
+// tensor kinds'.  tensor == nullptr is yfv2_crop_detections_*, check for check and launch for launch what it was.
+template <class Base, bool Half>
+struct TensorFrames : Base {
+  static int max_width(int W) {
+    if constexpr (std::is_same_v<Base, BgrFrames>) return yfv2_crop_tensor_max_width(W, Half);
+    else return yfv2_crop_tensor_yuv_max_width(W, Half);
+  }
+};
+
+template <class Kind, class Limit = Kind>
 static int crop_detections(yfv2_handle h, const char* what, const typename Kind::Frame* frames, int32_t B, const float* dets, const int32_t* count, int32_t R,
-                           const yfv2_crop_rule* rule, uint8_t* crops, int32_t* crop_src, int32_t* crop_rect, int32_t* crop_offset, int32_t* crop_skipped,
-                           int32_t cap, void* stream) {
+                           const yfv2_crop_rule* rule, void* crops, int32_t* crop_src, int32_t* crop_rect, int32_t* crop_offset, int32_t* crop_skipped,
+                           int32_t cap, void* stream, const yfv2_crop_tensor* tensor = nullptr) {
   const std::string w_ = what;
   if (!h) return fail(nullptr, YFV2_ERR_ARG, "null handle");
   if (!frames || !dets || !count || !rule || !crops || !crop_src || !crop_rect || !crop_offset) return fail(h, YFV2_ERR_ARG, w_ + ": null pointer");
@@ -248,12 +262,20 @@ static int crop_detections(yfv2_handle h, const char* what, const typename Kind:
   if (q.out_h < 1) return fail(h, YFV2_ERR_ARG, w_ + ": out_h must be >= 1");
   if (q.out_w < 4 || q.out_w % 4 != 0) return fail(h, YFV2_ERR_ARG, w_ + ": out_w must be a multiple of 4, at least 4");
   if (cap < 1 || (long long)cap * q.out_h > 0x7fffffffll) return fail(h, YFV2_ERR_ARG, w_ + ": cap must be >= 1 and cap * out_h at most 2^31 - 1");
-  if ((reinterpret_cast<uintptr_t>(crops) & 3) != 0) return fail(h, YFV2_ERR_ARG, w_ + ": crops must be 4-byte aligned");
+  if (!tensor && (reinterpret_cast<uintptr_t>(crops) & 3) != 0) return fail(h, YFV2_ERR_ARG, w_ + ": crops must be 4-byte aligned");
+  if (tensor) {
+    const yfv2_crop_tensor& t = *tensor;
+    if ((reinterpret_cast<uintptr_t>(crops) & 15) != 0) return fail(h, YFV2_ERR_ARG, w_ + ": out must be 16-byte aligned");
+    if (t.rgb < 0 || t.rgb > 1 || t.letterbox < 0 || t.letterbox > 1) return fail(h, YFV2_ERR_ARG, w_ + ": rgb and letterbox must be 0 or 1");
+    for (int c = 0; c < 3; ++c)
+      if (!std::isfinite(t.mean[c]) || !std::isfinite(t.std[c]) || !(t.std[c] > 0.f))
+        return fail(h, YFV2_ERR_ARG, w_ + ": plane " + std::to_string(c) + ": mean must be finite and std finite and > 0");
+  }
   if (!std::isfinite(q.pad_x) || !std::isfinite(q.pad_y) || q.pad_x < 0.f || q.pad_y < 0.f || q.pad_x > CROP_MAX_PAD || q.pad_y > CROP_MAX_PAD)
     return fail(h, YFV2_ERR_ARG, w_ + ": pad_x and pad_y must be finite numbers in [0, 16]");
   if (q.max_per_frame < 1) return fail(h, YFV2_ERR_ARG, w_ + ": max_per_frame must be >= 1");
   if (q.n_classes < 0 || (q.n_classes > 0 && !q.classes)) return fail(h, YFV2_ERR_ARG, w_ + ": n_classes < 0, or classes NULL with n_classes > 0");
-  CropPlanArgs a{};
+  CropTensorPlanArgs a{};
   if (!q.classes) {
     for (int i = 0; i < 8; ++i) a.classes[i] = i < 7 ? 0xffffffffu : 0x7fffffffu;     // classes 0..254
   } else {
@@ -264,32 +286,97 @@ static int crop_detections(yfv2_handle h, const char* what, const typename Kind:
     }
   }
   FrameBatch fb;
-  if (int rc = check_frames<Kind>(h, what, frames, B, fb, q.out_h, q.out_w)) return rc;
+  if (int rc = check_frames<Limit>(h, what, frames, B, fb, q.out_h, q.out_w)) return rc;
   if ((long long)B * R > 0x7fffffffll) return fail(h, YFV2_ERR_ARG, w_ + ": B * R above 2^31 - 1");
   DeviceGuard guard(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  // the workspace: n_sel (max_batch int32, rounded to 16 bytes), the table's head, the table: cap entries of the wider kind
-  const size_t n_bytes = (sizeof(int32_t) * (size_t)h->cfg.max_batch + 15) & ~(size_t)15;
+  // the workspace: n_sel (max_batch int32, rounded to 16 bytes), the table's head - the tensor launches' constants and the live
+  // count, the count last - and the table: cap entries of the widest kind
+  const size_t n_bytes = ((sizeof(int32_t) * (size_t)h->cfg.max_batch + 15) & ~(size_t)15) + sizeof(CropTensorHead) - sizeof(CountedHead);
   const int ws_cap = std::max(cap, h->crop_cap);
-  if (int rc = h->crop_ws.reserve(h, n_bytes + sizeof(CountedHead) + sizeof(CropFrameYuv) * (size_t)ws_cap, true)) return rc;
+  if (int rc = h->crop_ws.reserve(h, n_bytes + sizeof(CountedHead) + sizeof(TensorFrameYuv) * (size_t)ws_cap, true)) return rc;
   h->crop_cap = ws_cap;
   char* base = h->crop_ws.as<char>();
   a.dets = dets; a.count = count; a.B = B; a.R = R; a.out_h = q.out_h; a.out_w = q.out_w; a.pad_x = q.pad_x; a.pad_y = q.pad_y;
   a.max_per_frame = q.max_per_frame; a.n_sel = reinterpret_cast<int32_t*>(base); a.src = crop_src; a.rect = crop_rect; a.offset = crop_offset;
   a.skipped = crop_skipped; a.cap = cap; a.head = reinterpret_cast<CountedHead*>(base + n_bytes);
   void* table = base + n_bytes + sizeof(CountedHead);
+  if (tensor) {
+    const bool half = tensor->dtype == YFV2_F16;
+    for (int c = 0; c < 3; ++c) { a.p.mean[c] = tensor->mean[c]; a.p.std[c] = tensor->std[c]; }
+    a.p.fill = (uint32_t)tensor->fill[0] | (uint32_t)tensor->fill[1] << 8 | (uint32_t)tensor->fill[2] << 16;
+    a.p.rgb = tensor->rgb; a.letterbox = tensor->letterbox;
+    if (fb.yuv.empty())
+      return submit_frames(h, fb.t, h->d_frames, B, s, [&](const ResizeFrame* d) {
+        yfv2_launch_crop_tensor_plan(a, d, static_cast<TensorFrame*>(table), s);
+        yfv2_launch_crop_tensors(static_cast<const TensorFrame*>(table), cap, fb.max_w, crops, half, q.out_h, q.out_w, s);
+      });
+    return submit_frames(h, fb.yuv, h->d_frames_yuv, B, s, [&](const ResizeFrameYuv* d) {
+      yfv2_launch_crop_tensor_plan_yuv(a, d, static_cast<TensorFrameYuv*>(table), s);
+      yfv2_launch_crop_tensors_yuv(static_cast<const TensorFrameYuv*>(table), cap, fb.max_w, crops, half, q.out_h, q.out_w, s);
+    });
+  }
+  uint8_t* crops_u8 = static_cast<uint8_t*>(crops);
   if (fb.yuv.empty())
     return submit_frames(h, fb.t, h->d_frames, B, s, [&](const ResizeFrame* d) {
       yfv2_launch_crop_plan(a, d, static_cast<CropFrame*>(table), s);
-      yfv2_launch_resize_crops(static_cast<const CropFrame*>(table), cap, fb.max_w, crops, q.out_h, q.out_w, s);
+      yfv2_launch_resize_crops(static_cast<const CropFrame*>(table), cap, fb.max_w, crops_u8, q.out_h, q.out_w, s);
     });
   return submit_frames(h, fb.yuv, h->d_frames_yuv, B, s, [&](const ResizeFrameYuv* d) {
     yfv2_launch_crop_plan_yuv(a, d, static_cast<CropFrameYuv*>(table), s);
-    yfv2_launch_resize_crops_yuv(static_cast<const CropFrameYuv*>(table), cap, fb.max_w, crops, q.out_h, q.out_w, s);
+    yfv2_launch_resize_crops_yuv(static_cast<const CropFrameYuv*>(table), cap, fb.max_w, crops_u8, q.out_h, q.out_w, s);
   });
 }
 
+// the tensor entry points: the handle, the struct and its dtype, which picks the width limit; then the template above
+template <class Kind>
+static int crop_tensors(yfv2_handle h, const char* what, const typename Kind::Frame* frames, int32_t B, const float* dets, const int32_t* count, int32_t R,
+                        const yfv2_crop_rule* rule, const yfv2_crop_tensor* tensor, void* out, int32_t* crop_src, int32_t* crop_rect, int32_t* crop_offset,
+                        int32_t* crop_skipped, int32_t cap, void* stream) {
+  if (!h) return fail(nullptr, YFV2_ERR_ARG, "null handle");
+  if (!tensor) return fail(h, YFV2_ERR_ARG, std::string(what) + ": null pointer");
+  if (tensor->dtype == YFV2_F32)
+    return crop_detections<Kind, TensorFrames<Kind, false>>(h, what, frames, B, dets, count, R, rule, out, crop_src, crop_rect, crop_offset, crop_skipped, cap, stream, tensor);
+  if (tensor->dtype == YFV2_F16)
+    return crop_detections<Kind, TensorFrames<Kind, true>>(h, what, frames, B, dets, count, R, rule, out, crop_src, crop_rect, crop_offset, crop_skipped, cap, stream, tensor);
+  return fail(h, YFV2_ERR_ARG, std::string(what) + ": dtype must be YFV2_F32 or YFV2_F16");
+}
+
 extern "C" {
+
+int yfv2_crop_letterbox(int32_t cw, int32_t ch, int32_t out_h, int32_t out_w, int32_t letterbox, int32_t inner[4]) {
+  if (!inner) return fail(nullptr, YFV2_ERR_ARG, "yfv2_crop_letterbox: null pointer");
+  if (cw < 1 || ch < 1 || out_h < 1 || out_w < 1) return fail(nullptr, YFV2_ERR_ARG, "yfv2_crop_letterbox: cw, ch, out_h and out_w must be >= 1");
+  if (letterbox < 0 || letterbox > 1) return fail(nullptr, YFV2_ERR_ARG, "yfv2_crop_letterbox: letterbox must be 0 or 1");
+  int in[4];
+  yfv2_crop_letterbox_inner(cw, ch, out_h, out_w, letterbox, in);
+  for (int i = 0; i < 4; ++i) inner[i] = in[i];
+  return YFV2_OK;
+}
+
+int yfv2_crop_tensor_value(int32_t a, float mean, float std, float* f32, uint16_t* f16_bits) {
+  if (a < 0 || a > 255) return fail(nullptr, YFV2_ERR_ARG, "yfv2_crop_tensor_value: a must be in 0..255");
+  if (!std::isfinite(mean) || !std::isfinite(std) || !(std > 0.f))
+    return fail(nullptr, YFV2_ERR_ARG, "yfv2_crop_tensor_value: mean must be finite and std finite and > 0");
+  if (f32) *f32 = yfv2_crop_tensor_f32(a, mean, std);
+  if (f16_bits) {
+    const _Float16 v = yfv2_crop_tensor_f16(a, mean, std);
+    std::memcpy(f16_bits, &v, 2);
+  }
+  return YFV2_OK;
+}
+
+int yfv2_crop_tensors_u8(yfv2_handle h, const yfv2_frame* frames, int32_t B, const float* dets, const int32_t* count, int32_t R, const yfv2_crop_rule* rule,
+                         const yfv2_crop_tensor* tensor, void* out, int32_t* crop_src, int32_t* crop_rect, int32_t* crop_offset, int32_t* crop_skipped,
+                         int32_t cap, void* stream) {
+  return crop_tensors<BgrFrames>(h, "yfv2_crop_tensors_u8", frames, B, dets, count, R, rule, tensor, out, crop_src, crop_rect, crop_offset, crop_skipped, cap, stream);
+}
+
+int yfv2_crop_tensors_yuv(yfv2_handle h, const yfv2_frame_yuv* frames, int32_t B, const float* dets, const int32_t* count, int32_t R, const yfv2_crop_rule* rule,
+                          const yfv2_crop_tensor* tensor, void* out, int32_t* crop_src, int32_t* crop_rect, int32_t* crop_offset, int32_t* crop_skipped,
+                          int32_t cap, void* stream) {
+  return crop_tensors<YuvFrames>(h, "yfv2_crop_tensors_yuv", frames, B, dets, count, R, rule, tensor, out, crop_src, crop_rect, crop_offset, crop_skipped, cap, stream);
+}
 
 int yfv2_crop_rect(const float box[4], int32_t frame_h, int32_t frame_w, float pad_x, float pad_y, int32_t rect[4]) {
   if (!box || !rect) return fail(nullptr, YFV2_ERR_ARG, "yfv2_crop_rect: null pointer");

@@ -11,6 +11,8 @@
 // a handful of fp64 operations per row, cheaper than carrying its result through memory - and writes src, rect and the crop's
 // descriptor at slot k.  Workgroup 0 also writes offset[B] and the table head's live count min(total, cap), which is what the resize
 // launch's workgroups test.  Every output is an integer or a double the rule defines; nothing is accumulated where order could show.
+// The same two launches serve yfv2_crop_tensors_*  through two more kinds, whose descriptor carries the letterbox's
+// inner rectangle; COUNT and WRITE are what they are for the crops.
 // Built with -ffp-contract=off like every unit whose doubles must round as written (the rule carries its own pragma as well).
 #include "../../include/yfv2.h"
 #include "yfv2_device.h"
@@ -21,6 +23,7 @@ constexpr int CP_THREADS = 256;
 struct CropBgr {
   using Frame = ResizeFrame;
   using Out = CropFrame;
+  using Args = CropPlanArgs;
   static __device__ __forceinline__ void crop(const Frame& f, const int (&rc)[4], int H, int W, Out& o) {
     o.data = f.data + (long long)rc[1] * f.pitch + 3ll * rc[0];
     o.pitch = f.pitch;
@@ -32,6 +35,7 @@ struct CropBgr {
 struct CropYuv {
   using Frame = ResizeFrameYuv;
   using Out = CropFrameYuv;
+  using Args = CropPlanArgs;
   static __device__ __forceinline__ void crop(const Frame& f, const int (&rc)[4], int H, int W, Out& o) {
     static_cast<Frame&>(o) = f;
     yfv2_yuv_move(o, rc[0], rc[1]);
@@ -39,6 +43,26 @@ struct CropYuv {
     o.scale_x = yfv2_resize_scale(W, rc[2]); o.scale_y = yfv2_resize_scale(H, rc[3]);
   }
 };
+// ... and the two of the tensor launches (yfv2_crop_tensors_u8 / _yuv): the same view, resized to the INNER size
+// yfv2_crop_letterbox_inner gives it - (H, W) itself without letterbox - which the descriptor carries behind the crop's fields.
+// TENSOR: the write launch's workgroup 0 also leaves the call's constants in front of the table's head, where RowTensor reads them.
+template <class Base, class Desc>
+struct TensorKind {
+  using Frame = typename Base::Frame;
+  using Out = Desc;
+  using Args = CropTensorPlanArgs;
+  static constexpr bool TENSOR = true;
+  static __device__ __forceinline__ void crop(const Frame& f, const int (&rc)[4], const Args& a, Out& o) {
+    int in[4];
+    yfv2_crop_letterbox_inner(rc[2], rc[3], a.out_h, a.out_w, a.letterbox, in);
+    typename Base::Out view;
+    Base::crop(f, rc, in[3], in[2], view);
+    static_cast<typename Base::Out&>(o) = view;
+    o.ox0 = in[0]; o.oy0 = in[1]; o.iw = in[2]; o.ih = in[3];
+  }
+};
+using TensorBgr = TensorKind<CropBgr, TensorFrame>;
+using TensorYuv = TensorKind<CropYuv, TensorFrameYuv>;
 
 // a row passes iff its class column is a finite integer in 0..254 whose bit is set
 __device__ __forceinline__ bool crop_class_passes(float c, const uint32_t (&mask)[8]) {
@@ -48,7 +72,7 @@ __device__ __forceinline__ bool crop_class_passes(float c, const uint32_t (&mask
 }
 
 template <class Kind, bool WRITE>
-__global__ __launch_bounds__(CP_THREADS) void crop_plan_kernel(CropPlanArgs a, const typename Kind::Frame* __restrict__ frames, typename Kind::Out* __restrict__ table) {
+__global__ __launch_bounds__(CP_THREADS) void crop_plan_kernel(typename Kind::Args a, const typename Kind::Frame* __restrict__ frames, typename Kind::Out* __restrict__ table) {
   constexpr int WAVES = CP_THREADS / 64;
   __shared__ int s_sel[WAVES], s_skip[WAVES], s_sum[2];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -100,7 +124,8 @@ __global__ __launch_bounds__(CP_THREADS) void crop_plan_kernel(CropPlanArgs a, c
 #pragma unroll
         for (int i = 0; i < 4; ++i) a.rect[4 * k + i] = rc[i];
         typename Kind::Out o;
-        Kind::crop(f, rc, a.out_h, a.out_w, o);
+        if constexpr (requires { Kind::TENSOR; }) Kind::crop(f, rc, a, o);
+        else Kind::crop(f, rc, a.out_h, a.out_w, o);
         table[k] = o;
       }
     }
@@ -111,6 +136,8 @@ __global__ __launch_bounds__(CP_THREADS) void crop_plan_kernel(CropPlanArgs a, c
     if constexpr (WRITE) {
       a.offset[b] = first;
       if (b == 0) { a.offset[a.B] = total; a.head->live = min(total, a.cap); }
+      if constexpr (requires { Kind::TENSOR; })
+        if (b == 0) reinterpret_cast<CropTensorHead*>(a.head + 1)[-1].p = a.p;
     } else {
       a.n_sel[b] = min(taken, a.max_per_frame);
       if (a.skipped) a.skipped[b] = skipped;
@@ -119,10 +146,12 @@ __global__ __launch_bounds__(CP_THREADS) void crop_plan_kernel(CropPlanArgs a, c
 }
 
 template <class Kind>
-static void launch_crop_plan(const CropPlanArgs& a, const typename Kind::Frame* frames, typename Kind::Out* table, hipStream_t s) {
+static void launch_crop_plan(const typename Kind::Args& a, const typename Kind::Frame* frames, typename Kind::Out* table, hipStream_t s) {
   YFV2_LAUNCH((crop_plan_kernel<Kind, false>), dim3((unsigned)a.B), dim3(CP_THREADS), 0, s, a, frames, table);
   YFV2_LAUNCH((crop_plan_kernel<Kind, true>), dim3((unsigned)a.B), dim3(CP_THREADS), 0, s, a, frames, table);
 }
 
 void yfv2_launch_crop_plan(const CropPlanArgs& a, const ResizeFrame* frames, CropFrame* table, hipStream_t s) { launch_crop_plan<CropBgr>(a, frames, table, s); }
 void yfv2_launch_crop_plan_yuv(const CropPlanArgs& a, const ResizeFrameYuv* frames, CropFrameYuv* table, hipStream_t s) { launch_crop_plan<CropYuv>(a, frames, table, s); }
+void yfv2_launch_crop_tensor_plan(const CropTensorPlanArgs& a, const ResizeFrame* frames, TensorFrame* table, hipStream_t s) { launch_crop_plan<TensorBgr>(a, frames, table, s); }
+void yfv2_launch_crop_tensor_plan_yuv(const CropTensorPlanArgs& a, const ResizeFrameYuv* frames, TensorFrameYuv* table, hipStream_t s) { launch_crop_plan<TensorYuv>(a, frames, table, s); }

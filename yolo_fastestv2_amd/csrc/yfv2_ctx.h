@@ -125,9 +125,10 @@ struct yfv2_ctx {
   DeviceBlock tile_ws;
   int tile_cap_t = 0, tile_cap_f = 0;
   DeviceBlock tile_out;
-  // second-stage crops (yfv2_crop_detections_u8 / _yuv): max_batch int32 of per-frame selections, the counted table's head and
-  // crop_cap descriptors of the wider kind, which the plan launch writes and the resize launch reads.  Allocated by the first call
-  // (one device wait), grown - another wait - only by a call with a larger cap.
+  // second-stage crops (yfv2_crop_detections_u8 / _yuv, yfv2_crop_tensors_u8 / _yuv): max_batch int32 of per-frame selections, the
+  // counted table's head (CropTensorHead: the tensor launches' constants, then the live count) and crop_cap descriptors of the widest
+  // kind (TensorFrameYuv), which the plan launch writes and the resize launch reads.  Allocated by the first call (one device wait),
+  // grown - another wait - only by a call with a larger cap.
   DeviceBlock crop_ws;
   int crop_cap = 0;
   // the ncnn sample's path (yfv2_deploy_post / yfv2_detect_deploy_frames_u8).  deploy_word: int32 `dropped` of the last call, then

@@ -443,6 +443,61 @@ void yfv2_launch_crop_plan_yuv(const CropPlanArgs& a, const ResizeFrameYuv* fram
 // the resize of the live entries of a counted table into crops (cap, H, W, 3): grid cap * H, LDS for a source row of max_w pixels
 void yfv2_launch_resize_crops(const CropFrame* table, int cap, int max_w, unsigned char* crops, int H, int W, hipStream_t s);
 void yfv2_launch_resize_crops_yuv(const CropFrameYuv* table, int cap, int max_w, unsigned char* crops, int H, int W, hipStream_t s);
+// ---- second-stage crops as network input (yfv2_crop_tensors_u8 / _yuv): the same plan, the same resize body, the
+// row leaves as fp32 / fp16 planes.  THE TWO RULES of it, each written once: yfv2_crop_letterbox / yfv2_crop_tensor_value (host) and
+// the kernels (device) call these functions; include/yfv2.h states them for callers, tests/crop_tensors_model.py in numpy.
+// Where a cw x ch rectangle lands in the (H, W) output: inner = ox0, oy0, iw, ih.  Integers throughout, int64 intermediates.
+__host__ __device__ inline void yfv2_crop_letterbox_inner(int cw, int ch, int H, int W, int letterbox, int inner[4]) {
+  long long iw = W, ih = H;
+  if (letterbox) {
+    if ((long long)W * ch <= (long long)H * cw) ih = (2ll * ch * W + cw) / (2ll * cw);   // round-half-up of ch * W / cw, <= H
+    else iw = (2ll * cw * H + ch) / (2ll * ch);
+    if (ih < 1) ih = 1;
+    if (iw < 1) iw = 1;
+  }
+  inner[0] = letterbox ? (int)((W - iw) >> 1) : 0;
+  inner[1] = letterbox ? (int)((H - ih) >> 1) : 0;
+  inner[2] = (int)iw; inner[3] = (int)ih;
+}
+// What byte a becomes in a plane with (mean, std): two fp32 divisions and a subtraction, each rounded on its own - torchvision's
+// ToTensor then Normalize.  (__fdiv_rn: the device's IEEE-correct division whatever the unit's flags; the host's / is one.)
+__host__ __device__ inline float yfv2_crop_tensor_f32(int a, float mean, float std) {
+#pragma clang fp contract(off)
+#ifdef __HIP_DEVICE_COMPILE__
+  return __fdiv_rn(__fsub_rn(__fdiv_rn((float)a, 255.f), mean), std);
+#else
+  const float x = (float)a / 255.f;
+  const float d = x - mean;
+  return d / std;
+#endif
+}
+// ... and its binary16 form: one more rounding, to nearest even; overflow gives an infinity
+__host__ __device__ inline _Float16 yfv2_crop_tensor_f16(int a, float mean, float std) { return (_Float16)yfv2_crop_tensor_f32(a, mean, std); }
+// The descriptors of the tensor launches: the crop's counted descriptor with the inner rectangle behind it; scale_x / scale_y are
+// those of the INNER size (iw, ih), not of (H, W).  The call's constants travel in front of the table's CountedHead, written by
+// the plan's write launch: the descriptor load stays 16 bytes above the crop's, and the resize templates keep their signatures.
+struct CropTensorParams {
+  float mean[3], std[3];       // by OUTPUT plane
+  uint32_t fill;               // B | G << 8 | R << 16, the frame's byte order
+  int32_t rgb;                 // 1: plane c is byte channel 2 - c
+};
+struct CropTensorHead { CropTensorParams p; CountedHead head; };   // head last: entry 0 follows it, as in every counted table
+template <class D> struct Letterboxed : Counted<D> { int ox0, oy0, iw, ih; static constexpr bool LETTERBOX = true; };
+using TensorFrame = Letterboxed<ResizeFrame>;
+using TensorFrameYuv = Letterboxed<ResizeFrameYuv>;
+struct CropTensorPlanArgs : CropPlanArgs { CropTensorParams p; int letterbox; };   // the crop kinds' arguments stay what they were
+void yfv2_launch_crop_tensor_plan(const CropTensorPlanArgs& a, const ResizeFrame* frames, TensorFrame* table, hipStream_t s);
+void yfv2_launch_crop_tensor_plan_yuv(const CropTensorPlanArgs& a, const ResizeFrameYuv* frames, TensorFrameYuv* table, hipStream_t s);
+// LDS of one workgroup: the staging slots rounded to 16 bytes, three planes of W fp32 (half = false) or fp16 values; and the widest
+// frame that fits - (YFV2_LDS_FULL - 3 W e) / 6 - 6 for B, G, R frames (e = 4 or 2), walked for YUV frames.  Neither exceeds the
+// limit of yfv2_crop_detections_* at the same W.
+size_t yfv2_crop_tensor_lds_bytes(int SW, int W, bool half);
+int yfv2_crop_tensor_max_width(int W, bool half);
+size_t yfv2_crop_tensor_yuv_lds_bytes(int w, int W, bool half);
+int yfv2_crop_tensor_yuv_max_width(int W, bool half);
+// the live entries of a tensor table into out (cap, 3, H, W), fp32 or fp16, 16-byte aligned: grid cap * H
+void yfv2_launch_crop_tensors(const TensorFrame* table, int cap, int max_w, void* out, bool half, int H, int W, hipStream_t s);
+void yfv2_launch_crop_tensors_yuv(const TensorFrameYuv* table, int cap, int max_w, void* out, bool half, int H, int W, hipStream_t s);
 // ---- the per-stream IoU tracker (yfv2_track_update; kernel and the IoU's one function: yfv2_track.hip)
 constexpr int TRACK_MAX_R = 4096, TRACK_MAX_M = 1024;
 constexpr int TRACK_HEADER = 8, TRACK_SLOT = 10;     // int32 words of a stream's header and of one slot (include/yfv2.h)

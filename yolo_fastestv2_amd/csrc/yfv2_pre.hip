@@ -13,6 +13,7 @@
 // is assembled in LDS and leaves as aligned 4-byte stores (width % 4 == 0, so every output row starts 4-byte aligned).
 // Built with -ffp-contract=off: the coefficient arithmetic must round like the separate C operations it restates.
 #include <algorithm>
+#include <type_traits>
 
 #include "../../include/yfv2.h"
 #include "yfv2_device.h"
@@ -112,6 +113,79 @@ struct RowTrain {
   }
 };
 
+// RowTensor: the (cap, 3, H, W) fp32 or fp16 tensor of the crop-tensor entry points (yfv2_crop_tensors_u8 / _yuv):
+// a crop as a second network takes it.  The call's constants - mean, std, fill, the plane order - lie in front of the table's
+// CountedHead (CropTensorHead); begin reads them, uniformly, and re-indexes mean / std by BYTE channel, so that the unrolled put
+// indexes nothing at run time.  Every value is yfv2_crop_tensor_f32 / _f16 of its byte, evaluated directly: a crop's row is tens to
+// a few hundred pixels, fewer values than the 768 entries a per-workgroup table would hold.  Its LDS: the row as three planes of W
+// values in OUTPUT-plane order.  After a barrier the planes leave as 16-byte stores, three contiguous runs out[k][c][oy][0 .. W):
+// W % 4 == 0 and dst is 16-byte aligned, so every fp32 run is; an fp16 run is when W % 8 == 0 and is 8-byte aligned otherwise, and
+// then leaves as 8-byte stores.  A row outside the inner rectangle (letterbox) is a fill row: no staging, no LDS, no barrier.
+template <int THREADS, bool HALF>
+struct RowTensor {
+  using Out = std::conditional_t<HALF, _Float16, float>;
+  template <int N> using Vec = Out __attribute__((ext_vector_type(N)));
+  static constexpr int ALIGN = 16;
+  static constexpr bool AUGMENT = false;
+  static constexpr bool TENSOR = true;
+  static constexpr int N16 = 16 / (int)sizeof(Out);   // values of a 16-byte store
+  Out* dst;
+  float mean[3], std[3];      // by byte channel (B, G, R)
+  int fill[3];
+  int flip;                   // output plane of byte channel c: flip ? 2 - c : c
+  template <class Frame>
+  __device__ __forceinline__ void begin(const Frame* frames) {
+    const CropTensorParams& p = reinterpret_cast<const CropTensorHead*>(frames)[-1].p;
+    flip = p.rgb;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      mean[c] = flip ? p.mean[2 - c] : p.mean[c];
+      std[c] = flip ? p.std[2 - c] : p.std[c];
+      fill[c] = (int)((p.fill >> (8 * c)) & 255u);
+    }
+  }
+  __device__ __forceinline__ int plane(int c) const { return flip ? 2 - c : c; }
+  __device__ __forceinline__ Out value(int a, int c) const {
+    if constexpr (HALF) return yfv2_crop_tensor_f16(a, mean[c], std[c]);
+    else return yfv2_crop_tensor_f32(a, mean[c], std[c]);
+  }
+  __device__ __forceinline__ void put(unsigned char* lds, int ox, int c, int W, unsigned char byte) {
+    reinterpret_cast<Out*>(lds)[plane(c) * W + ox] = value(byte, c);
+  }
+  __device__ __forceinline__ void put_fill(unsigned char* lds, int ox, int W) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) put(lds, ox, c, W, (unsigned char)fill[c]);
+  }
+  __device__ __forceinline__ Out* run(int b, int p, int oy, int H, int W) const { return dst + (((size_t)b * 3 + p) * H + oy) * W; }
+  template <int N>
+  __device__ __forceinline__ void emit(const unsigned char* lds, int b, int oy, int H, int W) {
+    const int per = W / N;                              // stores per plane
+    for (int i = threadIdx.x; i < 3 * per; i += THREADS) {
+      const int p = i / per, q = i - p * per;
+      reinterpret_cast<Vec<N>*>(run(b, p, oy, H, W))[q] = reinterpret_cast<const Vec<N>*>(lds)[i];
+    }
+  }
+  __device__ __forceinline__ void end(const unsigned char* lds, int b, int oy, int H, int W) {
+    __syncthreads();
+    if (HALF && (W & 7)) emit<N16 / 2>(lds, b, oy, H, W);
+    else emit<N16>(lds, b, oy, H, W);
+  }
+  template <int N>
+  __device__ __forceinline__ void fill_run(Out* r, Out v, int W) {
+    Vec<N> pat;
+#pragma unroll
+    for (int j = 0; j < N; ++j) pat[j] = v;
+    for (int i = threadIdx.x; i < W / N; i += THREADS) reinterpret_cast<Vec<N>*>(r)[i] = pat;
+  }
+  __device__ __forceinline__ void fill_row(int b, int oy, int H, int W) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      if (HALF && (W & 7)) fill_run<N16 / 2>(run(b, plane(c), oy, H, W), value(fill[c], c), W);
+      else fill_run<N16>(run(b, plane(c), oy, H, W), value(fill[c], c), W);
+    }
+  }
+};
+
 __global__ __launch_bounds__(256) void resize_u8_kernel(ResizeArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tid = threadIdx.x;
@@ -177,6 +251,10 @@ __global__ __launch_bounds__(256) void resize_u8_kernel(ResizeArgs a) {
 // table's capacity and a workgroup whose entry is not live returns here - before the descriptor load and before any barrier, on a
 // value every thread of the workgroup reads alike.  For a descriptor without COUNTED the test is no code at all: the four host-table
 // instantiations are the instruction streams they were (profiles/crops_isa.txt).
+// A fourth pair, over Letterboxed<...> descriptors and RowTensor, writes the crops as a network's input: the row
+// and column of the resized view are the output's minus the inner rectangle's origin, the scales are those of the inner size, and
+// what lies outside the inner rectangle is fill.  All of it sits behind `if constexpr` on Row::TENSOR: the six other instantiations
+// are the instruction streams they were (profiles/crop_tensors_isa.txt).
 template <class Frame>
 __device__ __forceinline__ bool yfv2_not_live(const Frame* frames, int b) {
   if constexpr (requires { Frame::COUNTED; }) return b >= reinterpret_cast<const CountedHead*>(frames)[-1].live;
@@ -192,7 +270,13 @@ __global__ __launch_bounds__(RF_THREADS, 6) void resize_frames_u8_kernel(const F
   const int b = blockIdx.x / H, oy = blockIdx.x - b * H;
   if (yfv2_not_live(frames, b)) return;
   const Frame f = frames[b];
-  const RowCoef ry = yfv2_axis_coef(oy, f.scale_y, f.h, false);
+  int iy = oy;                                           // the row of the resized view: oy itself, except inside a letterbox
+  if constexpr (requires { Row::TENSOR; }) {
+    row.begin(frames);
+    iy = oy - f.oy0;
+    if (iy < 0 || iy >= f.ih) { row.fill_row(b, oy, H, W); return; }   // uniform, in front of every barrier
+  }
+  const RowCoef ry = yfv2_axis_coef(iy, f.scale_y, f.h, false);
   const int row_bytes = f.w * 3;
   const int slot = (row_bytes + 3 + Row::ALIGN - 1) & ~(Row::ALIGN - 1);
   unsigned char* R0 = smem;
@@ -233,7 +317,12 @@ __global__ __launch_bounds__(RF_THREADS, 6) void resize_frames_u8_kernel(const F
   const unsigned char* r0 = R0 + m0;
   const unsigned char* r1 = R1 + m1;
   for (int ox = tid; ox < W; ox += RF_THREADS) {
-    const RowCoef rx = yfv2_axis_coef(ox, f.scale_x, f.w, true);
+    int ix = ox;                                         // the column of the resized view, likewise
+    if constexpr (requires { Row::TENSOR; }) {
+      ix = ox - f.ox0;
+      if (ix < 0 || ix >= f.iw) { row.put_fill(OUT, ox, W); continue; }
+    }
+    const RowCoef rx = yfv2_axis_coef(ix, f.scale_x, f.w, true);
 #pragma unroll
     for (int c = 0; c < 3; ++c)
       row.put(OUT, ox, c, W, yfv2_blend(r0[rx.s0 * 3 + c], r0[rx.s1 * 3 + c], r1[rx.s0 * 3 + c], r1[rx.s1 * 3 + c], rx, ry));
@@ -301,7 +390,13 @@ __global__ __launch_bounds__(RY_THREADS, 8) void resize_frames_yuv_kernel(const 
   const int b = blockIdx.x / H, oy = blockIdx.x - b * H;
   if (yfv2_not_live(frames, b)) return;
   const Frame f = frames[b];
-  const RowCoef ry = yfv2_axis_coef(oy, f.scale_y, f.h, false);
+  int iy = oy;
+  if constexpr (requires { Row::TENSOR; }) {
+    row.begin(frames);
+    iy = oy - f.oy0;
+    if (iy < 0 || iy >= f.ih) { row.fill_row(b, oy, H, W); return; }
+  }
+  const RowCoef ry = yfv2_axis_coef(iy, f.scale_y, f.h, false);
   const bool planar = f.format == YFV2_YUV_I420;
   const int cw = ((f.w - 1 + f.px) >> 1) + 1, ch = ((f.h - 1 + f.py) >> 1) + 1;   // chroma samples per row, chroma rows of the frame
   const int cbytes = planar ? cw : 2 * cw;
@@ -385,7 +480,12 @@ __global__ __launch_bounds__(RY_THREADS, 8) void resize_frames_yuv_kernel(const 
   const unsigned char* y1 = LY1 + smis[1];
   const YuvCoef kc = f.coef;
   for (int ox = tid; ox < W; ox += RY_THREADS) {
-    const RowCoef rx = yfv2_axis_coef(ox, f.scale_x, f.w, true);
+    int ix = ox;
+    if constexpr (requires { Row::TENSOR; }) {
+      ix = ox - f.ox0;
+      if (ix < 0 || ix >= f.iw) { row.put_fill(OUT, ox, W); continue; }
+    }
+    const RowCoef rx = yfv2_axis_coef(ix, f.scale_x, f.w, true);
     const int j0 = ((rx.s0 + f.px) >> 1) * cstep, j1 = ((rx.s1 + f.px) >> 1) * cstep;
     int p00[3], p01[3], p10[3], p11[3];      // B, G, R of the taps (row s0 / s1, column sx0 / sx1)
     yfv2_yuv_to_bgr(y0[rx.s0], pu0[j0], pv0[j0], kc, p00);
@@ -420,6 +520,15 @@ size_t yfv2_resize_yuv_lds_bytes(int w, int W) { return 2 * (size_t)((w + 6) & ~
 
 YuvCoef yfv2_yuv_coef(int colour) { return YUV_COEF[colour]; }
 
+// RowTensor's launches: the staging slots rounded to 16 bytes, the row as three planes of fp32 or fp16 values; the B, G, R limit in
+// closed form (a slot is at most 3 w + 18 bytes), the YUV one walked down from the crops' own limit - so neither admits a frame that
+// yfv2_crop_detections_* refuses at the same out_w
+size_t yfv2_crop_tensor_lds_bytes(int SW, int W, bool half) { return 2 * (size_t)((SW * 3 + 18) & ~15) + (size_t)W * (half ? 6 : 12); }
+int yfv2_crop_tensor_max_width(int W, bool half) { return (YFV2_LDS_FULL - (half ? 6 : 12) * W) / 6 - 6; }
+size_t yfv2_crop_tensor_yuv_lds_bytes(int w, int W, bool half) {
+  return 2 * (size_t)((w + 18) & ~15) + 4 * (size_t)(((w >> 1) + 19) & ~15) + (size_t)W * (half ? 6 : 12);
+}
+
 // the widest frame whose workgroup fits a CU's LDS: the function above grows by about 4 bytes per pixel and never falls, so the
 // answer is next to (YFV2_LDS_FULL - 3 W) / 4 and two short walks find it exactly
 int yfv2_resize_yuv_max_width(int W) {
@@ -438,6 +547,12 @@ size_t yfv2_train_batch_yuv_lds_bytes(int w, int W) {
 int yfv2_train_batch_yuv_max_width(int W) {
   int w = yfv2_resize_yuv_max_width(W);
   while (w > 1 && yfv2_train_batch_yuv_lds_bytes(w, W) > (size_t)YFV2_LDS_FULL) --w;
+  return w;
+}
+
+int yfv2_crop_tensor_yuv_max_width(int W, bool half) {
+  int w = yfv2_resize_yuv_max_width(W);
+  while (w > 1 && yfv2_crop_tensor_yuv_lds_bytes(w, W, half) > (size_t)YFV2_LDS_FULL) --w;
   return w;
 }
 
@@ -475,4 +590,28 @@ void yfv2_launch_train_batch_frames(const TrainFrame* frames, int B, int max_w, 
 void yfv2_launch_train_batch_frames_yuv(const TrainFrameYuv* frames, int B, int max_w, float* dst, int H, int W, hipStream_t s) {
   YFV2_LAUNCH_LDS(yfv2_device(), train_batch_frames_yuv_kernel, YFV2_LDS_FULL, dim3((unsigned)(B * H)), dim3(RY_THREADS), yfv2_train_batch_yuv_lds_bytes(max_w, W), s,
                   frames, dst, H, W);
+}
+
+// The crop tensors of a counted table: the crops' grid and LDS rule, the row as fp32 or fp16 planes
+template <bool HALF>
+static void launch_crop_tensors(const TensorFrame* table, int cap, int max_w, void* out, int H, int W, hipStream_t s) {
+  using Row = RowTensor<RF_THREADS, HALF>;
+  YFV2_LAUNCH_LDS(yfv2_device(), (resize_frames_u8_kernel<TensorFrame, Row>), YFV2_LDS_FULL, dim3((unsigned)(cap * H)), dim3(RF_THREADS),
+                  yfv2_crop_tensor_lds_bytes(max_w, W, HALF), s, table, static_cast<typename Row::Out*>(out), H, W);
+}
+template <bool HALF>
+static void launch_crop_tensors_yuv(const TensorFrameYuv* table, int cap, int max_w, void* out, int H, int W, hipStream_t s) {
+  using Row = RowTensor<RY_THREADS, HALF>;
+  YFV2_LAUNCH_LDS(yfv2_device(), (resize_frames_yuv_kernel<TensorFrameYuv, Row>), YFV2_LDS_FULL, dim3((unsigned)(cap * H)), dim3(RY_THREADS),
+                  yfv2_crop_tensor_yuv_lds_bytes(max_w, W, HALF), s, table, static_cast<typename Row::Out*>(out), H, W);
+}
+
+void yfv2_launch_crop_tensors(const TensorFrame* table, int cap, int max_w, void* out, bool half, int H, int W, hipStream_t s) {
+  if (half) launch_crop_tensors<true>(table, cap, max_w, out, H, W, s);
+  else launch_crop_tensors<false>(table, cap, max_w, out, H, W, s);
+}
+
+void yfv2_launch_crop_tensors_yuv(const TensorFrameYuv* table, int cap, int max_w, void* out, bool half, int H, int W, hipStream_t s) {
+  if (half) launch_crop_tensors_yuv<true>(table, cap, max_w, out, H, W, s);
+  else launch_crop_tensors_yuv<false>(table, cap, max_w, out, H, W, s);
 }

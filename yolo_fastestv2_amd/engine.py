@@ -434,7 +434,8 @@ class Engine:
                                   frames, tiles, conf_thres, iou_thres, merge_thres, metric, max_out, tile, overlap, include_full, out, check)
 
     # ---- second-stage crops (include/yfv2.h yfv2_crop_detections_u8 / _yuv) ---------------------------------------
-    def _crop_detections(self, name, table, native, frames, dets, count, out_size, pad, max_per_frame, classes, cap, out):
+    def _crop_detections(self, name, table, native, frames, dets, count, out_size, pad, max_per_frame, classes, cap, out, tensor=None):
+        """tensor: None - uint8 (cap, h, w, 3) crops; (a _lib.CropTensor, its torch dtype) - the (cap, 3, h, w) tensor of crop_tensors"""
         arr, keep = table(frames)
         B = len(keep)
         if (not torch.is_tensor(dets) or dets.dim() != 3 or dets.shape[0] != B or dets.shape[2] != 6 or dets.dtype != torch.float32 or dets.device != self.device
@@ -454,24 +455,27 @@ class Engine:
         if cap is None:
             cap = B * min(R, max(max_per_frame, 1))
         cap = int(cap)
-        shapes = ((cap, out_h, out_w, 3), (cap,), (cap, 4), (B + 1,), (B,))
+        shapes = ((cap, out_h, out_w, 3) if tensor is None else (cap, 3, out_h, out_w), (cap,), (cap, 4), (B + 1,), (B,))
+        dt0, sh0 = torch.uint8 if tensor is None else tensor[1], shapes[0]
         if out is None:
             if cap < 1 or out_h < 1 or out_w < 1:
                 raise ValueError("%s: cap and out_size must be >= 1" % name)
-            out = tuple(torch.empty(sh, device=self.device, dtype=torch.uint8 if i == 0 else torch.int32) for i, sh in enumerate(shapes))
+            out = tuple(torch.empty(sh, device=self.device, dtype=dt0 if i == 0 else torch.int32) for i, sh in enumerate(shapes))
         else:
             if len(out) != 5:
                 raise ValueError("%s: out must be (crops, crop_src, crop_rect, crop_offset, crop_skipped)" % name)
             for i, (t, sh) in enumerate(zip(out, shapes)):
                 if t is None and i == 4:
                     continue            # crop_skipped is optional
-                dt = torch.uint8 if i == 0 else torch.int32
+                dt = dt0 if i == 0 else torch.int32
                 if not torch.is_tensor(t) or tuple(t.shape) != sh or t.dtype != dt or t.device != self.device or not t.is_contiguous():
-                    raise ValueError("%s: out must be contiguous (crops %s uint8, crop_src %s, crop_rect %s, crop_offset %s, crop_skipped %s or None, "
-                                     "int32) on %s" % ((name,) + shapes + (self.device,)))
+                    raise ValueError("%s: out must be contiguous (%s, crop_src %s, crop_rect %s, crop_offset %s, crop_skipped %s or None, "
+                                     "int32) on %s" % ((name, "crops %s uint8" % (sh0,) if tensor is None else "tensors %s %s" % (sh0, dt0)) + shapes[1:]
+                                                       + (self.device,)))
         self.ensure_batch(B)
         crops, src, rect, offset, skipped = out
-        check(native(self._h, arr, B, _ptr(dets), _ptr(count), R, C.byref(rule), _ptr(crops), _ptr(src), _ptr(rect), _ptr(offset),
+        extra = () if tensor is None else (C.byref(tensor[0]),)
+        check(native(self._h, arr, B, _ptr(dets), _ptr(count), R, C.byref(rule), *extra, _ptr(crops), _ptr(src), _ptr(rect), _ptr(offset),
                      _ptr(skipped) if skipped is not None else None, cap, _stream(self.device)), self._h)
         return crops, src, rect, offset, skipped
 
@@ -495,6 +499,40 @@ class Engine:
         bit-identical to crop_detections on the converted frames."""
         return self._crop_detections("crop_detections_yuv", self._yuv_table, _lib.lib().yfv2_crop_detections_yuv, frames, dets, count, out_size, pad,
                                      max_per_frame, classes, cap, out)
+
+    # ---- second-stage crops as network input (include/yfv2.h yfv2_crop_tensors_u8 / _yuv; DESIGN.md 4.21) ------------------------------
+    @staticmethod
+    def _crop_tensor(name, mean, std, rgb, letterbox, fill, dtype):
+        if dtype not in (torch.float32, torch.float16):
+            raise ValueError("%s: dtype must be torch.float32 or torch.float16, got %s" % (name, dtype))
+        t = _lib.CropTensor()
+        t.dtype, t.rgb, t.letterbox = _lib.F32 if dtype == torch.float32 else _lib.F16, int(bool(rgb)), int(bool(letterbox))
+        for what, src, dst, conv in (("mean", mean, t.mean, float), ("std", std, t.std, float), ("fill", fill, t.fill, int)):
+            v = [conv(a) for a in (src.tolist() if hasattr(src, "tolist") else src)]
+            if len(v) != 3 or (conv is int and not all(0 <= a <= 255 for a in v)):
+                raise ValueError("%s: %s must be three %s" % (name, what, "integers in 0..255" if conv is int else "numbers"))
+            dst[0], dst[1], dst[2] = v
+        return t, dtype
+
+    def crop_tensors(self, frames, dets, count, out_size, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0), rgb=False, letterbox=False, fill=(0, 0, 0),
+                     dtype=torch.float32, pad=0.0, max_per_frame=MAX_DET, classes=None, cap=None, out=None):
+        """`crop_detections` with the crops written as a second network takes them, in the same launch: (cap, 3, h, w) fp32 or fp16
+        (dtype), each byte a of the crop as ((a / 255) - mean[c]) / std[c] - torchvision's ToTensor and Normalize, every operation
+        rounded to fp32 on its own, then once to half for fp16.  mean / std: by OUTPUT plane; rgb: planes R, G, B instead of the frames'
+        B, G, R; letterbox: keep each rectangle's aspect ratio, centred in (h, w), the rest `fill` (B, G, R bytes, which go through
+        the same formula).  Everything else - frames, dets, count, pad, max_per_frame, classes, cap - as crop_detections, and
+        crop_src, crop_rect, crop_offset, crop_skipped are what it returns.  Returns (tensors, crop_src, crop_rect, crop_offset,
+        crop_skipped).  The rule, bit for bit: include/yfv2.h; with letterbox=False the bytes behind the values are crop_detections'
+        crops.  No uint8 crop is written.  Frames may be somewhat narrower than for crop_detections (the row is staged as three
+        planes of w values).  Enqueue only."""
+        return self._crop_detections("crop_tensors", self._frame_table, _lib.lib().yfv2_crop_tensors_u8, frames, dets, count, out_size, pad,
+                                     max_per_frame, classes, cap, out, self._crop_tensor("crop_tensors", mean, std, rgb, letterbox, fill, dtype))
+
+    def crop_tensors_yuv(self, frames, dets, count, out_size, mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0), rgb=False, letterbox=False,
+                         fill=(0, 0, 0), dtype=torch.float32, pad=0.0, max_per_frame=MAX_DET, classes=None, cap=None, out=None):
+        """`crop_tensors` for a list of yuv.YuvFrame: bit-identical to crop_tensors on the converted frames."""
+        return self._crop_detections("crop_tensors_yuv", self._yuv_table, _lib.lib().yfv2_crop_tensors_yuv, frames, dets, count, out_size, pad,
+                                     max_per_frame, classes, cap, out, self._crop_tensor("crop_tensors_yuv", mean, std, rgb, letterbox, fill, dtype))
 
     # ---- identity across frames: the per-stream IoU tracker (include/yfv2.h yfv2_track_update; DESIGN.md 4.18) -------------------
     def track_update(self, dets, count, streams, state, max_tracks, match_thres=0.3, class_aware=True, init_conf=0.0, max_misses=30,
