@@ -964,6 +964,12 @@ YFV2_API int64_t yfv2_debug_plan_image_ex(const yfv2_config* cfg, const yfv2_pla
 /* Host-only test hook: the channel order in which that plan stores stage 3's output C2 (label[k] = logical channel at
  * NHWC position k, 96 entries); returns 1 if the plan permutes (chain kernel), 0 for plain NHWC, negative on error. */
 YFV2_API int yfv2_debug_plan_c2_label(const yfv2_config* cfg, const yfv2_tensor_desc* tensors, int32_t n, int32_t* label);
+/* Host-only test hook: what the frame entry points' one launch takes and admits.  row_kind: 0 the uint8 batch of yfv2_resize_frames_* /
+ * yfv2_detect_frames_*, 1 the uint8 crops of yfv2_crop_detections_*, 2 the fp32 batch of yfv2_train_batch_frames_*, 3 / 4 the fp32 /
+ * fp16 tensor of yfv2_crop_tensors_*; yuv: 0 yfv2_frame, 1 yfv2_frame_yuv; w: a frame's width, 1 .. 2^26; W: the output row's width
+ * (the network's, or out_w), 1 .. 2^20.  *lds_bytes = the LDS of one workgroup of that launch for a frame w wide, *max_width = the
+ * widest frame the entry point admits at W (either may be NULL).  Opens no device. */
+YFV2_API int yfv2_debug_rows(int32_t row_kind, int32_t yuv, int32_t w, int32_t W, int64_t* lds_bytes, int32_t* max_width);
 
 #ifdef __cplusplus
 }

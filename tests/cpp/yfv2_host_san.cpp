@@ -123,6 +123,19 @@ int main() {
     }
   CHECK(n_maps == 96, "%d maps", n_maps);
 
+  // the row launches' LDS and width limits (yfv2_debug_rows): every kind at the ends of its argument ranges - the arithmetic stays
+  // inside int - and the widest frame it admits fits a CU's LDS
+  for (int kind = 0; kind < 5; ++kind)
+    for (int yuv = 0; yuv < 2; ++yuv)
+      for (int W : {1, 4, 352, 4096, 1 << 20}) {
+        int64_t lds = -1;
+        int32_t limit = -1;
+        for (int w : {1, 1920, 1 << 26}) CHECK(yfv2_debug_rows(kind, yuv, w, W, &lds, &limit) == YFV2_OK && lds > 0, "debug_rows(%d, %d, %d, %d)", kind, yuv, w, W);
+        if (W > 4096) continue;
+        CHECK(limit >= 1 && yfv2_debug_rows(kind, yuv, limit, W, &lds, nullptr) == YFV2_OK && lds <= 160 * 1024, "debug_rows limit (%d, %d, %d)", kind, yuv, W);
+      }
+  CHECK(yfv2_debug_rows(5, 0, 8, 8, nullptr, nullptr) == YFV2_ERR_ARG && yfv2_debug_rows(0, 0, 0, 8, nullptr, nullptr) == YFV2_ERR_ARG, "debug_rows arguments");
+
   // the null-handle path of every entry point that takes a handle: a code (or 0 / -1 where the return value is a count), no access
   const yfv2_handle h = nullptr;
   yfv2_destroy(h);

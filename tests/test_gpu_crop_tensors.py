@@ -16,6 +16,7 @@ import torch
 
 import crop_tensors_model as model
 import crops_model
+import rows_model
 import yuv_model
 
 pytestmark = pytest.mark.gpu
@@ -25,7 +26,6 @@ S_VAL, S_SRC, S_RECT, S_OFF, S_SKIP = -123.25, -7, -8, -9, -10      # the output
 MEAN, STD, FILL = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225), (114, 7, 201)      # one non-trivial triple of each
 PLAIN = dict(mean=(0.0, 0.0, 0.0), std=(1.0, 1.0, 1.0), fill=(0, 0, 0))
 R_HAND = 32
-LDS = 160 * 1024
 
 
 @pytest.fixture(scope="module")
@@ -343,7 +343,7 @@ def test_batch_independence(eng, scene):
 
 def _limit(out_w, half):
     """the width limit of the B, G, R entry point (include/yfv2.h)"""
-    return (LDS - (6 if half else 12) * out_w) // 6 - 6
+    return rows_model.max_width(rows_model.TENSOR_F16 if half else rows_model.TENSOR_F32, False, out_w)
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float16])

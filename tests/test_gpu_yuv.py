@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 import torch
 
+import rows_model
 import yuv_model as ym
 from frames_ref import MAX_DET
 from oracle import yfv2_oracle as oracle
@@ -144,7 +145,7 @@ def test_crops_of_padded_planes_at_odd_addresses(yfv2, dev, fmt):
 # ---- 3. the widest frame, and one pixel more -----------------------------------------------------------------------------------
 def test_widest_frame_and_the_limit(yfv2, dev, engine):
     from yolo_fastestv2_amd import _lib
-    limit = ym.max_width(352)
+    limit = rows_model.max_width(rows_model.U8, True, 352)
     assert limit == yfv2.yuv.max_width(352) == 40689
     rng = np.random.default_rng(300)
     eng = yfv2.Engine(dev, 352, 352, max_batch=3, plan={})

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import rows_model as rm
 import train_batch_model as tm
 from conftest import REPO
 
@@ -102,10 +103,12 @@ def test_lds_bytes_and_width_limits():
     full = ds.LDS_FULL
     for W in (32, 64, 96, 352, 640):
         m = ds.max_frame_width(W)
+        assert m == rm.max_width(rm.TRAIN, False, W) and ds.train_batch_lds_bytes(m, W) == rm.lds_bytes(rm.TRAIN, False, m, W)
         assert ds.train_batch_lds_bytes(m, W) <= full
         assert m < (full - 3 * W) // 6 - 2                              # below resize_frames' limit: what this takes, that takes
         assert ds.train_batch_lds_bytes(m + 6, W) > full                # and no more than a slot's rounding below the true maximum
         my = ds.max_frame_width(W, True)
+        assert my == rm.max_width(rm.TRAIN, True, W) and ds.train_batch_lds_bytes(my, W, True) == rm.lds_bytes(rm.TRAIN, True, my, W)
         assert ds.train_batch_lds_bytes(my, W, True) <= full < ds.train_batch_lds_bytes(my + 1, W, True)
         assert my <= yuv.max_width(W)
     assert ds.max_frame_width(352) == 26426 and ds.train_batch_lds_bytes(26426, 352) == full
@@ -113,11 +116,11 @@ def test_lds_bytes_and_width_limits():
     # the 16-byte slots hold what the staging writes, for every width and misalignment (the resize's own slots are the 4-byte form)
     for w in range(1, 200):
         for mis in range(4):
-            assert ((mis + 3 * w + 3) >> 2) * 4 <= (3 * w + 18) & ~15
-            assert ((mis + w + 3) >> 2) * 4 <= (w + 18) & ~15
+            assert ((mis + 3 * w + 3) >> 2) * 4 <= rm.slot(3 * w, 16)
+            assert ((mis + w + 3) >> 2) * 4 <= rm.slot(w, 16)
             for px in (0, 1):
                 cw = ((w - 1 + px) >> 1) + 1
-                half = ((w >> 1) + 19) & ~15
+                half = rm.slot((w >> 1) + 1, 16)
                 assert ((mis + cw + 3) >> 2) * 4 <= half and ((mis + 2 * cw + 3) >> 2) * 4 <= 2 * half
 
 

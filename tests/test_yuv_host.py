@@ -4,6 +4,7 @@ LDS / width limit.  The device side is tests/test_gpu_yuv.py."""
 import numpy as np
 import pytest
 
+import rows_model as rm
 import yuv_model as ym
 from frames_ref import stage_row
 
@@ -163,22 +164,22 @@ def test_lds_bytes_and_width_limit_against_the_restatement():
     from yolo_fastestv2_amd import yuv
     for W in (352, 64, 96, 640):
         for w in list(range(1, 70)) + [351, 352, 353, 1279, 1280, 1919, 1920, 1921, 3840, 27128, 40000]:
-            assert yuv.resize_lds_bytes(w, W) == ym.resize_lds_bytes(w, W), (w, W)
+            assert yuv.resize_lds_bytes(w, W) == rm.lds_bytes(rm.U8, True, w, W), (w, W)
             if w > 1:
                 assert yuv.resize_lds_bytes(w, W) >= yuv.resize_lds_bytes(w - 1, W)
         m = yuv.max_width(W)
-        assert m == ym.max_width(W)
-        assert ym.resize_lds_bytes(m, W) <= ym.LDS_FULL < ym.resize_lds_bytes(m + 1, W)
+        assert m == rm.max_width(rm.U8, True, W)
+        assert rm.lds_bytes(rm.U8, True, m, W) <= rm.LDS_FULL < rm.lds_bytes(rm.U8, True, m + 1, W)
     assert yuv.max_width(352) == 40689
     assert yuv.resize_lds_bytes(1920, 352) == 8760                      # 18 workgroups of a 1080p batch per CU by LDS
-    assert 2 * ((1920 * 3 + 6) & ~3) + 3 * 352 == 12584                 # ... where the B, G, R kernel's rows take 12 584 bytes
+    assert rm.lds_bytes(rm.U8, False, 1920, 352) == 12584               # ... where the B, G, R kernel's rows take 12 584 bytes
     # what the slots must hold, for every width and misalignment: a luma row, an interleaved row in two half-slots, a planar row in one
     for w in range(1, 200):
-        half = ((w >> 1) + 7) & ~3
+        half = rm.slot((w >> 1) + 1, 4)
         for px in (0, 1):
             cw = ((w - 1 + px) >> 1) + 1
             for mis in range(4):
-                assert ((mis + w + 3) >> 2) * 4 <= (w + 6) & ~3
+                assert ((mis + w + 3) >> 2) * 4 <= rm.slot(w, 4)
                 assert ((mis + cw + 3) >> 2) * 4 <= half
                 assert ((mis + 2 * cw + 3) >> 2) * 4 <= 2 * half
 

@@ -1,6 +1,6 @@
 """The numpy statement of the YUV 4:2:0 -> B, G, R rule of include/yfv2.h (yfv2_frame_yuv), shared by
 tests/test_yuv_host.py (CPU) and tests/test_gpu_yuv.py (GPU), plus helpers that build planes with pitch padding and poison
-bytes around a frame.  OpenCV is on neither machine: this is the published integer arithmetic written out, and parity with cv2
+bytes around a frame.  (The resize's LDS and width limit: tests/rows_model.py.)  OpenCV is on neither machine: this is the published integer arithmetic written out, and parity with cv2
 proper is unpinned, exactly as for the resize.
 """
 import numpy as np
@@ -18,7 +18,6 @@ COEF = {
     BT709_FULL: (0, 1048576, 1651297, -490864, -196424, 1945738),
 }
 POISON = 0xA5
-LDS_FULL = 160 * 1024
 
 
 def accumulators(Y, U, V, colour):
@@ -102,25 +101,3 @@ def bgr_to_nv12(bgr):
         uv[:, k::2] = np.clip(np.rint(q), 0, 255).astype(np.uint8)
     return y, uv
 
-
-def resize_lds_bytes(w, W):
-    """restatement of yfv2_resize_yuv_lds_bytes (yfv2_pre.hip): each staged row is its bytes plus up to 3 of head misalignment,
-    rounded up to dwords - two luma rows of w bytes, two chroma rows that are either one interleaved row of 2 * (w // 2 + 1) bytes
-    or two planar rows of w // 2 + 1 in a half-slot each (two half-slots hold the interleaved row) - and the 3 W output bytes"""
-    up4 = lambda n: (n + 3) // 4 * 4
-    luma = up4(w + 3)
-    half = up4(w // 2 + 1 + 3)
-    assert 2 * half >= up4(2 * (w // 2 + 1) + 3)
-    return 2 * luma + 2 * 2 * half + 3 * W
-
-
-def max_width(W):
-    """the widest frame with resize_lds_bytes <= a CU's LDS, by bisection on a function that never falls"""
-    lo, hi = 1, LDS_FULL
-    while lo < hi:
-        mid = (lo + hi + 1) // 2
-        if resize_lds_bytes(mid, W) <= LDS_FULL:
-            lo = mid
-        else:
-            hi = mid - 1
-    return lo

@@ -1,5 +1,5 @@
 // yfv2_api_debug.hip - host side of libyfv2.so, what measures and inspects: the host-only dry runs of the plan and the packer
-// (yfv2_debug_plan_*), the clock probe, the per-launch profile pass, the repeated step and the activation dump.  The handle and
+// (yfv2_debug_plan_*), the row launches' LDS and width limits (yfv2_debug_rows), the clock probe, the per-launch profile pass, the repeated step and the activation dump.  The handle and
 // the shared plumbing: yfv2_ctx.h.
 #include <algorithm>
 #include <cstdio>
@@ -94,6 +94,16 @@ int yfv2_debug_plan_c2_label(const yfv2_config* cfg, const yfv2_tensor_desc* ten
   if (int rc = d.build(cfg, nullptr, tensors, n)) return rc;
   for (int k = 0; k < 96; ++k) label[k] = d.ctx.plan.c2_permuted ? d.ctx.plan.c2_label[k] : k;
   return d.ctx.plan.c2_permuted ? 1 : 0;
+}
+
+// Host-only test hook: the one description of the row kernels (yfv2_pre.hip) as the launches and the entry points' checks read it,
+// so that the CPU suite can hold it against a restatement (tests/rows_model.py) for every kind.
+int yfv2_debug_rows(int32_t row_kind, int32_t yuv, int32_t w, int32_t W, int64_t* lds_bytes, int32_t* max_width) {
+  if (row_kind < 0 || row_kind >= YFV2_ROW_KINDS || yuv < 0 || yuv > 1 || w < 1 || w > (1 << 26) || W < 1 || W > (1 << 20))
+    return fail(nullptr, YFV2_ERR_ARG, "yfv2_debug_rows: bad argument");
+  if (lds_bytes) *lds_bytes = (int64_t)yfv2_rows_lds_bytes((Yfv2RowKind)row_kind, yuv != 0, w, W);
+  if (max_width) *max_width = yfv2_rows_max_width((Yfv2RowKind)row_kind, yuv != 0, W);
+  return YFV2_OK;
 }
 
 // effective shader clock, measured by the shader (yfv2_probe.hip): enqueue on `stream` ...

@@ -1,10 +1,11 @@
 // yfv2_api_frames.hip - host side of libyfv2.so, the entry points that take caller frames: the resize, detection on ragged
 // batches of frames, and tiled detection (tile plan, merge, both in one call).  The handle and the shared plumbing: yfv2_ctx.h.
 // Frames come in two kinds, yfv2_frame (packed B, G, R) and yfv2_frame_yuv (4:2:0 planes).  Each kind is described once
-// (BgrFrames, YuvFrames: what differs); check_frames<Kind> turns a caller's batch into a FrameBatch, enqueue_resize resizes
-// one, enqueue_train_batch makes the training batch of one, and resize_frames / train_batch_frames / detect_frames /
-// crop_detections (yfv2_crop_tensors_* too: the same template with a yfv2_crop_tensor) / detect_tiled are one template each.  The
-// extern "C" functions pass their names.
+// (BgrFrames, YuvFrames: what differs); what a batch becomes is a row kind (Yfv2RowKind, yfv2_internal.h: uint8 batch, counted
+// uint8 crops, training batch, fp32 / fp16 tensor), a VALUE: check_frames<Kind> turns a caller's batch into a FrameBatch under the
+// row kind's width limit (yfv2_rows_max_width), enqueue_rows uploads its table and launches the rows of the resize or the training
+// batch (yfv2_launch_rows), and resize_frames / train_batch_frames / detect_frames / crop_detections (yfv2_crop_tensors_* too: the
+// same template with a yfv2_crop_tensor) / detect_tiled are one template each.  The extern "C" functions pass their names.
 // yfv2_track_update (the per-stream tracker behind the detect calls) takes rows, not frames; its checks and its launch are here too.
 #include <algorithm>
 #include <cmath>
@@ -63,13 +64,12 @@ struct FrameBatch {
   int max_w = 1;
 };
 
-// ---- the two kinds: only what differs.  check = one caller frame (a whole frame of a tiled call too); max_width = the limit of
-// what is resized; expand = frame b of the batch into its device descriptor(s), after its own last check; crop = the frame that
-// a tile of `fr` is (the rectangle was checked).
+// ---- the two kinds: only what differs.  check = one caller frame (a whole frame of a tiled call too); expand = frame b of the
+// batch into its device descriptor(s), after its own last check; crop = the frame that a tile of `fr` is (the rectangle was checked).
 struct BgrFrames {
   using Frame = yfv2_frame;
+  static constexpr bool YUV = false;
   static int check(yfv2_handle h, const std::string& at, const Frame& f) { return check_frame(h, at, f); }
-  static int max_width(int W) { return yfv2_resize_max_width(W); }
   static int expand(yfv2_handle h, const std::string& at, const Frame& f, FrameBatch& fb, size_t b) {
     if (f.row_pitch > (1ll << 40) || (long long)(f.height - 1) * f.row_pitch > (1ll << 52))
       return fail(h, YFV2_ERR_ARG, at + "row_pitch out of range");
@@ -82,8 +82,8 @@ struct BgrFrames {
 // (kernel: resize_frames_yuv_kernel, yfv2_pre.hip)  The descriptor has the origin folded into the plane pointers.
 struct YuvFrames {
   using Frame = yfv2_frame_yuv;
+  static constexpr bool YUV = true;
   static int check(yfv2_handle h, const std::string& at, const Frame& f) { return check_frame_yuv(h, at, f); }
-  static int max_width(int W) { return yfv2_resize_yuv_max_width(W); }
   static int expand(yfv2_handle, const std::string&, const Frame& f, FrameBatch& fb, size_t b) {
     if (fb.yuv.empty()) fb.yuv.assign(fb.t.size(), ResizeFrameYuv{});
     ResizeFrameYuv& r = fb.yuv[b];
@@ -102,21 +102,18 @@ struct YuvFrames {
   }
 };
 
-// The training entry points take the same frames under the training kernels' own width limit (their LDS holds the row in fp32).
-struct TrainBgrFrames : BgrFrames { static int max_width(int W) { return yfv2_train_batch_max_width(W); } };
-struct TrainYuvFrames : YuvFrames { static int max_width(int W) { return yfv2_train_batch_yuv_max_width(W); } };
-
 // Ragged batches: every frame is checked here, before anything is enqueued, and expanded by its scales into fb.  The tables are
 // B entries of the handle's max_batch, so B is bound by max_batch on every entry point.
+// rows: what the frames become, which decides how wide one may be (a row kind's LDS holds the output row in its own format).
 // (H, W): what the frames are resized to - the network's size on every entry point but the crops', whose caller names it.
 template <class Kind>
-static int check_frames(yfv2_handle h, const char* what, const typename Kind::Frame* frames, int32_t B, FrameBatch& fb, int H, int W) {
+static int check_frames(yfv2_handle h, const char* what, const typename Kind::Frame* frames, int32_t B, FrameBatch& fb, Yfv2RowKind rows, int H, int W) {
   const std::string w_ = what;
   if (!frames) return fail(h, YFV2_ERR_ARG, w_ + ": null pointer");
   if (B < 1) return fail(h, YFV2_ERR_ARG, w_ + ": B < 1");
   if (B > h->cfg.max_batch)
     return fail(h, YFV2_ERR_BATCH, w_ + ": batch " + std::to_string(B) + " above max_batch=" + std::to_string(h->cfg.max_batch));
-  const int limit = Kind::max_width(W);
+  const int limit = yfv2_rows_max_width(rows, Kind::YUV, W);
   fb.t.assign((size_t)B, ResizeFrame{});
   for (int32_t b = 0; b < B; ++b) {
     const typename Kind::Frame& f = frames[b];
@@ -133,8 +130,8 @@ static int check_frames(yfv2_handle h, const char* what, const typename Kind::Fr
   return YFV2_OK;
 }
 template <class Kind>
-static int check_frames(yfv2_handle h, const char* what, const typename Kind::Frame* frames, int32_t B, FrameBatch& fb) {
-  return check_frames<Kind>(h, what, frames, B, fb, h->cfg.height, h->cfg.width);
+static int check_frames(yfv2_handle h, const char* what, const typename Kind::Frame* frames, int32_t B, FrameBatch& fb, Yfv2RowKind rows = YFV2_ROWS_U8) {
+  return check_frames<Kind>(h, what, frames, B, fb, rows, h->cfg.height, h->cfg.width);
 }
 
 // The submit of every frame batch: ONE copy of the descriptor table into the handle's table of its kind, ONE launch reading it.
@@ -146,19 +143,11 @@ static int submit_frames(yfv2_handle h, const std::vector<D>& table, void* d_tab
   return YFV2_OK;
 }
 
-// Uploads the table the resize kernel of the batch's kind reads and enqueues that ONE launch into dst; everything was checked.
-static int enqueue_resize(yfv2_handle h, const FrameBatch& fb, int32_t B, uint8_t* dst, hipStream_t s) {
-  const int H = h->cfg.height, W = h->cfg.width;
-  if (fb.yuv.empty())
-    return submit_frames(h, fb.t, h->d_frames, B, s, [&](const ResizeFrame* d) { yfv2_launch_resize_frames(d, B, fb.max_w, dst, H, W, s); });
-  return submit_frames(h, fb.yuv, h->d_frames_yuv, B, s, [&](const ResizeFrameYuv* d) { yfv2_launch_resize_frames_yuv(d, B, fb.max_w, dst, H, W, s); });
-}
-
-// The training batch of a checked frame batch: each descriptor with its frame's (alpha, beta) behind it (NULL, NULL: the identity),
-// through the same submit - the pair travels in the one descriptor copy.
-template <class T, class D>
-static std::vector<T> with_augment(const std::vector<D>& src, const float* alpha, const float* beta) {
-  std::vector<T> t(src.size());
+// A descriptor table with each frame's (alpha, beta) behind its descriptor (NULL, NULL: the identity): the training rows' table - the
+// pair travels in the one descriptor copy.
+template <class D>
+static auto with_augment(const std::vector<D>& src, const float* alpha, const float* beta) {
+  std::vector<std::conditional_t<std::is_same_v<D, ResizeFrame>, TrainFrame, TrainFrameYuv>> t(src.size());
   for (size_t b = 0; b < src.size(); ++b) {
     static_cast<D&>(t[b]) = src[b];
     t[b].alpha = alpha ? alpha[b] : 1.0f;
@@ -167,13 +156,17 @@ static std::vector<T> with_augment(const std::vector<D>& src, const float* alpha
   return t;
 }
 
-static int enqueue_train_batch(yfv2_handle h, const FrameBatch& fb, int32_t B, const float* alpha, const float* beta, float* dst, hipStream_t s) {
-  const int H = h->cfg.height, W = h->cfg.width;
-  if (fb.yuv.empty())
-    return submit_frames(h, with_augment<TrainFrame>(fb.t, alpha, beta), h->d_frames, B, s,
-                         [&](const TrainFrame* d) { yfv2_launch_train_batch_frames(d, B, fb.max_w, dst, H, W, s); });
-  return submit_frames(h, with_augment<TrainFrameYuv>(fb.yuv, alpha, beta), h->d_frames_yuv, B, s,
-                       [&](const TrainFrameYuv* d) { yfv2_launch_train_batch_frames_yuv(d, B, fb.max_w, dst, H, W, s); });
+// Uploads the table the row kernel of the batch's kind reads and enqueues that ONE launch into dst; everything was checked.
+// rows: YFV2_ROWS_U8, the resized batch, or YFV2_ROWS_TRAIN, the training batch of (alpha, beta).
+static int enqueue_rows(yfv2_handle h, const FrameBatch& fb, int32_t B, Yfv2RowKind rows, void* dst, hipStream_t s, const float* alpha = nullptr,
+                        const float* beta = nullptr) {
+  const bool yuv = !fb.yuv.empty();
+  auto submit = [&](const auto& table, void* d_table) {     // the batch's table, the handle's device table of its kind
+    auto launch = [&](const void* d) { yfv2_launch_rows(rows, yuv, d, B, fb.max_w, dst, h->cfg.height, h->cfg.width, s); };
+    if (rows == YFV2_ROWS_TRAIN) return submit_frames(h, with_augment(table, alpha, beta), d_table, B, s, launch);
+    return submit_frames(h, table, d_table, B, s, launch);
+  };
+  return yuv ? submit(fb.yuv, h->d_frames_yuv) : submit(fb.t, h->d_frames);
 }
 
 template <class Kind>
@@ -184,7 +177,7 @@ static int resize_frames(yfv2_handle h, const char* what, const typename Kind::F
   FrameBatch fb;
   if (int rc = check_frames<Kind>(h, what, frames, B, fb)) return rc;
   DeviceGuard guard(h->device);
-  return enqueue_resize(h, fb, B, dst, static_cast<hipStream_t>(stream));
+  return enqueue_rows(h, fb, B, YFV2_ROWS_U8, dst, static_cast<hipStream_t>(stream));
 }
 
 // yfv2_train_batch_frames_u8 / _yuv: its own arguments first, then check_frames, then each frame's pair; then the one submit.
@@ -197,12 +190,12 @@ static int train_batch_frames(yfv2_handle h, const char* what, const typename Ki
   if ((reinterpret_cast<uintptr_t>(dst) & 15) != 0) return fail(h, YFV2_ERR_ARG, w_ + ": dst must be 16-byte aligned");
   if (!alpha != !beta) return fail(h, YFV2_ERR_ARG, w_ + ": alpha and beta must both be given or both be NULL");
   FrameBatch fb;
-  if (int rc = check_frames<Kind>(h, what, frames, B, fb)) return rc;
+  if (int rc = check_frames<Kind>(h, what, frames, B, fb, YFV2_ROWS_TRAIN)) return rc;
   for (int32_t b = 0; alpha && b < B; ++b)
     if (!std::isfinite(alpha[b]) || !std::isfinite(beta[b]))
       return fail(h, YFV2_ERR_ARG, w_ + ": frame " + std::to_string(b) + ": alpha and beta must be finite numbers");
   DeviceGuard guard(h->device);
-  return enqueue_train_batch(h, fb, B, alpha, beta, dst, static_cast<hipStream_t>(stream));
+  return enqueue_rows(h, fb, B, YFV2_ROWS_TRAIN, dst, static_cast<hipStream_t>(stream), alpha, beta);
 }
 
 // What every detection on frames does once they are checked and expanded: the handle's resized batch, the resize, then
@@ -214,7 +207,7 @@ static int detect_frames_tail(yfv2_handle h, const FrameBatch& fb, int32_t B, fl
   DeviceGuard guard(h->device);
   if (int rc = h->frames_u8.reserve(h, (size_t)h->cfg.height * h->cfg.width * 3 * (size_t)h->cfg.max_batch, true)) return rc;   // the resized batch
   if (!fb.yuv.empty()) HIP_TRY(h, hipMemcpyAsync(h->d_frames, fb.t.data(), sizeof(ResizeFrame) * (size_t)B, hipMemcpyHostToDevice, s));
-  if (int rc = enqueue_resize(h, fb, B, h->frames_u8.as<uint8_t>(), s)) return rc;
+  if (int rc = enqueue_rows(h, fb, B, YFV2_ROWS_U8, h->frames_u8.as<uint8_t>(), s)) return rc;
   if (int rc = yfv2_detect_u8(h, h->frames_u8.as<uint8_t>(), B, conf_thres, iou_thres, dets, idx, count, stream)) return rc;
   yfv2_launch_frame_boxes(dets, count, h->d_frames, B, s);
   HIP_TRY(h, hipGetLastError());
@@ -238,18 +231,10 @@ static int detect_frames(yfv2_handle h, const char* what, const typename Kind::F
 constexpr int CROP_MAX_R = 4096;
 constexpr double CROP_MAX_PAD = 16.0;
 
-// yfv2_crop_tensors_u8 / _yuv are the same template with `tensor` given: `crops` is then the fp32 / fp16 tensor,
-// 16-byte aligned, the frames are held to the tensor rows' width limit (Kind below) and the plan and the resize launch are the
+// yfv2_crop_tensors_u8 / _yuv are the same template with `tensor` given (its dtype checked): `crops` is then the
+// fp32 / fp16 tensor, 16-byte aligned, the frames are held to the tensor rows' width limit and the plan and the row launch are the
 // tensor kinds'.  tensor == nullptr is yfv2_crop_detections_*, check for check and launch for launch what it was.
-template <class Base, bool Half>
-struct TensorFrames : Base {
-  static int max_width(int W) {
-    if constexpr (std::is_same_v<Base, BgrFrames>) return yfv2_crop_tensor_max_width(W, Half);
-    else return yfv2_crop_tensor_yuv_max_width(W, Half);
-  }
-};
-
-template <class Kind, class Limit = Kind>
+template <class Kind>
 static int crop_detections(yfv2_handle h, const char* what, const typename Kind::Frame* frames, int32_t B, const float* dets, const int32_t* count, int32_t R,
                            const yfv2_crop_rule* rule, void* crops, int32_t* crop_src, int32_t* crop_rect, int32_t* crop_offset, int32_t* crop_skipped,
                            int32_t cap, void* stream, const yfv2_crop_tensor* tensor = nullptr) {
@@ -285,8 +270,9 @@ static int crop_detections(yfv2_handle h, const char* what, const typename Kind:
       a.classes[c >> 5] |= 1u << (c & 31);
     }
   }
+  const Yfv2RowKind rows = !tensor ? YFV2_ROWS_COUNTED_U8 : tensor->dtype == YFV2_F16 ? YFV2_ROWS_TENSOR_F16 : YFV2_ROWS_TENSOR_F32;
   FrameBatch fb;
-  if (int rc = check_frames<Limit>(h, what, frames, B, fb, q.out_h, q.out_w)) return rc;
+  if (int rc = check_frames<Kind>(h, what, frames, B, fb, rows, q.out_h, q.out_w)) return rc;
   if ((long long)B * R > 0x7fffffffll) return fail(h, YFV2_ERR_ARG, w_ + ": B * R above 2^31 - 1");
   DeviceGuard guard(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
@@ -302,44 +288,27 @@ static int crop_detections(yfv2_handle h, const char* what, const typename Kind:
   a.skipped = crop_skipped; a.cap = cap; a.head = reinterpret_cast<CountedHead*>(base + n_bytes);
   void* table = base + n_bytes + sizeof(CountedHead);
   if (tensor) {
-    const bool half = tensor->dtype == YFV2_F16;
     for (int c = 0; c < 3; ++c) { a.p.mean[c] = tensor->mean[c]; a.p.std[c] = tensor->std[c]; }
     a.p.fill = (uint32_t)tensor->fill[0] | (uint32_t)tensor->fill[1] << 8 | (uint32_t)tensor->fill[2] << 16;
     a.p.rgb = tensor->rgb; a.letterbox = tensor->letterbox;
-    if (fb.yuv.empty())
-      return submit_frames(h, fb.t, h->d_frames, B, s, [&](const ResizeFrame* d) {
-        yfv2_launch_crop_tensor_plan(a, d, static_cast<TensorFrame*>(table), s);
-        yfv2_launch_crop_tensors(static_cast<const TensorFrame*>(table), cap, fb.max_w, crops, half, q.out_h, q.out_w, s);
-      });
-    return submit_frames(h, fb.yuv, h->d_frames_yuv, B, s, [&](const ResizeFrameYuv* d) {
-      yfv2_launch_crop_tensor_plan_yuv(a, d, static_cast<TensorFrameYuv*>(table), s);
-      yfv2_launch_crop_tensors_yuv(static_cast<const TensorFrameYuv*>(table), cap, fb.max_w, crops, half, q.out_h, q.out_w, s);
-    });
   }
-  uint8_t* crops_u8 = static_cast<uint8_t*>(crops);
-  if (fb.yuv.empty())
-    return submit_frames(h, fb.t, h->d_frames, B, s, [&](const ResizeFrame* d) {
-      yfv2_launch_crop_plan(a, d, static_cast<CropFrame*>(table), s);
-      yfv2_launch_resize_crops(static_cast<const CropFrame*>(table), cap, fb.max_w, crops_u8, q.out_h, q.out_w, s);
-    });
-  return submit_frames(h, fb.yuv, h->d_frames_yuv, B, s, [&](const ResizeFrameYuv* d) {
-    yfv2_launch_crop_plan_yuv(a, d, static_cast<CropFrameYuv*>(table), s);
-    yfv2_launch_resize_crops_yuv(static_cast<const CropFrameYuv*>(table), cap, fb.max_w, crops_u8, q.out_h, q.out_w, s);
-  });
+  const bool yuv = !fb.yuv.empty();
+  auto launch = [&](const void* d) {       // the plan's two launches, then the rows of the table they wrote
+    yfv2_launch_crop_plan(a, tensor != nullptr, yuv, d, table, s);
+    yfv2_launch_rows(rows, yuv, table, cap, fb.max_w, crops, q.out_h, q.out_w, s);
+  };
+  return yuv ? submit_frames(h, fb.yuv, h->d_frames_yuv, B, s, launch) : submit_frames(h, fb.t, h->d_frames, B, s, launch);
 }
 
-// the tensor entry points: the handle, the struct and its dtype, which picks the width limit; then the template above
+// the tensor entry points: the handle, the struct and its dtype, which picks the row kind; then the template above
 template <class Kind>
 static int crop_tensors(yfv2_handle h, const char* what, const typename Kind::Frame* frames, int32_t B, const float* dets, const int32_t* count, int32_t R,
                         const yfv2_crop_rule* rule, const yfv2_crop_tensor* tensor, void* out, int32_t* crop_src, int32_t* crop_rect, int32_t* crop_offset,
                         int32_t* crop_skipped, int32_t cap, void* stream) {
   if (!h) return fail(nullptr, YFV2_ERR_ARG, "null handle");
   if (!tensor) return fail(h, YFV2_ERR_ARG, std::string(what) + ": null pointer");
-  if (tensor->dtype == YFV2_F32)
-    return crop_detections<Kind, TensorFrames<Kind, false>>(h, what, frames, B, dets, count, R, rule, out, crop_src, crop_rect, crop_offset, crop_skipped, cap, stream, tensor);
-  if (tensor->dtype == YFV2_F16)
-    return crop_detections<Kind, TensorFrames<Kind, true>>(h, what, frames, B, dets, count, R, rule, out, crop_src, crop_rect, crop_offset, crop_skipped, cap, stream, tensor);
-  return fail(h, YFV2_ERR_ARG, std::string(what) + ": dtype must be YFV2_F32 or YFV2_F16");
+  if (tensor->dtype != YFV2_F32 && tensor->dtype != YFV2_F16) return fail(h, YFV2_ERR_ARG, std::string(what) + ": dtype must be YFV2_F32 or YFV2_F16");
+  return crop_detections<Kind>(h, what, frames, B, dets, count, R, rule, out, crop_src, crop_rect, crop_offset, crop_skipped, cap, stream, tensor);
 }
 
 extern "C" {
@@ -499,8 +468,8 @@ int yfv2_resize_u8(yfv2_handle h, const uint8_t* src, int32_t B, int32_t src_h, 
   if (!h) return fail(nullptr, YFV2_ERR_ARG, "null handle");
   if (!src || !dst || B < 1 || src_h < 1 || src_w < 1) return fail(h, YFV2_ERR_ARG, "yfv2_resize_u8: bad argument");
   if ((reinterpret_cast<uintptr_t>(dst) & 3) != 0) return fail(h, YFV2_ERR_ARG, "yfv2_resize_u8: dst must be 4-byte aligned");
-  if (yfv2_resize_lds_bytes(src_w, h->cfg.width) > (size_t)YFV2_LDS_FULL || (long long)B * h->cfg.height > 0x7fffffffll)
-    return fail(h, YFV2_ERR_ARG, "yfv2_resize_u8: source rows wider than " + std::to_string(yfv2_resize_max_width(h->cfg.width)) + " pixels are not supported");
+  if (yfv2_rows_lds_bytes(YFV2_ROWS_U8, false, src_w, h->cfg.width) > (size_t)YFV2_LDS_FULL || (long long)B * h->cfg.height > 0x7fffffffll)
+    return fail(h, YFV2_ERR_ARG, "yfv2_resize_u8: source rows wider than " + std::to_string(yfv2_rows_max_width(YFV2_ROWS_U8, false, h->cfg.width)) + " pixels are not supported");
   DeviceGuard guard(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const FrameScales sc = frame_scales(src_w, src_h, h->cfg.width, h->cfg.height);
@@ -521,11 +490,11 @@ int yfv2_resize_frames_yuv(yfv2_handle h, const yfv2_frame_yuv* frames, int32_t 
 }
 
 int yfv2_train_batch_frames_u8(yfv2_handle h, const yfv2_frame* frames, int32_t B, const float* alpha, const float* beta, float* dst, void* stream) {
-  return train_batch_frames<TrainBgrFrames>(h, "yfv2_train_batch_frames_u8", frames, B, alpha, beta, dst, stream);
+  return train_batch_frames<BgrFrames>(h, "yfv2_train_batch_frames_u8", frames, B, alpha, beta, dst, stream);
 }
 
 int yfv2_train_batch_frames_yuv(yfv2_handle h, const yfv2_frame_yuv* frames, int32_t B, const float* alpha, const float* beta, float* dst, void* stream) {
-  return train_batch_frames<TrainYuvFrames>(h, "yfv2_train_batch_frames_yuv", frames, B, alpha, beta, dst, stream);
+  return train_batch_frames<YuvFrames>(h, "yfv2_train_batch_frames_yuv", frames, B, alpha, beta, dst, stream);
 }
 
 int yfv2_detect_frames_u8(yfv2_handle h, const yfv2_frame* frames, int32_t B, float conf_thres, double iou_thres, float* dets,
@@ -789,7 +758,7 @@ int yfv2_detect_deploy_frames_u8(yfv2_handle h, const yfv2_frame* frames, int32_
   }
   float* d_scale = reinterpret_cast<float*>(h->deploy_word.as<char>() + 16);
   HIP_TRY(h, hipMemcpyAsync(d_scale, sc.data(), sizeof(float) * sc.size(), hipMemcpyHostToDevice, s));
-  if ((rc = enqueue_resize(h, fb, B, h->frames_u8.as<uint8_t>(), s))) return rc;
+  if ((rc = enqueue_rows(h, fb, B, YFV2_ROWS_U8, h->frames_u8.as<uint8_t>(), s))) return rc;
   float* out6[6];
   for (int i = 0; i < 6; ++i) out6[i] = h->ws.logits[i].p;
   if ((rc = yfv2_forward_u8(h, h->frames_u8.as<uint8_t>(), B, out6, stream))) return rc;   // (on the handle's lanes where the plan has them)

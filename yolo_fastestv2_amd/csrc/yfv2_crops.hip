@@ -146,12 +146,15 @@ __global__ __launch_bounds__(CP_THREADS) void crop_plan_kernel(typename Kind::Ar
 }
 
 template <class Kind>
-static void launch_crop_plan(const typename Kind::Args& a, const typename Kind::Frame* frames, typename Kind::Out* table, hipStream_t s) {
-  YFV2_LAUNCH((crop_plan_kernel<Kind, false>), dim3((unsigned)a.B), dim3(CP_THREADS), 0, s, a, frames, table);
-  YFV2_LAUNCH((crop_plan_kernel<Kind, true>), dim3((unsigned)a.B), dim3(CP_THREADS), 0, s, a, frames, table);
+static void launch_crop_plan(const typename Kind::Args& a, const void* frames, void* table, hipStream_t s) {
+  const auto* f = static_cast<const typename Kind::Frame*>(frames);
+  auto* t = static_cast<typename Kind::Out*>(table);
+  YFV2_LAUNCH((crop_plan_kernel<Kind, false>), dim3((unsigned)a.B), dim3(CP_THREADS), 0, s, a, f, t);
+  YFV2_LAUNCH((crop_plan_kernel<Kind, true>), dim3((unsigned)a.B), dim3(CP_THREADS), 0, s, a, f, t);
 }
 
-void yfv2_launch_crop_plan(const CropPlanArgs& a, const ResizeFrame* frames, CropFrame* table, hipStream_t s) { launch_crop_plan<CropBgr>(a, frames, table, s); }
-void yfv2_launch_crop_plan_yuv(const CropPlanArgs& a, const ResizeFrameYuv* frames, CropFrameYuv* table, hipStream_t s) { launch_crop_plan<CropYuv>(a, frames, table, s); }
-void yfv2_launch_crop_tensor_plan(const CropTensorPlanArgs& a, const ResizeFrame* frames, TensorFrame* table, hipStream_t s) { launch_crop_plan<TensorBgr>(a, frames, table, s); }
-void yfv2_launch_crop_tensor_plan_yuv(const CropTensorPlanArgs& a, const ResizeFrameYuv* frames, TensorFrameYuv* table, hipStream_t s) { launch_crop_plan<TensorYuv>(a, frames, table, s); }
+// the crop kinds take a's CropPlanArgs part: their kernels' arguments are what they were
+void yfv2_launch_crop_plan(const CropTensorPlanArgs& a, bool tensor, bool yuv, const void* frames, void* table, hipStream_t s) {
+  if (!tensor) !yuv ? launch_crop_plan<CropBgr>(a, frames, table, s) : launch_crop_plan<CropYuv>(a, frames, table, s);
+  else !yuv ? launch_crop_plan<TensorBgr>(a, frames, table, s) : launch_crop_plan<TensorYuv>(a, frames, table, s);
+}

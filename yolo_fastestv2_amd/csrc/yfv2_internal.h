@@ -334,9 +334,24 @@ struct ResizeArgs {
   int B, SH, SW, H, W;
   double scale_x, scale_y;   // 1 / (W / SW), 1 / (H / SH) in double, like cv::resize derives them
 };
-size_t yfv2_resize_lds_bytes(int SW, int W);
-int yfv2_resize_max_width(int W);   // the width limit of the ragged B, G, R entry points: (YFV2_LDS_FULL - 3 W) / 6 - 2
-void yfv2_launch_resize(const ResizeArgs& a, hipStream_t s);
+void yfv2_launch_resize(const ResizeArgs& a, hipStream_t s);   // LDS: yfv2_rows_lds_bytes(YFV2_ROWS_U8, false, a.SW, a.W)
+// The row kernels of a ragged batch (yfv2_pre.hip): one workgroup per (table entry, output row) resizes a frame's row and hands it
+// to the epilogue of its row kind.  A kind and a YUV flag name the instantiation and with it the table's descriptor type and dst's
+// element type; yfv2_pre.hip holds the one description of each (its LDS layout, hence its bytes and its width limit).
+enum Yfv2RowKind {         // descriptor (B, G, R / YUV)            dst
+  YFV2_ROWS_U8,            // ResizeFrame / ResizeFrameYuv          uint8 (n, H, W, 3), 4-byte aligned
+  YFV2_ROWS_COUNTED_U8,    // CropFrame / CropFrameYuv              uint8 (n, H, W, 3): the live entries of a counted table
+  YFV2_ROWS_TRAIN,         // TrainFrame / TrainFrameYuv            fp32 (n, 3, H, W), 16-byte aligned
+  YFV2_ROWS_TENSOR_F32,    // TensorFrame / TensorFrameYuv          fp32 (n, 3, H, W), 16-byte aligned: the live entries, letterboxed
+  YFV2_ROWS_TENSOR_F16,    // likewise                              fp16
+};
+constexpr int YFV2_ROW_KINDS = 5;
+// grid n * H (n: the batch, or a counted table's capacity), LDS for a source row of max_w pixels
+void yfv2_launch_rows(Yfv2RowKind kind, bool yuv, const void* table, int n, int max_w, void* dst, int H, int W, hipStream_t s);
+size_t yfv2_rows_lds_bytes(Yfv2RowKind kind, bool yuv, int w, int W);   // LDS of one workgroup for a frame w pixels wide, output rows of W
+// The widest frame the entry points of the kind admit.  B, G, R: (YFV2_LDS_FULL - the row's own bytes) / 6 - (ALIGN + 2) / 3, every
+// row up to it fits; YUV: the widest frame that fits.  A 16-byte kind never admits a frame that the uint8 kinds refuse at the same W.
+int yfv2_rows_max_width(Yfv2RowKind kind, bool yuv, int W);
 // one frame of a ragged batch (yfv2_resize_frames_u8 / yfv2_detect_frames_u8), expanded on the host and uploaded as a table
 struct ResizeFrame {
   const unsigned char* data;  // first byte of the frame (any alignment), device
@@ -345,7 +360,6 @@ struct ResizeFrame {
   double scale_x, scale_y;    // resize: 1 / (W / w), 1 / (H / h), as ResizeArgs
   double box_x, box_y;        // frame-coordinate epilogue: w / W, h / H (test.py:58)
 };
-void yfv2_launch_resize_frames(const ResizeFrame* frames, int B, int max_w, unsigned char* dst, int H, int W, hipStream_t s);
 // one YUV 4:2:0 frame of a ragged batch (yfv2_resize_frames_yuv / yfv2_detect_frames_yuv): the caller's yfv2_frame_yuv with its
 // origin folded into the plane pointers on the host - pixel (r, c) of the frame has its luma at y[r * pitch_y + c] and its chroma
 // at row (r + py) >> 1, sample (c + px) >> 1 of ca / cb - so the kernel sees every frame, crop or not, as a plane set of its own
@@ -375,22 +389,13 @@ __host__ __device__ inline void yfv2_yuv_move(ResizeFrameYuv& r, int dx, int dy)
 // The resize scale of one axis, `in` source pixels to `out`: cv::resize's inv_scale = dsize / ssize, scale = 1 / inv_scale, two
 // correctly rounded fp64 divisions on either side (no unit that calls it has a fast-math flag).
 __host__ __device__ inline double yfv2_resize_scale(int out, int in) { return 1.0 / ((double)out / (double)in); }
-size_t yfv2_resize_yuv_lds_bytes(int w, int W);   // LDS of one workgroup of the YUV resize for a frame w pixels wide
-int yfv2_resize_yuv_max_width(int W);             // the widest frame whose workgroup fits YFV2_LDS_FULL
 YuvCoef yfv2_yuv_coef(int colour);                // YFV2_BT601_LIMITED .. YFV2_BT709_FULL -> its row
-void yfv2_launch_resize_frames_yuv(const ResizeFrameYuv* frames, int B, int max_w, unsigned char* dst, int H, int W, hipStream_t s);
 // The training entry points (yfv2_train_batch_frames_u8 / _yuv): a frame's resize descriptor with its contrast / brightness pair
 // behind it, in the same table and the same one copy (the handle's tables are sized for these).  The resize kernels keep their own
 // descriptors and strides; the training kernels run the same body on the base part.
 struct TrainFrame : ResizeFrame { float alpha, beta; };
 struct TrainFrameYuv : ResizeFrameYuv { float alpha, beta; };
-size_t yfv2_train_batch_lds_bytes(int SW, int W);   // LDS of one workgroup: the resize's staging slots, the 256-entry fp32 table, three fp32 planes of W
-int yfv2_train_batch_max_width(int W);              // (YFV2_LDS_FULL - 1024 - 12 W) / 6 - 6, below yfv2_resize_max_width(W)
-size_t yfv2_train_batch_yuv_lds_bytes(int w, int W);
-int yfv2_train_batch_yuv_max_width(int W);          // the widest YUV frame that fits, <= yfv2_resize_yuv_max_width(W)
-void yfv2_launch_train_batch_frames(const TrainFrame* frames, int B, int max_w, float* dst /* (B,3,H,W), 16-byte aligned */, int H, int W, hipStream_t s);
-void yfv2_launch_train_batch_frames_yuv(const TrainFrameYuv* frames, int B, int max_w, float* dst, int H, int W, hipStream_t s);
-// ---- second-stage crops (yfv2_crop_detections_u8 / _yuv; kernels: yfv2_crops.hip, the resize launch: yfv2_pre.hip)
+// ---- second-stage crops (yfv2_crop_detections_u8 / _yuv; kernels: yfv2_crops.hip, the resize launch: yfv2_launch_rows)
 // THE RECTANGLE RULE, one axis of it, written once: yfv2_crop_rect (host) and the plan kernels (device) both call this function;
 // include/yfv2.h states it for callers, tests/crops_model.py in Python.  a1, a2: the box's two edges on the axis; pad: the factor;
 // n: the frame's length.  IEEE double throughout, every operation rounded on its own (the pragma holds whatever the unit's flags).
@@ -438,11 +443,6 @@ struct CropPlanArgs {
   int cap;
   CountedHead* head;           // directly in front of the descriptor table
 };
-void yfv2_launch_crop_plan(const CropPlanArgs& a, const ResizeFrame* frames, CropFrame* table, hipStream_t s);          // two launches
-void yfv2_launch_crop_plan_yuv(const CropPlanArgs& a, const ResizeFrameYuv* frames, CropFrameYuv* table, hipStream_t s);
-// the resize of the live entries of a counted table into crops (cap, H, W, 3): grid cap * H, LDS for a source row of max_w pixels
-void yfv2_launch_resize_crops(const CropFrame* table, int cap, int max_w, unsigned char* crops, int H, int W, hipStream_t s);
-void yfv2_launch_resize_crops_yuv(const CropFrameYuv* table, int cap, int max_w, unsigned char* crops, int H, int W, hipStream_t s);
 // ---- second-stage crops as network input (yfv2_crop_tensors_u8 / _yuv): the same plan, the same resize body, the
 // row leaves as fp32 / fp16 planes.  THE TWO RULES of it, each written once: yfv2_crop_letterbox / yfv2_crop_tensor_value (host) and
 // the kernels (device) call these functions; include/yfv2.h states them for callers, tests/crop_tensors_model.py in numpy.
@@ -486,18 +486,10 @@ template <class D> struct Letterboxed : Counted<D> { int ox0, oy0, iw, ih; stati
 using TensorFrame = Letterboxed<ResizeFrame>;
 using TensorFrameYuv = Letterboxed<ResizeFrameYuv>;
 struct CropTensorPlanArgs : CropPlanArgs { CropTensorParams p; int letterbox; };   // the crop kinds' arguments stay what they were
-void yfv2_launch_crop_tensor_plan(const CropTensorPlanArgs& a, const ResizeFrame* frames, TensorFrame* table, hipStream_t s);
-void yfv2_launch_crop_tensor_plan_yuv(const CropTensorPlanArgs& a, const ResizeFrameYuv* frames, TensorFrameYuv* table, hipStream_t s);
-// LDS of one workgroup: the staging slots rounded to 16 bytes, three planes of W fp32 (half = false) or fp16 values; and the widest
-// frame that fits - (YFV2_LDS_FULL - 3 W e) / 6 - 6 for B, G, R frames (e = 4 or 2), walked for YUV frames.  Neither exceeds the
-// limit of yfv2_crop_detections_* at the same W.
-size_t yfv2_crop_tensor_lds_bytes(int SW, int W, bool half);
-int yfv2_crop_tensor_max_width(int W, bool half);
-size_t yfv2_crop_tensor_yuv_lds_bytes(int w, int W, bool half);
-int yfv2_crop_tensor_yuv_max_width(int W, bool half);
-// the live entries of a tensor table into out (cap, 3, H, W), fp32 or fp16, 16-byte aligned: grid cap * H
-void yfv2_launch_crop_tensors(const TensorFrame* table, int cap, int max_w, void* out, bool half, int H, int W, hipStream_t s);
-void yfv2_launch_crop_tensors_yuv(const TensorFrameYuv* table, int cap, int max_w, void* out, bool half, int H, int W, hipStream_t s);
+// The plan of either family, two launches: frames = the batch's ResizeFrame / ResizeFrameYuv table (yuv), table = the counted table
+// it writes - CropFrame / CropFrameYuv, whose kernels take the CropPlanArgs part of a by value, or (tensor) TensorFrame /
+// TensorFrameYuv.  The rows of the table's live entries are then yfv2_launch_rows' (YFV2_ROWS_COUNTED_U8, YFV2_ROWS_TENSOR_*).
+void yfv2_launch_crop_plan(const CropTensorPlanArgs& a, bool tensor, bool yuv, const void* frames, void* table, hipStream_t s);
 // ---- the per-stream IoU tracker (yfv2_track_update; kernel and the IoU's one function: yfv2_track.hip)
 constexpr int TRACK_MAX_R = 4096, TRACK_MAX_M = 1024;
 constexpr int TRACK_HEADER = 8, TRACK_SLOT = 10;     // int32 words of a stream's header and of one slot (include/yfv2.h)

@@ -12,11 +12,23 @@
 // with aligned 4-byte loads (source row starts are arbitrary byte addresses), the blend reads LDS bytes, the output row
 // is assembled in LDS and leaves as aligned 4-byte stores (width % 4 == 0, so every output row starts 4-byte aligned).
 // Built with -ffp-contract=off: the coefficient arithmetic must round like the separate C operations it restates.
+//
+// The ragged-batch kernels are two templates over <Frame, Row> - the descriptor (B, G, R or YUV; plain, counted, with an augmentation
+// pair, letterboxed) and where the blended row goes (uint8 batch, fp32 training batch, fp32 / fp16 tensor) - in ten instantiations.
+// Each output kind is described ONCE: the Row states its ALIGN and its own LDS bytes, yfv2_slot places the staging slots for kernel and
+// host alike, FrameRows<Frame> gives the launch's LDS and the width limit of the frame kind, launch_rows<Frame, Row> is the one launch
+// body.  Other units reach the family through Yfv2RowKind, a YUV flag and yfv2_launch_rows / yfv2_rows_lds_bytes / yfv2_rows_max_width
+// (yfv2_internal.h); yfv2_debug_rows shows the last two to tests/test_rows_host.py, which sweeps them against tests/rows_model.py.
 #include <algorithm>
 #include <type_traits>
 
 #include "../../include/yfv2.h"
 #include "yfv2_device.h"
+
+// A staged source row in LDS: its bytes, up to 3 more in front (the row starts at any byte, the staging loads are aligned dwords),
+// rounded up to `align` - 4, or what the Row behind the slots needs.  THE layout function: the kernels place their slots with it and
+// the host sizes the launch with it (FrameRows below), so the two cannot drift apart.
+__host__ __device__ constexpr int yfv2_slot(int bytes, int align) { return (bytes + 3 + align - 1) & ~(align - 1); }
 
 struct RowCoef { int s0, s1, c0, c1; };
 
@@ -58,6 +70,7 @@ __device__ __forceinline__ void yfv2_emit_row(const unsigned char* OUT, unsigned
 // Those kernels are templates over their frame descriptor and a Row.  The kernel hands the Row the LDS behind its staging slots
 // (ALIGN-byte aligned; the slots are rounded to it): begin, before the staging barrier; put, every blended byte (output column ox,
 // channel c); end, the row is complete.  Everything in front of the Row - staging, guards, coefficients, blend - is the one body.
+// A Row also states what the host needs of it: ALIGN and lds_bytes(W), its own LDS behind the slots for an output row of W pixels.
 //
 // RowU8: the uint8 (B, H, W, 3) batch of the resize entry points.  The row is assembled in LDS and leaves through yfv2_emit_row.
 template <int THREADS>
@@ -65,6 +78,7 @@ struct RowU8 {
   using Out = unsigned char;
   static constexpr int ALIGN = 4;
   static constexpr bool AUGMENT = false;
+  __host__ __device__ static constexpr int lds_bytes(int W) { return 3 * W; }
   unsigned char* dst;
   __device__ __forceinline__ void put(unsigned char* lds, int ox, int c, int W, unsigned char v) { lds[ox * 3 + c] = v; }
   __device__ __forceinline__ void end(const unsigned char* lds, int b, int oy, int H, int W) { yfv2_emit_row<THREADS>(lds, dst, b, oy, H, W); }
@@ -85,7 +99,7 @@ __device__ __forceinline__ float yfv2_aug_entry(int a, float alpha, float beta) 
   return __fdiv_rn((float)q, 255.f);
 }
 
-// RowTrain: the fp32 (B, 3, H, W) batch of the training entry points (train_batch_frames_u8_kernel / _yuv_kernel below).  Its LDS:
+// RowTrain: the fp32 (B, 3, H, W) batch of the training entry points (the <TrainFrame, RowTrain> / <TrainFrameYuv, RowTrain> instantiations below).  Its LDS:
 // the frame's table, filled by the workgroup itself before the staging barrier, then the row as three planes of W floats - the
 // byte -> plane transposition: a thread's B, G, R of column ox go to planes[c][ox] (consecutive lanes, consecutive words).  After
 // a barrier the planes leave as 16-byte stores, three contiguous runs of W floats out[b][c][oy][0 .. W): W % 32 == 0 and dst is
@@ -95,6 +109,7 @@ struct RowTrain {
   using Out = float;
   static constexpr int ALIGN = 16;
   static constexpr bool AUGMENT = true;
+  __host__ __device__ static constexpr int lds_bytes(int W) { return YFV2_AUG_TABLE_BYTES + 3 * W * (int)sizeof(float); }
   float* dst;
   __device__ __forceinline__ void begin(unsigned char* lds, float alpha, float beta) {
     for (int a = threadIdx.x; a < 256; a += THREADS) reinterpret_cast<float*>(lds)[a] = yfv2_aug_entry(a, alpha, beta);
@@ -129,6 +144,7 @@ struct RowTensor {
   static constexpr bool AUGMENT = false;
   static constexpr bool TENSOR = true;
   static constexpr int N16 = 16 / (int)sizeof(Out);   // values of a 16-byte store
+  __host__ __device__ static constexpr int lds_bytes(int W) { return 3 * W * (int)sizeof(Out); }
   Out* dst;
   float mean[3], std[3];      // by byte channel (B, G, R)
   int fill[3];
@@ -192,7 +208,7 @@ __global__ __launch_bounds__(256) void resize_u8_kernel(ResizeArgs a) {
   const int b = blockIdx.x / a.H, oy = blockIdx.x - b * a.H;
   const RowCoef ry = yfv2_axis_coef(oy, a.scale_y, a.SH, false);
   const int row_bytes = a.SW * 3;
-  const int slot = (row_bytes + 3 + 3) & ~3;          // staged bytes per source row (head misalignment + tail round-up)
+  const int slot = yfv2_slot(row_bytes, 4);           // staged bytes per source row (head misalignment + tail round-up)
   unsigned char* R0 = smem;
   unsigned char* R1 = smem + slot;
   unsigned char* OUT = smem + 2 * slot;
@@ -244,7 +260,7 @@ __global__ __launch_bounds__(256) void resize_u8_kernel(ResizeArgs a) {
 // The kernel is a template over the descriptor and the epilogue (Row, above) - a template, not a shared function called by two
 // kernels: a function boundary alone reorders the uint8 instantiation's blend (profiles/train_batch_isa.txt), and the uint8
 // instantiation <ResizeFrame, RowU8> must stay the instruction stream it was.  <TrainFrame, RowTrain> is the training entry point's
-// launch (train_batch_frames_u8_kernel below): the same staging, guards, coefficients and blend, so its batch is the resize's
+// launch: the same staging, guards, coefficients and blend, so its batch is the resize's
 // bytes looked up in the frame's table.
 // A third pair of instantiations reads a table the DEVICE wrote (second-stage crops, yfv2_crops.hip): descriptors
 // Counted<...> with a CountedHead in front of entry 0.  The host does not know how many entries are live, so the grid covers the
@@ -278,7 +294,7 @@ __global__ __launch_bounds__(RF_THREADS, 6) void resize_frames_u8_kernel(const F
   }
   const RowCoef ry = yfv2_axis_coef(iy, f.scale_y, f.h, false);
   const int row_bytes = f.w * 3;
-  const int slot = (row_bytes + 3 + Row::ALIGN - 1) & ~(Row::ALIGN - 1);
+  const int slot = yfv2_slot(row_bytes, Row::ALIGN);
   unsigned char* R0 = smem;
   unsigned char* R1 = smem + slot;
   unsigned char* OUT = smem + 2 * slot;
@@ -330,9 +346,6 @@ __global__ __launch_bounds__(RF_THREADS, 6) void resize_frames_u8_kernel(const F
   row.end(OUT, b, oy, H, W);
 }
 
-// yfv2_train_batch_frames_u8's launch (a trace names it resize_frames_u8_kernel<TrainFrame, RowTrain<128>>)
-constexpr auto& train_batch_frames_u8_kernel = resize_frames_u8_kernel<TrainFrame, RowTrain<RF_THREADS>>;
-
 // ---- the same ragged batch from decoder-format frames: YUV 4:2:0 planes read in place (yfv2_resize_frames_yuv) ----
 // THE COLOUR FORMULA (the specification; include/yfv2.h states it for callers, tests/yuv_model.py in numpy).  All int32, SHIFT = 20,
 // every coefficient rint(k * 2^20); the limited-range rows carry 255/219 in the luma and 255/224 in the chroma coefficients:
@@ -371,8 +384,8 @@ __device__ __forceinline__ void yfv2_yuv_to_bgr(int Y, int U, int V, const YuvCo
 // 3 w to 4 w bytes per output row where the B, G, R kernel stages 6 w.  Each output pixel converts its four taps (s0 / s1 x sx0 /
 // sx1) to B, G, R and blends them with resize_frames_u8_kernel's expression: convert-then-blend is the only order that is
 // bit-identical to converting the frame and resizing it (the clamps and the rounding do not commute with the blend).
-// LDS per workgroup: two luma slots of (w + 6) & ~3, two chroma rows of two half-slots of ((w >> 1) + 7) & ~3 each (a half-slot
-// holds one I420 plane row at any misalignment, the two together one interleaved row), the output row 3 W.
+// LDS per workgroup: two luma slots of yfv2_slot(w), two chroma rows of two half-slots of yfv2_slot((w >> 1) + 1) each (a half-slot
+// holds one I420 plane row at any misalignment, the two together one interleaved row), then the Row's own bytes (RowU8: 3 W).
 // Threads and occupancy: a 1920-wide frame takes 2 * 1924 + 4 * 964 + 1056 = 8760 bytes, so 18 workgroups per CU fit the LDS -
 // more than the 16 that two-wave workgroups reach under the CU's 32-wave limit, so LDS does not bound this kernel (it bounds the
 // B, G, R one at 12-13).  Two waves keep the 352 output pixels' 5.5 waves of blend work at 6 wave-iterations (four waves would run
@@ -380,7 +393,7 @@ __device__ __forceinline__ void yfv2_yuv_to_bgr(int Y, int U, int V, const YuvCo
 // launch is a chain of round trips per workgroup (descriptor, staging loads, barrier, blend, barrier, stores), and what hides them is
 // workgroups in flight - measured 258 us at 8 waves per SIMD against 283 us at 6 on the probe's mix.
 // Like its neighbour a template over descriptor and epilogue: <ResizeFrameYuv, RowU8> is the resize, <TrainFrameYuv, RowTrain> the
-// training batch (train_batch_frames_yuv_kernel below; 43 VGPRs - the fp32 row goes to LDS where the uint8 row went).
+// training batch (43 VGPRs - the fp32 row goes to LDS where the uint8 row went).
 constexpr int RY_THREADS = 128;
 template <class Frame, class Row>
 __global__ __launch_bounds__(RY_THREADS, 8) void resize_frames_yuv_kernel(const Frame* __restrict__ frames, typename Row::Out* __restrict__ dst, int H, int W) {
@@ -402,7 +415,7 @@ __global__ __launch_bounds__(RY_THREADS, 8) void resize_frames_yuv_kernel(const 
   const int cbytes = planar ? cw : 2 * cw;
   const int cr0 = (ry.s0 + f.py) >> 1, cr1 = (ry.s1 + f.py) >> 1;
   const bool one_chroma_row = cr0 == cr1;
-  const int yslot = (f.w + 3 + Row::ALIGN - 1) & ~(Row::ALIGN - 1), chalf = ((f.w >> 1) + 4 + Row::ALIGN - 1) & ~(Row::ALIGN - 1);
+  const int yslot = yfv2_slot(f.w, Row::ALIGN), chalf = yfv2_slot((f.w >> 1) + 1, Row::ALIGN);
   unsigned char* LY0 = smem;
   unsigned char* LY1 = smem + yslot;
   unsigned char* LC0 = smem + 2 * yslot;
@@ -498,120 +511,79 @@ __global__ __launch_bounds__(RY_THREADS, 8) void resize_frames_yuv_kernel(const 
   row.end(OUT, b, oy, H, W);
 }
 
-// yfv2_train_batch_frames_yuv's launch
-constexpr auto& train_batch_frames_yuv_kernel = resize_frames_yuv_kernel<TrainFrameYuv, RowTrain<RY_THREADS>>;
-
-size_t yfv2_resize_lds_bytes(int SW, int W) { return 2 * (size_t)((SW * 3 + 6) & ~3) + (size_t)W * 3; }
-
-// train_batch_frames_u8_kernel's LDS (RowTrain): the two staging slots rounded to 16 bytes, the table, the row as three fp32 planes
-size_t yfv2_train_batch_lds_bytes(int SW, int W) { return 2 * (size_t)((SW * 3 + 18) & ~15) + YFV2_AUG_TABLE_BYTES + (size_t)W * 12; }
-
-// ... and the width limit of yfv2_train_batch_frames_u8 in closed form: every row up to it fits (at W = 352 the widest, 26 426, fills
-// YFV2_LDS_FULL to the byte).  Below yfv2_resize_max_width(W) for every W: each frame the training entry point takes, the resize takes.
-int yfv2_train_batch_max_width(int W) { return (YFV2_LDS_FULL - YFV2_AUG_TABLE_BYTES - 12 * W) / 6 - 6; }
-
-// The width limit the ragged B, G, R entry points enforce and yfv2_resize_u8's message names, in closed form.  For W % 4 == 0 it is
-// one pixel below the widest row whose yfv2_resize_lds_bytes fits YFV2_LDS_FULL (27128 against 27129 at W = 352); yfv2_resize_u8
-// itself tests the bytes, so it admits that one pixel more than its message says.
-int yfv2_resize_max_width(int W) { return (YFV2_LDS_FULL - 3 * W) / 6 - 2; }
-
-// resize_frames_yuv_kernel's LDS for a frame w pixels wide: two luma slots, two chroma rows of two half-slots, the output row
-size_t yfv2_resize_yuv_lds_bytes(int w, int W) { return 2 * (size_t)((w + 6) & ~3) + 4 * (size_t)(((w >> 1) + 7) & ~3) + (size_t)W * 3; }
-
 YuvCoef yfv2_yuv_coef(int colour) { return YUV_COEF[colour]; }
 
-// RowTensor's launches: the staging slots rounded to 16 bytes, the row as three planes of fp32 or fp16 values; the B, G, R limit in
-// closed form (a slot is at most 3 w + 18 bytes), the YUV one walked down from the crops' own limit - so neither admits a frame that
-// yfv2_crop_detections_* refuses at the same out_w
-size_t yfv2_crop_tensor_lds_bytes(int SW, int W, bool half) { return 2 * (size_t)((SW * 3 + 18) & ~15) + (size_t)W * (half ? 6 : 12); }
-int yfv2_crop_tensor_max_width(int W, bool half) { return (YFV2_LDS_FULL - (half ? 6 : 12) * W) / 6 - 6; }
-size_t yfv2_crop_tensor_yuv_lds_bytes(int w, int W, bool half) {
-  return 2 * (size_t)((w + 18) & ~15) + 4 * (size_t)(((w >> 1) + 19) & ~15) + (size_t)W * (half ? 6 : 12);
+// ---- the host side of the row kernels: ONE description per frame kind, used by every launch and every limit -----------------
+// FrameRows<Frame> is what the descriptor's frame kind (B, G, R: ResizeFrame and what derives from it; YUV: ResizeFrameYuv likewise)
+// decides: the kernel template, its block size, the LDS of a workgroup of <Frame, Row> for a frame w pixels wide - the staging slots
+// as the kernel places them (yfv2_slot) and the Row's own bytes - and the widest frame an entry point of that Row admits.
+template <class Frame, bool YUV = std::is_base_of_v<ResizeFrameYuv, Frame>>
+struct FrameRows {       // B, G, R: two source rows of 3 w bytes
+  static constexpr int THREADS = RF_THREADS;
+  template <class Row> static constexpr auto& kernel = resize_frames_u8_kernel<Frame, Row>;
+  template <class Row> static size_t lds_bytes(int w, int W) { return 2 * (size_t)yfv2_slot(3 * w, Row::ALIGN) + (size_t)Row::lds_bytes(W); }
+  // In closed form: a slot is at most 3 w + ALIGN + 2 bytes, so every row up to this fits.  For W % 4 == 0 it lies 1 to 5 pixels below
+  // the widest row that fits (27128 against 27129 for RowU8 at W = 352): the figure the entry points' messages and include/yfv2.h name.
+  template <class Row> static int max_width(int W) { return (YFV2_LDS_FULL - Row::lds_bytes(W)) / 6 - (Row::ALIGN + 2) / 3; }
+};
+template <class Frame>
+struct FrameRows<Frame, true> {   // YUV: two luma slots, two chroma rows of two half-slots each
+  static constexpr int THREADS = RY_THREADS;
+  template <class Row> static constexpr auto& kernel = resize_frames_yuv_kernel<Frame, Row>;
+  template <class Row> static size_t lds_bytes(int w, int W) {
+    return 2 * (size_t)yfv2_slot(w, Row::ALIGN) + 4 * (size_t)yfv2_slot((w >> 1) + 1, Row::ALIGN) + (size_t)Row::lds_bytes(W);
+  }
+  // The exact maximum: the function above grows by about 4 bytes per pixel and never falls, so the answer is next to
+  // (YFV2_LDS_FULL - the Row's bytes) / 4 and two short walks find it.
+  template <class Row> static int max_width(int W) {
+    int w = (int)std::max<long long>(1, ((long long)YFV2_LDS_FULL - Row::lds_bytes(W)) / 4);
+    while (w > 1 && lds_bytes<Row>(w, W) > (size_t)YFV2_LDS_FULL) --w;
+    while (lds_bytes<Row>(w + 1, W) <= (size_t)YFV2_LDS_FULL) ++w;
+    return w;
+  }
+};
+
+// The launch of every kind: one workgroup per (entry, output row) - n = the batch, or a counted table's capacity (the host does not
+// know how many entries are live) - and LDS for the widest FRAME of the call (an upper bound of every crop of it).
+template <class Frame, class Row>
+static void launch_rows(const void* table, int n, int max_w, void* dst, int H, int W, hipStream_t s) {
+  using F = FrameRows<Frame>;
+  YFV2_LAUNCH_LDS(yfv2_device(), (F::template kernel<Row>), YFV2_LDS_FULL, dim3((unsigned)(n * H)), dim3(F::THREADS), F::template lds_bytes<Row>(max_w, W), s,
+                  static_cast<const Frame*>(table), static_cast<typename Row::Out*>(dst), H, W);
 }
 
-// the widest frame whose workgroup fits a CU's LDS: the function above grows by about 4 bytes per pixel and never falls, so the
-// answer is next to (YFV2_LDS_FULL - 3 W) / 4 and two short walks find it exactly
-int yfv2_resize_yuv_max_width(int W) {
-  int w = (int)std::max<long long>(1, ((long long)YFV2_LDS_FULL - 3ll * W) / 4);
-  while (w > 1 && yfv2_resize_yuv_lds_bytes(w, W) > (size_t)YFV2_LDS_FULL) --w;
-  while (yfv2_resize_yuv_lds_bytes(w + 1, W) <= (size_t)YFV2_LDS_FULL) ++w;
-  return w;
+// What the other units see of the family: a row kind, a YUV flag, three functions.  THE TABLE of the ten instantiations: f is called
+// as f.operator()<Frame, Row>().  (The device compiler emits the kernels in the order they are named here - training first, the
+// tensors by frame kind - which is the order the unit's assembly is compared in, byte for byte: profiles/rows_refactor_isa.txt.)
+template <class Fn>
+static auto with_rows(Yfv2RowKind kind, bool yuv, Fn f) {
+  using U8 = RowU8<RF_THREADS>;                 using U8Y = RowU8<RY_THREADS>;
+  using Train = RowTrain<RF_THREADS>;           using TrainY = RowTrain<RY_THREADS>;
+  using F32 = RowTensor<RF_THREADS, false>;     using F32Y = RowTensor<RY_THREADS, false>;
+  using F16 = RowTensor<RF_THREADS, true>;      using F16Y = RowTensor<RY_THREADS, true>;
+  const bool half = kind == YFV2_ROWS_TENSOR_F16;
+  switch (kind) {
+    case YFV2_ROWS_TRAIN:      return !yuv ? f.template operator()<TrainFrame, Train>() : f.template operator()<TrainFrameYuv, TrainY>();
+    case YFV2_ROWS_U8:         return !yuv ? f.template operator()<ResizeFrame, U8>() : f.template operator()<ResizeFrameYuv, U8Y>();
+    case YFV2_ROWS_COUNTED_U8: return !yuv ? f.template operator()<CropFrame, U8>() : f.template operator()<CropFrameYuv, U8Y>();
+    default:                   // YFV2_ROWS_TENSOR_F32, YFV2_ROWS_TENSOR_F16
+      if (!yuv) return half ? f.template operator()<TensorFrame, F16>() : f.template operator()<TensorFrame, F32>();
+      return half ? f.template operator()<TensorFrameYuv, F16Y>() : f.template operator()<TensorFrameYuv, F32Y>();
+  }
 }
 
-// train_batch_frames_yuv_kernel's LDS, likewise: slots and half-slots rounded to 16 bytes, the table, the fp32 planes; and the
-// widest frame that fits, walked down from the resize's own limit (so never a frame that yfv2_resize_frames_yuv refuses)
-size_t yfv2_train_batch_yuv_lds_bytes(int w, int W) {
-  return 2 * (size_t)((w + 18) & ~15) + 4 * (size_t)(((w >> 1) + 19) & ~15) + YFV2_AUG_TABLE_BYTES + (size_t)W * 12;
+size_t yfv2_rows_lds_bytes(Yfv2RowKind kind, bool yuv, int w, int W) {
+  return with_rows(kind, yuv, [&]<class Frame, class Row>() { return FrameRows<Frame>::template lds_bytes<Row>(w, W); });
 }
 
-int yfv2_train_batch_yuv_max_width(int W) {
-  int w = yfv2_resize_yuv_max_width(W);
-  while (w > 1 && yfv2_train_batch_yuv_lds_bytes(w, W) > (size_t)YFV2_LDS_FULL) --w;
-  return w;
+int yfv2_rows_max_width(Yfv2RowKind kind, bool yuv, int W) {
+  return with_rows(kind, yuv, [&]<class Frame, class Row>() { return FrameRows<Frame>::template max_width<Row>(W); });
 }
 
-int yfv2_crop_tensor_yuv_max_width(int W, bool half) {
-  int w = yfv2_resize_yuv_max_width(W);
-  while (w > 1 && yfv2_crop_tensor_yuv_lds_bytes(w, W, half) > (size_t)YFV2_LDS_FULL) --w;
-  return w;
+void yfv2_launch_rows(Yfv2RowKind kind, bool yuv, const void* table, int n, int max_w, void* dst, int H, int W, hipStream_t s) {
+  with_rows(kind, yuv, [&]<class Frame, class Row>() { launch_rows<Frame, Row>(table, n, max_w, dst, H, W, s); });
 }
 
 void yfv2_launch_resize(const ResizeArgs& a, hipStream_t s) {
-  YFV2_LAUNCH_LDS(yfv2_device(), resize_u8_kernel, YFV2_LDS_FULL, dim3((unsigned)(a.B * a.H)), dim3(256), yfv2_resize_lds_bytes(a.SW, a.W), s, a);
-}
-
-void yfv2_launch_resize_frames(const ResizeFrame* frames, int B, int max_w, unsigned char* dst, int H, int W, hipStream_t s) {
-  YFV2_LAUNCH_LDS(yfv2_device(), (resize_frames_u8_kernel<ResizeFrame, RowU8<RF_THREADS>>), YFV2_LDS_FULL, dim3((unsigned)(B * H)), dim3(RF_THREADS), yfv2_resize_lds_bytes(max_w, W), s,
-                  frames, dst, H, W);
-}
-
-void yfv2_launch_resize_frames_yuv(const ResizeFrameYuv* frames, int B, int max_w, unsigned char* dst, int H, int W, hipStream_t s) {
-  YFV2_LAUNCH_LDS(yfv2_device(), (resize_frames_yuv_kernel<ResizeFrameYuv, RowU8<RY_THREADS>>), YFV2_LDS_FULL, dim3((unsigned)(B * H)), dim3(RY_THREADS), yfv2_resize_yuv_lds_bytes(max_w, W), s,
-                  frames, dst, H, W);
-}
-
-// The crops of a counted table: one workgroup per (entry of the table's capacity, output row); LDS for the widest FRAME of the call,
-// an upper bound of every crop of it (the crops' own widths exist on the device only).
-void yfv2_launch_resize_crops(const CropFrame* table, int cap, int max_w, unsigned char* crops, int H, int W, hipStream_t s) {
-  YFV2_LAUNCH_LDS(yfv2_device(), (resize_frames_u8_kernel<CropFrame, RowU8<RF_THREADS>>), YFV2_LDS_FULL, dim3((unsigned)(cap * H)), dim3(RF_THREADS), yfv2_resize_lds_bytes(max_w, W), s,
-                  table, crops, H, W);
-}
-
-void yfv2_launch_resize_crops_yuv(const CropFrameYuv* table, int cap, int max_w, unsigned char* crops, int H, int W, hipStream_t s) {
-  YFV2_LAUNCH_LDS(yfv2_device(), (resize_frames_yuv_kernel<CropFrameYuv, RowU8<RY_THREADS>>), YFV2_LDS_FULL, dim3((unsigned)(cap * H)), dim3(RY_THREADS), yfv2_resize_yuv_lds_bytes(max_w, W), s,
-                  table, crops, H, W);
-}
-
-void yfv2_launch_train_batch_frames(const TrainFrame* frames, int B, int max_w, float* dst, int H, int W, hipStream_t s) {
-  YFV2_LAUNCH_LDS(yfv2_device(), train_batch_frames_u8_kernel, YFV2_LDS_FULL, dim3((unsigned)(B * H)), dim3(RF_THREADS), yfv2_train_batch_lds_bytes(max_w, W), s,
-                  frames, dst, H, W);
-}
-
-void yfv2_launch_train_batch_frames_yuv(const TrainFrameYuv* frames, int B, int max_w, float* dst, int H, int W, hipStream_t s) {
-  YFV2_LAUNCH_LDS(yfv2_device(), train_batch_frames_yuv_kernel, YFV2_LDS_FULL, dim3((unsigned)(B * H)), dim3(RY_THREADS), yfv2_train_batch_yuv_lds_bytes(max_w, W), s,
-                  frames, dst, H, W);
-}
-
-// The crop tensors of a counted table: the crops' grid and LDS rule, the row as fp32 or fp16 planes
-template <bool HALF>
-static void launch_crop_tensors(const TensorFrame* table, int cap, int max_w, void* out, int H, int W, hipStream_t s) {
-  using Row = RowTensor<RF_THREADS, HALF>;
-  YFV2_LAUNCH_LDS(yfv2_device(), (resize_frames_u8_kernel<TensorFrame, Row>), YFV2_LDS_FULL, dim3((unsigned)(cap * H)), dim3(RF_THREADS),
-                  yfv2_crop_tensor_lds_bytes(max_w, W, HALF), s, table, static_cast<typename Row::Out*>(out), H, W);
-}
-template <bool HALF>
-static void launch_crop_tensors_yuv(const TensorFrameYuv* table, int cap, int max_w, void* out, int H, int W, hipStream_t s) {
-  using Row = RowTensor<RY_THREADS, HALF>;
-  YFV2_LAUNCH_LDS(yfv2_device(), (resize_frames_yuv_kernel<TensorFrameYuv, Row>), YFV2_LDS_FULL, dim3((unsigned)(cap * H)), dim3(RY_THREADS),
-                  yfv2_crop_tensor_yuv_lds_bytes(max_w, W, HALF), s, table, static_cast<typename Row::Out*>(out), H, W);
-}
-
-void yfv2_launch_crop_tensors(const TensorFrame* table, int cap, int max_w, void* out, bool half, int H, int W, hipStream_t s) {
-  if (half) launch_crop_tensors<true>(table, cap, max_w, out, H, W, s);
-  else launch_crop_tensors<false>(table, cap, max_w, out, H, W, s);
-}
-
-void yfv2_launch_crop_tensors_yuv(const TensorFrameYuv* table, int cap, int max_w, void* out, bool half, int H, int W, hipStream_t s) {
-  if (half) launch_crop_tensors_yuv<true>(table, cap, max_w, out, H, W, s);
-  else launch_crop_tensors_yuv<false>(table, cap, max_w, out, H, W, s);
+  YFV2_LAUNCH_LDS(yfv2_device(), resize_u8_kernel, YFV2_LDS_FULL, dim3((unsigned)(a.B * a.H)), dim3(256), yfv2_rows_lds_bytes(YFV2_ROWS_U8, false, a.SW, a.W), s, a);
 }

@@ -19,7 +19,6 @@ import torch
 from . import yuv
 
 LDS_FULL = 160 * 1024
-TABLE_BYTES = 1024
 
 
 def draw_contrast_brightness(rng=random):
@@ -57,22 +56,15 @@ def collate_targets(labels):
 
 
 def train_batch_lds_bytes(w, W, is_yuv=False):
-    """LDS of one workgroup of the training-batch launch for a frame w pixels wide at network width W (yfv2_pre.hip
-    yfv2_train_batch_lds_bytes / _yuv_lds_bytes): the resize's staging slots rounded to 16 bytes, the table, three fp32 planes of W"""
-    if is_yuv:
-        return 2 * ((w + 18) & ~15) + 4 * (((w >> 1) + 19) & ~15) + TABLE_BYTES + 12 * W
-    return 2 * ((3 * w + 18) & ~15) + TABLE_BYTES + 12 * W
+    """LDS of one workgroup of the training-batch launch for a frame w pixels wide at network width W: the resize's staging slots
+    rounded to 16 bytes, the table, three fp32 planes of W"""
+    return yuv.rows_lds(yuv.ROWS_TRAIN, is_yuv, w, W)[0]
 
 
 def max_frame_width(W, is_yuv=False):
-    """the widest frame Engine.train_batch_frames (is_yuv: train_batch_frames_yuv) admits at network width W
-    (yfv2_train_batch_max_width / yfv2_train_batch_yuv_max_width); below resize_frames' own limit"""
-    if not is_yuv:
-        return (LDS_FULL - TABLE_BYTES - 12 * W) // 6 - 6
-    w = yuv.max_width(W)
-    while w > 1 and train_batch_lds_bytes(w, W, True) > LDS_FULL:
-        w -= 1
-    return w
+    """the widest frame Engine.train_batch_frames (is_yuv: train_batch_frames_yuv) admits at network width W; never above
+    resize_frames' own limit"""
+    return yuv.rows_lds(yuv.ROWS_TRAIN, is_yuv, 1, W)[1]
 
 
 class TrainBatcher:

@@ -8,6 +8,8 @@
 ``(y, u, v)`` for I420 (YV12: pass ``(y, v, u)``).  A plane's row pitch is its ``stride(0)``; its bytes within a row must be
 contiguous.  Nothing here needs a device; the table goes to libyfv2.so as it is.
 """
+import ctypes as C
+
 import torch
 
 from . import _lib
@@ -15,22 +17,27 @@ from . import _lib
 FORMATS = {"nv12": 0, "nv21": 1, "i420": 2, 0: 0, 1: 1, 2: 2}
 COLOURS = {"bt601": 0, "bt601_limited": 0, "bt709": 1, "bt709_limited": 1, "bt601_full": 2, "jpeg": 2, "bt709_full": 3, 0: 0, 1: 1, 2: 2, 3: 3}
 LDS_FULL = 160 * 1024
+ROWS_U8, ROWS_COUNTED_U8, ROWS_TRAIN, ROWS_TENSOR_F32, ROWS_TENSOR_F16 = range(5)      # yfv2_debug_rows' row_kind
+
+
+def rows_lds(kind, is_yuv, w, W):
+    """(LDS bytes of one workgroup for a frame w pixels wide, the widest frame admitted) of the frame entry points' launch of row
+    kind ``kind`` at output width W, as libyfv2.so itself computes them (include/yfv2.h yfv2_debug_rows; no device needed)"""
+    lds, limit = C.c_int64(), C.c_int32()
+    if _lib.lib().yfv2_debug_rows(kind, int(bool(is_yuv)), w, W, C.byref(lds), C.byref(limit)) != _lib.OK:
+        raise ValueError("rows_lds(%r, %r, %r, %r): %s" % (kind, is_yuv, w, W, _lib.last_error()))
+    return lds.value, limit.value
 
 
 def resize_lds_bytes(w, W):
-    """LDS of one workgroup of the YUV resize for a frame w pixels wide and an output row of W pixels (yfv2_pre.hip
-    yfv2_resize_yuv_lds_bytes): two luma slots, two chroma rows of two half-slots each, the output row."""
-    return 2 * ((w + 6) & ~3) + 4 * (((w >> 1) + 7) & ~3) + 3 * W
+    """LDS of one workgroup of the YUV resize for a frame w pixels wide and an output row of W pixels: two luma slots, two chroma
+    rows of two half-slots each, the output row."""
+    return rows_lds(ROWS_U8, True, w, W)[0]
 
 
 def max_width(W):
-    """the widest YUV frame the resize admits at network width W (yfv2_resize_yuv_max_width)"""
-    w = max(1, (LDS_FULL - 3 * W) // 4)
-    while w > 1 and resize_lds_bytes(w, W) > LDS_FULL:
-        w -= 1
-    while resize_lds_bytes(w + 1, W) <= LDS_FULL:
-        w += 1
-    return w
+    """the widest YUV frame the resize admits at network width W"""
+    return rows_lds(ROWS_U8, True, 1, W)[1]
 
 
 class YuvFrame:
