@@ -639,6 +639,83 @@ YFV2_API int yfv2_track_update_two_pass(yfv2_handle h, const float* dets /* (B,R
                                         int32_t* track_pass /* (B,R) or NULL */, float* track_box /* (B,R,4) or NULL; needs motion */,
                                         float* fresh_dets /* (B,R,6) or NULL */, int32_t* fresh_src, int32_t* fresh_count, void* stream);
 
+/* ---- identity across frames, appearance association: the IoU fused with the cosine of second-stage embeddings ----
+ * yfv2_crop_tensors_* produces what a re-identification network takes; this form takes what it returns.  Every row comes with an
+ * embedding, every track keeps a unit-norm feature - a moving average of the embeddings it absorbed - and a first-pass edge between
+ * a row and a track whose boxes are close may be valued by the cosine of the two instead of the IoU (BoT-SORT's fusion: the larger
+ * similarity wins).  The form is opt-in and changes nothing above: the same kernel, the same walk, either state layout as it is, one
+ * pass or two.  The features live in a buffer of their own, so a state can be handed between this entry point and the others.
+ * THE RULE, bit for bit (tests/track_appearance_model.py restates it; its functions are behind yfv2_track_cosine and
+ * yfv2_track_feature_step).  Every fp32 operation is one separately rounded operation in the order written; divisions and the
+ * square root round to nearest.
+ *   emb          (B, R, D) fp32 on the device, 16-byte aligned: emb[b, r, :] is the embedding e of row r of frame b - the caller's
+ *                network output for the crop of that row; it need not be normalised.  Rows beyond n are not read.
+ *   feat         one caller-owned device buffer of S * M * (4 + D) int32 words; all zero = empty.  A slot of the table has the 4 + D
+ *                words feat[(stream * M + slot) * (4 + D) ..]: word 0 the int32 n_feat, the number of embeddings absorbed (0: the
+ *                track has no feature), words 1..3 zero, then D fp32 bits: the unit-norm feature f.
+ *   dot16(a, b)  the only reduction.  Sixteen partial sums P[j] = 0.0f; for i = 0 .. D/16 - 1 ascending: P[j] = P[j] + a[16 i + j] *
+ *                b[16 i + j]; then for stride = 8, 4, 2, 1: P[j] = P[j] + P[j + stride] for j < stride; the result is P[0].
+ *   appearance   of a row: n_r = sqrt(dot16(e, e)); the row HAS APPEARANCE when n_r is finite and > 0 (a NaN, an infinity, an
+ *                overflowing square or an all-zero e fails on its own: no element is tested).  Otherwise it takes part by IoU alone.
+ *   cosine       c(r, s) = dot16(e_r, f_s) / n_r, every NaN replaced by the quiet NaN 0x7fc00000; used only when finite.
+ * Per frame, on top of the rule of the layout and the pass form in use:
+ *   2 edges      (first pass only) v is the IoU as before (motion: against the predicted corners).  If the row has appearance, the
+ *                slot has n_feat > 0, double(v) > prox_thres, c is finite and double(c) > app_thres, then s = c > v ? c : v; else
+ *                s = v.  There is an edge when double(s) > match_thres; class_aware as before.  The walk orders by s descending, then
+ *                row, then slot.  Boxes that do not overlap never pair (prox_thres >= 0, the compare is strict).  The second pass
+ *                (3b) uses the IoU alone with match_thres_low.
+ *   4 matched    (either pass) track_cos[b, r] = c of the pair against the feature from BEFORE this frame's update; 0 if the row
+ *                has no appearance or the slot no feature.  Header word 7 - 0 in every other form, which do not touch it - += the
+ *                number of first-pass matches whose edge value was c (the conditions above held and c > v).  Then, if the row has
+ *                appearance: with n_feat == 0, f[d] = e[d] / n_r and n_feat = 1; otherwise g[d] = alpha * f[d] + beta * (e[d] /
+ *                n_r) with beta = 1.0f - alpha, m = sqrt(dot16(g, g)), and if m is finite and > 0, f[d] = g[d] / m and n_feat += 1 -
+ *                if not, the feature is unchanged.  A row without appearance leaves the feature unchanged.
+ *   5 unmatched  the feature is unchanged; a dead slot zeroes all its 4 + D words.
+ *   6 births     f = e / n_r, n_feat = 1; for a row without appearance all 4 + D words are zero.
+ *   7 header     track_cos (optional) is 0 where no track is assigned, for born rows and beyond n.
+ * Consequence: with app_thres = +inf no pair passes, and state, header (word 7 stays 0) and every shared output are those of the
+ * entry point of the same layout and pass form, bit for bit, while feat is still maintained.
+ * Defaults (documented, not applied by the C ABI): dim = 128, prox_thres = 0.5, app_thres = 0.75, alpha = 0.9 - BoT-SORT's
+ * proximity_thresh, 1 - appearance_thresh and the momentum of its feature average.
+ * LDS: one workgroup holds 28 R + 52 M bytes (the other forms: 24 R + 48 M; here also a row's n_r and a slot's n_feat), which must
+ * not exceed 163328 - a CU's 160 KiB less 512 bytes the kernel keeps: R = 4096 admits M <= 935, M = 1024 admits R <= 3931. */
+typedef struct yfv2_track_appearance {
+  int32_t dim;              /* D: floats of an embedding; a multiple of 16 in 16..2048 (pad another width with zeros: they add exactly) */
+  double  prox_thres;       /* the cosine counts only when double(IoU) > prox_thres; finite, >= 0 */
+  double  app_thres;        /* ... and when double(cosine) > app_thres; not NaN, +inf: never */
+  float   alpha;            /* weight of the old feature in the moving average; finite, in [0, 1] */
+} yfv2_track_appearance;
+
+/* int32 words of ONE stream's features: max_tracks * (4 + D); YFV2_ERR_ARG (negative) for max_tracks outside 1..1024 or a D that
+ * yfv2_track_appearance does not admit.  Host only. */
+YFV2_API int64_t yfv2_track_feature_words(int32_t max_tracks, int32_t D);
+
+/* The norm and the cosine of the rule for one embedding e and one feature f of D floats: *norm = sqrt(dot16(e, e)), *cos =
+ * dot16(e, f) / *norm, NaNs as 0x7fc00000 - computed whether or not the norm gives e an appearance.  Host only, no handle, like
+ * yfv2_track_iou: the functions the kernel calls.  YFV2_ERR_ARG for a NULL pointer or a D outside the rule's. */
+YFV2_API int yfv2_track_cosine(const float* e, const float* f, int32_t D, float* norm, float* cos);
+
+/* Step 4's feature update for one track: f_in / n_feat_in (>= 0) and the matched row's embedding e -> f_out / *n_feat_out
+ * (f_out may be f_in).  Host only; YFV2_ERR_ARG likewise, and for an alpha that is not finite or outside [0, 1]. */
+YFV2_API int yfv2_track_feature_step(const float* f_in, int32_t n_feat_in, const float* e, int32_t D, float alpha, float* f_out,
+                                     int32_t* n_feat_out);
+
+/* One update in the appearance form: motion NULL or not chooses the state's layout, second NULL or not one pass or two, exactly as
+ * for yfv2_track_update_two_pass; emb, feat and appearance as above; track_cos (B, R) fp32 or NULL; track_pass only with second,
+ * track_box only with motion.  Every check of the form it extends; also YFV2_ERR_ARG with a message, nothing enqueued, state and
+ * feat untouched, for: emb, feat or appearance NULL; emb not 16-byte aligned; dim not a multiple of 16 or outside 16..2048;
+ * prox_thres not finite or negative; app_thres NaN; alpha not finite or outside [0, 1]; 28 R + 52 max_tracks above 163328.
+ * Enqueue only: one workgroup per frame, one launch per 768 frames, no host wait, no handle workspace.  An addition within ABI 7:
+ * yfv2_abi_version() is unchanged. */
+YFV2_API int yfv2_track_update_appearance(yfv2_handle h, const float* dets /* (B,R,6) */, const int32_t* count /* (B) */, int32_t R, int32_t B,
+                                          const int32_t* stream_of /* HOST, B */, int32_t* state, int32_t S, const yfv2_track_rule* rule,
+                                          const yfv2_track_motion* motion /* NULL: the plain slots */, const yfv2_track_second* second /* NULL: one pass */,
+                                          const yfv2_track_appearance* appearance, const float* emb /* (B,R,D) */, int32_t* feat,
+                                          int32_t* track_id /* (B,R) */, int32_t* track_hits /* (B,R) or NULL */,
+                                          int32_t* track_pass /* (B,R) or NULL; needs second */, float* track_box /* (B,R,4) or NULL; needs motion */,
+                                          float* track_cos /* (B,R) or NULL */, float* fresh_dets /* (B,R,6) or NULL */, int32_t* fresh_src,
+                                          int32_t* fresh_count, void* stream);
+
 /* ---- the ncnn sample's deployment path (sample/ncnn/src/yolo-fastestv2.cpp) ----
  * The reference's only native component post-processes differently from its Python path in every step that decides which boxes
  * come out: no objectness pre-filter (score = cls * obj > thresh only), boxes scaled to the source frame and TRUNCATED TO int

@@ -27,8 +27,22 @@ the first --host-frames frames are compared with tests/track_two_pass_model.py b
 parallel form's over ALL --frames frames of the first --round-streams streams (default 8; on the host, nothing timed), reported
 without the first frame, which has no tracks and so no round.  Default --json: profiles/track_two_pass_probe.json, with --motion
 profiles/track_two_pass_motion_probe.json.
+
+--appearance: the appearance form (Tracker(appearance=dict(dim=--dim)), yfv2_track_update_appearance; fp32 embeddings of one width,
+every object a unit vector of its own plus noise) on the same regime, in the plain and in the motion layout (--motion: the motion
+layout only; --two-pass: two passes in every variant).  THREE variants alternate, a fresh tracker each pass: the shipped form of the
+layout and pass count; the appearance form with app_thres = +inf - the rows' norms, the gating and the features' upkeep, with no
+cosine ever counting; the appearance form at its defaults (prox_thres 0.5, app_thres 0.75, alpha 0.9).  Passes and statistics as for
+--motion.  The state of the +inf variant must equal the shipped form's; the default variant's state, features and outputs of the
+first --host-frames frames of the first streams are compared with tests/track_appearance_model.py bit for bit, and the model's
+parallel form gives the first pass's rounds, the gated pairs (pairs whose cosine the first pass needs) and the matches valued by the
+cosine per frame.  What the form does not do: embeddings other than fp32; more than one width per tracker; re-identification
+after a track's death; a gallery of several features per track; appearance in the second pass; anything but the maximum of IoU and
+cosine as the fused value (BoT-SORT's minimum of the two distances), which cannot separate a wrong pair at IoU ~1 from a right pair
+at cosine ~1; it is not a DetectPipeline form and not in yfv2.hpp.  Default --json: profiles/track_appearance_probe.json.
 usage: python tools/track_probe.py [--streams 256] [--frames 30] [--host-frames 2] [--iters 20] [--motion [--reps 5]]
                                    [--two-pass [--motion] [--low-share 0.3] [--reps 5] [--round-streams 8]]
+                                   [--appearance [--motion] [--two-pass] [--dim 128] [--reps 5] [--round-streams 8]]
 """
 import argparse
 import json
@@ -207,6 +221,85 @@ def run_two_pass(eng, dev, seq, host_frames, reps, motion, round_streams):
             "issued": {"one_pass": heads[False][0], "two_pass": heads[True][0]}, "live": {"one_pass": heads[False][1], "two_pass": heads[True][1]}}
 
 
+def sequence_emb(rng, S, T, live, seen_n, D, noise=0.1):
+    """sequence() with an embedding per row: every object has a unit vector of its own, a row's embedding is that vector plus
+    noise of relative size `noise`.  -> T (dets (S, R, 6), count (S), emb (S, R, D))"""
+    pos = rng.uniform(0, [1800, 1000], (S, live, 2))
+    size = rng.uniform(30, 120, (S, live, 2))
+    cls = rng.integers(0, 80, (S, live)).astype(np.float32)
+    proto = rng.normal(size=(S, live, D)).astype(np.float32)
+    proto /= np.linalg.norm(proto, axis=2, keepdims=True)
+    out = []
+    for _ in range(T):
+        pos += rng.uniform(-3, 3, pos.shape)
+        dets, emb = np.zeros((S, R, 6), np.float32), np.zeros((S, R, D), np.float32)
+        count = np.zeros(S, np.int32)
+        for s in range(S):
+            seen = rng.permutation(live)[:seen_n]
+            conf = np.sort(rng.uniform(0.3, 1.0, len(seen)))[::-1]
+            dets[s, :len(seen)] = np.concatenate([pos[s, seen], pos[s, seen] + size[s, seen], conf[:, None], cls[s, seen, None]], axis=1)
+            emb[s, :len(seen)] = proto[s, seen] + (noise / np.sqrt(D)) * rng.normal(size=(len(seen), D)).astype(np.float32)
+            count[s] = len(seen)
+        out.append((dets, count, emb))
+    return out
+
+
+def run_appearance(eng, dev, seq, host_frames, reps, motion, two, round_streams, D):
+    """three variants alternating in one process: the shipped form of the layout and pass count, the appearance form with
+    app_thres = +inf (the norms, the gating and the features' upkeep, no cosine ever counts) and the appearance form at its defaults"""
+    import track_appearance_model
+    import track_model
+    S = seq[0][0].shape[0]
+    rule = dict(max_tracks=M, match_thres=0.3, class_aware=True, init_conf=0.0, max_misses=30, confirm_hits=3)
+    dseq = [(torch.from_numpy(d).to(dev), torch.from_numpy(c).to(dev), torch.from_numpy(e).to(dev)) for d, c, e in seq]
+    base = (torch.empty((S, R), device=dev, dtype=torch.int32), torch.empty((S, R), device=dev, dtype=torch.int32), torch.empty((S, R, 6), device=dev),
+            torch.empty((S, R), device=dev, dtype=torch.int32), torch.empty((S,), device=dev, dtype=torch.int32))
+    base += ((torch.empty((S, R, 4), device=dev),) if motion else ()) + ((torch.empty((S, R), device=dev, dtype=torch.int32),) if two else ())
+    outs = {"shipped": base, "inf": base + (torch.empty((S, R), device=dev),), "defaults": base + (torch.empty((S, R), device=dev),)}
+    apps = {"shipped": None, "inf": dict(dim=D, app_thres=float("inf")), "defaults": dict(dim=D)}
+    ms, states = {k: [] for k in apps}, {}
+    for rep in range(reps + 1):                             # pass 0 is the warm-up of the three forms
+        for k, app in apps.items():
+            tr = yfv2.Tracker(eng, S, motion=motion or None, two_pass=two or None, appearance=app, **rule)
+            for d, c, e in dseq:
+                kw = dict(emb=e, cos=True) if app else {}
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                tr.update(d, c, fresh=True, box=motion, passes=two, out=outs[k], **kw)
+                e1.record()
+                torch.cuda.synchronize()
+                if rep:
+                    ms[k].append(e0.elapsed_time(e1))
+            same = k not in states or bool(torch.equal(states[k], tr.state))
+            states[k] = tr.state.clone()
+            assert same, "two passes over one sequence left different states"
+    # the appearance form at its defaults against its model, and the model's rounds and gated pairs, on the first streams
+    K = min(round_streams, S)
+    model = track_appearance_model.Model(K, appearance=apps["defaults"], second=two or None, motion=motion or None, **rule)
+    chk = yfv2.Tracker(eng, K, motion=motion or None, two_pass=two or None, appearance=apps["defaults"], **rule)
+    same = True
+    for t, (d, c, e) in enumerate(seq):
+        want = model.update(d[:K], c[:K], e[:K], match=track_model.mutual_best)
+        if t < host_frames:
+            got = chk.update(dseq[t][0][:K].contiguous(), dseq[t][1][:K].contiguous(), emb=dseq[t][2][:K].contiguous(), cos=True)
+            same = (same and bool(torch.equal(chk.state.cpu(), torch.from_numpy(model.state))) and bool(torch.equal(chk.feat.cpu(), torch.from_numpy(model.feat)))
+                    and bool(torch.equal(got[0].cpu(), torch.from_numpy(want["track_id"])))
+                    and bool(torch.equal(got[-1].cpu().view(torch.int32), torch.from_numpy(want["track_cos"]).view(torch.int32))))
+    rounds = model.stats["rounds"][K:]
+    frames = K * (len(seq) - 1)
+    heads = {k: states[k][:, :8].sum(0).tolist() for k in states}
+    med = {k: statistics.median(v) for k, v in ms.items()}
+    return {"rows_per_frame": int(round(float(np.mean([c.mean() for _d, c, _e in seq])))), "reps": reps,
+            "shipped_ms": spread(ms["shipped"]), "appearance_inf_ms": spread(ms["inf"]), "appearance_ms": spread(ms["defaults"]),
+            "ratio_inf": round(med["inf"] / med["shipped"], 3), "ratio": round(med["defaults"] / med["shipped"], 3),
+            "inf_state_equals_shipped": bool(torch.equal(states["inf"], states["shipped"])), "appearance_equals_model": same,
+            "model": {"streams": K, "frames": len(seq) - 1, "of": "every frame but the first of the first streams, host model, parallel walk",
+                      "first_pass_rounds": {"max": max(r[0] for r in rounds), "mean": round(float(np.mean([r[0] for r in rounds])), 2)},
+                      "gated_pairs_per_frame": round(model.stats["gated"] / frames, 1),
+                      "by_appearance_per_frame": round(model.stats["by_appearance"] / frames, 1)},
+            "by_appearance": heads["defaults"][7], "issued": {k: heads[k][0] for k in heads}, "live": {k: heads[k][1] for k in heads}}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--streams", type=int, default=256)
@@ -219,8 +312,12 @@ def main():
     ap.add_argument("--two-pass", action="store_true")
     ap.add_argument("--low-share", type=float, default=0.3)
     ap.add_argument("--round-streams", type=int, default=8)
+    ap.add_argument("--appearance", action="store_true")
+    ap.add_argument("--dim", type=int, default=128)
     ap.add_argument("--json", default=None)
     args = ap.parse_args()
+    if args.json is None and args.appearance:
+        args.json = os.path.join(REPO, "profiles", "track_appearance%s%s_probe.json" % ("_two_pass" if args.two_pass else "", "_motion" if args.motion else ""))
     if args.json is None:
         args.json = os.path.join(REPO, "profiles", ("track_two_pass_motion_probe.json" if args.motion else "track_two_pass_probe.json") if args.two_pass else "track_motion_probe.json" if args.motion else "track_probe.json")
 
@@ -229,6 +326,22 @@ def main():
     eng = yfv2.Engine(dev, 352, 352, 80, 3, anchors=ANCHORS, max_batch=S, plan={})
     eng.load_state_dict(yfv2.random_state_dict(0))
     rng = np.random.default_rng(args.seed)
+    if args.appearance:
+        layouts = [True] if args.motion else [False, True]
+        res = {"tool": "track_probe --appearance" + (" --motion" if args.motion else "") + (" --two-pass" if args.two_pass else ""), "streams": S, "R": R, "M": M,
+               "D": args.dim, "frames": args.frames, "host_frames": args.host_frames, "passes": 2 if args.two_pass else 1,
+               "appearance": dict(prox_thres=0.5, app_thres=0.75, alpha=0.9), "round_trip_ms_it_replaces": "profiles/track_probe.json round_trip_ms"}
+        full, sparse = sequence_emb(rng, S, args.frames, 333, 300, args.dim), sequence_emb(rng, S, args.frames, 33, 30, args.dim)
+        for motion in layouts:
+            res["motion" if motion else "plain"] = {
+                "full": run_appearance(eng, dev, full, args.host_frames, args.reps, motion, args.two_pass, min(args.round_streams, 4), args.dim),
+                "sparse": run_appearance(eng, dev, sparse, args.host_frames, args.reps, motion, args.two_pass, min(args.round_streams, 4), args.dim)}
+        line = json.dumps(res)
+        print(line)
+        os.makedirs(os.path.dirname(os.path.abspath(args.json)), exist_ok=True)
+        with open(args.json, "w") as f:
+            f.write(line + "\n")
+        return
     if args.two_pass:
         res = {"tool": "track_probe --two-pass" + (" --motion" if args.motion else ""), "streams": S, "R": R, "M": M, "frames": args.frames,
                "host_frames": args.host_frames, "layout": "motion" if args.motion else "plain",

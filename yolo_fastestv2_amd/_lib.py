@@ -115,6 +115,11 @@ class TrackSecond(C.Structure):
     _fields_ = [("high_conf", C.c_float), ("low_conf", C.c_float), ("match_thres_low", C.c_double), ("tracked_only", C.c_int32)]
 
 
+class TrackAppearance(C.Structure):
+    """yfv2_track_appearance (include/yfv2.h): the embedding width, the two thresholds and the momentum of the tracker's appearance form."""
+    _fields_ = [("dim", C.c_int32), ("prox_thres", C.c_double), ("app_thres", C.c_double), ("alpha", C.c_float)]
+
+
 class KmeansInfo(C.Structure):
     """yfv2_kmeans_info (include/yfv2.h): what ended yfv2_anchor_kmeans' loop."""
     _fields_ = [("struct_size", C.c_int32), ("iterations", C.c_int32), ("converged", C.c_int32), ("empty_cluster", C.c_int32),
@@ -211,6 +216,14 @@ _PROTOTYPES = {
     "yfv2_track_update_two_pass": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_int32,
                                              C.POINTER(TrackRule), C.POINTER(TrackMotion), C.POINTER(TrackSecond), C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "yfv2_track_feature_words": (C.c_int64, [C.c_int32, C.c_int32]),
+    "yfv2_track_cosine": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "yfv2_track_feature_step": (C.c_int, [C.POINTER(C.c_float), C.c_int32, C.POINTER(C.c_float), C.c_int32, C.c_float, C.POINTER(C.c_float),
+                                          C.POINTER(C.c_int32)]),
+    "yfv2_track_update_appearance": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.c_void_p, C.c_int32,
+                                               C.POINTER(TrackRule), C.POINTER(TrackMotion), C.POINTER(TrackSecond), C.POINTER(TrackAppearance),
+                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                               C.c_void_p, C.c_void_p, C.c_void_p]),
     "yfv2_export_maps": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "yfv2_deploy_post": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_float, C.c_float, C.c_void_p, C.c_void_p,
                                    C.c_int32, C.c_void_p]),

@@ -527,6 +527,22 @@ struct TrackTwoArgs : TrackMotionArgs {   // the other forms' arguments stay wha
   int32_t* track_pass;         // (B, R) or null, offset like dets
 };
 void yfv2_launch_track_two_pass(const TrackTwoArgs& a, bool motion, int frames, hipStream_t s);   // motion: a.state in 32-word slots
+// the appearance form (yfv2_track_update_appearance): either layout, one pass or two; a track's feature is a slot of
+// TRACK_FEAT_HEAD + D words in a buffer of its own (word 0: n_feat, then zeros, then the D fp32 bits of the unit feature)
+constexpr int TRACK_FEAT_HEAD = 4, TRACK_APP_MIN_D = 16, TRACK_APP_MAX_D = 2048;
+// LDS of one workgroup: the other forms' 24 R + 48 M (launch_track, yfv2_track.hip) and, in the appearance form, 4 bytes per row (its
+// norm) and 4 per slot (its n_feat).  TRACK_APP_LDS_MAX: a CU's 160 KiB less 512 bytes for the kernel's static LDS (336 used).
+constexpr size_t yfv2_track_lds_bytes(bool appearance, int R, int M) { return (size_t)(appearance ? 28 : 24) * R + (size_t)(appearance ? 52 : 48) * M; }
+constexpr size_t TRACK_APP_LDS_MAX = (size_t)YFV2_LDS_FULL - 512;
+struct TrackAppArgs : TrackTwoArgs {   // the other forms' arguments stay what they were: their kernels are the ones they were
+  const float* emb;            // (B, R, D), offset like dets
+  int32_t* feat;               // S * M * (TRACK_FEAT_HEAD + D) words
+  float* track_cos;            // (B, R) or null, offset like dets
+  int D;
+  double prox, app;            // the cosine counts when double(IoU) > prox and double(cosine) > app
+  float alpha, beta;           // the feature's moving average: alpha * f + beta * e / |e|, beta = 1.0f - alpha
+};
+void yfv2_launch_track_appearance(const TrackAppArgs& a, bool motion, bool two_pass, int frames, hipStream_t s);
 // dets columns 0-3 of the first count[b] rows of frame b times frames[b].box_x / box_y (yfv2_post.hip)
 void yfv2_launch_frame_boxes(float* dets, const int32_t* count, const ResizeFrame* frames, int B, hipStream_t s);
 void yfv2_launch_decode(const DecodeArgs& a, hipStream_t s);

@@ -40,6 +40,7 @@
 #include <algorithm>
 #include <cmath>
 #include <type_traits>
+#include <vector>
 
 #include "../../include/yfv2.h"
 #include "yfv2_device.h"
@@ -123,6 +124,42 @@ __host__ __device__ __forceinline__ void track_birth(const float z[4], const Tra
   }
 }
 __host__ __device__ __forceinline__ bool track_finite(float v) { return (v < 0.0f ? -v : v) <= 3.402823466e38f; }   // NaN or an infinity fails
+
+// ---- the appearance form's arithmetic (include/yfv2.h "appearance association"): dot16 is sixteen partial sums and a tree over them.
+// track_dot16_part is partial sum j - what ONE lane of a 16-lane group computes in the kernel, and what the host entry points loop
+// over; the tree is four DPP row steps in the kernel (group_dot16 below) and track_dot16_tree on the host: the same additions.
+__host__ __device__ __forceinline__ float track_dot16_part(const float* a, const float* b, int D, int j) {
+#pragma clang fp contract(off)
+  float p = 0.0f;
+  for (int i = j; i < D; i += 16) p = p + a[i] * b[i];
+  return p;
+}
+inline float track_dot16_tree(float P[16]) {
+#pragma clang fp contract(off)
+  for (int stride = 8; stride >= 1; stride >>= 1)
+    for (int j = 0; j < stride; ++j) P[j] = P[j] + P[j + stride];
+  return P[0];
+}
+// The square root rounded to nearest on both passes: sqrtf.  On the device that is the compiler's correctly rounded fp32 square root
+// (hipcc's default, -fhip-fp32-correctly-rounded-divide-sqrt); __fsqrt_rn is NOT - without OCML_BASIC_ROUNDED_OPERATIONS the
+// toolchain's header defines it as the native, approximate instruction, which is one ulp off on sqrt(0.82f).
+__host__ __device__ __forceinline__ float track_sqrt(float v) { return sqrtf(v); }
+// a vector's norm from dot16(e, e), and whether it gives the row an appearance (an update a new feature): finite and > 0
+__host__ __device__ __forceinline__ bool track_norm_ok(float n) { return n > 0.0f && track_finite(n); }
+// the cosine of a row of norm n_r with a unit feature, from dot16(e, f); one quiet NaN, like the filter's results
+__host__ __device__ __forceinline__ float track_cosine(float dot, float n_r) { return track_canon(track_div(dot, n_r)); }
+// the value of a first-pass edge: the cosine c where both sides have an appearance (has), the boxes are close enough and c passes
+// its own threshold and is the larger, else the IoU v.  by_app: the value is c
+__host__ __device__ __forceinline__ float track_fuse(float v, float c, bool has, double prox, double app, bool& by_app) {
+  by_app = has && (double)v > prox && track_finite(c) && (double)c > app && c > v;
+  return by_app ? c : v;
+}
+// one element of a feature: of a first embedding, and of the moving average before it is normalised
+__host__ __device__ __forceinline__ float track_feat_first(float e, float n_r) { return track_div(e, n_r); }
+__host__ __device__ __forceinline__ float track_feat_blend(float f, float e, float n_r, float alpha, float beta) {
+#pragma clang fp contract(off)
+  return alpha * f + beta * track_div(e, n_r);
+}
 
 namespace {
 
@@ -213,13 +250,57 @@ __device__ __forceinline__ void row_box_store(float* track_box, size_t row, floa
   o[0] = c.x; o[1] = c.y; o[2] = c.z; o[3] = c.w;
 }
 
-// MOTION: the slots are TRACK_SLOT_MOTION words and carry filters (above); TWO: the rounds run twice, over the HIGH rows and over
-// the LOW rows (TrackTwoArgs; a plain table leaves its motion part unused); everything else is the one kernel
-template <bool MOTION, bool TWO>
-using track_args_t = std::conditional_t<TWO, TrackTwoArgs, std::conditional_t<MOTION, TrackMotionArgs, TrackArgs>>;
+// ---- the appearance form: a 16-lane group (a DPP row; lane j of it holds partial sum j) per pair, per slot or per row
+// lane l <- lane l + N of its row: the tree step P[j] = P[j] + P[j + N] for j < N (the lanes above N hold values nothing reads)
+template <int N>
+__device__ __forceinline__ float row_down(float v) {
+  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x100 + N, 0xf, 0xf, true));
+}
+__device__ __forceinline__ float group_tree(float p) {      // -> dot16's result in the group's lane 0
+#pragma clang fp contract(off)
+  p = p + row_down<8>(p);
+  p = p + row_down<4>(p);
+  p = p + row_down<2>(p);
+  p = p + row_down<1>(p);
+  return p;
+}
+__device__ __forceinline__ float group_dot16(const float* a, const float* b, int D, int j) { return group_tree(track_dot16_part(a, b, D, j)); }
+__device__ __forceinline__ int* app_counter() {              // static LDS of the appearance kernels only: the others never name it
+  __shared__ int s_app;
+  return &s_app;
+}
+// The cosines of the wave's gated pairs of ONE slot (feature f): `gated` is the ballot of the lanes whose row passed the cheap tests,
+// lane l's row is row_base + l.  Four pairs per step, one per 16-lane group; a gated lane gets its own c = dot16(e, f) / n_r.
+__device__ __forceinline__ float wave_cosines(unsigned long long gated, const float* emb_rows, int row_base, const float* f, int D, float n_r, int lane) {
+  const int grp = lane >> 4, j = lane & 15;
+  float c = 0.0f;
+  while (gated) {
+    int src[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      src[k] = gated ? __builtin_ctzll(gated) : -1;
+      gated &= gated - 1ull;
+    }
+    const int mine = grp == 0 ? src[0] : grp == 1 ? src[1] : grp == 2 ? src[2] : src[3];
+    float dot = 0.0f;
+    if (mine >= 0) dot = group_dot16(emb_rows + (size_t)(row_base + mine) * D, f, D, j);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float d = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, dot), 16 * k));
+      if (lane == src[k]) c = track_cosine(d, n_r);
+    }
+  }
+  return c;
+}
 
-template <bool MOTION, bool TWO>
-__global__ __launch_bounds__(TK_MAX_THREADS) void track_kernel(track_args_t<MOTION, TWO> a) {
+// MOTION: the slots are TRACK_SLOT_MOTION words and carry filters (above); TWO: the rounds run twice, over the HIGH rows and over
+// the LOW rows (TrackTwoArgs; a plain table leaves its motion part unused); APP: first-pass edges may take the cosine of the row's
+// embedding with the track's feature, and the features are kept (TrackAppArgs); everything else is the one kernel
+template <bool MOTION, bool TWO, bool APP>
+using track_args_t = std::conditional_t<APP, TrackAppArgs, std::conditional_t<TWO, TrackTwoArgs, std::conditional_t<MOTION, TrackMotionArgs, TrackArgs>>>;
+
+template <bool MOTION, bool TWO, bool APP = false>
+__global__ __launch_bounds__(TK_MAX_THREADS) void track_kernel(track_args_t<MOTION, TWO, APP> a) {
   constexpr int SLOT = MOTION ? TRACK_SLOT_MOTION : TRACK_SLOT;
   extern __shared__ __attribute__((aligned(16))) unsigned char tk_lds[];
   __shared__ int s_cnt[TK_MAX_THREADS / 64];
@@ -242,8 +323,25 @@ __global__ __launch_bounds__(TK_MAX_THREADS) void track_kernel(track_args_t<MOTI
   const int n = min(max(a.count[b], 0), R);
   const float* const rows = a.dets + (size_t)b * R * 6;
   const int issued = head[0];
+  // (appearance) a row's norm, 0 = no appearance, and a slot's n_feat, after the other forms' arrays; the stream's features; a
+  // thread's place in its 16-lane group and the number of groups
+  float* rnorm = nullptr;
+  int* sfeat = nullptr;
+  int32_t* feat = nullptr;
+  const float* emb = nullptr;
+  int D = 0, FS = 0, gj = 0, ng = 0;
+  if constexpr (APP) {
+    rnorm = reinterpret_cast<float*>(sage + M);
+    sfeat = reinterpret_cast<int*>(rnorm + R);
+    D = a.D; FS = TRACK_FEAT_HEAD + D; gj = tid & 15; ng = nt >> 4;
+    feat = a.feat + (size_t)a.stream_of[b] * (size_t)M * (size_t)FS;
+    emb = a.emb + (size_t)b * R * D;
+  }
 
   if (tid == 0) s_deaths = 0;
+  if constexpr (APP) {
+    if (tid == 0) *app_counter() = 0;
+  }
   for (int s = tid; s < M; s += nt) {
     int32_t* w = slots + SLOT * s;
     if constexpr (MOTION) sbox[s] = slot_predict(w, a.motion);
@@ -251,6 +349,14 @@ __global__ __launch_bounds__(TK_MAX_THREADS) void track_kernel(track_args_t<MOTI
     sconf[s] = i2f(w[4]); scls[s] = i2f(w[5]);
     sid[s] = w[6]; shits[s] = w[7]; smiss[s] = w[8]; sage[s] = w[9];
     skey[s] = w[6] == 0 ? ~0ull : 0ull;
+    if constexpr (APP) sfeat[s] = feat[(size_t)s * FS];
+  }
+  if constexpr (APP) {                                        // the rows' norms, once per frame: a group per row
+    for (int r = tid >> 4; r < n; r += ng) {
+      const float* e = emb + (size_t)r * D;
+      const float nr = track_sqrt(group_dot16(e, e, D, gj));
+      if (gj == 0) rnorm[r] = track_norm_ok(nr) ? nr : 0.0f;
+    }
   }
   for (int r = tid; r < n; r += nt) {
     const float* row = rows + 6 * r;
@@ -293,6 +399,46 @@ __global__ __launch_bounds__(TK_MAX_THREADS) void track_kernel(track_args_t<MOTI
     }
     for (;;) {
       int any = 0;
+      if constexpr (APP) {
+        // The same scan with every lane of a wave in the slot loop, so that the wave can work on its gated pairs together: a lane
+        // whose row is done (or beyond n) scans with act = false and offers nothing.  In the first pass a slot with a feature makes
+        // the lanes whose row has an appearance, the slot's class and an IoU above prox_thres vote; their cosines are computed four
+        // pairs per step by wave_cosines, and the edge's value is track_fuse's.
+        for (int r0 = 0; r0 < n; r0 += nt) {
+          const int r = r0 + tid;
+          const int2 q = r < n ? rst[r] : make_int2(-1, 0);
+          const bool act = r < n && !(q.y == 0 || q.y == TK_TAKEN);
+          if (__ballot(act) == 0ull) continue;
+          const float4 g = act ? rbox[r] : make_float4(0.f, 0.f, 0.f, 0.f);
+          const float garea = track_area(g.x, g.y, g.z, g.w);
+          const float gcls = act ? rows[6 * r + 5] : 0.0f;
+          const float nr = act && pass == 0 ? rnorm[r] : 0.0f;
+          const unsigned long long low = (unsigned)~r;
+          int best = -1, bv = 0;
+          for (int s = 0; s < M; ++s) {
+            if ((int)(skey[s] >> 32) < 0) continue;
+            const bool open = act && !(aware && !(scls[s] == gcls));
+            const float4 t = sbox[s];
+            float v = track_iou(t.x, t.y, t.z, t.w, track_area(t.x, t.y, t.z, t.w), g.x, g.y, g.z, g.w, garea);
+            if (pass == 0 && sfeat[s] > 0) {
+              const bool gate = open && nr > 0.0f && (double)v > a.prox;
+              const unsigned long long gated = __ballot(gate);
+              if (gated != 0ull) {
+                const float c = wave_cosines(gated, emb, r0 + tid - lane, reinterpret_cast<const float*>(feat + (size_t)s * FS + TRACK_FEAT_HEAD), D, nr, lane);
+                bool by_app;
+                v = track_fuse(v, c, gate, a.prox, a.app, by_app);
+              }
+            }
+            if (open && (double)v > thres) {
+              const int vb = f2i(v);
+              atomicMax(&skey[s], ((unsigned long long)(unsigned)vb << 32) | low);
+              if (vb > bv) { bv = vb; best = s; }
+            }
+          }
+          if (act) rst[r] = make_int2(best, bv);
+          any |= best >= 0;
+        }
+      } else
       for (int r = tid; r < n; r += nt) {
         const int2 q = rst[r];
         if (q.y == 0 || q.y == TK_TAKEN) continue;
@@ -342,6 +488,57 @@ __global__ __launch_bounds__(TK_MAX_THREADS) void track_kernel(track_args_t<MOTI
       }
       __syncthreads();
     }
+  }
+
+  // ---- (appearance) steps 4 and 5 of the features, a group per live slot, while sbox, smiss and the keys are still the frame's:
+  // the pair's cosine against the feature as it was, whether the walk took the pair at that cosine (header word 7), then the
+  // feature's update; a slot that step 5 is about to kill loses its feature.  Lane j reads and writes elements 16 i + j only.
+  if constexpr (APP) {
+    for (int s = tid >> 4; s < M; s += ng) {
+      if (sid[s] == 0) continue;
+      int32_t* fw = feat + (size_t)s * FS;
+      float* f = reinterpret_cast<float*>(fw + TRACK_FEAT_HEAD);
+      const unsigned long long k = skey[s];
+      if ((int)(k >> 32) == TK_TAKEN) {
+        const int r = (int)(unsigned)k;
+        const float nr = rnorm[r];
+        const int nf = sfeat[s];
+        const float* e = emb + (size_t)r * D;
+        float c = 0.0f;
+        if (nr > 0.0f && nf > 0) {
+          c = track_cosine(group_dot16(e, f, D, gj), nr);
+          if (gj == 0) {
+            bool first = true, by_app;
+            if constexpr (TWO) first = rows[6 * r + 4] >= a.high_conf;
+            const float4 t = sbox[s], g = rbox[r];
+            const float v = track_iou(t.x, t.y, t.z, t.w, track_area(t.x, t.y, t.z, t.w), g.x, g.y, g.z, g.w, track_area(g.x, g.y, g.z, g.w));
+            track_fuse(v, c, first, a.prox, a.app, by_app);
+            if (by_app) atomicAdd(app_counter(), 1);           // an integer sum: the same in any order
+          }
+        }
+        if (gj == 0 && a.track_cos) a.track_cos[(size_t)b * R + r] = c;
+        if (nr > 0.0f) {
+          if (nf == 0) {
+            for (int i = gj; i < D; i += 16) f[i] = track_feat_first(e[i], nr);
+            if (gj == 0) fw[0] = 1;
+          } else {
+            float p = 0.0f;
+            for (int i = gj; i < D; i += 16) {
+              const float gv = track_feat_blend(f[i], e[i], nr, a.alpha, a.beta);
+              p = __fadd_rn(p, __fmul_rn(gv, gv));
+            }
+            const float m = __shfl(track_sqrt(group_tree(p)), lane & ~15);
+            if (track_norm_ok(m)) {
+              for (int i = gj; i < D; i += 16) f[i] = track_div(track_feat_blend(f[i], e[i], nr, a.alpha, a.beta), m);
+              if (gj == 0) fw[0] = nf + 1;
+            }
+          }
+        }
+      } else if (smiss[s] + 1 > a.max_misses) {
+        for (int i = gj; i < FS; i += 16) fw[i] = 0;
+      }
+    }
+    __syncthreads();
   }
 
   // ---- steps 4 and 5: matched slots take their row, the others miss and may die
@@ -425,6 +622,22 @@ __global__ __launch_bounds__(TK_MAX_THREADS) void track_kernel(track_args_t<MOTI
   }
   const int born = min(nb, nfree);
   __syncthreads();
+  if constexpr (APP) {                                        // step 6 of the features, a group per born row (its slot's hits are 1)
+    for (int r = tid >> 4; r < n; r += ng) {
+      const int2 q = rst[r];
+      if (q.y != TK_TAKEN || shits[q.x] != 1) continue;
+      int32_t* fw = feat + (size_t)q.x * FS;
+      const float nr = rnorm[r];
+      if (nr > 0.0f) {
+        const float* e = emb + (size_t)r * D;
+        float* f = reinterpret_cast<float*>(fw + TRACK_FEAT_HEAD);
+        for (int i = gj; i < D; i += 16) f[i] = track_feat_first(e[i], nr);
+        if (gj < TRACK_FEAT_HEAD) fw[gj] = gj == 0 ? 1 : 0;
+      } else {
+        for (int i = gj; i < FS; i += 16) fw[i] = 0;
+      }
+    }
+  }
 
   // ---- steps 7 and 8: the rows' outputs, the fresh rows in row order
   const bool emit = a.fresh_dets != nullptr;
@@ -448,6 +661,8 @@ __global__ __launch_bounds__(TK_MAX_THREADS) void track_kernel(track_args_t<MOTI
       if (a.track_hits) a.track_hits[(size_t)b * R + r] = hits;
       if constexpr (MOTION)
         if (id == 0) row_box_store(a.track_box, (size_t)b * R + r, make_float4(0.f, 0.f, 0.f, 0.f));   // an assigned row's was written with its filter
+      if constexpr (APP)
+        if (a.track_cos && hits < 2) a.track_cos[(size_t)b * R + r] = 0.0f;                            // a matched row's was written with its feature
     }
     if (emit) {
       const bool fresh = hits == a.confirm_hits;             // hits >= 1 on an assigned row, 0 elsewhere; confirm_hits >= 1
@@ -482,17 +697,25 @@ __global__ __launch_bounds__(TK_MAX_THREADS) void track_kernel(track_args_t<MOTI
     head[4] += s_deaths;
     head[5] += nb - born;
     if constexpr (TWO) head[6] += nsecond;
+    if constexpr (APP) head[7] += *app_counter();              // written before the barrier that follows the features' step 4
     if (emit) a.fresh_count[b] = nfresh;
   }
 }
 
 }  // namespace
 
-template <bool MOTION, bool TWO>
-static void launch_track(const track_args_t<MOTION, TWO>& a, int frames, hipStream_t s) {
+// Dynamic LDS: 24 R + 48 M bytes, and 28 R + 52 M in the appearance form (yfv2_track_lds_bytes, yfv2_internal.h), whose entry point
+// refuses an (R, M) above TRACK_APP_LDS_MAX - the other forms' largest, R = 4096 and M = 1024, is 144 KB.
+template <bool MOTION, bool TWO, bool APP = false>
+static void launch_track(const track_args_t<MOTION, TWO, APP>& a, int frames, hipStream_t s) {
   const int threads = std::min(TK_MAX_THREADS, std::max(64, (a.R + 63) / 64 * 64));
-  const size_t lds = (size_t)24 * a.R + (size_t)48 * a.M;
-  YFV2_LAUNCH_LDS(yfv2_device(), (track_kernel<MOTION, TWO>), 24 * TRACK_MAX_R + 48 * TRACK_MAX_M, dim3((unsigned)frames), dim3((unsigned)threads), lds, s, a);
+  const size_t lds = yfv2_track_lds_bytes(APP, a.R, a.M);
+  constexpr int limit = APP ? (int)TRACK_APP_LDS_MAX : (int)yfv2_track_lds_bytes(false, TRACK_MAX_R, TRACK_MAX_M);
+  YFV2_LAUNCH_LDS(yfv2_device(), (track_kernel<MOTION, TWO, APP>), limit, dim3((unsigned)frames), dim3((unsigned)threads), lds, s, a);
+}
+void yfv2_launch_track_appearance(const TrackAppArgs& a, bool motion, bool two_pass, int frames, hipStream_t s) {
+  if (motion) { if (two_pass) launch_track<true, true, true>(a, frames, s); else launch_track<true, false, true>(a, frames, s); }
+  else { if (two_pass) launch_track<false, true, true>(a, frames, s); else launch_track<false, false, true>(a, frames, s); }
 }
 void yfv2_launch_track(const TrackArgs& a, int frames, hipStream_t s) { launch_track<false, false>(a, frames, s); }
 void yfv2_launch_track_motion(const TrackMotionArgs& a,int frames, hipStream_t s) { launch_track<true, false>(a, frames, s); }
@@ -504,6 +727,53 @@ void yfv2_launch_track_two_pass(const TrackTwoArgs& a, bool motion, int frames, 
 extern "C" int yfv2_track_iou(const float a[4], const float b[4], float* v) {
   if (!a || !b || !v) return yfv2_ctx_fail(nullptr, YFV2_ERR_ARG, "yfv2_track_iou: null pointer");
   *v = track_iou(a[0], a[1], a[2], a[3], track_area(a[0], a[1], a[2], a[3]), b[0], b[1], b[2], b[3], track_area(b[0], b[1], b[2], b[3]));
+  return YFV2_OK;
+}
+
+// ---- the appearance form's arithmetic for the host (tests pin it to the model without a device): the partial sums, the tree and
+// the element functions are the ones the kernel calls
+static float host_dot16(const float* a, const float* b, int D) {
+  float P[16];
+  for (int j = 0; j < 16; ++j) P[j] = track_dot16_part(a, b, D, j);
+  return track_dot16_tree(P);
+}
+static bool app_dim_ok(int32_t D) { return D >= TRACK_APP_MIN_D && D <= TRACK_APP_MAX_D && D % 16 == 0; }
+
+extern "C" int yfv2_track_cosine(const float* e, const float* f, int32_t D, float* norm, float* cos) {
+  if (!e || !f || !norm || !cos) return yfv2_ctx_fail(nullptr, YFV2_ERR_ARG, "yfv2_track_cosine: null pointer");
+  if (!app_dim_ok(D)) return yfv2_ctx_fail(nullptr, YFV2_ERR_ARG, "yfv2_track_cosine: D must be a multiple of 16 in 16..2048");
+  const float n = track_canon(track_sqrt(host_dot16(e, e, D)));
+  *norm = n;
+  *cos = track_cosine(host_dot16(e, f, D), n);
+  return YFV2_OK;
+}
+
+extern "C" int yfv2_track_feature_step(const float* f_in, int32_t n_feat_in, const float* e, int32_t D, float alpha, float* f_out, int32_t* n_feat_out) {
+  if (!f_in || !e || !f_out || !n_feat_out) return yfv2_ctx_fail(nullptr, YFV2_ERR_ARG, "yfv2_track_feature_step: null pointer");
+  if (!app_dim_ok(D)) return yfv2_ctx_fail(nullptr, YFV2_ERR_ARG, "yfv2_track_feature_step: D must be a multiple of 16 in 16..2048");
+  if (n_feat_in < 0) return yfv2_ctx_fail(nullptr, YFV2_ERR_ARG, "yfv2_track_feature_step: n_feat_in < 0");
+  if (!std::isfinite(alpha) || alpha < 0.0f || alpha > 1.0f) return yfv2_ctx_fail(nullptr, YFV2_ERR_ARG, "yfv2_track_feature_step: alpha must be in [0, 1]");
+  const float beta = 1.0f - alpha;
+  const float nr = track_sqrt(host_dot16(e, e, D));
+  std::vector<float> g(f_in, f_in + D);
+  int32_t nf = n_feat_in;
+  if (track_norm_ok(nr)) {
+    if (nf == 0) {
+      for (int i = 0; i < D; ++i) g[i] = track_feat_first(e[i], nr);
+      nf = 1;
+    } else {
+      for (int i = 0; i < D; ++i) g[i] = track_feat_blend(f_in[i], e[i], nr, alpha, beta);
+      const float m = track_sqrt(host_dot16(g.data(), g.data(), D));
+      if (track_norm_ok(m)) {
+        for (int i = 0; i < D; ++i) g[i] = track_div(g[i], m);
+        nf += 1;
+      } else {
+        std::copy(f_in, f_in + D, g.begin());
+      }
+    }
+  }
+  std::copy(g.begin(), g.end(), f_out);
+  *n_feat_out = nf;
   return YFV2_OK;
 }
 

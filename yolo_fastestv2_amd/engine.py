@@ -581,9 +581,49 @@ class Engine:
         return self._track_update("track_update_motion", motion, box, dets, count, streams, state, max_tracks, match_thres, class_aware, init_conf,
                                   max_misses, confirm_hits, fresh, out)
 
+    def track_update_appearance(self, dets, count, emb, streams, state, feat, max_tracks, match_thres=0.3, class_aware=True, init_conf=0.0,
+                                max_misses=30, confirm_hits=3, dim=128, prox_thres=0.5, app_thres=0.75, alpha=0.9, motion=None, two_pass=None,
+                                fresh=False, box=False, passes=False, cos=False, out=None):
+        """The update of any layout and pass form with appearance association (include/yfv2.h yfv2_track_update_appearance;
+        DESIGN.md 4.22).  emb: contiguous fp32 (B, R, dim) on the device, row r's embedding (a re-identification network's output for
+        the row's crop; not necessarily normalised); feat: contiguous int32 (S, max_tracks * (4 + dim)), all zero = empty, the
+        tracks' features, updated in place.  A first-pass edge whose IoU is above prox_thres takes the cosine of the row's embedding
+        with the track's feature as its value when that is above app_thres and above the IoU; a matched row's embedding is blended
+        into the feature with momentum alpha.  motion: None, True or a dict as for track_update_two_pass; two_pass: None - one pass -
+        or True or a dict with any of high_conf, low_conf, match_thres_low, tracked_only.  Returns what the call of that layout and
+        pass form returns (passes=True only with two_pass, box=True only with motion) and, with cos=True, last of all track_cos
+        (B, R) fp32: the cosine of each matched row with its track's feature before this update, 0 elsewhere."""
+        name = "track_update_appearance"
+        if motion is None or motion is False:
+            motion = None
+            if box:
+                raise ValueError(name + ": box=True needs motion")
+        else:
+            given = {} if motion is True else dict(motion)
+            motion = dict(std_pos=given.pop("std_pos", 1.0 / 20), std_vel=given.pop("std_vel", 1.0 / 160), std_meas=given.pop("std_meas", 1.0 / 20))
+            if given:
+                raise ValueError(name + ": motion takes std_pos, std_vel and std_meas, not %s" % sorted(given))
+        if two_pass is None or two_pass is False:
+            second = None
+            if passes:
+                raise ValueError(name + ": passes=True needs two_pass")
+        else:
+            given = {} if two_pass is True else dict(two_pass)
+            second = dict(high_conf=given.pop("high_conf", 0.5), low_conf=given.pop("low_conf", 0.1), match_thres_low=given.pop("match_thres_low", 0.5),
+                          tracked_only=given.pop("tracked_only", True))
+            if given:
+                raise ValueError(name + ": two_pass takes high_conf, low_conf, match_thres_low and tracked_only, not %s" % sorted(given))
+        dim = int(dim)
+        if dim < 16 or dim > 2048 or dim % 16:
+            raise ValueError(name + ": dim must be a multiple of 16 in 16..2048")
+        appearance = dict(dim=dim, prox_thres=prox_thres, app_thres=app_thres, alpha=alpha, emb=emb, feat=feat, cos=cos)
+        return self._track_update(name, motion, box, dets, count, streams, state, max_tracks, match_thres, class_aware, init_conf, max_misses,
+                                  confirm_hits, fresh, out, second=second, passes=passes, appearance=appearance)
+
     def _track_update(self, name, motion, box, dets, count, streams, state, max_tracks, match_thres, class_aware, init_conf, max_misses, confirm_hits,
-                      fresh, out, second=None, passes=False):
-        """the checks and the call of every form; motion: None or the three stds; second: None or the two-pass form's four values"""
+                      fresh, out, second=None, passes=False, appearance=None):
+        """the checks and the call of every form; motion: None or the three stds; second: None or the two-pass form's four values;
+        appearance: None or the appearance form's four values with its emb, feat and cos"""
         if (not torch.is_tensor(dets) or dets.dim() != 3 or dets.shape[2] != 6 or dets.dtype != torch.float32 or dets.device != self.device
                 or not dets.is_contiguous()):
             raise ValueError(name + ": dets must be contiguous fp32 (B,R,6) on %s" % (self.device,))
@@ -601,9 +641,19 @@ class Engine:
                 or not state.is_contiguous()):
             raise ValueError(name + ": state must be contiguous int32 (S,%d) on %s" % (words, self.device))
         S = int(state.shape[0])
-        shapes = ((B, R), (B, R)) + (((B, R, 6), (B, R), (B,)) if fresh else ()) + (((B, R, 4),) if box else ()) + (((B, R),) if passes else ())
+        cos = appearance is not None and bool(appearance["cos"])
+        if appearance is not None:
+            D, emb, feat = appearance["dim"], appearance["emb"], appearance["feat"]
+            if (not torch.is_tensor(emb) or tuple(emb.shape) != (B, R, D) or emb.dtype != torch.float32 or emb.device != self.device
+                    or not emb.is_contiguous()):
+                raise ValueError(name + ": emb must be contiguous fp32 (%d,%d,%d) on %s" % (B, R, D, self.device))
+            if (not torch.is_tensor(feat) or tuple(feat.shape) != (S, max_tracks * (4 + D)) or feat.dtype != torch.int32 or feat.device != self.device
+                    or not feat.is_contiguous()):
+                raise ValueError(name + ": feat must be contiguous int32 (%d,%d) on %s" % (S, max_tracks * (4 + D), self.device))
+        shapes = (((B, R), (B, R)) + (((B, R, 6), (B, R), (B,)) if fresh else ()) + (((B, R, 4),) if box else ()) + (((B, R),) if passes else ())
+                  + (((B, R),) if cos else ()))
         dtypes = ((torch.int32, torch.int32) + ((torch.float32, torch.int32, torch.int32) if fresh else ()) + ((torch.float32,) if box else ())
-                  + ((torch.int32,) if passes else ()))
+                  + ((torch.int32,) if passes else ()) + ((torch.float32,) if cos else ()))
         if out is None:
             out = tuple(torch.empty(sh, device=self.device, dtype=dt) for sh, dt in zip(shapes, dtypes))
         else:
@@ -619,7 +669,17 @@ class Engine:
         tid, hits = _ptr(out[0]), _ptr(out[1])
         fr = [_ptr(t) for t in out[2:5]] if fresh else [None] * 3
         mo = None if motion is None else _lib.TrackMotion(float(motion["std_pos"]), float(motion["std_vel"]), float(motion["std_meas"]))
-        if second is not None:
+        if appearance is not None:
+            se = None if second is None else _lib.TrackSecond(float(second["high_conf"]), float(second["low_conf"]), float(second["match_thres_low"]),
+                                                              1 if second["tracked_only"] else 0)
+            ap = _lib.TrackAppearance(appearance["dim"], float(appearance["prox_thres"]), float(appearance["app_thres"]), float(appearance["alpha"]))
+            at = 5 if fresh else 2                            # the optional outputs after the fresh ones: box, passes, cos
+            check(_lib.lib().yfv2_track_update_appearance(self._h, _ptr(dets), _ptr(count), R, B, arr, _ptr(state), S, C.byref(rule),
+                                                          None if mo is None else C.byref(mo), None if se is None else C.byref(se), C.byref(ap),
+                                                          _ptr(appearance["emb"]), _ptr(appearance["feat"]), tid, hits,
+                                                          _ptr(out[at + (1 if box else 0)]) if passes else None, _ptr(out[at]) if box else None,
+                                                          _ptr(out[-1]) if cos else None, *fr, _stream(self.device)), self._h)
+        elif second is not None:
             se = _lib.TrackSecond(float(second["high_conf"]), float(second["low_conf"]), float(second["match_thres_low"]), 1 if second["tracked_only"] else 0)
             check(_lib.lib().yfv2_track_update_two_pass(self._h, _ptr(dets), _ptr(count), R, B, arr, _ptr(state), S, C.byref(rule),
                                                         None if mo is None else C.byref(mo), C.byref(se), tid, hits, _ptr(out[-1]) if passes else None,
