@@ -280,13 +280,42 @@ YFV2_API int yfv2_detect_tiled_u8(yfv2_handle h, const yfv2_frame* frames, int32
  *                  G = clamp((yy + (1 << 19) + CVG * v + CUG * u) >> 20, 0, 255)
  *                  B = clamp((yy + (1 << 19) + CUB * u) >> 20, 0, 255)              stored B, G, R: the network's channel order
  * OpenCV is not in this image: the tests compare with a numpy statement of this published arithmetic (tests/yuv_model.py) - parity
- * with cv2 proper is unpinned, exactly as for the resize. */
-enum { YFV2_YUV_NV12 = 0, YFV2_YUV_NV21 = 1, YFV2_YUV_I420 = 2 };
+ * with cv2 proper is unpinned, exactly as for the resize.
+ *
+ * 10-bit frames: what HEVC Main10, AV1 and VP9 profile 2 streams decode to.  Two formats of two-byte samples,
+ * little-endian 16-bit words; yfv2_frame_yuv is unchanged (uint8_t* plane pointers, pitches in BYTES):
+ *   YFV2_YUV_P010  semi-planar like NV12, U first in the interleaved plane; the value is in the HIGH 10 bits, v = word >> 6, and
+ *                  the low 6 bits are ignored, whatever they hold (the hardware decoders' format)
+ *   YFV2_YUV_I010  planar like I420 (yuv420p10le); the value is in the LOW 10 bits, v = word & 1023, and the high bits are ignored
+ *   pixel (r, c)   the 8-bit rule with every sample index doubled to a byte offset: luma word at y + R * pitch_y + 2 * C; chroma at
+ *                  (R >> 1, C >> 1), replicated: P010 u + (R>>1) * pitch_c + 4 * (C>>1) is U and the word after it V; I010
+ *                  u + (R>>1) * pitch_c + 2 * (C>>1) is U and v + ... is V
+ *   colour         the same expression on 10-bit codes; the 8-bit B, G, R is rounded ONCE from 10-bit precision, not truncated to
+ *                  8 bits first.  Every literal is rint(k * 2^20) of the real coefficient per 10-bit code - limited range: luma
+ *                  255 / (219 * 4), chroma 255 / (224 * 4) times 2(1-Kr), -2Kr(1-Kr)/Kg, -2Kb(1-Kb)/Kg, 2(1-Kb); full range:
+ *                  255 / 1023 in place of both; Kr / Kb = 0.299 / 0.114 (BT.601), 0.2126 / 0.0722 (BT.709).  These are NOT OpenCV
+ *                  literals: cv2 has no P010 conversion to agree with (tests/yuv16_model.py re-derives them in float64).
+ *                                        off  CY      CVR     CVG      CUG      CUB
+ *                    YFV2_BT601_LIMITED  64   305236  418389  -213115  -102698  528805
+ *                    YFV2_BT709_LIMITED  64   305236  469956  -139699  -55902   553753
+ *                    YFV2_BT601_FULL     0    261375  366448  -186658  -89949   463157
+ *                    YFV2_BT709_FULL     0    261375  411614  -122356  -48962   485008
+ *                  yy = max(Y - off, 0) * CY; u = U - 512; v = V - 512; R, G, B as above (int32, + (1 << 19), >> 20, clamp to 0..255)
+ * THE RULE is the one above: every *_yuv entry point on a 10-bit frame is bit-identical to converting the frame with this formula
+ * and calling the _u8 entry point of the same name.  For limited-range frames whose samples are 4 times 8-bit samples the result is within 1 of the
+ * 8-bit rule on those.  Checked in addition, before anything is enqueued (YFV2_ERR_ARG, the message names the frame and the
+ * field): y, u (and v) 2-byte aligned; pitch_y and pitch_c even; pitch_y >= 2 * (x0 + width); pitch_c at least the last chroma byte
+ * of a row; a frame wider than the two-byte width limit - the widest whose two luma rows, chroma rows and output row fit 160 KiB of
+ * LDS, 20 343 at cfg.width 352 (half of the 8-bit limit: the staged rows take twice the bytes); and all frames of one call must
+ * have ONE sample width - a call that mixes 8-bit and 10-bit frames is refused, the message naming the first frame that differs
+ * from frame 0 (one launch is one kernel instantiation; split the batch). */
+enum { YFV2_YUV_NV12 = 0, YFV2_YUV_NV21 = 1, YFV2_YUV_I420 = 2,
+       YFV2_YUV_P010 = 16, YFV2_YUV_I010 = 17 };   /* bit 4: two-byte samples (the 10-bit formats, below) */
 enum { YFV2_BT601_LIMITED = 0, YFV2_BT709_LIMITED = 1, YFV2_BT601_FULL = 2, YFV2_BT709_FULL = 3 };
 typedef struct yfv2_frame_yuv {
-  const uint8_t* y;        /* DEVICE: luma plane, any alignment */
-  const uint8_t* u;        /* NV12/NV21: the interleaved chroma plane; I420: the U plane */
-  const uint8_t* v;        /* I420: the V plane; ignored for NV12/NV21 */
+  const uint8_t* y;        /* DEVICE: luma plane, any alignment (P010/I010: 2-byte aligned, like u and v) */
+  const uint8_t* u;        /* NV12/NV21/P010: the interleaved chroma plane; I420/I010: the U plane */
+  const uint8_t* v;        /* I420/I010: the V plane; ignored for NV12/NV21/P010 */
   int64_t pitch_y, pitch_c;/* bytes per row of the luma / chroma plane(s) */
   int32_t x0, y0;          /* top-left pixel of the frame inside the planes (any parity): a crop needs no copy */
   int32_t width, height;   /* pixels, >= 1, any parity */
@@ -335,7 +364,7 @@ YFV2_API int yfv2_detect_tiled_yuv(yfv2_handle h, const yfv2_frame_yuv* frames, 
  * alpha, beta: HOST, B floats each; they travel with the frame descriptors in their one copy on `stream`.  dst: DEVICE, 16-byte
  * aligned.  Checked before anything is enqueued (YFV2_ERR_ARG with a message): everything yfv2_resize_frames_u8 / _yuv checks of
  * the frames, under a lower width limit - the row is staged in LDS as fp32: (160 KiB - 1024 - 12 cfg.width) / 6 - 6 pixels for
- * B, G, R frames (26 426 at width 352), 39 641 for YUV frames at width 352; exactly one of alpha / beta NULL; an alpha or beta that is
+ * B, G, R frames (26 426 at width 352), 39 641 for YUV frames at width 352 (19 819 for P010 / I010 frames); exactly one of alpha / beta NULL; an alpha or beta that is
  * not finite (the message names the frame); dst NULL or not 16-byte aligned.  B > max_batch is YFV2_ERR_BATCH.  Enqueue only: no
  * workspace, no device wait. */
 YFV2_API int yfv2_train_batch_frames_u8(yfv2_handle h, const yfv2_frame* frames, int32_t B,
@@ -1047,6 +1076,9 @@ YFV2_API int yfv2_debug_plan_c2_label(const yfv2_config* cfg, const yfv2_tensor_
  * (the network's, or out_w), 1 .. 2^20.  *lds_bytes = the LDS of one workgroup of that launch for a frame w wide, *max_width = the
  * widest frame the entry point admits at W (either may be NULL).  Opens no device. */
 YFV2_API int yfv2_debug_rows(int32_t row_kind, int32_t yuv, int32_t w, int32_t W, int64_t* lds_bytes, int32_t* max_width);
+/* ... and for yfv2_frame_yuv frames of two-byte samples (YFV2_YUV_P010 / _I010): the same arguments, checks and results.  (yuv = 1
+ * above is the one-byte formats and yuv = 2 stays an argument error.)  An addition within ABI 7. */
+YFV2_API int yfv2_debug_rows16(int32_t row_kind, int32_t w, int32_t W, int64_t* lds_bytes, int32_t* max_width);
 
 #ifdef __cplusplus
 }

@@ -81,10 +81,11 @@ def timed(fn, iters):
     return e0.elapsed_time(e1) / iters
 
 
-def trace_stats(args):
+def trace_stats(args, script=os.path.abspath(__file__)):
+    """the kernels' (calls, average ns) of `script --child` (this tool's, or yuv16_probe.py's) under rocprofv3"""
     with tempfile.TemporaryDirectory() as d:
         cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "-o", "yuv", "--",
-               sys.executable, os.path.abspath(__file__), "--child", "--frames", str(args.frames), "--iters", str(args.iters),
+               sys.executable, script, "--child", "--frames", str(args.frames), "--iters", str(args.iters),
                "--warmup", str(args.warmup), "--seed", str(args.seed)]
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
         if r.returncode != 0:

@@ -101,8 +101,18 @@ int yfv2_debug_plan_c2_label(const yfv2_config* cfg, const yfv2_tensor_desc* ten
 int yfv2_debug_rows(int32_t row_kind, int32_t yuv, int32_t w, int32_t W, int64_t* lds_bytes, int32_t* max_width) {
   if (row_kind < 0 || row_kind >= YFV2_ROW_KINDS || yuv < 0 || yuv > 1 || w < 1 || w > (1 << 26) || W < 1 || W > (1 << 20))
     return fail(nullptr, YFV2_ERR_ARG, "yfv2_debug_rows: bad argument");
-  if (lds_bytes) *lds_bytes = (int64_t)yfv2_rows_lds_bytes((Yfv2RowKind)row_kind, yuv != 0, w, W);
-  if (max_width) *max_width = yfv2_rows_max_width((Yfv2RowKind)row_kind, yuv != 0, W);
+  const Yfv2FrameKind frames = yuv ? YFV2_FRAMES_YUV8 : YFV2_FRAMES_BGR;
+  if (lds_bytes) *lds_bytes = (int64_t)yfv2_rows_lds_bytes((Yfv2RowKind)row_kind, frames, w, W);
+  if (max_width) *max_width = yfv2_rows_max_width((Yfv2RowKind)row_kind, frames, W);
+  return YFV2_OK;
+}
+
+// ... and of the YUV frame kind with two-byte samples (YFV2_YUV_P010 / _I010; tests/yuv16_model.py): the same checks
+int yfv2_debug_rows16(int32_t row_kind, int32_t w, int32_t W, int64_t* lds_bytes, int32_t* max_width) {
+  if (row_kind < 0 || row_kind >= YFV2_ROW_KINDS || w < 1 || w > (1 << 26) || W < 1 || W > (1 << 20))
+    return fail(nullptr, YFV2_ERR_ARG, "yfv2_debug_rows16: bad argument");
+  if (lds_bytes) *lds_bytes = (int64_t)yfv2_rows_lds_bytes((Yfv2RowKind)row_kind, YFV2_FRAMES_YUV16, w, W);
+  if (max_width) *max_width = yfv2_rows_max_width((Yfv2RowKind)row_kind, YFV2_FRAMES_YUV16, W);
   return YFV2_OK;
 }
 

@@ -37,19 +37,27 @@ static int check_frame(yfv2_handle h, const std::string& at, const yfv2_frame& f
 // what every YUV entry point checks of one caller's frame - a whole frame of yfv2_detect_tiled_yuv or a frame of a batch; `at` as in
 // check_frame.  The width limit is not here: it binds what is resized, which for a tiled frame are its tiles.
 static int check_frame_yuv(yfv2_handle h, const std::string& at, const yfv2_frame_yuv& f) {
-  if (f.format != YFV2_YUV_NV12 && f.format != YFV2_YUV_NV21 && f.format != YFV2_YUV_I420)
+  if (f.format != YFV2_YUV_NV12 && f.format != YFV2_YUV_NV21 && f.format != YFV2_YUV_I420 && f.format != YFV2_YUV_P010 && f.format != YFV2_YUV_I010)
     return fail(h, YFV2_ERR_ARG, at + "unknown format " + std::to_string(f.format));
+  const int sb = yfv2_yuv_sample_bytes(f.format);           // 2: every sample index below is doubled to a byte offset
   if (f.colour < YFV2_BT601_LIMITED || f.colour > YFV2_BT709_FULL) return fail(h, YFV2_ERR_ARG, at + "unknown colour " + std::to_string(f.colour));
   if (f.height < 1 || f.width < 1) return fail(h, YFV2_ERR_ARG, at + "height and width must be >= 1");
   if (f.x0 < 0 || f.y0 < 0) return fail(h, YFV2_ERR_ARG, at + "x0 and y0 must be >= 0");
   if (!f.y) return fail(h, YFV2_ERR_ARG, at + "null y");
   if (!f.u) return fail(h, YFV2_ERR_ARG, at + "null u");
-  const bool planar = f.format == YFV2_YUV_I420;
-  if (planar && !f.v) return fail(h, YFV2_ERR_ARG, at + "null v (I420)");
+  const bool planar = yfv2_yuv_planar(f.format);
+  if (planar && !f.v) return fail(h, YFV2_ERR_ARG, at + (sb == 1 ? "null v (I420)" : "null v (I010)"));
+  if (sb == 2) {
+    if (reinterpret_cast<uintptr_t>(f.y) & 1) return fail(h, YFV2_ERR_ARG, at + "y must be 2-byte aligned (two-byte samples)");
+    if (reinterpret_cast<uintptr_t>(f.u) & 1) return fail(h, YFV2_ERR_ARG, at + "u must be 2-byte aligned (two-byte samples)");
+    if (planar && (reinterpret_cast<uintptr_t>(f.v) & 1)) return fail(h, YFV2_ERR_ARG, at + "v must be 2-byte aligned (two-byte samples)");
+    if (f.pitch_y & 1) return fail(h, YFV2_ERR_ARG, at + "pitch_y " + std::to_string(f.pitch_y) + " must be even (two-byte samples)");
+    if (f.pitch_c & 1) return fail(h, YFV2_ERR_ARG, at + "pitch_c " + std::to_string(f.pitch_c) + " must be even (two-byte samples)");
+  }
   const long long xe = (long long)f.x0 + f.width, ye = (long long)f.y0 + f.height;     // one past the frame's last column / row in the planes
   if (xe > 0x7fffffffll || ye > 0x7fffffffll) return fail(h, YFV2_ERR_ARG, at + "x0 + width and y0 + height must be below 2^31");
-  if (f.pitch_y < xe) return fail(h, YFV2_ERR_ARG, at + "pitch_y " + std::to_string(f.pitch_y) + " < x0 + width");
-  const long long crow = (((xe - 1) >> 1) + 1) * (planar ? 1 : 2);                       // chroma bytes of a row up to the frame's last sample
+  if (f.pitch_y < sb * xe) return fail(h, YFV2_ERR_ARG, at + "pitch_y " + std::to_string(f.pitch_y) + (sb == 1 ? " < x0 + width" : " < 2 * (x0 + width)"));
+  const long long crow = (((xe - 1) >> 1) + 1) * (planar ? 1 : 2) * sb;                  // chroma bytes of a row up to the frame's last sample
   if (f.pitch_c < crow) return fail(h, YFV2_ERR_ARG, at + "pitch_c " + std::to_string(f.pitch_c) + " < " + std::to_string(crow) + ", the last chroma byte of a row");
   if (f.pitch_y > (1ll << 40) || (ye - 1) * f.pitch_y > (1ll << 52)) return fail(h, YFV2_ERR_ARG, at + "pitch_y out of range");
   if (f.pitch_c > (1ll << 40) || ((ye - 1) >> 1) * f.pitch_c > (1ll << 52)) return fail(h, YFV2_ERR_ARG, at + "pitch_c out of range");
@@ -62,13 +70,15 @@ struct FrameBatch {
   std::vector<ResizeFrame> t;
   std::vector<ResizeFrameYuv> yuv;
   int max_w = 1;
+  int sample_bytes = 1;       // of a YUV batch: one launch is one instantiation, so all its frames have one sample width
+  Yfv2FrameKind kind() const { return yuv.empty() ? YFV2_FRAMES_BGR : sample_bytes == 2 ? YFV2_FRAMES_YUV16 : YFV2_FRAMES_YUV8; }
 };
 
 // ---- the two kinds: only what differs.  check = one caller frame (a whole frame of a tiled call too); expand = frame b of the
 // batch into its device descriptor(s), after its own last check; crop = the frame that a tile of `fr` is (the rectangle was checked).
 struct BgrFrames {
   using Frame = yfv2_frame;
-  static constexpr bool YUV = false;
+  static Yfv2FrameKind kind(const Frame&) { return YFV2_FRAMES_BGR; }
   static int check(yfv2_handle h, const std::string& at, const Frame& f) { return check_frame(h, at, f); }
   static int expand(yfv2_handle h, const std::string& at, const Frame& f, FrameBatch& fb, size_t b) {
     if (f.row_pitch > (1ll << 40) || (long long)(f.height - 1) * f.row_pitch > (1ll << 52))
@@ -82,14 +92,15 @@ struct BgrFrames {
 // (kernel: resize_frames_yuv_kernel, yfv2_pre.hip)  The descriptor has the origin folded into the plane pointers.
 struct YuvFrames {
   using Frame = yfv2_frame_yuv;
-  static constexpr bool YUV = true;
+  static Yfv2FrameKind kind(const Frame& f) { return yfv2_yuv_sample_bytes(f.format) == 2 ? YFV2_FRAMES_YUV16 : YFV2_FRAMES_YUV8; }   // (of a checked frame)
   static int check(yfv2_handle h, const std::string& at, const Frame& f) { return check_frame_yuv(h, at, f); }
   static int expand(yfv2_handle, const std::string&, const Frame& f, FrameBatch& fb, size_t b) {
     if (fb.yuv.empty()) fb.yuv.assign(fb.t.size(), ResizeFrameYuv{});
     ResizeFrameYuv& r = fb.yuv[b];
-    r.y = f.y; r.ca = f.u; r.cb = f.format == YFV2_YUV_I420 ? f.v : nullptr;      // the planes at their own origin ...
+    fb.sample_bytes = yfv2_yuv_sample_bytes(f.format);
+    r.y = f.y; r.ca = f.u; r.cb = yfv2_yuv_planar(f.format) ? f.v : nullptr;      // the planes at their own origin ...
     r.pitch_y = f.pitch_y; r.pitch_c = f.pitch_c; r.h = f.height; r.w = f.width;
-    r.px = 0; r.py = 0; r.format = f.format; r.coef = yfv2_yuv_coef(f.colour);
+    r.px = 0; r.py = 0; r.format = f.format; r.coef = yfv2_yuv_coef(f.colour, fb.sample_bytes);
     yfv2_yuv_move(r, f.x0, f.y0);                                                 // ... moved to the frame's (the fold, yfv2_internal.h)
     r.scale_x = fb.t[b].scale_x; r.scale_y = fb.t[b].scale_y;
     return YFV2_OK;
@@ -113,12 +124,17 @@ static int check_frames(yfv2_handle h, const char* what, const typename Kind::Fr
   if (B < 1) return fail(h, YFV2_ERR_ARG, w_ + ": B < 1");
   if (B > h->cfg.max_batch)
     return fail(h, YFV2_ERR_BATCH, w_ + ": batch " + std::to_string(B) + " above max_batch=" + std::to_string(h->cfg.max_batch));
-  const int limit = yfv2_rows_max_width(rows, Kind::YUV, W);
+  Yfv2FrameKind kind = YFV2_FRAMES_BGR;      // of frame 0, once it is checked; the width limit is that kind's
+  int limit = 0;
   fb.t.assign((size_t)B, ResizeFrame{});
   for (int32_t b = 0; b < B; ++b) {
     const typename Kind::Frame& f = frames[b];
     const std::string at = w_ + ": frame " + std::to_string(b) + ": ";
     if (int rc = Kind::check(h, at, f)) return rc;
+    if (b == 0) { kind = Kind::kind(f); limit = yfv2_rows_max_width(rows, kind, W); }
+    if (Kind::kind(f) != kind)
+      return fail(h, YFV2_ERR_ARG, at + "format has " + (kind == YFV2_FRAMES_YUV16 ? "one-byte samples, frame 0 two-byte" : "two-byte samples, frame 0 one-byte") +
+                                       " samples: the frames of one call must have one sample width");
     if (f.width > limit) return fail(h, YFV2_ERR_ARG, at + "frames wider than " + std::to_string(limit) + " pixels are not supported");
     const FrameScales s = frame_scales(f.width, f.height, W, H);
     ResizeFrame& r = fb.t[(size_t)b];
@@ -162,7 +178,7 @@ static int enqueue_rows(yfv2_handle h, const FrameBatch& fb, int32_t B, Yfv2RowK
                         const float* beta = nullptr) {
   const bool yuv = !fb.yuv.empty();
   auto submit = [&](const auto& table, void* d_table) {     // the batch's table, the handle's device table of its kind
-    auto launch = [&](const void* d) { yfv2_launch_rows(rows, yuv, d, B, fb.max_w, dst, h->cfg.height, h->cfg.width, s); };
+    auto launch = [&](const void* d) { yfv2_launch_rows(rows, fb.kind(), d, B, fb.max_w, dst, h->cfg.height, h->cfg.width, s); };
     if (rows == YFV2_ROWS_TRAIN) return submit_frames(h, with_augment(table, alpha, beta), d_table, B, s, launch);
     return submit_frames(h, table, d_table, B, s, launch);
   };
@@ -295,7 +311,7 @@ static int crop_detections(yfv2_handle h, const char* what, const typename Kind:
   const bool yuv = !fb.yuv.empty();
   auto launch = [&](const void* d) {       // the plan's two launches, then the rows of the table they wrote
     yfv2_launch_crop_plan(a, tensor != nullptr, yuv, d, table, s);
-    yfv2_launch_rows(rows, yuv, table, cap, fb.max_w, crops, q.out_h, q.out_w, s);
+    yfv2_launch_rows(rows, fb.kind(), table, cap, fb.max_w, crops, q.out_h, q.out_w, s);
   };
   return yuv ? submit_frames(h, fb.yuv, h->d_frames_yuv, B, s, launch) : submit_frames(h, fb.t, h->d_frames, B, s, launch);
 }
@@ -511,8 +527,8 @@ int yfv2_resize_u8(yfv2_handle h, const uint8_t* src, int32_t B, int32_t src_h, 
   if (!h) return fail(nullptr, YFV2_ERR_ARG, "null handle");
   if (!src || !dst || B < 1 || src_h < 1 || src_w < 1) return fail(h, YFV2_ERR_ARG, "yfv2_resize_u8: bad argument");
   if ((reinterpret_cast<uintptr_t>(dst) & 3) != 0) return fail(h, YFV2_ERR_ARG, "yfv2_resize_u8: dst must be 4-byte aligned");
-  if (yfv2_rows_lds_bytes(YFV2_ROWS_U8, false, src_w, h->cfg.width) > (size_t)YFV2_LDS_FULL || (long long)B * h->cfg.height > 0x7fffffffll)
-    return fail(h, YFV2_ERR_ARG, "yfv2_resize_u8: source rows wider than " + std::to_string(yfv2_rows_max_width(YFV2_ROWS_U8, false, h->cfg.width)) + " pixels are not supported");
+  if (yfv2_rows_lds_bytes(YFV2_ROWS_U8, YFV2_FRAMES_BGR, src_w, h->cfg.width) > (size_t)YFV2_LDS_FULL || (long long)B * h->cfg.height > 0x7fffffffll)
+    return fail(h, YFV2_ERR_ARG, "yfv2_resize_u8: source rows wider than " + std::to_string(yfv2_rows_max_width(YFV2_ROWS_U8, YFV2_FRAMES_BGR, h->cfg.width)) + " pixels are not supported");
   DeviceGuard guard(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const FrameScales sc = frame_scales(src_w, src_h, h->cfg.width, h->cfg.height);

@@ -334,10 +334,15 @@ struct ResizeArgs {
   int B, SH, SW, H, W;
   double scale_x, scale_y;   // 1 / (W / SW), 1 / (H / SH) in double, like cv::resize derives them
 };
-void yfv2_launch_resize(const ResizeArgs& a, hipStream_t s);   // LDS: yfv2_rows_lds_bytes(YFV2_ROWS_U8, false, a.SW, a.W)
+void yfv2_launch_resize(const ResizeArgs& a, hipStream_t s);   // LDS: yfv2_rows_lds_bytes(YFV2_ROWS_U8, YFV2_FRAMES_BGR, a.SW, a.W)
 // The row kernels of a ragged batch (yfv2_pre.hip): one workgroup per (table entry, output row) resizes a frame's row and hands it
-// to the epilogue of its row kind.  A kind and a YUV flag name the instantiation and with it the table's descriptor type and dst's
-// element type; yfv2_pre.hip holds the one description of each (its LDS layout, hence its bytes and its width limit).
+// to the epilogue of its row kind.  A row kind and a frame kind name the instantiation and with it the table's descriptor type and
+// dst's element type; yfv2_pre.hip holds the one description of each (its LDS layout, hence its bytes and its width limit).
+enum Yfv2FrameKind {       // what a frame's samples are
+  YFV2_FRAMES_BGR,         // packed B, G, R bytes (yfv2_frame)
+  YFV2_FRAMES_YUV8,        // yfv2_frame_yuv, 1-byte samples: NV12, NV21, I420
+  YFV2_FRAMES_YUV16,       // yfv2_frame_yuv, 2-byte samples: P010, I010 (the descriptors are the 1-byte kind's, byte for byte)
+};
 enum Yfv2RowKind {         // descriptor (B, G, R / YUV)            dst
   YFV2_ROWS_U8,            // ResizeFrame / ResizeFrameYuv          uint8 (n, H, W, 3), 4-byte aligned
   YFV2_ROWS_COUNTED_U8,    // CropFrame / CropFrameYuv              uint8 (n, H, W, 3): the live entries of a counted table
@@ -347,11 +352,12 @@ enum Yfv2RowKind {         // descriptor (B, G, R / YUV)            dst
 };
 constexpr int YFV2_ROW_KINDS = 5;
 // grid n * H (n: the batch, or a counted table's capacity), LDS for a source row of max_w pixels
-void yfv2_launch_rows(Yfv2RowKind kind, bool yuv, const void* table, int n, int max_w, void* dst, int H, int W, hipStream_t s);
-size_t yfv2_rows_lds_bytes(Yfv2RowKind kind, bool yuv, int w, int W);   // LDS of one workgroup for a frame w pixels wide, output rows of W
+void yfv2_launch_rows(Yfv2RowKind kind, Yfv2FrameKind frames, const void* table, int n, int max_w, void* dst, int H, int W, hipStream_t s);
+size_t yfv2_rows_lds_bytes(Yfv2RowKind kind, Yfv2FrameKind frames, int w, int W);   // LDS of one workgroup for a frame w pixels wide, output rows of W
 // The widest frame the entry points of the kind admit.  B, G, R: (YFV2_LDS_FULL - the row's own bytes) / 6 - (ALIGN + 2) / 3, every
-// row up to it fits; YUV: the widest frame that fits.  A 16-byte kind never admits a frame that the uint8 kinds refuse at the same W.
-int yfv2_rows_max_width(Yfv2RowKind kind, bool yuv, int W);
+// row up to it fits; YUV, either sample width: the widest frame that fits.  A 16-byte kind never admits a frame that the uint8 kinds
+// refuse at the same W, and 2-byte samples never one that 1-byte samples refuse.
+int yfv2_rows_max_width(Yfv2RowKind kind, Yfv2FrameKind frames, int W);
 // one frame of a ragged batch (yfv2_resize_frames_u8 / yfv2_detect_frames_u8), expanded on the host and uploaded as a table
 struct ResizeFrame {
   const unsigned char* data;  // first byte of the frame (any alignment), device
@@ -363,11 +369,15 @@ struct ResizeFrame {
 // one YUV 4:2:0 frame of a ragged batch (yfv2_resize_frames_yuv / yfv2_detect_frames_yuv): the caller's yfv2_frame_yuv with its
 // origin folded into the plane pointers on the host - pixel (r, c) of the frame has its luma at y[r * pitch_y + c] and its chroma
 // at row (r + py) >> 1, sample (c + px) >> 1 of ca / cb - so the kernel sees every frame, crop or not, as a plane set of its own
-struct YuvCoef { int off, cy, cvr, cvg, cug, cub; };   // one row of the colour table (yfv2_pre.hip)
+// A frame of 2-byte samples (YFV2_YUV_P010 / _I010: bit 4 of the format) is the same descriptor: every sample index below is doubled
+// to a byte offset, the planes are 2-byte aligned and the pitches even, and the coefficients are the 10-bit table's.
+struct YuvCoef { int off, cy, cvr, cvg, cug, cub; };   // one row of a colour table (yfv2_pre.hip)
+__host__ __device__ constexpr int yfv2_yuv_sample_bytes(int format) { return (format & 16) ? 2 : 1; }
+__host__ __device__ constexpr bool yfv2_yuv_planar(int format) { return format == 2 || format == 17; }   // YFV2_YUV_I420, YFV2_YUV_I010 (include/yfv2.h)
 struct ResizeFrameYuv {
   const unsigned char* y;     // luma of pixel (0, 0): plane + y0 * pitch_y + x0 (any alignment), device
-  const unsigned char* ca;    // NV12 / NV21: the interleaved plane at chroma row y0 >> 1, byte 2 * (x0 >> 1); I420: the U plane at (y0 >> 1, x0 >> 1)
-  const unsigned char* cb;    // I420: the V plane likewise; NV12 / NV21: null
+  const unsigned char* ca;    // NV12 / NV21 / P010: the interleaved plane at chroma row y0 >> 1, sample pair x0 >> 1; I420 / I010: the U plane at (y0 >> 1, x0 >> 1)
+  const unsigned char* cb;    // I420 / I010: the V plane likewise; NV12 / NV21 / P010: null
   long long pitch_y, pitch_c; // bytes from one row to the next
   int h, w;
   int px, py;                 // x0 & 1, y0 & 1: the parity of the origin decides which pixels share a chroma sample
@@ -380,8 +390,9 @@ struct ResizeFrameYuv {
 __host__ __device__ inline void yfv2_yuv_move(ResizeFrameYuv& r, int dx, int dy) {
   const bool planar = r.cb != nullptr;
   const int cx = (dx + r.px) >> 1, cy = (dy + r.py) >> 1;      // chroma sample / row of the new origin, from the old one's
-  const long long coff = (long long)cy * r.pitch_c + (long long)cx * (planar ? 1 : 2);
-  r.y += (long long)dy * r.pitch_y + dx;
+  const int sb = yfv2_yuv_sample_bytes(r.format);            // an offset in samples is sb times that in bytes
+  const long long coff = (long long)cy * r.pitch_c + (long long)cx * ((planar ? 1 : 2) * sb);
+  r.y += (long long)dy * r.pitch_y + (long long)dx * sb;
   r.ca += coff;
   if (planar) r.cb += coff;
   r.px = (dx + r.px) & 1; r.py = (dy + r.py) & 1;
@@ -389,12 +400,15 @@ __host__ __device__ inline void yfv2_yuv_move(ResizeFrameYuv& r, int dx, int dy)
 // The resize scale of one axis, `in` source pixels to `out`: cv::resize's inv_scale = dsize / ssize, scale = 1 / inv_scale, two
 // correctly rounded fp64 divisions on either side (no unit that calls it has a fast-math flag).
 __host__ __device__ inline double yfv2_resize_scale(int out, int in) { return 1.0 / ((double)out / (double)in); }
-YuvCoef yfv2_yuv_coef(int colour);                // YFV2_BT601_LIMITED .. YFV2_BT709_FULL -> its row
+YuvCoef yfv2_yuv_coef(int colour, int sample_bytes = 1);   // YFV2_BT601_LIMITED .. YFV2_BT709_FULL -> its row of the 8-bit (1) or 10-bit (2) table
 // The training entry points (yfv2_train_batch_frames_u8 / _yuv): a frame's resize descriptor with its contrast / brightness pair
 // behind it, in the same table and the same one copy (the handle's tables are sized for these).  The resize kernels keep their own
 // descriptors and strides; the training kernels run the same body on the base part.
 struct TrainFrame : ResizeFrame { float alpha, beta; };
 struct TrainFrameYuv : ResizeFrameYuv { float alpha, beta; };
+// The descriptors of the 2-byte instantiations of resize_frames_yuv_kernel: the layouts above, the sample width in the TYPE, so that
+// the 1-byte instantiations keep their names and their instruction streams.  The host and the crop plan write the 1-byte types.
+template <class D> struct Samples16 : D { static constexpr int SAMPLE_BYTES = 2; };
 // ---- second-stage crops (yfv2_crop_detections_u8 / _yuv; kernels: yfv2_crops.hip, the resize launch: yfv2_launch_rows)
 // THE RECTANGLE RULE, one axis of it, written once: yfv2_crop_rect (host) and the plan kernels (device) both call this function;
 // include/yfv2.h states it for callers, tests/crops_model.py in Python.  a1, a2: the box's two edges on the axis; pad: the factor;
@@ -486,9 +500,10 @@ template <class D> struct Letterboxed : Counted<D> { int ox0, oy0, iw, ih; stati
 using TensorFrame = Letterboxed<ResizeFrame>;
 using TensorFrameYuv = Letterboxed<ResizeFrameYuv>;
 struct CropTensorPlanArgs : CropPlanArgs { CropTensorParams p; int letterbox; };   // the crop kinds' arguments stay what they were
-// The plan of either family, two launches: frames = the batch's ResizeFrame / ResizeFrameYuv table (yuv), table = the counted table
-// it writes - CropFrame / CropFrameYuv, whose kernels take the CropPlanArgs part of a by value, or (tensor) TensorFrame /
-// TensorFrameYuv.  The rows of the table's live entries are then yfv2_launch_rows' (YFV2_ROWS_COUNTED_U8, YFV2_ROWS_TENSOR_*).
+// The plan of either family, two launches: frames = the batch's ResizeFrame / ResizeFrameYuv table (yuv, either sample
+// width: the fold reads the format), table = the counted table it writes - CropFrame / CropFrameYuv, whose kernels take the
+// CropPlanArgs part of a by value, or (tensor) TensorFrame / TensorFrameYuv.  The rows of the table's live entries are then
+// yfv2_launch_rows' (YFV2_ROWS_COUNTED_U8, YFV2_ROWS_TENSOR_*).
 void yfv2_launch_crop_plan(const CropTensorPlanArgs& a, bool tensor, bool yuv, const void* frames, void* table, hipStream_t s);
 // ---- the per-stream IoU tracker (yfv2_track_update; kernel and the IoU's one function: yfv2_track.hip)
 constexpr int TRACK_MAX_R = 4096, TRACK_MAX_M = 1024;

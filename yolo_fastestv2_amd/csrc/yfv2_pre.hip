@@ -14,10 +14,10 @@
 // Built with -ffp-contract=off: the coefficient arithmetic must round like the separate C operations it restates.
 //
 // The ragged-batch kernels are two templates over <Frame, Row> - the descriptor (B, G, R or YUV; plain, counted, with an augmentation
-// pair, letterboxed) and where the blended row goes (uint8 batch, fp32 training batch, fp32 / fp16 tensor) - in ten instantiations.
+// pair, letterboxed) and where the blended row goes (uint8 batch, fp32 training batch, fp32 / fp16 tensor) - in ten instantiations, and five more of the YUV template for 2-byte samples (P010, I010).
 // Each output kind is described ONCE: the Row states its ALIGN and its own LDS bytes, yfv2_slot places the staging slots for kernel and
 // host alike, FrameRows<Frame> gives the launch's LDS and the width limit of the frame kind, launch_rows<Frame, Row> is the one launch
-// body.  Other units reach the family through Yfv2RowKind, a YUV flag and yfv2_launch_rows / yfv2_rows_lds_bytes / yfv2_rows_max_width
+// body.  Other units reach the family through Yfv2RowKind, Yfv2FrameKind and yfv2_launch_rows / yfv2_rows_lds_bytes / yfv2_rows_max_width
 // (yfv2_internal.h); yfv2_debug_rows shows the last two to tests/test_rows_host.py, which sweeps them against tests/rows_model.py.
 #include <algorithm>
 #include <type_traits>
@@ -376,6 +376,43 @@ __device__ __forceinline__ void yfv2_yuv_to_bgr(int Y, int U, int V, const YuvCo
   p[2] = min(max((yy + __mul24(k.cvr, v)) >> 20, 0), 255);
 }
 
+// THE 10-BIT COLOUR FORMULA (YFV2_YUV_P010 / _I010; include/yfv2.h states it for callers, tests/yuv16_model.py in numpy): the same
+// expression on 10-bit codes, the 8-bit B, G, R rounded ONCE from 10-bit precision.  Every literal is rint(k * 2^20) of the real
+// coefficient per 10-bit code - limited range: luma 255 / (219 * 4), chroma 255 / (224 * 4) times 2(1-Kr), -2Kr(1-Kr)/Kg,
+// -2Kb(1-Kb)/Kg, 2(1-Kb); full range: 255 / 1023 in place of both - computed from those formulas, not OpenCV literals (cv2 has no
+// P010 conversion to agree with):
+//                         off  CY      CVR     CVG      CUG      CUB
+//   YFV2_BT601_LIMITED    64   305236  418389  -213115  -102698  528805
+//   YFV2_BT709_LIMITED    64   305236  469956  -139699  -55902   553753
+//   YFV2_BT601_FULL       0    261375  366448  -186658  -89949   463157
+//   YFV2_BT709_FULL       0    261375  411614  -122356  -48962   485008
+//   yy = max(Y - off, 0) * CY;  u = U - 512;  v = V - 512;  R, G, B as above
+// The accumulators stay within [-2.83e8, 5.77e8] over the 10-bit cube (tests/test_yuv16_host.py bounds them by the corners).
+static const YuvCoef YUV_COEF16[4] = {
+    {64, 305236, 418389, -213115, -102698, 528805},
+    {64, 305236, 469956, -139699, -55902, 553753},
+    {0, 261375, 366448, -186658, -89949, 463157},
+    {0, 261375, 411614, -122356, -48962, 485008},
+};
+
+// As above: |coefficient| < 2^20, |Y - off| <= 1023, |u|, |v| <= 512, every factor below 2^24 and every product int32.
+__device__ __forceinline__ void yfv2_yuv16_to_bgr(int Y, int U, int V, const YuvCoef& k, int (&p)[3]) {
+  const int yy = __mul24(max(Y - k.off, 0), k.cy) + (1 << 19), u = U - 512, v = V - 512;
+  p[0] = min(max((yy + __mul24(k.cub, u)) >> 20, 0), 255);
+  p[1] = min(max((yy + __mul24(k.cvg, v) + __mul24(k.cug, u)) >> 20, 0), 255);
+  p[2] = min(max((yy + __mul24(k.cvr, v)) >> 20, 0), 255);
+}
+
+// The sample width of a YUV descriptor type: 2 for Samples16<...> (yfv2_internal.h), 1 for every other.
+template <class Frame>
+constexpr int yfv2_sample_bytes() {
+  if constexpr (requires { Frame::SAMPLE_BYTES; }) return Frame::SAMPLE_BYTES;
+  else return 1;
+}
+// THE VALUE OF A WORD, the two rules of the 2-byte formats: P010 carries its 10 bits in the high bits (word >> 6; the low 6 are
+// ignored), I010 in the low bits (word & 1023; the high 6 are ignored).  shift = 6 / 0 is uniform over a workgroup.
+__device__ __forceinline__ int yfv2_sample10(const unsigned short* p, int i, int shift) { return ((int)p[i] >> shift) & 1023; }
+
 // One workgroup per (frame, output row), the scheme of resize_frames_u8_kernel.  Staged in LDS, as aligned dwords with the same
 // guard - a dword is loaded whole only when its four bytes lie in the frame's own extent OF THAT PLANE (first row's first needed byte
 // to last row's last needed byte), otherwise byte by byte from those that do: luma rows s0 and s1, w bytes each, and the chroma rows
@@ -394,6 +431,16 @@ __device__ __forceinline__ void yfv2_yuv_to_bgr(int Y, int U, int V, const YuvCo
 // workgroups in flight - measured 258 us at 8 waves per SIMD against 283 us at 6 on the probe's mix.
 // Like its neighbour a template over descriptor and epilogue: <ResizeFrameYuv, RowU8> is the resize, <TrainFrameYuv, RowTrain> the
 // training batch (43 VGPRs - the fp32 row goes to LDS where the uint8 row went).
+// TWO-BYTE SAMPLES (YFV2_YUV_P010 / _I010): the descriptor type Samples16<D> makes SB = 2, and the same body stages
+// twice the bytes - two luma slots of yfv2_slot(2 w), four chroma half-slots of yfv2_slot(2 * ((w >> 1) + 1)), then the Row's bytes.
+// The dword staging and its guard are unchanged (the planes are 2-byte aligned and the pitches even, so smis is 0 or 2); only the tap
+// reads (16-bit LDS reads: a sub-dword LDS read is one instruction whatever its width, so the blend issues what the byte kernel
+// issues plus the bit-field extracts) and yfv2_sample10 are new code.  For SB = 1 nothing below differs from what it was
+// (profiles/yuv16_isa.txt: the ten existing instantiations' streams, hashed, parent against child).  Same launch bound:
+// <Samples16<ResizeFrameYuv>, RowU8> needs 61 VGPRs (the counted twin 61, training 43, the tensors 46 / 44), so 8 waves per SIMD
+// still fit the registers, and no instantiation spills to scratch.  By LDS a 1920-wide frame takes 2 * 3844 + 4 * 1928 + 1056 =
+// 16456 bytes: 9 workgroups per CU (18 of its 32 waves) where the byte kernel reaches its 16 - at 1080p this kernel is LDS-bound, at
+// 1280 wide it has 14, from 640 wide down the 16 of the launch bound again.
 constexpr int RY_THREADS = 128;
 template <class Frame, class Row>
 __global__ __launch_bounds__(RY_THREADS, 8) void resize_frames_yuv_kernel(const Frame* __restrict__ frames, typename Row::Out* __restrict__ dst, int H, int W) {
@@ -410,19 +457,20 @@ __global__ __launch_bounds__(RY_THREADS, 8) void resize_frames_yuv_kernel(const 
     if (iy < 0 || iy >= f.ih) { row.fill_row(b, oy, H, W); return; }
   }
   const RowCoef ry = yfv2_axis_coef(iy, f.scale_y, f.h, false);
-  const bool planar = f.format == YFV2_YUV_I420;
+  constexpr int SB = yfv2_sample_bytes<Frame>();          // bytes of a sample: everything counted in bytes below carries it
+  const bool planar = f.format == (SB == 1 ? YFV2_YUV_I420 : YFV2_YUV_I010);
   const int cw = ((f.w - 1 + f.px) >> 1) + 1, ch = ((f.h - 1 + f.py) >> 1) + 1;   // chroma samples per row, chroma rows of the frame
-  const int cbytes = planar ? cw : 2 * cw;
+  const int cbytes = SB * (planar ? cw : 2 * cw);
   const int cr0 = (ry.s0 + f.py) >> 1, cr1 = (ry.s1 + f.py) >> 1;
   const bool one_chroma_row = cr0 == cr1;
-  const int yslot = yfv2_slot(f.w, Row::ALIGN), chalf = yfv2_slot((f.w >> 1) + 1, Row::ALIGN);
+  const int yslot = yfv2_slot(SB * f.w, Row::ALIGN), chalf = yfv2_slot(SB * ((f.w >> 1) + 1), Row::ALIGN);
   unsigned char* LY0 = smem;
   unsigned char* LY1 = smem + yslot;
   unsigned char* LC0 = smem + 2 * yslot;
   unsigned char* LC1 = LC0 + 2 * chalf;
   unsigned char* OUT = LC0 + 4 * chalf;
   if constexpr (Row::AUGMENT) row.begin(OUT, f.alpha, f.beta);
-  const long long extent_y = (long long)(f.h - 1) * f.pitch_y + f.w;
+  const long long extent_y = (long long)(f.h - 1) * f.pitch_y + SB * f.w;
   const long long extent_c = (long long)(ch - 1) * f.pitch_c + cbytes;
   // Six row segments: luma s0, s1; chroma plane a rows cr0, cr1; chroma plane b (I420's V) rows cr0, cr1.  A segment that is not
   // staged (the second chroma row when it is the first, plane b of an interleaved format) has no dwords.  Everything about a segment
@@ -436,7 +484,7 @@ __global__ __launch_bounds__(RY_THREADS, 8) void resize_frames_yuv_kernel(const 
 #pragma unroll
   for (int k = 0; k < 6; ++k) {
     const long long g = k < 2 ? (long long)(k == 0 ? ry.s0 : ry.s1) * f.pitch_y : (long long)((k & 1) ? cr1 : cr0) * f.pitch_c;
-    const int n = k < 2 ? f.w : (((k & 1) && one_chroma_row) || (k >= 4 && !planar) ? 0 : cbytes);
+    const int n = k < 2 ? SB * f.w : (((k & 1) && one_chroma_row) || (k >= 4 && !planar) ? 0 : cbytes);
     smis[k] = (int)((reinterpret_cast<uintptr_t>(sbase[k]) + g) & 3);
     const long long first = g - smis[k];                  // offset of the segment's dword 0 from its plane's base
     sptr[k] = sbase[k] + first;
@@ -480,18 +528,27 @@ __global__ __launch_bounds__(RY_THREADS, 8) void resize_frames_yuv_kernel(const 
   __syncthreads();
   // U and V of chroma sample j of blended row 0 / 1: pu[j * cstep], pv[j * cstep]
   const int cstep = planar ? 1 : 2;
-  const unsigned char* a0 = LC0 + smis[2];
-  const unsigned char* a1 = one_chroma_row ? a0 : LC1 + smis[3];
-  const unsigned char* b0 = planar ? LC0 + chalf + smis[4] : a0 + 1;
-  const unsigned char* b1 = planar ? (one_chroma_row ? b0 : LC1 + chalf + smis[5]) : a1 + 1;
-  const bool swapped = f.format == YFV2_YUV_NV21;
-  const unsigned char* pu0 = swapped ? b0 : a0;
-  const unsigned char* pv0 = swapped ? a0 : b0;
-  const unsigned char* pu1 = swapped ? b1 : a1;
-  const unsigned char* pv1 = swapped ? a1 : b1;
-  const unsigned char* y0 = LY0 + smis[0];
-  const unsigned char* y1 = LY1 + smis[1];
   const YuvCoef kc = f.coef;
+  // Taps: sample s of a staged row is its byte s (1-byte samples) or its 16-bit word s, of which yfv2_sample10 takes the value - a
+  // slot is 4-byte aligned and a 2-byte plane's misalignment is 0 or 2, so every word is aligned.  Everything else is one body.
+  using Sample = std::conditional_t<SB == 1, unsigned char, unsigned short>;
+  const int vshift = planar ? 0 : 6;                       // (2-byte samples only)
+  auto at = [&](const unsigned char* lds, int mis) { return reinterpret_cast<const Sample*>(lds + mis); };
+  const Sample* a0 = at(LC0, smis[2]);
+  const Sample* a1 = one_chroma_row ? a0 : at(LC1, smis[3]);
+  const Sample* b0 = planar ? at(LC0 + chalf, smis[4]) : a0 + 1;
+  const Sample* b1 = planar ? (one_chroma_row ? b0 : at(LC1 + chalf, smis[5])) : a1 + 1;
+  const bool swapped = SB == 1 && f.format == YFV2_YUV_NV21;
+  const Sample* pu0 = swapped ? b0 : a0;
+  const Sample* pv0 = swapped ? a0 : b0;
+  const Sample* pu1 = swapped ? b1 : a1;
+  const Sample* pv1 = swapped ? a1 : b1;
+  const Sample* y0 = at(LY0, smis[0]);
+  const Sample* y1 = at(LY1, smis[1]);
+  auto tap = [&](const Sample* y, const Sample* pu, const Sample* pv, int s, int j, int (&p)[3]) {
+    if constexpr (SB == 1) yfv2_yuv_to_bgr(y[s], pu[j], pv[j], kc, p);
+    else yfv2_yuv16_to_bgr(yfv2_sample10(y, s, vshift), yfv2_sample10(pu, j, vshift), yfv2_sample10(pv, j, vshift), kc, p);
+  };
   for (int ox = tid; ox < W; ox += RY_THREADS) {
     int ix = ox;
     if constexpr (requires { Row::TENSOR; }) {
@@ -501,17 +558,17 @@ __global__ __launch_bounds__(RY_THREADS, 8) void resize_frames_yuv_kernel(const 
     const RowCoef rx = yfv2_axis_coef(ix, f.scale_x, f.w, true);
     const int j0 = ((rx.s0 + f.px) >> 1) * cstep, j1 = ((rx.s1 + f.px) >> 1) * cstep;
     int p00[3], p01[3], p10[3], p11[3];      // B, G, R of the taps (row s0 / s1, column sx0 / sx1)
-    yfv2_yuv_to_bgr(y0[rx.s0], pu0[j0], pv0[j0], kc, p00);
-    yfv2_yuv_to_bgr(y0[rx.s1], pu0[j1], pv0[j1], kc, p01);
-    yfv2_yuv_to_bgr(y1[rx.s0], pu1[j0], pv1[j0], kc, p10);
-    yfv2_yuv_to_bgr(y1[rx.s1], pu1[j1], pv1[j1], kc, p11);
+    tap(y0, pu0, pv0, rx.s0, j0, p00);
+    tap(y0, pu0, pv0, rx.s1, j1, p01);
+    tap(y1, pu1, pv1, rx.s0, j0, p10);
+    tap(y1, pu1, pv1, rx.s1, j1, p11);
 #pragma unroll
     for (int c = 0; c < 3; ++c) row.put(OUT, ox, c, W, yfv2_blend(p00[c], p01[c], p10[c], p11[c], rx, ry));
   }
   row.end(OUT, b, oy, H, W);
 }
 
-YuvCoef yfv2_yuv_coef(int colour) { return YUV_COEF[colour]; }
+YuvCoef yfv2_yuv_coef(int colour, int sample_bytes) { return sample_bytes == 2 ? YUV_COEF16[colour] : YUV_COEF[colour]; }
 
 // ---- the host side of the row kernels: ONE description per frame kind, used by every launch and every limit -----------------
 // FrameRows<Frame> is what the descriptor's frame kind (B, G, R: ResizeFrame and what derives from it; YUV: ResizeFrameYuv likewise)
@@ -527,16 +584,17 @@ struct FrameRows {       // B, G, R: two source rows of 3 w bytes
   template <class Row> static int max_width(int W) { return (YFV2_LDS_FULL - Row::lds_bytes(W)) / 6 - (Row::ALIGN + 2) / 3; }
 };
 template <class Frame>
-struct FrameRows<Frame, true> {   // YUV: two luma slots, two chroma rows of two half-slots each
+struct FrameRows<Frame, true> {   // YUV: two luma slots, two chroma rows of two half-slots each, of SB-byte samples
   static constexpr int THREADS = RY_THREADS;
+  static constexpr int SB = yfv2_sample_bytes<Frame>();
   template <class Row> static constexpr auto& kernel = resize_frames_yuv_kernel<Frame, Row>;
   template <class Row> static size_t lds_bytes(int w, int W) {
-    return 2 * (size_t)yfv2_slot(w, Row::ALIGN) + 4 * (size_t)yfv2_slot((w >> 1) + 1, Row::ALIGN) + (size_t)Row::lds_bytes(W);
+    return 2 * (size_t)yfv2_slot(SB * w, Row::ALIGN) + 4 * (size_t)yfv2_slot(SB * ((w >> 1) + 1), Row::ALIGN) + (size_t)Row::lds_bytes(W);
   }
-  // The exact maximum: the function above grows by about 4 bytes per pixel and never falls, so the answer is next to
-  // (YFV2_LDS_FULL - the Row's bytes) / 4 and two short walks find it.
+  // The exact maximum: the function above grows by about 4 SB bytes per pixel and never falls, so the answer is next to
+  // (YFV2_LDS_FULL - the Row's bytes) / (4 SB) and two short walks find it.
   template <class Row> static int max_width(int W) {
-    int w = (int)std::max<long long>(1, ((long long)YFV2_LDS_FULL - Row::lds_bytes(W)) / 4);
+    int w = (int)std::max<long long>(1, ((long long)YFV2_LDS_FULL - Row::lds_bytes(W)) / (4 * SB));
     while (w > 1 && lds_bytes<Row>(w, W) > (size_t)YFV2_LDS_FULL) --w;
     while (lds_bytes<Row>(w + 1, W) <= (size_t)YFV2_LDS_FULL) ++w;
     return w;
@@ -552,38 +610,43 @@ static void launch_rows(const void* table, int n, int max_w, void* dst, int H, i
                   static_cast<const Frame*>(table), static_cast<typename Row::Out*>(dst), H, W);
 }
 
-// What the other units see of the family: a row kind, a YUV flag, three functions.  THE TABLE of the ten instantiations: f is called
-// as f.operator()<Frame, Row>().  (The device compiler emits the kernels in the order they are named here - training first, the
-// tensors by frame kind - which is the order the unit's assembly is compared in, byte for byte: profiles/rows_refactor_isa.txt.)
+// What the other units see of the family: a row kind, a frame kind, three functions.  THE TABLE of the fifteen instantiations: f is
+// called as f.operator()<Frame, Row>().  (The device compiler emits the kernels in the order they are named here - training first,
+// the tensors by frame kind, within a row kind B, G, R, then 1-byte, then 2-byte YUV.)
 template <class Fn>
-static auto with_rows(Yfv2RowKind kind, bool yuv, Fn f) {
+static auto with_rows(Yfv2RowKind kind, Yfv2FrameKind frames, Fn f) {
   using U8 = RowU8<RF_THREADS>;                 using U8Y = RowU8<RY_THREADS>;
   using Train = RowTrain<RF_THREADS>;           using TrainY = RowTrain<RY_THREADS>;
   using F32 = RowTensor<RF_THREADS, false>;     using F32Y = RowTensor<RY_THREADS, false>;
   using F16 = RowTensor<RF_THREADS, true>;      using F16Y = RowTensor<RY_THREADS, true>;
   const bool half = kind == YFV2_ROWS_TENSOR_F16;
+  // one row kind: its B, G, R descriptor and Row, its YUV descriptor (1-byte samples; Samples16<...> of it for 2-byte) and Row
+  auto pick = [&]<class Bgr, class RowBgr, class Yuv, class RowYuv>() {
+    if (frames == YFV2_FRAMES_BGR) return f.template operator()<Bgr, RowBgr>();
+    if (frames == YFV2_FRAMES_YUV8) return f.template operator()<Yuv, RowYuv>();
+    return f.template operator()<Samples16<Yuv>, RowYuv>();
+  };
   switch (kind) {
-    case YFV2_ROWS_TRAIN:      return !yuv ? f.template operator()<TrainFrame, Train>() : f.template operator()<TrainFrameYuv, TrainY>();
-    case YFV2_ROWS_U8:         return !yuv ? f.template operator()<ResizeFrame, U8>() : f.template operator()<ResizeFrameYuv, U8Y>();
-    case YFV2_ROWS_COUNTED_U8: return !yuv ? f.template operator()<CropFrame, U8>() : f.template operator()<CropFrameYuv, U8Y>();
+    case YFV2_ROWS_TRAIN:      return pick.template operator()<TrainFrame, Train, TrainFrameYuv, TrainY>();
+    case YFV2_ROWS_U8:         return pick.template operator()<ResizeFrame, U8, ResizeFrameYuv, U8Y>();
+    case YFV2_ROWS_COUNTED_U8: return pick.template operator()<CropFrame, U8, CropFrameYuv, U8Y>();
     default:                   // YFV2_ROWS_TENSOR_F32, YFV2_ROWS_TENSOR_F16
-      if (!yuv) return half ? f.template operator()<TensorFrame, F16>() : f.template operator()<TensorFrame, F32>();
-      return half ? f.template operator()<TensorFrameYuv, F16Y>() : f.template operator()<TensorFrameYuv, F32Y>();
+      return half ? pick.template operator()<TensorFrame, F16, TensorFrameYuv, F16Y>() : pick.template operator()<TensorFrame, F32, TensorFrameYuv, F32Y>();
   }
 }
 
-size_t yfv2_rows_lds_bytes(Yfv2RowKind kind, bool yuv, int w, int W) {
-  return with_rows(kind, yuv, [&]<class Frame, class Row>() { return FrameRows<Frame>::template lds_bytes<Row>(w, W); });
+size_t yfv2_rows_lds_bytes(Yfv2RowKind kind, Yfv2FrameKind frames, int w, int W) {
+  return with_rows(kind, frames, [&]<class Frame, class Row>() { return FrameRows<Frame>::template lds_bytes<Row>(w, W); });
 }
 
-int yfv2_rows_max_width(Yfv2RowKind kind, bool yuv, int W) {
-  return with_rows(kind, yuv, [&]<class Frame, class Row>() { return FrameRows<Frame>::template max_width<Row>(W); });
+int yfv2_rows_max_width(Yfv2RowKind kind, Yfv2FrameKind frames, int W) {
+  return with_rows(kind, frames, [&]<class Frame, class Row>() { return FrameRows<Frame>::template max_width<Row>(W); });
 }
 
-void yfv2_launch_rows(Yfv2RowKind kind, bool yuv, const void* table, int n, int max_w, void* dst, int H, int W, hipStream_t s) {
-  with_rows(kind, yuv, [&]<class Frame, class Row>() { launch_rows<Frame, Row>(table, n, max_w, dst, H, W, s); });
+void yfv2_launch_rows(Yfv2RowKind kind, Yfv2FrameKind frames, const void* table, int n, int max_w, void* dst, int H, int W, hipStream_t s) {
+  with_rows(kind, frames, [&]<class Frame, class Row>() { launch_rows<Frame, Row>(table, n, max_w, dst, H, W, s); });
 }
 
 void yfv2_launch_resize(const ResizeArgs& a, hipStream_t s) {
-  YFV2_LAUNCH_LDS(yfv2_device(), resize_u8_kernel, YFV2_LDS_FULL, dim3((unsigned)(a.B * a.H)), dim3(256), yfv2_rows_lds_bytes(YFV2_ROWS_U8, false, a.SW, a.W), s, a);
+  YFV2_LAUNCH_LDS(yfv2_device(), resize_u8_kernel, YFV2_LDS_FULL, dim3((unsigned)(a.B * a.H)), dim3(256), yfv2_rows_lds_bytes(YFV2_ROWS_U8, YFV2_FRAMES_BGR, a.SW, a.W), s, a);
 }

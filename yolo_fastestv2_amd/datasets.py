@@ -55,16 +55,22 @@ def collate_targets(labels):
     return torch.cat(out, 0) if out else torch.zeros((0, 6), dtype=torch.float32)
 
 
-def train_batch_lds_bytes(w, W, is_yuv=False):
+def _train_rows(w, W, is_yuv, bits):
+    if bits not in (8, 10) or (bits == 10 and not is_yuv):
+        raise ValueError("bits must be 8, or 10 for YUV frames (\"p010\", \"i010\"), got %r" % (bits,))
+    return yuv.rows_lds(yuv.ROWS_TRAIN, is_yuv, w, W) if bits == 8 else yuv.rows_lds16(yuv.ROWS_TRAIN, w, W)
+
+
+def train_batch_lds_bytes(w, W, is_yuv=False, bits=8):
     """LDS of one workgroup of the training-batch launch for a frame w pixels wide at network width W: the resize's staging slots
     rounded to 16 bytes, the table, three fp32 planes of W"""
-    return yuv.rows_lds(yuv.ROWS_TRAIN, is_yuv, w, W)[0]
+    return _train_rows(w, W, is_yuv, bits)[0]
 
 
-def max_frame_width(W, is_yuv=False):
-    """the widest frame Engine.train_batch_frames (is_yuv: train_batch_frames_yuv) admits at network width W; never above
-    resize_frames' own limit"""
-    return yuv.rows_lds(yuv.ROWS_TRAIN, is_yuv, 1, W)[1]
+def max_frame_width(W, is_yuv=False, bits=8):
+    """the widest frame Engine.train_batch_frames (is_yuv: train_batch_frames_yuv; bits = 10: "p010" / "i010" frames) admits at
+    network width W; never above resize_frames' own limit"""
+    return _train_rows(1, W, is_yuv, bits)[1]
 
 
 class TrainBatcher:

@@ -7,6 +7,13 @@
 ``planes`` are uint8 device tensors: ``(y, uv)`` for NV12 / NV21 - uv either (rows, bytes) or (rows, samples, 2) - and
 ``(y, u, v)`` for I420 (YV12: pass ``(y, v, u)``).  A plane's row pitch is its ``stride(0)``; its bytes within a row must be
 contiguous.  Nothing here needs a device; the table goes to libyfv2.so as it is.
+
+The 10-bit formats have little-endian 16-bit samples: "p010" (semi-planar, the value in the high 10 bits: what
+the hardware decoders write for HEVC Main10, AV1 and VP9 profile 2) and "i010" = "yuv420p10le" (planar, the value in the low 10
+bits: what software decoders write).  Their planes are ``torch.int16`` tensors (``torch.uint16`` where this torch has it) of
+shape (rows, samples) - uv also (rows, samples, 2) - with pitch ``2 * stride(0)``, or ``torch.uint8`` tensors holding the bytes,
+with pitch ``stride(0)``.  A frame of byte tensors must state its ``width`` and ``height``: a byte plane is also a valid 8-bit
+plane, so the rectangle is not guessed from it.  All frames of one call have one sample width.
 """
 import ctypes as C
 
@@ -14,7 +21,17 @@ import torch
 
 from . import _lib
 
-FORMATS = {"nv12": 0, "nv21": 1, "i420": 2, 0: 0, 1: 1, 2: 2}
+FORMATS = {"nv12": 0, "nv21": 1, "i420": 2, 0: 0, 1: 1, 2: 2,
+           "p010": 16, "i010": 17, "yuv420p10le": 17, "yuv420p10": 17, 16: 16, 17: 17}      # bit 4: two-byte samples
+PLANAR = (2, 17)
+WORD_DTYPES = tuple(getattr(torch, n) for n in ("int16", "uint16") if hasattr(torch, n))
+
+
+def sample_bytes(format):
+    """bytes of one sample of the (integer) format"""
+    return 2 if format & 16 else 1
+
+
 COLOURS = {"bt601": 0, "bt601_limited": 0, "bt709": 1, "bt709_limited": 1, "bt601_full": 2, "jpeg": 2, "bt709_full": 3, 0: 0, 1: 1, 2: 2, 3: 3}
 LDS_FULL = 160 * 1024
 ROWS_U8, ROWS_COUNTED_U8, ROWS_TRAIN, ROWS_TENSOR_F32, ROWS_TENSOR_F16 = range(5)      # yfv2_debug_rows' row_kind
@@ -35,26 +52,39 @@ def resize_lds_bytes(w, W):
     return rows_lds(ROWS_U8, True, w, W)[0]
 
 
-def max_width(W):
-    """the widest YUV frame the resize admits at network width W"""
-    return rows_lds(ROWS_U8, True, 1, W)[1]
+def rows_lds16(kind, w, W):
+    """``rows_lds`` for YUV frames of two-byte samples ("p010", "i010"; include/yfv2.h yfv2_debug_rows16)"""
+    lds, limit = C.c_int64(), C.c_int32()
+    if _lib.lib().yfv2_debug_rows16(kind, w, W, C.byref(lds), C.byref(limit)) != _lib.OK:
+        raise ValueError("rows_lds16(%r, %r, %r): %s" % (kind, w, W, _lib.last_error()))
+    return lds.value, limit.value
+
+
+def max_width(W, bits=8):
+    """the widest YUV frame the resize admits at network width W: bits = 8 for NV12 / NV21 / I420, 10 for P010 / I010"""
+    if bits not in (8, 10):
+        raise ValueError("bits must be 8 or 10, got %r" % (bits,))
+    return rows_lds(ROWS_U8, True, 1, W)[1] if bits == 8 else rows_lds16(ROWS_U8, 1, W)[1]
 
 
 class YuvFrame:
-    """One YUV 4:2:0 frame: planes + format ("nv12", "nv21", "i420") + colour ("bt601", "bt709" - limited range - "bt601_full" alias
+    """One YUV 4:2:0 frame: planes + format ("nv12", "nv21", "i420"; "p010", "i010" alias "yuv420p10le") + colour ("bt601", "bt709" - limited range - "bt601_full" alias
     "jpeg", "bt709_full") and the rectangle of the planes that is the frame (default: all of the luma plane from (x0, y0) on)."""
-    __slots__ = ("planes", "format", "colour", "x0", "y0", "width", "height")
+    __slots__ = ("planes", "format", "colour", "x0", "y0", "width", "height", "planar", "sample_bytes")
 
     def __init__(self, planes, format="nv12", colour="bt601", x0=0, y0=0, width=None, height=None):
         self.planes = tuple(planes)
         if format not in FORMATS or isinstance(format, bool):
-            raise ValueError("format must be one of 'nv12', 'nv21', 'i420', got %r" % (format,))
+            raise ValueError("format must be one of 'nv12', 'nv21', 'i420', 'p010', 'i010' ('yuv420p10le'), got %r" % (format,))
         if colour not in COLOURS or isinstance(colour, bool):
             raise ValueError("colour must be one of 'bt601', 'bt709', 'bt601_full' ('jpeg'), 'bt709_full', got %r" % (colour,))
         self.format, self.colour = FORMATS[format], COLOURS[colour]
+        self.planar, self.sample_bytes = self.format in PLANAR, sample_bytes(self.format)
         self.x0, self.y0 = int(x0), int(y0)
         if not self.planes or not torch.is_tensor(self.planes[0]) or self.planes[0].dim() != 2:
             raise ValueError("planes[0] must be the 2-D luma plane")
+        if self.sample_bytes == 2 and self.planes[0].dtype == torch.uint8 and (width is None or height is None):
+            raise ValueError("a %r frame of uint8 (byte) planes must state its width and height" % (format,))
         self.width = int(self.planes[0].shape[1]) - self.x0 if width is None else int(width)
         self.height = int(self.planes[0].shape[0]) - self.y0 if height is None else int(height)
 
@@ -91,6 +121,24 @@ def _plane(i, name, p, device, rows, row_bytes):
     return int(p.stride(0)) if p.shape[0] > 1 else max(have, 1)
 
 
+def _plane16(i, name, p, device, rows, row_samples):
+    """`_plane` for two-byte samples: `rows` rows of `row_samples` samples, of a 16-bit tensor (pitch = 2 * stride(0)) or of a uint8
+    tensor of the bytes (pitch = stride(0)) -> pitch in bytes"""
+    if torch.is_tensor(p) and p.dtype == torch.uint8:
+        return _plane(i, name, p, device, rows, 2 * row_samples)
+    if not torch.is_tensor(p) or p.dtype not in WORD_DTYPES or p.device != device:
+        raise ValueError("frame %d: plane %s must be an int16 / uint16 tensor (or uint8: the bytes) on %s" % (i, name, device))
+    if p.dim() == 3 and p.shape[2] == 2 and name == "uv" and (p.shape[1] <= 1 or p.stride(1) == 2) and p.stride(2) == 1:
+        have = 2 * int(p.shape[1])
+    elif p.dim() == 2 and (p.shape[1] <= 1 or p.stride(1) == 1):
+        have = int(p.shape[1])
+    else:
+        raise ValueError("frame %d: plane %s must be 2-D with contiguous rows (uv may be (rows, samples, 2))" % (i, name))
+    if p.shape[0] < rows or have < row_samples:
+        raise ValueError("frame %d: plane %s is %d rows x %d samples, the frame reads %d x %d of it" % (i, name, p.shape[0], have, rows, row_samples))
+    return 2 * (int(p.stride(0)) if p.shape[0] > 1 else max(have, 1))
+
+
 def frame_table(frames, device):
     """list / tuple of YuvFrame (or plane tuples) -> (yfv2_frame_yuv array, the frames).  Every plane must hold what its frame's
     rectangle reads: the native library sees pointers and pitches only and cannot check that."""
@@ -98,23 +146,27 @@ def frame_table(frames, device):
         raise ValueError("frames must be a non-empty list or tuple of YuvFrame")
     frames = [as_frame(f) for f in frames]
     arr = (_lib.FrameYuv * len(frames))()
+    sb = frames[0].sample_bytes
+    plane = _plane if sb == 1 else _plane16          # (takes a row's length in samples)
     for i, f in enumerate(frames):
-        planar = f.format == FORMATS["i420"]
+        planar = f.planar
+        if f.sample_bytes != sb:
+            raise ValueError("frame %d: %d-byte samples in a call whose frame 0 has %d-byte samples: one sample width per call" % (i, f.sample_bytes, sb))
         if len(f.planes) != (3 if planar else 2):
-            raise ValueError("frame %d: %s takes %d planes, got %d" % (i, "i420" if planar else "nv12 / nv21", 3 if planar else 2, len(f.planes)))
+            raise ValueError("frame %d: %s takes %d planes, got %d" % (i, "i420 / i010" if planar else "nv12 / nv21 / p010", 3 if planar else 2, len(f.planes)))
         if f.x0 < 0 or f.y0 < 0:
             raise ValueError("frame %d: x0 and y0 must be >= 0" % i)
         a = arr[i]
         a.x0, a.y0, a.width, a.height, a.format, a.colour = f.x0, f.y0, f.width, f.height, f.format, f.colour
         if f.width >= 1 and f.height >= 1:      # (a frame without pixels is the native check's to report)
             crows, csamples = ((f.y0 + f.height - 1) >> 1) + 1, ((f.x0 + f.width - 1) >> 1) + 1
-            a.pitch_y = _plane(i, "y", f.planes[0], device, f.y0 + f.height, f.x0 + f.width)
+            a.pitch_y = plane(i, "y", f.planes[0], device, f.y0 + f.height, f.x0 + f.width)
             if planar:
-                a.pitch_c = _plane(i, "u", f.planes[1], device, crows, csamples)
-                if _plane(i, "v", f.planes[2], device, crows, csamples) != a.pitch_c:
+                a.pitch_c = plane(i, "u", f.planes[1], device, crows, csamples)
+                if plane(i, "v", f.planes[2], device, crows, csamples) != a.pitch_c:
                     raise ValueError("frame %d: planes u and v must have the same row pitch" % i)
                 a.v = f.planes[2].data_ptr()
             else:
-                a.pitch_c = _plane(i, "uv", f.planes[1], device, crows, 2 * csamples)
+                a.pitch_c = plane(i, "uv", f.planes[1], device, crows, 2 * csamples)
         a.y, a.u = f.planes[0].data_ptr(), f.planes[1].data_ptr()
     return arr, frames
