@@ -24,6 +24,8 @@ Outputs (all small, committed):
                        its own float64 evaluation - the noise floor a device path is held to (python make_golden.py floor)
   golden_loss.npz      seeded logits + targets -> reference utils/loss.py compute_loss values and its autograd
                        gradients w.r.t. the six logit maps (python make_golden.py loss)
+  golden_loss_shapes.npz  the same at other input sizes, batches, class counts and logit ranges: the case table of
+                       tests/loss_cases.py (python make_golden.py loss_shapes)
   golden_post_adversarial.npz  crafted decoded tensors (tests/adversarial_post.py, rebuilt from seeds) -> reference
                        non_max_suppression rows + survivor indices over a grid of thresholds (python make_golden.py adversarial)
 
@@ -333,6 +335,60 @@ def make_loss_golden():
     finally:
         torch.Tensor.clamp_ = orig
     np.savez_compressed(os.path.join(HERE, "golden_loss.npz"), **out)
+
+
+def make_loss_shapes_golden():
+    """golden_loss_shapes.npz: make_loss_golden's procedure (the reference's own compute_loss, the same clamp_ shim, its autograd
+    gradients, bit equality with the oracle asserted before anything is written) over the table of tests/loss_cases.py: other
+    input sizes (cfg width / height and per-axis scaled anchors), batches, class counts, label counts and saturated logits.  The
+    reference gets the rows that meet yfv2_loss's precondition (a bad_rows case: its valid rows only)."""
+    import importlib.util
+    sys.path.insert(0, os.path.dirname(HERE))
+    import loss_cases as LC
+    torch.set_num_threads(1)
+    spec = importlib.util.spec_from_file_location("ref_loss", os.path.join(REF, "utils", "loss.py"))
+    L = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(L)
+    orig = torch.Tensor.clamp_
+
+    def clamp_(self, mn=None, mx=None):
+        fix = lambda v: int(v) if (torch.is_tensor(v) and not self.is_floating_point()) else v  # noqa: E731
+        return orig(self, fix(mn), fix(mx))
+    torch.Tensor.clamp_ = clamp_
+    out = {"n": np.asarray(len(LC.CASES)), "cases": np.asarray([c[:6] for c in LC.CASES], np.int64), "flavours": np.asarray([c.flavour for c in LC.CASES])}
+    try:
+        for ci, c in enumerate(LC.CASES):
+            preds, t_all, valid = LC.case_inputs(c)
+            t = np.ascontiguousarray(t_all[valid])
+            anchors = LC.anchors_for(c.H, c.W)
+            cfg = {"anchor_num": 3, "classes": c.classes, "width": c.W, "height": c.H, "anchors": anchors}
+            p1 = [torch.from_numpy(p.copy()).requires_grad_() for p in preds]
+            p2 = [torch.from_numpy(p.copy()).requires_grad_() for p in preds]
+            ref = L.compute_loss(p1, torch.from_numpy(t), cfg, torch.device("cpu"))
+            ref[3].backward()
+            mine = oracle.compute_loss(p2, torch.from_numpy(t), anchors, c.classes, 3, c.W, c.H)
+            mine[3].backward()
+            for a, b in zip(ref, mine):
+                assert float(a) == float(b), "oracle compute_loss != reference compute_loss"
+            for a, b in zip(p1, p2):
+                ga = a.grad if a.grad is not None else torch.zeros_like(a)
+                gb = b.grad if b.grad is not None else torch.zeros_like(b)
+                assert torch.equal(ga, gb), "oracle gradients != reference autograd gradients"
+            out["targets%d" % ci] = t_all
+            out["loss%d" % ci] = np.asarray([float(v) for v in ref], np.float32)
+            for k, p in enumerate(p1):
+                g = (p.grad if p.grad is not None else torch.zeros_like(p)).numpy().reshape(-1)
+                if k % 3 == 1:
+                    out["grad%d_%d" % (ci, k)] = g
+                else:
+                    nz = np.flatnonzero(g)
+                    out["grad%d_%d_idx" % (ci, k)], out["grad%d_%d_val" % (ci, k)] = nz.astype(np.int64), g[nz]
+            print("loss shapes case", ci, LC.case_id(c), [float(v) for v in ref])
+    finally:
+        torch.Tensor.clamp_ = orig
+    path = os.path.join(HERE, "golden_loss_shapes.npz")
+    np.savez_compressed(path, **out)
+    print("golden_loss_shapes.npz", os.path.getsize(path), "bytes")
 
 
 TRAIN_CASES = ((80, 3, 9, 21, 0.001), (20, 2, 4, 22, 0.0004))   # classes, batch, labels, seed, lr
@@ -678,6 +734,8 @@ if __name__ == "__main__":
         make_curve_golden()   # only golden_curve.npz
     elif len(sys.argv) > 1 and sys.argv[1] == "loss":
         make_loss_golden()    # only golden_loss.npz
+    elif len(sys.argv) > 1 and sys.argv[1] == "loss_shapes":
+        make_loss_shapes_golden()   # only golden_loss_shapes.npz
     elif len(sys.argv) > 1 and sys.argv[1] == "floor":
         make_floor_golden()   # only golden_floor.npz
     elif len(sys.argv) > 1 and sys.argv[1] == "adversarial":

@@ -397,3 +397,138 @@ def test_single_tensor_sgd_step_is_torch_sgd():
         ref.grad = g.clone()
         opt.step()
     assert torch.allclose(p.cpu(), ref.detach(), rtol=2e-6, atol=1e-7), float((p.cpu() - ref.detach()).abs().max())
+
+
+def _sgd_pair(make_params, groups):
+    """device parameters under yfv2.SGD and CPU clones under torch.optim.SGD, in the same parameter groups"""
+    import yolo_fastestv2_amd as yfv2
+    dev = torch.device("cuda:0")
+    host = make_params()
+    mine = [[torch.nn.Parameter(_same_layout_on(p.detach(), dev), requires_grad=p.requires_grad) for p in g] for g in host]
+    ref = [[torch.nn.Parameter(p.detach().clone(memory_format=torch.preserve_format), requires_grad=p.requires_grad) for p in g] for g in host]
+    opt = yfv2.SGD([dict(params=g, **kw) for g, kw in zip(mine, groups)], lr=groups[0]["lr"])
+    ropt = torch.optim.SGD([dict(params=g, **kw) for g, kw in zip(ref, groups)], lr=groups[0]["lr"])
+    return mine, ref, opt, ropt
+
+
+def _same_layout_on(t, dev):
+    out = torch.empty_strided(t.shape, t.stride(), dtype=t.dtype, device=dev)
+    out.copy_(t)
+    assert out.stride() == t.stride()
+    return out
+
+
+def _close(a, b):
+    return torch.allclose(a.detach().cpu(), b.detach(), rtol=2e-6, atol=1e-7)   # test_single_tensor_sgd_step_is_torch_sgd's: FMA contraction
+
+
+def test_sgd_over_many_unequal_tensors_two_groups_three_steps_is_torch_sgd():
+    """yfv2.SGD (yfv2_sgd_step_multi through utils/optim.py) against torch.optim.SGD on free-standing tensors over three steps:
+    213 parameters of 1 .. 70 000 elements (one of them 0-d), none a multiple of the 256-thread block - the first group's 200 fill
+    three launches of the 96-item table with very unequal n; two groups with their own lr / momentum / weight decay; lr rewritten between steps
+    (train.py's warm-up); a frozen parameter; a parameter whose gradient appears in step 2 only (first_step flags mixed within one
+    table); a gradient that is a non-contiguous view.  Parameters and momentum buffers are compared after every step, and every
+    stepped parameter's autograd version moves by exactly one per step, as under an in-place torch op (a 70 000-element vector
+    once had it moved 70 000 times, through as many Python-level views, and a 0-d parameter raised).  Values are
+    kept below 2 in magnitude almost everywhere so that the absolute term of the tolerance covers a contracted product's rounding."""
+    rng = np.random.Generator(np.random.PCG64(77))
+    sizes = np.exp(rng.uniform(0, np.log(70000), 230)).astype(np.int64)       # log-uniform: a few large tensors among many small ones
+    sizes = np.concatenate(([1, 2, 255, 257, 70000], sizes[sizes % 256 != 0][:207]))
+    sizes = rng.permutation(sizes)
+    assert len(sizes) == 212 and sizes.min() == 1 and sizes.max() == 70000 and not (sizes % 256 == 0).any()
+    gen = torch.Generator().manual_seed(78)
+    groups = (dict(lr=0.01, momentum=0.949, weight_decay=5e-4), dict(lr=0.1, momentum=0.0, weight_decay=0.0))
+
+    def make():
+        ps = [torch.randn(int(n), generator=gen) * 0.5 for n in sizes]
+        ps[7] = ps[7][:int(sizes[7]) // 6 * 6].reshape(-1, 6) if sizes[7] >= 6 else torch.randn(5, 6, generator=gen) * 0.5   # 2-d: takes the strided gradient
+        ps[3].requires_grad_(False)
+        ps.append(torch.randn((), generator=gen) * 0.5)
+        return [ps[:200], ps[200:]]
+
+    mine, ref, opt, ropt = _sgd_pair(make, groups)
+    frozen, late, strided = (0, 3), (0, 11), (0, 7)
+    assert len(mine[0]) == 200 and len(mine[1]) == 13 and mine[1][12].dim() == 0
+    dev = mine[0][0].device
+    lrs = ((0.01, 0.1), (0.004, 0.07), (0.02, 0.1))
+    flat = [(gi, pi) for gi in range(2) for pi in range(len(mine[gi]))]
+    offs = np.concatenate(([0], np.cumsum([ref[gi][pi].numel() for gi, pi in flat])))
+
+    def compare(what, step, got, want):
+        """one transfer per step and kind: the device tensors concatenated against the CPU ones, then the first offender named"""
+        g, w = torch.cat([t.detach().flatten() for t in got]).cpu(), torch.cat([t.detach().flatten() for t in want])
+        bad = torch.nonzero((g - w).abs() > 1e-7 + 2e-6 * w.abs()).flatten()      # torch.allclose's rule
+        if len(bad) or not torch.isfinite(g).all():
+            at = int(bad[0]) if len(bad) else -1
+            raise AssertionError("%s, step %d: %d elements off, first at flat index %d: %r against %r" % (what, step, len(bad), at, float(g[at]), float(w[at])))
+
+    for step, lr in enumerate(lrs):
+        # one flat gradient per step, sent once; each parameter's gradient is a view of it (as the Detector's bucket is)
+        G = torch.randn(int(offs[-1]), generator=gen) * 0.3
+        Gd = G.to(dev)
+        for k, (gi, pi) in enumerate(flat):
+            p, r = mine[gi][pi], ref[gi][pi]
+            opt.param_groups[gi]["lr"] = ropt.param_groups[gi]["lr"] = lr[gi]
+            if (gi, pi) == frozen or ((gi, pi) == late and step == 0):
+                p.grad = r.grad = None
+            elif (gi, pi) == strided:
+                wide = torch.randn(r.shape[0], 2 * r.shape[1], generator=gen) * 0.3
+                r.grad, p.grad = wide[:, ::2].clone(), wide.to(dev)[:, ::2]
+                assert not p.grad.is_contiguous()
+            else:
+                r.grad, p.grad = G[offs[k]:offs[k + 1]].view(r.shape), Gd[offs[k]:offs[k + 1]].view(r.shape)
+        versions = [mine[gi][pi]._version for gi, pi in flat]
+        opt.step()
+        ropt.step()
+        moved = [mine[gi][pi]._version - v for (gi, pi), v in zip(flat, versions)]
+        assert moved == [0 if ref[gi][pi].grad is None else 1 for gi, pi in flat], moved
+        compare("parameters", step, [mine[gi][pi] for gi, pi in flat], [ref[gi][pi] for gi, pi in flat])
+        stepped = [(gi, pi) for gi, pi in flat if ref[gi][pi].grad is not None]
+        assert all(("momentum_buffer" in ropt.state[ref[gi][pi]]) == (gi == 0) for gi, pi in stepped)
+        # momentum 0: torch keeps no buffer; the kernel's holds d = g + 0 * p
+        compare("momentum buffers", step, [opt.state[mine[gi][pi]]["momentum_buffer"] for gi, pi in stepped],
+                [ropt.state[ref[gi][pi]]["momentum_buffer"] if gi == 0 else ref[gi][pi].grad for gi, pi in stepped])
+        assert torch.equal(mine[0][3].detach().cpu(), ref[0][3].detach()) and mine[0][3] not in opt.state
+        assert (mine[0][11] in opt.state) == (step > 0)
+        assert len(stepped) == (211 if step == 0 else 212)
+
+
+def test_sgd_steps_dense_non_contiguous_parameters_as_torch_sgd():
+    """A dense parameter in another memory order - a channels_last conv weight (autograd gives its gradient the same strides),
+    a transposed matrix - gets torch.optim.SGD's update: the kernel walks numel() elements from each pointer, so parameter,
+    gradient and momentum buffer must be walked in ONE order, whatever layout the gradient arrives in.  A parameter with gaps
+    cannot be walked that way and is refused by its strides."""
+    import yolo_fastestv2_amd as yfv2
+    gen = torch.Generator().manual_seed(79)
+    groups = (dict(lr=0.01, momentum=0.949, weight_decay=5e-4),)
+
+    def make():
+        cl = (torch.randn(8, 4, 3, 3, generator=gen) * 0.5).contiguous(memory_format=torch.channels_last)
+        tr = (torch.randn(5, 7, generator=gen) * 0.5).t()
+        plain = torch.randn(8, 4, 3, 3, generator=gen) * 0.5
+        assert not cl.is_contiguous() and not tr.is_contiguous() and cl.stride() == (36, 1, 12, 4) and tr.stride() == (1, 7)
+        return [[cl, tr, plain]]
+
+    mine, ref, opt, ropt = _sgd_pair(make, groups)
+    assert mine[0][0].stride() == (36, 1, 12, 4) and mine[0][1].stride() == (1, 7)
+    dev = mine[0][0].device
+    for step in range(3):
+        for p, r in zip(mine[0], ref[0]):
+            g = torch.randn(r.shape, generator=gen) * 0.3            # row-major ...
+            if step != 1:
+                g = torch.empty_strided(r.shape, r.stride()).copy_(g)  # ... or in the parameter's own order, as autograd delivers it
+            r.grad, p.grad = g, _same_layout_on(g, dev)
+        opt.step()
+        ropt.step()
+        torch.cuda.synchronize()
+        for pi, (p, r) in enumerate(zip(mine[0], ref[0])):
+            assert p.stride() == r.stride()
+            assert _close(p, r), (step, pi, float((p.detach().cpu() - r.detach()).abs().max()))
+            assert _close(opt.state[p]["momentum_buffer"], ropt.state[r]["momentum_buffer"]), (step, pi)
+    gappy = torch.nn.Parameter(torch.randn(6, 8, generator=gen).to(dev)[:, ::2])
+    assert gappy.stride() == (8, 2)
+    gappy.grad = torch.ones_like(gappy)
+    before = gappy.detach().clone()
+    with pytest.raises(RuntimeError, match=r"strides \(8, 2\)"):
+        yfv2.SGD([gappy], lr=0.01, momentum=0.9).step()
+    assert torch.equal(gappy.detach(), before)
