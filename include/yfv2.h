@@ -1048,6 +1048,15 @@ YFV2_API int64_t yfv2_debug_activation(yfv2_handle h, int32_t which, int32_t B, 
  * test replays the float64 oracle on exactly those decisions (tests/test_train_gpu.py).  Returns the element count (with
  * host_dst NULL or capacity too small: the count needed, nothing copied), -1 on error.  Synchronises the device. */
 YFV2_API int64_t yfv2_debug_train_relu_output(yfv2_handle h, const char* conv_name, float* host_dst, int64_t capacity);
+/* ... and every tensor a training kernel reads or writes, after a yfv2_train_forward and after the yfv2_train_backward that follows it
+ * (the arenas are bump-allocated and the gradient arena is zeroed only at the start of a backward: all of them are intact when either
+ * call has returned).  name = a conv's state_dict prefix: which = 0 the conv's output y (before BatchNorm), 1 the op's output window
+ * (after BatchNorm [+ ReLU]), 2 / 3 the gradients of those two, 4 / 5 the saved batch mean / 1 / sqrt(biased variance + eps), C floats.
+ * name = "backbone.maxpool", "backbone.stageS.I" (a shuffle block's concatenated output) or "fpn.p2" (the upsample + concat tensor):
+ * which = 1 the value, 3 its gradient.  Dense (B,C,H,W); the contract of yfv2_debug_train_relu_output (size query with NULL, -1 and a
+ * message on misuse, synchronises the device).  Gradients read before the first backward are whatever the arena holds.  An addition
+ * within ABI 7. */
+YFV2_API int64_t yfv2_debug_train_tensor(yfv2_handle h, const char* name, int32_t which, float* host_dst, int64_t capacity);
 
 /* Host-only test hook: validates cfg, builds the launch plan and packs the weights exactly as yfv2_create +
  * yfv2_load_weights do, WITHOUT a device (the workspace gets made-up addresses used only for pointer arithmetic);

@@ -181,6 +181,7 @@ int main() {
   CHECK(yfv2_debug_repeat_step(h, nullptr, 1, nullptr, 0, 1, nullptr) == YFV2_ERR_ARG, "debug_repeat_step");
   CHECK(yfv2_debug_activation(h, 0, 1, nullptr, 0) == YFV2_ERR_ARG, "debug_activation");
   CHECK(yfv2_debug_train_relu_output(h, "x", nullptr, 0) == -1, "debug_train_relu_output");
+  CHECK(yfv2_debug_train_tensor(h, "x", 0, nullptr, 0) == -1, "debug_train_tensor");
 
   std::printf("host_san ok: %d checks\n", g_checks);
   return 0;

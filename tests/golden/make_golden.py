@@ -487,6 +487,99 @@ def make_train_golden():
     np.savez_compressed(os.path.join(HERE, "golden_train.npz"), **out)
 
 
+TRAIN_SHAPES_SUBSAMPLE = (1024, 8)   # a kept tensor of more than 1024 elements is stored as every 8th (flat order): the file stays the size of golden_loss_shapes.npz
+
+
+def train_shapes_keep(t):
+    """what golden_train_shapes.npz stores of one kept tensor (numpy array in, flat array out)"""
+    limit, step = TRAIN_SHAPES_SUBSAMPLE
+    flat = np.ascontiguousarray(t).reshape(-1)
+    return flat[::step] if flat.size > limit else flat
+
+
+def make_train_shapes_golden():
+    """golden_train_shapes.npz: make_train_golden's procedure (the reference's own Detector in train() mode, its compute_loss
+    with the clamp_ shim, backward, SGD step; oracle.train_step held to it by the same rules before anything is written) over
+    the table of tests/train_cases.py: other input sizes (cfg width / height, per-axis scaled anchors), batches and class counts.
+    Stored per case: the four losses, every parameter's gradient norm and largest entry, the gradients and updated values of
+    the TRAIN_KEEP tensors (train_shapes_keep) and TRAIN_BN's running statistics.  For a case whose `raises` is set, the file
+    records that the reference raises (nn.BatchNorm2d on one value per channel) and with what message."""
+    import importlib.util
+    sys.path.insert(0, os.path.dirname(HERE))
+    import train_cases as TC
+    torch.set_num_threads(1)
+    det, _ = import_reference()
+    spec = importlib.util.spec_from_file_location("ref_loss", os.path.join(REF, "utils", "loss.py"))
+    L = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(L)
+    orig = torch.Tensor.clamp_
+
+    def clamp_(self, mn=None, mx=None):
+        fix = lambda v: int(v) if (torch.is_tensor(v) and not self.is_floating_point()) else v  # noqa: E731
+        return orig(self, fix(mn), fix(mx))
+    torch.Tensor.clamp_ = clamp_
+    out = {"n": np.asarray(len(TC.CASES)), "cases": np.asarray([c[:6] for c in TC.CASES], np.int64), "raises": np.asarray([c.raises for c in TC.CASES]),
+           "lr": np.asarray(TC.LR, np.float64), "subsample": np.asarray(TRAIN_SHAPES_SUBSAMPLE, np.int64)}
+    try:
+        for ci, c in enumerate(TC.CASES):
+            w, x, t = TC.case_inputs(c)
+            anchors = TC.anchors_for(c.H, c.W)
+            cfg = {"anchor_num": 3, "classes": c.classes, "width": c.W, "height": c.H, "anchors": anchors}
+            model = det.Detector(c.classes, 3, True)
+            print(model.load_state_dict({k: v.clone() for k, v in w.items()}))
+            model.train()
+            opt = torch.optim.SGD(params=model.parameters(), lr=TC.LR, momentum=0.949, weight_decay=0.0005)
+            out["targets%d" % ci] = t
+            if c.raises:
+                try:
+                    model(torch.from_numpy(x))
+                    raise AssertionError("the reference accepted one value per channel")
+                except ValueError as e:
+                    out["error%d" % ci] = np.asarray(str(e))
+                try:
+                    oracle.train_step(w, torch.from_numpy(x), torch.from_numpy(t), anchors, c.classes, TC.LR, width=c.W, height=c.H)
+                    raise AssertionError("the oracle accepted one value per channel")
+                except ValueError as e:
+                    assert str(e) == str(out["error%d" % ci]), (str(e), out["error%d" % ci])
+                print("train shapes case", ci, TC.case_id(c), "raises:", out["error%d" % ci])
+                continue
+            preds = model(torch.from_numpy(x))
+            ref = L.compute_loss(preds, torch.from_numpy(t), cfg, torch.device("cpu"))
+            ref[3].backward()
+            grads = {k: (p.grad.clone() if p.grad is not None else torch.zeros_like(p)) for k, p in model.named_parameters()}
+            opt.step()
+            after = {k: v.detach().clone() for k, v in model.state_dict().items()}
+            mine = oracle.train_step(w, torch.from_numpy(x), torch.from_numpy(t), anchors, c.classes, TC.LR, width=c.W, height=c.H)
+            # ---- the oracle against the reference, by make_train_golden's rules, before anything is written
+            for a, b in zip(ref, mine["losses"]):
+                assert abs(float(a) - b) <= 1e-6 * max(1.0, abs(float(a))), ("loss", float(a), b)
+            worst = 0.0
+            for k, g in grads.items():
+                d = float((g - mine["grads"][k]).abs().max()); sc = float(g.abs().max())
+                worst = max(worst, d / max(sc, 1e-12))
+                assert d <= 1e-5 * max(sc, 1e-6), ("grad", k, d, sc)
+            for k, v in after.items():
+                d = float((v.double() - mine["new_w"][k].double()).abs().max())
+                assert d <= 1e-6 * max(1.0, float(v.double().abs().max())), ("after", k, d)
+            print("train shapes case", ci, TC.case_id(c), [float(v) for v in ref], "worst relative gradient difference oracle vs reference %.2e" % worst)
+            out["loss%d" % ci] = np.asarray([float(v) for v in ref], np.float32)
+            names = sorted(grads)
+            out["names"] = np.asarray(names)     # (the same 225 at every case)
+            out["gnorm%d" % ci] = np.asarray([float(grads[k].double().norm()) for k in names], np.float64)
+            out["gmax%d" % ci] = np.asarray([float(grads[k].abs().max()) for k in names], np.float32)
+            for k in TRAIN_KEEP:
+                out["grad%d:%s" % (ci, k)] = train_shapes_keep(grads[k].numpy())
+                out["after%d:%s" % (ci, k)] = train_shapes_keep(after[k].numpy())
+            for bnn in TRAIN_BN:
+                for sfx in (".running_mean", ".running_var"):
+                    out["after%d:%s" % (ci, bnn + sfx)] = after[bnn + sfx].numpy()
+    finally:
+        torch.Tensor.clamp_ = orig
+    path = os.path.join(HERE, "golden_train_shapes.npz")
+    np.savez_compressed(path, **out)
+    print("golden_train_shapes.npz", os.path.getsize(path), "bytes")
+
+
 CURVE = dict(classes=80, B=8, T=20, seed=131, lr=0.001, batches_per_epoch=2, iterations=12, perturbed_runs=3)
 CURVE64 = dict(classes=80, B=64, T=150, seed=164, lr=0.001, batches_per_epoch=2, iterations=12, perturbed_runs=2)   # train.py's regime: SURVEY 8(f) row 3 names bs = 64
 CURVES = (("", CURVE), ("b64_", CURVE64))
@@ -730,6 +823,8 @@ def make_adversarial_golden():
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "train":
         make_train_golden()   # only golden_train.npz
+    elif len(sys.argv) > 1 and sys.argv[1] == "train_shapes":
+        make_train_shapes_golden()   # only golden_train_shapes.npz
     elif len(sys.argv) > 1 and sys.argv[1] == "curve":
         make_curve_golden()   # only golden_curve.npz
     elif len(sys.argv) > 1 and sys.argv[1] == "loss":

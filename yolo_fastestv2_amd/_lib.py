@@ -255,6 +255,7 @@ _PROTOTYPES = {
                                   C.c_void_p, C.c_void_p]),
     "yfv2_debug_activation": (C.c_int64, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int64]),
     "yfv2_debug_train_relu_output": (C.c_int64, [C.c_void_p, C.c_char_p, C.c_void_p, C.c_int64]),
+    "yfv2_debug_train_tensor": (C.c_int64, [C.c_void_p, C.c_char_p, C.c_int32, C.c_void_p, C.c_int64]),
 }
 
 _lib = None

@@ -655,6 +655,7 @@ struct Train {
   std::map<std::string, float*> param, pgrad;   // the binding
   int B = 0; std::vector<Op> ops; size_t n_body = 0;   // the list recorded for batch B (empty after a new binding); ops[n_body ..] are the six output convs
   std::vector<Finish> fin;                      // in the order the backward first meets them (wgrad_finish_multi_kernel's chunks)
+  std::vector<std::pair<std::string, Tens>> named;   // the tensors no conv names: the max-pool output, each block's output, the FPN concat (yfv2_debug_train_tensor)
   size_t arena_floats = 0, pool_ints = 0, bn_doubles = 0, wg_doubles = 0;   // what the list uses of the blocks below
   DeviceBlock acts, grads, pool_arg;            // the two arenas; the max-pool's winners
   DeviceBlock dscr;                             // four doubles per BatchNorm channel: sum, sum of squares, the two backward sums (zeroed per forward)
@@ -707,13 +708,14 @@ struct Train {
   // shufflenetv2.py:19-63,102-109, fpn.py, detector.py:21-47 for `batch` images: the list, every arena offset, both scratch ranges.
   // A tensor missing from the binding: `err`, and the list is not to be run
   void record(int batch) {
-    B = batch; ops.clear(); fin.clear(); err.clear();
+    B = batch; ops.clear(); fin.clear(); named.clear(); err.clear();
     arena_floats = bn_doubles = wg_doubles = 0;
     const int H = cfg.height, W = cfg.width, A = cfg.anchor_num;
     // the input is NOT copied: the stem reads the caller's tensor (it needs no gradient)
     const Tens stem = conv_bn(Conv::Stem, dense(3, H, W), 24, "backbone.first_conv", 0, true);
     Tens cur = alloc(24, H / 4, W / 4), c2;
     plain(OpKind::MaxPool, stem, {}, cur);
+    named.emplace_back("backbone.maxpool", cur);
     pool_ints = (size_t)B * 24 * cur.H * cur.W;
     const int repeats[3] = {4, 8, 4}, chans[4] = {24, 48, 96, 192};
     for (int si = 0; si < 3; ++si) {
@@ -732,6 +734,7 @@ struct Train {
           conv_bn(Conv::Pointwise, m2, slice(out, mid, 1, mid), p + ".branch_main", 5, true);
         }
         cur = out;
+        named.emplace_back(p, out);
       }
       if (si == 1) c2 = cur;
     }
@@ -739,6 +742,7 @@ struct Train {
     const Tens cls3 = tower("fpn.cls_head_3.block", s3), reg3 = tower("fpn.reg_head_3.block", s3);
     const Tens p2 = alloc(c3.C + c2.C, c2.H, c2.W);
     plain(OpKind::UpCat, c3, c2, p2);
+    named.emplace_back("fpn.p2", p2);
     const Tens s2 = conv_bn(Conv::Pointwise, p2, 72, "fpn.conv1x1_2", 0, true);
     const Tens cls2 = tower("fpn.cls_head_2.block", s2), reg2 = tower("fpn.reg_head_2.block", s2);
     n_body = ops.size();
@@ -905,6 +909,10 @@ int yfv2_train_forward(yfv2_handle h, const float* x, int32_t B, float* const ou
   if (!h || !x || !out6 || B < 1) return yfv2_ctx_fail(h, YFV2_ERR_ARG, "yfv2_train_forward: bad argument");
   Train* t = train_of(h, false);
   if (!t || t->param.empty()) return yfv2_ctx_fail(h, YFV2_ERR_STATE, "yfv2_train_forward: yfv2_train_bind has not been called");
+  // nn.BatchNorm2d in train mode refuses a channel with a single value (the coarsest map is height / 32 x width / 32 per image): the
+  // batch variance of one value is 0 and the unbiased one undefined
+  if ((int64_t)B * (t->cfg.height / 32) * (t->cfg.width / 32) <= 1)
+    return yfv2_ctx_fail(h, YFV2_ERR_ARG, "yfv2_train_forward: expected more than 1 value per channel when training (batch 1 on a 1 x 1 map)");
   hipStream_t s = static_cast<hipStream_t>(stream);
   DeviceGuard guard(t->cfg.device);
   t->forward_done = false;
@@ -952,25 +960,42 @@ int yfv2_train_backward(yfv2_handle h, const float* const grad6[6], void* stream
   return YFV2_OK;
 }
 
+// which: 0 the conv output y, 1 the op's output window (a named tensor: its value), 2 / 3 their gradients, 4 / 5 the saved mean / invstd
+int64_t yfv2_debug_train_tensor(yfv2_handle h, const char* name, int32_t which, float* host_dst, int64_t capacity) {
+  Train* t = h ? train_of(h, false) : nullptr;
+  if (!t || !name || which < 0 || which > 5) { (void)yfv2_ctx_fail(h, YFV2_ERR_ARG, "yfv2_debug_train_tensor: bad argument"); return -1; }
+  const auto it = std::find_if(t->ops.begin(), t->ops.end(), [&](const Op& o) { return o.kind == OpKind::ConvBn && o.name == name; });
+  const auto nt = std::find_if(t->named.begin(), t->named.end(), [&](const std::pair<std::string, Tens>& p) { return p.first == name; });
+  const bool is_conv = it != t->ops.end(), is_named = !is_conv && nt != t->named.end() && (which == 1 || which == 3);
+  if ((!is_conv && !is_named) || !t->acts.p || !t->grads.p) {
+    (void)yfv2_ctx_fail(h, YFV2_ERR_STATE, "yfv2_debug_train_tensor: no such tensor in the last yfv2_train_forward"); return -1;
+  }
+  DeviceGuard guard(t->cfg.device);
+  Tens src;
+  if (which >= 4) { src = dense(it->y.C, 1, 1); src.off = it->stat + (which == 5 ? (size_t)it->y.C : 0); }   // (C,): one "image" of C channels
+  else src = is_named ? nt->second : ((which & 1) ? it->out : it->y);
+  const int images = which >= 4 ? 1 : t->B;
+  const V z = (which == 2 || which == 3) ? t->grad(src) : t->act(src);
+  const int64_t n = (int64_t)images * z.C * z.H * z.W;
+  if (!host_dst || capacity < n) return n;
+  float* dense_p = nullptr;
+  if (hipDeviceSynchronize() != hipSuccess || hipMalloc(reinterpret_cast<void**>(&dense_p), (size_t)n * sizeof(float)) != hipSuccess) {
+    (void)yfv2_ctx_fail(h, YFV2_ERR_DEVICE, "yfv2_debug_train_tensor: device error"); return -1;
+  }
+  const V d{dense_p, z.C, 0, 1, z.C, z.H, z.W};
+  hipLaunchKernelGGL(view_copy_kernel, dim3(blocks_for((size_t)n)), dim3(256), 0, nullptr, d, z, images, 0);
+  const hipError_t e = hipMemcpy(host_dst, dense_p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost);
+  (void)hipFree(dense_p);
+  if (e != hipSuccess) { (void)yfv2_ctx_fail(h, YFV2_ERR_DEVICE, "yfv2_debug_train_tensor: copy failed"); return -1; }
+  return n;
+}
+
 int64_t yfv2_debug_train_relu_output(yfv2_handle h, const char* conv_name, float* host_dst, int64_t capacity) {
   Train* t = h ? train_of(h, false) : nullptr;
   if (!t || !conv_name) { (void)yfv2_ctx_fail(h, YFV2_ERR_ARG, "yfv2_debug_train_relu_output: bad argument"); return -1; }
   const auto it = std::find_if(t->ops.begin(), t->ops.end(), [&](const Op& o) { return o.kind == OpKind::ConvBn && o.relu && o.name == conv_name; });
   if (it == t->ops.end() || !t->acts.p) { (void)yfv2_ctx_fail(h, YFV2_ERR_STATE, "yfv2_debug_train_relu_output: no such ReLU output in the last yfv2_train_forward"); return -1; }
-  DeviceGuard guard(t->cfg.device);
-  const V z = t->act(it->out);
-  const int64_t n = (int64_t)t->B * z.C * z.H * z.W;
-  if (!host_dst || capacity < n) return n;
-  float* dense = nullptr;
-  if (hipDeviceSynchronize() != hipSuccess || hipMalloc(reinterpret_cast<void**>(&dense), (size_t)n * sizeof(float)) != hipSuccess) {
-    (void)yfv2_ctx_fail(h, YFV2_ERR_DEVICE, "yfv2_debug_train_relu_output: device error"); return -1;
-  }
-  const V d{dense, z.C, 0, 1, z.C, z.H, z.W};
-  hipLaunchKernelGGL(view_copy_kernel, dim3(blocks_for((size_t)n)), dim3(256), 0, nullptr, d, z, t->B, 0);
-  const hipError_t e = hipMemcpy(host_dst, dense, (size_t)n * sizeof(float), hipMemcpyDeviceToHost);
-  (void)hipFree(dense);
-  if (e != hipSuccess) { (void)yfv2_ctx_fail(h, YFV2_ERR_DEVICE, "yfv2_debug_train_relu_output: copy failed"); return -1; }
-  return n;
+  return yfv2_debug_train_tensor(h, conv_name, 1, host_dst, capacity);   // the op's output window
 }
 
 int yfv2_sgd_step(yfv2_handle h, float* param, const float* grad, float* momentum_buf, int64_t n, float lr, float momentum, float weight_decay,

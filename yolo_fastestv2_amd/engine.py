@@ -945,6 +945,22 @@ class Engine:
             check(-1, self._h)
         return host
 
+    TRAIN_TENSOR = {"y": 0, "out": 1, "grad_y": 2, "grad_out": 3, "mean": 4, "invstd": 5}
+
+    def debug_train_tensor(self, name, which):
+        """flat host tensor: one tensor of the training arenas after the last train_forward / train_backward (include/yfv2.h
+        yfv2_debug_train_tensor).  name: a conv's state_dict prefix, or "backbone.maxpool", "backbone.stageS.I", "fpn.p2";
+        which: "y", "out", "grad_y", "grad_out", "mean", "invstd" (or the number)"""
+        L = _lib.lib()
+        w = self.TRAIN_TENSOR[which] if isinstance(which, str) else int(which)
+        n = L.yfv2_debug_train_tensor(self._h, name.encode(), w, None, 0)
+        if n < 0:
+            check(-1, self._h)
+        host = torch.empty(n, dtype=torch.float32)
+        if L.yfv2_debug_train_tensor(self._h, name.encode(), w, C.c_void_p(host.data_ptr()), n) != n:
+            check(-1, self._h)
+        return host
+
     def sgd_step(self, param, grad, buf, lr, momentum, weight_decay, first):
         check(_lib.lib().yfv2_sgd_step(self._h, _ptr(param), _ptr(grad), _ptr(buf), param.numel(), float(lr), float(momentum), float(weight_decay),
                                        1 if first else 0, _stream(self.device)), self._h)

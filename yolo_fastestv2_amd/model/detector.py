@@ -295,6 +295,8 @@ class Detector(nn.Module):
                 raise NotImplementedError("export_onnx=True is an inference layout (detector.py:33-44): call .eval()")
             if x.dtype != torch.float32 or x.dim() != 4 or x.shape[1] != 3:
                 raise ValueError("train mode takes the fp32 (B,3,H,W) tensor train.py:101 builds")
+            if x.shape[0] * (x.shape[2] // 32) * (x.shape[3] // 32) <= 1:      # nn.BatchNorm2d's own refusal, before any launch
+                raise ValueError("Expected more than 1 value per channel when training, got input size %s" % str(torch.Size((x.shape[0], 96, x.shape[2] // 32, x.shape[3] // 32))))   # (stage4.0.branch_proj.1 meets it first)
             params = [p for _, p in self.named_parameters()]
             out = _TrainForward.apply(self, x.contiguous(), *params)
             out[0]._yfv2_engine = self.engine_for(x, sync=False)
