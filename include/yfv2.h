@@ -261,10 +261,11 @@ YFV2_API int yfv2_detect_tiled_u8(yfv2_handle h, const yfv2_frame* frames, int32
                                   float conf_thres, double iou_thres, double merge_thres, int32_t merge_metric, int32_t max_out,
                                   float* dets, int32_t* src, int32_t* count, void* stream);
 
-/* ---- decoder-format frames: YUV 4:2:0 planes read in place ----
- * Video and JPEG decoders write a luma plane and half-resolution chroma - one interleaved plane (NV12 / NV21) or two planes
- * (I420; YV12 = I420 with u and v swapped by the caller) - each with a row pitch of its own.  The entry points below take those
- * planes as they are.  THE RULE: the result for a YUV frame is bit-identical to converting the frame to packed B, G, R with the
+/* ---- decoder-format frames: YUV planes read in place (the samplings other than 4:2:0: 4.24) ----
+ * Video decoders write a luma plane and half-resolution chroma - one interleaved plane (NV12 / NV21) or two planes
+ * (I420; YV12 = I420 with u and v swapped by the caller) - each with a row pitch of its own.  A JPEG decoder keeps the sampling of
+ * its file - 4:4:4, 4:4:0, 4:2:2 (planar, or one packed plane), grey, or 4:2:0 - and capture devices deliver packed 4:2:2: the six
+ * further 8-bit formats below.  The entry points below take those planes as they are.  THE RULE: the result for a YUV frame is bit-identical to converting the frame to packed B, G, R with the
  * integer formula below and passing that to the _u8 entry point of the same name.
  *   pixel (r, c)   R = y0 + r, C = x0 + c; luma y[R * pitch_y + C]; chroma at (R >> 1, C >> 1), replicated, no interpolation (as
  *                  cv2 and the decoders' own sample converters do): NV12 u[(R>>1) * pitch_c + 2 * (C>>1)] is U and the byte after
@@ -308,15 +309,41 @@ YFV2_API int yfv2_detect_tiled_u8(yfv2_handle h, const yfv2_frame* frames, int32
  * of a row; a frame wider than the two-byte width limit - the widest whose two luma rows, chroma rows and output row fit 160 KiB of
  * LDS, 20 343 at cfg.width 352 (half of the 8-bit limit: the staged rows take twice the bytes); and all frames of one call must
  * have ONE sample width - a call that mixes 8-bit and 10-bit frames is refused, the message naming the first frame that differs
- * from frame 0 (one launch is one kernel instantiation; split the batch). */
+ * from frame 0 (one launch is one kernel instantiation; split the batch).
+ *
+ * The other 8-bit samplings: six formats of one-byte samples; yfv2_frame_yuv is unchanged.  Pixel (r, c) of the
+ * frame is (R, C) = (y0 + r, x0 + c) of the planes and reads
+ *   YFV2_YUV_I422  planes y, u, v   luma y[R * pitch_y + C]; U u[R * pitch_c + (C >> 1)]; V likewise in v           (4:2:2, planar)
+ *   YFV2_YUV_I440  planes y, u, v   luma as above; chroma at ((R >> 1), C)                                            (4:4:0)
+ *   YFV2_YUV_I444  planes y, u, v   luma as above; chroma at (R, C)                                                   (4:4:4)
+ *   YFV2_YUV_YUYV  plane y only     luma y[R * pitch_y + 2 C]; U y[R * pitch_y + 4 (C >> 1) + 1]; V that + 2          (YUY2: Y0 U Y1 V)
+ *   YFV2_YUV_UYVY  plane y only     luma y[R * pitch_y + 2 C + 1]; U y[R * pitch_y + 4 (C >> 1)]; V that + 2          (U Y0 V Y1)
+ *   YFV2_YUV_GREY  plane y only     luma y[R * pitch_y + C]; U = V = 128                                              (4:0:0)
+ * Chroma is replicated, never interpolated, exactly as for 4:2:0 (a JPEG decoder's "fancy" up-sampling is not this rule).  The
+ * colour formula is the 8-bit one above with the same four tables; for YFV2_YUV_GREY it runs with u = v = 0, so a full-range grey
+ * frame gives B = G = R = Y.  THE RULE is the one above: every *_yuv entry point on such a frame is bit-identical to converting the
+ * frame with that formula and calling the _u8 entry point of the same name.  Origin and size may have any parity: a tile or a crop
+ * of a packed frame at odd x0 starts in the middle of a macropixel.
+ * Checked before anything is enqueued (YFV2_ERR_ARG, the message names the frame and the field): u and v may be NULL and pitch_c is
+ * ignored for YUYV, UYVY and GREY; u and v must not be NULL for the three planar formats; pitch_y >= x0 + width for the planar formats
+ * and grey, pitch_y >= 4 * (((x0 + width - 1) >> 1) + 1) for the packed ones (an odd last pixel still reads its whole macropixel, and
+ * nothing beyond it); pitch_c at least the last chroma byte of a row, with the format's horizontal shift; the range checks on the
+ * pitches with the format's vertical shift.
+ * ONE CALL MAY MIX 8-BIT FORMATS.  A call whose frames are all NV12, NV21 or I420 is the launch it always was.  A call with at least
+ * one frame of these six formats runs the GENERAL 8-bit launch, which reads every 8-bit format, the three 4:2:0 ones included - a
+ * 4:2:0 frame in such a call gives the same bits as in a 4:2:0-only call.  The general launch stages up to three full-width rows per
+ * blended source row (a 4:4:4 frame has them), so its width limit is lower - 27 125 pixels at cfg.width 352 where a 4:2:0-only call
+ * admits 40 689 (26 429 against 39 641 for training batches) - and it applies to EVERY frame of a mixed call, the NV12 ones too: the
+ * message names the limit and says why.  Mixing 8-bit and 10-bit frames stays refused, as above. */
 enum { YFV2_YUV_NV12 = 0, YFV2_YUV_NV21 = 1, YFV2_YUV_I420 = 2,
-       YFV2_YUV_P010 = 16, YFV2_YUV_I010 = 17 };   /* bit 4: two-byte samples (the 10-bit formats, below) */
+       YFV2_YUV_I422 = 3, YFV2_YUV_I440 = 4, YFV2_YUV_I444 = 5, YFV2_YUV_YUYV = 6, YFV2_YUV_UYVY = 7, YFV2_YUV_GREY = 8,   /*  */
+       YFV2_YUV_P010 = 16, YFV2_YUV_I010 = 17 };   /* bit 4: two-byte samples (the 10-bit formats, above) */
 enum { YFV2_BT601_LIMITED = 0, YFV2_BT709_LIMITED = 1, YFV2_BT601_FULL = 2, YFV2_BT709_FULL = 3 };
 typedef struct yfv2_frame_yuv {
-  const uint8_t* y;        /* DEVICE: luma plane, any alignment (P010/I010: 2-byte aligned, like u and v) */
-  const uint8_t* u;        /* NV12/NV21/P010: the interleaved chroma plane; I420/I010: the U plane */
-  const uint8_t* v;        /* I420/I010: the V plane; ignored for NV12/NV21/P010 */
-  int64_t pitch_y, pitch_c;/* bytes per row of the luma / chroma plane(s) */
+  const uint8_t* y;        /* DEVICE: luma plane, any alignment (P010/I010: 2-byte aligned, like u and v); YUYV/UYVY: the one packed plane */
+  const uint8_t* u;        /* NV12/NV21/P010: the interleaved chroma plane; I420/I422/I440/I444/I010: the U plane; ignored for YUYV/UYVY/GREY */
+  const uint8_t* v;        /* I420/I422/I440/I444/I010: the V plane; ignored for every other format */
+  int64_t pitch_y, pitch_c;/* bytes per row of the luma / chroma plane(s); pitch_c is ignored for YUYV/UYVY/GREY */
   int32_t x0, y0;          /* top-left pixel of the frame inside the planes (any parity): a crop needs no copy */
   int32_t width, height;   /* pixels, >= 1, any parity */
   int32_t format, colour;  /* YFV2_YUV_*, YFV2_BT* */
@@ -1088,6 +1115,9 @@ YFV2_API int yfv2_debug_rows(int32_t row_kind, int32_t yuv, int32_t w, int32_t W
 /* ... and for yfv2_frame_yuv frames of two-byte samples (YFV2_YUV_P010 / _I010): the same arguments, checks and results.  (yuv = 1
  * above is the one-byte formats and yuv = 2 stays an argument error.)  An addition within ABI 7. */
 YFV2_API int yfv2_debug_rows16(int32_t row_kind, int32_t w, int32_t W, int64_t* lds_bytes, int32_t* max_width);
+/* ... and for the GENERAL one-byte launch, the one of a call with at least one frame that is not 4:2:0 (YFV2_YUV_I422 .. _GREY): the
+ * same arguments, checks and results.  An addition within ABI 7. */
+YFV2_API int yfv2_debug_rows_any(int32_t row_kind, int32_t w, int32_t W, int64_t* lds_bytes, int32_t* max_width);
 
 #ifdef __cplusplus
 }

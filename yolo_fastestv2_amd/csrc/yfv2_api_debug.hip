@@ -116,6 +116,15 @@ int yfv2_debug_rows16(int32_t row_kind, int32_t w, int32_t W, int64_t* lds_bytes
   return YFV2_OK;
 }
 
+// ... and of the general 1-byte YUV frame kind (a batch with a frame that is not 4:2:0; tests/yuv_any_model.py): the same checks
+int yfv2_debug_rows_any(int32_t row_kind, int32_t w, int32_t W, int64_t* lds_bytes, int32_t* max_width) {
+  if (row_kind < 0 || row_kind >= YFV2_ROW_KINDS || w < 1 || w > (1 << 26) || W < 1 || W > (1 << 20))
+    return fail(nullptr, YFV2_ERR_ARG, "yfv2_debug_rows_any: bad argument");
+  if (lds_bytes) *lds_bytes = (int64_t)yfv2_rows_lds_bytes((Yfv2RowKind)row_kind, YFV2_FRAMES_YUV8_ANY, w, W);
+  if (max_width) *max_width = yfv2_rows_max_width((Yfv2RowKind)row_kind, YFV2_FRAMES_YUV8_ANY, W);
+  return YFV2_OK;
+}
+
 // effective shader clock, measured by the shader (yfv2_probe.hip): enqueue on `stream` ...
 int yfv2_clock_probe_begin(yfv2_handle h, int32_t workgroups, float milliseconds, int32_t busy, void* stream) {
   if (!h || workgroups < 1 || workgroups > 4096 || !(milliseconds > 0.f) || milliseconds > 10000.f)

@@ -1,6 +1,6 @@
 // yfv2_api_frames.hip - host side of libyfv2.so, the entry points that take caller frames: the resize, detection on ragged
 // batches of frames, and tiled detection (tile plan, merge, both in one call).  The handle and the shared plumbing: yfv2_ctx.h.
-// Frames come in two kinds, yfv2_frame (packed B, G, R) and yfv2_frame_yuv (4:2:0 planes).  Each kind is described once
+// Frames come in two kinds, yfv2_frame (packed B, G, R) and yfv2_frame_yuv (YUV planes: 4:2:0 at 8 or 10 bits, or any 8-bit sampling).  Each kind is described once
 // (BgrFrames, YuvFrames: what differs); what a batch becomes is a row kind (Yfv2RowKind, yfv2_internal.h: uint8 batch, counted
 // uint8 crops, training batch, fp32 / fp16 tensor), a VALUE: check_frames<Kind> turns a caller's batch into a FrameBatch under the
 // row kind's width limit (yfv2_rows_max_width), enqueue_rows uploads its table and launches the rows of the resize or the training
@@ -37,16 +37,25 @@ static int check_frame(yfv2_handle h, const std::string& at, const yfv2_frame& f
 // what every YUV entry point checks of one caller's frame - a whole frame of yfv2_detect_tiled_yuv or a frame of a batch; `at` as in
 // check_frame.  The width limit is not here: it binds what is resized, which for a tiled frame are its tiles.
 static int check_frame_yuv(yfv2_handle h, const std::string& at, const yfv2_frame_yuv& f) {
-  if (f.format != YFV2_YUV_NV12 && f.format != YFV2_YUV_NV21 && f.format != YFV2_YUV_I420 && f.format != YFV2_YUV_P010 && f.format != YFV2_YUV_I010)
+  if (!(f.format >= YFV2_YUV_NV12 && f.format <= YFV2_YUV_GREY) && f.format != YFV2_YUV_P010 && f.format != YFV2_YUV_I010)
     return fail(h, YFV2_ERR_ARG, at + "unknown format " + std::to_string(f.format));
+  static const char* const names8[] = {"NV12", "NV21", "I420", "I422", "I440", "I444", "YUYV", "UYVY", "GREY"};
   const int sb = yfv2_yuv_sample_bytes(f.format);           // 2: every sample index below is doubled to a byte offset
   if (f.colour < YFV2_BT601_LIMITED || f.colour > YFV2_BT709_FULL) return fail(h, YFV2_ERR_ARG, at + "unknown colour " + std::to_string(f.colour));
   if (f.height < 1 || f.width < 1) return fail(h, YFV2_ERR_ARG, at + "height and width must be >= 1");
   if (f.x0 < 0 || f.y0 < 0) return fail(h, YFV2_ERR_ARG, at + "x0 and y0 must be >= 0");
   if (!f.y) return fail(h, YFV2_ERR_ARG, at + "null y");
-  if (!f.u) return fail(h, YFV2_ERR_ARG, at + "null u");
-  const bool planar = yfv2_yuv_planar(f.format);
-  if (planar && !f.v) return fail(h, YFV2_ERR_ARG, at + (sb == 1 ? "null v (I420)" : "null v (I010)"));
+  const bool planar = yfv2_yuv_planar(f.format), packed = yfv2_yuv_packed(f.format);
+  const bool chroma = !packed && !yfv2_yuv_grey(f.format);  // the format has chroma planes: u (and v), pitch_c
+  if (chroma && !f.u) return fail(h, YFV2_ERR_ARG, at + "null u");
+  if (planar && !f.v) {
+    std::string msg = at + "null v (" + (sb == 1 ? names8[f.format] : "I010") + ")";
+    // The values 3, 4 and 5 were refused as unknown before the planar 4:2:2 / 4:4:0 / 4:4:4 formats took them, and a caller's table
+    // written for two planes has no v: say what the value means now and what it got before, whichever of the two the caller meant.
+    if (f.format >= YFV2_YUV_I422 && f.format <= YFV2_YUV_I444)
+      msg += ": format " + std::to_string(f.format) + " takes the planes y, u and v (a library older than these formats answers \"unknown format " + std::to_string(f.format) + "\")";
+    return fail(h, YFV2_ERR_ARG, msg);
+  }
   if (sb == 2) {
     if (reinterpret_cast<uintptr_t>(f.y) & 1) return fail(h, YFV2_ERR_ARG, at + "y must be 2-byte aligned (two-byte samples)");
     if (reinterpret_cast<uintptr_t>(f.u) & 1) return fail(h, YFV2_ERR_ARG, at + "u must be 2-byte aligned (two-byte samples)");
@@ -56,11 +65,17 @@ static int check_frame_yuv(yfv2_handle h, const std::string& at, const yfv2_fram
   }
   const long long xe = (long long)f.x0 + f.width, ye = (long long)f.y0 + f.height;     // one past the frame's last column / row in the planes
   if (xe > 0x7fffffffll || ye > 0x7fffffffll) return fail(h, YFV2_ERR_ARG, at + "x0 + width and y0 + height must be below 2^31");
-  if (f.pitch_y < sb * xe) return fail(h, YFV2_ERR_ARG, at + "pitch_y " + std::to_string(f.pitch_y) + (sb == 1 ? " < x0 + width" : " < 2 * (x0 + width)"));
-  const long long crow = (((xe - 1) >> 1) + 1) * (planar ? 1 : 2) * sb;                  // chroma bytes of a row up to the frame's last sample
-  if (f.pitch_c < crow) return fail(h, YFV2_ERR_ARG, at + "pitch_c " + std::to_string(f.pitch_c) + " < " + std::to_string(crow) + ", the last chroma byte of a row");
+  if (packed) {                                             // up to the last macropixel's last byte: an odd last pixel reads all of it
+    const long long prow = 4 * (((xe - 1) >> 1) + 1);
+    if (f.pitch_y < prow)
+      return fail(h, YFV2_ERR_ARG, at + "pitch_y " + std::to_string(f.pitch_y) + " < " + std::to_string(prow) + " = 4 * (((x0 + width - 1) >> 1) + 1), the last macropixel of a row (" + names8[f.format] + ")");
+  } else if (f.pitch_y < sb * xe)
+    return fail(h, YFV2_ERR_ARG, at + "pitch_y " + std::to_string(f.pitch_y) + (sb == 1 ? " < x0 + width" : " < 2 * (x0 + width)"));
+  const int sx = yfv2_yuv_shift_x(f.format), sy = yfv2_yuv_shift_y(f.format);
+  const long long crow = (((xe - 1) >> sx) + 1) * (planar ? 1 : 2) * sb;                 // chroma bytes of a row up to the frame's last sample
+  if (chroma && f.pitch_c < crow) return fail(h, YFV2_ERR_ARG, at + "pitch_c " + std::to_string(f.pitch_c) + " < " + std::to_string(crow) + ", the last chroma byte of a row");
   if (f.pitch_y > (1ll << 40) || (ye - 1) * f.pitch_y > (1ll << 52)) return fail(h, YFV2_ERR_ARG, at + "pitch_y out of range");
-  if (f.pitch_c > (1ll << 40) || ((ye - 1) >> 1) * f.pitch_c > (1ll << 52)) return fail(h, YFV2_ERR_ARG, at + "pitch_c out of range");
+  if (chroma && (f.pitch_c > (1ll << 40) || ((ye - 1) >> sy) * f.pitch_c > (1ll << 52))) return fail(h, YFV2_ERR_ARG, at + "pitch_c out of range");
   return YFV2_OK;
 }
 
@@ -71,7 +86,8 @@ struct FrameBatch {
   std::vector<ResizeFrameYuv> yuv;
   int max_w = 1;
   int sample_bytes = 1;       // of a YUV batch: one launch is one instantiation, so all its frames have one sample width
-  Yfv2FrameKind kind() const { return yuv.empty() ? YFV2_FRAMES_BGR : sample_bytes == 2 ? YFV2_FRAMES_YUV16 : YFV2_FRAMES_YUV8; }
+  bool general = false;       // of a 1-byte YUV batch: a frame of it is not 4:2:0, so the launch is the general kind's (a property of the whole batch)
+  Yfv2FrameKind kind() const { return yuv.empty() ? YFV2_FRAMES_BGR : sample_bytes == 2 ? YFV2_FRAMES_YUV16 : general ? YFV2_FRAMES_YUV8_ANY : YFV2_FRAMES_YUV8; }
 };
 
 // ---- the two kinds: only what differs.  check = one caller frame (a whole frame of a tiled call too); expand = frame b of the
@@ -79,6 +95,7 @@ struct FrameBatch {
 struct BgrFrames {
   using Frame = yfv2_frame;
   static Yfv2FrameKind kind(const Frame&) { return YFV2_FRAMES_BGR; }
+  static bool general(const Frame*, int32_t) { return false; }
   static int check(yfv2_handle h, const std::string& at, const Frame& f) { return check_frame(h, at, f); }
   static int expand(yfv2_handle h, const std::string& at, const Frame& f, FrameBatch& fb, size_t b) {
     if (f.row_pitch > (1ll << 40) || (long long)(f.height - 1) * f.row_pitch > (1ll << 52))
@@ -92,7 +109,13 @@ struct BgrFrames {
 // (kernel: resize_frames_yuv_kernel, yfv2_pre.hip)  The descriptor has the origin folded into the plane pointers.
 struct YuvFrames {
   using Frame = yfv2_frame_yuv;
-  static Yfv2FrameKind kind(const Frame& f) { return yfv2_yuv_sample_bytes(f.format) == 2 ? YFV2_FRAMES_YUV16 : YFV2_FRAMES_YUV8; }   // (of a checked frame)
+  static Yfv2FrameKind kind(const Frame& f) { return yfv2_yuv_sample_bytes(f.format) == 2 ? YFV2_FRAMES_YUV16 : YFV2_FRAMES_YUV8; }   // (of a checked frame) by sample width
+  // whether a batch of 1-byte frames needs the general launch: one of its formats is an 8-bit one that is not 4:2:0 (YFV2_YUV_I422 .. _GREY)
+  static bool general(const Frame* frames, int32_t B) {
+    for (int32_t b = 0; b < B; ++b)
+      if (frames[b].format >= YFV2_YUV_I422 && frames[b].format <= YFV2_YUV_GREY) return true;
+    return false;
+  }
   static int check(yfv2_handle h, const std::string& at, const Frame& f) { return check_frame_yuv(h, at, f); }
   static int expand(yfv2_handle, const std::string&, const Frame& f, FrameBatch& fb, size_t b) {
     if (fb.yuv.empty()) fb.yuv.assign(fb.t.size(), ResizeFrameYuv{});
@@ -100,6 +123,9 @@ struct YuvFrames {
     fb.sample_bytes = yfv2_yuv_sample_bytes(f.format);
     r.y = f.y; r.ca = f.u; r.cb = yfv2_yuv_planar(f.format) ? f.v : nullptr;      // the planes at their own origin ...
     r.pitch_y = f.pitch_y; r.pitch_c = f.pitch_c; r.h = f.height; r.w = f.width;
+    if (yfv2_yuv_packed(f.format)) {              // the one plane is both: y the luma byte of pixel (0, 0), ca the U byte of its macropixel
+      r.y = f.y + (f.format == YFV2_YUV_UYVY ? 1 : 0); r.ca = f.y + (f.format == YFV2_YUV_YUYV ? 1 : 0); r.pitch_c = f.pitch_y;
+    } else if (yfv2_yuv_grey(f.format)) { r.ca = nullptr; r.pitch_c = 0; }
     r.px = 0; r.py = 0; r.format = f.format; r.coef = yfv2_yuv_coef(f.colour, fb.sample_bytes);
     yfv2_yuv_move(r, f.x0, f.y0);                                                 // ... moved to the frame's (the fold, yfv2_internal.h)
     r.scale_x = fb.t[b].scale_x; r.scale_y = fb.t[b].scale_y;
@@ -124,18 +150,31 @@ static int check_frames(yfv2_handle h, const char* what, const typename Kind::Fr
   if (B < 1) return fail(h, YFV2_ERR_ARG, w_ + ": B < 1");
   if (B > h->cfg.max_batch)
     return fail(h, YFV2_ERR_BATCH, w_ + ": batch " + std::to_string(B) + " above max_batch=" + std::to_string(h->cfg.max_batch));
-  Yfv2FrameKind kind = YFV2_FRAMES_BGR;      // of frame 0, once it is checked; the width limit is that kind's
-  int limit = 0;
+  Yfv2FrameKind kind = YFV2_FRAMES_BGR;      // the sample width's, of frame 0, once it is checked
+  // The launch's kind is a property of the WHOLE batch, decided here, before any width is checked: one frame that is not 4:2:0 makes
+  // a 1-byte batch the general kind's, whose width limit then binds every frame of the call (a frame of an unknown format is refused
+  // by its own check below).
+  const bool general = Kind::general(frames, B);
+  int limit = 0, limit420 = 0;
   fb.t.assign((size_t)B, ResizeFrame{});
   for (int32_t b = 0; b < B; ++b) {
     const typename Kind::Frame& f = frames[b];
     const std::string at = w_ + ": frame " + std::to_string(b) + ": ";
     if (int rc = Kind::check(h, at, f)) return rc;
-    if (b == 0) { kind = Kind::kind(f); limit = yfv2_rows_max_width(rows, kind, W); }
+    if (b == 0) {
+      kind = Kind::kind(f);
+      fb.general = general && kind == YFV2_FRAMES_YUV8;
+      limit = yfv2_rows_max_width(rows, fb.general ? YFV2_FRAMES_YUV8_ANY : kind, W);
+      if (fb.general) limit420 = yfv2_rows_max_width(rows, YFV2_FRAMES_YUV8, W);
+    }
     if (Kind::kind(f) != kind)
       return fail(h, YFV2_ERR_ARG, at + "format has " + (kind == YFV2_FRAMES_YUV16 ? "one-byte samples, frame 0 two-byte" : "two-byte samples, frame 0 one-byte") +
                                        " samples: the frames of one call must have one sample width");
-    if (f.width > limit) return fail(h, YFV2_ERR_ARG, at + "frames wider than " + std::to_string(limit) + " pixels are not supported");
+    if (f.width > limit)
+      return fail(h, YFV2_ERR_ARG, at + "frames wider than " + std::to_string(limit) + " pixels are not supported" +
+                                       (fb.general ? " in a call with a frame that is not 4:2:0: its one launch holds three full-width rows per source row in LDS (a call of NV12, NV21 and I420 frames alone admits " +
+                                                         std::to_string(limit420) + ")"
+                                                   : std::string()));
     const FrameScales s = frame_scales(f.width, f.height, W, H);
     ResizeFrame& r = fb.t[(size_t)b];
     r.h = f.height; r.w = f.width; r.scale_x = s.scale_x; r.scale_y = s.scale_y; r.box_x = s.box_x; r.box_y = s.box_y;

@@ -342,6 +342,8 @@ enum Yfv2FrameKind {       // what a frame's samples are
   YFV2_FRAMES_BGR,         // packed B, G, R bytes (yfv2_frame)
   YFV2_FRAMES_YUV8,        // yfv2_frame_yuv, 1-byte samples: NV12, NV21, I420
   YFV2_FRAMES_YUV16,       // yfv2_frame_yuv, 2-byte samples: P010, I010 (the descriptors are the 1-byte kind's, byte for byte)
+  YFV2_FRAMES_YUV8_ANY,    // yfv2_frame_yuv, 1-byte samples of ANY sampling: the three above and I422, I440, I444, YUYV, UYVY, GREY - the kind of a
+                           // batch with at least one frame that is not 4:2:0 (the same descriptors again)
 };
 enum Yfv2RowKind {         // descriptor (B, G, R / YUV)            dst
   YFV2_ROWS_U8,            // ResizeFrame / ResizeFrameYuv          uint8 (n, H, W, 3), 4-byte aligned
@@ -355,8 +357,8 @@ constexpr int YFV2_ROW_KINDS = 5;
 void yfv2_launch_rows(Yfv2RowKind kind, Yfv2FrameKind frames, const void* table, int n, int max_w, void* dst, int H, int W, hipStream_t s);
 size_t yfv2_rows_lds_bytes(Yfv2RowKind kind, Yfv2FrameKind frames, int w, int W);   // LDS of one workgroup for a frame w pixels wide, output rows of W
 // The widest frame the entry points of the kind admit.  B, G, R: (YFV2_LDS_FULL - the row's own bytes) / 6 - (ALIGN + 2) / 3, every
-// row up to it fits; YUV, either sample width: the widest frame that fits.  A 16-byte kind never admits a frame that the uint8 kinds
-// refuse at the same W, and 2-byte samples never one that 1-byte samples refuse.
+// row up to it fits; YUV, every kind: the widest frame that fits.  A 16-byte kind never admits a frame that the uint8 kinds
+// refuse at the same W, and neither 2-byte samples nor the general 1-byte kind one that the 4:2:0 1-byte kind refuses.
 int yfv2_rows_max_width(Yfv2RowKind kind, Yfv2FrameKind frames, int W);
 // one frame of a ragged batch (yfv2_resize_frames_u8 / yfv2_detect_frames_u8), expanded on the host and uploaded as a table
 struct ResizeFrame {
@@ -373,29 +375,45 @@ struct ResizeFrame {
 // to a byte offset, the planes are 2-byte aligned and the pitches even, and the coefficients are the 10-bit table's.
 struct YuvCoef { int off, cy, cvr, cvg, cug, cub; };   // one row of a colour table (yfv2_pre.hip)
 __host__ __device__ constexpr int yfv2_yuv_sample_bytes(int format) { return (format & 16) ? 2 : 1; }
-__host__ __device__ constexpr bool yfv2_yuv_planar(int format) { return format == 2 || format == 17; }   // YFV2_YUV_I420, YFV2_YUV_I010 (include/yfv2.h)
+// What a format is (include/yfv2.h YFV2_YUV_*): planar = U and V in planes of their own (I420, I422, I440, I444, I010); packed = one
+// plane of 4-byte macropixels (YUYV: Y0 U Y1 V, UYVY: U Y0 V Y1); grey = luma only; and the chroma shifts - pixel (R, C) takes the
+// chroma sample (R >> sy, C >> sx).  The five 4:2:0 formats have sx = sy = 1.
+__host__ __device__ constexpr bool yfv2_yuv_planar(int format) { return format == 2 || format == 17 || (format >= 3 && format <= 5); }
+__host__ __device__ constexpr bool yfv2_yuv_packed(int format) { return format == 6 || format == 7; }
+__host__ __device__ constexpr bool yfv2_yuv_grey(int format) { return format == 8; }
+__host__ __device__ constexpr int yfv2_yuv_shift_x(int format) { return format == 4 || format == 5 || format == 8 ? 0 : 1; }
+__host__ __device__ constexpr int yfv2_yuv_shift_y(int format) { return format == 3 || (format >= 5 && format <= 8) ? 0 : 1; }
+__host__ __device__ constexpr bool yfv2_yuv_is420(int format) { return yfv2_yuv_shift_x(format) == 1 && yfv2_yuv_shift_y(format) == 1; }
 struct ResizeFrameYuv {
   const unsigned char* y;     // luma of pixel (0, 0): plane + y0 * pitch_y + x0 (any alignment), device
   const unsigned char* ca;    // NV12 / NV21 / P010: the interleaved plane at chroma row y0 >> 1, sample pair x0 >> 1; I420 / I010: the U plane at (y0 >> 1, x0 >> 1)
   const unsigned char* cb;    // I420 / I010: the V plane likewise; NV12 / NV21 / P010: null
   long long pitch_y, pitch_c; // bytes from one row to the next
   int h, w;
-  int px, py;                 // x0 & 1, y0 & 1: the parity of the origin decides which pixels share a chroma sample
+  // (the other 8-bit samplings, yfv2_yuv_move: I422 / I440 / I444 as I420 with their own shifts; YUYV / UYVY: y the luma byte of pixel
+  // (0, 0), ca the U byte of its macropixel, cb null, pitch_c = pitch_y; GREY: ca and cb null)
+  int px, py;                 // x0 & 1, y0 & 1 on a subsampled axis (0 on any other): the parity of the origin decides which pixels share a chroma sample
   int format;                 // YFV2_YUV_*
   YuvCoef coef;               // the colour standard's row, copied in by the host: the kernel does not wait for a second, dependent load
   double scale_x, scale_y;    // resize: 1 / (W / w), 1 / (H / h), as ResizeArgs
 };
 // THE FOLD of an origin into the plane pointers, written once for the host (a caller's x0, y0; a tile's) and the device (a crop's
 // rectangle, yfv2_crops.hip): the descriptor's pixel (dy, dx) becomes its pixel (0, 0).  h and w stay the caller's to set.
+// By format: a pixel is sb bytes of luma (2 in a packed plane); a chroma sample is (dx + px) >> sx columns and (dy + py) >> sy rows
+// away, a column being sb bytes of a planar plane, 2 sb of an interleaved one and 4 of a packed one; a parity is kept only on an
+// axis that is subsampled; GREY has no chroma to move.  A PACKED frame's one plane is both: y is the luma byte of pixel (0, 0), ca
+// the U byte of the macropixel that holds it, pitch_c = pitch_y.  For the five 4:2:0 formats every result is what it was.
 __host__ __device__ inline void yfv2_yuv_move(ResizeFrameYuv& r, int dx, int dy) {
   const bool planar = r.cb != nullptr;
-  const int cx = (dx + r.px) >> 1, cy = (dy + r.py) >> 1;      // chroma sample / row of the new origin, from the old one's
+  const int sx = yfv2_yuv_shift_x(r.format), sy = yfv2_yuv_shift_y(r.format);
+  const int cx = (dx + r.px) >> sx, cy = (dy + r.py) >> sy;  // chroma sample / row of the new origin, from the old one's
   const int sb = yfv2_yuv_sample_bytes(r.format);            // an offset in samples is sb times that in bytes
-  const long long coff = (long long)cy * r.pitch_c + (long long)cx * ((planar ? 1 : 2) * sb);
-  r.y += (long long)dy * r.pitch_y + (long long)dx * sb;
-  r.ca += coff;
+  const bool packed = yfv2_yuv_packed(r.format);
+  const long long coff = (long long)cy * r.pitch_c + (long long)cx * (packed ? 4 : (planar ? 1 : 2) * sb);
+  r.y += (long long)dy * r.pitch_y + (long long)dx * (packed ? 2 : sb);
+  if (!yfv2_yuv_grey(r.format)) r.ca += coff;
   if (planar) r.cb += coff;
-  r.px = (dx + r.px) & 1; r.py = (dy + r.py) & 1;
+  r.px = sx ? (dx + r.px) & 1 : 0; r.py = sy ? (dy + r.py) & 1 : 0;
 }
 // The resize scale of one axis, `in` source pixels to `out`: cv::resize's inv_scale = dsize / ssize, scale = 1 / inv_scale, two
 // correctly rounded fp64 divisions on either side (no unit that calls it has a fast-math flag).
@@ -409,6 +427,9 @@ struct TrainFrameYuv : ResizeFrameYuv { float alpha, beta; };
 // The descriptors of the 2-byte instantiations of resize_frames_yuv_kernel: the layouts above, the sample width in the TYPE, so that
 // the 1-byte instantiations keep their names and their instruction streams.  The host and the crop plan write the 1-byte types.
 template <class D> struct Samples16 : D { static constexpr int SAMPLE_BYTES = 2; };
+// ... and of the GENERAL 1-byte instantiations (YFV2_FRAMES_YUV8_ANY), which read every 8-bit format: the same layouts again, and in
+// the type the fact that the sampling is not known to be 4:2:0 - the kernel derives it from the format, uniformly over a workgroup.
+template <class D> struct AnySampling : D { static constexpr bool ANY_SAMPLING = true; };
 // ---- second-stage crops (yfv2_crop_detections_u8 / _yuv; kernels: yfv2_crops.hip, the resize launch: yfv2_launch_rows)
 // THE RECTANGLE RULE, one axis of it, written once: yfv2_crop_rect (host) and the plan kernels (device) both call this function;
 // include/yfv2.h states it for callers, tests/crops_model.py in Python.  a1, a2: the box's two edges on the axis; pad: the factor;

@@ -14,7 +14,7 @@
 // Built with -ffp-contract=off: the coefficient arithmetic must round like the separate C operations it restates.
 //
 // The ragged-batch kernels are two templates over <Frame, Row> - the descriptor (B, G, R or YUV; plain, counted, with an augmentation
-// pair, letterboxed) and where the blended row goes (uint8 batch, fp32 training batch, fp32 / fp16 tensor) - in ten instantiations, and five more of the YUV template for 2-byte samples (P010, I010).
+// pair, letterboxed) and where the blended row goes (uint8 batch, fp32 training batch, fp32 / fp16 tensor) - in ten instantiations, five more of the YUV template for 2-byte samples (P010, I010) and five for the general 1-byte kind (any 8-bit sampling).
 // Each output kind is described ONCE: the Row states its ALIGN and its own LDS bytes, yfv2_slot places the staging slots for kernel and
 // host alike, FrameRows<Frame> gives the launch's LDS and the width limit of the frame kind, launch_rows<Frame, Row> is the one launch
 // body.  Other units reach the family through Yfv2RowKind, Yfv2FrameKind and yfv2_launch_rows / yfv2_rows_lds_bytes / yfv2_rows_max_width
@@ -409,6 +409,12 @@ constexpr int yfv2_sample_bytes() {
   if constexpr (requires { Frame::SAMPLE_BYTES; }) return Frame::SAMPLE_BYTES;
   else return 1;
 }
+// Whether a YUV descriptor type is of the general 1-byte kind, AnySampling<...> (yfv2_internal.h): any 8-bit format, not 4:2:0 only.
+template <class Frame>
+constexpr bool yfv2_any_sampling() {
+  if constexpr (requires { Frame::ANY_SAMPLING; }) return true;
+  else return false;
+}
 // THE VALUE OF A WORD, the two rules of the 2-byte formats: P010 carries its 10 bits in the high bits (word >> 6; the low 6 are
 // ignored), I010 in the low bits (word & 1023; the high 6 are ignored).  shift = 6 / 0 is uniform over a workgroup.
 __device__ __forceinline__ int yfv2_sample10(const unsigned short* p, int i, int shift) { return ((int)p[i] >> shift) & 1023; }
@@ -441,6 +447,21 @@ __device__ __forceinline__ int yfv2_sample10(const unsigned short* p, int i, int
 // still fit the registers, and no instantiation spills to scratch.  By LDS a 1920-wide frame takes 2 * 3844 + 4 * 1928 + 1056 =
 // 16456 bytes: 9 workgroups per CU (18 of its 32 waves) where the byte kernel reaches its 16 - at 1080p this kernel is LDS-bound, at
 // 1280 wide it has 14, from 640 wide down the 16 of the launch bound again.
+// ANY 8-BIT SAMPLING (YFV2_YUV_I422 / _I440 / _I444 / _YUYV / _UYVY / _GREY beside the three 4:2:0 formats): the
+// descriptor type AnySampling<D> makes ANY true, and the same body takes the sampling from f.format - the chroma shifts sx, sy
+// (pixel (r, c): chroma row (r + py) >> sy, sample (c + px) >> sx; with sy = 0 the two chroma rows coincide exactly when the two luma
+// rows do), packed or not, grey or not - all uniform over the workgroup.  What is staged per blended source row: planar and
+// interleaved formats the luma row and the chroma row(s) of the format's own width, as above; a PACKED row once, as chroma segment
+// a, from the macropixel of pixel 0 to that of pixel w - 1 (4 cw bytes; luma, U and V are then three taps into it, luma at stride
+// 2, chroma at stride 4), with no luma segment; GREY the luma row alone, U = V = 128 being one dword the workgroup writes into the
+// free U slot and reads at chroma stride 0.  The guard is the one above, per plane; a packed plane's extent runs from the first to
+// the last macropixel of the rectangle.  The LDS layout is the general kind's own (FrameRows below): six slots of yfv2_slot(w), about
+// 6 bytes per source pixel like the B, G, R kernel.  A 4:2:0 frame in such a launch goes through the same arithmetic on the same
+// bytes as in a 4:2:0-only launch: the same bits.  For a descriptor that is not AnySampling<...> every ANY term is a constant
+// (sx = sy = 1, packed = grey = false) and the fifteen other instantiations are the instruction streams they were
+// (profiles/yuv_any_isa.txt).  Same launch bound: <AnySampling<ResizeFrameYuv>, RowU8> needs 60 VGPRs (the counted twin 59, training
+// 42, the tensors 44 / 42), no instantiation uses scratch.  By LDS a 1920-wide frame takes 6 * 1924 + 1056 = 12600 bytes: 13
+// workgroups per CU (26 of its 32 waves), the 16 of the launch bound from 1525 wide down.
 constexpr int RY_THREADS = 128;
 template <class Frame, class Row>
 __global__ __launch_bounds__(RY_THREADS, 8) void resize_frames_yuv_kernel(const Frame* __restrict__ frames, typename Row::Out* __restrict__ dst, int H, int W) {
@@ -458,17 +479,22 @@ __global__ __launch_bounds__(RY_THREADS, 8) void resize_frames_yuv_kernel(const 
   }
   const RowCoef ry = yfv2_axis_coef(iy, f.scale_y, f.h, false);
   constexpr int SB = yfv2_sample_bytes<Frame>();          // bytes of a sample: everything counted in bytes below carries it
-  const bool planar = f.format == (SB == 1 ? YFV2_YUV_I420 : YFV2_YUV_I010);
-  const int cw = ((f.w - 1 + f.px) >> 1) + 1, ch = ((f.h - 1 + f.py) >> 1) + 1;   // chroma samples per row, chroma rows of the frame
-  const int cbytes = SB * (planar ? cw : 2 * cw);
-  const int cr0 = (ry.s0 + f.py) >> 1, cr1 = (ry.s1 + f.py) >> 1;
+  constexpr bool ANY = yfv2_any_sampling<Frame>();        // the general kind: the sampling comes from f.format, uniform over the workgroup
+  const bool packed = ANY && yfv2_yuv_packed(f.format), grey = ANY && yfv2_yuv_grey(f.format);
+  const bool planar = ANY ? yfv2_yuv_planar(f.format) : f.format == (SB == 1 ? YFV2_YUV_I420 : YFV2_YUV_I010);
+  const int sx = ANY ? yfv2_yuv_shift_x(f.format) : 1, sy = ANY ? yfv2_yuv_shift_y(f.format) : 1;   // pixel (r, c): chroma (r >> sy, c >> sx)
+  const int cw = ((f.w - 1 + f.px) >> sx) + 1, ch = ((f.h - 1 + f.py) >> sy) + 1;   // chroma samples per row, chroma rows of the frame
+  const int cbytes = grey ? 0 : packed ? 4 * cw : SB * (planar ? cw : 2 * cw);      // (packed: the macropixels of the row, luma and all)
+  const int cr0 = (ry.s0 + f.py) >> sy, cr1 = (ry.s1 + f.py) >> sy;
   const bool one_chroma_row = cr0 == cr1;
-  const int yslot = yfv2_slot(SB * f.w, Row::ALIGN), chalf = yfv2_slot(SB * ((f.w >> 1) + 1), Row::ALIGN);
+  // 4:2:0 kinds: [luma 0][luma 1][chroma 0: two half-slots][chroma 1: likewise].  The general kind: six slots of yfv2_slot(w), a group
+  // of three per blended row, [luma][U][V] - an interleaved row lies over U and V, a packed row over all three (FrameRows below).
+  const int yslot = yfv2_slot(SB * f.w, Row::ALIGN), chalf = ANY ? yslot : yfv2_slot(SB * ((f.w >> 1) + 1), Row::ALIGN);
   unsigned char* LY0 = smem;
-  unsigned char* LY1 = smem + yslot;
-  unsigned char* LC0 = smem + 2 * yslot;
-  unsigned char* LC1 = LC0 + 2 * chalf;
-  unsigned char* OUT = LC0 + 4 * chalf;
+  unsigned char* LY1 = smem + (ANY ? 3 : 1) * yslot;
+  unsigned char* LC0 = ANY ? smem + (packed ? 0 : yslot) : smem + 2 * yslot;
+  unsigned char* LC1 = ANY ? LC0 + 3 * yslot : LC0 + 2 * chalf;
+  unsigned char* OUT = ANY ? smem + 6 * yslot : LC0 + 4 * chalf;
   if constexpr (Row::AUGMENT) row.begin(OUT, f.alpha, f.beta);
   const long long extent_y = (long long)(f.h - 1) * f.pitch_y + SB * f.w;
   const long long extent_c = (long long)(ch - 1) * f.pitch_c + cbytes;
@@ -476,7 +502,10 @@ __global__ __launch_bounds__(RY_THREADS, 8) void resize_frames_yuv_kernel(const 
   // staged (the second chroma row when it is the first, plane b of an interleaved format) has no dwords.  Everything about a segment
   // is wave-uniform, the guard included once it is counted in bytes from the segment's dword 0 (sptr, 4-byte aligned): the bytes
   // [blo, bhi) of that stream lie in the plane's extent, so dword i is loaded whole iff blo <= 4 i and 4 i + 4 <= bhi.
-  const unsigned char* sbase[6] = {f.y, f.y, f.ca, f.ca, f.cb, f.cb};
+  // A packed plane is staged as the chroma segments a, from the macropixel of pixel 0 (f.ca is its U byte: byte 1 of a YUYV, byte 0
+  // of a UYVY macropixel) to that of pixel w - 1; it has no luma segments.  GREY has no chroma segments.
+  const int uoff = packed && f.format == YFV2_YUV_YUYV ? 1 : 0;
+  const unsigned char* sbase[6] = {f.y, f.y, f.ca - uoff, f.ca - uoff, f.cb, f.cb};
   unsigned char* slds[6] = {LY0, LY1, LC0, LC1, LC0 + chalf, LC1 + chalf};
   const unsigned char* sptr[6];
   int smis[6], snd[6], sblo[6], sbhi[6];
@@ -484,7 +513,7 @@ __global__ __launch_bounds__(RY_THREADS, 8) void resize_frames_yuv_kernel(const 
 #pragma unroll
   for (int k = 0; k < 6; ++k) {
     const long long g = k < 2 ? (long long)(k == 0 ? ry.s0 : ry.s1) * f.pitch_y : (long long)((k & 1) ? cr1 : cr0) * f.pitch_c;
-    const int n = k < 2 ? SB * f.w : (((k & 1) && one_chroma_row) || (k >= 4 && !planar) ? 0 : cbytes);
+    const int n = k < 2 ? (packed ? 0 : SB * f.w) : (((k & 1) && one_chroma_row) || (k >= 4 && !planar) ? 0 : cbytes);
     smis[k] = (int)((reinterpret_cast<uintptr_t>(sbase[k]) + g) & 3);
     const long long first = g - smis[k];                  // offset of the segment's dword 0 from its plane's base
     sptr[k] = sbase[k] + first;
@@ -525,18 +554,20 @@ __global__ __launch_bounds__(RY_THREADS, 8) void resize_frames_yuv_kernel(const 
         *reinterpret_cast<unsigned*>(slds[k] + o) = e;
       }
     }
+  if constexpr (ANY)
+    if (grey && tid == 0) *reinterpret_cast<unsigned*>(LC0) = 0x80808080u;   // U = V = 128, the one chroma sample of a GREY frame (cstep 0)
   __syncthreads();
   // U and V of chroma sample j of blended row 0 / 1: pu[j * cstep], pv[j * cstep]
-  const int cstep = planar ? 1 : 2;
+  const int cstep = grey ? 0 : packed ? 4 : planar ? 1 : 2;
   const YuvCoef kc = f.coef;
   // Taps: sample s of a staged row is its byte s (1-byte samples) or its 16-bit word s, of which yfv2_sample10 takes the value - a
   // slot is 4-byte aligned and a 2-byte plane's misalignment is 0 or 2, so every word is aligned.  Everything else is one body.
   using Sample = std::conditional_t<SB == 1, unsigned char, unsigned short>;
   const int vshift = planar ? 0 : 6;                       // (2-byte samples only)
   auto at = [&](const unsigned char* lds, int mis) { return reinterpret_cast<const Sample*>(lds + mis); };
-  const Sample* a0 = at(LC0, smis[2]);
+  const Sample* a0 = at(LC0, grey ? 0 : smis[2]);
   const Sample* a1 = one_chroma_row ? a0 : at(LC1, smis[3]);
-  const Sample* b0 = planar ? at(LC0 + chalf, smis[4]) : a0 + 1;
+  const Sample* b0 = planar ? at(LC0 + chalf, smis[4]) : a0 + 1;      // (ANY: LC0 + chalf, the V slot of the row's group)
   const Sample* b1 = planar ? (one_chroma_row ? b0 : at(LC1 + chalf, smis[5])) : a1 + 1;
   const bool swapped = SB == 1 && f.format == YFV2_YUV_NV21;
   const Sample* pu0 = swapped ? b0 : a0;
@@ -545,8 +576,17 @@ __global__ __launch_bounds__(RY_THREADS, 8) void resize_frames_yuv_kernel(const 
   const Sample* pv1 = swapped ? a1 : b1;
   const Sample* y0 = at(LY0, smis[0]);
   const Sample* y1 = at(LY1, smis[1]);
+  if constexpr (ANY) {
+    if (packed) {             // a0 / a1: byte 0 of the row's first macropixel.  U at uoff, V two bytes on; luma of pixel s at 2 (s + px) + 1 - uoff
+      pu0 = a0 + uoff; pv0 = pu0 + 2; pu1 = a1 + uoff; pv1 = pu1 + 2;
+      y0 = a0 + 2 * f.px + 1 - uoff; y1 = a1 + 2 * f.px + 1 - uoff;
+    }
+    if (grey) { pv0 = pu0; pu1 = pu0; pv1 = pu0; }
+  }
+  const int ysh = packed ? 1 : 0;                          // luma of pixel s: y[s << ysh]
   auto tap = [&](const Sample* y, const Sample* pu, const Sample* pv, int s, int j, int (&p)[3]) {
-    if constexpr (SB == 1) yfv2_yuv_to_bgr(y[s], pu[j], pv[j], kc, p);
+    if constexpr (ANY) yfv2_yuv_to_bgr(y[s << ysh], pu[j], pv[j], kc, p);
+    else if constexpr (SB == 1) yfv2_yuv_to_bgr(y[s], pu[j], pv[j], kc, p);
     else yfv2_yuv16_to_bgr(yfv2_sample10(y, s, vshift), yfv2_sample10(pu, j, vshift), yfv2_sample10(pv, j, vshift), kc, p);
   };
   for (int ox = tid; ox < W; ox += RY_THREADS) {
@@ -556,7 +596,8 @@ __global__ __launch_bounds__(RY_THREADS, 8) void resize_frames_yuv_kernel(const 
       if (ix < 0 || ix >= f.iw) { row.put_fill(OUT, ox, W); continue; }
     }
     const RowCoef rx = yfv2_axis_coef(ix, f.scale_x, f.w, true);
-    const int j0 = ((rx.s0 + f.px) >> 1) * cstep, j1 = ((rx.s1 + f.px) >> 1) * cstep;
+    const int j0 = ANY ? __mul24((rx.s0 + f.px) >> sx, cstep) : ((rx.s0 + f.px) >> 1) * cstep;
+    const int j1 = ANY ? __mul24((rx.s1 + f.px) >> sx, cstep) : ((rx.s1 + f.px) >> 1) * cstep;
     int p00[3], p01[3], p10[3], p11[3];      // B, G, R of the taps (row s0 / s1, column sx0 / sx1)
     tap(y0, pu0, pv0, rx.s0, j0, p00);
     tap(y0, pu0, pv0, rx.s1, j1, p01);
@@ -587,14 +628,20 @@ template <class Frame>
 struct FrameRows<Frame, true> {   // YUV: two luma slots, two chroma rows of two half-slots each, of SB-byte samples
   static constexpr int THREADS = RY_THREADS;
   static constexpr int SB = yfv2_sample_bytes<Frame>();
+  static constexpr bool ANY = yfv2_any_sampling<Frame>();
+  static constexpr int PER_PIXEL = ANY ? 6 : 4 * SB;      // staged bytes per source pixel, about
   template <class Row> static constexpr auto& kernel = resize_frames_yuv_kernel<Frame, Row>;
+  // The general kind (AnySampling<...>): SIX slots of yfv2_slot(w), a group of three per blended row - [luma][U][V], each a full-width
+  // row of a 4:4:4 frame at any misalignment; an interleaved chroma row (at most w + 2 bytes) lies over U and V, a packed row (the
+  // macropixels of the row, at most 2 w + 4 bytes, at any misalignment at most 2 w + 8 staged) over all three: 3 (w + 3) >= 2 w + 8.
   template <class Row> static size_t lds_bytes(int w, int W) {
-    return 2 * (size_t)yfv2_slot(SB * w, Row::ALIGN) + 4 * (size_t)yfv2_slot(SB * ((w >> 1) + 1), Row::ALIGN) + (size_t)Row::lds_bytes(W);
+    if constexpr (ANY) return 6 * (size_t)yfv2_slot(w, Row::ALIGN) + (size_t)Row::lds_bytes(W);
+    else return 2 * (size_t)yfv2_slot(SB * w, Row::ALIGN) + 4 * (size_t)yfv2_slot(SB * ((w >> 1) + 1), Row::ALIGN) + (size_t)Row::lds_bytes(W);
   }
-  // The exact maximum: the function above grows by about 4 SB bytes per pixel and never falls, so the answer is next to
-  // (YFV2_LDS_FULL - the Row's bytes) / (4 SB) and two short walks find it.
+  // The exact maximum: the function above grows by about PER_PIXEL bytes per pixel and never falls, so the answer is next to
+  // (YFV2_LDS_FULL - the Row's bytes) / PER_PIXEL and two short walks find it.
   template <class Row> static int max_width(int W) {
-    int w = (int)std::max<long long>(1, ((long long)YFV2_LDS_FULL - Row::lds_bytes(W)) / (4 * SB));
+    int w = (int)std::max<long long>(1, ((long long)YFV2_LDS_FULL - Row::lds_bytes(W)) / PER_PIXEL);
     while (w > 1 && lds_bytes<Row>(w, W) > (size_t)YFV2_LDS_FULL) --w;
     while (lds_bytes<Row>(w + 1, W) <= (size_t)YFV2_LDS_FULL) ++w;
     return w;
@@ -610,9 +657,9 @@ static void launch_rows(const void* table, int n, int max_w, void* dst, int H, i
                   static_cast<const Frame*>(table), static_cast<typename Row::Out*>(dst), H, W);
 }
 
-// What the other units see of the family: a row kind, a frame kind, three functions.  THE TABLE of the fifteen instantiations: f is
+// What the other units see of the family: a row kind, a frame kind, three functions.  THE TABLE of the twenty instantiations: f is
 // called as f.operator()<Frame, Row>().  (The device compiler emits the kernels in the order they are named here - training first,
-// the tensors by frame kind, within a row kind B, G, R, then 1-byte, then 2-byte YUV.)
+// the tensors by frame kind, within a row kind B, G, R, then 1-byte 4:2:0, then 2-byte, then general 1-byte YUV.)
 template <class Fn>
 static auto with_rows(Yfv2RowKind kind, Yfv2FrameKind frames, Fn f) {
   using U8 = RowU8<RF_THREADS>;                 using U8Y = RowU8<RY_THREADS>;
@@ -620,11 +667,13 @@ static auto with_rows(Yfv2RowKind kind, Yfv2FrameKind frames, Fn f) {
   using F32 = RowTensor<RF_THREADS, false>;     using F32Y = RowTensor<RY_THREADS, false>;
   using F16 = RowTensor<RF_THREADS, true>;      using F16Y = RowTensor<RY_THREADS, true>;
   const bool half = kind == YFV2_ROWS_TENSOR_F16;
-  // one row kind: its B, G, R descriptor and Row, its YUV descriptor (1-byte samples; Samples16<...> of it for 2-byte) and Row
+  // one row kind: its B, G, R descriptor and Row, its YUV descriptor (1-byte 4:2:0; Samples16<...> of it for 2-byte samples,
+  // AnySampling<...> of it for the general 1-byte kind) and Row
   auto pick = [&]<class Bgr, class RowBgr, class Yuv, class RowYuv>() {
     if (frames == YFV2_FRAMES_BGR) return f.template operator()<Bgr, RowBgr>();
     if (frames == YFV2_FRAMES_YUV8) return f.template operator()<Yuv, RowYuv>();
-    return f.template operator()<Samples16<Yuv>, RowYuv>();
+    if (frames == YFV2_FRAMES_YUV16) return f.template operator()<Samples16<Yuv>, RowYuv>();
+    return f.template operator()<AnySampling<Yuv>, RowYuv>();
   };
   switch (kind) {
     case YFV2_ROWS_TRAIN:      return pick.template operator()<TrainFrame, Train, TrainFrameYuv, TrainY>();

@@ -55,22 +55,27 @@ def collate_targets(labels):
     return torch.cat(out, 0) if out else torch.zeros((0, 6), dtype=torch.float32)
 
 
-def _train_rows(w, W, is_yuv, bits):
+def _train_rows(w, W, is_yuv, bits, general=False):
     if bits not in (8, 10) or (bits == 10 and not is_yuv):
         raise ValueError("bits must be 8, or 10 for YUV frames (\"p010\", \"i010\"), got %r" % (bits,))
+    if general:
+        if not is_yuv or bits != 8:
+            raise ValueError("general=True is the launch of 8-bit YUV frames of any sampling")
+        return yuv.rows_lds_any(yuv.ROWS_TRAIN, w, W)
     return yuv.rows_lds(yuv.ROWS_TRAIN, is_yuv, w, W) if bits == 8 else yuv.rows_lds16(yuv.ROWS_TRAIN, w, W)
 
 
-def train_batch_lds_bytes(w, W, is_yuv=False, bits=8):
+def train_batch_lds_bytes(w, W, is_yuv=False, bits=8, general=False):
     """LDS of one workgroup of the training-batch launch for a frame w pixels wide at network width W: the resize's staging slots
     rounded to 16 bytes, the table, three fp32 planes of W"""
-    return _train_rows(w, W, is_yuv, bits)[0]
+    return _train_rows(w, W, is_yuv, bits, general)[0]
 
 
-def max_frame_width(W, is_yuv=False, bits=8):
-    """the widest frame Engine.train_batch_frames (is_yuv: train_batch_frames_yuv; bits = 10: "p010" / "i010" frames) admits at
-    network width W; never above resize_frames' own limit"""
-    return _train_rows(1, W, is_yuv, bits)[1]
+def max_frame_width(W, is_yuv=False, bits=8, general=False):
+    """the widest frame Engine.train_batch_frames (is_yuv: train_batch_frames_yuv; bits = 10: "p010" / "i010" frames; general: a
+    batch with an 8-bit frame that is not 4:2:0 - a JPEG set's "i444", "i422", "i440", "yuyv", "uyvy", "grey" - whose limit binds
+    every frame of the batch) admits at network width W; never above resize_frames' own limit"""
+    return _train_rows(1, W, is_yuv, bits, general)[1]
 
 
 class TrainBatcher:

@@ -14,6 +14,13 @@ bits: what software decoders write).  Their planes are ``torch.int16`` tensors (
 shape (rows, samples) - uv also (rows, samples, 2) - with pitch ``2 * stride(0)``, or ``torch.uint8`` tensors holding the bytes,
 with pitch ``stride(0)``.  A frame of byte tensors must state its ``width`` and ``height``: a byte plane is also a valid 8-bit
 plane, so the rectangle is not guessed from it.  All frames of one call have one sample width.
+
+The other 8-bit samplings - what a JPEG decoder writes for a file that is not 4:2:0, and what capture devices
+deliver: "i444" = "yuv444p", "i422" = "yuv422p", "i440" = "yuv440p" take ``(y, u, v)``; "yuyv" = "yuy2" = "yuyv422", "uyvy" =
+"uyvy422" and "grey" = "gray" = "y800" take ONE plane, ``(p,)`` or the tensor itself.  A packed plane is a 2-D uint8 tensor of
+the bytes - two per pixel - or ``(rows, pixels, 2)``.  An alias picks the format only: the colour stays explicit ("jpeg" for
+JPEG files).  One call may mix every 8-bit format; a call with a frame that is not 4:2:0 has the general launch's lower width
+limit (``max_width(W, general=True)``) for all of its frames.
 """
 import ctypes as C
 
@@ -22,8 +29,14 @@ import torch
 from . import _lib
 
 FORMATS = {"nv12": 0, "nv21": 1, "i420": 2, 0: 0, 1: 1, 2: 2,
+           "i422": 3, "yuv422p": 3, "i440": 4, "yuv440p": 4, "i444": 5, "yuv444p": 5, 3: 3, 4: 4, 5: 5,
+           "yuyv": 6, "yuy2": 6, "yuyv422": 6, "uyvy": 7, "uyvy422": 7, "grey": 8, "gray": 8, "y800": 8, 6: 6, 7: 7, 8: 8,
            "p010": 16, "i010": 17, "yuv420p10le": 17, "yuv420p10": 17, 16: 16, 17: 17}      # bit 4: two-byte samples
-PLANAR = (2, 17)
+PLANAR = (2, 3, 4, 5, 17)
+PACKED = (6, 7)                # one plane of 4-byte macropixels: two bytes per pixel
+GREY = 8
+SHIFTS = {3: (1, 0), 4: (0, 1), 5: (0, 0), 6: (1, 0), 7: (1, 0), 8: (0, 0)}      # format -> chroma shift (x, y); every other format (1, 1)
+FORMAT_NAMES = {0: "nv12", 1: "nv21", 2: "i420", 3: "i422", 4: "i440", 5: "i444", 6: "yuyv", 7: "uyvy", 8: "grey", 16: "p010", 17: "i010"}
 WORD_DTYPES = tuple(getattr(torch, n) for n in ("int16", "uint16") if hasattr(torch, n))
 
 
@@ -60,27 +73,49 @@ def rows_lds16(kind, w, W):
     return lds.value, limit.value
 
 
-def max_width(W, bits=8):
-    """the widest YUV frame the resize admits at network width W: bits = 8 for NV12 / NV21 / I420, 10 for P010 / I010"""
+def rows_lds_any(kind, w, W):
+    """``rows_lds`` for the general one-byte launch: a call with a frame that is not 4:2:0 (include/yfv2.h yfv2_debug_rows_any)"""
+    lds, limit = C.c_int64(), C.c_int32()
+    if _lib.lib().yfv2_debug_rows_any(kind, w, W, C.byref(lds), C.byref(limit)) != _lib.OK:
+        raise ValueError("rows_lds_any(%r, %r, %r): %s" % (kind, w, W, _lib.last_error()))
+    return lds.value, limit.value
+
+
+def max_width(W, bits=8, general=False):
+    """the widest YUV frame the resize admits at network width W: bits = 8 for NV12 / NV21 / I420, 10 for P010 / I010;
+    general=True: in a call with at least one 8-bit frame that is not 4:2:0 (which binds every frame of that call)"""
     if bits not in (8, 10):
         raise ValueError("bits must be 8 or 10, got %r" % (bits,))
+    if general:
+        if bits != 8:
+            raise ValueError("the general launch reads 8-bit frames only")
+        return rows_lds_any(ROWS_U8, 1, W)[1]
     return rows_lds(ROWS_U8, True, 1, W)[1] if bits == 8 else rows_lds16(ROWS_U8, 1, W)[1]
 
 
 class YuvFrame:
-    """One YUV 4:2:0 frame: planes + format ("nv12", "nv21", "i420"; "p010", "i010" alias "yuv420p10le") + colour ("bt601", "bt709" - limited range - "bt601_full" alias
-    "jpeg", "bt709_full") and the rectangle of the planes that is the frame (default: all of the luma plane from (x0, y0) on)."""
-    __slots__ = ("planes", "format", "colour", "x0", "y0", "width", "height", "planar", "sample_bytes")
+    """One YUV frame: planes + format ("nv12", "nv21", "i420"; "p010", "i010" alias "yuv420p10le"; "i422", "i440", "i444", "yuyv",
+    "uyvy", "grey" and their pix_fmt aliases) + colour ("bt601", "bt709" - limited range - "bt601_full" alias
+    "jpeg", "bt709_full") and the rectangle of the planes that is the frame (default: all of the luma plane from (x0, y0) on; of a
+    packed plane: all of its pixels, bytes // 2)."""
+    __slots__ = ("planes", "format", "colour", "x0", "y0", "width", "height", "planar", "sample_bytes", "packed")
 
     def __init__(self, planes, format="nv12", colour="bt601", x0=0, y0=0, width=None, height=None):
-        self.planes = tuple(planes)
+        self.planes = (planes,) if torch.is_tensor(planes) else tuple(planes)
         if format not in FORMATS or isinstance(format, bool):
-            raise ValueError("format must be one of 'nv12', 'nv21', 'i420', 'p010', 'i010' ('yuv420p10le'), got %r" % (format,))
+            raise ValueError("format must be one of 'nv12', 'nv21', 'i420', 'p010', 'i010' ('yuv420p10le'), 'i422', 'i440', 'i444', 'yuyv', 'uyvy', 'grey', got %r" % (format,))
         if colour not in COLOURS or isinstance(colour, bool):
             raise ValueError("colour must be one of 'bt601', 'bt709', 'bt601_full' ('jpeg'), 'bt709_full', got %r" % (colour,))
         self.format, self.colour = FORMATS[format], COLOURS[colour]
-        self.planar, self.sample_bytes = self.format in PLANAR, sample_bytes(self.format)
+        self.planar, self.sample_bytes, self.packed = self.format in PLANAR, sample_bytes(self.format), self.format in PACKED
         self.x0, self.y0 = int(x0), int(y0)
+        if self.packed:
+            p = self.planes[0] if self.planes else None
+            if not torch.is_tensor(p) or not (p.dim() == 2 or (p.dim() == 3 and p.shape[2] == 2)):
+                raise ValueError("planes[0] must be the packed plane: 2-D bytes, or (rows, pixels, 2)")
+            self.width = (int(p.shape[1]) // 2 if p.dim() == 2 else int(p.shape[1])) - self.x0 if width is None else int(width)
+            self.height = int(p.shape[0]) - self.y0 if height is None else int(height)
+            return
         if not self.planes or not torch.is_tensor(self.planes[0]) or self.planes[0].dim() != 2:
             raise ValueError("planes[0] must be the 2-D luma plane")
         if self.sample_bytes == 2 and self.planes[0].dtype == torch.uint8 and (width is None or height is None):
@@ -98,7 +133,7 @@ class YuvFrame:
 
 
 def as_frame(f):
-    """YuvFrame, or a bare tuple of planes: (y, uv) is NV12, (y, u, v) I420, both BT.601 limited range"""
+    """YuvFrame, or a bare tuple of planes: (y, uv) is NV12, (y, u, v) I420, both BT.601 limited range (every other format: a YuvFrame)"""
     if isinstance(f, YuvFrame):
         return f
     if isinstance(f, (tuple, list)) and len(f) in (2, 3) and all(torch.is_tensor(p) for p in f):
@@ -110,12 +145,12 @@ def _plane(i, name, p, device, rows, row_bytes):
     """checks one plane against what the frame reads of it: `rows` rows of `row_bytes` bytes from its first byte -> pitch"""
     if not torch.is_tensor(p) or p.dtype != torch.uint8 or p.device != device:
         raise ValueError("frame %d: plane %s must be a uint8 tensor on %s" % (i, name, device))
-    if p.dim() == 3 and p.shape[2] == 2 and name == "uv" and (p.shape[1] <= 1 or p.stride(1) == 2) and p.stride(2) == 1:
+    if p.dim() == 3 and p.shape[2] == 2 and name in ("uv", "packed") and (p.shape[1] <= 1 or p.stride(1) == 2) and p.stride(2) == 1:
         have = 2 * int(p.shape[1])
     elif p.dim() == 2 and (p.shape[1] <= 1 or p.stride(1) == 1):
         have = int(p.shape[1])
     else:
-        raise ValueError("frame %d: plane %s must be 2-D with contiguous rows (uv may be (rows, samples, 2))" % (i, name))
+        raise ValueError("frame %d: plane %s must be 2-D with contiguous rows (uv may be (rows, samples, 2), a packed plane (rows, pixels, 2))" % (i, name))
     if p.shape[0] < rows or have < row_bytes:
         raise ValueError("frame %d: plane %s is %d rows x %d bytes, the frame reads %d x %d of it" % (i, name, p.shape[0], have, rows, row_bytes))
     return int(p.stride(0)) if p.shape[0] > 1 else max(have, 1)
@@ -152,21 +187,28 @@ def frame_table(frames, device):
         planar = f.planar
         if f.sample_bytes != sb:
             raise ValueError("frame %d: %d-byte samples in a call whose frame 0 has %d-byte samples: one sample width per call" % (i, f.sample_bytes, sb))
-        if len(f.planes) != (3 if planar else 2):
-            raise ValueError("frame %d: %s takes %d planes, got %d" % (i, "i420 / i010" if planar else "nv12 / nv21 / p010", 3 if planar else 2, len(f.planes)))
+        want = 3 if planar else 1 if (f.packed or f.format == GREY) else 2
+        if len(f.planes) != want:
+            raise ValueError("frame %d: %s takes %d plane%s, got %d" % (i, FORMAT_NAMES[f.format], want, "" if want == 1 else "s", len(f.planes)))
         if f.x0 < 0 or f.y0 < 0:
             raise ValueError("frame %d: x0 and y0 must be >= 0" % i)
         a = arr[i]
         a.x0, a.y0, a.width, a.height, a.format, a.colour = f.x0, f.y0, f.width, f.height, f.format, f.colour
+        sx, sy = SHIFTS.get(f.format, (1, 1))
         if f.width >= 1 and f.height >= 1:      # (a frame without pixels is the native check's to report)
-            crows, csamples = ((f.y0 + f.height - 1) >> 1) + 1, ((f.x0 + f.width - 1) >> 1) + 1
-            a.pitch_y = plane(i, "y", f.planes[0], device, f.y0 + f.height, f.x0 + f.width)
+            crows, csamples = ((f.y0 + f.height - 1) >> sy) + 1, ((f.x0 + f.width - 1) >> sx) + 1
+            if f.packed:                        # up to the last macropixel of the rectangle, whole
+                a.pitch_y = plane(i, "packed", f.planes[0], device, f.y0 + f.height, 4 * csamples)
+            else:
+                a.pitch_y = plane(i, "y", f.planes[0], device, f.y0 + f.height, f.x0 + f.width)
             if planar:
                 a.pitch_c = plane(i, "u", f.planes[1], device, crows, csamples)
                 if plane(i, "v", f.planes[2], device, crows, csamples) != a.pitch_c:
                     raise ValueError("frame %d: planes u and v must have the same row pitch" % i)
                 a.v = f.planes[2].data_ptr()
-            else:
+            elif want == 2:
                 a.pitch_c = plane(i, "uv", f.planes[1], device, crows, 2 * csamples)
-        a.y, a.u = f.planes[0].data_ptr(), f.planes[1].data_ptr()
+        a.y = f.planes[0].data_ptr()
+        if want > 1:
+            a.u = f.planes[1].data_ptr()
     return arr, frames
