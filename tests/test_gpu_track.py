@@ -6,87 +6,17 @@ the rule as written) bit for bit - torch.equal, no tolerance anywhere; rows of t
 bad arguments fail before anything is launched.
 """
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 import torch
 
 import track_model as tm
+from track_pair import F32, S_CNT, S_DETS, S_HITS, S_ID, S_SRC, Pair, _box, _frame, dev, eng, yfv2  # noqa: F401  (dev, eng, yfv2: the fixtures)
 
 pytestmark = pytest.mark.gpu
 
 NAN, INF = float("nan"), float("inf")
-F32 = np.float32
-S_ID, S_HITS, S_DETS, S_SRC, S_CNT = -7, -8, -3.0, -9, -10          # the outputs are pre-filled with these
-
-
-@pytest.fixture(scope="module")
-def yfv2():
-    import yolo_fastestv2_amd
-    assert torch.cuda.is_available(), "-m gpu tests need an MI355X"
-    assert os.path.exists(yolo_fastestv2_amd.LIB_PATH), "libyfv2.so not built"
-    return yolo_fastestv2_amd
-
-
-@pytest.fixture(scope="module")
-def dev():
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def eng(yfv2, dev):
-    """the tracker needs no weights: an engine of the usual size"""
-    return yfv2.Engine(dev, 352, 352, max_batch=4, plan={})
-
-
-class Pair:
-    """a device Tracker and the model, stepped together and compared after every call"""
-
-    def __init__(self, yfv2, eng, streams, **rule):
-        self.dev = eng.device
-        self.tracker = yfv2.Tracker(eng, streams, **rule)
-        self.model = tm.Model(streams, **rule)
-
-    def step(self, dets, count, streams=None, fresh=True):
-        dets = np.ascontiguousarray(dets, F32)
-        count = np.asarray(count, np.int32)
-        B, R = dets.shape[:2]
-        d, c = torch.from_numpy(dets).to(self.dev), torch.from_numpy(count).to(self.dev)
-        out = [torch.full((B, R), S_ID, device=self.dev, dtype=torch.int32), torch.full((B, R), S_HITS, device=self.dev, dtype=torch.int32)]
-        if fresh:
-            out += [torch.full((B, R, 6), S_DETS, device=self.dev, dtype=torch.float32), torch.full((B, R), S_SRC, device=self.dev, dtype=torch.int32),
-                    torch.full((B,), S_CNT, device=self.dev, dtype=torch.int32)]
-        got = self.tracker.update(d, c, streams, fresh=fresh, out=tuple(out))
-        assert all(g is o for g, o in zip(got, out))
-        want = self.model.update(dets, count, streams)
-        got = [g.cpu() for g in got]
-        assert torch.equal(self.tracker.state.cpu(), torch.from_numpy(self.model.state)), "state"
-        assert torch.equal(got[0], torch.from_numpy(want["track_id"])), "track_id"
-        assert torch.equal(got[1], torch.from_numpy(want["track_hits"])), "track_hits"
-        if fresh:
-            assert torch.equal(got[4], torch.from_numpy(want["fresh_count"])), "fresh_count"
-            for b in range(B):
-                k = int(want["fresh_count"][b])
-                assert torch.equal(got[3][b, :k], torch.from_numpy(want["fresh_src"][b, :k])), "fresh_src"
-                assert torch.equal(got[2][b, :k].view(torch.int32), torch.from_numpy(want["fresh_dets"][b, :k]).view(torch.int32)), "fresh_dets"
-                assert (got[3][b, k:] == S_SRC).all() and (got[2][b, k:] == S_DETS).all(), "rows beyond fresh_count were written"
-        return want
-
-    def header(self, stream=0):
-        return self.model.state[stream, :6].tolist()         # issued, live, frames, births, deaths, dropped
-
-
-def _frame(rows, R):
-    """rows: lists of x1, y1, x2, y2, conf, cls -> (1, R, 6) padded with a filler that is itself a valid row, and the count"""
-    d = np.tile(np.array([900.0, 900.0, 910.0, 910.0, 0.99, 0.0], F32), (1, R, 1))
-    if rows:
-        d[0, :len(rows)] = np.array(rows, F32)
-    return d, [len(rows)]
-
-
-def _box(x, y=0.0, w=10.0, h=10.0, conf=0.9, cls=0.0):
-    return [x, y, x + w, y + h, conf, cls]
 
 
 def test_lifecycle(yfv2, eng):

@@ -9,7 +9,6 @@ fresh outputs beyond fresh_count are not written; bad arguments fail before anyt
 """
 import ctypes as C
 import itertools
-import os
 
 import numpy as np
 import pytest
@@ -17,103 +16,12 @@ import torch
 
 import track_appearance_model as ta
 import track_model as tm
-import track_motion_model as mm
-import track_two_pass_model as tp
+from track_pair import (F32, LAYOUTS, PASSES, S_BOX, S_CNT, S_COS, S_DETS, S_HITS, S_ID, S_PASS, S_SRC, Pair, _bits, _diff, dev, eng,  # noqa: F401
+                        yfv2)                                                                                                       # (dev, eng, yfv2: the fixtures)
 
 pytestmark = pytest.mark.gpu
 
 NAN, INF = float("nan"), float("inf")
-F32 = np.float32
-S_ID, S_HITS, S_DETS, S_SRC, S_CNT, S_BOX, S_PASS, S_COS = -7, -8, -3.0, -9, -10, -5.0, -11, -6.0          # the outputs are pre-filled with these
-LAYOUTS = [None, True]                                                                                     # motion: the plain slots, the motion slots
-PASSES = [None, True]                                                                                      # second: one pass, two
-
-
-@pytest.fixture(scope="module")
-def yfv2():
-    import yolo_fastestv2_amd
-    assert torch.cuda.is_available(), "-m gpu tests need an MI355X"
-    assert os.path.exists(yolo_fastestv2_amd.LIB_PATH), "libyfv2.so not built"
-    return yolo_fastestv2_amd
-
-
-@pytest.fixture(scope="module")
-def dev():
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def eng(yfv2, dev):
-    """the tracker needs no weights: an engine of the usual size"""
-    return yfv2.Engine(dev, 352, 352, max_batch=4, plan={})
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-def _diff(what, got, want):
-    if not torch.equal(got, want):
-        bad = (got != want).nonzero()[:6].tolist()
-        raise AssertionError("%s (index, device, model): %s" % (what, [(i, hex(int(got[tuple(i)]) & 0xFFFFFFFF), hex(int(want[tuple(i)]) & 0xFFFFFFFF)) for i in bad]))
-
-
-class Pair:
-    """a device Tracker in the appearance form and the model, stepped together and compared after every call"""
-
-    def __init__(self, yfv2, eng, streams, appearance, second=None, motion=None, **rule):
-        self.dev, self.motion, self.second = eng.device, motion, second
-        self.tracker = yfv2.Tracker(eng, streams, motion=motion, two_pass=second, appearance=appearance, **rule)
-        self.model = ta.Model(streams, appearance=appearance, second=second, motion=motion, **rule)
-
-    def step(self, dets, count, emb, streams=None, **kw):
-        dets, emb = np.ascontiguousarray(dets, F32), np.ascontiguousarray(emb, F32)
-        count = np.asarray(count, np.int32)
-        want = self.model.update(dets, count, emb, streams)
-        self.compare(dets, count, emb, streams, want, self.model.state, self.model.feat, **kw)
-        return want
-
-    def compare(self, dets, count, emb, streams, want, wstate, wfeat, fresh=True, box=None, passes=None, cos=True):
-        box = (self.motion is not None) if box is None else box
-        passes = (self.second is not None) if passes is None else passes
-        B, R = dets.shape[:2]
-        d, c = torch.from_numpy(dets).to(self.dev), torch.from_numpy(np.asarray(count, np.int32)).to(self.dev)
-        e = torch.from_numpy(emb).to(self.dev)
-        out = [torch.full((B, R), S_ID, device=self.dev, dtype=torch.int32), torch.full((B, R), S_HITS, device=self.dev, dtype=torch.int32)]
-        if fresh:
-            out += [torch.full((B, R, 6), S_DETS, device=self.dev, dtype=torch.float32), torch.full((B, R), S_SRC, device=self.dev, dtype=torch.int32),
-                    torch.full((B,), S_CNT, device=self.dev, dtype=torch.int32)]
-        at = len(out)
-        if box:
-            out += [torch.full((B, R, 4), S_BOX, device=self.dev, dtype=torch.float32)]
-        if passes:
-            out += [torch.full((B, R), S_PASS, device=self.dev, dtype=torch.int32)]
-        if cos:
-            out += [torch.full((B, R), S_COS, device=self.dev, dtype=torch.float32)]
-        got = self.tracker.update(d, c, streams, fresh=fresh, box=box, passes=passes, emb=e, cos=cos, out=tuple(out))
-        assert all(g is o for g, o in zip(got, out))
-        got = [g.cpu() for g in got]
-        _diff("state", self.tracker.state.cpu(), torch.from_numpy(wstate))
-        _diff("feat", self.tracker.feat.cpu(), torch.from_numpy(wfeat))
-        assert torch.equal(got[0], torch.from_numpy(want["track_id"])), "track_id"
-        assert torch.equal(got[1], torch.from_numpy(want["track_hits"])), "track_hits"
-        if cos:
-            _diff("track_cos", _bits(got[-1]), _bits(torch.from_numpy(want["track_cos"])))
-        if passes:
-            assert torch.equal(got[at + (1 if box else 0)], torch.from_numpy(want["track_pass"])), "track_pass"
-        if box:
-            _diff("track_box", _bits(got[at]), _bits(torch.from_numpy(want["track_box"])))
-        if fresh:
-            assert torch.equal(got[4], torch.from_numpy(want["fresh_count"])), "fresh_count"
-            for b in range(B):
-                k = int(want["fresh_count"][b])
-                assert torch.equal(got[3][b, :k], torch.from_numpy(want["fresh_src"][b, :k])), "fresh_src"
-                assert torch.equal(_bits(got[2][b, :k]), _bits(torch.from_numpy(want["fresh_dets"][b, :k]))), "fresh_dets"
-                assert (got[3][b, k:] == S_SRC).all() and (got[2][b, k:] == S_DETS).all(), "rows beyond fresh_count were written"
-
-    def header(self, stream=0):
-        return self.model.state[stream, :8].tolist()         # issued, live, frames, births, deaths, dropped, second, by appearance
-
 
 # ---- 1 the scenarios
 @pytest.mark.parametrize("second", PASSES)
@@ -122,11 +30,11 @@ def test_the_jump(yfv2, eng, motion, second):
     """IoU 0.143 frame to frame, match_thres 0.3, prox_thres 0.1: the shipped form issues a new id per frame, the constant embedding
     keeps one (the plain layout: 7 matches by the cosine; the motion layout predicts a nearer box after the first leap)"""
     rule = dict(max_tracks=4, match_thres=0.3, max_misses=0, confirm_hits=3)
-    p = Pair(yfv2, eng, 1, dict(dim=16, prox_thres=0.1, app_thres=0.75), second=second, motion=motion, **rule)
+    p = Pair(yfv2, eng, 1, appearance=dict(dim=16, prox_thres=0.1, app_thres=0.75), second=second, motion=motion, **rule)
     shipped = yfv2.Tracker(eng, 1, **rule)
     ids, ids_shipped = [], []
     for d, c, e in ta.jump_case():
-        ids.append(int(p.step(d, c, e)["track_id"][0, 0]))
+        ids.append(int(p.step(d, c, emb=e)["track_id"][0, 0]))
         ids_shipped.append(int(shipped.update(torch.from_numpy(d).to(p.dev), torch.from_numpy(c).to(p.dev))[0][0, 0]))
     assert ids_shipped == list(range(1, 9)) and ids[:2] == [1, 1]
     if motion is None:
@@ -139,17 +47,17 @@ def test_the_jump(yfv2, eng, motion, second):
 @pytest.mark.parametrize("motion", LAYOUTS)
 def test_the_neighbour_the_tie_and_the_skipped_update(yfv2, eng, motion, second):
     rule = dict(max_tracks=4, match_thres=0.3, max_misses=5, confirm_hits=3)
-    p = Pair(yfv2, eng, 1, dict(dim=16), second=second, motion=motion, **rule)
+    p = Pair(yfv2, eng, 1, appearance=dict(dim=16), second=second, motion=motion, **rule)
     for d, c, e in ta.neighbour_case():
-        o = p.step(d, c, e)
+        o = p.step(d, c, emb=e)
     assert o["track_id"][0, 0] == 2 and o["track_cos"][0, 0] == 1.0 and p.header()[7] == 1
-    p = Pair(yfv2, eng, 1, dict(dim=16), second=second, motion=motion, **rule)
+    p = Pair(yfv2, eng, 1, appearance=dict(dim=16), second=second, motion=motion, **rule)
     for d, c, e in ta.neighbour_case(tie=True):
-        o = p.step(d, c, e)
+        o = p.step(d, c, emb=e)
     assert o["track_id"][0, 0] == 1 and o["track_cos"][0, 0] == 0.0 and p.header()[7] == 0
-    p = Pair(yfv2, eng, 1, dict(dim=16, alpha=0.5), second=second, motion=motion, **rule)
+    p = Pair(yfv2, eng, 1, appearance=dict(dim=16, alpha=0.5), second=second, motion=motion, **rule)
     for d, c, e in ta.flip_case():
-        o = p.step(d, c, e)
+        o = p.step(d, c, emb=e)
     assert o["track_cos"][0, 0] == -1.0 and p.model.stats["skipped"] == 1 and p.model.features()[0][0] == 1
 
 
@@ -164,9 +72,9 @@ def test_random_walks(yfv2, eng, R, M, motion, second):
     m, calls, shown = ta.walk_calls(R, M, motion, second)
     for k, v in ta.LEAST.items():
         assert shown.get(k, 0) >= v, (k, shown)
-    p = Pair(yfv2, eng, 2, dict(ta.WALK_APP, dim=ta.WALKS[(R, M)][0]), second=second, motion=motion, **m.rule)
+    p = Pair(yfv2, eng, 2, appearance=dict(ta.WALK_APP, dim=ta.WALKS[(R, M)][0]), second=second, motion=motion, **m.rule)
     for d, c, e, streams, want, wstate, wfeat in calls:
-        p.compare(d, c, e, streams, want, wstate, wfeat)
+        p.compare(d, c, streams, want, wstate, wfeat, e)
 
 
 # ---- 3 equivalence with the shipped forms
@@ -224,10 +132,10 @@ def test_the_widest_embedding(yfv2, eng):
     """D = 2048 at R = 65, M = 64: 128 steps per partial sum, three calls"""
     R, M, D = 65, 64, 2048
     rule = dict(max_tracks=M, match_thres=0.3, init_conf=0.3, max_misses=2, confirm_hits=2)
-    p = Pair(yfv2, eng, 1, dict(ta.WALK_APP, dim=D), motion=True, second=True, **rule)
+    p = Pair(yfv2, eng, 1, appearance=dict(ta.WALK_APP, dim=D), motion=True, second=True, **rule)
     for d, c, e in ta.walk_case(5, 1, 3, R, M, D, objects=80, bad=0.1):
         d[0, 0], c[0] = (10.0, 10.0, 50.0, 60.0, 0.9, 0.0), max(int(c[0]), 1) if c[0] <= R else R
-        p.step(d, c, e)
+        p.step(d, c, emb=e)
     assert p.header()[7] > 0 and p.model.stats["matched_without"] + p.model.stats.get("born_without", 0) > 0
 
 
@@ -237,7 +145,7 @@ def test_the_largest_table_the_lds_admits_and_the_first_it_refuses(yfv2, eng, de
     R, M, D = 4096, 935, 16
     assert 28 * R + 52 * M <= 163328 < 28 * R + 52 * (M + 1)
     rule = dict(max_tracks=M, match_thres=0.3, max_misses=1, confirm_hits=2)
-    p = Pair(yfv2, eng, 1, dict(ta.WALK_APP, dim=D), **rule)
+    p = Pair(yfv2, eng, 1, appearance=dict(ta.WALK_APP, dim=D), **rule)
     rng = np.random.default_rng(11)
     n0, n1 = 900, 1100
 
@@ -256,7 +164,7 @@ def test_the_largest_table_the_lds_admits_and_the_first_it_refuses(yfv2, eng, de
     p.tracker.state.copy_(torch.from_numpy(p.model.state))
     p.tracker.feat.copy_(torch.from_numpy(p.model.feat))
     d, c, e = frame(n1, 28.0)                                                         # IoU 12 / 68 = 0.18: matched by the cosine; 200 more rows, 35 slots
-    o = p.step(d, c, e)
+    o = p.step(d, c, emb=e)
     assert p.header()[7] >= 800 and p.header()[1] == M and p.header()[5] == n1 - M and (o["track_id"][0, :n1] != 0).sum() == M
     big = torch.zeros((1, 8 + 10 * (M + 1)), device=dev, dtype=torch.int32)
     feat = torch.zeros((1, (M + 1) * (4 + D)), device=dev, dtype=torch.int32)
@@ -279,10 +187,10 @@ def test_launch_split(yfv2, eng, motion, second):
     d[:, 1] = d[:, 0] + F32(200.0)
     d[:, 1, 4:] = (0.8, 0.0)
     e = rng.normal(size=(B, R, D)).astype(F32)
-    p = Pair(yfv2, eng, B, dict(dim=D, prox_thres=0.1), second=second, motion=motion, max_tracks=4, confirm_hits=2)
-    p.step(d, np.full(B, 2, np.int32), e, streams)
+    p = Pair(yfv2, eng, B, appearance=dict(dim=D, prox_thres=0.1), second=second, motion=motion, max_tracks=4, confirm_hits=2)
+    p.step(d, np.full(B, 2, np.int32), streams, emb=e)
     d[:, :2, :4] += F32(3.0)
-    o = p.step(d, np.full(B, 2, np.int32), e, streams)
+    o = p.step(d, np.full(B, 2, np.int32), streams, emb=e)
     assert (o["fresh_count"] == 2).all() and (p.model.state[:, 0] == 2).all() and (p.model.state[:, 7] == 2).all()
     assert (np.abs(o["track_cos"][768, :2] - 1.0) < 1e-5).all() and not o["track_cos"][768, 2:].any()
 
@@ -295,10 +203,10 @@ def test_optional_outputs(yfv2, eng, motion, second):
     (track_hits, which the Python layer always passes, is left out through the C ABI in the argument test)"""
     seq = ta.jump_case(frames=4)
     combos = [c for c in itertools.product([False, True], repeat=4) if (motion or not c[1]) and (second or not c[2])]      # fresh, box, passes, cos
-    ps = [Pair(yfv2, eng, 1, dict(dim=16, prox_thres=0.1), second=second, motion=motion, max_tracks=4, confirm_hits=2) for _ in combos]
+    ps = [Pair(yfv2, eng, 1, appearance=dict(dim=16, prox_thres=0.1), second=second, motion=motion, max_tracks=4, confirm_hits=2) for _ in combos]
     for d, c, e in seq:
         for p, (fresh, box, passes, cos) in zip(ps, combos):
-            p.step(d, c, e, fresh=fresh, box=box, passes=passes, cos=cos)
+            p.step(d, c, emb=e, fresh=fresh, box=box, passes=passes, cos=cos)
     for p in ps[1:]:
         assert torch.equal(p.tracker.state, ps[0].tracker.state) and torch.equal(p.tracker.feat, ps[0].tracker.feat)
     assert ps[0].header()[:6] == [1, 1, 4, 1, 0, 0] and ps[0].header()[7] >= 1

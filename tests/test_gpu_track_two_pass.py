@@ -8,112 +8,23 @@ the shipped one-pass form of its layout on the device, bit for bit; rows of the 
 bad arguments fail before anything is launched.
 """
 import ctypes as C
-import os
+import functools
 
 import numpy as np
 import pytest
 import torch
 
 import track_model as tm
-import track_motion_model as mm
+import track_pair
 import track_two_pass_model as tp
+from track_pair import (F32, LAYOUTS, S_BOX, S_CNT, S_DETS, S_HITS, S_ID, S_PASS, S_SRC, _bits, _box, _frame, dev, eng,  # noqa: F401
+                        yfv2)                                                                                           # (dev, eng, yfv2: the fixtures)
 
 pytestmark = pytest.mark.gpu
 
 NAN, INF = float("nan"), float("inf")
-F32 = np.float32
-S_ID, S_HITS, S_DETS, S_SRC, S_CNT, S_BOX, S_PASS = -7, -8, -3.0, -9, -10, -5.0, -11          # the outputs are pre-filled with these
-LAYOUTS = [None, True]                                                                       # motion: the plain slots, the motion slots
 
-
-@pytest.fixture(scope="module")
-def yfv2():
-    import yolo_fastestv2_amd
-    assert torch.cuda.is_available(), "-m gpu tests need an MI355X"
-    assert os.path.exists(yolo_fastestv2_amd.LIB_PATH), "libyfv2.so not built"
-    return yolo_fastestv2_amd
-
-
-@pytest.fixture(scope="module")
-def dev():
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def eng(yfv2, dev):
-    """the tracker needs no weights: an engine of the usual size"""
-    return yfv2.Engine(dev, 352, 352, max_batch=4, plan={})
-
-
-def _bits(t):
-    return t.contiguous().view(torch.int32)
-
-
-class Pair:
-    """a device Tracker in the two-pass form and the model, stepped together and compared after every call"""
-
-    def __init__(self, yfv2, eng, streams, second=True, motion=None, **rule):
-        self.dev, self.motion = eng.device, motion
-        self.tracker = yfv2.Tracker(eng, streams, motion=motion, two_pass=second, **rule)
-        self.model = tp.Model(streams, second=second, motion=motion, **rule)
-
-    def step(self, dets, count, streams=None, fresh=True, box=None, passes=True):
-        dets = np.ascontiguousarray(dets, F32)
-        count = np.asarray(count, np.int32)
-        want = self.model.update(dets, count, streams)
-        self.compare(dets, count, streams, want, self.model.state, fresh, box, passes)
-        return want
-
-    def compare(self, dets, count, streams, want, wstate, fresh=True, box=None, passes=True):
-        box = (self.motion is not None) if box is None else box
-        B, R = dets.shape[:2]
-        d, c = torch.from_numpy(dets).to(self.dev), torch.from_numpy(np.asarray(count, np.int32)).to(self.dev)
-        out = [torch.full((B, R), S_ID, device=self.dev, dtype=torch.int32), torch.full((B, R), S_HITS, device=self.dev, dtype=torch.int32)]
-        if fresh:
-            out += [torch.full((B, R, 6), S_DETS, device=self.dev, dtype=torch.float32), torch.full((B, R), S_SRC, device=self.dev, dtype=torch.int32),
-                    torch.full((B,), S_CNT, device=self.dev, dtype=torch.int32)]
-        if box:
-            out += [torch.full((B, R, 4), S_BOX, device=self.dev, dtype=torch.float32)]
-        if passes:
-            out += [torch.full((B, R), S_PASS, device=self.dev, dtype=torch.int32)]
-        got = self.tracker.update(d, c, streams, fresh=fresh, box=box, passes=passes, out=tuple(out))
-        assert all(g is o for g, o in zip(got, out))
-        got = [g.cpu() for g in got]
-        state, wstate = self.tracker.state.cpu(), torch.from_numpy(wstate)
-        if not torch.equal(state, wstate):
-            bad = (state != wstate).nonzero()[:6].tolist()
-            raise AssertionError("state (stream, word, device, model): %s" % [(s, w, hex(state[s, w] & 0xFFFFFFFF), hex(wstate[s, w] & 0xFFFFFFFF)) for s, w in bad])
-        assert torch.equal(got[0], torch.from_numpy(want["track_id"])), "track_id"
-        assert torch.equal(got[1], torch.from_numpy(want["track_hits"])), "track_hits"
-        if passes:
-            assert torch.equal(got[-1], torch.from_numpy(want["track_pass"])), "track_pass"
-        if box:
-            assert torch.equal(_bits(got[5 if fresh else 2]), _bits(torch.from_numpy(want["track_box"]))), "track_box"
-        if fresh:
-            assert torch.equal(got[4], torch.from_numpy(want["fresh_count"])), "fresh_count"
-            for b in range(B):
-                k = int(want["fresh_count"][b])
-                assert torch.equal(got[3][b, :k], torch.from_numpy(want["fresh_src"][b, :k])), "fresh_src"
-                assert torch.equal(_bits(got[2][b, :k]), _bits(torch.from_numpy(want["fresh_dets"][b, :k]))), "fresh_dets"
-                assert (got[3][b, k:] == S_SRC).all() and (got[2][b, k:] == S_DETS).all(), "rows beyond fresh_count were written"
-
-    def header(self, stream=0):
-        return self.model.state[stream, :7].tolist()         # issued, live, frames, births, deaths, dropped, second
-
-    def slots(self, stream=0):
-        return self.model.state[stream, tm.HEADER:].reshape(self.model.M, -1)
-
-
-def _frame(rows, R=4):
-    """rows: lists of x1, y1, x2, y2, conf, cls -> (1, R, 6) padded with a filler that is itself a valid row, and the count"""
-    d = np.tile(np.array([900.0, 900.0, 910.0, 910.0, 0.99, 0.0], F32), (1, R, 1))
-    if rows:
-        d[0, :len(rows)] = np.array(rows, F32)
-    return d, [len(rows)]
-
-
-def _box(x, y=0.0, w=10.0, h=10.0, conf=0.9, cls=0.0):
-    return [x, y, x + w, y + h, conf, cls]
+Pair = functools.partial(track_pair.Pair, second=True)          # every tracker of this file has two passes; second=dict(...) sets their rule
 
 
 # ---- 1 equivalence with the shipped form

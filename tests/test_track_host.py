@@ -235,3 +235,68 @@ def test_model_lifecycle_by_hand():
     assert m.state[0, :6].tolist() == [3, 0, 5, 3, 3, 2] and not m.state[0, tm.HEADER:].any()
     o = step([A], 9)                                        # count > R is R; the id is new
     assert o["track_id"][0].tolist() == [4, 0, 0, 0]
+
+
+def _output_description_in_every_combination():
+    """the package's one description of what an update returns: names, shapes and dtypes in the order the docstrings promise"""
+    import itertools
+
+    import torch
+    from yolo_fastestv2_amd import tracking
+    B, R = 3, 5
+    i32, f32 = torch.int32, torch.float32
+    for fresh, box, passes, cos in itertools.product((False, True), repeat=4):
+        want = [("track_id", (B, R), i32), ("track_hits", (B, R), i32)]
+        if fresh:
+            want += [("fresh_dets", (B, R, 6), f32), ("fresh_src", (B, R), i32), ("fresh_count", (B,), i32)]
+        want += [("track_box", (B, R, 4), f32)] * box + [("track_pass", (B, R), i32)] * passes + [("track_cos", (B, R), f32)] * cos
+        assert list(tracking.outputs(B, R, fresh, box, passes, cos)) == want, (fresh, box, passes, cos)
+        assert list(tracking.outputs(B, R, fresh=fresh, box=box, passes=passes, cos=cos)) == want
+    assert [n for n, _, _ in tracking.outputs(B, R)] == ["track_id", "track_hits"]
+
+
+def _option_errors_come_from_the_one_normaliser_under_each_callers_name():
+    """motion / two_pass / appearance: None, False, True or a dict of known keys - Tracker and the two engine methods that take such
+    an option refuse an unknown key with the same sentence under their own name, before anything touches a device"""
+    import yolo_fastestv2_amd as yfv2
+    from yolo_fastestv2_amd import tracking
+    t = tracking
+    assert t.MOTION_DEFAULTS == dict(std_pos=1.0 / 20, std_vel=1.0 / 160, std_meas=1.0 / 20)
+    assert t.TWO_PASS_DEFAULTS == dict(high_conf=0.5, low_conf=0.1, match_thres_low=0.5, tracked_only=True)
+    assert t.APPEARANCE_DEFAULTS == dict(dim=128, prox_thres=0.5, app_thres=0.75, alpha=0.9)
+    for off in (None, False):
+        assert t.option("x", "motion", off, t.MOTION_DEFAULTS) is None
+    assert t.option("x", "motion", True, t.MOTION_DEFAULTS) == t.MOTION_DEFAULTS
+    got = t.option("x", "two_pass", dict(low_conf=0, tracked_only=0), t.TWO_PASS_DEFAULTS)
+    assert got == dict(high_conf=0.5, low_conf=0.0, match_thres_low=0.5, tracked_only=False)
+    assert [type(v) for v in got.values()] == [float, float, float, bool]
+    got = t.option("x", "appearance", dict(dim=64.0, alpha=1), t.APPEARANCE_DEFAULTS)
+    assert got == dict(dim=64, prox_thres=0.5, app_thres=0.75, alpha=1.0) and type(got["dim"]) is int and type(got["alpha"]) is float
+    assert t.option("x", "motion", True, t.MOTION_DEFAULTS) is not t.MOTION_DEFAULTS
+    motion = "%s: motion takes std_pos, std_vel and std_meas, not ['sigma', 'zeta']"
+    two = "%s: two_pass takes high_conf, low_conf, match_thres_low and tracked_only, not ['mid_conf']"
+    app = "%s: appearance takes dim, prox_thres, app_thres and alpha, not ['width']"
+    bad_motion, bad_two, bad_app = dict(zeta=1, std_pos=1, sigma=2), dict(mid_conf=0.3), dict(width=3)
+    eng = object.__new__(yfv2.Engine)                        # no handle, no device: the option errors come first
+    args = (None,) * 5
+    callers = {
+        ("Tracker", "motion"): lambda: yfv2.Tracker(None, 1, motion=bad_motion),
+        ("Tracker", "two_pass"): lambda: yfv2.Tracker(None, 1, two_pass=bad_two),
+        ("Tracker", "appearance"): lambda: yfv2.Tracker(None, 1, appearance=bad_app),
+        ("track_update_two_pass", "motion"): lambda: eng.track_update_two_pass(*args, motion=bad_motion),
+        ("track_update_appearance", "motion"): lambda: eng.track_update_appearance(*args, None, None, motion=bad_motion),
+        ("track_update_appearance", "two_pass"): lambda: eng.track_update_appearance(*args, None, None, two_pass=bad_two),
+    }
+    for (caller, name), call in callers.items():
+        with pytest.raises(ValueError) as e:
+            call()
+        assert str(e.value) == dict(motion=motion, two_pass=two, appearance=app)[name] % caller
+        with pytest.raises(ValueError) as e:
+            t.option(caller, name, dict(motion=bad_motion, two_pass=bad_two, appearance=bad_app)[name],
+                     dict(motion=t.MOTION_DEFAULTS, two_pass=t.TWO_PASS_DEFAULTS, appearance=t.APPEARANCE_DEFAULTS)[name])
+        assert str(e.value) == dict(motion=motion, two_pass=two, appearance=app)[name] % caller
+
+
+def test_tracker_python_layer_states_outputs_and_options_once():
+    _output_description_in_every_combination()
+    _option_errors_come_from_the_one_normaliser_under_each_callers_name()

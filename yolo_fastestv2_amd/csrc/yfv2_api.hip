@@ -1,5 +1,5 @@
-// yfv2_api.hip - host side of libyfv2.so, first of four units: the handle's lifetime, the lanes, weights and anchors, and the
-// forward / decode / NMS / detect entry points declared in include/yfv2.h (frames and tiles: yfv2_api_frames.hip; statistics, loss,
+// yfv2_api.hip - host side of libyfv2.so, first of five units: the handle's lifetime, the lanes, weights and anchors, and the
+// forward / decode / NMS / detect entry points declared in include/yfv2.h (frames and tiles: yfv2_api_frames.hip; the tracker: yfv2_api_track.hip; statistics, loss,
 // k-means and AP: yfv2_api_eval.hip; dry runs, probes and dumps: yfv2_api_debug.hip; the handle itself: yfv2_ctx.h).  The forward
 // is a static list of launches ("plan") built once per weight load (yfv2_plan.hip); running it enqueues the launches on the
 // caller's stream, nothing else.  Weight folding / re-layout: yfv2_pack.hip.

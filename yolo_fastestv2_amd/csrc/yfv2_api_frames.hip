@@ -6,7 +6,6 @@
 // row kind's width limit (yfv2_rows_max_width), enqueue_rows uploads its table and launches the rows of the resize or the training
 // batch (yfv2_launch_rows), and resize_frames / train_batch_frames / detect_frames / crop_detections (yfv2_crop_tensors_* too: the
 // same template with a yfv2_crop_tensor) / detect_tiled are one template each.  The extern "C" functions pass their names.
-// yfv2_track_update (the per-stream tracker behind the detect calls) takes rows, not frames; its checks and its launch are here too.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -421,145 +420,6 @@ int yfv2_crop_detections_u8(yfv2_handle h, const yfv2_frame* frames, int32_t B, 
 int yfv2_crop_detections_yuv(yfv2_handle h, const yfv2_frame_yuv* frames, int32_t B, const float* dets, const int32_t* count, int32_t R, const yfv2_crop_rule* rule,
                              uint8_t* crops, int32_t* crop_src, int32_t* crop_rect, int32_t* crop_offset, int32_t* crop_skipped, int32_t cap, void* stream) {
   return crop_detections<YuvFrames>(h, "yfv2_crop_detections_yuv", frames, B, dets, count, R, rule, crops, crop_src, crop_rect, crop_offset, crop_skipped, cap, stream);
-}
-
-// ---- the per-stream IoU tracker (its motion form 4.19, its two-pass form 4.20; kernel, and yfv2_track_iou /
-// yfv2_track_filter_step beside the one function each of them exposes: yfv2_track.hip) -------
-// Every check first; then one launch per TRACK_CHUNK frames (the streams of a launch travel in its arguments: no table, no copy,
-// no workspace).  The frames of a call are distinct streams, so the launches share nothing.
-int64_t yfv2_track_state_words(int32_t max_tracks) {
-  if (max_tracks < 1 || max_tracks > TRACK_MAX_M) return fail(nullptr, YFV2_ERR_ARG, "yfv2_track_state_words: max_tracks must be in 1.." + std::to_string(TRACK_MAX_M));
-  return (int64_t)TRACK_HEADER + (int64_t)TRACK_SLOT * max_tracks;
-}
-
-int64_t yfv2_track_motion_state_words(int32_t max_tracks) {
-  if (max_tracks < 1 || max_tracks > TRACK_MAX_M) return fail(nullptr, YFV2_ERR_ARG, "yfv2_track_motion_state_words: max_tracks must be in 1.." + std::to_string(TRACK_MAX_M));
-  return (int64_t)TRACK_HEADER + (int64_t)TRACK_SLOT_MOTION * max_tracks;
-}
-
-int64_t yfv2_track_feature_words(int32_t max_tracks, int32_t D) {
-  if (max_tracks < 1 || max_tracks > TRACK_MAX_M) return fail(nullptr, YFV2_ERR_ARG, "yfv2_track_feature_words: max_tracks must be in 1.." + std::to_string(TRACK_MAX_M));
-  if (D < TRACK_APP_MIN_D || D > TRACK_APP_MAX_D || D % 16 != 0) return fail(nullptr, YFV2_ERR_ARG, "yfv2_track_feature_words: D must be a multiple of 16 in 16..2048");
-  return (int64_t)max_tracks * (TRACK_FEAT_HEAD + D);
-}
-
-// the appearance form's own arguments (yfv2_track_update_appearance); the other entry points pass none
-struct TrackAppIn {
-  const yfv2_track_appearance* rule;
-  const float* emb;
-  int32_t* feat;
-  float* track_cos;
-};
-
-// all forms: motion == nullptr is a plain table (with_motion tells a missing argument from the plain form); two_pass: second is
-// required and the launch is the two-pass kernel of the table's layout; app: the appearance form, of either layout and pass count
-static int track_update(const std::string& w_, bool with_motion, bool two_pass, yfv2_handle h, const float* dets, const int32_t* count, int32_t R, int32_t B,
-                        const int32_t* stream_of, int32_t* state, int32_t S, const yfv2_track_rule* rule, const yfv2_track_motion* motion,
-                        const yfv2_track_second* second, int32_t* track_id, int32_t* track_hits, int32_t* track_pass, float* track_box, float* fresh_dets,
-                        int32_t* fresh_src, int32_t* fresh_count, void* stream, const TrackAppIn* app = nullptr) {
-  if (!h) return fail(nullptr, YFV2_ERR_ARG, "null handle");
-  if (!dets || !count || !stream_of || !state || !rule || !track_id || (with_motion && !motion) || (two_pass && !second))
-    return fail(h, YFV2_ERR_ARG, w_ + ": null pointer");
-  if (app && (!app->rule || !app->emb || !app->feat)) return fail(h, YFV2_ERR_ARG, w_ + ": null pointer");
-  const int given = (fresh_dets != nullptr) + (fresh_src != nullptr) + (fresh_count != nullptr);
-  if (given != 0 && given != 3) return fail(h, YFV2_ERR_ARG, w_ + ": fresh_dets, fresh_src and fresh_count must all be given or all be NULL");
-  if (B < 1) return fail(h, YFV2_ERR_ARG, w_ + ": B < 1");
-  if (S < 1) return fail(h, YFV2_ERR_ARG, w_ + ": S < 1");
-  if (R < 1 || R > TRACK_MAX_R) return fail(h, YFV2_ERR_ARG, w_ + ": R must be in 1.." + std::to_string(TRACK_MAX_R));
-  const yfv2_track_rule& q = *rule;
-  if (q.max_tracks < 1 || q.max_tracks > TRACK_MAX_M) return fail(h, YFV2_ERR_ARG, w_ + ": max_tracks must be in 1.." + std::to_string(TRACK_MAX_M));
-  if (!std::isfinite(q.match_thres) || q.match_thres < 0.0) return fail(h, YFV2_ERR_ARG, w_ + ": match_thres must be a finite number >= 0");
-  if (std::isnan(q.init_conf)) return fail(h, YFV2_ERR_ARG, w_ + ": init_conf is not a number");
-  if (q.max_misses < 0) return fail(h, YFV2_ERR_ARG, w_ + ": max_misses must be >= 0");
-  if (q.confirm_hits < 1) return fail(h, YFV2_ERR_ARG, w_ + ": confirm_hits must be >= 1");
-  if (with_motion)
-    for (const float v : {motion->std_pos, motion->std_vel, motion->std_meas})
-      if (!std::isfinite(v) || !(v > 0.0f)) return fail(h, YFV2_ERR_ARG, w_ + ": std_pos, std_vel and std_meas must be finite and > 0");
-  if (two_pass) {
-    if (std::isnan(second->high_conf) || std::isnan(second->low_conf)) return fail(h, YFV2_ERR_ARG, w_ + ": high_conf or low_conf is not a number");
-    if (second->low_conf > second->high_conf) return fail(h, YFV2_ERR_ARG, w_ + ": low_conf must not exceed high_conf");
-    if (!std::isfinite(second->match_thres_low) || second->match_thres_low < 0.0)
-      return fail(h, YFV2_ERR_ARG, w_ + ": match_thres_low must be a finite number >= 0");
-    if (track_box && !with_motion) return fail(h, YFV2_ERR_ARG, w_ + ": track_box needs motion");
-  }
-  if (app) {
-    const yfv2_track_appearance& p = *app->rule;
-    if (track_box && !with_motion) return fail(h, YFV2_ERR_ARG, w_ + ": track_box needs motion");
-    if (track_pass && !two_pass) return fail(h, YFV2_ERR_ARG, w_ + ": track_pass needs second");
-    if ((reinterpret_cast<uintptr_t>(app->emb) & 15) != 0) return fail(h, YFV2_ERR_ARG, w_ + ": emb must be 16-byte aligned");
-    if (p.dim < TRACK_APP_MIN_D || p.dim > TRACK_APP_MAX_D || p.dim % 16 != 0) return fail(h, YFV2_ERR_ARG, w_ + ": dim must be a multiple of 16 in 16..2048");
-    if (!std::isfinite(p.prox_thres) || p.prox_thres < 0.0) return fail(h, YFV2_ERR_ARG, w_ + ": prox_thres must be a finite number >= 0");
-    if (std::isnan(p.app_thres)) return fail(h, YFV2_ERR_ARG, w_ + ": app_thres is not a number");
-    if (!std::isfinite(p.alpha) || p.alpha < 0.0f || p.alpha > 1.0f) return fail(h, YFV2_ERR_ARG, w_ + ": alpha must be in [0, 1]");
-    if (yfv2_track_lds_bytes(true, R, q.max_tracks) > TRACK_APP_LDS_MAX)
-      return fail(h, YFV2_ERR_ARG, w_ + ": 28 R + 52 max_tracks must not exceed " + std::to_string(TRACK_APP_LDS_MAX) + " bytes of LDS");
-  }
-  std::vector<int32_t> sorted(stream_of, stream_of + B);
-  std::sort(sorted.begin(), sorted.end());
-  if (sorted.front() < 0 || sorted.back() >= S)
-    return fail(h, YFV2_ERR_ARG, w_ + ": stream " + std::to_string(sorted.front() < 0 ? sorted.front() : sorted.back()) + " outside [0, S)");
-  for (int32_t b = 1; b < B; ++b)
-    if (sorted[b] == sorted[b - 1]) return fail(h, YFV2_ERR_ARG, w_ + ": stream " + std::to_string(sorted[b]) + " named twice (one frame per stream and call)");
-  DeviceGuard guard(h->device);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  TrackAppArgs a{};                        // the two-pass launch takes its TrackTwoArgs part, the motion launch its TrackMotionArgs part, the plain launch its TrackArgs part
-  a.R = R; a.M = q.max_tracks; a.state = state; a.thres = q.match_thres; a.class_aware = q.class_aware; a.init_conf = q.init_conf;
-  a.max_misses = q.max_misses; a.confirm_hits = q.confirm_hits;
-  if (with_motion) a.motion = TrackMotion{motion->std_pos, motion->std_vel, motion->std_meas};
-  if (two_pass) { a.high_conf = second->high_conf; a.low_conf = second->low_conf; a.thres_low = second->match_thres_low; a.tracked_only = second->tracked_only; }
-  if (app) {
-    a.feat = app->feat; a.D = app->rule->dim; a.prox = app->rule->prox_thres; a.app = app->rule->app_thres;
-    a.alpha = app->rule->alpha; a.beta = 1.0f - a.alpha;
-  }
-  for (int32_t b0 = 0; b0 < B; b0 += TRACK_CHUNK) {
-    const int frames = std::min<int32_t>(TRACK_CHUNK, B - b0);
-    const size_t row0 = (size_t)b0 * R;
-    if (app) { a.emb = app->emb + row0 * (size_t)a.D; a.track_cos = app->track_cos ? app->track_cos + row0 : nullptr; }
-    a.dets = dets + row0 * 6; a.count = count + b0; a.track_id = track_id + row0; a.track_hits = track_hits ? track_hits + row0 : nullptr;
-    a.fresh_dets = fresh_dets ? fresh_dets + row0 * 6 : nullptr; a.fresh_src = fresh_src ? fresh_src + row0 : nullptr;
-    a.fresh_count = fresh_count ? fresh_count + b0 : nullptr;
-    a.track_box = track_box ? track_box + row0 * 4 : nullptr;
-    a.track_pass = track_pass ? track_pass + row0 : nullptr;
-    std::copy(stream_of + b0, stream_of + b0 + frames, a.stream_of);
-    if (app) yfv2_launch_track_appearance(a, with_motion, two_pass, frames, s);
-    else if (two_pass) yfv2_launch_track_two_pass(a, with_motion, frames, s);
-    else if (with_motion) yfv2_launch_track_motion(a, frames, s);
-    else yfv2_launch_track(a, frames, s);
-  }
-  HIP_TRY(h, hipGetLastError());
-  return YFV2_OK;
-}
-
-int yfv2_track_update(yfv2_handle h, const float* dets, const int32_t* count, int32_t R, int32_t B, const int32_t* stream_of, int32_t* state, int32_t S,
-                      const yfv2_track_rule* rule, int32_t* track_id, int32_t* track_hits, float* fresh_dets, int32_t* fresh_src, int32_t* fresh_count,
-                      void* stream) {
-  return track_update("yfv2_track_update", false, false, h, dets, count, R, B, stream_of, state, S, rule, nullptr, nullptr, track_id, track_hits, nullptr,
-                      nullptr, fresh_dets, fresh_src, fresh_count, stream);
-}
-
-int yfv2_track_update_motion(yfv2_handle h, const float* dets, const int32_t* count, int32_t R, int32_t B, const int32_t* stream_of, int32_t* state,
-                             int32_t S, const yfv2_track_rule* rule, const yfv2_track_motion* motion, int32_t* track_id, int32_t* track_hits,
-                             float* track_box, float* fresh_dets, int32_t* fresh_src, int32_t* fresh_count, void* stream) {
-  return track_update("yfv2_track_update_motion", true, false, h, dets, count, R, B, stream_of, state, S, rule, motion, nullptr, track_id, track_hits, nullptr,
-                      track_box, fresh_dets, fresh_src, fresh_count, stream);
-}
-
-int yfv2_track_update_two_pass(yfv2_handle h, const float* dets, const int32_t* count, int32_t R, int32_t B, const int32_t* stream_of, int32_t* state,
-                               int32_t S, const yfv2_track_rule* rule, const yfv2_track_motion* motion, const yfv2_track_second* second, int32_t* track_id,
-                               int32_t* track_hits, int32_t* track_pass, float* track_box, float* fresh_dets, int32_t* fresh_src, int32_t* fresh_count,
-                               void* stream) {
-  return track_update("yfv2_track_update_two_pass", motion != nullptr, true, h, dets, count, R, B, stream_of, state, S, rule, motion, second, track_id,
-                      track_hits, track_pass, track_box, fresh_dets, fresh_src, fresh_count, stream);
-}
-
-int yfv2_track_update_appearance(yfv2_handle h, const float* dets, const int32_t* count, int32_t R, int32_t B, const int32_t* stream_of, int32_t* state,
-                                 int32_t S, const yfv2_track_rule* rule, const yfv2_track_motion* motion, const yfv2_track_second* second,
-                                 const yfv2_track_appearance* appearance, const float* emb, int32_t* feat, int32_t* track_id, int32_t* track_hits,
-                                 int32_t* track_pass, float* track_box, float* track_cos, float* fresh_dets, int32_t* fresh_src, int32_t* fresh_count,
-                                 void* stream) {
-  const TrackAppIn app{appearance, emb, feat, track_cos};
-  return track_update("yfv2_track_update_appearance", motion != nullptr, second != nullptr, h, dets, count, R, B, stream_of, state, S, rule, motion, second,
-                      track_id, track_hits, track_pass, track_box, fresh_dets, fresh_src, fresh_count, stream, &app);
 }
 
 int yfv2_resize_u8(yfv2_handle h, const uint8_t* src, int32_t B, int32_t src_h, int32_t src_w, uint8_t* dst, void* stream) {

@@ -1,5 +1,5 @@
 // yfv2_ctx.h - the handle behind yfv2_handle and the plumbing the API units share (yfv2_api.hip: lifetime, lanes, weights, forward
-// and post; yfv2_api_frames.hip; yfv2_api_eval.hip; yfv2_api_debug.hip): error reporting, the device guard, the two owning memory
+// and post; yfv2_api_frames.hip; yfv2_api_track.hip; yfv2_api_eval.hip; yfv2_api_debug.hip): error reporting, the device guard, the two owning memory
 // types and the sized struct copies.  Private, like yfv2_plan.h; yfv2_train.hip reaches the handle through yfv2_internal.h's three
 // accessors instead.  Brings the HIP runtime and <cstring>, <string>, <vector> to the units that include it.
 #pragma once

@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include <atomic>
+#include <cmath>
 
 // Every launch of the forward path goes through YFV2_LAUNCH.  Normally a plain launch; while yfv2_profile_forward runs a plan step, the
 // step's FIRST launch records its own begin and every launch its own end into the calling thread's event pair (hipExtLaunchKernel: the
@@ -553,8 +554,6 @@ struct TrackMotionArgs : TrackArgs {   // the plain form's arguments stay what t
   TrackMotion motion;
   float* track_box;            // (B, R, 4) or null, offset like dets
 };
-void yfv2_launch_track(const TrackArgs& a, int frames, hipStream_t s);   // one workgroup per frame, frames <= TRACK_CHUNK
-void yfv2_launch_track_motion(const TrackMotionArgs& a, int frames, hipStream_t s);   // ... of track_kernel<true>; a.state in 32-word slots
 // the two-pass form (yfv2_track_update_two_pass): either layout, the rounds run over the HIGH rows and then the LOW
 struct TrackTwoArgs : TrackMotionArgs {   // the other forms' arguments stay what they were: their kernels are the ones they were
   float high_conf, low_conf;   // a valid row is HIGH at conf >= high_conf, LOW at low_conf <= conf < high_conf, else takes no part
@@ -562,7 +561,6 @@ struct TrackTwoArgs : TrackMotionArgs {   // the other forms' arguments stay wha
   int tracked_only;            // != 0: a slot with misses != 0 at the frame's start is not offered to the second pass
   int32_t* track_pass;         // (B, R) or null, offset like dets
 };
-void yfv2_launch_track_two_pass(const TrackTwoArgs& a, bool motion, int frames, hipStream_t s);   // motion: a.state in 32-word slots
 // the appearance form (yfv2_track_update_appearance): either layout, one pass or two; a track's feature is a slot of
 // TRACK_FEAT_HEAD + D words in a buffer of its own (word 0: n_feat, then zeros, then the D fp32 bits of the unit feature)
 constexpr int TRACK_FEAT_HEAD = 4, TRACK_APP_MIN_D = 16, TRACK_APP_MAX_D = 2048;
@@ -578,7 +576,16 @@ struct TrackAppArgs : TrackTwoArgs {   // the other forms' arguments stay what t
   double prox, app;            // the cosine counts when double(IoU) > prox and double(cosine) > app
   float alpha, beta;           // the feature's moving average: alpha * f + beta * e / |e|, beta = 1.0f - alpha
 };
-void yfv2_launch_track_appearance(const TrackAppArgs& a, bool motion, bool two_pass, int frames, hipStream_t s);
+// The limits of the entry points (yfv2_api_track.hip) and of the host arithmetic (yfv2_track.hip), each written once.
+inline bool yfv2_track_tracks_ok(int32_t M) { return M >= 1 && M <= TRACK_MAX_M; }
+inline bool yfv2_track_dim_ok(int32_t D) { return D >= TRACK_APP_MIN_D && D <= TRACK_APP_MAX_D && D % 16 == 0; }
+inline bool yfv2_track_motion_ok(float std_pos, float std_vel, float std_meas) {
+  return std::isfinite(std_pos) && std_pos > 0.f && std::isfinite(std_vel) && std_vel > 0.f && std::isfinite(std_meas) && std_meas > 0.f;
+}
+// The one launcher: form picks the instantiation of track_kernel, which takes the part of `a` that is its own argument type (the
+// plain kernel its TrackArgs part, ...).  One workgroup per frame, frames <= TRACK_CHUNK; motion: a.state in 32-word slots.
+struct TrackForm { bool motion, two_pass, appearance; };
+void yfv2_launch_track(const TrackAppArgs& a, TrackForm form, int frames, hipStream_t s);
 // dets columns 0-3 of the first count[b] rows of frame b times frames[b].box_x / box_y (yfv2_post.hip)
 void yfv2_launch_frame_boxes(float* dets, const int32_t* count, const ResizeFrame* frames, int B, hipStream_t s);
 void yfv2_launch_decode(const DecodeArgs& a, hipStream_t s);

@@ -713,15 +713,18 @@ static void launch_track(const track_args_t<MOTION, TWO, APP>& a, int frames, hi
   constexpr int limit = APP ? (int)TRACK_APP_LDS_MAX : (int)yfv2_track_lds_bytes(false, TRACK_MAX_R, TRACK_MAX_M);
   YFV2_LAUNCH_LDS(yfv2_device(), (track_kernel<MOTION, TWO, APP>), limit, dim3((unsigned)frames), dim3((unsigned)threads), lds, s, a);
 }
-void yfv2_launch_track_appearance(const TrackAppArgs& a, bool motion, bool two_pass, int frames, hipStream_t s) {
-  if (motion) { if (two_pass) launch_track<true, true, true>(a, frames, s); else launch_track<true, false, true>(a, frames, s); }
-  else { if (two_pass) launch_track<false, true, true>(a, frames, s); else launch_track<false, false, true>(a, frames, s); }
-}
-void yfv2_launch_track(const TrackArgs& a, int frames, hipStream_t s) { launch_track<false, false>(a, frames, s); }
-void yfv2_launch_track_motion(const TrackMotionArgs& a,int frames, hipStream_t s) { launch_track<true, false>(a, frames, s); }
-void yfv2_launch_track_two_pass(const TrackTwoArgs& a, bool motion, int frames, hipStream_t s) {
-  if (motion) launch_track<true, true>(a, frames, s);
-  else launch_track<false, true>(a, frames, s);
+// a binds to each instantiation's own argument type (a base of TrackAppArgs): a kernel is passed that part and nothing else
+void yfv2_launch_track(const TrackAppArgs& a, TrackForm form, int frames, hipStream_t s) {
+  switch (form.motion | form.two_pass << 1 | form.appearance << 2) {
+    case 0: return launch_track<false, false>(a, frames, s);
+    case 1: return launch_track<true, false>(a, frames, s);
+    case 2: return launch_track<false, true>(a, frames, s);
+    case 3: return launch_track<true, true>(a, frames, s);
+    case 4: return launch_track<false, false, true>(a, frames, s);
+    case 5: return launch_track<true, false, true>(a, frames, s);
+    case 6: return launch_track<false, true, true>(a, frames, s);
+    case 7: return launch_track<true, true, true>(a, frames, s);
+  }
 }
 
 extern "C" int yfv2_track_iou(const float a[4], const float b[4], float* v) {
@@ -737,11 +740,10 @@ static float host_dot16(const float* a, const float* b, int D) {
   for (int j = 0; j < 16; ++j) P[j] = track_dot16_part(a, b, D, j);
   return track_dot16_tree(P);
 }
-static bool app_dim_ok(int32_t D) { return D >= TRACK_APP_MIN_D && D <= TRACK_APP_MAX_D && D % 16 == 0; }
 
 extern "C" int yfv2_track_cosine(const float* e, const float* f, int32_t D, float* norm, float* cos) {
   if (!e || !f || !norm || !cos) return yfv2_ctx_fail(nullptr, YFV2_ERR_ARG, "yfv2_track_cosine: null pointer");
-  if (!app_dim_ok(D)) return yfv2_ctx_fail(nullptr, YFV2_ERR_ARG, "yfv2_track_cosine: D must be a multiple of 16 in 16..2048");
+  if (!yfv2_track_dim_ok(D)) return yfv2_ctx_fail(nullptr, YFV2_ERR_ARG, "yfv2_track_cosine: D must be a multiple of 16 in 16..2048");
   const float n = track_canon(track_sqrt(host_dot16(e, e, D)));
   *norm = n;
   *cos = track_cosine(host_dot16(e, f, D), n);
@@ -750,7 +752,7 @@ extern "C" int yfv2_track_cosine(const float* e, const float* f, int32_t D, floa
 
 extern "C" int yfv2_track_feature_step(const float* f_in, int32_t n_feat_in, const float* e, int32_t D, float alpha, float* f_out, int32_t* n_feat_out) {
   if (!f_in || !e || !f_out || !n_feat_out) return yfv2_ctx_fail(nullptr, YFV2_ERR_ARG, "yfv2_track_feature_step: null pointer");
-  if (!app_dim_ok(D)) return yfv2_ctx_fail(nullptr, YFV2_ERR_ARG, "yfv2_track_feature_step: D must be a multiple of 16 in 16..2048");
+  if (!yfv2_track_dim_ok(D)) return yfv2_ctx_fail(nullptr, YFV2_ERR_ARG, "yfv2_track_feature_step: D must be a multiple of 16 in 16..2048");
   if (n_feat_in < 0) return yfv2_ctx_fail(nullptr, YFV2_ERR_ARG, "yfv2_track_feature_step: n_feat_in < 0");
   if (!std::isfinite(alpha) || alpha < 0.0f || alpha > 1.0f) return yfv2_ctx_fail(nullptr, YFV2_ERR_ARG, "yfv2_track_feature_step: alpha must be in [0, 1]");
   const float beta = 1.0f - alpha;
@@ -778,13 +780,10 @@ extern "C" int yfv2_track_feature_step(const float* f_in, int32_t n_feat_in, con
 }
 
 // ---- the motion form's arithmetic for the host (tests pin it to the model without a device)
-static bool motion_ok(const yfv2_track_motion* m) {
-  return m && std::isfinite(m->std_pos) && m->std_pos > 0.f && std::isfinite(m->std_vel) && m->std_vel > 0.f && std::isfinite(m->std_meas) && m->std_meas > 0.f;
-}
-
 extern "C" int yfv2_track_filter_step(const float in[5], const float* z, float scale_predict, float scale_update, const yfv2_track_motion* motion, float out[5]) {
   if (!in || !out || !motion) return yfv2_ctx_fail(nullptr, YFV2_ERR_ARG, "yfv2_track_filter_step: null pointer");
-  if (!motion_ok(motion)) return yfv2_ctx_fail(nullptr, YFV2_ERR_ARG, "yfv2_track_filter_step: std_pos, std_vel and std_meas must be finite and > 0");
+  if (!yfv2_track_motion_ok(motion->std_pos, motion->std_vel, motion->std_meas))
+    return yfv2_ctx_fail(nullptr, YFV2_ERR_ARG, "yfv2_track_filter_step: std_pos, std_vel and std_meas must be finite and > 0");
   const TrackMotion m{motion->std_pos, motion->std_vel, motion->std_meas};
   const TrackFilter f = track_filter_step(TrackFilter{in[0], in[1], in[2], in[3], in[4]}, true, z != nullptr, z ? *z : 0.0f, scale_predict, scale_update, m);
   out[0] = f.x; out[1] = f.v; out[2] = f.p00; out[3] = f.p01; out[4] = f.p11;
@@ -793,7 +792,8 @@ extern "C" int yfv2_track_filter_step(const float in[5], const float* z, float s
 
 extern "C" int yfv2_track_birth(const float row_box[4], const yfv2_track_motion* motion, float out[20]) {
   if (!row_box || !out || !motion) return yfv2_ctx_fail(nullptr, YFV2_ERR_ARG, "yfv2_track_birth: null pointer");
-  if (!motion_ok(motion)) return yfv2_ctx_fail(nullptr, YFV2_ERR_ARG, "yfv2_track_birth: std_pos, std_vel and std_meas must be finite and > 0");
+  if (!yfv2_track_motion_ok(motion->std_pos, motion->std_vel, motion->std_meas))
+    return yfv2_ctx_fail(nullptr, YFV2_ERR_ARG, "yfv2_track_birth: std_pos, std_vel and std_meas must be finite and > 0");
   const TrackMotion m{motion->std_pos, motion->std_vel, motion->std_meas};
   float z[4];
   TrackFilter f[4];

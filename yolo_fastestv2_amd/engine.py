@@ -5,8 +5,9 @@ import ctypes as C
 
 import torch
 
-from . import _lib, tiling, yuv
+from . import _lib, tiling, tracking, yuv
 from ._lib import MAX_DET, Config, TensorDesc, check
+from .tracking import APPEARANCE_DEFAULTS as _APP, MOTION_DEFAULTS as _MOT, TWO_PASS_DEFAULTS as _TWO
 
 LOGIT_ORDER = ("reg_2", "obj_2", "cls_2", "reg_3", "obj_3", "cls_3")  # detector.py:47
 
@@ -544,12 +545,12 @@ class Engine:
         with fresh=True, also (fresh_dets (B, R, 6), fresh_src (B, R), fresh_count (B)): the rows whose track reached confirm_hits in
         this frame, compacted in row order, which is the (dets, count) pair crop_detections takes.  out: the same tuple, preallocated.
         The rule, bit for bit: include/yfv2.h.  Enqueue only: one launch, no host wait."""
-        return self._track_update("track_update", None, False, dets, count, streams, state, max_tracks, match_thres, class_aware, init_conf, max_misses,
-                                  confirm_hits, fresh, out)
+        rule = (match_thres, class_aware, init_conf, max_misses, confirm_hits)
+        return tracking.update(self, "track_update", dets, count, streams, state, max_tracks, rule, fresh=fresh, out=out)
 
     def track_update_two_pass(self, dets, count, streams, state, max_tracks, match_thres=0.3, class_aware=True, init_conf=0.0, max_misses=30,
-                              confirm_hits=3, high_conf=0.5, low_conf=0.1, match_thres_low=0.5, tracked_only=True, motion=None, fresh=False,
-                              box=False, passes=False, out=None):
+                              confirm_hits=3, high_conf=_TWO["high_conf"], low_conf=_TWO["low_conf"], match_thres_low=_TWO["match_thres_low"],
+                              tracked_only=_TWO["tracked_only"], motion=None, fresh=False, box=False, passes=False, out=None):
         """track_update / track_update_motion with two association passes (include/yfv2.h yfv2_track_update_two_pass):
         the rows with conf >= high_conf are matched first, the rows with low_conf <= conf < high_conf are then offered to the tracks
         still unmatched (tracked_only: only to those that were matched in their last frame) with IoU > match_thres_low, and start no
@@ -557,33 +558,29 @@ class Engine:
         of std_pos, std_vel, std_meas - the motion form's (S, 8 + 32 * max_tracks), and box=True is allowed.  Returns what the
         one-pass call of the layout returns and, with passes=True, last of all track_pass (B, R) int32: 1 for a row matched in the
         first pass or born, 2 for a row matched in the second pass, 0 for a row without a track."""
-        if motion is None or motion is False:
-            motion = None
-            if box:
-                raise ValueError("track_update_two_pass: box=True needs motion")
-        else:
-            given = {} if motion is True else dict(motion)
-            motion = dict(std_pos=given.pop("std_pos", 1.0 / 20), std_vel=given.pop("std_vel", 1.0 / 160), std_meas=given.pop("std_meas", 1.0 / 20))
-            if given:
-                raise ValueError("track_update_two_pass: motion takes std_pos, std_vel and std_meas, not %s" % sorted(given))
+        name = "track_update_two_pass"
+        motion = tracking.option(name, "motion", motion, _MOT)
+        if box and motion is None:
+            raise ValueError(name + ": box=True needs motion")
+        rule = (match_thres, class_aware, init_conf, max_misses, confirm_hits)
         second = dict(high_conf=high_conf, low_conf=low_conf, match_thres_low=match_thres_low, tracked_only=tracked_only)
-        return self._track_update("track_update_two_pass", motion, box, dets, count, streams, state, max_tracks, match_thres, class_aware, init_conf,
-                                  max_misses, confirm_hits, fresh, out, second=second, passes=passes)
+        return tracking.update(self, name, dets, count, streams, state, max_tracks, rule, motion=motion, second=second, fresh=fresh, box=box,
+                               passes=passes, out=out)
 
     def track_update_motion(self, dets, count, streams, state, max_tracks, match_thres=0.3, class_aware=True, init_conf=0.0, max_misses=30,
-                            confirm_hits=3, std_pos=1.0 / 20, std_vel=1.0 / 160, std_meas=1.0 / 20, fresh=False, box=False, out=None):
+                            confirm_hits=3, std_pos=_MOT["std_pos"], std_vel=_MOT["std_vel"], std_meas=_MOT["std_meas"], fresh=False, box=False, out=None):
         """track_update with a motion model (include/yfv2.h yfv2_track_update_motion): every track carries a
         constant-velocity Kalman filter per coordinate cx, cy, w, h, a row is matched against the box the filter PREDICTS, and a track
         that is not seen coasts.  state: contiguous int32 (S, 8 + 32 * max_tracks).  std_pos, std_vel, std_meas: the filter's noise
         scales, relative to the track's width / height (finite, > 0).  Returns what track_update returns and, with box=True, after
         it track_box (B, R, 4) fp32: the filtered corners of each row's track, zero where a row has none."""
+        rule = (match_thres, class_aware, init_conf, max_misses, confirm_hits)
         motion = dict(std_pos=std_pos, std_vel=std_vel, std_meas=std_meas)
-        return self._track_update("track_update_motion", motion, box, dets, count, streams, state, max_tracks, match_thres, class_aware, init_conf,
-                                  max_misses, confirm_hits, fresh, out)
+        return tracking.update(self, "track_update_motion", dets, count, streams, state, max_tracks, rule, motion=motion, fresh=fresh, box=box, out=out)
 
     def track_update_appearance(self, dets, count, emb, streams, state, feat, max_tracks, match_thres=0.3, class_aware=True, init_conf=0.0,
-                                max_misses=30, confirm_hits=3, dim=128, prox_thres=0.5, app_thres=0.75, alpha=0.9, motion=None, two_pass=None,
-                                fresh=False, box=False, passes=False, cos=False, out=None):
+                                max_misses=30, confirm_hits=3, dim=_APP["dim"], prox_thres=_APP["prox_thres"], app_thres=_APP["app_thres"], alpha=_APP["alpha"],
+                                motion=None, two_pass=None, fresh=False, box=False, passes=False, cos=False, out=None):
         """The update of any layout and pass form with appearance association (include/yfv2.h yfv2_track_update_appearance;
         DESIGN.md 4.22).  emb: contiguous fp32 (B, R, dim) on the device, row r's embedding (a re-identification network's output for
         the row's crop; not necessarily normalised); feat: contiguous int32 (S, max_tracks * (4 + dim)), all zero = empty, the
@@ -594,103 +591,19 @@ class Engine:
         pass form returns (passes=True only with two_pass, box=True only with motion) and, with cos=True, last of all track_cos
         (B, R) fp32: the cosine of each matched row with its track's feature before this update, 0 elsewhere."""
         name = "track_update_appearance"
-        if motion is None or motion is False:
-            motion = None
-            if box:
-                raise ValueError(name + ": box=True needs motion")
-        else:
-            given = {} if motion is True else dict(motion)
-            motion = dict(std_pos=given.pop("std_pos", 1.0 / 20), std_vel=given.pop("std_vel", 1.0 / 160), std_meas=given.pop("std_meas", 1.0 / 20))
-            if given:
-                raise ValueError(name + ": motion takes std_pos, std_vel and std_meas, not %s" % sorted(given))
-        if two_pass is None or two_pass is False:
-            second = None
-            if passes:
-                raise ValueError(name + ": passes=True needs two_pass")
-        else:
-            given = {} if two_pass is True else dict(two_pass)
-            second = dict(high_conf=given.pop("high_conf", 0.5), low_conf=given.pop("low_conf", 0.1), match_thres_low=given.pop("match_thres_low", 0.5),
-                          tracked_only=given.pop("tracked_only", True))
-            if given:
-                raise ValueError(name + ": two_pass takes high_conf, low_conf, match_thres_low and tracked_only, not %s" % sorted(given))
+        motion = tracking.option(name, "motion", motion, _MOT)
+        if box and motion is None:
+            raise ValueError(name + ": box=True needs motion")
+        second = tracking.option(name, "two_pass", two_pass, _TWO)
+        if passes and second is None:
+            raise ValueError(name + ": passes=True needs two_pass")
         dim = int(dim)
         if dim < 16 or dim > 2048 or dim % 16:
             raise ValueError(name + ": dim must be a multiple of 16 in 16..2048")
-        appearance = dict(dim=dim, prox_thres=prox_thres, app_thres=app_thres, alpha=alpha, emb=emb, feat=feat, cos=cos)
-        return self._track_update(name, motion, box, dets, count, streams, state, max_tracks, match_thres, class_aware, init_conf, max_misses,
-                                  confirm_hits, fresh, out, second=second, passes=passes, appearance=appearance)
-
-    def _track_update(self, name, motion, box, dets, count, streams, state, max_tracks, match_thres, class_aware, init_conf, max_misses, confirm_hits,
-                      fresh, out, second=None, passes=False, appearance=None):
-        """the checks and the call of every form; motion: None or the three stds; second: None or the two-pass form's four values;
-        appearance: None or the appearance form's four values with its emb, feat and cos"""
-        if (not torch.is_tensor(dets) or dets.dim() != 3 or dets.shape[2] != 6 or dets.dtype != torch.float32 or dets.device != self.device
-                or not dets.is_contiguous()):
-            raise ValueError(name + ": dets must be contiguous fp32 (B,R,6) on %s" % (self.device,))
-        B, R = int(dets.shape[0]), int(dets.shape[1])
-        if not torch.is_tensor(count) or tuple(count.shape) != (B,) or count.dtype != torch.int32 or count.device != self.device or not count.is_contiguous():
-            raise ValueError(name + ": count must be contiguous int32 (%d,) on %s" % (B, self.device))
-        streams = [int(s) for s in streams]
-        if len(streams) != B:
-            raise ValueError(name + ": %d streams for %d frames" % (len(streams), B))
-        max_tracks = int(max_tracks)
-        if not 1 <= max_tracks <= 1024:
-            raise ValueError(name + ": max_tracks must be in 1..1024")
-        words = 8 + (10 if motion is None else 32) * max_tracks
-        if (not torch.is_tensor(state) or state.dim() != 2 or state.shape[1] != words or state.dtype != torch.int32 or state.device != self.device
-                or not state.is_contiguous()):
-            raise ValueError(name + ": state must be contiguous int32 (S,%d) on %s" % (words, self.device))
-        S = int(state.shape[0])
-        cos = appearance is not None and bool(appearance["cos"])
-        if appearance is not None:
-            D, emb, feat = appearance["dim"], appearance["emb"], appearance["feat"]
-            if (not torch.is_tensor(emb) or tuple(emb.shape) != (B, R, D) or emb.dtype != torch.float32 or emb.device != self.device
-                    or not emb.is_contiguous()):
-                raise ValueError(name + ": emb must be contiguous fp32 (%d,%d,%d) on %s" % (B, R, D, self.device))
-            if (not torch.is_tensor(feat) or tuple(feat.shape) != (S, max_tracks * (4 + D)) or feat.dtype != torch.int32 or feat.device != self.device
-                    or not feat.is_contiguous()):
-                raise ValueError(name + ": feat must be contiguous int32 (%d,%d) on %s" % (S, max_tracks * (4 + D), self.device))
-        shapes = (((B, R), (B, R)) + (((B, R, 6), (B, R), (B,)) if fresh else ()) + (((B, R, 4),) if box else ()) + (((B, R),) if passes else ())
-                  + (((B, R),) if cos else ()))
-        dtypes = ((torch.int32, torch.int32) + ((torch.float32, torch.int32, torch.int32) if fresh else ()) + ((torch.float32,) if box else ())
-                  + ((torch.int32,) if passes else ()) + ((torch.float32,) if cos else ()))
-        if out is None:
-            out = tuple(torch.empty(sh, device=self.device, dtype=dt) for sh, dt in zip(shapes, dtypes))
-        else:
-            if len(out) != len(shapes):
-                raise ValueError(name + ": out must hold %d tensors" % len(shapes))
-            for t, sh, dt in zip(out, shapes, dtypes):
-                if not torch.is_tensor(t) or tuple(t.shape) != sh or t.dtype != dt or t.device != self.device or not t.is_contiguous():
-                    raise ValueError(name + ": out must be contiguous tensors of shapes %s on %s" % (shapes, self.device))
-        rule = _lib.TrackRule()
-        rule.max_tracks, rule.match_thres, rule.class_aware = max_tracks, float(match_thres), 1 if class_aware else 0
-        rule.init_conf, rule.max_misses, rule.confirm_hits = float(init_conf), int(max_misses), int(confirm_hits)
-        arr = (C.c_int32 * max(B, 1))(*streams)
-        tid, hits = _ptr(out[0]), _ptr(out[1])
-        fr = [_ptr(t) for t in out[2:5]] if fresh else [None] * 3
-        mo = None if motion is None else _lib.TrackMotion(float(motion["std_pos"]), float(motion["std_vel"]), float(motion["std_meas"]))
-        if appearance is not None:
-            se = None if second is None else _lib.TrackSecond(float(second["high_conf"]), float(second["low_conf"]), float(second["match_thres_low"]),
-                                                              1 if second["tracked_only"] else 0)
-            ap = _lib.TrackAppearance(appearance["dim"], float(appearance["prox_thres"]), float(appearance["app_thres"]), float(appearance["alpha"]))
-            at = 5 if fresh else 2                            # the optional outputs after the fresh ones: box, passes, cos
-            check(_lib.lib().yfv2_track_update_appearance(self._h, _ptr(dets), _ptr(count), R, B, arr, _ptr(state), S, C.byref(rule),
-                                                          None if mo is None else C.byref(mo), None if se is None else C.byref(se), C.byref(ap),
-                                                          _ptr(appearance["emb"]), _ptr(appearance["feat"]), tid, hits,
-                                                          _ptr(out[at + (1 if box else 0)]) if passes else None, _ptr(out[at]) if box else None,
-                                                          _ptr(out[-1]) if cos else None, *fr, _stream(self.device)), self._h)
-        elif second is not None:
-            se = _lib.TrackSecond(float(second["high_conf"]), float(second["low_conf"]), float(second["match_thres_low"]), 1 if second["tracked_only"] else 0)
-            check(_lib.lib().yfv2_track_update_two_pass(self._h, _ptr(dets), _ptr(count), R, B, arr, _ptr(state), S, C.byref(rule),
-                                                        None if mo is None else C.byref(mo), C.byref(se), tid, hits, _ptr(out[-1]) if passes else None,
-                                                        _ptr(out[5 if fresh else 2]) if box else None, *fr, _stream(self.device)), self._h)
-        elif motion is None:
-            check(_lib.lib().yfv2_track_update(self._h, _ptr(dets), _ptr(count), R, B, arr, _ptr(state), S, C.byref(rule), tid, hits, *fr, _stream(self.device)),
-                  self._h)
-        else:
-            check(_lib.lib().yfv2_track_update_motion(self._h, _ptr(dets), _ptr(count), R, B, arr, _ptr(state), S, C.byref(rule), C.byref(mo), tid, hits,
-                                                      _ptr(out[-1]) if box else None, *fr, _stream(self.device)), self._h)
-        return out
+        rule = (match_thres, class_aware, init_conf, max_misses, confirm_hits)
+        appearance = dict(dim=dim, prox_thres=prox_thres, app_thres=app_thres, alpha=alpha)
+        return tracking.update(self, name, dets, count, streams, state, max_tracks, rule, motion=motion, second=second, appearance=appearance, emb=emb,
+                               feat=feat, fresh=fresh, box=box, passes=passes, cos=cos, out=out)
 
     # ---- the ncnn sample's deployment path (include/yfv2.h yfv2_export_maps / yfv2_deploy_post; DESIGN.md 4.14) ------------------
     def map_shapes(self, B):

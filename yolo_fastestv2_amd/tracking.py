@@ -31,7 +31,11 @@ fits better, keeps its id.  It combines with motion and two_pass:
     emb = reid(crops)                                                                    # the caller's network -> (B, R, 128) fp32
     track_id, track_hits, track_cos = tr.update(dets, count, emb=emb, cos=True)
 """
+import ctypes as C
+
 import torch
+
+from . import _lib
 
 HEADER_WORDS, SLOT_WORDS = 8, 10
 MOTION_SLOT_WORDS, FILTER_WORD = 32, 10          # the motion form's slot; its filters: words 10..29, cx, cy, w, h as x, v, p00, p01, p11
@@ -40,6 +44,113 @@ TWO_PASS_DEFAULTS = dict(high_conf=0.5, low_conf=0.1, match_thres_low=0.5, track
 APPEARANCE_DEFAULTS = dict(dim=128, prox_thres=0.5, app_thres=0.75, alpha=0.9)
 FEATURE_HEAD_WORDS = 4                           # a track's feature: n_feat, three zero words, then dim fp32
 HEADER_FIELDS = ("issued", "live", "frames", "births", "deaths", "dropped")
+
+
+class _Completed(dict):
+    """what option() returns: handing it to option() again (Tracker.update does, on every call) costs nothing"""
+
+
+def option(caller, name, value, defaults):
+    """The rule of motion / two_pass / appearance, for every caller that takes one: None or False - the form is off, None; True or a
+    dict with any of the defaults' keys - the completed dict, each value as the type of its default."""
+    if value is None or value is False:
+        return None
+    if type(value) is _Completed:
+        return value
+    given = {} if value is True else dict(value)
+    if given.keys() - defaults.keys():
+        keys = list(defaults)
+        raise ValueError("%s: %s takes %s and %s, not %s" % (caller, name, ", ".join(keys[:-1]), keys[-1], sorted(given.keys() - defaults.keys())))
+    return _Completed((k, type(v)(given[k]) if k in given else v) for k, v in defaults.items())
+
+
+def outputs(B, R, fresh=False, box=False, passes=False, cos=False):
+    """What an update returns, in order: a list of (name, shape, dtype).  Allocation, the check of a caller's `out` and the pointers
+    of the native call all read it by name; a new optional output is one line here."""
+    i32, f32 = torch.int32, torch.float32
+    out = [("track_id", (B, R), i32), ("track_hits", (B, R), i32)]
+    if fresh:
+        out += [("fresh_dets", (B, R, 6), f32), ("fresh_src", (B, R), i32), ("fresh_count", (B,), i32)]
+    if box:
+        out.append(("track_box", (B, R, 4), f32))
+    if passes:
+        out.append(("track_pass", (B, R), i32))
+    if cos:
+        out.append(("track_cos", (B, R), f32))
+    return out
+
+
+# The native call of a form - the entry point that takes the LAST of motion, second, appearance that is given - and what it takes
+# between the rule and the three fresh outputs, by name (include/yfv2.h): the structs, emb and feat, and the outputs (None: absent).
+_FRESH = ("fresh_dets", "fresh_src", "fresh_count")
+_NATIVE = {
+    None: ("yfv2_track_update", ("track_id", "track_hits")),
+    "motion": ("yfv2_track_update_motion", ("motion", "track_id", "track_hits", "track_box")),
+    "second": ("yfv2_track_update_two_pass", ("motion", "second", "track_id", "track_hits", "track_pass", "track_box")),
+    "appearance": ("yfv2_track_update_appearance", ("motion", "second", "appearance", "emb", "feat", "track_id", "track_hits", "track_pass", "track_box",
+                                                    "track_cos")),
+}
+_NATIVE = {form: (native, takes + _FRESH) for form, (native, takes) in _NATIVE.items()}
+
+
+def update(engine, name, dets, count, streams, state, max_tracks, rule, motion=None, second=None, appearance=None, emb=None, feat=None, fresh=False,
+           box=False, passes=False, cos=False, out=None):
+    """The checks and the call of every form, on engine's handle, device and current stream (Engine.track_update* are this).  rule:
+    (match_thres, class_aware, init_conf, max_misses, confirm_hits); motion: None or the three stds; second: None or the two-pass
+    form's four values; appearance: None or the appearance form's four values, with emb and feat."""
+    device = engine.device
+    if (not torch.is_tensor(dets) or dets.dim() != 3 or dets.shape[2] != 6 or dets.dtype != torch.float32 or dets.device != device
+            or not dets.is_contiguous()):
+        raise ValueError(name + ": dets must be contiguous fp32 (B,R,6) on %s" % (device,))
+    B, R = int(dets.shape[0]), int(dets.shape[1])
+    if not torch.is_tensor(count) or tuple(count.shape) != (B,) or count.dtype != torch.int32 or count.device != device or not count.is_contiguous():
+        raise ValueError(name + ": count must be contiguous int32 (%d,) on %s" % (B, device))
+    streams = [int(s) for s in streams]
+    if len(streams) != B:
+        raise ValueError(name + ": %d streams for %d frames" % (len(streams), B))
+    max_tracks = int(max_tracks)
+    if not 1 <= max_tracks <= 1024:
+        raise ValueError(name + ": max_tracks must be in 1..1024")
+    words = HEADER_WORDS + (SLOT_WORDS if motion is None else MOTION_SLOT_WORDS) * max_tracks
+    if (not torch.is_tensor(state) or state.dim() != 2 or state.shape[1] != words or state.dtype != torch.int32 or state.device != device
+            or not state.is_contiguous()):
+        raise ValueError(name + ": state must be contiguous int32 (S,%d) on %s" % (words, device))
+    S = int(state.shape[0])
+    if appearance is not None:
+        D = appearance["dim"]
+        if (not torch.is_tensor(emb) or tuple(emb.shape) != (B, R, D) or emb.dtype != torch.float32 or emb.device != device
+                or not emb.is_contiguous()):
+            raise ValueError(name + ": emb must be contiguous fp32 (%d,%d,%d) on %s" % (B, R, D, device))
+        if (not torch.is_tensor(feat) or tuple(feat.shape) != (S, max_tracks * (FEATURE_HEAD_WORDS + D)) or feat.dtype != torch.int32
+                or feat.device != device or not feat.is_contiguous()):
+            raise ValueError(name + ": feat must be contiguous int32 (%d,%d) on %s" % (S, max_tracks * (FEATURE_HEAD_WORDS + D), device))
+    desc = outputs(B, R, fresh, box, passes, cos)
+    if out is None:
+        out = tuple(torch.empty(sh, device=device, dtype=dt) for _, sh, dt in desc)
+    else:
+        if len(out) != len(desc):
+            raise ValueError(name + ": out must hold %d tensors" % len(desc))
+        for t, (_, sh, dt) in zip(out, desc):
+            if not torch.is_tensor(t) or tuple(t.shape) != sh or t.dtype != dt or t.device != device or not t.is_contiguous():
+                raise ValueError(name + ": out must be contiguous tensors of shapes %s on %s" % (tuple(sh for _, sh, _ in desc), device))
+    arg = {key: t.data_ptr() for (key, _, _), t in zip(desc, out)}      # the prototypes (_lib.py) take addresses as ints
+    match_thres, class_aware, init_conf, max_misses, confirm_hits = rule
+    ru = _lib.TrackRule()
+    ru.max_tracks, ru.match_thres, ru.class_aware = max_tracks, float(match_thres), 1 if class_aware else 0
+    ru.init_conf, ru.max_misses, ru.confirm_hits = float(init_conf), int(max_misses), int(confirm_hits)
+    if motion is not None:
+        mo = _lib.TrackMotion(float(motion["std_pos"]), float(motion["std_vel"]), float(motion["std_meas"]))
+        arg["motion"] = C.byref(mo)
+    if second is not None:
+        se = _lib.TrackSecond(float(second["high_conf"]), float(second["low_conf"]), float(second["match_thres_low"]), 1 if second["tracked_only"] else 0)
+        arg["second"] = C.byref(se)
+    if appearance is not None:
+        ap = _lib.TrackAppearance(D, float(appearance["prox_thres"]), float(appearance["app_thres"]), float(appearance["alpha"]))
+        arg["appearance"], arg["emb"], arg["feat"] = C.byref(ap), emb.data_ptr(), feat.data_ptr()
+    native, takes = _NATIVE["appearance" if appearance is not None else "second" if second is not None else "motion" if motion is not None else None]
+    _lib.check(getattr(_lib.lib(), native)(engine._h, dets.data_ptr(), count.data_ptr(), R, B, (C.c_int32 * max(B, 1))(*streams), state.data_ptr(), S, C.byref(ru),
+                                           *map(arg.get, takes), torch.cuda.current_stream(device).cuda_stream), engine._h)
+    return out
 
 
 class Tracker:
@@ -63,30 +174,11 @@ class Tracker:
             raise ValueError("Tracker: streams must be >= 1 and max_tracks in 1..1024")
         self.rule = dict(match_thres=float(match_thres), class_aware=bool(class_aware), init_conf=float(init_conf), max_misses=int(max_misses),
                          confirm_hits=int(confirm_hits))
-        if motion is None or motion is False:
-            self.motion = None
-        else:
-            given = {} if motion is True else dict(motion)
-            if set(given) - set(MOTION_DEFAULTS):
-                raise ValueError("Tracker: motion takes std_pos, std_vel and std_meas, not %s" % sorted(set(given) - set(MOTION_DEFAULTS)))
-            self.motion = {k: float(given.get(k, v)) for k, v in MOTION_DEFAULTS.items()}
-        if two_pass is None or two_pass is False:
-            self.two_pass = None
-        else:
-            given = {} if two_pass is True else dict(two_pass)
-            if set(given) - set(TWO_PASS_DEFAULTS):
-                raise ValueError("Tracker: two_pass takes high_conf, low_conf, match_thres_low and tracked_only, not %s"
-                                 % sorted(set(given) - set(TWO_PASS_DEFAULTS)))
-            self.two_pass = {k: type(v)(given.get(k, v)) for k, v in TWO_PASS_DEFAULTS.items()}
-        if appearance is None or appearance is False:
-            self.appearance = None
-        else:
-            given = {} if appearance is True else dict(appearance)
-            if set(given) - set(APPEARANCE_DEFAULTS):
-                raise ValueError("Tracker: appearance takes dim, prox_thres, app_thres and alpha, not %s" % sorted(set(given) - set(APPEARANCE_DEFAULTS)))
-            self.appearance = {k: type(v)(given.get(k, v)) for k, v in APPEARANCE_DEFAULTS.items()}
-            if not 16 <= self.appearance["dim"] <= 2048 or self.appearance["dim"] % 16:
-                raise ValueError("Tracker: appearance dim must be a multiple of 16 in 16..2048")
+        self.motion = option("Tracker", "motion", motion, MOTION_DEFAULTS)
+        self.two_pass = option("Tracker", "two_pass", two_pass, TWO_PASS_DEFAULTS)
+        self.appearance = option("Tracker", "appearance", appearance, APPEARANCE_DEFAULTS)
+        if self.appearance is not None and (not 16 <= self.appearance["dim"] <= 2048 or self.appearance["dim"] % 16):
+            raise ValueError("Tracker: appearance dim must be a multiple of 16 in 16..2048")
         self.slot_words = SLOT_WORDS if self.motion is None else MOTION_SLOT_WORDS
         self.state = torch.zeros((self.streams, HEADER_WORDS + self.slot_words * self.max_tracks), dtype=torch.int32, device=engine.device)
         self.feat = None
