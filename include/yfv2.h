@@ -295,7 +295,7 @@ YFV2_API int yfv2_detect_tiled_u8(yfv2_handle h, const yfv2_frame* frames, int32
  *                  8 bits first.  Every literal is rint(k * 2^20) of the real coefficient per 10-bit code - limited range: luma
  *                  255 / (219 * 4), chroma 255 / (224 * 4) times 2(1-Kr), -2Kr(1-Kr)/Kg, -2Kb(1-Kb)/Kg, 2(1-Kb); full range:
  *                  255 / 1023 in place of both; Kr / Kb = 0.299 / 0.114 (BT.601), 0.2126 / 0.0722 (BT.709).  These are NOT OpenCV
- *                  literals: cv2 has no P010 conversion to agree with (tests/yuv16_model.py re-derives them in float64).
+ *                  literals: cv2 has no P010 conversion to agree with (tests/yuv_model.py re-derives them in float64).
  *                                        off  CY      CVR     CVG      CUG      CUB
  *                    YFV2_BT601_LIMITED  64   305236  418389  -213115  -102698  528805
  *                    YFV2_BT709_LIMITED  64   305236  469956  -139699  -55902   553753

@@ -1,11 +1,13 @@
 """The LDS of a workgroup of the row kernels (yfv2_pre.hip: resize_frames_u8_kernel / resize_frames_yuv_kernel) and the width
-limits the frame entry points derive from it, restated once for all five row kinds and both frame kinds - what the kernels'
+limits the frame entry points derive from it, restated once for all five row kinds and all four frame kinds - what the kernels'
 staging needs, written from that need and not from the library's expressions.  tests/test_rows_host.py sweeps the library
-(yfv2_debug_rows) against this file; the GPU tests take their at-the-limit widths from here.
+(yfv2_debug_rows, yfv2_debug_rows16, yfv2_debug_rows_any) against this file; the GPU tests take their at-the-limit widths from here.
 """
 LDS_FULL = 160 * 1024
 U8, COUNTED_U8, TRAIN, TENSOR_F32, TENSOR_F16 = range(5)     # yfv2_debug_rows' row_kind
 KINDS = (U8, COUNTED_U8, TRAIN, TENSOR_F32, TENSOR_F16)
+KIND_IDS = ["u8", "counted_u8", "train", "tensor_f32", "tensor_f16"]
+BGR, YUV8, YUV16, YUV8_ANY = range(4)                          # the frame kinds: B, G, R; YUV 4:2:0 of 1-byte and of 2-byte samples; any 8-bit YUV
 TABLE_BYTES = 256 * 4                                          # the training rows' augmentation table
 
 
@@ -24,32 +26,37 @@ def slot(n, a):
     return (n + 3 + a - 1) // a * a
 
 
-def lds_bytes(kind, is_yuv, w, W):
-    """B, G, R: two source rows of 3 w bytes.  YUV: two luma rows of w bytes and two chroma rows, each either one interleaved row of
-    2 * (w // 2 + 1) bytes or two planar rows of w // 2 + 1 in a half-slot each (two half-slots hold the interleaved row)."""
+def lds_bytes(kind, frames, w, W):
+    """B, G, R: two source rows of 3 w bytes.  YUV 4:2:0 of sb-byte samples: two luma rows of sb w bytes and two chroma rows, each
+    either one interleaved row of 2 sb (w // 2 + 1) bytes or two planar rows of sb (w // 2 + 1) in a half-slot each (two half-slots
+    hold the interleaved row).  The general launch: six slots of w bytes, a group of three per blended source row ([luma][U][V]; an
+    interleaved row lies over U and V, a packed row over all three).  Then the row kind's own bytes."""
     a = align(kind)
-    if not is_yuv:
+    if frames == BGR:
         return 2 * slot(3 * w, a) + own_bytes(kind, W)
-    half = slot(w // 2 + 1, a)
-    assert 2 * half >= slot(2 * (w // 2 + 1), a)
-    return 2 * slot(w, a) + 2 * 2 * half + own_bytes(kind, W)
+    if frames == YUV8_ANY:
+        return 6 * slot(w, a) + own_bytes(kind, W)
+    sb = 2 if frames == YUV16 else 1
+    half = slot(sb * (w // 2 + 1), a)
+    assert 2 * half >= slot(2 * sb * (w // 2 + 1), a)
+    return 2 * slot(sb * w, a) + 2 * 2 * half + own_bytes(kind, W)
 
 
-def exact_max_width(kind, is_yuv, W):
+def exact_max_width(kind, frames, W):
     """the widest frame with lds_bytes <= a CU's LDS, by bisection on a function that never falls (1 if none fits)"""
     lo, hi = 1, LDS_FULL
     while lo < hi:
         mid = (lo + hi + 1) // 2
-        if lds_bytes(kind, is_yuv, mid, W) <= LDS_FULL:
+        if lds_bytes(kind, frames, mid, W) <= LDS_FULL:
             lo = mid
         else:
             hi = mid - 1
     return lo
 
 
-def max_width(kind, is_yuv, W):
+def max_width(kind, frames, W):
     """the limit the entry points enforce (include/yfv2.h).  YUV: the exact maximum.  B, G, R: a closed form - a slot is at most
     3 w + align + 2 bytes - which lies a few pixels below the exact maximum."""
-    if is_yuv:
-        return exact_max_width(kind, True, W)
+    if frames != BGR:
+        return exact_max_width(kind, frames, W)
     return (LDS_FULL - own_bytes(kind, W)) // 6 - (align(kind) + 2) // 3

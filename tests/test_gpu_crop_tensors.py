@@ -343,7 +343,7 @@ def test_batch_independence(eng, scene):
 
 def _limit(out_w, half):
     """the width limit of the B, G, R entry point (include/yfv2.h)"""
-    return rows_model.max_width(rows_model.TENSOR_F16 if half else rows_model.TENSOR_F32, False, out_w)
+    return rows_model.max_width(rows_model.TENSOR_F16 if half else rows_model.TENSOR_F32, rows_model.BGR, out_w)
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float16])

@@ -7,7 +7,6 @@ include/yfv2.h (tests/yuv_model.py states it in numpy) and passing it to the exi
 comparison is exact.
 """
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
@@ -15,65 +14,18 @@ import torch
 
 import rows_model
 import yuv_model as ym
-from frames_ref import MAX_DET
-from oracle import yfv2_oracle as oracle
+from yuv_frames import (SENTINEL, _bgr, _out, _picture, _plane_set, _ptr, _same, _to, check_detect_frames, check_detect_tiled, check_pipeline,
+                        check_widest_frame_and_limit, dev, engine, new_engine, yfv2)  # noqa: F401  (the fixtures, by name)
 
 pytestmark = pytest.mark.gpu
-
-SENTINEL = -12345.0
-
-
-@pytest.fixture(scope="module")
-def yfv2():
-    import yolo_fastestv2_amd
-    assert torch.cuda.is_available(), "-m gpu tests need an MI355X"
-    assert os.path.exists(yolo_fastestv2_amd.LIB_PATH), "libyfv2.so not built"
-    return yolo_fastestv2_amd
-
-
-@pytest.fixture(scope="module")
-def dev():
-    return torch.device("cuda:0")
-
-
-def _engine(yfv2, dev, cfg, weights, max_batch):
-    eng = yfv2.Engine(dev, cfg["height"], cfg["width"], cfg["classes"], cfg["anchor_num"], anchors=cfg["anchors"], max_batch=max_batch, plan={})
-    eng.load_state_dict(weights)
-    return eng
-
-
-@pytest.fixture(scope="module")
-def engine(yfv2, dev, cfg, coco_weights):
-    return _engine(yfv2, dev, cfg, coco_weights, 16)
-
-
-def _out(eng, B):
-    dets, idx, cnt = eng.new_det_buffers(B)
-    dets.fill_(SENTINEL)
-    idx.fill_(-7)
-    cnt.fill_(-9)
-    return dets, idx, cnt
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def _to(dev, planes):
-    return tuple(torch.from_numpy(np.ascontiguousarray(p)).to(dev) for p in planes)
-
-
-def _same_words(got, want, what):
-    g, w = got.cpu().numpy(), want.cpu().numpy()
-    bad = np.argwhere(g.view(np.uint32 if g.dtype.itemsize == 4 else np.uint8) != w.view(np.uint32 if w.dtype.itemsize == 4 else np.uint8))
-    assert bad.size == 0, "%s: %d words differ, first at %s: %r vs %r" % (what, len(bad), bad[0].tolist(), g[tuple(bad[0])], w[tuple(bad[0])])
+FORMATS = ym.FORMATS420
 
 
 # ---- 1. resize equals convert-then-resize ------------------------------------------------------------------------------------
 SIZES_WH = [(1, 1), (2, 2), (3, 5), (5, 3), (7, 9), (33, 47), (351, 353), (352, 352), (640, 480), (1279, 721)]
 
 
-@pytest.mark.parametrize("fmt", ym.FORMATS, ids=["nv12", "nv21", "i420"])
+@pytest.mark.parametrize("fmt", FORMATS, ids=["nv12", "nv21", "i420"])
 def test_resize_yuv_is_convert_then_resize(yfv2, dev, fmt):
     """One ragged batch: every size of the list (1 x 1 up to 1279 x 721, 352 x 352 being the identity resize - the pure conversion),
     each with the colour standard k % 4, and the 7 x 9 and 640 x 480 frames once more under each of the other three standards.
@@ -93,14 +45,14 @@ def test_resize_yuv_is_convert_then_resize(yfv2, dev, fmt):
     want = eng.resize_frames(bgr)
     assert got.dtype == torch.uint8 and tuple(got.shape) == (len(items), 352, 352, 3)
     for b, (w, h, colour) in enumerate(items):
-        _same_words(got[b], want[b], "frame %d (%d x %d, colour %d)" % (b, w, h, colour))
+        _same(got[b], want[b], "frame %d (%d x %d, colour %d)" % (b, w, h, colour))
     k = SIZES_WH.index((352, 352))
     assert torch.equal(got[k], bgr[k]), "the identity resize is the pure conversion"
     assert bool((got == 0).any()) and bool((got == 255).any())
 
 
 # ---- 2. crops ----------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("fmt", ym.FORMATS, ids=["nv12", "nv21", "i420"])
+@pytest.mark.parametrize("fmt", FORMATS, ids=["nv12", "nv21", "i420"])
 def test_crops_of_padded_planes_at_odd_addresses(yfv2, dev, fmt):
     """One 97 x 131 plane set in ONE byte tensor that ends with the last plane's last byte: the luma plane at byte offset 1, the
     chroma plane(s) at offsets that are 3 (and 2) mod 4, each allocated exactly ((rows - 1) * pitch + width bytes), odd pitches, the
@@ -109,20 +61,8 @@ def test_crops_of_padded_planes_at_odd_addresses(yfv2, dev, fmt):
     rows, cols = 97, 131
     planes = ym.random_planes(rng, rows, cols, fmt)
     pitches = [137] + [planes[1].shape[1] + 5] * (len(planes) - 1)
-    flats = [ym.pad_plane(p, q) for p, q in zip(planes, pitches)]
-    offs, o = [], 0
-    for k, f in enumerate(flats):
-        o += ((1, 3, 2)[k] - o) % 4
-        offs.append(o)
-        o += len(f)
-    host = np.full(o, ym.POISON, np.uint8)
-    for f, q in zip(flats, offs):
-        host[q:q + len(f)] = f
-    flat = torch.from_numpy(host).to(dev)
-    assert flat.data_ptr() % 4 == 0 and [q % 4 for q in offs] == [1, 3, 2][:len(offs)] and offs[-1] + len(flats[-1]) == flat.numel()
-    views = tuple(torch.as_strided(flat, p.shape, (q, 1), off) for p, q, off in zip(planes, pitches, offs))
-    for v, p in zip(views, planes):
-        assert np.array_equal(v.cpu().numpy(), p)
+    flat, host, views, offs = _plane_set(dev, planes, pitches, [(1, 4), (3, 4), (2, 4)])
+    assert [q % 4 for q in offs] == [1, 3, 2][:len(offs)]
     rects = []
     for x0, y0 in ((0, 0), (1, 0), (0, 1), (1, 1)):
         rects.append((x0, y0, cols - x0, rows - y0))                   # ends on the last row and column
@@ -135,50 +75,22 @@ def test_crops_of_padded_planes_at_odd_addresses(yfv2, dev, fmt):
     got = eng.resize_frames_yuv(frames)
     want = eng.resize_frames(bgr)
     for b, r in enumerate(rects):
-        _same_words(got[b], want[b], "crop %d %s" % (b, r))
+        _same(got[b], want[b], "crop %d %s" % (b, r))
     # a frame made with crop() is the same descriptor
     again = eng.resize_frames_yuv([yfv2.YuvFrame(views, fmt, 1).crop(*rects[4])])
-    _same_words(again[0], eng.resize_frames([torch.from_numpy(ym.yuv_to_bgr(planes, fmt, 1, *rects[4])).to(dev)])[0], "crop()")
+    _same(again[0], eng.resize_frames([torch.from_numpy(ym.yuv_to_bgr(planes, fmt, 1, *rects[4])).to(dev)])[0], "crop()")
     assert np.array_equal(flat.cpu().numpy(), host)
 
 
 # ---- 3. the widest frame, and one pixel more -----------------------------------------------------------------------------------
 def test_widest_frame_and_the_limit(yfv2, dev, engine):
-    from yolo_fastestv2_amd import _lib
-    limit = rows_model.max_width(rows_model.U8, True, 352)
+    limit = rows_model.max_width(rows_model.U8, rows_model.YUV8, 352)
     assert limit == yfv2.yuv.max_width(352) == 40689
-    rng = np.random.default_rng(300)
-    eng = yfv2.Engine(dev, 352, 352, max_batch=3, plan={})
-    frames, bgr = [], []
-    for fmt in ym.FORMATS:
-        planes = ym.random_planes(rng, 2, limit, fmt)
-        frames.append(yfv2.YuvFrame(_to(dev, planes), fmt, ym.BT709_FULL))
-        bgr.append(ym.yuv_to_bgr(planes, fmt, ym.BT709_FULL, 0, 0, limit, 2))
-    got = eng.resize_frames_yuv(frames)
-    for b in range(3):
-        # (wider than the B, G, R entry point admits: the reference is the oracle's resize, which test_gpu_frames pins it to)
-        assert np.array_equal(got[b].cpu().numpy(), oracle.resize_linear_u8(bgr[b], 352, 352)), b
-    # limit + 1: refused with a message, nothing launched
     wide = yfv2.YuvFrame((torch.zeros((2, limit + 1), dtype=torch.uint8, device=dev), torch.zeros((1, limit + 2), dtype=torch.uint8, device=dev)), "nv12")
-    dst = torch.full((2, 352, 352, 3), 77, dtype=torch.uint8, device=dev)
-    out = _out(engine, 2)
-    torch.cuda.synchronize()
-    for call in (lambda: eng.resize_frames_yuv([frames[0], wide], out=dst), lambda: engine.detect_frames_yuv([frames[0], wide], 0.3, 0.4, out=out)):
-        with pytest.raises(_lib.Yfv2Error) as e:
-            call()
-        assert e.value.code == _lib.ERR_ARG and "frame 1" in str(e.value) and "wider than %d" % limit in str(e.value), str(e.value)
-    torch.cuda.synchronize()
-    assert bool((dst == 77).all()) and bool((out[0] == SENTINEL).all()) and bool((out[2] == -9).all()), "a failed call wrote its output"
+    check_widest_frame_and_limit(yfv2, dev, engine, np.random.default_rng(300), FORMATS, limit, [wide], by_oracle=True)
 
 
 # ---- 4. detection ----------------------------------------------------------------------------------------------------------------
-def _picture(images_u8, k, h, w, seed):
-    hwc = np.ascontiguousarray(images_u8[k % len(images_u8)].transpose(1, 2, 0))
-    rng = np.random.default_rng(seed)
-    f = oracle.resize_linear_u8(hwc, w, h)
-    return np.clip(f.astype(np.int16) + rng.integers(-3, 4, f.shape), 0, 255).astype(np.uint8)
-
-
 @pytest.fixture(scope="module")
 def nv12_batch(yfv2, dev, images_u8):
     """a mixed-size batch of NV12 frames made from the reference pictures, and the same frames converted by the model: computed once"""
@@ -187,78 +99,40 @@ def nv12_batch(yfv2, dev, images_u8):
     for k, (h, w) in enumerate(sizes):
         planes = ym.bgr_to_nv12(_picture(images_u8, k, h, w, 500 + k))
         frames.append(yfv2.YuvFrame(_to(dev, planes), "nv12", "bt601"))
-        bgr.append(torch.from_numpy(ym.yuv_to_bgr(planes, ym.NV12, ym.BT601_LIMITED, 0, 0, w, h)).to(dev))
+        bgr.append(_bgr(dev, ym.yuv_to_bgr(planes, ym.NV12, ym.BT601_LIMITED, 0, 0, w, h)))
     return frames, bgr
 
 
 @pytest.mark.parametrize("conf", [0.3, 0.01])
 def test_detect_frames_yuv_is_detect_frames_on_the_converted_frames(engine, nv12_batch, conf):
-    frames, bgr = nv12_batch
-    B = len(frames)
-    got = engine.detect_frames_yuv(frames, conf, 0.4, out=_out(engine, B))
-    want = engine.detect_frames(bgr, conf, 0.4, out=_out(engine, B))
-    assert torch.equal(got[2], want[2]), (got[2].tolist(), want[2].tolist())
-    assert torch.equal(got[1], want[1])
-    _same_words(got[0], want[0], "dets at conf %g" % conf)
+    want = check_detect_frames(engine, *nv12_batch, conf)
     assert int((want[2] > 0).sum()) >= 4, want[2].tolist()
     # frame coordinates: a box of the 1920-wide frame reaches beyond the network's 352 columns
     assert float(want[0][1, :int(want[2][1]), 2].max()) > 352.0
 
 
-def test_detect_tiled_yuv_is_detect_tiled_on_the_converted_frames(yfv2, engine, dev, images_u8):
-    """F = 2 frames of 500 x 420; 352 x 352 tiles 75 pixels apart, so a column of tiles starts at x = 75: odd origins read in place"""
-    tiles = [t for f in range(2) for t in yfv2.plan_tiles(420, 500, tile=(352, 352), overlap=(277, 277), frame=f)]
-    assert len(tiles) <= engine.max_batch and any(t[1] % 2 == 1 for t in tiles) and any(t[1] % 2 == 0 and t[1] > 0 for t in tiles)
+def _tiled_pair(yfv2, dev, images_u8):
     frames, bgr = [], []
     for f in range(2):
         planes = ym.bgr_to_nv12(_picture(images_u8, 1 + f, 420, 500, 600 + f))
         frames.append(yfv2.YuvFrame(_to(dev, planes), "nv12", "bt601"))
-        bgr.append(torch.from_numpy(ym.yuv_to_bgr(planes, ym.NV12, ym.BT601_LIMITED, 0, 0, 500, 420)).to(dev))
+        bgr.append(_bgr(dev, ym.yuv_to_bgr(planes, ym.NV12, ym.BT601_LIMITED, 0, 0, 500, 420)))
+    return frames, bgr
 
-    def buffers():
-        d, s, c = engine.new_tiled_buffers(2)
-        d.fill_(SENTINEL)
-        s.fill_(-7)
-        c.fill_(-9)
-        return d, s, c
 
-    got = engine.detect_tiled_yuv(frames, tiles=tiles, conf_thres=0.3, iou_thres=0.4, out=buffers())
-    want = engine.detect_tiled(bgr, tiles=tiles, conf_thres=0.3, iou_thres=0.4, out=buffers())
-    assert torch.equal(got[2], want[2]) and torch.equal(got[1], want[1]), (got[2].tolist(), want[2].tolist())
-    _same_words(got[0], want[0], "tiled dets")
-    assert int(want[2].sum()) > 0
-    # the plan made by the call itself (tiles=None) is the B, G, R call's plan
-    got = engine.detect_tiled_yuv(frames, conf_thres=0.3, iou_thres=0.4, overlap=(277, 277), out=buffers())
-    assert torch.equal(got[2], want[2]) and torch.equal(got[1], want[1])
-    _same_words(got[0], want[0], "tiled dets, planned by the call")
+def test_detect_tiled_yuv_is_detect_tiled_on_the_converted_frames(yfv2, engine, dev, images_u8):
+    check_detect_tiled(yfv2, engine, *_tiled_pair(yfv2, dev, images_u8), planned_by_the_call=True)
 
 
 def test_pipeline_submit_frames_yuv(yfv2, dev, cfg, coco_weights, engine, nv12_batch):
     frames, _ = nv12_batch
-    pipe = yfv2.DetectPipeline(dev, cfg["height"], cfg["width"], cfg["classes"], cfg["anchor_num"], anchors=cfg["anchors"], max_batch=8, depth=2, plan={})
-    pipe.load_state_dict(coco_weights)
-    batches = [frames[:3], frames, frames[2:6]]
-    tickets = [pipe.submit_frames_yuv(fr, 0.3, 0.4) for fr in batches[:2]]
-    results = [tuple(t.clone() for t in pipe.result(t)) for t in tickets]
-    torch.cuda.synchronize()      # the copies are complete before the third submit reuses the first slot
-    results.append(tuple(t.clone() for t in pipe.result(pipe.submit_frames_yuv(batches[2], 0.3, 0.4))))
-    pipe.synchronize()
-    total = 0
-    for (d, i, c), fr in zip(results, batches):
-        rd, ri, rc = engine.detect_frames_yuv(fr, 0.3, 0.4)
-        assert tuple(d.shape) == (len(fr), MAX_DET, 6) and torch.equal(c, rc)
-        for b in range(len(fr)):
-            k = int(c[b])
-            total += k
-            assert torch.equal(i[b, :k], ri[b, :k])
-            _same_words(d[b, :k], rd[b, :k], "pipeline frame %d" % b)
-    assert total > 0
+    check_pipeline(yfv2, dev, cfg, coco_weights, engine, [(frames[:3], None), (frames, None), (frames[2:6], None)], 8)
 
 
 # ---- 5. argument errors ------------------------------------------------------------------------------------------------------------
 def test_yuv_argument_errors_launch_nothing(yfv2, dev, cfg, coco_weights, nv12_batch):
     from yolo_fastestv2_amd import _lib
-    eng = _engine(yfv2, dev, cfg, coco_weights, 4)
+    eng = new_engine(yfv2, dev, cfg, coco_weights, 4)
     frames, bgr = nv12_batch
     y, uv = frames[0].planes           # 480 x 640
     u = torch.zeros((240, 320), dtype=torch.uint8, device=dev)
@@ -363,4 +237,4 @@ def test_yuv_argument_errors_launch_nothing(yfv2, dev, cfg, coco_weights, nv12_b
     got = eng.detect_frames_yuv(frames[:2], 0.3, 0.4, out=_out(eng, 2))
     want = eng.detect_frames(bgr[:2], 0.3, 0.4, out=_out(eng, 2))
     assert torch.equal(got[2], want[2]) and torch.equal(got[1], want[1])
-    _same_words(got[0], want[0], "after the errors")
+    _same(got[0], want[0], "after the errors")

@@ -3,79 +3,24 @@ I420, through every *_yuv entry point (include/yfv2.h YFV2_YUV_I422 .. YFV2_YUV_
 MI355X.
 
 One claim, everywhere: the result for such a frame is bit-identical to converting that frame to B, G, R with the integer rule of
-include/yfv2.h (tests/yuv_any_model.py states it in numpy) and passing it to the B, G, R entry point of the same name ON THE DEVICE.
+include/yfv2.h (tests/yuv_model.py states it in numpy) and passing it to the B, G, R entry point of the same name ON THE DEVICE.
 Every comparison is exact: the file has no tolerance.
 """
 import ctypes as C
-import os
 
 import numpy as np
 import pytest
 import torch
 
 import rows_model
-import yuv_any_model as ma
-from frames_ref import MAX_DET
-from oracle import yfv2_oracle as oracle
+import yuv_model as ym
+from yuv_frames import (SENTINEL, _bgr, _frame, _out, _pair, _picture, _plane_set, _ptr, _same, _to, check_crop_detections, check_crop_tensors, check_detect_frames,
+                        check_detect_tiled, check_pipeline, check_train_batch, check_widest_frame_and_limit, dev, engine, yfv2)  # noqa: F401  (the fixtures, by name)
 
 pytestmark = pytest.mark.gpu
-
-SENTINEL = -12345.0
-NEW = ma.NEW_FORMATS
-IDS = [ma.NAMES[f] for f in NEW]
-
-
-@pytest.fixture(scope="module")
-def yfv2():
-    import yolo_fastestv2_amd
-    assert torch.cuda.is_available(), "-m gpu tests need an MI355X"
-    assert os.path.exists(yolo_fastestv2_amd.LIB_PATH), "libyfv2.so not built"
-    return yolo_fastestv2_amd
-
-
-@pytest.fixture(scope="module")
-def dev():
-    return torch.device("cuda:0")
-
-
-@pytest.fixture(scope="module")
-def engine(yfv2, dev, cfg, coco_weights):
-    eng = yfv2.Engine(dev, cfg["height"], cfg["width"], cfg["classes"], cfg["anchor_num"], anchors=cfg["anchors"], max_batch=16, plan={})
-    eng.load_state_dict(coco_weights)
-    return eng
-
-
-def _out(eng, B):
-    dets, idx, cnt = eng.new_det_buffers(B)
-    dets.fill_(SENTINEL)
-    idx.fill_(-7)
-    cnt.fill_(-9)
-    return dets, idx, cnt
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr())
-
-
-def _to(dev, planes):
-    return tuple(torch.from_numpy(np.ascontiguousarray(p)).to(dev) for p in planes)
-
-
-def _bgr(dev, a):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
-def _same(got, want, what):
-    assert got.dtype == want.dtype and got.shape == want.shape, (what, got.dtype, want.dtype, tuple(got.shape), tuple(want.shape))
-    if not torch.equal(got, want):
-        g, w = got.cpu().numpy(), want.cpu().numpy()
-        view = {4: np.uint32, 2: np.uint16, 1: np.uint8}
-        bad = np.argwhere(g.view(view[g.dtype.itemsize]) != w.view(view[w.dtype.itemsize]))
-        raise AssertionError("%s: %d values differ, first at %s: %r vs %r" % (what, len(bad), bad[0].tolist(), g[tuple(bad[0])], w[tuple(bad[0])]))
-
-
-def _frame(yfv2, dev, planes, fmt, colour, *rect):
-    return yfv2.YuvFrame(_to(dev, planes), ma.NAMES[fmt], colour, *rect)
+NEW = ym.NEW_FORMATS
+FORMATS = ym.FORMATS8
+IDS = [ym.NAMES[f] for f in NEW]
 
 
 # ---- 1. resize equals convert-then-resize ------------------------------------------------------------------------------------
@@ -87,13 +32,13 @@ def test_resize_is_convert_then_resize(yfv2, dev, fmt):
     """One ragged batch at W = H = 352: one pixel, a macropixel and a half, odd ends, up-scaling (chroma rows coincide), 1:1 - the
     pure conversion - and down-scaling; bt601_full everywhere and all four colours on 17 x 31; random bytes over all of 0..255."""
     rng = np.random.default_rng(100 + fmt)
-    cases = [(w, h, ma.BT601_FULL) for w, h in SIZES_WH] + [(17, 31, c) for c in ma.COLOURS if c != ma.BT601_FULL]
+    cases = [(w, h, ym.BT601_FULL) for w, h in SIZES_WH] + [(17, 31, c) for c in ym.COLOURS if c != ym.BT601_FULL]
     eng = yfv2.Engine(dev, 352, 352, max_batch=len(cases), plan={})
     frames, bgr = [], []
     for w, h, colour in cases:
-        planes = ma.random_planes(rng, h, w, fmt)
-        frames.append(yfv2.YuvFrame(_to(dev, planes), ma.NAMES[fmt], colour, 0, 0, w, h))
-        bgr.append(_bgr(dev, ma.yuv_to_bgr(planes, fmt, colour, 0, 0, w, h)))
+        planes = ym.random_planes(rng, h, w, fmt)
+        frames.append(yfv2.YuvFrame(_to(dev, planes), ym.NAMES[fmt], colour, 0, 0, w, h))
+        bgr.append(_bgr(dev, ym.yuv_to_bgr(planes, fmt, colour, 0, 0, w, h)))
     got = eng.resize_frames_yuv(frames)
     want = eng.resize_frames(bgr)
     assert got.dtype == torch.uint8 and tuple(got.shape) == (len(cases), 352, 352, 3)
@@ -105,25 +50,9 @@ def test_resize_is_convert_then_resize(yfv2, dev, fmt):
 
 
 # ---- 2. crops of padded planes ---------------------------------------------------------------------------------------------------
-def _plane_set(dev, planes, delta, poison):
-    """the planes in ONE uint8 device tensor that ends with the last plane's last byte: every plane at an odd byte address, allocated
-    exactly ((rows - 1) * pitch + row bytes), pitch = row bytes + delta, `poison` in the padding and between the planes"""
-    pitches = [p.shape[1] + delta for p in planes]
-    flats = [ma.pad_plane(p, q, poison) for p, q in zip(planes, pitches)]
-    offs, o = [], 0
-    for f in flats:
-        o += 1 - o % 2
-        offs.append(o)
-        o += len(f)
-    host = np.full(o, poison, np.uint8)
-    for f, q in zip(flats, offs):
-        host[q:q + len(f)] = f
-    flat = torch.from_numpy(host).to(dev)
-    assert flat.data_ptr() % 4 == 0 and all(q % 2 == 1 for q in offs) and offs[-1] + len(flats[-1]) == flat.numel()
-    views = tuple(torch.as_strided(flat, p.shape, (q, 1), off) for p, q, off in zip(planes, pitches, offs))
-    for v, p in zip(views, planes):
-        assert np.array_equal(v.cpu().numpy(), p)
-    return flat, host, views
+def _odd_plane_set(dev, planes, delta, poison):
+    """every plane at an odd byte address, pitch = row bytes + delta"""
+    return _plane_set(dev, planes, [p.shape[1] + delta for p in planes], [(1, 2)] * 3, poison)[:3]
 
 
 @pytest.mark.parametrize("fmt", NEW, ids=IDS)
@@ -133,7 +62,7 @@ def test_crops_of_padded_planes_read_in_place(yfv2, dev, fmt):
     of the allocation), and one inside the picture with poison on both sides of every row.  Run again with another poison."""
     rng = np.random.default_rng(200 + fmt)
     rows, cols = 21, 37
-    planes = ma.random_planes(rng, rows, cols, fmt)
+    planes = ym.random_planes(rng, rows, cols, fmt)
     rects = []
     for x0, y0 in ((0, 0), (1, 0), (0, 1), (1, 1)):
         rects.append((x0, y0, cols - x0, rows - y0))
@@ -141,21 +70,21 @@ def test_crops_of_padded_planes_read_in_place(yfv2, dev, fmt):
     rects += [(cols - 1, rows - 1, 1, 1), (cols - 2, 0, 2, rows)]
     assert {(x0 & 1, y0 & 1) for x0, y0, _w, _h in rects} == {(0, 0), (1, 0), (0, 1), (1, 1)}
     eng = yfv2.Engine(dev, 352, 352, max_batch=len(rects), plan={})
-    want = eng.resize_frames([_bgr(dev, ma.yuv_to_bgr(planes, fmt, k % 4, *r)) for k, r in enumerate(rects)])
+    want = eng.resize_frames([_bgr(dev, ym.yuv_to_bgr(planes, fmt, k % 4, *r)) for k, r in enumerate(rects)])
     for delta in (1, 2, 3, 13):
         outs = []
-        for poison in (ma.POISON, 0x3C):
-            flat, host, views = _plane_set(dev, planes, delta, poison)
-            frames = [yfv2.YuvFrame(views, ma.NAMES[fmt], k % 4, *r) for k, r in enumerate(rects)]
+        for poison in (ym.POISON, 0x3C):
+            flat, host, views = _odd_plane_set(dev, planes, delta, poison)
+            frames = [yfv2.YuvFrame(views, ym.NAMES[fmt], k % 4, *r) for k, r in enumerate(rects)]
             outs.append(eng.resize_frames_yuv(frames))
             for b, r in enumerate(rects):
                 _same(outs[-1][b], want[b], "pitch + %d, poison %#x, crop %d %s" % (delta, poison, b, r))
             assert np.array_equal(flat.cpu().numpy(), host)
         assert torch.equal(outs[0], outs[1]), "the bytes around the planes changed the result"
     # crop() of a whole frame is the same descriptor
-    flat, host, views = _plane_set(dev, planes, 13, ma.POISON)
-    again = eng.resize_frames_yuv([yfv2.YuvFrame(views, ma.NAMES[fmt], 1, 0, 0, cols, rows).crop(*rects[3])])
-    _same(again[0], eng.resize_frames([_bgr(dev, ma.yuv_to_bgr(planes, fmt, 1, *rects[3]))])[0], "crop()")
+    flat, host, views = _odd_plane_set(dev, planes, 13, ym.POISON)
+    again = eng.resize_frames_yuv([yfv2.YuvFrame(views, ym.NAMES[fmt], 1, 0, 0, cols, rows).crop(*rects[3])])
+    _same(again[0], eng.resize_frames([_bgr(dev, ym.yuv_to_bgr(planes, fmt, 1, *rects[3]))])[0], "crop()")
 
 
 # ---- 3. one call mixes the formats --------------------------------------------------------------------------------------------------
@@ -167,11 +96,11 @@ def mixed(yfv2, dev):
     """nine frames, one of each 8-bit format, of different sizes and colours, and their model conversions: computed once"""
     rng = np.random.default_rng(300)
     frames, bgr = [], []
-    for k, (fmt, (w, h)) in enumerate(zip(ma.FORMATS, MIX_WH)):
-        planes = ma.random_planes(rng, h + 1, w + 3, fmt)
+    for k, (fmt, (w, h)) in enumerate(zip(FORMATS, MIX_WH)):
+        planes = ym.random_planes(rng, h + 1, w + 3, fmt)
         rect = (k % 3, k % 2, w, h)
         frames.append(_frame(yfv2, dev, planes, fmt, k % 4, *rect))
-        bgr.append(_bgr(dev, ma.yuv_to_bgr(planes, fmt, k % 4, *rect)))
+        bgr.append(_bgr(dev, ym.yuv_to_bgr(planes, fmt, k % 4, *rect)))
     return frames, bgr
 
 
@@ -180,12 +109,12 @@ def test_mixed_batch_is_each_frame_alone(yfv2, dev, mixed):
     eng = yfv2.Engine(dev, 352, 352, max_batch=9, plan={})
     got = eng.resize_frames_yuv(frames)
     want = eng.resize_frames(bgr)
-    for b, fmt in enumerate(ma.FORMATS):
-        _same(got[b], eng.resize_frames_yuv([frames[b]])[0], "%s alone" % ma.NAMES[fmt])
-        _same(got[b], want[b], "%s against the model" % ma.NAMES[fmt])
+    for b, fmt in enumerate(FORMATS):
+        _same(got[b], eng.resize_frames_yuv([frames[b]])[0], "%s alone" % ym.NAMES[fmt])
+        _same(got[b], want[b], "%s against the model" % ym.NAMES[fmt])
     only420 = eng.resize_frames_yuv(frames[:3])                      # the 4:2:0-only launch
     for b in range(3):
-        _same(got[b], only420[b], "%s in a 4:2:0-only call" % ma.NAMES[ma.FORMATS[b]])
+        _same(got[b], only420[b], "%s in a 4:2:0-only call" % ym.NAMES[FORMATS[b]])
     # the order of the frames does not matter either: the general frame last, first, in the middle
     back = eng.resize_frames_yuv(frames[::-1])
     for b in range(9):
@@ -195,41 +124,26 @@ def test_mixed_batch_is_each_frame_alone(yfv2, dev, mixed):
 # ---- 4. the widest frame, and the limits ----------------------------------------------------------------------------------------------
 def test_widest_frame_and_the_limits(yfv2, dev, engine):
     from yolo_fastestv2_amd import _lib
-    limit, limit420 = ma.max_width(rows_model.U8, 352), rows_model.max_width(rows_model.U8, True, 352)
+    limit, limit420 = rows_model.max_width(rows_model.U8, rows_model.YUV8_ANY, 352), rows_model.max_width(rows_model.U8, rows_model.YUV8, 352)
     assert limit == yfv2.yuv.max_width(352, general=True) == 27125 < limit420 == yfv2.yuv.max_width(352) == 40689
-    assert limit <= rows_model.max_width(rows_model.U8, False, 352)          # the B, G, R reference call admits the converted frame
+    assert limit <= rows_model.max_width(rows_model.U8, rows_model.BGR, 352)          # the B, G, R reference call admits the converted frame
     rng = np.random.default_rng(400)
-    eng = yfv2.Engine(dev, 352, 352, max_batch=2, plan={})
-    frames, bgr = [], []
-    for fmt in (ma.I444, ma.YUYV):
-        planes = ma.random_planes(rng, 2, limit, fmt)
-        frames.append(_frame(yfv2, dev, planes, fmt, ma.BT709_FULL, 0, 0, limit, 2))
-        bgr.append(_bgr(dev, ma.yuv_to_bgr(planes, fmt, ma.BT709_FULL, 0, 0, limit, 2)))
-    got = eng.resize_frames_yuv(frames)
-    want = eng.resize_frames(bgr)
-    for b in range(2):
-        _same(got[b], want[b], "the widest %s frame" % ("i444", "yuyv")[b])
-    # limit + 1: refused with the limit in the message, nothing launched
     z = lambda r, c: torch.zeros((r, c), dtype=torch.uint8, device=dev)
     wide444 = yfv2.YuvFrame((z(2, limit + 1), z(2, limit + 1), z(2, limit + 1)), "i444")
     wide_yuyv = yfv2.YuvFrame(z(2, 2 * (limit + 1)), "yuyv")
     assert wide_yuyv.width == limit + 1
+    eng, frames, dst, out = check_widest_frame_and_limit(yfv2, dev, engine, rng, (ym.I444, ym.YUYV), limit, [wide444, wide_yuyv])
     # an NV12 frame wider than the general limit and inside the 4:2:0 one: accepted alone, refused beside an I444 frame
     nv12_w = limit + 1001
     assert limit < nv12_w <= limit420
-    planes = ma.random_planes(rng, 2, nv12_w, ma.NV12)
-    nv12 = _frame(yfv2, dev, planes, ma.NV12, ma.BT601_FULL)
+    nv12 = _frame(yfv2, dev, ym.random_planes(rng, 2, nv12_w, ym.NV12), ym.NV12, ym.BT601_FULL)
     alone = eng.resize_frames_yuv([nv12])
     # (the B, G, R resize does not admit a frame that wide; the claim here is acceptance - the bytes of NV12 frames are tests/test_gpu_yuv.py's)
     assert tuple(alone.shape) == (1, 352, 352, 3)
-    dst = torch.full((2, 352, 352, 3), 77, dtype=torch.uint8, device=dev)
-    out = _out(engine, 2)
-    torch.cuda.synchronize()
-    for bad, who in ((wide444, 1), (wide_yuyv, 1), (nv12, 1)):
-        for call in (lambda: eng.resize_frames_yuv([frames[0], bad], out=dst), lambda: engine.detect_frames_yuv([frames[0], bad], 0.3, 0.4, out=out)):
-            with pytest.raises(_lib.Yfv2Error) as e:
-                call()
-            assert e.value.code == _lib.ERR_ARG and "frame %d" % who in str(e.value) and "wider than %d" % limit in str(e.value), str(e.value)
+    for call in (lambda: eng.resize_frames_yuv([frames[0], nv12], out=dst), lambda: engine.detect_frames_yuv([frames[0], nv12], 0.3, 0.4, out=out)):
+        with pytest.raises(_lib.Yfv2Error) as e:
+            call()
+        assert e.value.code == _lib.ERR_ARG and "frame 1" in str(e.value) and "wider than %d" % limit in str(e.value), str(e.value)
     with pytest.raises(_lib.Yfv2Error) as e:
         eng.resize_frames_yuv([nv12, frames[0]], out=dst)               # the batch's kind is not frame 0's: the NV12 frame comes first here
     assert "frame 0" in str(e.value) and "wider than %d" % limit in str(e.value) and "4:2:0" in str(e.value) and str(limit420) in str(e.value), str(e.value)
@@ -238,73 +152,35 @@ def test_widest_frame_and_the_limits(yfv2, dev, engine):
 
 
 # ---- 5. detection ----------------------------------------------------------------------------------------------------------------
-def _picture(images_u8, k, h, w, seed):
-    hwc = np.ascontiguousarray(images_u8[k % len(images_u8)].transpose(1, 2, 0))
-    rng = np.random.default_rng(seed)
-    f = oracle.resize_linear_u8(hwc, w, h)
-    return np.clip(f.astype(np.int16) + rng.integers(-3, 4, f.shape), 0, 255).astype(np.uint8)
-
-
 @pytest.fixture(scope="module")
 def picture_batch(yfv2, dev, images_u8):
     """a mixed-size, mixed-format batch made from the reference pictures, and the same frames converted by the model: computed once"""
     frames, bgr = [], []
-    for k, (fmt, (w, h)) in enumerate([(ma.I444, (352, 352)), (ma.YUYV, (480, 360)), (ma.NV12, (640, 480)), (ma.I422, (353, 301)), (ma.GREY, (400, 300)), (ma.I440, (500, 420))]):
-        planes = ma.from_i444(ma.bgr_to_i444(_picture(images_u8, k, h, w, 500 + k)), fmt)
+    for k, (fmt, (w, h)) in enumerate([(ym.I444, (352, 352)), (ym.YUYV, (480, 360)), (ym.NV12, (640, 480)), (ym.I422, (353, 301)), (ym.GREY, (400, 300)), (ym.I440, (500, 420))]):
+        planes = ym.from_i444(ym.bgr_to_i444(_picture(images_u8, k, h, w, 500 + k)), fmt)
         frames.append(_frame(yfv2, dev, planes, fmt, "jpeg", 0, 0, w, h))
-        bgr.append(_bgr(dev, ma.yuv_to_bgr(planes, fmt, ma.BT601_FULL, 0, 0, w, h)))
+        bgr.append(_bgr(dev, ym.yuv_to_bgr(planes, fmt, ym.BT601_FULL, 0, 0, w, h)))
     return frames, bgr
 
 
 @pytest.mark.parametrize("conf", [0.3, 0.01])
 def test_detect_frames_yuv_is_detect_frames_on_the_converted_frames(engine, picture_batch, conf):
-    frames, bgr = picture_batch
-    B = len(frames)
-    got = engine.detect_frames_yuv(frames, conf, 0.4, out=_out(engine, B))
-    want = engine.detect_frames(bgr, conf, 0.4, out=_out(engine, B))
-    assert torch.equal(got[2], want[2]), (got[2].tolist(), want[2].tolist())
-    assert torch.equal(got[1], want[1])
-    _same(got[0], want[0], "dets at conf %g" % conf)
-    assert int(want[2].sum()) > 0, want[2].tolist()
+    check_detect_frames(engine, *picture_batch, conf)
 
 
 def test_detect_tiled_yuv_is_detect_tiled_on_the_converted_frames(yfv2, engine, dev, images_u8):
-    """a YUYV and an I440 frame of 500 x 420; 352 x 352 tiles 75 pixels apart, so a column of tiles starts at x = 75 and a row at
-    y = 68: odd origins read in place, in the middle of a macropixel"""
-    tiles = [t for f in range(2) for t in yfv2.plan_tiles(420, 500, tile=(352, 352), overlap=(277, 277), frame=f)]
-    assert len(tiles) <= engine.max_batch and any(t[1] % 2 == 1 for t in tiles) and any(t[1] % 2 == 0 and t[1] > 0 for t in tiles)
+    """a YUYV and an I440 frame: the odd origins lie in the middle of a macropixel"""
     frames, bgr = [], []
-    for f, fmt in enumerate((ma.YUYV, ma.I440)):
-        planes = ma.from_i444(ma.bgr_to_i444(_picture(images_u8, 1 + f, 420, 500, 600 + f)), fmt)
+    for f, fmt in enumerate((ym.YUYV, ym.I440)):
+        planes = ym.from_i444(ym.bgr_to_i444(_picture(images_u8, 1 + f, 420, 500, 600 + f)), fmt)
         frames.append(_frame(yfv2, dev, planes, fmt, "jpeg", 0, 0, 500, 420))
-        bgr.append(_bgr(dev, ma.yuv_to_bgr(planes, fmt, ma.BT601_FULL, 0, 0, 500, 420)))
-
-    def buffers():
-        d, s, c = engine.new_tiled_buffers(2)
-        d.fill_(SENTINEL)
-        s.fill_(-7)
-        c.fill_(-9)
-        return d, s, c
-
-    got = engine.detect_tiled_yuv(frames, tiles=tiles, conf_thres=0.3, iou_thres=0.4, out=buffers())
-    want = engine.detect_tiled(bgr, tiles=tiles, conf_thres=0.3, iou_thres=0.4, out=buffers())
-    assert torch.equal(got[2], want[2]) and torch.equal(got[1], want[1]), (got[2].tolist(), want[2].tolist())
-    _same(got[0], want[0], "tiled dets")
-    assert int(want[2].sum()) > 0
+        bgr.append(_bgr(dev, ym.yuv_to_bgr(planes, fmt, ym.BT601_FULL, 0, 0, 500, 420)))
+    check_detect_tiled(yfv2, engine, frames, bgr)
 
 
 def test_pipeline_submit_frames_yuv(yfv2, dev, cfg, coco_weights, engine, picture_batch):
     frames, bgr = (x[:4] for x in picture_batch)
-    pipe = yfv2.DetectPipeline(dev, cfg["height"], cfg["width"], cfg["classes"], cfg["anchor_num"], anchors=cfg["anchors"], max_batch=4, depth=2, plan={})
-    pipe.load_state_dict(coco_weights)
-    d, i, c = (t.clone() for t in pipe.result(pipe.submit_frames_yuv(frames, 0.3, 0.4)))
-    pipe.synchronize()
-    rd, ri, rc = engine.detect_frames(bgr, 0.3, 0.4)
-    assert tuple(d.shape) == (len(frames), MAX_DET, 6) and torch.equal(c, rc) and int(c.sum()) > 0
-    for b in range(len(frames)):
-        k = int(c[b])
-        assert torch.equal(i[b, :k], ri[b, :k])
-        _same(d[b, :k], rd[b, :k], "pipeline frame %d" % b)
+    check_pipeline(yfv2, dev, cfg, coco_weights, engine, [(frames, bgr)], 4)
 
 
 # ---- 6. training batches and second-stage crops --------------------------------------------------------------------------------
@@ -312,80 +188,31 @@ def test_pipeline_submit_frames_yuv(yfv2, dev, cfg, coco_weights, engine, pictur
 def small(yfv2, dev):
     """4 small frames - YUYV at an odd origin, I440 whole, UYVY at an even origin, NV12 at an odd one - and their model conversions"""
     rng = np.random.default_rng(41)
-    frames, bgr = [], []
-    for fmt, colour, (rows, cols), rect in ((ma.YUYV, ma.BT709_LIMITED, (45, 84), (3, 1, 77, 41)), (ma.I440, ma.BT601_FULL, (64, 96), (0, 0, 96, 64)),
-                                            (ma.UYVY, ma.BT601_LIMITED, (33, 40), (2, 3, 37, 29)), (ma.NV12, ma.BT709_FULL, (40, 50), (1, 1, 49, 39))):
-        planes = ma.random_planes(rng, rows, cols, fmt)
-        frames.append(_frame(yfv2, dev, planes, fmt, colour, *rect))
-        bgr.append(_bgr(dev, ma.yuv_to_bgr(planes, fmt, colour, *rect)))
-    return frames, bgr
+    pairs = [_pair(yfv2, dev, ym.random_planes(rng, rows, cols, fmt), fmt, colour, *rect)
+             for fmt, colour, (rows, cols), rect in ((ym.YUYV, ym.BT709_LIMITED, (45, 84), (3, 1, 77, 41)), (ym.I440, ym.BT601_FULL, (64, 96), (0, 0, 96, 64)),
+                                                     (ym.UYVY, ym.BT601_LIMITED, (33, 40), (2, 3, 37, 29)), (ym.NV12, ym.BT709_FULL, (40, 50), (1, 1, 49, 39)))]
+    return [f for f, _ in pairs], [b for _, b in pairs]
 
 
 def test_train_batch_frames_yuv(yfv2, dev, small):
-    frames, bgr = small
-    eng = yfv2.Engine(dev, 64, 96, max_batch=4, plan={})
-    alpha, beta = [1.0, 0.5, 1.75, 0.25], [0.0, 0.25, -7.25, 31.5]
-    for a, b in ((alpha, beta), (None, None)):
-        got = eng.train_batch_frames_yuv(frames, a, b)
-        assert got.dtype == torch.float32 and tuple(got.shape) == (4, 3, 64, 96)
-        _same(got, eng.train_batch_frames(bgr, a, b), "training batch")
-    from yolo_fastestv2_amd import datasets
-    labels = [np.zeros((0, 6), np.float32)] * 4
-    imgs, _ = datasets.TrainBatcher(eng)(frames, labels)
-    _same(imgs, eng.train_batch_frames(bgr), "TrainBatcher")
+    check_train_batch(yfv2, dev, *small, [1.0, 0.5, 1.75, 0.25], [0.0, 0.25, -7.25, 31.5])
 
 
-def _hand_rows(frames):
-    """hand-made rows: with pad 0.25 a box 8 wide from x1 starts its rectangle at x1 - 2 - odd and even origins on every frame, the
-    packed ones too, folded into the plane pointers ON THE DEVICE; then inside, touching the far corner, one outside (skipped), the
-    whole frame"""
-    dets = np.full((len(frames), 8, 6), -3.0, np.float32)
-    count = np.zeros(len(frames), np.int32)
-    for b, f in enumerate(frames):
-        w, h = f.width, f.height
-        rows = [(9.0, 6.0, 17.0, 14.0, 0.9, 0), (10.0, 7.0, 18.0, 15.0, 0.8, 1), (0.31 * w, 0.22 * h, 0.74 * w, 0.81 * h, 0.7, 2), (w - 9.0, h - 7.0, w + 4.0, h + 4.0, 0.6, 3),
-                (0.0, 0.0, 1.0, 1.0, 0.5, 0), (w + 5.0, 2.0, w + 9.0, 8.0, 0.4, 0), (0.0, 0.0, float(w), float(h), 0.3, 4)]
-        dets[b, :len(rows)], count[b] = rows, len(rows)
-    return dets, count
-
-
-def _check_plan(got, want, R, packed_frames):
-    total = int(want[3][-1])
-    assert total >= 20
-    for b in packed_frames:          # rectangles at odd and even x (and y) on the packed frames
-        mine = [r for r, s in zip(want[2][:total].tolist(), want[1][:total].tolist()) if s // R == b]
-        assert {r[0] & 1 for r in mine} == {0, 1} and {r[1] & 1 for r in mine} == {0, 1}, mine
-    for g, w_, name in zip(got[1:], want[1:], ("crop_src", "crop_rect", "crop_offset", "crop_skipped")):
-        n = total if name in ("crop_src", "crop_rect") else len(w_)          # (slots beyond the total are not written)
-        assert torch.equal(g[:n], w_[:n]), name
-    return total
+def _rows(w, h):
+    """with pad 0.25 a box 8 wide from x1 starts its rectangle at x1 - 2 - odd and even origins on every frame, the packed ones too,
+    folded into the plane pointers ON THE DEVICE; then inside, touching the far corner, one outside (skipped), the whole frame"""
+    return [(9.0, 6.0, 17.0, 14.0, 0.9, 0), (10.0, 7.0, 18.0, 15.0, 0.8, 1), (0.31 * w, 0.22 * h, 0.74 * w, 0.81 * h, 0.7, 2), (w - 9.0, h - 7.0, w + 4.0, h + 4.0, 0.6, 3),
+            (0.0, 0.0, 1.0, 1.0, 0.5, 0), (w + 5.0, 2.0, w + 9.0, 8.0, 0.4, 0), (0.0, 0.0, float(w), float(h), 0.3, 4)]
 
 
 def test_crop_detections_yuv(yfv2, dev, small):
-    frames, bgr = small
-    eng = yfv2.Engine(dev, 352, 352, max_batch=4, plan={})
-    dets, count = _hand_rows(frames)
-    d, c = torch.from_numpy(dets).to(dev), torch.from_numpy(count).to(dev)
-    got = eng.crop_detections_yuv(frames, d, c, (32, 32), pad=0.25)
-    want = eng.crop_detections(bgr, d, c, (32, 32), pad=0.25)
-    torch.cuda.synchronize()
-    total = _check_plan(got, want, 8, (0, 2))
-    _same(got[0][:total], want[0][:total], "crops")
+    """rectangles at odd and even x (and y) on each of the packed frames, 0 and 2"""
+    check_crop_detections(yfv2, dev, *small, _rows, 0.25, 20, [{0}, {2}])
 
 
 @pytest.mark.parametrize("dtype,letterbox", [(torch.float32, False), (torch.float16, True)], ids=["fp32", "fp16_letterboxed"])
 def test_crop_tensors_yuv(yfv2, dev, small, dtype, letterbox):
-    frames, bgr = small
-    eng = yfv2.Engine(dev, 352, 352, max_batch=4, plan={})
-    dets, count = _hand_rows(frames)
-    d, c = torch.from_numpy(dets).to(dev), torch.from_numpy(count).to(dev)
-    kw = dict(pad=0.25, mean=(0.485, 0.456, 0.406), std=(0.229, 0.224, 0.225), rgb=True, letterbox=letterbox, fill=(114, 7, 201), dtype=dtype)
-    got = eng.crop_tensors_yuv(frames, d, c, (32, 32), **kw)
-    want = eng.crop_tensors(bgr, d, c, (32, 32), **kw)
-    torch.cuda.synchronize()
-    total = _check_plan(got, want, 8, (0, 2))
-    assert got[0].dtype == dtype
-    _same(got[0][:total], want[0][:total], "tensors")
+    check_crop_tensors(yfv2, dev, *small, _rows, 0.25, 20, [{0}, {2}], dtype, letterbox)
 
 
 # ---- 7. argument errors ------------------------------------------------------------------------------------------------------------
@@ -406,11 +233,11 @@ def test_argument_errors_launch_nothing(yfv2, dev, engine, picture_batch):
     torch.cuda.synchronize()
     L, h = _lib.lib(), engine._h
     st = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    i444 = dict(y=y.data_ptr(), u=u.data_ptr(), v=u.data_ptr(), pitch_y=1280, pitch_c=640, x0=0, y0=0, width=640, height=480, format=ma.I444, colour=2)
-    i422, i440 = dict(i444, format=ma.I422, pitch_c=320), dict(i444, format=ma.I440)
-    yuyv = dict(i444, u=None, v=None, pitch_c=-5, format=ma.YUYV)
-    uyvy, grey = dict(yuyv, format=ma.UYVY), dict(yuyv, format=ma.GREY)
-    nv12 = dict(i444, v=None, format=ma.NV12)
+    i444 = dict(y=y.data_ptr(), u=u.data_ptr(), v=u.data_ptr(), pitch_y=1280, pitch_c=640, x0=0, y0=0, width=640, height=480, format=ym.I444, colour=2)
+    i422, i440 = dict(i444, format=ym.I422, pitch_c=320), dict(i444, format=ym.I440)
+    yuyv = dict(i444, u=None, v=None, pitch_c=-5, format=ym.YUYV)
+    uyvy, grey = dict(yuyv, format=ym.UYVY), dict(yuyv, format=ym.GREY)
+    nv12 = dict(i444, v=None, format=ym.NV12)
     p010 = dict(i444, y=p10.data_ptr(), u=p10.data_ptr(), v=None, pitch_c=1280, format=16, colour=0)
 
     def table(*fs):

@@ -1,63 +1,33 @@
 """CPU-only: the library's one description of the row kernels - the LDS a launch asks for and the width limit an entry point
-enforces, for every row kind and both frame kinds (include/yfv2.h yfv2_debug_rows; yfv2_pre.hip FrameRows) - against the one
+enforces, for every row kind and frame kind (include/yfv2.h yfv2_debug_rows, _rows16, _rows_any; yfv2_pre.hip FrameRows) - against the one
 restatement, tests/rows_model.py.  A launch that asked for less LDS than its kernel uses would write outside its allocation on the
 device; this sweep is what holds the host's arithmetic to the kernels' layout without a device."""
-import ctypes as C
-import os
-import re
 
 import pytest
 
 import rows_model as rm
-from conftest import REPO
+from rows_checks import _rows, check_export, check_lds_bytes_and_limit
 
 FULL = rm.LDS_FULL
 
 
-def _rows(kind, is_yuv, w, W):
-    from yolo_fastestv2_amd import _lib
-    lds, limit = C.c_int64(-1), C.c_int32(-1)
-    assert _lib.lib().yfv2_debug_rows(kind, int(is_yuv), w, W, C.byref(lds), C.byref(limit)) == _lib.OK, (kind, is_yuv, w, W)
-    return lds.value, limit.value
-
-
 def test_export_is_declared_bound_and_checks_its_arguments():
     from yolo_fastestv2_amd import _lib, yuv
-    L = _lib.lib()
-    assert L.yfv2_abi_version() == _lib.ABI_VERSION == 7                      # additive: the ABI number stays
-    res, args = _lib._PROTOTYPES["yfv2_debug_rows"]
-    assert res is C.c_int and args == [C.c_int32] * 4 + [C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
-    header = open(os.path.join(REPO, "include", "yfv2.h")).read()
-    assert re.search(r"YFV2_API int yfv2_debug_rows\(int32_t row_kind, int32_t yuv, int32_t w, int32_t W, int64_t\* lds_bytes, int32_t\* max_width\);", header)
+    check_export("yfv2_debug_rows", ("yuv",), yuv.rows_lds)
     assert (yuv.ROWS_U8, yuv.ROWS_COUNTED_U8, yuv.ROWS_TRAIN, yuv.ROWS_TENSOR_F32, yuv.ROWS_TENSOR_F16) == rm.KINDS
-    assert L.yfv2_debug_rows(0, 0, 1920, 352, None, None) == _lib.OK          # either output may be NULL
-    for bad in ((-1, 0, 8, 8), (5, 0, 8, 8), (0, 2, 8, 8), (0, -1, 8, 8), (0, 0, 0, 8), (0, 0, (1 << 26) + 1, 8), (0, 0, 8, 0), (0, 0, 8, (1 << 20) + 1)):
-        assert L.yfv2_debug_rows(*bad, None, None) == _lib.ERR_ARG, bad
-    with pytest.raises(ValueError):
-        yuv.rows_lds(9, False, 8, 8)
+    for bad in ((0, 2, 8, 8), (0, -1, 8, 8)):                                  # yuv is 0 or 1
+        assert _lib.lib().yfv2_debug_rows(*bad, None, None) == _lib.ERR_ARG, bad
 
 
 @pytest.mark.parametrize("is_yuv", [False, True], ids=["bgr", "yuv"])
-@pytest.mark.parametrize("kind", rm.KINDS, ids=["u8", "counted_u8", "train", "tensor_f32", "tensor_f16"])
+@pytest.mark.parametrize("kind", rm.KINDS, ids=rm.KIND_IDS)
 def test_lds_bytes_and_limit_equal_the_restatement(kind, is_yuv):
-    """every W % 4 == 0 up to 4096: the limit, and the bytes at the widths where a rule could break - the smallest frames, around
-    the limit, a 1080p row, around the exact maximum"""
-    for W in range(4, 4097, 4):
-        limit = _rows(kind, is_yuv, 1, W)[1]
-        assert limit == rm.max_width(kind, is_yuv, W), W
-        exact = rm.exact_max_width(kind, is_yuv, W)
-        for w in {1, 2, 3, limit - 1, limit, limit + 1, 1920, exact - 1, exact + 1, limit + 6}:
-            assert _rows(kind, is_yuv, w, W)[0] == rm.lds_bytes(kind, is_yuv, w, W), (w, W)
-        assert rm.lds_bytes(kind, is_yuv, limit, W) <= FULL, W                 # what is admitted fits ...
-        if is_yuv:
-            assert limit == exact and rm.lds_bytes(kind, True, limit + 1, W) > FULL, W       # ... and nothing wider would
-        else:
-            assert limit <= exact and rm.lds_bytes(kind, False, limit + 6, W) > FULL, W      # ... no more than a slot's rounding below
+    check_lds_bytes_and_limit(kind, rm.YUV8 if is_yuv else rm.BGR)
 
 
 def test_pinned_values():
     assert _rows(rm.U8, False, 1, 352)[1] == 27128 and _rows(rm.COUNTED_U8, False, 1, 352)[1] == 27128
-    assert rm.exact_max_width(rm.U8, False, 352) == 27129                      # yfv2_resize_u8 tests the bytes: one pixel more
+    assert rm.exact_max_width(rm.U8, rm.BGR, 352) == 27129                      # yfv2_resize_u8 tests the bytes: one pixel more
     assert _rows(rm.U8, True, 1, 352)[1] == 40689
     assert _rows(rm.TRAIN, False, 26426, 352) == (FULL, 26426)                 # the widest training row fills the LDS to the byte
     assert _rows(rm.TRAIN, True, 1, 352)[1] == 39641

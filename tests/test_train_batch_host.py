@@ -103,12 +103,12 @@ def test_lds_bytes_and_width_limits():
     full = ds.LDS_FULL
     for W in (32, 64, 96, 352, 640):
         m = ds.max_frame_width(W)
-        assert m == rm.max_width(rm.TRAIN, False, W) and ds.train_batch_lds_bytes(m, W) == rm.lds_bytes(rm.TRAIN, False, m, W)
+        assert m == rm.max_width(rm.TRAIN, rm.BGR, W) and ds.train_batch_lds_bytes(m, W) == rm.lds_bytes(rm.TRAIN, rm.BGR, m, W)
         assert ds.train_batch_lds_bytes(m, W) <= full
         assert m < (full - 3 * W) // 6 - 2                              # below resize_frames' limit: what this takes, that takes
         assert ds.train_batch_lds_bytes(m + 6, W) > full                # and no more than a slot's rounding below the true maximum
         my = ds.max_frame_width(W, True)
-        assert my == rm.max_width(rm.TRAIN, True, W) and ds.train_batch_lds_bytes(my, W, True) == rm.lds_bytes(rm.TRAIN, True, my, W)
+        assert my == rm.max_width(rm.TRAIN, rm.YUV8, W) and ds.train_batch_lds_bytes(my, W, True) == rm.lds_bytes(rm.TRAIN, rm.YUV8, my, W)
         assert ds.train_batch_lds_bytes(my, W, True) <= full < ds.train_batch_lds_bytes(my + 1, W, True)
         assert my <= yuv.max_width(W)
     assert ds.max_frame_width(352) == 26426 and ds.train_batch_lds_bytes(26426, 352) == full

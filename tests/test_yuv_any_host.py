@@ -1,10 +1,9 @@
 """CPU-only checks of the 8-bit YUV samplings beyond 4:2:0 (include/yfv2.h YFV2_YUV_I422 .. YFV2_YUV_GREY): the
-model's addressing against offsets worked out by hand, grey, the three forms of one 4:2:2 picture, the 4:2:0 formats against
-tests/yuv_model.py, the general launch's LDS and width limit (yfv2_debug_rows_any) against tests/yuv_any_model.py, yuv.frame_table
+model's addressing against offsets worked out by hand (all eleven formats of tests/yuv_model.py, from one body), grey, the three
+forms of one 4:2:2 picture, the model against bytes recorded before its three predecessors were folded, the general launch's LDS and width limit (yfv2_debug_rows_any) against tests/rows_model.py, yuv.frame_table
 on the new plane shapes and on mixed lists, and the host-side sanitizer program tests/cpp/yfv2_yuv_any_san.cpp.
 The argument checks of the C ABI need a handle, and a handle needs a device: they are in tests/test_gpu_yuv_any.py
 (test_argument_errors_launch_nothing).  The device side is that file."""
-import ctypes as C
 import os
 import re
 import subprocess
@@ -14,76 +13,79 @@ import pytest
 import torch
 
 import rows_model as rm
-import yuv_any_model as ma
 import yuv_model as ym
 from conftest import REPO
+from rows_checks import _rows, check_export, check_lds_bytes_and_limit
 
 FULL = rm.LDS_FULL
+FORMATS = ym.FORMATS8
 
 
 def _rows_any(kind, w, W):
-    from yolo_fastestv2_amd import _lib
-    lds, limit = C.c_int64(-1), C.c_int32(-1)
-    assert _lib.lib().yfv2_debug_rows_any(kind, w, W, C.byref(lds), C.byref(limit)) == _lib.OK, (kind, w, W)
-    return lds.value, limit.value
+    return _rows(kind, rm.YUV8_ANY, w, W)
 
 
 # ---- 1. the addressing -----------------------------------------------------------------------------------------------------------
 def _by_hand(fmt, R, C):
-    """(luma, U, V) byte positions of pixel (R, C) as (plane, row, byte), written out per format from include/yfv2.h's table"""
-    if fmt == ma.NV12:
+    """(luma, U, V) sample positions of pixel (R, C) as (plane, row, sample), written out per format from include/yfv2.h's table"""
+    if fmt in (ym.NV12, ym.P010):
         return (0, R, C), (1, R // 2, 2 * (C // 2)), (1, R // 2, 2 * (C // 2) + 1)
-    if fmt == ma.NV21:
+    if fmt == ym.NV21:
         return (0, R, C), (1, R // 2, 2 * (C // 2) + 1), (1, R // 2, 2 * (C // 2))
-    if fmt == ma.I420:
+    if fmt in (ym.I420, ym.I010):
         return (0, R, C), (1, R // 2, C // 2), (2, R // 2, C // 2)
-    if fmt == ma.I422:
+    if fmt == ym.I422:
         return (0, R, C), (1, R, C // 2), (2, R, C // 2)
-    if fmt == ma.I440:
+    if fmt == ym.I440:
         return (0, R, C), (1, R // 2, C), (2, R // 2, C)
-    if fmt == ma.I444:
+    if fmt == ym.I444:
         return (0, R, C), (1, R, C), (2, R, C)
-    if fmt == ma.YUYV:
+    if fmt == ym.YUYV:
         return (0, R, 2 * C), (0, R, 4 * (C // 2) + 1), (0, R, 4 * (C // 2) + 3)
-    if fmt == ma.UYVY:
+    if fmt == ym.UYVY:
         return (0, R, 2 * C + 1), (0, R, 4 * (C // 2)), (0, R, 4 * (C // 2) + 2)
     return (0, R, C), None, None
 
 
-@pytest.mark.parametrize("fmt", ma.FORMATS, ids=[ma.NAMES[f] for f in ma.FORMATS])
+@pytest.mark.parametrize("fmt", ym.FORMATS, ids=[ym.NAMES[f] for f in ym.FORMATS])
 def test_chroma_addressing_every_parity(fmt):
-    """a 5 x 4 frame at every origin parity inside 7 x 6 planes: each pixel is the conversion of the three bytes at the hand-computed
-    offsets; the planes hold distinct bytes, so a wrong offset shows"""
-    w, h = 5, 4
+    """frames at every origin parity inside 11 x 13 planes - one pixel up to the whole plane, its last pixel, ending on its last row
+    and column - each pixel is the conversion of the three samples at the hand-computed offsets; the planes hold random samples, so
+    a wrong offset shows"""
+    bits, mid = ym.TABLE[fmt].bits, 1 << (ym.TABLE[fmt].bits - 1)
     rng = np.random.default_rng(7 + fmt)
-    planes = ma.random_planes(rng, h + 2, w + 2, fmt)
-    assert [p.shape for p in planes] == {ma.NV12: [(6, 7), (3, 8)], ma.NV21: [(6, 7), (3, 8)], ma.I420: [(6, 7), (3, 4), (3, 4)], ma.I422: [(6, 7), (6, 4), (6, 4)],
-                                         ma.I440: [(6, 7), (3, 7), (3, 7)], ma.I444: [(6, 7), (6, 7), (6, 7)], ma.YUYV: [(6, 16)], ma.UYVY: [(6, 16)], ma.GREY: [(6, 7)]}[fmt]
-    for x0 in (0, 1):
-        for y0 in (0, 1):
-            got = ma.yuv_to_bgr(planes, fmt, ma.BT601_FULL, x0, y0, w, h)
-            assert got.shape == (h, w, 3) and got.dtype == np.uint8
-            for r in range(h):
-                for c in range(w):
-                    ly, lu, lv = _by_hand(fmt, y0 + r, x0 + c)
-                    u, v = (128, 128) if lu is None else (planes[lu[0]][lu[1], lu[2]], planes[lv[0]][lv[1], lv[2]])
-                    assert got[r, c].tolist() == ym.convert(planes[ly[0]][ly[1], ly[2]], u, v, ma.BT601_FULL).tolist(), (x0, y0, r, c)
+    assert ym.plane_shapes(6, 7, fmt) == {ym.NV12: [(6, 7), (3, 8)], ym.NV21: [(6, 7), (3, 8)], ym.I420: [(6, 7), (3, 4), (3, 4)], ym.I422: [(6, 7), (6, 4), (6, 4)],
+                                          ym.I440: [(6, 7), (3, 7), (3, 7)], ym.I444: [(6, 7), (6, 7), (6, 7)], ym.YUYV: [(6, 16)], ym.UYVY: [(6, 16)], ym.GREY: [(6, 7)],
+                                          ym.P010: [(6, 7), (3, 8)], ym.I010: [(6, 7), (3, 4), (3, 4)]}[fmt]
+    planes = ym.random_planes(rng, 11, 13, fmt)
+    assert [p.shape for p in planes] == ym.plane_shapes(11, 13, fmt) and all(p.dtype == (np.uint8 if bits == 8 else np.uint16) for p in planes)
+    val = [ym.sample_values(p, fmt) for p in planes] if bits == 10 else planes
+    cases = [(x0, y0, w, h) for x0 in (0, 1, 2, 3) for y0 in (0, 1, 2) for w, h in ((1, 1), (2, 2), (3, 5), (4, 3), (5, 4), (7, 6))]
+    cases += [(0, 0, 13, 11), (12, 10, 1, 1), (5, 4, 8, 7), (6, 5, 7, 6)]          # the whole plane; its last pixel; ending on the last row and column
+    for x0, y0, w, h in cases:
+        got = ym.yuv_to_bgr(planes, fmt, ym.BT601_FULL, x0, y0, w, h)
+        assert got.shape == (h, w, 3) and got.dtype == np.uint8
+        for r in range(h):
+            for c in range(w):
+                ly, lu, lv = _by_hand(fmt, y0 + r, x0 + c)
+                u, v = (mid, mid) if lu is None else (val[lu[0]][lu[1], lu[2]], val[lv[0]][lv[1], lv[2]])
+                assert got[r, c].tolist() == ym.convert(val[ly[0]][ly[1], ly[2]], u, v, ym.BT601_FULL, bits).tolist(), (x0, y0, r, c)
     # two offsets by hand, numbers only: pixel (3, 3) of a YUYV row is luma byte 6, U byte 5, V byte 7; of a UYVY row 7, 4, 6
-    assert ma.offsets(ma.YUYV, 3, 3) == ((0, 3, 6), (0, 3, 5), (0, 3, 7)) and ma.offsets(ma.UYVY, 3, 3) == ((0, 3, 7), (0, 3, 4), (0, 3, 6))
-    assert ma.offsets(ma.I440, 3, 3) == ((0, 3, 3), (1, 1, 3), (2, 1, 3)) and ma.offsets(ma.I422, 3, 3) == ((0, 3, 3), (1, 3, 1), (2, 3, 1))
+    assert ym.offsets(ym.YUYV, 3, 3) == ((0, 3, 6), (0, 3, 5), (0, 3, 7)) and ym.offsets(ym.UYVY, 3, 3) == ((0, 3, 7), (0, 3, 4), (0, 3, 6))
+    assert ym.offsets(ym.I440, 3, 3) == ((0, 3, 3), (1, 1, 3), (2, 1, 3)) and ym.offsets(ym.I422, 3, 3) == ((0, 3, 3), (1, 3, 1), (2, 3, 1))
 
 
 def test_grey_is_i444_with_neutral_chroma_and_full_range_grey_is_identity():
     rng = np.random.default_rng(11)
     y = rng.integers(0, 256, (9, 13), dtype=np.uint8)
     neutral = np.full_like(y, 128)
-    for colour in ma.COLOURS:
+    for colour in ym.COLOURS:
         for x0, y0, w, h in ((0, 0, 13, 9), (1, 2, 11, 6), (12, 8, 1, 1)):
-            assert np.array_equal(ma.yuv_to_bgr((y,), ma.GREY, colour, x0, y0, w, h), ma.yuv_to_bgr((y, neutral, neutral), ma.I444, colour, x0, y0, w, h))
+            assert np.array_equal(ym.yuv_to_bgr((y,), ym.GREY, colour, x0, y0, w, h), ym.yuv_to_bgr((y, neutral, neutral), ym.I444, colour, x0, y0, w, h))
     ramp = np.arange(256, dtype=np.uint8)[None, :]
-    got = ma.yuv_to_bgr((ramp,), ma.GREY, ma.BT601_FULL, 0, 0, 256, 1)
+    got = ym.yuv_to_bgr((ramp,), ym.GREY, ym.BT601_FULL, 0, 0, 256, 1)
     assert np.array_equal(got, np.repeat(ramp[0][:, None], 3, axis=1)[None])             # B = G = R = Y for all 256 values
-    assert np.array_equal(ma.yuv_to_bgr((ramp,), ma.GREY, ma.BT709_FULL, 0, 0, 256, 1), got)
+    assert np.array_equal(ym.yuv_to_bgr((ramp,), ym.GREY, ym.BT709_FULL, 0, 0, 256, 1), got)
 
 
 def test_one_picture_in_three_422_forms_and_the_other_subsamplings():
@@ -91,66 +93,51 @@ def test_one_picture_in_three_422_forms_and_the_other_subsamplings():
     the I444 picture at the pixels whose own chroma sample was taken (even column / row on the subsampled axes)"""
     rng = np.random.default_rng(13)
     for rows, cols in ((8, 10), (7, 9)):
-        src = ma.random_planes(rng, rows, cols, ma.I444)
-        full = ma.yuv_to_bgr(src, ma.I444, ma.BT601_FULL, 0, 0, cols, rows)
-        want = ma.yuv_to_bgr(ma.from_i444(src, ma.I422), ma.I422, ma.BT601_FULL, 0, 0, cols, rows)
-        for fmt in (ma.YUYV, ma.UYVY):
+        src = ym.random_planes(rng, rows, cols, ym.I444)
+        full = ym.yuv_to_bgr(src, ym.I444, ym.BT601_FULL, 0, 0, cols, rows)
+        want = ym.yuv_to_bgr(ym.from_i444(src, ym.I422), ym.I422, ym.BT601_FULL, 0, 0, cols, rows)
+        for fmt in (ym.YUYV, ym.UYVY):
             for x0, y0, w, h in ((0, 0, cols, rows), (1, 1, cols - 1, rows - 1), (3, 2, 4, 3)):
-                got = ma.yuv_to_bgr(ma.from_i444(src, fmt), fmt, ma.BT601_FULL, x0, y0, w, h)
+                got = ym.yuv_to_bgr(ym.from_i444(src, fmt), fmt, ym.BT601_FULL, x0, y0, w, h)
                 assert np.array_equal(got, want[y0:y0 + h, x0:x0 + w]), (fmt, x0, y0)
-        for fmt in ma.FORMATS:
-            if fmt == ma.GREY:
+        for fmt in FORMATS:
+            if fmt == ym.GREY:
                 continue
-            sx, sy = ma.SHIFTS[fmt]
-            got = ma.yuv_to_bgr(ma.from_i444(src, fmt), fmt, ma.BT601_FULL, 0, 0, cols, rows)
+            sx, sy = ym.SHIFTS[fmt]
+            got = ym.yuv_to_bgr(ym.from_i444(src, fmt), fmt, ym.BT601_FULL, 0, 0, cols, rows)
             assert np.array_equal(got[::1 << sy, ::1 << sx], full[::1 << sy, ::1 << sx]), fmt
-            assert (fmt == ma.I444) == np.array_equal(got, full)
-        assert np.array_equal(ma.from_i444(src, ma.GREY)[0], src[0])
+            assert (fmt == ym.I444) == np.array_equal(got, full)
+        assert np.array_equal(ym.from_i444(src, ym.GREY)[0], src[0])
 
 
-@pytest.mark.parametrize("fmt", (ma.NV12, ma.NV21, ma.I420), ids=["nv12", "nv21", "i420"])
-def test_the_420_formats_are_the_shipped_model(fmt):
-    rng = np.random.default_rng(17 + fmt)
-    planes = ym.random_planes(rng, 11, 13, fmt)
-    for colour in ma.COLOURS:
-        for x0, y0, w, h in ((0, 0, 13, 11), (1, 0, 12, 11), (0, 1, 13, 10), (3, 5, 7, 4), (12, 10, 1, 1)):
-            assert np.array_equal(ma.yuv_to_bgr(planes, fmt, colour, x0, y0, w, h), ym.yuv_to_bgr(planes, fmt, colour, x0, y0, w, h))
-    assert [p.shape for p in ma.random_planes(rng, 11, 13, fmt)] == [p.shape for p in planes]
+@pytest.mark.parametrize("fmt", ym.FORMATS, ids=[ym.NAMES[f] for f in ym.FORMATS])
+def test_the_model_reproduces_the_recorded_bytes(fmt):
+    """tests/golden/yuv_model_bgr.npz: yuv_to_bgr of one seeded 9 x 7 picture per format, the 5 x 5 frame at the odd origin (3, 1),
+    under each colour - recorded with the three per-family models this file replaced (the 4:2:0 formats: two of them agreed).
+    The one model returns those bytes."""
+    gold = np.load(os.path.join(REPO, "tests", "golden", "yuv_model_bgr.npz"))
+    x0, y0, w, h = (int(v) for v in gold["rect"])
+    assert (x0, y0, w, h) == (3, 1, 5, 5)
+    planes = tuple(gold["f%d_plane%d" % (fmt, k)] for k in range(ym.TABLE[fmt].planes))
+    assert [p.shape for p in planes] == ym.plane_shapes(7, 9, fmt)
+    for colour in ym.COLOURS:
+        got = ym.yuv_to_bgr(planes, fmt, colour, x0, y0, w, h)
+        assert got.dtype == np.uint8 and np.array_equal(got, gold["f%d_c%d" % (fmt, colour)]), (fmt, colour)
 
 
 # ---- 2. the general launch's LDS and width limit --------------------------------------------------------------------------------
 def test_export_is_declared_bound_and_checks_its_arguments():
-    from yolo_fastestv2_amd import _lib, yuv
-    L = _lib.lib()
-    assert L.yfv2_abi_version() == _lib.ABI_VERSION == 7                      # additive: the ABI number stays
-    res, args = _lib._PROTOTYPES["yfv2_debug_rows_any"]
-    assert res is C.c_int and args == [C.c_int32] * 3 + [C.POINTER(C.c_int64), C.POINTER(C.c_int32)]
+    from yolo_fastestv2_amd import yuv
+    check_export("yfv2_debug_rows_any", (), yuv.rows_lds_any)
     header = open(os.path.join(REPO, "include", "yfv2.h")).read()
-    assert re.search(r"YFV2_API int yfv2_debug_rows_any\(int32_t row_kind, int32_t w, int32_t W, int64_t\* lds_bytes, int32_t\* max_width\);", header)
     assert re.search(r"YFV2_YUV_I422 = 3, YFV2_YUV_I440 = 4, YFV2_YUV_I444 = 5, YFV2_YUV_YUYV = 6, YFV2_YUV_UYVY = 7, YFV2_YUV_GREY = 8", header)
-    assert L.yfv2_debug_rows_any(0, 1920, 352, None, None) == _lib.OK         # either output may be NULL
-    for bad in ((-1, 8, 8), (5, 8, 8), (0, 0, 8), (0, (1 << 26) + 1, 8), (0, 8, 0), (0, 8, (1 << 20) + 1)):
-        assert L.yfv2_debug_rows_any(*bad, None, None) == _lib.ERR_ARG, bad
-    with pytest.raises(ValueError):
-        yuv.rows_lds_any(9, 8, 8)
     with pytest.raises(ValueError):
         yuv.max_width(352, bits=10, general=True)
 
 
-@pytest.mark.parametrize("kind", rm.KINDS, ids=["u8", "counted_u8", "train", "tensor_f32", "tensor_f16"])
+@pytest.mark.parametrize("kind", rm.KINDS, ids=rm.KIND_IDS)
 def test_lds_bytes_and_limit_equal_the_model(kind):
-    """w in 1..4100 and at the limit +- 2, W in {32, 352, 4096}: bytes and limit are the model's; the limit is exact; the general
-    kind never admits a frame the 4:2:0 kind refuses at the same W"""
-    for W in (32, 352, 4096):
-        limit = _rows_any(kind, 1, W)[1]
-        assert limit == ma.max_width(kind, W), W
-        for w in list(range(1, 4101)) + [limit + d for d in (-2, -1, 0, 1, 2)]:
-            assert _rows_any(kind, w, W) == (ma.lds_bytes(kind, w, W), limit), (w, W)
-        assert ma.lds_bytes(kind, limit, W) <= FULL < ma.lds_bytes(kind, limit + 1, W), W
-        assert _rows_any(kind, limit, W)[0] <= FULL < _rows_any(kind, limit + 1, W)[0], W
-        assert limit <= rm.max_width(kind, True, W), W
-        for w in (1, 2, 3, 640, 1920, limit):
-            assert ma.lds_bytes(kind, w, W) >= rm.lds_bytes(kind, True, w, W), (w, W)
+    check_lds_bytes_and_limit(kind, rm.YUV8_ANY)
 
 
 def test_layout_holds_a_packed_row_and_a_full_width_chroma_row():
@@ -170,7 +157,7 @@ def test_layout_holds_a_packed_row_and_a_full_width_chroma_row():
 def test_pinned_values_and_package_functions():
     from yolo_fastestv2_amd import datasets as ds, yuv
     general = yuv.max_width(352, general=True)
-    assert general == _rows_any(rm.U8, 1, 352)[1] == ma.max_width(rm.U8, 352) == 27125 < yuv.max_width(352) == 40689
+    assert general == _rows_any(rm.U8, 1, 352)[1] == rm.max_width(rm.U8, rm.YUV8_ANY, 352) == 27125 < yuv.max_width(352) == 40689
     assert _rows_any(rm.U8, 1920, 352)[0] == 6 * 1924 + 1056 == 12600 and FULL // 12600 == 13      # workgroups of a 1080p batch per CU by LDS
     assert ds.max_frame_width(352, True, general=True) == _rows_any(rm.TRAIN, 1, 352)[1] == 26429
     for W in (32, 64, 352, 640):
@@ -196,39 +183,39 @@ def test_frame_table_takes_the_new_formats():
                         ("uyvy", 7), ("uyvy422", 7), ("grey", 8), ("gray", 8), ("y800", 8)):
         assert yuv.FORMATS[name] == yuv.FORMATS[value] == value
     # planar: three planes, one chroma pitch, default size from the luma plane
-    for fmt in (ma.I422, ma.I440, ma.I444):
-        y, u, v = (_t(p) for p in ma.random_planes(rng, 9, 13, fmt))
-        a = yuv.frame_table([yuv.YuvFrame((y, u, v), ma.NAMES[fmt], "jpeg")], cpu)[0][0]
+    for fmt in (ym.I422, ym.I440, ym.I444):
+        y, u, v = (_t(p) for p in ym.random_planes(rng, 9, 13, fmt))
+        a = yuv.frame_table([yuv.YuvFrame((y, u, v), ym.NAMES[fmt], "jpeg")], cpu)[0][0]
         assert (a.format, a.colour, a.width, a.height, a.pitch_y, a.pitch_c) == (fmt, 2, 13, 9, 13, u.shape[1])
         assert (a.y, a.u, a.v) == (y.data_ptr(), u.data_ptr(), v.data_ptr())
-        for bad in (yuv.YuvFrame((y, u), ma.NAMES[fmt]), yuv.YuvFrame((y, u, v[:, :-1]), ma.NAMES[fmt]), yuv.YuvFrame((y, u[:-1], v), ma.NAMES[fmt]),
-                    yuv.YuvFrame((y[:, :-1], u, v), ma.NAMES[fmt], width=13)):
+        for bad in (yuv.YuvFrame((y, u), ym.NAMES[fmt]), yuv.YuvFrame((y, u, v[:, :-1]), ym.NAMES[fmt]), yuv.YuvFrame((y, u[:-1], v), ym.NAMES[fmt]),
+                    yuv.YuvFrame((y[:, :-1], u, v), ym.NAMES[fmt], width=13)):
             with pytest.raises(ValueError, match="frame 0"):
                 yuv.frame_table([bad], cpu)
     # packed: ONE plane, 2-D bytes or (rows, pixels, 2); width = bytes // 2 - x0 or pixels - x0
-    for fmt in (ma.YUYV, ma.UYVY):
-        p = _t(ma.random_planes(rng, 9, 14, fmt)[0])
+    for fmt in (ym.YUYV, ym.UYVY):
+        p = _t(ym.random_planes(rng, 9, 14, fmt)[0])
         assert tuple(p.shape) == (9, 28)
         for planes in ((p,), p, (p.view(9, 14, 2),)):
-            f = yuv.YuvFrame(planes, ma.NAMES[fmt], "bt709")
+            f = yuv.YuvFrame(planes, ym.NAMES[fmt], "bt709")
             a = yuv.frame_table([f], cpu)[0][0]
             assert (f.width, f.height) == (14, 9) and (a.format, a.width, a.height, a.pitch_y, a.y) == (fmt, 14, 9, 28, p.data_ptr()) and not a.u and not a.v
-        f = yuv.YuvFrame(p.view(9, 14, 2), ma.NAMES[fmt], x0=3, y0=2)
-        assert (f.width, f.height) == (11, 7) and yuv.YuvFrame(p, ma.NAMES[fmt], x0=3, y0=2).width == 11
-        c = yuv.YuvFrame(p, ma.NAMES[fmt]).crop(3, 1, 5, 4)          # an odd origin: the middle of a macropixel
+        f = yuv.YuvFrame(p.view(9, 14, 2), ym.NAMES[fmt], x0=3, y0=2)
+        assert (f.width, f.height) == (11, 7) and yuv.YuvFrame(p, ym.NAMES[fmt], x0=3, y0=2).width == 11
+        c = yuv.YuvFrame(p, ym.NAMES[fmt]).crop(3, 1, 5, 4)          # an odd origin: the middle of a macropixel
         a = yuv.frame_table([c], cpu)[0][0]
         assert (a.x0, a.y0, a.width, a.height) == (3, 1, 5, 4)
         # an odd last pixel reads its whole macropixel: 13 pixels need 28 bytes, and a plane one byte short of that is refused
-        odd = yuv.YuvFrame(p, ma.NAMES[fmt], width=13)
+        odd = yuv.YuvFrame(p, ym.NAMES[fmt], width=13)
         assert yuv.frame_table([odd], cpu)[0][0].width == 13
         with pytest.raises(ValueError, match=r"frame 1: plane packed"):
-            yuv.frame_table([odd, yuv.YuvFrame(p[:, :27], ma.NAMES[fmt], width=13)], cpu)
+            yuv.frame_table([odd, yuv.YuvFrame(p[:, :27], ym.NAMES[fmt], width=13)], cpu)
         with pytest.raises(ValueError, match="frame 0"):
-            yuv.frame_table([yuv.YuvFrame(p[:8], ma.NAMES[fmt], height=9)], cpu)
+            yuv.frame_table([yuv.YuvFrame(p[:8], ym.NAMES[fmt], height=9)], cpu)
         with pytest.raises(ValueError, match="1 plane"):
-            yuv.frame_table([yuv.YuvFrame((p, p), ma.NAMES[fmt])], cpu)
+            yuv.frame_table([yuv.YuvFrame((p, p), ym.NAMES[fmt])], cpu)
     # grey: one plane
-    g = _t(ma.random_planes(rng, 9, 13, ma.GREY)[0])
+    g = _t(ym.random_planes(rng, 9, 13, ym.GREY)[0])
     a = yuv.frame_table([yuv.YuvFrame(g, "gray", "jpeg", x0=1)], cpu)[0][0]
     assert (a.format, a.width, a.height, a.pitch_y, a.y, a.x0) == (8, 12, 9, 13, g.data_ptr(), 1) and not a.u
     with pytest.raises(ValueError, match=r"frame 0: plane y"):
@@ -241,8 +228,8 @@ def test_frame_table_takes_mixed_8_bit_lists_and_refuses_10_bit_among_them():
     from yolo_fastestv2_amd import yuv
     cpu = torch.device("cpu")
     rng = np.random.default_rng(37)
-    mk = lambda fmt, rows, cols: yuv.YuvFrame(tuple(_t(p) for p in ma.random_planes(rng, rows, cols, fmt)), ma.NAMES[fmt], "jpeg")
-    frames = [mk(ma.NV12, 10, 14), mk(ma.I444, 9, 13), mk(ma.YUYV, 7, 6), mk(ma.GREY, 3, 4)]
+    mk = lambda fmt, rows, cols: yuv.YuvFrame(tuple(_t(p) for p in ym.random_planes(rng, rows, cols, fmt)), ym.NAMES[fmt], "jpeg")
+    frames = [mk(ym.NV12, 10, 14), mk(ym.I444, 9, 13), mk(ym.YUYV, 7, 6), mk(ym.GREY, 3, 4)]
     arr, out = yuv.frame_table(frames, cpu)
     assert [a.format for a in arr] == [0, 5, 6, 8] and [(a.width, a.height) for a in arr] == [(14, 10), (13, 9), (6, 7), (4, 3)] and len(out) == 4
     p010 = yuv.YuvFrame((torch.zeros((4, 6), dtype=torch.int16), torch.zeros((2, 6), dtype=torch.int16)), "p010")

@@ -8,6 +8,8 @@ import rows_model as rm
 import yuv_model as ym
 from frames_ref import stage_row
 
+FORMATS = ym.FORMATS420
+
 
 # ---- 1. the colour rule ------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("colour", ym.COLOURS)
@@ -53,26 +55,11 @@ def test_accumulators_fit_int32_over_all_triples(colour):
         worst = max(worst, int(np.abs(a).max()))
     assert worst < 2 ** 31 - 1, worst
     assert 5.0e8 < worst < 6.0e8, worst      # the largest |accumulator| is about 5.7e8 for each standard
-    off, cy = ym.COEF[colour][:2]
+    off, cy = ym.COEF[8][colour][:2]
     assert (255 - off) * cy + (1 << 19) < 2 ** 31
 
 
 # ---- 2. chroma indexing --------------------------------------------------------------------------------------------------------
-def _slow(planes, fmt, colour, x0, y0, w, h):
-    out = np.zeros((h, w, 3), np.uint8)
-    for r in range(h):
-        for c in range(w):
-            R, C = y0 + r, x0 + c
-            if fmt == ym.I420:
-                u, v = planes[1][R // 2, C // 2], planes[2][R // 2, C // 2]
-            else:
-                u, v = planes[1][R // 2, 2 * (C // 2)], planes[1][R // 2, 2 * (C // 2) + 1]
-                if fmt == ym.NV21:
-                    u, v = v, u
-            out[r, c] = ym.convert(planes[0][R, C], u, v, colour)
-    return out
-
-
 def _folded(planes, fmt, colour, x0, y0, w, h):
     """the kernel's view (ResizeFrameYuv): the origin folded into the plane pointers, the parities kept - pixel (r, c) reads luma
     y[r, c] and chroma row (r + py) >> 1, sample (c + px) >> 1 from the folded bases"""
@@ -95,16 +82,16 @@ def _folded(planes, fmt, colour, x0, y0, w, h):
     return ym.convert(y[r, c], U, V, colour)
 
 
-@pytest.mark.parametrize("fmt", ym.FORMATS)
+@pytest.mark.parametrize("fmt", FORMATS)
 def test_chroma_indexing_every_parity(fmt):
+    """the kernel's folded view reads what the model reads (the model against offsets by hand, every format:
+    tests/test_yuv_any_host.py test_chroma_addressing_every_parity)"""
     rng = np.random.default_rng(5 + fmt)
     planes = ym.random_planes(rng, 11, 13, fmt)
     cases = [(x0, y0, w, h) for x0 in (0, 1, 2, 3) for y0 in (0, 1, 2) for w, h in ((1, 1), (2, 2), (3, 5), (4, 3), (7, 6))]
     cases += [(0, 0, 13, 11), (12, 10, 1, 1), (5, 4, 8, 7), (6, 5, 7, 6)]          # the whole plane; its last pixel; ending on the last row and column
     for x0, y0, w, h in cases:
-        want = _slow(planes, fmt, ym.BT709_LIMITED, x0, y0, w, h)
-        assert np.array_equal(ym.yuv_to_bgr(planes, fmt, ym.BT709_LIMITED, x0, y0, w, h), want), (x0, y0, w, h)
-        assert np.array_equal(_folded(planes, fmt, ym.BT709_LIMITED, x0, y0, w, h), want), (x0, y0, w, h)
+        assert np.array_equal(_folded(planes, fmt, ym.BT709_LIMITED, x0, y0, w, h), ym.yuv_to_bgr(planes, fmt, ym.BT709_LIMITED, x0, y0, w, h)), (x0, y0, w, h)
     # 2 x 2 blocks share their chroma: an even-origin 2 x 2 frame with constant luma is one colour, an odd-origin one is four
     flat = (np.full_like(planes[0], 128),) + planes[1:]
     assert len(np.unique(ym.yuv_to_bgr(flat, fmt, 0, 2, 2, 2, 2).reshape(-1, 3), axis=0)) == 1
@@ -164,15 +151,15 @@ def test_lds_bytes_and_width_limit_against_the_restatement():
     from yolo_fastestv2_amd import yuv
     for W in (352, 64, 96, 640):
         for w in list(range(1, 70)) + [351, 352, 353, 1279, 1280, 1919, 1920, 1921, 3840, 27128, 40000]:
-            assert yuv.resize_lds_bytes(w, W) == rm.lds_bytes(rm.U8, True, w, W), (w, W)
+            assert yuv.resize_lds_bytes(w, W) == rm.lds_bytes(rm.U8, rm.YUV8, w, W), (w, W)
             if w > 1:
                 assert yuv.resize_lds_bytes(w, W) >= yuv.resize_lds_bytes(w - 1, W)
         m = yuv.max_width(W)
-        assert m == rm.max_width(rm.U8, True, W)
-        assert rm.lds_bytes(rm.U8, True, m, W) <= rm.LDS_FULL < rm.lds_bytes(rm.U8, True, m + 1, W)
+        assert m == rm.max_width(rm.U8, rm.YUV8, W)
+        assert rm.lds_bytes(rm.U8, rm.YUV8, m, W) <= rm.LDS_FULL < rm.lds_bytes(rm.U8, rm.YUV8, m + 1, W)
     assert yuv.max_width(352) == 40689
     assert yuv.resize_lds_bytes(1920, 352) == 8760                      # 18 workgroups of a 1080p batch per CU by LDS
-    assert rm.lds_bytes(rm.U8, False, 1920, 352) == 12584               # ... where the B, G, R kernel's rows take 12 584 bytes
+    assert rm.lds_bytes(rm.U8, rm.BGR, 1920, 352) == 12584               # ... where the B, G, R kernel's rows take 12 584 bytes
     # what the slots must hold, for every width and misalignment: a luma row, an interleaved row in two half-slots, a planar row in one
     for w in range(1, 200):
         half = rm.slot((w >> 1) + 1, 4)

@@ -30,6 +30,15 @@ struct DryRun {
   }
 };
 
+// The body of the three yfv2_debug_rows* exports: `who` is the entry point's name, for the message.
+int debug_rows(const char* who, int32_t row_kind, Yfv2FrameKind frames, int32_t w, int32_t W, int64_t* lds_bytes, int32_t* max_width) {
+  if (row_kind < 0 || row_kind >= YFV2_ROW_KINDS || w < 1 || w > (1 << 26) || W < 1 || W > (1 << 20))
+    return fail(nullptr, YFV2_ERR_ARG, std::string(who) + ": bad argument");
+  if (lds_bytes) *lds_bytes = (int64_t)yfv2_rows_lds_bytes((Yfv2RowKind)row_kind, frames, w, W);
+  if (max_width) *max_width = yfv2_rows_max_width((Yfv2RowKind)row_kind, frames, W);
+  return YFV2_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -96,33 +105,21 @@ int yfv2_debug_plan_c2_label(const yfv2_config* cfg, const yfv2_tensor_desc* ten
   return d.ctx.plan.c2_permuted ? 1 : 0;
 }
 
-// Host-only test hook: the one description of the row kernels (yfv2_pre.hip) as the launches and the entry points' checks read it,
-// so that the CPU suite can hold it against a restatement (tests/rows_model.py) for every kind.
+// Host-only test hooks: the one description of the row kernels (yfv2_pre.hip) as the launches and the entry points' checks read it,
+// so that the CPU suite can hold it against a restatement (tests/rows_model.py) for every row kind and frame kind.
 int yfv2_debug_rows(int32_t row_kind, int32_t yuv, int32_t w, int32_t W, int64_t* lds_bytes, int32_t* max_width) {
-  if (row_kind < 0 || row_kind >= YFV2_ROW_KINDS || yuv < 0 || yuv > 1 || w < 1 || w > (1 << 26) || W < 1 || W > (1 << 20))
-    return fail(nullptr, YFV2_ERR_ARG, "yfv2_debug_rows: bad argument");
-  const Yfv2FrameKind frames = yuv ? YFV2_FRAMES_YUV8 : YFV2_FRAMES_BGR;
-  if (lds_bytes) *lds_bytes = (int64_t)yfv2_rows_lds_bytes((Yfv2RowKind)row_kind, frames, w, W);
-  if (max_width) *max_width = yfv2_rows_max_width((Yfv2RowKind)row_kind, frames, W);
-  return YFV2_OK;
+  if (yuv < 0 || yuv > 1) return fail(nullptr, YFV2_ERR_ARG, "yfv2_debug_rows: bad argument");
+  return debug_rows("yfv2_debug_rows", row_kind, yuv ? YFV2_FRAMES_YUV8 : YFV2_FRAMES_BGR, w, W, lds_bytes, max_width);
 }
 
-// ... and of the YUV frame kind with two-byte samples (YFV2_YUV_P010 / _I010; tests/yuv16_model.py): the same checks
+// ... of the YUV frame kind with two-byte samples (YFV2_YUV_P010 / _I010)
 int yfv2_debug_rows16(int32_t row_kind, int32_t w, int32_t W, int64_t* lds_bytes, int32_t* max_width) {
-  if (row_kind < 0 || row_kind >= YFV2_ROW_KINDS || w < 1 || w > (1 << 26) || W < 1 || W > (1 << 20))
-    return fail(nullptr, YFV2_ERR_ARG, "yfv2_debug_rows16: bad argument");
-  if (lds_bytes) *lds_bytes = (int64_t)yfv2_rows_lds_bytes((Yfv2RowKind)row_kind, YFV2_FRAMES_YUV16, w, W);
-  if (max_width) *max_width = yfv2_rows_max_width((Yfv2RowKind)row_kind, YFV2_FRAMES_YUV16, W);
-  return YFV2_OK;
+  return debug_rows("yfv2_debug_rows16", row_kind, YFV2_FRAMES_YUV16, w, W, lds_bytes, max_width);
 }
 
-// ... and of the general 1-byte YUV frame kind (a batch with a frame that is not 4:2:0; tests/yuv_any_model.py): the same checks
+// ... and of the general 1-byte YUV frame kind (a batch with a frame that is not 4:2:0)
 int yfv2_debug_rows_any(int32_t row_kind, int32_t w, int32_t W, int64_t* lds_bytes, int32_t* max_width) {
-  if (row_kind < 0 || row_kind >= YFV2_ROW_KINDS || w < 1 || w > (1 << 26) || W < 1 || W > (1 << 20))
-    return fail(nullptr, YFV2_ERR_ARG, "yfv2_debug_rows_any: bad argument");
-  if (lds_bytes) *lds_bytes = (int64_t)yfv2_rows_lds_bytes((Yfv2RowKind)row_kind, YFV2_FRAMES_YUV8_ANY, w, W);
-  if (max_width) *max_width = yfv2_rows_max_width((Yfv2RowKind)row_kind, YFV2_FRAMES_YUV8_ANY, W);
-  return YFV2_OK;
+  return debug_rows("yfv2_debug_rows_any", row_kind, YFV2_FRAMES_YUV8_ANY, w, W, lds_bytes, max_width);
 }
 
 // effective shader clock, measured by the shader (yfv2_probe.hip): enqueue on `stream` ...

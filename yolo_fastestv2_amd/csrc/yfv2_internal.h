@@ -9,6 +9,8 @@
 #include <atomic>
 #include <cmath>
 
+#include "../../include/yfv2.h"   // the YFV2_YUV_* format names
+
 // Every launch of the forward path goes through YFV2_LAUNCH.  Normally a plain launch; while yfv2_profile_forward runs a plan step, the
 // step's FIRST launch records its own begin and every launch its own end into the calling thread's event pair (hipExtLaunchKernel: the
 // dispatch's own timestamps - what rocprofv3 reports - instead of hipEventRecord packets in front of and behind the launch, which
@@ -378,12 +380,13 @@ struct YuvCoef { int off, cy, cvr, cvg, cug, cub; };   // one row of a colour ta
 __host__ __device__ constexpr int yfv2_yuv_sample_bytes(int format) { return (format & 16) ? 2 : 1; }
 // What a format is (include/yfv2.h YFV2_YUV_*): planar = U and V in planes of their own (I420, I422, I440, I444, I010); packed = one
 // plane of 4-byte macropixels (YUYV: Y0 U Y1 V, UYVY: U Y0 V Y1); grey = luma only; and the chroma shifts - pixel (R, C) takes the
-// chroma sample (R >> sy, C >> sx).  The five 4:2:0 formats have sx = sy = 1.
-__host__ __device__ constexpr bool yfv2_yuv_planar(int format) { return format == 2 || format == 17 || (format >= 3 && format <= 5); }
-__host__ __device__ constexpr bool yfv2_yuv_packed(int format) { return format == 6 || format == 7; }
-__host__ __device__ constexpr bool yfv2_yuv_grey(int format) { return format == 8; }
-__host__ __device__ constexpr int yfv2_yuv_shift_x(int format) { return format == 4 || format == 5 || format == 8 ? 0 : 1; }
-__host__ __device__ constexpr int yfv2_yuv_shift_y(int format) { return format == 3 || (format >= 5 && format <= 8) ? 0 : 1; }
+// chroma sample (R >> sy, C >> sx).  The five 4:2:0 formats have sx = sy = 1.  Comparisons, not a table: the kernels evaluate them on
+// a run-time format.
+__host__ __device__ constexpr bool yfv2_yuv_planar(int format) { return format == YFV2_YUV_I420 || format == YFV2_YUV_I010 || (format >= YFV2_YUV_I422 && format <= YFV2_YUV_I444); }
+__host__ __device__ constexpr bool yfv2_yuv_packed(int format) { return format == YFV2_YUV_YUYV || format == YFV2_YUV_UYVY; }
+__host__ __device__ constexpr bool yfv2_yuv_grey(int format) { return format == YFV2_YUV_GREY; }
+__host__ __device__ constexpr int yfv2_yuv_shift_x(int format) { return format == YFV2_YUV_I440 || format == YFV2_YUV_I444 || format == YFV2_YUV_GREY ? 0 : 1; }
+__host__ __device__ constexpr int yfv2_yuv_shift_y(int format) { return format == YFV2_YUV_I422 || (format >= YFV2_YUV_I444 && format <= YFV2_YUV_GREY) ? 0 : 1; }
 __host__ __device__ constexpr bool yfv2_yuv_is420(int format) { return yfv2_yuv_shift_x(format) == 1 && yfv2_yuv_shift_y(format) == 1; }
 struct ResizeFrameYuv {
   const unsigned char* y;     // luma of pixel (0, 0): plane + y0 * pitch_y + x0 (any alignment), device

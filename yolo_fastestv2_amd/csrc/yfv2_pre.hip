@@ -14,7 +14,8 @@
 // Built with -ffp-contract=off: the coefficient arithmetic must round like the separate C operations it restates.
 //
 // The ragged-batch kernels are two templates over <Frame, Row> - the descriptor (B, G, R or YUV; plain, counted, with an augmentation
-// pair, letterboxed) and where the blended row goes (uint8 batch, fp32 training batch, fp32 / fp16 tensor) - in ten instantiations, five more of the YUV template for 2-byte samples (P010, I010) and five for the general 1-byte kind (any 8-bit sampling).
+// pair, letterboxed) and where the blended row goes (uint8 batch, fp32 training batch, fp32 / fp16 tensor) - in twenty instantiations: five of the B, G, R template and fifteen of the YUV one (five each for 1-byte 4:2:0 samples, for 2-byte
+// samples - P010, I010 - and for the general 1-byte kind, any 8-bit sampling).  With resize_u8_kernel the unit has 21 kernels.
 // Each output kind is described ONCE: the Row states its ALIGN and its own LDS bytes, yfv2_slot places the staging slots for kernel and
 // host alike, FrameRows<Frame> gives the launch's LDS and the width limit of the frame kind, launch_rows<Frame, Row> is the one launch
 // body.  Other units reach the family through Yfv2RowKind, Yfv2FrameKind and yfv2_launch_rows / yfv2_rows_lds_bytes / yfv2_rows_max_width
@@ -360,23 +361,8 @@ __global__ __launch_bounds__(RF_THREADS, 6) void resize_frames_u8_kernel(const F
 //   B = clamp((yy + (1 << 19) + CUB * u) >> 20, 0, 255)               output order B, G, R: the network's channel order
 // The accumulators stay below 5.8e8 in magnitude over all 2^24 (Y, U, V) (tests/test_yuv_host.py sweeps them).  Chroma is replicated,
 // not interpolated.  OpenCV is not in this image: parity with cv2 proper is unpinned, exactly as for the resize above.
-static const YuvCoef YUV_COEF[4] = {
-    {16, 1220542, 1673527, -852492, -409993, 2116026},
-    {16, 1220945, 1879825, -558796, -223607, 2215014},
-    {0, 1048576, 1470104, -748826, -360853, 1858077},
-    {0, 1048576, 1651297, -490864, -196424, 1945738},
-};
-
-// Every factor fits 24 bits (|coefficient| < 2^23, |Y - off|, |u|, |v| <= 255) and every product int32, so the multiplies are
-// __mul24: full-rate v_mul_i32_i24 / v_mad_i32_i24 where a 32-bit integer multiply runs at a quarter of the rate - the same values.
-__device__ __forceinline__ void yfv2_yuv_to_bgr(int Y, int U, int V, const YuvCoef& k, int (&p)[3]) {
-  const int yy = __mul24(max(Y - k.off, 0), k.cy) + (1 << 19), u = U - 128, v = V - 128;
-  p[0] = min(max((yy + __mul24(k.cub, u)) >> 20, 0), 255);
-  p[1] = min(max((yy + __mul24(k.cvg, v) + __mul24(k.cug, u)) >> 20, 0), 255);
-  p[2] = min(max((yy + __mul24(k.cvr, v)) >> 20, 0), 255);
-}
-
-// THE 10-BIT COLOUR FORMULA (YFV2_YUV_P010 / _I010; include/yfv2.h states it for callers, tests/yuv16_model.py in numpy): the same
+//
+// THE 10-BIT COLOUR FORMULA (YFV2_YUV_P010 / _I010; include/yfv2.h states it for callers, tests/yuv_model.py in numpy): the same
 // expression on 10-bit codes, the 8-bit B, G, R rounded ONCE from 10-bit precision.  Every literal is rint(k * 2^20) of the real
 // coefficient per 10-bit code - limited range: luma 255 / (219 * 4), chroma 255 / (224 * 4) times 2(1-Kr), -2Kr(1-Kr)/Kg,
 // -2Kb(1-Kb)/Kg, 2(1-Kb); full range: 255 / 1023 in place of both - computed from those formulas, not OpenCV literals (cv2 has no
@@ -388,16 +374,24 @@ __device__ __forceinline__ void yfv2_yuv_to_bgr(int Y, int U, int V, const YuvCo
 //   YFV2_BT709_FULL       0    261375  411614  -122356  -48962   485008
 //   yy = max(Y - off, 0) * CY;  u = U - 512;  v = V - 512;  R, G, B as above
 // The accumulators stay within [-2.83e8, 5.77e8] over the 10-bit cube (tests/test_yuv16_host.py bounds them by the corners).
-static const YuvCoef YUV_COEF16[4] = {
-    {64, 305236, 418389, -213115, -102698, 528805},
-    {64, 305236, 469956, -139699, -55902, 553753},
-    {0, 261375, 366448, -186658, -89949, 463157},
-    {0, 261375, 411614, -122356, -48962, 485008},
+static const YuvCoef YUV_COEF[2][4] = {   // [sample bytes - 1][colour]
+    {{16, 1220542, 1673527, -852492, -409993, 2116026},
+     {16, 1220945, 1879825, -558796, -223607, 2215014},
+     {0, 1048576, 1470104, -748826, -360853, 1858077},
+     {0, 1048576, 1651297, -490864, -196424, 1945738}},
+    {{64, 305236, 418389, -213115, -102698, 528805},
+     {64, 305236, 469956, -139699, -55902, 553753},
+     {0, 261375, 366448, -186658, -89949, 463157},
+     {0, 261375, 411614, -122356, -48962, 485008}},
 };
 
-// As above: |coefficient| < 2^20, |Y - off| <= 1023, |u|, |v| <= 512, every factor below 2^24 and every product int32.
-__device__ __forceinline__ void yfv2_yuv16_to_bgr(int Y, int U, int V, const YuvCoef& k, int (&p)[3]) {
-  const int yy = __mul24(max(Y - k.off, 0), k.cy) + (1 << 19), u = U - 512, v = V - 512;
+// MID: the chroma midpoint, 128 for 8-bit samples and 512 for 10-bit ones.  Every factor fits 24 bits (8 bits: |coefficient| < 2^23,
+// |Y - off|, |u|, |v| <= 255; 10 bits: |coefficient| < 2^20, |Y - off| <= 1023, |u|, |v| <= 512) and every product int32, so the
+// multiplies are __mul24: full-rate v_mul_i32_i24 / v_mad_i32_i24 where a 32-bit integer multiply runs at a quarter of the rate - the
+// same values.
+template <int MID>
+__device__ __forceinline__ void yfv2_yuv_to_bgr(int Y, int U, int V, const YuvCoef& k, int (&p)[3]) {
+  const int yy = __mul24(max(Y - k.off, 0), k.cy) + (1 << 19), u = U - MID, v = V - MID;
   p[0] = min(max((yy + __mul24(k.cub, u)) >> 20, 0), 255);
   p[1] = min(max((yy + __mul24(k.cvg, v) + __mul24(k.cug, u)) >> 20, 0), 255);
   p[2] = min(max((yy + __mul24(k.cvr, v)) >> 20, 0), 255);
@@ -585,9 +579,9 @@ __global__ __launch_bounds__(RY_THREADS, 8) void resize_frames_yuv_kernel(const 
   }
   const int ysh = packed ? 1 : 0;                          // luma of pixel s: y[s << ysh]
   auto tap = [&](const Sample* y, const Sample* pu, const Sample* pv, int s, int j, int (&p)[3]) {
-    if constexpr (ANY) yfv2_yuv_to_bgr(y[s << ysh], pu[j], pv[j], kc, p);
-    else if constexpr (SB == 1) yfv2_yuv_to_bgr(y[s], pu[j], pv[j], kc, p);
-    else yfv2_yuv16_to_bgr(yfv2_sample10(y, s, vshift), yfv2_sample10(pu, j, vshift), yfv2_sample10(pv, j, vshift), kc, p);
+    if constexpr (ANY) yfv2_yuv_to_bgr<128>(y[s << ysh], pu[j], pv[j], kc, p);
+    else if constexpr (SB == 1) yfv2_yuv_to_bgr<128>(y[s], pu[j], pv[j], kc, p);
+    else yfv2_yuv_to_bgr<512>(yfv2_sample10(y, s, vshift), yfv2_sample10(pu, j, vshift), yfv2_sample10(pv, j, vshift), kc, p);
   };
   for (int ox = tid; ox < W; ox += RY_THREADS) {
     int ix = ox;
@@ -609,7 +603,7 @@ __global__ __launch_bounds__(RY_THREADS, 8) void resize_frames_yuv_kernel(const 
   row.end(OUT, b, oy, H, W);
 }
 
-YuvCoef yfv2_yuv_coef(int colour, int sample_bytes) { return sample_bytes == 2 ? YUV_COEF16[colour] : YUV_COEF[colour]; }
+YuvCoef yfv2_yuv_coef(int colour, int sample_bytes) { return YUV_COEF[sample_bytes - 1][colour]; }
 
 // ---- the host side of the row kernels: ONE description per frame kind, used by every launch and every limit -----------------
 // FrameRows<Frame> is what the descriptor's frame kind (B, G, R: ResizeFrame and what derives from it; YUV: ResizeFrameYuv likewise)

@@ -28,35 +28,47 @@ import torch
 
 from . import _lib
 
-FORMATS = {"nv12": 0, "nv21": 1, "i420": 2, 0: 0, 1: 1, 2: 2,
-           "i422": 3, "yuv422p": 3, "i440": 4, "yuv440p": 4, "i444": 5, "yuv444p": 5, 3: 3, 4: 4, 5: 5,
-           "yuyv": 6, "yuy2": 6, "yuyv422": 6, "uyvy": 7, "uyvy422": 7, "grey": 8, "gray": 8, "y800": 8, 6: 6, 7: 7, 8: 8,
-           "p010": 16, "i010": 17, "yuv420p10le": 17, "yuv420p10": 17, 16: 16, 17: 17}      # bit 4: two-byte samples
-PLANAR = (2, 3, 4, 5, 17)
-PACKED = (6, 7)                # one plane of 4-byte macropixels: two bytes per pixel
-GREY = 8
-SHIFTS = {3: (1, 0), 4: (0, 1), 5: (0, 0), 6: (1, 0), 7: (1, 0), 8: (0, 0)}      # format -> chroma shift (x, y); every other format (1, 1)
-FORMAT_NAMES = {0: "nv12", 1: "nv21", 2: "i420", 3: "i422", 4: "i440", 5: "i444", 6: "yuyv", 7: "uyvy", 8: "grey", 16: "p010", 17: "i010"}
+# What a format is, once: (YFV2_YUV_* code - bit 4: two-byte samples -, its name and pix_fmt aliases, bytes of a sample, planes - three: U
+# and V in planes of their own -, chroma shifts (x, y), packed: one plane of 4-byte macropixels, two bytes per pixel; grey: luma only)
+_TABLE = (
+    (0, ("nv12",), 1, 2, (1, 1), False, False),
+    (1, ("nv21",), 1, 2, (1, 1), False, False),
+    (2, ("i420",), 1, 3, (1, 1), False, False),
+    (3, ("i422", "yuv422p"), 1, 3, (1, 0), False, False),
+    (4, ("i440", "yuv440p"), 1, 3, (0, 1), False, False),
+    (5, ("i444", "yuv444p"), 1, 3, (0, 0), False, False),
+    (6, ("yuyv", "yuy2", "yuyv422"), 1, 1, (1, 0), True, False),
+    (7, ("uyvy", "uyvy422"), 1, 1, (1, 0), True, False),
+    (8, ("grey", "gray", "y800"), 1, 1, (0, 0), False, True),
+    (16, ("p010",), 2, 2, (1, 1), False, False),
+    (17, ("i010", "yuv420p10le", "yuv420p10"), 2, 3, (1, 1), False, False),
+)
+FORMATS = {key: code for code, names, *_ in _TABLE for key in names + (code,)}
+FORMAT_NAMES = {code: names[0] for code, names, *_ in _TABLE}
+_SAMPLE_BYTES = {code: sb for code, _, sb, *_ in _TABLE}
+sample_bytes = _SAMPLE_BYTES.__getitem__      # bytes of one sample of the (integer) format
+_PLANES = {code: planes for code, _, _, planes, *_ in _TABLE}
+SHIFTS = {code: shifts for code, _, _, _, shifts, *_ in _TABLE}      # format -> chroma shift (x, y)
+PLANAR = tuple(code for code, planes in _PLANES.items() if planes == 3)
+PACKED = tuple(row[0] for row in _TABLE if row[5])
+GREY, = (row[0] for row in _TABLE if row[6])
 WORD_DTYPES = tuple(getattr(torch, n) for n in ("int16", "uint16") if hasattr(torch, n))
-
-
-def sample_bytes(format):
-    """bytes of one sample of the (integer) format"""
-    return 2 if format & 16 else 1
-
-
 COLOURS = {"bt601": 0, "bt601_limited": 0, "bt709": 1, "bt709_limited": 1, "bt601_full": 2, "jpeg": 2, "bt709_full": 3, 0: 0, 1: 1, 2: 2, 3: 3}
 LDS_FULL = 160 * 1024
 ROWS_U8, ROWS_COUNTED_U8, ROWS_TRAIN, ROWS_TENSOR_F32, ROWS_TENSOR_F16 = range(5)      # yfv2_debug_rows' row_kind
 
 
+def _rows(hook, who, said, *args):      # the body of the three rows_lds*: `who(said)` is the caller, for the message
+    lds, limit = C.c_int64(), C.c_int32()
+    if getattr(_lib.lib(), hook)(*args, C.byref(lds), C.byref(limit)) != _lib.OK:
+        raise ValueError("%s(%s): %s" % (who, ", ".join("%r" % (a,) for a in said), _lib.last_error()))
+    return lds.value, limit.value
+
+
 def rows_lds(kind, is_yuv, w, W):
     """(LDS bytes of one workgroup for a frame w pixels wide, the widest frame admitted) of the frame entry points' launch of row
     kind ``kind`` at output width W, as libyfv2.so itself computes them (include/yfv2.h yfv2_debug_rows; no device needed)"""
-    lds, limit = C.c_int64(), C.c_int32()
-    if _lib.lib().yfv2_debug_rows(kind, int(bool(is_yuv)), w, W, C.byref(lds), C.byref(limit)) != _lib.OK:
-        raise ValueError("rows_lds(%r, %r, %r, %r): %s" % (kind, is_yuv, w, W, _lib.last_error()))
-    return lds.value, limit.value
+    return _rows("yfv2_debug_rows", "rows_lds", (kind, is_yuv, w, W), kind, int(bool(is_yuv)), w, W)
 
 
 def resize_lds_bytes(w, W):
@@ -67,18 +79,12 @@ def resize_lds_bytes(w, W):
 
 def rows_lds16(kind, w, W):
     """``rows_lds`` for YUV frames of two-byte samples ("p010", "i010"; include/yfv2.h yfv2_debug_rows16)"""
-    lds, limit = C.c_int64(), C.c_int32()
-    if _lib.lib().yfv2_debug_rows16(kind, w, W, C.byref(lds), C.byref(limit)) != _lib.OK:
-        raise ValueError("rows_lds16(%r, %r, %r): %s" % (kind, w, W, _lib.last_error()))
-    return lds.value, limit.value
+    return _rows("yfv2_debug_rows16", "rows_lds16", (kind, w, W), kind, w, W)
 
 
 def rows_lds_any(kind, w, W):
     """``rows_lds`` for the general one-byte launch: a call with a frame that is not 4:2:0 (include/yfv2.h yfv2_debug_rows_any)"""
-    lds, limit = C.c_int64(), C.c_int32()
-    if _lib.lib().yfv2_debug_rows_any(kind, w, W, C.byref(lds), C.byref(limit)) != _lib.OK:
-        raise ValueError("rows_lds_any(%r, %r, %r): %s" % (kind, w, W, _lib.last_error()))
-    return lds.value, limit.value
+    return _rows("yfv2_debug_rows_any", "rows_lds_any", (kind, w, W), kind, w, W)
 
 
 def max_width(W, bits=8, general=False):
@@ -141,37 +147,29 @@ def as_frame(f):
     raise ValueError("expected a YuvFrame or a tuple of plane tensors (y, uv) / (y, u, v), got %s" % type(f).__name__)
 
 
-def _plane(i, name, p, device, rows, row_bytes):
-    """checks one plane against what the frame reads of it: `rows` rows of `row_bytes` bytes from its first byte -> pitch"""
-    if not torch.is_tensor(p) or p.dtype != torch.uint8 or p.device != device:
-        raise ValueError("frame %d: plane %s must be a uint8 tensor on %s" % (i, name, device))
+# sample bytes -> (a plane's dtypes, their name, the unit of a row's length, the other shapes taken), for _plane's messages
+_PLANE_WORDS = {1: ((torch.uint8,), "a uint8 tensor", "bytes", "uv may be (rows, samples, 2), a packed plane (rows, pixels, 2)"),
+                2: (WORD_DTYPES, "an int16 / uint16 tensor (or uint8: the bytes)", "samples", "uv may be (rows, samples, 2)")}
+
+
+def _plane(i, name, p, device, rows, row_samples, sb):
+    """checks one plane against what the frame reads of it: `rows` rows of `row_samples` samples from its first one -> pitch in bytes.
+    One-byte samples: a uint8 tensor.  Two-byte samples: a 16-bit tensor (pitch = 2 * stride(0)) or a uint8 tensor of the bytes
+    (pitch = stride(0))."""
+    if sb == 2 and torch.is_tensor(p) and p.dtype == torch.uint8:
+        return _plane(i, name, p, device, rows, 2 * row_samples, 1)
+    words = _PLANE_WORDS[sb]
+    if not torch.is_tensor(p) or p.dtype not in words[0] or p.device != device:
+        raise ValueError("frame %d: plane %s must be %s on %s" % (i, name, words[1], device))
     if p.dim() == 3 and p.shape[2] == 2 and name in ("uv", "packed") and (p.shape[1] <= 1 or p.stride(1) == 2) and p.stride(2) == 1:
         have = 2 * int(p.shape[1])
     elif p.dim() == 2 and (p.shape[1] <= 1 or p.stride(1) == 1):
         have = int(p.shape[1])
     else:
-        raise ValueError("frame %d: plane %s must be 2-D with contiguous rows (uv may be (rows, samples, 2), a packed plane (rows, pixels, 2))" % (i, name))
-    if p.shape[0] < rows or have < row_bytes:
-        raise ValueError("frame %d: plane %s is %d rows x %d bytes, the frame reads %d x %d of it" % (i, name, p.shape[0], have, rows, row_bytes))
-    return int(p.stride(0)) if p.shape[0] > 1 else max(have, 1)
-
-
-def _plane16(i, name, p, device, rows, row_samples):
-    """`_plane` for two-byte samples: `rows` rows of `row_samples` samples, of a 16-bit tensor (pitch = 2 * stride(0)) or of a uint8
-    tensor of the bytes (pitch = stride(0)) -> pitch in bytes"""
-    if torch.is_tensor(p) and p.dtype == torch.uint8:
-        return _plane(i, name, p, device, rows, 2 * row_samples)
-    if not torch.is_tensor(p) or p.dtype not in WORD_DTYPES or p.device != device:
-        raise ValueError("frame %d: plane %s must be an int16 / uint16 tensor (or uint8: the bytes) on %s" % (i, name, device))
-    if p.dim() == 3 and p.shape[2] == 2 and name == "uv" and (p.shape[1] <= 1 or p.stride(1) == 2) and p.stride(2) == 1:
-        have = 2 * int(p.shape[1])
-    elif p.dim() == 2 and (p.shape[1] <= 1 or p.stride(1) == 1):
-        have = int(p.shape[1])
-    else:
-        raise ValueError("frame %d: plane %s must be 2-D with contiguous rows (uv may be (rows, samples, 2))" % (i, name))
+        raise ValueError("frame %d: plane %s must be 2-D with contiguous rows (%s)" % (i, name, words[3]))
     if p.shape[0] < rows or have < row_samples:
-        raise ValueError("frame %d: plane %s is %d rows x %d samples, the frame reads %d x %d of it" % (i, name, p.shape[0], have, rows, row_samples))
-    return 2 * (int(p.stride(0)) if p.shape[0] > 1 else max(have, 1))
+        raise ValueError("frame %d: plane %s is %d rows x %d %s, the frame reads %d x %d of it" % (i, name, p.shape[0], have, words[2], rows, row_samples))
+    return sb * (int(p.stride(0)) if p.shape[0] > 1 else max(have, 1))
 
 
 def frame_table(frames, device):
@@ -182,32 +180,31 @@ def frame_table(frames, device):
     frames = [as_frame(f) for f in frames]
     arr = (_lib.FrameYuv * len(frames))()
     sb = frames[0].sample_bytes
-    plane = _plane if sb == 1 else _plane16          # (takes a row's length in samples)
     for i, f in enumerate(frames):
         planar = f.planar
         if f.sample_bytes != sb:
             raise ValueError("frame %d: %d-byte samples in a call whose frame 0 has %d-byte samples: one sample width per call" % (i, f.sample_bytes, sb))
-        want = 3 if planar else 1 if (f.packed or f.format == GREY) else 2
+        want = _PLANES[f.format]
         if len(f.planes) != want:
             raise ValueError("frame %d: %s takes %d plane%s, got %d" % (i, FORMAT_NAMES[f.format], want, "" if want == 1 else "s", len(f.planes)))
         if f.x0 < 0 or f.y0 < 0:
             raise ValueError("frame %d: x0 and y0 must be >= 0" % i)
         a = arr[i]
         a.x0, a.y0, a.width, a.height, a.format, a.colour = f.x0, f.y0, f.width, f.height, f.format, f.colour
-        sx, sy = SHIFTS.get(f.format, (1, 1))
+        sx, sy = SHIFTS[f.format]
         if f.width >= 1 and f.height >= 1:      # (a frame without pixels is the native check's to report)
             crows, csamples = ((f.y0 + f.height - 1) >> sy) + 1, ((f.x0 + f.width - 1) >> sx) + 1
             if f.packed:                        # up to the last macropixel of the rectangle, whole
-                a.pitch_y = plane(i, "packed", f.planes[0], device, f.y0 + f.height, 4 * csamples)
+                a.pitch_y = _plane(i, "packed", f.planes[0], device, f.y0 + f.height, 4 * csamples, sb)
             else:
-                a.pitch_y = plane(i, "y", f.planes[0], device, f.y0 + f.height, f.x0 + f.width)
+                a.pitch_y = _plane(i, "y", f.planes[0], device, f.y0 + f.height, f.x0 + f.width, sb)
             if planar:
-                a.pitch_c = plane(i, "u", f.planes[1], device, crows, csamples)
-                if plane(i, "v", f.planes[2], device, crows, csamples) != a.pitch_c:
+                a.pitch_c = _plane(i, "u", f.planes[1], device, crows, csamples, sb)
+                if _plane(i, "v", f.planes[2], device, crows, csamples, sb) != a.pitch_c:
                     raise ValueError("frame %d: planes u and v must have the same row pitch" % i)
                 a.v = f.planes[2].data_ptr()
             elif want == 2:
-                a.pitch_c = plane(i, "uv", f.planes[1], device, crows, 2 * csamples)
+                a.pitch_c = _plane(i, "uv", f.planes[1], device, crows, 2 * csamples, sb)
         a.y = f.planes[0].data_ptr()
         if want > 1:
             a.u = f.planes[1].data_ptr()
